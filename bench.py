@@ -39,6 +39,32 @@ REFERENCE_SOURCE_CPU = {"seconds_per_window_forward": 20.9, "threads": 8, "host"
                         "how": "tools/time_reference_cpu.py: UViT3DPose.forward of the reference's source, Bm=1, T=8, 256x256"}
 
 
+DUMP_LIMIT = 64_000_000  # bytes on disk: all files of one --dump-outputs together, .npy headers included
+
+
+def dump_outputs(path: str, arrays: dict) -> dict:
+    """--dump-outputs: what the timed path returned in its last step, one `<path>/<name>.npy` per array (float64 stays float64,
+    every other dtype is written as float32).  Arrays are written whole while they fit DUMP_LIMIT together; otherwise each array
+    above its even share of what is left is replaced by a fixed sample of its flattened elements (the sorted indices
+    torch.randint(numel, (share,), generator=torch.Generator().manual_seed(0)) draws), identical from run to run.
+    Returns {name: {"shape", "sampled"}} for the result line."""
+    os.makedirs(path, exist_ok=True)
+    items = sorted(((n, t.detach()) for n, t in arrays.items()), key=lambda kv: kv[1].numel())
+    left, info = DUMP_LIMIT, {}
+    for i, (name, t) in enumerate(items):
+        t = t.double() if t.dtype == torch.float64 else t.float()
+        share = (left // (len(items) - i) - 4096) // t.element_size()  # 4 KB: room for the .npy header
+        sampled = t.numel() > share
+        if sampled:
+            idx = torch.randint(t.numel(), (share,), generator=torch.Generator().manual_seed(0)).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        fn = os.path.join(path, name + ".npy")
+        np.save(fn, t.cpu().numpy())
+        left -= os.path.getsize(fn)
+        info[name] = {"shape": list(arrays[name].shape), "sampled": sampled}
+    return info
+
+
 def executed_flop_fraction(res: int, frames: int, dead_rows: float, frozen_rows: float) -> float:
     """Share of the reference's per-forward FLOPs (WINDOW_FLOP) the engine executes in a sampling step.  Removed,
     all bit-exact: the pose patch-embed and every per-pixel FiLM projection (once per window instead of once per
@@ -146,6 +172,8 @@ def bench_train_k600(args, rank, world, dist):
         losses.append(train_step(args.warmup + i))
     barrier()
     dt = time.perf_counter() - t0
+    dumped = dump_outputs(args.dump_outputs, {"loss": losses[-1], "params": tr.params, "grads": tr.grads}) \
+        if args.dump_outputs and rank == 0 else None
     losses = [float(l.item()) for l in losses]
     assert all(np.isfinite(losses)), losses
     if dist is not None:
@@ -178,6 +206,8 @@ def bench_train_k600(args, rank, world, dist):
                          "achieved": step_flop * args.steps / dt / 1e12, "peak": 2500.0, "unit": "TFLOP/s", "frac": step_flop * args.steps / dt / 1e12 / 2500.0,
                          "traffic": None},
         }
+        if dumped:
+            line["dumped_outputs"] = dumped
         print(json.dumps(line), flush=True)
     if dist is not None:
         dist.barrier()
@@ -223,6 +253,8 @@ def bench_train_re10k(args, rank, world, dist):
     losses = [step(args.warmup + i) for i in range(args.steps)]
     barrier()
     dt = time.perf_counter() - t0
+    dumped = dump_outputs(args.dump_outputs, {"loss": losses[-1], "params": tr.flat, "grads": tr.flat_grads}) \
+        if args.dump_outputs and rank == 0 else None
     losses = [float(l.item()) for l in losses]
     assert all(np.isfinite(losses)), losses
     if dist is not None:
@@ -244,6 +276,8 @@ def bench_train_re10k(args, rank, world, dist):
             "roofline": {"bound": "mfma", "kernel": "whole training step (3 x forward FLOPs)", "achieved": tf, "peak": 2500.0, "unit": "TFLOP/s",
                          "frac": tf / 2500.0, "traffic": None},
         }
+        if dumped:
+            line["dumped_outputs"] = dumped
         print(json.dumps(line), flush=True)
     if dist is not None:
         dist.barrier()
@@ -274,9 +308,9 @@ def bench_k600(args, rank, world, dist):
     b = args.batch
     xs = torch.randn(b, 5, 16, 16, 16, generator=torch.Generator().manual_seed(rank)).cuda()
     if diff:
-        run = lambda: sampler._sample_all_videos(xs, n_context_tokens=2)["prediction"]
+        run = lambda: sampler._sample_all_videos(xs, n_context_tokens=2)
     else:
-        run = lambda: sampler._predict_videos(xs, n_context_tokens=2, conditions=None)
+        run = lambda: {"prediction": sampler._predict_videos(xs, n_context_tokens=2, conditions=None)}
 
     def barrier():
         if dist is not None:
@@ -296,7 +330,8 @@ def bench_k600(args, rank, world, dist):
         out = run()
     barrier()
     dt = time.perf_counter() - t0
-    assert torch.isfinite(out).all()
+    assert torch.isfinite(out["prediction"]).all()
+    dumped = dump_outputs(args.dump_outputs, out) if args.dump_outputs and rank == 0 else None
     if dist is not None:
         tmax = torch.tensor([dt], device="cuda")
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -345,6 +380,8 @@ def bench_k600(args, rank, world, dist):
                          "flop_per_launch": flop_per_launch, "source": roofline_source if attn_n else None},
             "sampler_mode": "hipgraph" if use_graph else "eager",
         }
+        if dumped:
+            line["dumped_outputs"] = dumped
         if not args.no_cpu_baseline and world == 1:
             from oracle import dit as odit
             cores = min(16, os.cpu_count() or 1)
@@ -455,7 +492,8 @@ def coordinate(args):
         return rc, (json.loads(rows[-1]) if rows else None), err, time.perf_counter() - t0
 
     head_args = ["--workload", "8f", "--steps", str(args.steps), "--warmup", str(args.warmup)] + (["--no-cpu-baseline"] if args.no_cpu_baseline else []) + \
-                (["--eager"] if args.eager else []) + (["--graph"] if args.graph else []) + (["--attn-safe"] if args.attn_safe else [])
+                (["--eager"] if args.eager else []) + (["--graph"] if args.graph else []) + (["--attn-safe"] if args.attn_safe else []) + \
+                (["--dump-outputs", args.dump_outputs] if args.dump_outputs else [])
     rc, line, err, _ = run(0, head_args, 1500)
     if rc != 0 or (rank == 0 and line is None):
         sys.stderr.write(err[-4000:])
@@ -505,6 +543,8 @@ def bench_vae_decode(args):
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "bf16", "data": "synthetic latents, seeded random-init weights",
             "config": {"workload": f"VideoVAE decoder: {b} videos x 5 latent tokens (16x16x16) -> 17 frames 128x128 per call", "ms_per_video": dt * 1e3 / b}}
+    if args.dump_outputs:
+        line["dumped_outputs"] = dump_outputs(args.dump_outputs, {"frames": out})
     print(json.dumps(line), flush=True)
 
 
@@ -561,11 +601,18 @@ def main():
     ap.add_argument("--attn-safe", action="store_true", help="level-2 attention on the running-max kernel (what weights beyond the QK-norm bound get)")
     ap.add_argument("--dry-run", action="store_true", help="host plumbing only (CPU, gloo): plans, shards and gathers every window but launches nothing")
     ap.add_argument("--batch", type=int, default=8, help="k600: videos per GPU (bash/k600 validation.batch_size)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy (float32, at most 64 MB in all; "
+                         "a fixed seeded sample of larger outputs).  Inputs are seeded: the same arguments give the same inputs on every run")
     ap.add_argument("--workload", choices=["8f", "200f", "k600", "k600diff", "train_k600", "train_k600diff", "train_re10k", "vae_decode"], default="8f",
                     help="8f: BASELINE config 2 (default, the metric's single-GPU configuration); 200f: config 3, the "
                          "200-frame rollout (keyframe density 0.0625, stabilized HG 4.0/0.02 + interpolation HG 1.5, batches of "
                          "4 windows), interpolation windows sharded over ranks")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs:
+        args.dump_outputs = os.path.abspath(args.dump_outputs)
     use_graph = (GRAPH_DEFAULT or args.graph) and not args.eager
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -660,6 +707,7 @@ def main():
     barrier()
     dt = time.perf_counter() - t0
     assert torch.isfinite(out).all()
+    dumped = dump_outputs(args.dump_outputs, {"videos": out}) if args.dump_outputs and rank == 0 else None
     ranks_identical = None
     if world > 1:
         tmax = torch.tensor([dt], device=dev)
@@ -747,6 +795,8 @@ def main():
             line["graph_captures"], line["graph_step_replays"] = sampler.graph_captures, sampler.graph_replays
         if ranks_identical is not None:
             line["ranks_bit_identical"] = ranks_identical
+        if dumped:
+            line["dumped_outputs"] = dumped
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.barrier()

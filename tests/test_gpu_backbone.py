@@ -3,9 +3,13 @@
 Tolerance (north_star: "within a stated fp tolerance"): relative L2 error of the v-prediction
 <= 2e-2 against the fp32 golden captured from the reference source (bf16 storage of activations,
 fp32 accumulation and fp32 norm statistics; 38 residual blocks deep)."""
+import os
+
 import numpy as np
 import pytest
 import torch
+
+from conftest import GOLDEN
 
 pytestmark = pytest.mark.gpu
 
@@ -30,7 +34,7 @@ def rel(a, b):
 @pytest.fixture(scope="module")
 def w64():
     from oracle import pose as opose, uvit as ouvit
-    g = np.load("tests/golden/backbone_w64.npz")
+    g = np.load(os.path.join(GOLDEN, "backbone_w64.npz"))
     ocfg = ouvit.UViTConfig(resolution=64)
     params = ouvit.seeded_params(ocfg, 3)
     x, k, poses = (torch.from_numpy(g[n]) for n in ("x", "k", "poses"))

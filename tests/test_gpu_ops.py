@@ -3,11 +3,14 @@ Tolerances: bf16 inputs are exact in both paths (the reference consumes the same
 so GEMM/conv/attention differ only by fp32 accumulation order (+ bf16 rounding of P in attention)."""
 import ctypes as C
 import math
+import os
 
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
+
+from conftest import GOLDEN
 
 pytestmark = pytest.mark.gpu
 
@@ -165,7 +168,7 @@ def test_attention_production_shapes_vs_fp32_softmax(capi, variant, b, heads, n,
 
 def test_ray_encode_vs_oracle(capi):
     from oracle import pose as opose
-    g = np.load("tests/golden/ray_encoding.npz")
+    g = np.load(os.path.join(GOLDEN, "ray_encoding.npz"))
     poses = torch.from_numpy(g["poses"])
     out = torch.empty(2, 8, 180, 8, 8, device="cuda")
     pd = poses.cuda()
