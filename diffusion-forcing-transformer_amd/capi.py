@@ -41,8 +41,31 @@ class DiTConfig(C.Structure):
     ]
 
 
-# name -> (restype, argtypes); every symbol include/dfot_hip.h declares
 _P, _I, _L, _F = C.c_void_p, C.c_int, C.c_int64, C.c_float
+_I32 = C.c_int32
+
+
+class GemmDesc(C.Structure):
+    """dfot_gemm_desc (include/dfot_hip.h): every argument of the GEMM launcher, for dfot_op_gemm_ex"""
+    _fields_ = [
+        ("amode", _I32), ("epi", _I32), ("variant", _I32),
+        ("A", _P), ("lda", _L), ("W", _P), ("ldw", _L),
+        ("M", _I32), ("N", _I32), ("K", _I32), ("H", _I32), ("Wd", _I32), ("Cin", _I32),
+        ("live", _P), ("bias", _P), ("bias_rows", _I32),
+        ("out_f32", _P), ("out_bf16", _P), ("ldo", _L),
+        ("resid", _P), ("resid_bf", _P),
+        ("gate", _P), ("gate_index", _P), ("ldg", _L), ("gate_rows", _I32),
+        ("act", _I32), ("pre_act", _P), ("raw", _P), ("ldraw", _L), ("tr_rows", _I32),
+        ("gn_part", _P), ("gn_rows_per_bt", _I32), ("gn_cpg", _I32),
+        ("out2", _P), ("ldo2", _L), ("split", _I32),
+        ("q", _P), ("k", _P), ("v", _P),
+        ("qw", _P), ("kw", _P), ("rope_cs", _P),
+        ("heads", _I32), ("d", _I32), ("ntok", _I32), ("qscale", _F), ("dstride", _I32), ("eps", _F),
+        ("ksplit", _I32), ("slice_stride", _L),
+    ]
+
+
+# name -> (restype, argtypes); every symbol include/dfot_hip.h declares
 SIGNATURES = {
     "dfot_last_error": (C.c_char_p, []),
     "dfot_version": (_I, []),
@@ -105,6 +128,8 @@ SIGNATURES = {
     "dfot_vspace_loss": (_I, [_P] * 9 + [_I, _I, _L, _P]),
     "dfot_op_gemm": (_I, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _P]),
     "dfot_op_conv3x3": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "dfot_op_gemm_ex": (_I, [C.POINTER(GemmDesc), _P]),
+    "dfot_op_gemm_desc_bytes": (_L, []),
     "dfot_op_attention": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "dfot_op_attention_padded": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "dfot_op_attention_bwd": (_I, [_P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _P]),

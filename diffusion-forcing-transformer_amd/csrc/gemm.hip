@@ -570,7 +570,7 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& g, const int tile_inde
         }
       }
       if constexpr (EPI == E_BF16) {
-        if (g.act == 1 && g.pre_act && live) {  // training: keep the pre-activation too (same shape and row stride as the output)
+        if (g.act != 0 && g.pre_act && live) {  // training: keep the pre-activation too (same shape and row stride as the output)
 #pragma unroll
           for (int p = 0; p < 2; ++p) {
             const int r = p * 8 + (lane >> 3);

@@ -1094,6 +1094,30 @@ int dfot_op_conv3x3(const void* a, const void* w, const float* bias, float* y, i
   return launch_gemm(A_CONV3, E_F32, variant, g, (hipStream_t)stream);
 }
 
+int dfot_op_gemm_ex(const dfot_gemm_desc* d, void* stream) {
+  DFOT_REQUIRE(d, DFOT_ERR_ARG, "op_gemm_ex: null descriptor");
+  GemmArgs g;
+  if (d->amode == A_CONV3) {
+    int rc = zero_page(const_cast<bf16**>(&g.zeros));
+    if (rc) return rc;
+  }
+  g.A = (const bf16*)d->A; g.lda = d->lda; g.W = (const bf16*)d->W; g.ldw = d->ldw;
+  g.M = d->M; g.N = d->N; g.K = d->K; g.H = d->H; g.Wd = d->Wd; g.Cin = d->Cin;
+  g.live = d->live; g.bias = d->bias; g.bias_rows = d->bias_rows;
+  g.out_f32 = d->out_f32; g.out_bf16 = (bf16*)d->out_bf16; g.ldo = d->ldo;
+  g.resid = d->resid; g.resid_bf = (const bf16*)d->resid_bf;
+  g.gate = d->gate; g.gate_index = d->gate_index; g.ldg = d->ldg; g.gate_rows = d->gate_rows;
+  g.act = d->act; g.pre_act = (bf16*)d->pre_act; g.raw = (bf16*)d->raw; g.ldraw = d->ldraw; g.tr_rows = d->tr_rows;
+  g.gn_part = d->gn_part; g.gn_rows_per_bt = d->gn_rows_per_bt; g.gn_cpg = d->gn_cpg;
+  g.out2 = (bf16*)d->out2; g.ldo2 = d->ldo2; g.split = d->split;
+  g.q = (bf16*)d->q; g.k = (bf16*)d->k; g.v = (bf16*)d->v;
+  g.qw = d->qw; g.kw = d->kw; g.rope_cs = d->rope_cs;
+  g.heads = d->heads; g.d = d->d; g.ntok = d->ntok; g.qscale = d->qscale; g.dstride = d->dstride; g.eps = d->eps;
+  g.ksplit = d->ksplit; g.slice_stride = d->slice_stride;
+  return launch_gemm(d->amode, d->epi, d->variant, g, (hipStream_t)stream);
+}
+int64_t dfot_op_gemm_desc_bytes(void) { return (int64_t)sizeof(dfot_gemm_desc); }
+
 int dfot_op_attention(const void* q, const void* k, const void* v, void* o, int ldo, int batch, int heads, int n, int d,
                       int variant, void* stream) {
   return launch_attention((const bf16*)q, (const bf16*)k, (const bf16*)v, (bf16*)o, ldo, batch, heads, n, d, variant,

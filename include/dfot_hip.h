@@ -286,6 +286,31 @@ int dfot_op_gemm(const void* a_bf16, int lda, const void* w_bf16, const float* b
 /* y[BT,H,W,Cout] (fp32) = conv3x3(pad 1)(a[BT,H,W,Cin] bf16, w[Cout][9*Cin] bf16 tap-major) + bias */
 int dfot_op_conv3x3(const void* a_bf16, const void* w_bf16, const float* bias, float* y, int bt, int h, int w,
                     int cin, int cout, int variant, void* stream);
+/* Test entry to the whole GEMM / implicit-GEMM launcher with every fused epilogue.  The fields mirror the engine's internal
+ * argument block one to one (amode 0 = dense A, 1 = conv3x3; epi 0 = fp32, 1 = bf16, 2 = fused attention+MLP projection,
+ * 3 = DiT q|k|v; variant as for the plain GEMM entry); their meaning is documented at that block.  Pointers are device pointers
+ * or NULL; the conv zero page is supplied by the library.  The launcher's own checks are the only validation. */
+typedef struct {
+  int32_t amode, epi, variant;
+  const void* A; int64_t lda;
+  const void* W; int64_t ldw;
+  int32_t M, N, K, H, Wd, Cin;
+  const uint8_t* live;
+  const float* bias; int32_t bias_rows;
+  float* out_f32; void* out_bf16; int64_t ldo;
+  const float* resid; const void* resid_bf;
+  const float* gate; const int32_t* gate_index; int64_t ldg; int32_t gate_rows;
+  int32_t act; void* pre_act; void* raw; int64_t ldraw; int32_t tr_rows;
+  float* gn_part; int32_t gn_rows_per_bt, gn_cpg;
+  void* out2; int64_t ldo2; int32_t split;
+  void *q, *k, *v;
+  const float *qw, *kw, *rope_cs;
+  int32_t heads, d, ntok; float qscale; int32_t dstride; float eps;
+  int32_t ksplit; int64_t slice_stride;
+} dfot_gemm_desc;
+int dfot_op_gemm_ex(const dfot_gemm_desc* desc, void* stream);
+/* sizeof(dfot_gemm_desc): the Python mirror of the struct checks its layout against it */
+int64_t dfot_op_gemm_desc_bytes(void);
 /* o[B,N,heads*d] (bf16, row stride ldo) = softmax(q k^T) v ; q,k,v [B,heads,N,d] bf16; q pre-scaled by
  * log2(e)/sqrt(d) (the kernel works in the exp2 domain). d in {64,128}; N % 128 == 0 (d=64) or % 64. */
 int dfot_op_attention(const void* q, const void* k, const void* v, void* o, int ldo, int batch, int heads, int n,

@@ -65,16 +65,18 @@ def test_backbone_vs_golden_and_oracle_taps(w64, dma, variant):
     spec = [("down0", ocfg.channels[1], 1), ("down1", ocfg.channels[2], 2),
             ("down2", ocfg.channels[3], 3), ("mid", ocfg.channels[3], 3), ("up2", ocfg.channels[2], 2),
             ("up1", ocfg.channels[1], 1), ("up0", ocfg.channels[0], 0)]
+    tap_err = {}
     for name, ch, lvl in spec:
         got = model.read_tap(name, ch, lvl, 2).cpu()
-        r = rel(got, taps[name])
-        print(f"tap {name}: rel_l2={r:.3e}")
+        tap_err[name] = rel(got, taps[name])
+        print(f"tap {name}: rel_l2={tap_err[name]:.3e}")
     r_or = rel(v, w64["ref"])
     r_go = rel(v, w64["golden"])
     print(f"backbone gemm_variant={dma} attn_variant={variant}: rel_l2 vs oracle {r_or:.3e}, vs reference golden {r_go:.3e}, "
           f"max_abs {(v - w64['golden']).abs().max().item():.3e}")
     assert torch.isfinite(v).all()
     assert r_go < REL_TOL and r_or < REL_TOL
+    assert all(e < REL_TOL for e in tap_err.values()), tap_err
 
 
 def test_large_qk_norm_weights_take_the_running_max_attention(w64):

@@ -26,6 +26,14 @@ def test_library_exports_every_symbol_declared_in_header():
     assert lib.dfot_version() >= 1
 
 
+def test_gemm_descriptor_layout_matches_the_header():
+    """capi.GemmDesc mirrors dfot_gemm_desc field by field: a field added, dropped or widened on one side only changes the size"""
+    import __graft_entry__ as g
+    g.build()
+    from dfot_amd import capi
+    assert ctypes.sizeof(capi.GemmDesc) == capi.lib.dfot_op_gemm_desc_bytes()
+
+
 def _imports(path):
     tree = ast.parse(open(path).read())
     for node in ast.walk(tree):
