@@ -4,7 +4,12 @@
 
 namespace dfot {
 
-enum AMode { A_DENSE = 0, A_CONV3 = 1 };
+// A_CONV3T: implicit-GEMM 3x3 / 3x3x3 convolution with spatial stride 1 or 2 and a causal temporal window (VideoVAE encoder, vae.hip):
+//   output row m = (b, t_o, y_o, x_o) of [B][To][H][Wd]; tap (dt, dy, dx), K = kt * 9 * Cin tap-major;
+//   source frame max(st * t_o + dt - (kt - 1), 0) (first-frame replication of PaddedConv3D), source pixel (s * y_o + dy - p, s * x_o + dx - p)
+//   with p = 1 for s = 1 and p = 0 for s = 2 (the (0, 1) zero padding of Downsample / Spatial2xTime2x3DDownsample); out-of-image pixels read
+//   the zero page
+enum AMode { A_DENSE = 0, A_CONV3 = 1, A_CONV3T = 2 };
 enum Epi { E_F32 = 0, E_BF16 = 1, E_QKV = 2, E_QKV_DIT = 3 };
 
 struct GemmArgs {
@@ -19,6 +24,9 @@ struct GemmArgs {
   // conv: optional per-image flags (device uint8 [M / (H * Wd)]); the tiles of an image whose flag is 0 exit at once (no loads, no stores,
   // no GroupNorm partials): images whose output the caller discards.  A tile must lie inside one image (launcher)
   const uint8_t* live = nullptr;
+  // A_CONV3T geometry (internal: not in dfot_gemm_desc).  H, Wd are the OUTPUT image size; the input is [B][Tin][Hin][Win][Cin]
+  int To = 0, Tin = 0, Hin = 0, Win = 0;
+  int cs = 1, ct = 1, ckt = 1;  // spatial stride, time stride, temporal taps (1 or 3)
   // epilogue
   const float* bias = nullptr;
   float* out_f32 = nullptr;

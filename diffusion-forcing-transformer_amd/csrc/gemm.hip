@@ -118,6 +118,7 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& g, const int tile_inde
   const int ppos = lane % CPR;  // 16-byte position within the LDS row
   const bf16* a_src[ACH];
   int a_y[ACH], a_x[ACH];
+  [[maybe_unused]] int a_t[ACH];  // A_CONV3T: first source frame of the row's temporal window (may be negative: clamped per tap)
   const bf16* w_src[WCH];
   int a_chunk[ACH];
 #pragma unroll
@@ -129,13 +130,27 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& g, const int tile_inde
     if constexpr (AMODE == A_DENSE) {
       a_src[i] = g.A + m * g.lda + c * 8 + kbeg;
       a_y[i] = a_x[i] = 0;
-    } else {
+    } else if constexpr (AMODE == A_CONV3) {
       const unsigned mu = (unsigned)m;  // 32-bit divisions (M < 2^31)
       const int xw = (int)(mu % (unsigned)g.Wd);
       const int yh = (int)((mu / (unsigned)g.Wd) % (unsigned)g.H);
       a_x[i] = xw;
       a_y[i] = yh;
       a_src[i] = g.A + m * (long)g.Cin + c * 8;
+    } else {
+      // A_CONV3T: row -> (b, t_o, y_o, x_o); the row keeps the base of its video and the top-left-front corner of its window
+      unsigned mu = (unsigned)m;
+      const int xo = (int)(mu % (unsigned)g.Wd);
+      mu /= (unsigned)g.Wd;
+      const int yo = (int)(mu % (unsigned)g.H);
+      mu /= (unsigned)g.H;
+      const int to = (int)(mu % (unsigned)g.To);
+      const unsigned bv = mu / (unsigned)g.To;
+      const int pad = g.cs == 1 ? 1 : 0;
+      a_x[i] = g.cs * xo - pad;
+      a_y[i] = g.cs * yo - pad;
+      a_t[i] = g.ct * to - (g.ckt - 1);
+      a_src[i] = g.A + (long)bv * ((long)g.Tin * g.Hin * g.Win * g.Cin) + c * 8;
     }
   }
 #pragma unroll
@@ -149,21 +164,35 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& g, const int tile_inde
 
   // conv3x3: k-tile kt covers channels [cv_c0, cv_c0 + BKT) of tap (cv_dy, cv_dx).  issue() is called with consecutive k-tiles
   // (stride KS), so the tap position is carried along instead of being re-derived with three integer divisions per k-tile
-  [[maybe_unused]] int cv_c0 = 0, cv_dy = -1, cv_dx = -1;
+  [[maybe_unused]] int cv_c0 = 0, cv_dy = -1, cv_dx = -1, cv_dt = 0;
   if constexpr (AMODE == A_CONV3) {
     const int kbase = kgroup * BKT + (int)kbeg;  // first k-tile of this k-group (of this workgroup's K slice: split-K into partial outputs)
     const int tap = kbase / g.Cin;
     cv_c0 = kbase - tap * g.Cin;
     cv_dy = tap / 3 - 1;
     cv_dx = tap % 3 - 1;
+  } else if constexpr (AMODE == A_CONV3T) {  // taps (dt, dy, dx) counted from 0: the padding is in a_t / a_y / a_x
+    const int kbase = kgroup * BKT + (int)kbeg;
+    const int tap = kbase / g.Cin;
+    cv_c0 = kbase - tap * g.Cin;
+    cv_dt = tap / 9;
+    cv_dy = (tap % 9) / 3;
+    cv_dx = tap % 3;
   }
   auto a_addr = [&](int i, int kt) -> const bf16* {
     if constexpr (AMODE == A_DENSE) {
       return a_src[i] + (long)kt * BKT;
-    } else {
+    } else if constexpr (AMODE == A_CONV3) {
       const int yy = a_y[i] + cv_dy, xx = a_x[i] + cv_dx;
       const bool ok = (yy >= 0) && (yy < g.H) && (xx >= 0) && (xx < g.Wd);
       const bf16* p = a_src[i] + ((long)cv_dy * g.Wd + cv_dx) * g.Cin + cv_c0;
+      return ok ? p : g.zeros + a_chunk[i] * 8;
+    } else {
+      int tt = a_t[i] + cv_dt;
+      tt = tt < 0 ? 0 : tt;  // causal first-frame replication: a clamp, not a zero
+      const int yy = a_y[i] + cv_dy, xx = a_x[i] + cv_dx;
+      const bool ok = (yy >= 0) && (yy < g.Hin) && (xx >= 0) && (xx < g.Win);
+      const bf16* p = a_src[i] + ((long)(tt * g.Hin + yy) * g.Win + xx) * g.Cin + cv_c0;
       return ok ? p : g.zeros + a_chunk[i] * 8;
     }
   };
@@ -175,6 +204,18 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& g, const int tile_inde
         if (++cv_dx > 1) {
           cv_dx = -1;
           ++cv_dy;
+        }
+      }
+    } else if constexpr (AMODE == A_CONV3T) {
+      cv_c0 += KS * BKT;
+      while (cv_c0 >= g.Cin) {
+        cv_c0 -= g.Cin;
+        if (++cv_dx > 2) {
+          cv_dx = 0;
+          if (++cv_dy > 2) {
+            cv_dy = 0;
+            ++cv_dt;
+          }
         }
       }
     }
@@ -861,7 +902,9 @@ static int launch_t(const GemmArgs& g, hipStream_t stream) {
 template <int AMODE, int EPI>
 static int launch_v(int variant, const GemmArgs& g, hipStream_t s) {
   switch (variant) {
-    case GEMM_REGS_128: return launch_t<128, 128, 64, 2, AMODE, EPI, false>(g, s);
+    case GEMM_REGS_128:
+      if constexpr (AMODE == A_CONV3T) break;  // (the strided conv mode is instantiated for the LDS-DMA forms gemm_pick_variant picks)
+      else return launch_t<128, 128, 64, 2, AMODE, EPI, false>(g, s);
     case GEMM_DMA_128: return launch_t<128, 128, 64, 2, AMODE, EPI, true>(g, s);
     case GEMM_DMA_256x256: return launch_t<256, 256, 64, 2, AMODE, EPI, true>(g, s);
     case GEMM_DMA_512x128: return launch_t<512, 128, 64, 2, AMODE, EPI, true>(g, s);
@@ -869,7 +912,7 @@ static int launch_v(int variant, const GemmArgs& g, hipStream_t s) {
       if constexpr (AMODE != A_DENSE) break;
       else return launch_t<256, 192, 64, 2, AMODE, EPI, true>(g, s);
     case GEMM_DMA3_256x144:  // (also the long-K Downsample / Upsample convolutions: run_down / run_up)
-      if constexpr (EPI != E_F32 && !(EPI == E_BF16 && AMODE == A_DENSE)) break;  // E_BF16: the level-2 out-projection onto the bf16 stream
+      if constexpr ((EPI != E_F32 && !(EPI == E_BF16 && AMODE == A_DENSE)) || AMODE == A_CONV3T) break;  // E_BF16: the level-2 out-projection onto the bf16 stream
       else {
         if (g.gn_part) break;
         return launch_t<256, 144, 64, 3, AMODE, EPI, true>(g, s);
@@ -934,6 +977,20 @@ int launch_gemm(int amode, int epi, int variant, const GemmArgs& g, hipStream_t 
     DFOT_REQUIRE(g.H > 0 && g.Wd > 0 && g.M % (g.H * g.Wd) == 0, DFOT_ERR_SHAPE, "conv3x3: M=%d not a whole number of %dx%d images", g.M, g.H, g.Wd);
     DFOT_REQUIRE(!g.live || (g.H * g.Wd) % bm == 0, DFOT_ERR_SHAPE, "conv3x3: live-image flags need whole %d-row tiles per %dx%d image", bm, g.H, g.Wd);
   }
+  if (amode == A_CONV3T) {
+    // every source address a row can form stays inside its own video: t in [0, Tin) (the clamp covers t < 0, st (To - 1) <= Tin - 1
+    // bounds the top), y / x outside [0, Hin) x [0, Win) read the zero page
+    DFOT_REQUIRE(epi == E_F32 && g.ksplit <= 1 && !g.live && !g.gate && !g.bias_rows, DFOT_ERR_ARG, "conv3t: plain fp32 epilogue only");
+    DFOT_REQUIRE(g.Cin % BK == 0 && (g.ckt == 1 || g.ckt == 3) && g.K == g.ckt * 9 * g.Cin && (g.cs == 1 || g.cs == 2) && (g.ct == 1 || g.ct == 2),
+                 DFOT_ERR_SHAPE, "conv3t: Cin=%d (multiple of %d), kt=%d in {1,3}, K=%d = kt*9*Cin, strides s=%d t=%d in {1,2}", g.Cin, BK, g.ckt, g.K,
+                 g.cs, g.ct);
+    DFOT_REQUIRE(g.zeros != nullptr, DFOT_ERR_ARG, "conv3t: zero page missing");
+    DFOT_REQUIRE(g.H > 0 && g.Wd > 0 && g.To > 0 && g.Hin == g.cs * g.H && g.Win == g.cs * g.Wd && g.Tin >= 1 && g.ct * (g.To - 1) <= g.Tin - 1 &&
+                     g.To == (g.Tin - 1) / g.ct + 1,
+                 DFOT_ERR_SHAPE, "conv3t: input %dx%dx%d, output %dx%dx%d do not match strides s=%d t=%d", g.Tin, g.Hin, g.Win, g.To, g.H, g.Wd, g.cs, g.ct);
+    DFOT_REQUIRE(g.M % (g.To * g.H * g.Wd) == 0, DFOT_ERR_SHAPE, "conv3t: M=%d not a whole number of %dx%dx%d videos", g.M, g.To, g.H, g.Wd);
+    DFOT_REQUIRE((long)g.Tin * g.Hin * g.Win * g.Cin < (1L << 31), DFOT_ERR_SHAPE, "conv3t: one input video must hold < 2^31 elements");
+  }
   if (epi == E_QKV) {
     DFOT_REQUIRE(g.q && g.k && g.v && g.qw && g.kw && g.rope_cs && (g.out2 || g.N == g.split), DFOT_ERR_ARG, "qkv epilogue: null pointer");
     DFOT_REQUIRE(!g.raw || (g.ldraw >= g.N && g.ldraw % 8 == 0), DFOT_ERR_SHAPE, "qkv epilogue: raw copy needs ldraw >= N, a multiple of 8");
@@ -981,6 +1038,8 @@ int launch_gemm(int amode, int epi, int variant, const GemmArgs& g, hipStream_t 
       case E_F32: return launch_v<A_CONV3, E_F32>(variant, g, stream);
       case E_BF16: return launch_v<A_CONV3, E_BF16>(variant, g, stream);
     }
+  } else if (amode == A_CONV3T && epi == E_F32) {
+    return launch_v<A_CONV3T, E_F32>(variant, g, stream);
   }
   set_error("gemm: unsupported mode/epilogue combination %d/%d", amode, epi);
   return DFOT_ERR_ARG;

@@ -10,8 +10,16 @@
 //                              (T, H, W) (align_corners = False: out 2i -> 0.25 x[i-1] + 0.75 x[i], out 2i+1 -> 0.75 x[i] + 0.25 x[i+1], clamped)
 //   dfot_op_softmax_rows       P = softmax(scale * S) per row, fp32 -> bf16 (AttnBlock3D, attention.py:127-129: one head of C channels per
 //                              frame, so the scores go through the GEMM kernel, not the flash kernels whose head dim stops at 128)
+// Encoder (VideoVAE._encode / encode, model.py:38-150,402-443; BaseVideoAlgo._encode, base_pytorch_video_algo.py:585-596):
+//   dfot_op_conv3t_f32         strided / causal-temporal implicit-GEMM convolution (A_CONV3T of gemm.hip): 3x3 per frame or 3x3x3 with the
+//                              temporal taps accumulated in registers, spatial stride 1 (pad 1) or 2 (pad (0, 1)), time stride 1 or 2
+//   dfot_op_vae_pixels         strided fp32 frames -> channels-last bf16 [B][T][H][W][64], a * x + b on channels 0-2 (the 2y - 1 of _encode),
+//                              zeros in 3-63: conv_in then runs on the stride-1 conv with Cin = 64
+//   dfot_op_vae_posterior      quant_conv moments [B][T][h][w][ld] -> DiagonalGaussianDistribution (distribution.py): mean, clamped logvar,
+//                              std, and mean + std * eps, optionally (x - data_mean) / data_std (_normalize_x), all in b t c h w
 #include "common.h"
 #include "dfot_hip.h"
+#include "gemm.h"
 #include "kernels.h"
 
 namespace dfot {
@@ -118,6 +126,54 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(const float* __restri
   for (int j = lane; j < n; j += 64) p[row * n + j] = f2bf(__expf(sr[j] * scale - m) * inv);
 }
 
+// one thread per pixel: three strided fp32 reads, 64 bf16 channels written as 8 x 16 B
+__global__ void vae_pixels_kernel(const float* __restrict__ x, long sb, long sc, long st, long sh, long sw, float a, float b0,
+                                  bf16* __restrict__ out, long pixels, int t, int h, int w) {
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= pixels) return;
+  const int xx = (int)(idx % w);
+  long r = idx / w;
+  const int yy = (int)(r % h);
+  r /= h;
+  const int tt = (int)(r % t);
+  const long b = r / t;
+  const float* src = x + b * sb + tt * st + yy * sh + xx * sw;
+  bf16x8 v0;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) v0[j] = f2bf(j < 3 ? a * src[j * sc] + b0 : 0.f);
+  bf16x8* dst = reinterpret_cast<bf16x8*>(out + idx * 64);
+  dst[0] = v0;
+  bf16x8 z;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) z[j] = f2bf(0.f);
+#pragma unroll
+  for (int j = 1; j < 8; ++j) dst[j] = z;
+}
+
+// one thread per latent element of b t c h w
+__global__ void vae_posterior_kernel(const float* __restrict__ mom, int ld, const float* __restrict__ eps, const float* __restrict__ dmean,
+                                     const float* __restrict__ dstd, float* __restrict__ mean, float* __restrict__ logvar, float* __restrict__ stdv,
+                                     float* __restrict__ z, long total, int hw, int zc) {
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= total) return;
+  const int p = (int)(idx % hw);
+  const long r = idx / hw;
+  const int c = (int)(r % zc);
+  const long bt = r / zc;
+  const float* m = mom + (bt * hw + p) * ld;
+  const float mu = m[c];
+  const float lv = fminf(fmaxf(m[zc + c], -30.f), 20.f);
+  const float sd = expf(0.5f * lv);
+  if (mean) mean[idx] = mu;
+  if (logvar) logvar[idx] = lv;
+  if (stdv) stdv[idx] = sd;
+  if (z) {
+    float v = eps ? mu + sd * eps[idx] : mu;
+    if (dmean) v = (v - dmean[c]) / dstd[c];
+    z[idx] = v;
+  }
+}
+
 }  // namespace
 }  // namespace dfot
 
@@ -158,6 +214,57 @@ int dfot_op_upsample3d(const float* x, float* out, int batch, int frames, int h,
   const int t_out = mode == 1 ? 1 + 2 * (frames - 1) : frames;
   const long total4 = (long)batch * t_out * (2 * h) * (2 * w) * (channels / 4);
   hipLaunchKernelGGL(upsample3d_kernel, dim3(cdiv(total4, 256)), dim3(256), 0, (hipStream_t)stream, x, out, total4, frames, h, w, channels, mode);
+  DFOT_CHECK_HIP(hipGetLastError());
+  return DFOT_OK;
+}
+
+static bf16* g_conv3t_zeros = nullptr;
+
+int dfot_op_conv3t_f32(const void* a, const void* w, const float* bias, const float* resid, float* y, int batch, int t_in, int h_in, int w_in,
+                       int cin, int cout, int kt, int stride_s, int stride_t, void* stream) {
+  DFOT_REQUIRE(a && w && y && a != y, DFOT_ERR_ARG, "op_conv3t_f32: null or aliased argument");
+  DFOT_REQUIRE(batch > 0 && t_in > 0 && (stride_s == 1 || stride_s == 2) && (stride_t == 1 || stride_t == 2) && h_in % stride_s == 0 &&
+                   w_in % stride_s == 0,
+               DFOT_ERR_SHAPE, "op_conv3t_f32: batch=%d T=%d H=%d W=%d with strides s=%d t=%d", batch, t_in, h_in, w_in, stride_s, stride_t);
+  if (!g_conv3t_zeros) {
+    DFOT_CHECK_HIP(hipMalloc(&g_conv3t_zeros, 256));
+    DFOT_CHECK_HIP(hipMemset(g_conv3t_zeros, 0, 256));
+  }
+  GemmArgs g;
+  g.zeros = g_conv3t_zeros;
+  g.H = h_in / stride_s; g.Wd = w_in / stride_s; g.To = (t_in - 1) / stride_t + 1;
+  g.Tin = t_in; g.Hin = h_in; g.Win = w_in; g.cs = stride_s; g.ct = stride_t; g.ckt = kt;
+  const long m = (long)batch * g.To * g.H * g.Wd;
+  DFOT_REQUIRE(m < (1L << 31), DFOT_ERR_SHAPE, "op_conv3t_f32: M=%ld rows", m);
+  g.A = (const bf16*)a; g.W = (const bf16*)w; g.M = (int)m; g.N = cout; g.K = kt * 9 * cin; g.Cin = cin;
+  g.bias = bias; g.resid = resid; g.out_f32 = y; g.ldo = cout;
+  // Batch-invariant results: every tile form sums K in the same order except the intra-workgroup split-K one (two k-groups, folded at
+  // the end), so whether K is split is decided from ONE video's rows.  A video then encodes to the same bits whatever it is batched with.
+  const int rows1 = g.To * g.H * g.Wd;
+  int variant = gemm_pick_variant(A_CONV3T, g.M, g.N, g.K, true);
+  const bool split1 = gemm_pick_variant(A_CONV3T, rows1, g.N, g.K, true) == GEMM_DMA_128_KS2;
+  if (split1 != (variant == GEMM_DMA_128_KS2)) variant = split1 ? GEMM_DMA_128_KS2 : GEMM_DMA_128;
+  return launch_gemm(A_CONV3T, E_F32, variant, g, (hipStream_t)stream);
+}
+
+int dfot_op_vae_pixels(const float* x, int64_t sb, int64_t sc, int64_t st, int64_t sh, int64_t sw, float a, float b, void* out, int batch, int frames,
+                       int h, int w, void* stream) {
+  DFOT_REQUIRE(x && out, DFOT_ERR_ARG, "op_vae_pixels: null argument");
+  DFOT_REQUIRE(batch > 0 && frames > 0 && h > 0 && w > 0, DFOT_ERR_SHAPE, "op_vae_pixels: empty shape");
+  const long pixels = (long)batch * frames * h * w;
+  hipLaunchKernelGGL(vae_pixels_kernel, dim3(cdiv(pixels, 256)), dim3(256), 0, (hipStream_t)stream, x, (long)sb, (long)sc, (long)st, (long)sh,
+                     (long)sw, a, b, (bf16*)out, pixels, frames, h, w);
+  DFOT_CHECK_HIP(hipGetLastError());
+  return DFOT_OK;
+}
+
+int dfot_op_vae_posterior(const float* moments, int ld, const float* eps, const float* data_mean, const float* data_std, float* mean, float* logvar,
+                          float* stdv, float* z, int batch, int frames, int hw, int zc, void* stream) {
+  DFOT_REQUIRE(moments && ld >= 2 * zc && zc > 0 && (!data_mean == !data_std) && (z || (!eps && !data_mean)), DFOT_ERR_ARG,
+               "op_vae_posterior: bad argument (ld >= 2 * zc, data_mean with data_std, eps / normalisation need z)");
+  const long total = (long)batch * frames * zc * hw;
+  hipLaunchKernelGGL(vae_posterior_kernel, dim3(cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, moments, ld, eps, data_mean, data_std, mean,
+                     logvar, stdv, z, total, hw, zc);
   DFOT_CHECK_HIP(hipGetLastError());
   return DFOT_OK;
 }

@@ -2,11 +2,14 @@
 """Training loop with the MI355X engine, the way the reference's Lightning trainer drives `training_step`.
 
   python examples/train.py k600     [--ckpt K600.ckpt] [--steps 100] [--batch 8] [--save out.ckpt]
+  python examples/train.py k600 --pixels [--vae-ckpt VideoVAE_K600.ckpt]                # online latents: frames -> VideoVAE encoder -> step
   python examples/train.py k600diff [--accumulate 2]                                  # the model bash/k600/*.sh train
   python examples/train.py re10k    [--batch 8]                                       # RE10K UViT3DPose (BASELINE config 5), synthetic frames + poses
   python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 examples/train.py k600   # data parallel, one rank per GPU
 
-Data are synthetic latents (no dataset offline); everything else is the reference's recipe: per-token noise levels from
+Data are synthetic latents (no dataset offline), or with --pixels synthetic 17 x 128 x 128 frames encoded online the way the K600
+configuration does it (latent.type: online: `_encode` + `_normalize_x` on every batch, data_mean / data_std of
+configurations/dataset/kinetics_600.yaml); everything else is the reference's recipe: per-token noise levels from
 `_get_training_noise_levels` (random_independent for @DiT/XL, random_uniform + variable context for bash/k600), fused-min-SNR
 v-loss, AdamW lr 5e-5 / wd 0.01 / betas (0.9, 0.99), gradient clipping 1.0, gradients averaged over the ranks.
 The saved file uses the reference's key names (`diffusion_model.model.*`) and loads into the reference or into the samplers here.
@@ -22,6 +25,11 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import dfot_amd  # noqa: E402
 
 
+# configurations/dataset/kinetics_600.yaml: per-channel statistics of the VideoVAE latents
+K600_DATA_MEAN = [-0.284, 0.016, -0.728, -0.138, 0.941, -2.504, 0.147, -0.062, 0.833, 0.151, -0.627, 0.269, 0.268, -0.732, -1.598, 0.199]
+K600_DATA_STD = [5.591, 5.257, 7.033, 6.401, 6.091, 11.233, 5.608, 7.5, 5.277, 5.46, 5.179, 6.8, 5.474, 5.111, 7.078, 5.024]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("model", choices=["k600", "k600diff", "re10k"])
@@ -32,6 +40,8 @@ def main():
     ap.add_argument("--lr", type=float, default=5e-5)
     ap.add_argument("--warmup-steps", type=int, default=10000, help="re10k: linear lr warm-up (constant_with_warmup, realestate10k_video_generation.yaml)")
     ap.add_argument("--save")
+    ap.add_argument("--pixels", action="store_true", help="k600 / k600diff: encode synthetic frames online with the VideoVAE encoder")
+    ap.add_argument("--vae-ckpt", help="--pixels: reference VideoVAE checkpoint (vae.* keys); random encoder weights otherwise")
     a = ap.parse_args()
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")))
@@ -61,11 +71,24 @@ def main():
         trainer.load_state_dict({k: v.detach() for k, v in init.state_dict().items()})
     del init
     g = torch.Generator().manual_seed(1000 + rank)
+    encoder = None
+    if a.pixels:
+        encoder = dfot_amd.VideoVAEEncoder(z_channels=16, embed_dim=16, resolution=128, temporal_length=17).cuda()
+        if a.vae_ckpt:
+            sd = torch.load(a.vae_ckpt, map_location="cpu", weights_only=False)
+            encoder.load_reference_state_dict(sd.get("state_dict", sd))
+        else:
+            encoder.init_random(seed=0)
+        gv = torch.Generator(device="cuda").manual_seed(2000 + rank)
     masks = torch.ones(a.batch, 5, dtype=torch.bool)
     t0 = time.perf_counter()
     for step in range(a.steps):
         for _ in range(a.accumulate):
-            frames = torch.randn(a.batch, 5, 16, 16, 16, generator=g)
+            if encoder is not None:   # on_after_batch_transfer with latent.type online: _encode (vae.batch_size 2) then _normalize_x
+                videos = torch.rand(a.batch, 17, 3, 128, 128, device="cuda", generator=gv)
+                frames = dfot_amd.encode_videos(encoder, videos, vae_batch_size=2, generator=gv, data_mean=K600_DATA_MEAN, data_std=K600_DATA_STD)
+            else:
+                frames = torch.randn(a.batch, 5, 16, 16, 16, generator=g)
             noise = torch.randn(a.batch, 10 if diff else 5, 16, 16, 16, generator=g)
             levels, loss_masks = sampling.sample(a.batch, 5, masks, g, training=True)
             loss = (trainer.difference_loss_and_grads if diff else trainer.loss_and_grads)(frames, levels, noise, loss_masks)

@@ -459,6 +459,24 @@ int dfot_op_frame_shift(const void* x, void* out, int batch, int frames, int64_t
 int dfot_op_upsample3d(const float* x, float* out, int batch, int frames, int h, int w, int channels, int mode, void* stream);
 /* probs[r][:] = softmax(scale * scores[r][:]) (fp32 -> bf16): the frame-wise single-head attention of AttnBlock3D (attention.py:127-129) */
 int dfot_op_softmax_rows(const float* scores, void* probs, int64_t rows, int n, float scale, void* stream);
+/* ---- VideoVAE encoder pieces (algorithms/vae/video_vae/model.py:38-150,402-443, updownsample.py Downsample /
+ * Spatial2xTime2x3DDownsample, distribution.py; called from BaseVideoAlgo._encode, base_pytorch_video_algo.py:585-596). ------------------- */
+/* y fp32 [B][To][H][W][Cout] (+ bias, + resid fp32 of the same shape) = convolution of a bf16 [B][Tin][Hin][Win][Cin] with w bf16
+ * [Cout][kt][3][3][Cin] (K = kt*9*Cin tap-major), one launch.  Source frame of output frame t_o and temporal tap dt:
+ * max(stride_t * t_o + dt - (kt - 1), 0) (causal first-frame replication); source pixel (s y_o + dy - p, s x_o + dx - p), p = 1 for s = 1
+ * and 0 for s = 2 (zero padding (0, 1)).  H = Hin / s, W = Win / s, To = (Tin - 1) / stride_t + 1.  kt in {1, 3}, s and stride_t in
+ * {1, 2}, Cin % 64 == 0, Cout % 4 == 0, B*To*H*W a multiple of 128. */
+int dfot_op_conv3t_f32(const void* a, const void* w, const float* bias, const float* resid, float* y, int batch, int t_in, int h_in, int w_in,
+                       int cin, int cout, int kt, int stride_s, int stride_t, void* stream);
+/* out bf16 [B][T][H][W][64] = a * x + b on channels 0-2, 0 on 3-63; x fp32 (B, 3, T, H, W) addressed with element strides sb, sc, st, sh, sw
+ * (any permutation of the layout) */
+int dfot_op_vae_pixels(const float* x, int64_t sb, int64_t sc, int64_t st, int64_t sh, int64_t sw, float a, float b, void* out, int batch, int frames,
+                       int h, int w, void* stream);
+/* DiagonalGaussianDistribution of the moments fp32 [B][T][hw][ld] (mean = channels [0, zc), logvar = [zc, 2 zc) clamped to [-30, 20]), every
+ * output fp32 [B][T][zc][hw] (b t c h w) and optional: mean, logvar, std = exp(logvar / 2), z = mean + std * eps (eps in the same layout;
+ * NULL: z = mean), then z = (z - data_mean[c]) / data_std[c] when both are given. */
+int dfot_op_vae_posterior(const float* moments, int ld, const float* eps, const float* data_mean, const float* data_std, float* mean, float* logvar,
+                          float* std_, float* z, int batch, int frames, int hw, int zc, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Micro-benchmarks of the C-ABI primitives at the RE10K model shapes (model batch 2), HIP-event timed.
-Usage (GPU box): python tools/bench_ops.py [gemm] [conv] [attn]"""
+Usage (GPU box): python tools/bench_ops.py [gemm] [conv] [attn] [vae_encode]"""
 import ctypes as C
 import math
 import os
@@ -55,8 +55,64 @@ def attn(b, heads, n, d, variant):
     return ms, 4.0 * b * heads * n * n * d / ms / 1e9
 
 
+def vae_encode(b=2, t=17, res=128):
+    """VideoVAE encoder (K600: hidden 128, z 16) on b videos of t x res x res frames: the whole encode_videos after warm-up, then every
+    convolution shape of the plan on its own, grouped by class.  FLOPs are the reference's (true channel counts), from the shapes here."""
+    enc = dfot_amd.VideoVAEEncoder(z_channels=16, embed_dim=16, resolution=res, temporal_length=17).cuda()
+    enc.init_random(seed=0)
+    videos = torch.rand(b, t, 3, res, res, device="cuda")
+    noise = torch.randn(b, (t - 1) // 4 + 1, 16, res // 8, res // 8, device="cuda")
+    ms = timeit(lambda: dfot_amd.encode_videos(enc, videos, vae_batch_size=b, noise=noise), iters=10, warm=3)
+    # (class, count, B, T_in, H_in, W_in, true Cin, Cin as run, Cout, kt, s, st)
+    c = [128, 256, 512, 512]
+    t1, t2 = (t - 1) // 2 + 1, (t - 1) // 4 + 1
+    r1, r2, r3 = res // 2, res // 4, res // 8
+    convs = [("2-D stride 1", 1, b, t, res, res, 3, 64, c[0], 1, 1, 1),                      # conv_in
+             ("2-D stride 1", 4, b, t, res, res, c[0], c[0], c[0], 1, 1, 1),              # level 0 res blocks
+             ("2-D stride 2", 1, b, t, res, res, c[0], c[0], c[0], 1, 2, 1),              # level 0 Downsample
+             ("2-D stride 1", 1, b, t, r1, r1, c[0], c[0], c[1], 1, 1, 1),
+             ("2-D stride 1", 3, b, t, r1, r1, c[1], c[1], c[1], 1, 1, 1),                # level 1 res blocks
+             ("3x3x3 stride 2", 1, b, t, r1, r1, c[1], c[1], c[1], 3, 2, 2),              # level 1 downsample
+             ("3x3x3 stride 1", 1, b, t1, r2, r2, c[1], c[1], c[2], 3, 1, 1),
+             ("3x3x3 stride 1", 3, b, t1, r2, r2, c[2], c[2], c[2], 3, 1, 1),             # level 2 res blocks
+             ("3x3x3 stride 2", 1, b, t1, r2, r2, c[2], c[2], c[2], 3, 2, 2),             # level 2 downsample
+             ("3x3x3 stride 1", 8, b, t2, r3, r3, c[3], c[3], c[3], 3, 1, 1),             # level 3 + mid res blocks
+             ("3x3x3 stride 1", 1, b, t2, r3, r3, c[3], c[3], 32, 3, 1, 1)]               # conv_out (run with 64 output columns)
+    total_flop = 0.0
+    by_class = {}
+    for cls, n, bb, tt, hh, ww, ci_true, ci, co, kt, s, st in convs:
+        to, ho, wo = (tt - 1) // st + 1, hh // s, ww // s
+        flop = 2.0 * bb * to * ho * wo * co * kt * 9 * ci_true
+        co_run = -(-co // 64) * 64
+        a = torch.randn(bb, tt, hh, ww, ci, device="cuda").bfloat16()
+        wt = (torch.randn(co_run, kt * 9 * ci, device="cuda") / math.sqrt(kt * 9 * ci)).bfloat16()
+        out = torch.empty(bb, to, ho, wo, co_run, device="cuda")
+        if kt == 1 and s == 1:
+            fn = lambda: capi.check(capi.lib.dfot_op_conv3x3_f32(P(a), P(wt), None, None, P(out), bb * tt, hh, ww, ci, co_run, S()))
+        else:
+            fn = lambda: capi.check(capi.lib.dfot_op_conv3t_f32(P(a), P(wt), None, None, P(out), bb, tt, hh, ww, ci, co_run, kt, s, st, S()))
+        cms = timeit(fn)
+        print(f"vae_encode conv {cls:14s} x{n} {bb}x{tt}x{hh}x{ww} {ci_true}->{co} kt={kt} s={s} st={st}: {cms*1e3:8.1f} us  "
+              f"{flop / cms / 1e9:7.1f} TF/s", flush=True)
+        e = by_class.setdefault(cls, [0.0, 0.0])
+        e[0] += n * cms
+        e[1] += n * flop
+        total_flop += n * flop
+    # the rest of the plan: 1x1 shortcuts, attention projections and products, quant_conv
+    other = 2.0 * b * t * r1 * r1 * c[0] * c[1] + 2.0 * b * t1 * r2 * r2 * c[1] * c[2]
+    other += b * t2 * (4 * 2.0 * r3 * r3 * c[3] * c[3] + 2 * 2.0 * (r3 * r3) ** 2 * c[3]) + 2.0 * b * t2 * r3 * r3 * 32 * 32
+    total_flop += other
+    for cls, (cms, flop) in by_class.items():
+        print(f"vae_encode class {cls:14s}: {cms:7.3f} ms per {b} videos  {flop / 1e12:6.3f} TFLOP  {flop / cms / 1e9:7.1f} TF/s  "
+              f"({flop / cms / 1e9 / 2500:.2f} of the 2.5 PF bf16 peak)", flush=True)
+    print(f"vae_encode {b} x {t} x {res}^2: {ms:.3f} ms = {ms / b:.3f} ms per video, {total_flop / b / 1e12:.3f} TFLOP per video, "
+          f"{total_flop / ms / 1e9:.1f} TF/s", flush=True)
+
+
 def main():
     what = sys.argv[1:] or ["gemm", "conv", "attn"]
+    if "vae_encode" in what:
+        vae_encode()
     variants = [int(x) for x in os.environ.get("VARIANTS", "1").split(",")]
     if "gemm" in what:
         for name, (m, n, k) in {"L2 qkv+mlp": (16384, 4032, 576), "L2 out": (16384, 576, 2880), "L3 qkv+mlp": (4096, 8064, 1152),
