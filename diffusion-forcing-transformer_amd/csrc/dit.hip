@@ -432,7 +432,7 @@ __global__ __launch_bounds__(256) void final_layer_kernel(const float* __restric
 
 // hidden = 64 * VEC * CNT with VEC = 2 when hidden % 128 == 0 (8-byte accesses), else 1
 #define DIT_LN_DISPATCH(CALL)                                  \
-  switch (hidden % 128 == 0 ? hidden / 128 : -(hidden / 64)) { \
+  switch (hidden % 128 == 0 ? hidden / 128 : hidden % 64 == 0 ? -(hidden / 64) : 0) { \
     case 1: CALL(2, 1); break;                                 \
     case 2: CALL(2, 2); break;                                 \
     case 3: CALL(2, 3); break;                                 \

@@ -1125,9 +1125,11 @@ int dfot_op_attention(const void* q, const void* k, const void* v, void* o, int 
 }
 
 int dfot_op_f32_to_bf16(const float* src, void* dst, int64_t n, void* stream) {
+  DFOT_REQUIRE(src && dst && n >= 0, DFOT_ERR_ARG, "op_f32_to_bf16: null argument");
   return launch_f32_to_bf16(src, (bf16*)dst, (long)n, (hipStream_t)stream);
 }
 int dfot_op_bf16_to_f32(const void* src, float* dst, int64_t n, void* stream) {
+  DFOT_REQUIRE(src && dst && n >= 0, DFOT_ERR_ARG, "op_bf16_to_f32: null argument");
   return launch_bf16_to_f32((const bf16*)src, dst, (long)n, (hipStream_t)stream);
 }
 

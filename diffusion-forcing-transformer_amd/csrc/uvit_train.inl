@@ -876,6 +876,7 @@ int dfot_op_transpose_bf16(const void* src, void* dst, int rows, int cols, void*
 }
 int dfot_op_colsum_bf16(const void* src, int ld, float* out, int64_t rows, int n, void* stream) {
   DFOT_REQUIRE(src && out, DFOT_ERR_ARG, "op_colsum_bf16: null argument");
+  DFOT_REQUIRE(n > 0 && rows >= 0 && ld >= n, DFOT_ERR_SHAPE, "op_colsum_bf16: %d columns with row stride %d", n, ld);
   hipStream_t s = (hipStream_t)stream;
   DFOT_CHECK_HIP(hipMemsetAsync(out, 0, (size_t)n * sizeof(float), s));
   return launch_colsum_bf16((const bf16*)src, out, (long)rows, n, (long)ld, s);
@@ -927,6 +928,9 @@ int dfot_op_fused_proj_train(const void* a, int lda, const void* w, const float*
 int dfot_op_silu_cols(const void* src, int lds_, int scol0, const void* grad, int ldg, int gcol0, void* dst, int ldd, int dcol0, int64_t rows,
                       int ncols, void* stream) {
   DFOT_REQUIRE(src && dst && ncols % 8 == 0 && scol0 % 8 == 0 && dcol0 % 8 == 0 && gcol0 % 8 == 0, DFOT_ERR_ARG, "op_silu_cols: bad argument");
+  // 16-byte loads and stores at every row: the row strides are multiples of 8 elements too
+  DFOT_REQUIRE(lds_ % 8 == 0 && ldd % 8 == 0 && (!grad || ldg % 8 == 0), DFOT_ERR_SHAPE, "op_silu_cols: row strides %d / %d / %d must be multiples of 8",
+               lds_, ldg, ldd);
   hipLaunchKernelGGL(silu_cols_kernel, dim3(cdiv((long)rows * (ncols / 8), 256)), dim3(256), 0, (hipStream_t)stream, (const bf16*)src, (long)lds_, scol0,
                      (const bf16*)grad, (long)ldg, gcol0, (bf16*)dst, (long)ldd, dcol0, (long)rows, ncols);
   DFOT_CHECK_HIP(hipGetLastError());
@@ -1249,6 +1253,7 @@ int dfot_op_frame_sums_bf16(const void* src, int64_t ld, float* out, int bt, int
 // x fp32 [n] = hi + lo with both parts in bf16 (n % 8 == 0): the operands of a three-product fp32-accurate GEMM on the bf16 matrix cores
 int dfot_op_split_bf16(const float* x, void* hi, void* lo, int64_t n, void* stream) {
   DFOT_REQUIRE(x && hi && lo && n % 8 == 0, DFOT_ERR_ARG, "op_split_bf16: null argument or n not a multiple of 8");
+  DFOT_REQUIRE((((uintptr_t)x | (uintptr_t)hi | (uintptr_t)lo) & 15) == 0, DFOT_ERR_ARG, "op_split_bf16: pointers must be 16-byte aligned");
   hipLaunchKernelGGL(split_bf16_kernel, dim3(cdiv((long)n / 8, 256)), dim3(256), 0, (hipStream_t)stream, x, (bf16*)hi, (bf16*)lo, (long)n / 8);
   DFOT_CHECK_HIP(hipGetLastError());
   return DFOT_OK;
@@ -1286,26 +1291,42 @@ int dfot_op_conv3x3_f32(const void* a, const void* w, const float* bias, const f
   g.bias = bias; g.resid = resid; g.out_f32 = y; g.ldo = cout;
   return launch_gemm(A_CONV3, E_F32, GEMM_AUTO, g, (hipStream_t)stream);
 }
-int dfot_op_pool2_bf16(const float* x, void* out, int bt, int h, int w, int c, void* stream) { return launch_pool2_bf16(x, (bf16*)out, bt, h, w, c, (hipStream_t)stream); }
+// (h, w) of the resampling entries: the fine map's size, except upsample_add (the coarse one); 4 channels per thread
+int dfot_op_pool2_bf16(const float* x, void* out, int bt, int h, int w, int c, void* stream) {
+  DFOT_REQUIRE(x && out, DFOT_ERR_ARG, "op_pool2_bf16: null argument");
+  DFOT_REQUIRE(bt >= 0 && h > 0 && w > 0 && h % 2 == 0 && w % 2 == 0 && c > 0 && c % 4 == 0, DFOT_ERR_SHAPE,
+               "op_pool2_bf16: %d x %d x %d: even sizes and channels a multiple of 4", h, w, c);
+  return launch_pool2_bf16(x, (bf16*)out, bt, h, w, c, (hipStream_t)stream);
+}
 int dfot_op_pool2_bwd(const float* dp, float* dx, int bt, int h, int w, int c, void* stream) {
+  DFOT_REQUIRE(dp && dx, DFOT_ERR_ARG, "op_pool2_bwd: null argument");
   DFOT_REQUIRE(c % 4 == 0, DFOT_ERR_SHAPE, "op_pool2_bwd: channels %d must be a multiple of 4", c);
+  DFOT_REQUIRE(bt >= 0 && h > 0 && w > 0 && h % 2 == 0 && w % 2 == 0 && c > 0, DFOT_ERR_SHAPE, "op_pool2_bwd: %d x %d must be even", h, w);
   const long total = (long)bt * h * w * (c / 4);
   hipLaunchKernelGGL(pool2_bwd_kernel, dim3(cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, dp, dx, total, h, w, c);
   DFOT_CHECK_HIP(hipGetLastError());
   return DFOT_OK;
 }
-int dfot_op_sub_bf16(const float* a, const float* b, void* out, int64_t n, void* stream) { return launch_sub_bf16(a, b, (bf16*)out, (long)n, (hipStream_t)stream); }
+int dfot_op_sub_bf16(const float* a, const float* b, void* out, int64_t n, void* stream) {
+  DFOT_REQUIRE(a && b && out && n >= 0, DFOT_ERR_ARG, "op_sub_bf16: null argument");
+  return launch_sub_bf16(a, b, (bf16*)out, (long)n, (hipStream_t)stream);
+}
 int dfot_op_upsample_add(const float* t, const float* skip, float* out, int bt, int h, int w, int c, void* stream) {
+  DFOT_REQUIRE(t && skip && out, DFOT_ERR_ARG, "op_upsample_add: null argument");
+  DFOT_REQUIRE(bt >= 0 && h > 0 && w > 0 && c > 0 && c % 4 == 0, DFOT_ERR_SHAPE, "op_upsample_add: %d x %d x %d: channels a multiple of 4", h, w, c);
   return launch_upsample_add(t, skip, out, bt, h, w, c, (hipStream_t)stream);
 }
 int dfot_op_upsample_bwd(const float* dy, float* ds, int bt, int h, int w, int c, void* stream) {
+  DFOT_REQUIRE(dy && ds, DFOT_ERR_ARG, "op_upsample_bwd: null argument");
   DFOT_REQUIRE(c % 4 == 0, DFOT_ERR_SHAPE, "op_upsample_bwd: channels %d must be a multiple of 4", c);
+  DFOT_REQUIRE(bt >= 0 && h > 0 && w > 0 && h % 2 == 0 && w % 2 == 0 && c > 0, DFOT_ERR_SHAPE, "op_upsample_bwd: %d x %d must be even", h, w);
   const long total = (long)bt * (h / 2) * (w / 2) * (c / 4);
   hipLaunchKernelGGL(upsample_bwd_kernel, dim3(cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, dy, ds, total, h, w, c);
   DFOT_CHECK_HIP(hipGetLastError());
   return DFOT_OK;
 }
 int dfot_op_axpy(float* a, const float* b, float alpha, int64_t n, void* stream) {
+  DFOT_REQUIRE(a && b && n >= 0, DFOT_ERR_ARG, "op_axpy: null argument");
   const long n4 = ((((uintptr_t)a | (uintptr_t)b) & 15) == 0) ? (long)n / 4 : 0;
   if (n4) hipLaunchKernelGGL(axpy_kernel4, dim3(cdiv(n4, 256)), dim3(256), 0, (hipStream_t)stream, a, b, alpha, n4);
   if (n - 4 * n4) hipLaunchKernelGGL(axpy_kernel, dim3(cdiv((long)n - 4 * n4, 256)), dim3(256), 0, (hipStream_t)stream, a + 4 * n4, b + 4 * n4, alpha, (long)n - 4 * n4);
@@ -1314,22 +1335,33 @@ int dfot_op_axpy(float* a, const float* b, float alpha, int64_t n, void* stream)
 }
 int dfot_op_mul_cols(void* dst, int ldd, int dcol0, const void* mask, int64_t rows, int ncols, void* stream) {
   DFOT_REQUIRE(dst && mask && ncols % 8 == 0 && dcol0 % 8 == 0, DFOT_ERR_ARG, "op_mul_cols: bad argument");
+  DFOT_REQUIRE(ldd % 8 == 0 && ldd >= dcol0 + ncols, DFOT_ERR_SHAPE, "op_mul_cols: row stride %d (columns %d + %d)", ldd, dcol0, ncols);
   hipLaunchKernelGGL(mul_cols_kernel, dim3(cdiv((long)rows * (ncols / 8), 256)), dim3(256), 0, (hipStream_t)stream, (bf16*)dst, (long)ldd, dcol0,
                      (const bf16*)mask, (long)rows, ncols);
   DFOT_CHECK_HIP(hipGetLastError());
   return DFOT_OK;
 }
 int dfot_op_emb_pyramid(const void* emb0, void* emb1, void* emb2, void* emb3, int bt, int r0, int e, void* stream) {
+  DFOT_REQUIRE(emb0 && emb1 && emb2 && emb3, DFOT_ERR_ARG, "op_emb_pyramid: null argument");
   return launch_emb_pyramid((const bf16*)emb0, (bf16*)emb1, (bf16*)emb2, (bf16*)emb3, bt, r0, e, (hipStream_t)stream);
 }
 int dfot_op_cond_repack(const float* cond, void* a, int bt, int res, int cdim, int kpad, void* stream) {
+  DFOT_REQUIRE(cond && a, DFOT_ERR_ARG, "op_cond_repack: null argument");
+  // a patch row holds 4 * cdim values: a shorter row pitch would let each row overwrite the next
+  DFOT_REQUIRE(cdim > 0 && res > 0 && kpad >= 4 * cdim, DFOT_ERR_SHAPE, "op_cond_repack: row pitch %d < 4 x %d", kpad, cdim);
   return launch_cond_repack(cond, (bf16*)a, bt, res, cdim, kpad, (hipStream_t)stream);
 }
 int dfot_op_embed_input(const float* x, const float* w, const float* b, float* out, int bt, int res, int cin, int c0, void* stream) {
+  DFOT_REQUIRE(x && w && b && out, DFOT_ERR_ARG, "op_embed_input: null argument");
+  DFOT_REQUIRE(cin > 0 && c0 > 0, DFOT_ERR_SHAPE, "op_embed_input: %d -> %d channels", cin, c0);
   return launch_embed_input(x, w, b, out, bt, res, cin, c0, (hipStream_t)stream);
 }
 // dW [C0][Cin][p][p] += , db [C0] += of the k = s = p patch embedding (dx0 fp32 [pix][C0], x fp32 [BT][Cin][R][R]); outputs zeroed here
 int dfot_op_embed_input_wgrad(const float* dx0, const float* x, float* dw, float* db, int bt, int res, int cin, int c0, int ps, void* stream) {
+  DFOT_REQUIRE(dx0 && x && dw && db, DFOT_ERR_ARG, "op_embed_input_wgrad: null argument");
+  // the kernel stages 64 patches of cin * ps^2 values in LDS
+  DFOT_REQUIRE(bt > 0 && ps > 0 && res > 0 && res % ps == 0 && cin > 0 && c0 > 0 && cin * ps * ps <= 256, DFOT_ERR_SHAPE,
+               "op_embed_input_wgrad: resolution %d, patch %d, %d input channels", res, ps, cin);
   hipStream_t s = (hipStream_t)stream;
   const long rows = (long)bt * (res / ps) * (res / ps);
   const int kdim = cin * ps * ps;
@@ -1350,9 +1382,13 @@ int dfot_op_embed_input_dgrad(const float* dx0, const float* w, float* dx, int b
   return DFOT_OK;
 }
 int dfot_op_project_output(const float* x0, const float* w, const float* b, float* out, int bt, int res, int c0, int cout, void* stream) {
+  DFOT_REQUIRE(x0 && w && b && out, DFOT_ERR_ARG, "op_project_output: null argument");
+  DFOT_REQUIRE(cout > 0 && c0 > 0 && res % 2 == 0, DFOT_ERR_SHAPE, "op_project_output: %d -> %d channels at resolution %d", c0, cout, res);
   return launch_project_output(x0, w, b, out, bt, res, c0, cout, (hipStream_t)stream);
 }
 int dfot_op_outgrad_gather(const float* dout, void* dpatch, int bt, int res, int cout, int ps, void* stream) {
+  DFOT_REQUIRE(dout && dpatch, DFOT_ERR_ARG, "outgrad_gather: null argument");
+  DFOT_REQUIRE(ps > 0 && res % ps == 0 && cout > 0, DFOT_ERR_SHAPE, "outgrad_gather: resolution %d, patch %d", res, ps);
   hipStream_t s = (hipStream_t)stream;
   const long pix = (long)bt * (res / ps) * (res / ps);
   DFOT_REQUIRE(cout * ps * ps <= 64, DFOT_ERR_SHAPE, "outgrad_gather: more than 64 output values per pixel");

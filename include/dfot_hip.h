@@ -387,8 +387,9 @@ int dfot_op_attention_fwd_lse(const void* q, const void* k, const void* v, void*
 int dfot_op_attention_bwd_lse(const void* q, const void* k, const void* v, const void* o, const void* d_o, int ldo, const float* lse, float* delta,
                               void* dq, void* dk, void* dv, int batch, int heads, int n, int d, void* stream);
 /* ResBlock / resampler / embedding pieces of the UViT training driver (channels-last fp32 streams, bf16 GEMM operands).
- * Shape contract of the vectorised kernels: GroupNorm entries take 128, 256, 512 or 1024 channels; pool2_bwd / upsample_bwd channels
- * % 4 == 0; frame sums / split_bf16 lengths % 8 == 0 (anything else returns DFOT_ERR_SHAPE). */
+ * Shape contract of the vectorised kernels: GroupNorm entries take 128, 256, 512 or 1024 channels; pool2_bf16 / pool2_bwd / upsample_add /
+ * upsample_bwd channels % 4 == 0 and, except upsample_add (which takes the coarse size), even h and w; frame sums / split_bf16 lengths
+ * % 8 == 0, split_bf16 pointers 16-byte aligned; cond_repack kpad >= 4 cdim (anything else returns DFOT_ERR_SHAPE or DFOT_ERR_ARG). */
 int dfot_op_gn_silu_fwd(const float* x, const float* gamma, const float* beta, const void* film, float eps, void* out, float* stats, int bt,
                         int pixels, int channels, void* stream);
 

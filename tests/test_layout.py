@@ -131,3 +131,61 @@ def test_no_kernel_spills_registers(tmp_path):
                 offenders.append((fn, m.group(1)[:80], int(sp.group(1))))
         assert names
     assert not offenders, offenders
+
+
+def _header_prototypes():
+    """name -> (return type, [argument declarations]) of every function include/dfot_hip.h declares (comments stripped)"""
+    hdr = open(os.path.join(ROOT, "include", "dfot_hip.h")).read()
+    hdr = re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S)
+    hdr = re.sub(r"//[^\n]*", " ", hdr)
+    protos = {}
+    for m in re.finditer(r"([A-Za-z_][A-Za-z0-9_ ]*?\**)\s*\b(dfot_[a-z0-9_]+)\s*\(([^;{]*?)\)\s*;", hdr, re.S):
+        args = " ".join(m.group(3).split())
+        protos[m.group(2)] = (" ".join(m.group(1).split()), [] if args in ("", "void") else [a.strip() for a in args.split(",")])
+    return protos
+
+
+def _ctype_of(decl):
+    """the ctypes class a C declaration ("const float* x", "int64_t n", "dfot_uvit_t h", "const char*") must be bound with; 'ptr' for any pointer
+    (array parameters included)"""
+    words = decl.replace("*", " * ").split()
+    if "*" in words or "[" in decl or words[0].endswith("_t") and words[0].startswith("dfot_"):  # the handle typedefs are struct pointers
+        return "ptr"
+    base = [w for w in words if w not in ("const", "unsigned")]
+    return {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "float": ctypes.c_float, "double": ctypes.c_double,
+            "size_t": ctypes.c_size_t}[base[0]]
+
+
+def _is_pointer_ctype(t):
+    return t in (ctypes.c_void_p, ctypes.c_char_p) or (isinstance(t, type) and issubclass(t, ctypes._Pointer))
+
+
+def test_ctypes_signatures_match_the_header_prototypes_argument_by_argument():
+    """capi.SIGNATURES binds every entry point with the header's argument list: same count, int -> c_int, int64_t -> c_int64, float ->
+    c_float, size_t -> c_size_t, any pointer -> c_void_p / c_char_p / POINTER.  A mismatch passes garbage through ctypes silently
+    (an int64_t bound as c_int truncates; a float bound as c_int reinterprets)."""
+    from dfot_amd import capi
+    protos = _header_prototypes()
+    assert set(protos) == set(capi.SIGNATURES), set(protos) ^ set(capi.SIGNATURES)
+    bad = []
+    for name, (ret, args) in sorted(protos.items()):
+        res, argtypes = capi.SIGNATURES[name]
+        if len(args) != len(argtypes):
+            bad.append(f"{name}: {len(args)} arguments in the header, {len(argtypes)} bound")
+            continue
+        for i, (decl, bound) in enumerate(zip(args + [ret], list(argtypes) + [res])):
+            want = _ctype_of(decl)
+            ok = _is_pointer_ctype(bound) if want == "ptr" else bound is want
+            if not ok:
+                bad.append(f"{name} {'return' if i == len(args) else f'argument {i}'} `{decl}` bound as {getattr(bound, '__name__', bound)}")
+    assert not bad, "\n".join(bad)
+
+
+def test_every_op_entry_point_is_named_by_a_test():
+    """every dfot_op_* symbol of the header is called (named) in at least one tests/test_*.py file: a new entry point cannot land untested"""
+    names = sorted(n for n in _header_prototypes() if n.startswith("dfot_op_"))
+    assert len(names) >= 60
+    tdir = os.path.join(ROOT, "tests")
+    text = "\n".join(open(os.path.join(tdir, f)).read() for f in sorted(os.listdir(tdir)) if f.startswith("test_") and f.endswith(".py"))
+    untested = [n for n in names if not re.search(r"\b" + n + r"\b", text)]
+    assert not untested, untested
