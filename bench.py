@@ -6,12 +6,15 @@ x_shape [3,256,256], context 1 frame, 50 DDIM steps, vanilla history guidance 4.
 7 generated frames) on synthetic latents and seeded random-init weights.  With --gpus N every rank samples
 its own video (independent units, no data-path collective; weak scaling); value = frames of all ranks / max time.
 
-Also reports on rank 0:
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line, nothing more.  With --full it also
+reports on rank 0:
   roofline     dominant kernel = level-2 flash attention (N=8192, d=64, 18 (batch,head) units per launch);
                algorithmic FLOPs per launch = 4*N^2*d*heads*Bm = 309.2 GFLOP, duration = HIP events
-               recorded on the launch stream around every such launch inside the timed region.
+               recorded on the launch stream around every such launch (hipGraph mode: one eager sample after the timed
+               region; the eager step loop is event-timed inside the timed region with or without --full).
   cpu_baseline the CPU oracle (oracle/, a plain-PyTorch fp32 port of the reference path) timed on the host cores on a
                bounded sample (one window-forward), converted to frames/s of the same workload.
+  extra        short labelled runs of the other BASELINE configurations and A/B modes, each a fresh worker process.
 """
 from __future__ import annotations
 
@@ -37,6 +40,8 @@ GRAPH_DEFAULT = True  # sampler mode of the headline line: the north_star's hipG
 # travel to the GPU box, so the figure is quoted next to the oracle ("port") timing taken on the box itself
 REFERENCE_SOURCE_CPU = {"seconds_per_window_forward": 20.9, "threads": 8, "host": "build container (8 vCPU Xeon 2.1 GHz), torch 2.10 CPU, fp32",
                         "how": "tools/time_reference_cpu.py: UViT3DPose.forward of the reference's source, Bm=1, T=8, 256x256"}
+# roofline.source of a plain run in hipGraph mode: the attention launches are only event-timed in an eager pass of their own
+ROOFLINE_NOT_MEASURED = "not measured: hipGraph step loop; --full adds an eager pass of one sample after the timed region"
 
 
 DUMP_LIMIT = 64_000_000  # bytes on disk: all files of one --dump-outputs together, .npy headers included
@@ -338,7 +343,8 @@ def bench_k600(args, rank, world, dist):
         dt = float(tmax.item())
     fwd = sampler.window_forwards
     roofline_source = "HIP events around every attention launch inside the timed region (eager step loop)"
-    if use_graph and rank == 0:  # the same kernels launched eagerly once more, bracketed by events (not part of `value`)
+    unmeasured = ROOFLINE_NOT_MEASURED if use_graph and not args.full else None
+    if use_graph and rank == 0 and args.full:  # the same kernels launched eagerly once more, bracketed by events (not part of `value`)
         sampler.use_graph = False
         model.set_option("time_attn", args.sampling_steps * 28)
         run()
@@ -377,12 +383,12 @@ def bench_k600(args, rank, world, dist):
                                                       "attn_kernel_v2<128,2,80,96> (DiT attention, N=1280, head dim 72 in 128-wide rows)"),
                          "achieved": achieved, "peak": 2500.0, "unit": "TFLOP/s", "frac": achieved / 2500.0 if achieved else None,
                          "traffic": k600_traffic(diff, b), "launches": attn_n, "avg_launch_ms": attn_ms / max(attn_n, 1),
-                         "flop_per_launch": flop_per_launch, "source": roofline_source if attn_n else None},
+                         "flop_per_launch": flop_per_launch, "source": roofline_source if attn_n else unmeasured},
             "sampler_mode": "hipgraph" if use_graph else "eager",
         }
         if dumped:
             line["dumped_outputs"] = dumped
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             from oracle import dit as odit
             cores = min(16, os.cpu_count() or 1)
             torch.set_num_threads(cores)
@@ -445,8 +451,9 @@ def extra_jobs(args, world: int) -> dict:
 
 
 def coordinate(args):
-    """The process the driver starts (one per rank under `torch.distributed.run`, or the single `python bench.py`).  It NEVER touches
-    the GPU: the headline and every extra run as fresh `--worker` children, one after the other, so each starts on a clean device and a
+    """`--full` on the default workload: the process started (one per rank under `torch.distributed.run`, or the single
+    `python bench.py --full`).  It NEVER touches the GPU: the headline and every extra run as fresh `--worker` children, one after the
+    other, so each starts on a clean device and a
     failing or hanging extra cannot cost the headline line.  With N > 1 ranks the N coordinators agree on one rendezvous port per job
     over a CPU (gloo) group and keep in step with barriers; rank 0 assembles and prints the ONE JSON line."""
     import datetime
@@ -471,7 +478,7 @@ def coordinate(args):
         box = [ports]
         cdist.broadcast_object_list(box, src=0)
         ports = box[0]
-    base = [sys.executable, os.path.abspath(__file__), "--worker", "--sampling-steps", str(args.sampling_steps), "--res", str(args.res)] + \
+    base = [sys.executable, os.path.abspath(__file__), "--worker", "--full", "--sampling-steps", str(args.sampling_steps), "--res", str(args.res)] + \
            (["--dry-run"] if args.dry_run else [])
     # a child is a rank of ITS OWN job: same RANK / WORLD_SIZE, a fresh port, nothing of the launcher's agent-store settings
     env0 = {k: v for k, v in os.environ.items() if not k.startswith("TORCHELASTIC_") and k not in ("GROUP_RANK", "ROLE_RANK", "ROLE_WORLD_SIZE")}
@@ -593,8 +600,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--res", type=int, default=256)
     ap.add_argument("--sampling-steps", type=int, default=50)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="8f only: skip the short runs of the other BASELINE configs appended under 'extra'")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: cpu_baseline, the roofline's eager pass in hipGraph mode and (8f) the short runs of "
+                         "the other BASELINE configs under 'extra'.  Without it a run only sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full, 8f only: skip the short runs of the other BASELINE configs appended under 'extra'")
     ap.add_argument("--worker", action="store_true", help="internal: this process IS a rank of one workload (started by the coordinator)")
     ap.add_argument("--graph", action="store_true", help="hipGraph step loop (the default): all remaining DDIM steps of a window as ONE graph")
     ap.add_argument("--eager", action="store_true", help="force the eager step loop (A/B against the default)")
@@ -620,8 +630,8 @@ def main():
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
-    if not args.worker and args.workload == "8f" and not args.no_extras:
-        # the driver's command: headline (config 2) + the other BASELINE configs, each a fresh worker process of its own
+    if args.full and not args.worker and args.workload == "8f" and not args.no_extras:
+        # headline (config 2) + the other BASELINE configs, each a fresh worker process of its own
         return coordinate(args)
     dev = "cpu" if args.dry_run else "cuda"
     if not args.dry_run:
@@ -726,7 +736,8 @@ def main():
     fwd = sampler.window_forwards
     roofline_source = "HIP events around every level-2 attention launch inside the timed region (eager step loop)"
     roofline_fwd = fwd
-    if model is not None and sampler.use_graph and rank == 0 and not long_rollout:
+    unmeasured = ROOFLINE_NOT_MEASURED if model is not None and sampler.use_graph and not long_rollout and not args.full else None
+    if model is not None and sampler.use_graph and rank == 0 and not long_rollout and args.full:
         # the same kernels, launched eagerly once more so that they can be bracketed by events (not part of `value`)
         sampler.use_graph = False
         model.set_option("time_attn", attn_per_sample)
@@ -780,7 +791,7 @@ def main():
                          "achieved": achieved, "peak": 2500.0, "unit": "TFLOP/s",
                          "frac": achieved / 2500.0 if achieved else None, "traffic": traffic, "traffic_source": traffic_source,
                          "launches": attn_n, "avg_launch_ms": attn_ms / max(attn_n, 1),
-                         "flop_per_launch": flop_per_launch, "source": roofline_source if attn_n else None},
+                         "flop_per_launch": flop_per_launch, "source": roofline_source if attn_n else unmeasured},
             # which level-2 attention kernel these weights got and why: the fast kernel needs the bound below 64
             "attention_kernel": kname, "score_bound": model.query("score_bound_l2") if model is not None else None,
         }
@@ -788,7 +799,7 @@ def main():
             line["keyframe_phase"] = (f"{world // 2} rank pair(s) each evaluate the two History-Guidance branches of the sequential key-frame windows; "
                                       "pairs beyond the first repeat the first pair's work (replicated state, no broadcast) -- that phase does not "
                                       "scale past 2 ranks" + ("" if world % 2 == 0 else "; odd world: no branch split, every rank evaluates both branches"))
-        if not args.no_cpu_baseline and world == 1 and not args.dry_run:  # reported baseline: rank 0 at N=1 only
+        if args.full and not args.no_cpu_baseline and world == 1 and not args.dry_run:  # reported baseline: rank 0 at N=1 only
             line["cpu_baseline"] = cpu_baseline(res, 1, frames_per_sample, fwd // args.steps)
         line["sampler_mode"] = "dry-run (host plumbing only, nothing launched)" if args.dry_run else ("hipgraph" if sampler.use_graph else "eager")
         if sampler.use_graph and not args.dry_run:  # captures paid (once per window shape) and steps replayed, warm-up included

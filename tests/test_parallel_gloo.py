@@ -329,17 +329,17 @@ def test_bench_gpus_flag_starts_the_ranks():
 
 @pytest.mark.timeout(900)
 def test_bench_driver_command_measures_the_sharded_workloads():
-    """the driver's multi-GPU command is `bench.py --gpus N` with the DEFAULT workload.  Its line must carry, next
-    to the weak-scaling 8f headline, the workloads whose N-rank form is not N replicas: `extra.200f` (sharded windows, branch split,
-    ranks bit-identical) with n_gpus = N, and `extra.train_re10k` (here: marked skipped, the dry run has no device).  Rank processes
-    are coordinators that never touch the GPU; headline and extras are fresh worker processes with their own rendezvous."""
+    """`bench.py --gpus N --full` with the DEFAULT workload.  Its line must carry, next to the weak-scaling 8f
+    headline, the workloads whose N-rank form is not N replicas: `extra.200f` (sharded windows, branch split, ranks bit-identical)
+    with n_gpus = N, and `extra.train_re10k` (here: marked skipped, the dry run has no device).  Rank processes are coordinators
+    that never touch the GPU; headline and extras are fresh worker processes with their own rendezvous."""
     import json
     import subprocess
     import sys
     from conftest import ROOT
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--res", "64", "--sampling-steps", "2", "--dry-run",
-                        "--steps", "1", "--warmup", "0"], capture_output=True, text=True, timeout=800, env=env)
+                        "--full", "--steps", "1", "--warmup", "0"], capture_output=True, text=True, timeout=800, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     rows = [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(rows) == 1
@@ -351,3 +351,25 @@ def test_bench_driver_command_measures_the_sharded_workloads():
     assert ex["200f"]["n_gpus"] == 2 and ex["200f"]["rccl_ranks"] == 2 and ex["200f"]["ranks_bit_identical"] is True
     assert ex["200f"]["scaling"] == "strong" and "keyframe_phase" in ex["200f"]
     assert "skipped" in ex["train_re10k"]
+
+
+@pytest.mark.timeout(600)
+def test_bench_plain_run_is_the_headline_alone():
+    """Without `--full` the default command does only what its headline needs: the rank processes ARE the 8f workers (no
+    coordinator, no extras) and the line carries the headline fields but no `extra` and no `cpu_baseline`."""
+    import json
+    import subprocess
+    import sys
+    from conftest import ROOT
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--res", "64", "--sampling-steps", "2", "--dry-run",
+                        "--steps", "1", "--warmup", "0"], capture_output=True, text=True, timeout=500, env=env)
+    assert r.returncode == 0, r.stderr[-2000:]
+    rows = [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(rows) == 1
+    line = rows[0]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in line, k
+    assert line["n_gpus"] == 2 and line["scaling"] == "weak" and line["rccl_ranks"] == 2 and line["steps"] == 1 and line["warmup"] == 0
+    assert line["config"]["frames_per_step"] == 7 and abs(line["value"] * line["ms_per_step"] / 1e3 - 14) < 1e-6  # two videos
+    assert "extra" not in line and "cpu_baseline" not in line
