@@ -13,22 +13,11 @@
 // V^T fragment is fetched in that same order by two ds_read_b64_tr_b16 per step
 // (cdna_hip_programming.md section 3 "accumulator tile as the next MFMA's operand", T10).
 // Scores are in the exp2 domain: the caller folds log2(e)/sqrt(d) into q.
-#include "common.h"
+#include "attention_common.h"
 #include "dfot_hip.h"
 #include "kernels.h"
 
 namespace dfot {
-
-template <int D>
-struct AttnCfg {
-  static constexpr int KV = 64;                  // keys per tile
-  static constexpr int ROWB = D * 2;             // bytes per K/V row in LDS
-  static constexpr int TILE = KV * ROWB;         // bytes of one K or V tile
-  static constexpr int CH = D / 8;               // 16-byte chunks per row
-  static constexpr int PER_THREAD = KV * CH / 256;
-  __device__ static int swz_k(int row, int c) { return D == 64 ? (c ^ ((row >> 1) & 7)) : (c ^ (row & 15)); }
-  __device__ static int swz_v(int row, int c) { return D == 64 ? (c ^ (((row >> 1) & 1) << 2)) : (c ^ ((row & 3) << 2)); }
-};
 
 template <int D, bool USE_TR>
 __global__ __launch_bounds__(256) void attn_kernel(const bf16* __restrict__ Q, const bf16* __restrict__ K,
@@ -143,19 +132,7 @@ __global__ __launch_bounds__(256) void attn_kernel(const bf16* __restrict__ Q, c
         for (int s = 0; s < 2; ++s) {
           bf16x8 vf;
           if constexpr (USE_TR) {
-            // 16-lane group gi=lane>>4 reads the 4x16 block rows kb+{0..3}, cols dvt*32 + 16*(gi&1) + {0..15};
-            // lane 4q+p of the group supplies row q, columns 4p..4p+3
-            const int kb = kt2 * 32 + 16 * s + 4 * lh;
-            const int q4 = (lane & 15) >> 2, p4 = lane & 3;
-            const int col = dvt * 32 + 16 * ((lane >> 4) & 1) + 4 * p4;
-            const int r0 = kb + q4, r1 = kb + 8 + q4;
-            const char* a0 = sv + r0 * C::ROWB + C::swz_v(r0, col >> 3) * 16 + (col & 7) * 2;
-            const char* a1 = sv + r1 * C::ROWB + C::swz_v(r1, col >> 3) * 16 + (col & 7) * 2;
-            const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-                (bf16x4 __attribute__((address_space(3)))*)(a0));
-            const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-                (bf16x4 __attribute__((address_space(3)))*)(a1));
-            vf = bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+            vf = tr_frag_v<D>(sv, dvt, kt2, s, lane);
           } else {
             const int dv = dvt * 32 + lq;
 #pragma unroll
@@ -187,22 +164,6 @@ __global__ __launch_bounds__(256) void attn_kernel(const bf16* __restrict__ Q, c
       for (int j = 0; j < 4; ++j) o4[j] = f2bf(oacc[dvt][4 * g4 + j] * inv);
       *reinterpret_cast<bf16x4*>(orow + dvt * 32 + 8 * g4 + 4 * lh) = o4;
     }
-}
-
-typedef __attribute__((ext_vector_type(2))) unsigned v2_u32x2;
-template <int OFF>
-__device__ __forceinline__ v2_u32x2 v2_read_tr16(unsigned addr) {
-  v2_u32x2 r;
-  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(r) : "v"(addr), "n"(OFF));
-  return r;
-}
-__device__ __forceinline__ void v2_lds_wait(v2_u32x2& a, v2_u32x2& b, v2_u32x2& c, v2_u32x2& d, v2_u32x2& e, v2_u32x2& f, v2_u32x2& g, v2_u32x2& h) {
-  asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e), "+v"(f), "+v"(g), "+v"(h));
-}
-__device__ __forceinline__ bf16x8 v2_bf16x8(v2_u32x2 lo, v2_u32x2 hi) {
-  typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-  const u32x4 v = {lo[0], lo[1], hi[0], hi[1]};
-  return __builtin_bit_cast(bf16x8, v);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -372,9 +333,8 @@ __global__ __launch_bounds__(256, QRELOAD ? 4 : 1) void attn_kernel_v2(const bf1
     l_i += rs;
 
     // ---- O^T += V^T P^T ----
-    // V^T fragments by ds_read_b64_tr_b16 through inline asm: hipcc puts `s_waitcnt vmcnt(0)` in front of the builtin form while an
-    // LDS-DMA is in flight (it cannot see that the prefetched stage is another one), which drained the K/V ring at this point of every
-    // tile.  The bank swizzle depends on q4 only, so one base address per lane and 32-column block; (kt2, s, +8) are immediate offsets.
+    // V^T fragments by the inline-asm form of the transposed read (lds_read_tr16, common.h: an LDS-DMA is in flight here).  The bank
+    // swizzle depends on q4 only, so one base address per lane and 32-column block; (kt2, s, +8) are immediate offsets.
     if (prio) __builtin_amdgcn_s_setprio(1);
     if constexpr (QRELOAD) {  // the 128-VGPR experiment keeps the builtin reads (the asm form's eight live results cost it spills)
 #pragma unroll
@@ -382,18 +342,8 @@ __global__ __launch_bounds__(256, QRELOAD ? 4 : 1) void attn_kernel_v2(const bf1
 #pragma unroll
         for (int kt2 = 0; kt2 < 2; ++kt2)
 #pragma unroll
-          for (int s = 0; s < 2; ++s) {
-            const int kb = kt2 * 32 + 16 * s + 4 * lh;
-            const int q4 = (lane & 15) >> 2, p4 = lane & 3;
-            const int col = dvt * 32 + 16 * ((lane >> 4) & 1) + 4 * p4;
-            const int r0 = kb + q4, r1 = kb + 8 + q4;
-            const char* a0 = sv + r0 * C::ROWB + C::swz_v(r0, col >> 3) * 16 + (col & 7) * 2;
-            const char* a1 = sv + r1 * C::ROWB + C::swz_v(r1, col >> 3) * 16 + (col & 7) * 2;
-            const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((bf16x4 __attribute__((address_space(3)))*)(a0));
-            const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((bf16x4 __attribute__((address_space(3)))*)(a1));
-            const bf16x8 vf = bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-            oacc[dvt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pf[kt2][s], oacc[dvt], 0, 0, 0);
-          }
+          for (int s = 0; s < 2; ++s)
+            oacc[dvt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_frag_v<D>(sv, dvt, kt2, s, lane), pf[kt2][s], oacc[dvt], 0, 0, 0);
     } else {
   #pragma unroll
       for (int dvt = 0; dvt < DV / 32; ++dvt) {
@@ -401,15 +351,15 @@ __global__ __launch_bounds__(256, QRELOAD ? 4 : 1) void attn_kernel_v2(const bf1
         const int col = dvt * 32 + 16 * ((lane >> 4) & 1) + 4 * p4;
         const int r0 = 4 * lh + q4;
         const unsigned va = (unsigned)(size_t)DFOT_LDS_PTR(sv) + r0 * C::ROWB + C::swz_v(r0, col >> 3) * 16 + (col & 7) * 2;
-        v2_u32x2 r000 = v2_read_tr16<0 * C::ROWB>(va), r001 = v2_read_tr16<8 * C::ROWB>(va);
-        v2_u32x2 r010 = v2_read_tr16<16 * C::ROWB>(va), r011 = v2_read_tr16<24 * C::ROWB>(va);
-        v2_u32x2 r100 = v2_read_tr16<32 * C::ROWB>(va), r101 = v2_read_tr16<40 * C::ROWB>(va);
-        v2_u32x2 r110 = v2_read_tr16<48 * C::ROWB>(va), r111 = v2_read_tr16<56 * C::ROWB>(va);
-        v2_lds_wait(r000, r001, r010, r011, r100, r101, r110, r111);
-        oacc[dvt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(v2_bf16x8(r000, r001), pf[0][0], oacc[dvt], 0, 0, 0);
-        oacc[dvt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(v2_bf16x8(r010, r011), pf[0][1], oacc[dvt], 0, 0, 0);
-        oacc[dvt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(v2_bf16x8(r100, r101), pf[1][0], oacc[dvt], 0, 0, 0);
-        oacc[dvt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(v2_bf16x8(r110, r111), pf[1][1], oacc[dvt], 0, 0, 0);
+        u32x2 r000 = lds_read_tr16<0 * C::ROWB>(va), r001 = lds_read_tr16<8 * C::ROWB>(va);
+        u32x2 r010 = lds_read_tr16<16 * C::ROWB>(va), r011 = lds_read_tr16<24 * C::ROWB>(va);
+        u32x2 r100 = lds_read_tr16<32 * C::ROWB>(va), r101 = lds_read_tr16<40 * C::ROWB>(va);
+        u32x2 r110 = lds_read_tr16<48 * C::ROWB>(va), r111 = lds_read_tr16<56 * C::ROWB>(va);
+        lds_wait(r000, r001, r010, r011, r100, r101, r110, r111);
+        oacc[dvt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(r000, r001), pf[0][0], oacc[dvt], 0, 0, 0);
+        oacc[dvt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(r010, r011), pf[0][1], oacc[dvt], 0, 0, 0);
+        oacc[dvt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(r100, r101), pf[1][0], oacc[dvt], 0, 0, 0);
+        oacc[dvt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(r110, r111), pf[1][1], oacc[dvt], 0, 0, 0);
       }
     }
     if (prio) __builtin_amdgcn_s_setprio(0);
@@ -448,14 +398,10 @@ __global__ __launch_bounds__(256, QRELOAD ? 4 : 1) void attn_kernel_v2(const bf1
 template <int D, int NST, int DQK = D, int DV = D, bool QRELOAD = false>
 static int launch_attn_v2(const bf16* q, const bf16* k, const bf16* v, bf16* o, long ldo, int batch, int heads, int n,
                           hipStream_t stream, int ohs = D, int dvalid = D, float* lse = nullptr) {
-  auto kern = attn_kernel_v2<D, NST, DQK, DV, QRELOAD>;
+  constexpr auto kern = attn_kernel_v2<D, NST, DQK, DV, QRELOAD>;
   constexpr int xcd_flag = 1 | 2;  // bit 0: XCD-aware tile order, bit 1: s_setprio around the MFMA clusters (+1-2 %): both always on
   const int lds = 2 * NST * AttnCfg<D>::TILE;
-  static bool attr_set = false;
-  if (!attr_set) {
-    DFOT_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    attr_set = true;
-  }
+  if (int rc = ensure_dyn_lds<kern>(lds)) return rc;
   const int tiles = (n / 128) * batch * heads;
   hipLaunchKernelGGL(kern, dim3(tiles), dim3(256), lds, stream, q, k, v, o, ldo, n, heads, xcd_flag, ohs, dvalid, lse);
   DFOT_CHECK_HIP(hipGetLastError());
@@ -465,13 +411,9 @@ static int launch_attn_v2(const bf16* q, const bf16* k, const bf16* v, bf16* o, 
 template <int D, bool TR>
 static int launch_attn_t(const bf16* q, const bf16* k, const bf16* v, bf16* o, long ldo, int batch, int heads, int n,
                          hipStream_t stream) {
-  auto kern = attn_kernel<D, TR>;
+  constexpr auto kern = attn_kernel<D, TR>;
   const int lds = 4 * AttnCfg<D>::TILE;
-  static bool attr_set = false;
-  if (!attr_set) {
-    DFOT_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    attr_set = true;
-  }
+  if (int rc = ensure_dyn_lds<kern>(lds)) return rc;
   hipLaunchKernelGGL(kern, dim3(n / 128, batch * heads), dim3(256), lds, stream, q, k, v, o, ldo, n, heads);
   DFOT_CHECK_HIP(hipGetLastError());
   return DFOT_OK;

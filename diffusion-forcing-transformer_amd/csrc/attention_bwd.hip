@@ -326,21 +326,6 @@ struct DmaCfg {
   }
 };
 
-typedef __attribute__((ext_vector_type(2))) unsigned bw_u32x2;
-template <int OFF>
-__device__ __forceinline__ bw_u32x2 bw_read_tr16(unsigned addr) {
-  bw_u32x2 r;
-  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(r) : "v"(addr), "n"(OFF));
-  return r;
-}
-__device__ __forceinline__ void bw_wait(bw_u32x2& a, bw_u32x2& b, bw_u32x2& c, bw_u32x2& d, bw_u32x2& e, bw_u32x2& f, bw_u32x2& g, bw_u32x2& h) {
-  asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e), "+v"(f), "+v"(g), "+v"(h));
-}
-__device__ __forceinline__ bf16x8 bw_bf16x8(bw_u32x2 lo, bw_u32x2 hi) {
-  typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-  const u32x4 v = {lo[0], lo[1], hi[0], hi[1]};
-  return __builtin_bit_cast(bf16x8, v);
-}
 // byte offset inside a tile of this lane's transposed read for the feature block dvt (32 features) and row half h (rows 8h..): rows
 // 4 lh + 8 h + q4 (+ 16 s + 32 kt2 as an immediate: multiples of 16 rows leave the swizzle unchanged)
 template <int D>
@@ -351,20 +336,20 @@ __device__ __forceinline__ unsigned bw_tr_off(int dvt, int h, int lane) {
   const int chunk = 4 * dvt + 2 * g + (p4 >> 1);
   return (unsigned)(row * C::ROWB + C::swz(row, chunk) * 16 + (p4 & 1) * 8);
 }
-// the four X^T fragments (kt2, s) of feature block dvt of one tile
+// the four X^T fragments (kt2, s) of feature block dvt of one tile (inline-asm reads: an LDS-DMA is in flight, see lds_read_tr16 in common.h)
 template <int D>
 __device__ __forceinline__ void bw_tr_frags(unsigned tile_addr, int dvt, int lane, bf16x8 (&f)[2][2]) {
   using C = DmaCfg<D>;
   const unsigned a0 = tile_addr + bw_tr_off<D>(dvt, 0, lane), a1 = tile_addr + bw_tr_off<D>(dvt, 1, lane);
-  bw_u32x2 r000 = bw_read_tr16<0 * C::ROWB>(a0), r001 = bw_read_tr16<0 * C::ROWB>(a1);
-  bw_u32x2 r010 = bw_read_tr16<16 * C::ROWB>(a0), r011 = bw_read_tr16<16 * C::ROWB>(a1);
-  bw_u32x2 r100 = bw_read_tr16<32 * C::ROWB>(a0), r101 = bw_read_tr16<32 * C::ROWB>(a1);
-  bw_u32x2 r110 = bw_read_tr16<48 * C::ROWB>(a0), r111 = bw_read_tr16<48 * C::ROWB>(a1);
-  bw_wait(r000, r001, r010, r011, r100, r101, r110, r111);
-  f[0][0] = bw_bf16x8(r000, r001);
-  f[0][1] = bw_bf16x8(r010, r011);
-  f[1][0] = bw_bf16x8(r100, r101);
-  f[1][1] = bw_bf16x8(r110, r111);
+  u32x2 r000 = lds_read_tr16<0 * C::ROWB>(a0), r001 = lds_read_tr16<0 * C::ROWB>(a1);
+  u32x2 r010 = lds_read_tr16<16 * C::ROWB>(a0), r011 = lds_read_tr16<16 * C::ROWB>(a1);
+  u32x2 r100 = lds_read_tr16<32 * C::ROWB>(a0), r101 = lds_read_tr16<32 * C::ROWB>(a1);
+  u32x2 r110 = lds_read_tr16<48 * C::ROWB>(a0), r111 = lds_read_tr16<48 * C::ROWB>(a1);
+  lds_wait(r000, r001, r010, r011, r100, r101, r110, r111);
+  f[0][0] = as_bf16x8(r000, r001);
+  f[0][1] = as_bf16x8(r010, r011);
+  f[1][0] = as_bf16x8(r100, r101);
+  f[1][1] = as_bf16x8(r110, r111);
 }
 
 template <int D, int DC = D, int DW = D>
@@ -762,12 +747,8 @@ static int launch_bwd_t(const bf16* q, const bf16* k, const bf16* v, const bf16*
   if (dma == 2 || (dma == 1 && D == 128)) {
     using C = DmaCfg<D>;
     const int lds1 = 4 * C::TILE, lds2 = 2 * (2 * C::TILE + 2 * C::TR * 4);
-    static bool attr_set = false;
-    if (!attr_set) {
-      DFOT_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_dq_dma_kernel<D, DC, DW>), hipFuncAttributeMaxDynamicSharedMemorySize, lds1));
-      DFOT_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_dkv_dma_kernel<D, DC, DW>), hipFuncAttributeMaxDynamicSharedMemorySize, lds2));
-      attr_set = true;
-    }
+    if (int rc = ensure_dyn_lds<attn_bwd_dq_dma_kernel<D, DC, DW>>(lds1)) return rc;
+    if (int rc = ensure_dyn_lds<attn_bwd_dkv_dma_kernel<D, DC, DW>>(lds2)) return rc;
     if (!g_bwd_zeros) {
       void* z = nullptr;
       DFOT_CHECK_HIP(hipMalloc(&z, 256));
@@ -783,12 +764,8 @@ static int launch_bwd_t(const bf16* q, const bf16* k, const bf16* v, const bf16*
   }
   using C = BwdCfg<D>;
   const int lds1 = 4 * C::TILE, lds2 = 2 * (2 * C::TILE + 2 * C::TR * 4);
-  static bool attr_set = false;
-  if (!attr_set) {
-    DFOT_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_dq_kernel<D, DC, DW>), hipFuncAttributeMaxDynamicSharedMemorySize, lds1));
-    DFOT_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_dkv_kernel<D, DC, DW>), hipFuncAttributeMaxDynamicSharedMemorySize, lds2));
-    attr_set = true;
-  }
+  if (int rc = ensure_dyn_lds<attn_bwd_dq_kernel<D, DC, DW>>(lds1)) return rc;
+  if (int rc = ensure_dyn_lds<attn_bwd_dkv_kernel<D, DC, DW>>(lds2)) return rc;
   hipLaunchKernelGGL((attn_bwd_dq_kernel<D, DC, DW>), dim3(grid), dim3(256), lds1, s, q, k, v, d_o, ldo, l2, delta, dq, n, heads, d, sq);
   DFOT_CHECK_HIP(hipGetLastError());
   hipLaunchKernelGGL((attn_bwd_dkv_kernel<D, DC, DW>), dim3(grid), dim3(256), lds2, s, q, k, v, d_o, ldo, l2, delta, dk, dv, n, heads, d, sk);

@@ -9,10 +9,10 @@
 // results (O, m, l) are merged through LDS at the end (no HBM partials for this split).  One such workgroup fills a CU (128 KiB of
 // LDS), so the launch now runs in lock-step rounds, and the left-over of the last round is balanced as in attention_v3.hip: the first
 // `full` work items are whole tiles, the remaining tiles are split over the keys into `nsplit` segments each (fp32 partials in the
-// caller's AttnScratch + attn128_merge_kernel).
+// caller's AttnScratch, planned and merged by attention_split.hip).
 // Same math as attn_kernel_v2: S^T = K Q^T with the running max folded into the accumulator init, deferred rescale (threshold 2^8),
 // O^T += V^T P^T with V^T by transposed LDS reads, exp2 domain (q arrives scaled by log2(e) / sqrt(d)).
-#include "common.h"
+#include "attention_common.h"
 #include "dfot_hip.h"
 #include "kernels.h"
 
@@ -27,24 +27,7 @@ constexpr int IPW = (TILE / 1024) / 4;           // 1-KiB DMA instructions per w
 constexpr int RPI = 1024 / ROWB;                 // rows per DMA instruction: 4
 constexpr float THR = 8.0f;
 
-__device__ __forceinline__ int swz_k(int row, int c) { return c ^ (row & 15); }
-__device__ __forceinline__ int swz_v(int row, int c) { return c ^ ((row & 3) << 2); }
-
-typedef __attribute__((ext_vector_type(2))) unsigned ks_u32x2;
-template <int OFF>
-__device__ __forceinline__ ks_u32x2 ks_read_tr16(unsigned addr) {
-  ks_u32x2 r;
-  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(r) : "v"(addr), "n"(OFF));
-  return r;
-}
-__device__ __forceinline__ void ks_lds_wait(ks_u32x2& a, ks_u32x2& b, ks_u32x2& c, ks_u32x2& d, ks_u32x2& e, ks_u32x2& f, ks_u32x2& g, ks_u32x2& h) {
-  asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e), "+v"(f), "+v"(g), "+v"(h));
-}
-__device__ __forceinline__ bf16x8 ks_bf16x8(ks_u32x2 lo, ks_u32x2 hi) {
-  typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-  const u32x4 v = {lo[0], lo[1], hi[0], hi[1]};
-  return __builtin_bit_cast(bf16x8, v);
-}
+using Cfg = AttnCfg<D>;  // the K / V bank swizzles of 128-element rows
 
 __global__ __launch_bounds__(512, 1) void attn128_ks2_kernel(const bf16* __restrict__ Q, const bf16* __restrict__ K, const bf16* __restrict__ V,
                                                              bf16* __restrict__ O, long ldo, int N, int heads, int full_tiles, int nsplit,
@@ -85,8 +68,8 @@ __global__ __launch_bounds__(512, 1) void attn128_ks2_kernel(const bf16* __restr
   for (int i = 0; i < IPW; ++i) {
     const int inst = wl * IPW + i;
     const int row = inst * RPI + lane / CH, pos = lane % CH;
-    koff[i] = row * D + swz_k(row, pos) * 8;
-    voff[i] = row * D + swz_v(row, pos) * 8;
+    koff[i] = row * D + Cfg::swz_k(row, pos) * 8;
+    voff[i] = row * D + Cfg::swz_v(row, pos) * 8;
   }
   auto issue = [&](int kt, int stage) {  // kt: global key-tile index
     char* sk = smem + stage * 2 * TILE;
@@ -133,7 +116,7 @@ __global__ __launch_bounds__(512, 1) void attn128_ks2_kernel(const bf16* __restr
         const int row = kt2 * 32 + lq;
 #pragma unroll
         for (int ks = 0; ks < D / 16; ++ks) {
-          const bf16x8 kf = *reinterpret_cast<const bf16x8*>(sk + row * ROWB + swz_k(row, ks * 2 + lh) * 16);
+          const bf16x8 kf = *reinterpret_cast<const bf16x8*>(sk + row * ROWB + Cfg::swz_k(row, ks * 2 + lh) * 16);
           sacc[kt2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[ks], sacc[kt2], 0, 0, 0);
         }
       }
@@ -184,16 +167,16 @@ __global__ __launch_bounds__(512, 1) void attn128_ks2_kernel(const bf16* __restr
         const int q4 = (lane & 15) >> 2, p4 = lane & 3;
         const int col = dvt * 32 + 16 * ((lane >> 4) & 1) + 4 * p4;
         const int r0 = 4 * lh + q4;
-        const unsigned va = (unsigned)(size_t)DFOT_LDS_PTR(sv) + r0 * ROWB + swz_v(r0, col >> 3) * 16 + (col & 7) * 2;
-        ks_u32x2 r000 = ks_read_tr16<0 * ROWB>(va), r001 = ks_read_tr16<8 * ROWB>(va);
-        ks_u32x2 r010 = ks_read_tr16<16 * ROWB>(va), r011 = ks_read_tr16<24 * ROWB>(va);
-        ks_u32x2 r100 = ks_read_tr16<32 * ROWB>(va), r101 = ks_read_tr16<40 * ROWB>(va);
-        ks_u32x2 r110 = ks_read_tr16<48 * ROWB>(va), r111 = ks_read_tr16<56 * ROWB>(va);
-        ks_lds_wait(r000, r001, r010, r011, r100, r101, r110, r111);
-        oacc[dvt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ks_bf16x8(r000, r001), pf[0][0], oacc[dvt], 0, 0, 0);
-        oacc[dvt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ks_bf16x8(r010, r011), pf[0][1], oacc[dvt], 0, 0, 0);
-        oacc[dvt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ks_bf16x8(r100, r101), pf[1][0], oacc[dvt], 0, 0, 0);
-        oacc[dvt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ks_bf16x8(r110, r111), pf[1][1], oacc[dvt], 0, 0, 0);
+        const unsigned va = (unsigned)(size_t)DFOT_LDS_PTR(sv) + r0 * ROWB + Cfg::swz_v(r0, col >> 3) * 16 + (col & 7) * 2;
+        u32x2 r000 = lds_read_tr16<0 * ROWB>(va), r001 = lds_read_tr16<8 * ROWB>(va);
+        u32x2 r010 = lds_read_tr16<16 * ROWB>(va), r011 = lds_read_tr16<24 * ROWB>(va);
+        u32x2 r100 = lds_read_tr16<32 * ROWB>(va), r101 = lds_read_tr16<40 * ROWB>(va);
+        u32x2 r110 = lds_read_tr16<48 * ROWB>(va), r111 = lds_read_tr16<56 * ROWB>(va);
+        lds_wait(r000, r001, r010, r011, r100, r101, r110, r111);
+        oacc[dvt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(r000, r001), pf[0][0], oacc[dvt], 0, 0, 0);
+        oacc[dvt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(r010, r011), pf[0][1], oacc[dvt], 0, 0, 0);
+        oacc[dvt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(r100, r101), pf[1][0], oacc[dvt], 0, 0, 0);
+        oacc[dvt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(r110, r111), pf[1][1], oacc[dvt], 0, 0, 0);
       }
       __builtin_amdgcn_s_setprio(0);
     }
@@ -228,7 +211,7 @@ __global__ __launch_bounds__(512, 1) void attn128_ks2_kernel(const bf16* __restr
 
   const float l_tot = l_i + __shfl_xor(l_i, 32);
   const int rloc = wl * 32 + lq;
-  if (seg >= 0) {  // key segment: fp32 partial (O, m, l) for attn128_merge_kernel
+  if (seg >= 0) {  // key segment: fp32 partial (O, m, l) for the merge kernel
     float* prow = part_o + ((long)seg * QR + rloc) * D;
 #pragma unroll
     for (int dvt = 0; dvt < D / 32; ++dvt)
@@ -256,37 +239,6 @@ __global__ __launch_bounds__(512, 1) void attn128_ks2_kernel(const bf16* __restr
     }
 }
 
-// combine the key segments of the left-over tiles: O = sum_s 2^(m_s - M) O_s / sum_s 2^(m_s - M) l_s.  One thread per (query row, 4 columns)
-__global__ __launch_bounds__(256) void attn128_merge_kernel(const float* __restrict__ part_o, const float* __restrict__ part_ml, bf16* __restrict__ O,
-                                                            long ldo, int N, int heads, int full_tiles, int nsplit, int rem_tiles) {
-  constexpr int TPR = D / 4;
-  const long gid = (long)blockIdx.x * 256 + threadIdx.x;
-  const long row = gid / TPR;
-  const int c4 = (int)(gid % TPR) * 4;
-  if (row >= (long)rem_tiles * QR) return;
-  const int lt = (int)(row / QR), rloc = (int)(row % QR);
-  const int qtiles = N / QR;
-  float mmax = -INFINITY;
-  for (int s = 0; s < nsplit; ++s) mmax = fmaxf(mmax, part_ml[((long)(lt * nsplit + s) * QR + rloc) * 2]);
-  float acc[4] = {0.f, 0.f, 0.f, 0.f}, l = 0.f;
-  for (int s = 0; s < nsplit; ++s) {
-    const long pr = (long)(lt * nsplit + s) * QR + rloc;
-    const float w = exp2f(part_ml[pr * 2] - mmax);
-    l += w * part_ml[pr * 2 + 1];
-    const f32x4 o = *reinterpret_cast<const f32x4*>(part_o + pr * D + c4);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[j] += w * o[j];
-  }
-  const float inv = 1.0f / l;
-  const int tile = full_tiles + lt;
-  const int bh = tile / qtiles, b = bh / heads, hd = bh % heads;
-  const int qrow = (tile % qtiles) * QR + rloc;
-  bf16x4 o4;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) o4[j] = f2bf(acc[j] * inv);
-  *reinterpret_cast<bf16x4*>(O + ((long)b * N + qrow) * ldo + hd * D + c4) = o4;
-}
-
 }  // namespace
 
 static AttnSplit plan_ks(int batch, int heads, int n) { return attn_plan_split(batch, heads, n, QR, 1); }  // one 8-wave workgroup per CU
@@ -303,7 +255,7 @@ bool attention_ks_applies(int batch, int heads, int n, int d) {
 size_t attention_ks_scratch_bytes(int batch, int heads, int n, int d) {
   if (!attention_ks_applies(batch, heads, n, d)) return 0;
   const AttnSplit sp = plan_ks(batch, heads, n);
-  return sp.nsplit == 1 ? 0 : (size_t)sp.rem * sp.nsplit * QR * (D + 2) * sizeof(float);
+  return attn_partial_bytes(sp, QR, D);
 }
 
 // q, k, v: [B][heads][N][128] bf16, q pre-scaled by log2(e) / sqrt(d); o: row r of batch b, head hd at o[(b * N + r) * ldo + hd * 128]
@@ -313,23 +265,14 @@ int launch_attention_ks(const bf16* q, const bf16* k, const bf16* v, bf16* o, lo
   DFOT_REQUIRE(n > 0 && n % QR == 0 && (n / KV) % 2 == 0 && ldo % 4 == 0, DFOT_ERR_SHAPE, "attention ks: N=%d / ldo=%ld unsupported", n, ldo);
   const AttnSplit sp = plan_ks(batch, heads, n);
   float *po = nullptr, *pml = nullptr;
-  int rc = attn_partials(sp, QR, &po, &pml, scratch, D);
+  int rc = attn_partials(sp, QR, D, &po, &pml, scratch);
   if (rc) return rc;
   const int lds = 2 * RING;
-  static bool attr_set = false;
-  if (!attr_set) {
-    DFOT_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(attn128_ks2_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    attr_set = true;
-  }
+  if ((rc = ensure_dyn_lds<attn128_ks2_kernel>(lds))) return rc;
   hipLaunchKernelGGL(attn128_ks2_kernel, dim3(sp.full + sp.rem * sp.nsplit), dim3(512), lds, stream, q, k, v, o, ldo, n, heads,
                      sp.full + (sp.nsplit == 1 ? sp.rem : 0), sp.nsplit, po, pml);
   DFOT_CHECK_HIP(hipGetLastError());
-  if (sp.nsplit > 1) {
-    const long threads = (long)sp.rem * QR * (D / 4);
-    hipLaunchKernelGGL(attn128_merge_kernel, dim3(cdiv(threads, 256)), dim3(256), 0, stream, po, pml, o, ldo, n, heads, sp.full, sp.nsplit, sp.rem);
-    DFOT_CHECK_HIP(hipGetLastError());
-  }
-  return DFOT_OK;
+  return attn_launch_merge(sp, QR, D, po, pml, o, ldo, n, heads, stream);
 }
 
 }  // namespace dfot

@@ -12,10 +12,13 @@
 //    ranges add up without rescaling;
 //  * balanced tail: with S = 2 workgroups per CU resident, T query tiles run as floor(T/S) full rounds; the T mod S
 //    left-over tiles are split over the key axis into `nsplit` segments each (rem*nsplit <= S), so the last round is as
-//    full as the others and 1/nsplit as long.  Segments write fp32 partial (O, m, l); attn64_merge_kernel combines them.
-#include "common.h"
+//    full as the others and 1/nsplit as long.  Segments write fp32 partial (O, m, l); attention_split.hip plans the split and
+//    merges them.
+#include "attention_common.h"
 #include "dfot_hip.h"
 #include "kernels.h"
+
+#include <type_traits>
 
 namespace dfot {
 
@@ -25,29 +28,7 @@ constexpr int D = 64, KV = 64, ROWB = 128, TILE = KV * ROWB;   // one K (or V) t
 constexpr int QROWS = 256;                                     // query rows per workgroup (4 waves x 64)
 constexpr float THR = 8.0f;
 
-__device__ __forceinline__ int swz_k(int row, int c) { return c ^ ((row >> 1) & 7); }
-__device__ __forceinline__ int swz_v(int row, int c) { return c ^ (((row >> 1) & 1) << 2); }
-
-typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
-
-// ds_read_b64_tr_b16 through inline asm: hipcc (ROCm 7.2) puts `s_waitcnt vmcnt(0)` in front of the builtin form while an
-// LDS-DMA is in flight (it cannot see that the prefetched stage is a different one), which drains the K/V ring every tile.
-// The asm form is invisible to that pass; its completion is awaited by lds_wait() below, which passes the destination
-// registers through the wait so that no consumer can be scheduled above it.
-template <int OFF>
-__device__ __forceinline__ u32x2 lds_read_tr16(unsigned addr) {
-  u32x2 r;
-  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(r) : "v"(addr), "n"(OFF));
-  return r;
-}
-__device__ __forceinline__ void lds_wait(u32x2& a, u32x2& b, u32x2& c, u32x2& d, u32x2& e, u32x2& f, u32x2& g, u32x2& h) {
-  asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e), "+v"(f), "+v"(g), "+v"(h));
-}
-__device__ __forceinline__ bf16x8 as_bf16x8(u32x2 lo, u32x2 hi) {
-  typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-  const u32x4 v = {lo[0], lo[1], hi[0], hi[1]};
-  return __builtin_bit_cast(bf16x8, v);
-}
+using Cfg = AttnCfg<D>;  // the K / V bank swizzles of 64-element rows
 
 template <int NST, bool NOMAX>
 __global__ __launch_bounds__(256, 2) void attn64_kernel_v3(const bf16* __restrict__ Q, const bf16* __restrict__ K,
@@ -95,8 +76,8 @@ __global__ __launch_bounds__(256, 2) void attn64_kernel_v3(const bf16* __restric
   for (int i = 0; i < 2; ++i) {
     const int inst = wave * 2 + i;
     const int row = inst * 8 + (lane >> 3), pos = lane & 7;
-    koff[i] = row * D + swz_k(row, pos) * 8;
-    voff[i] = row * D + swz_v(row, pos) * 8;
+    koff[i] = row * D + Cfg::swz_k(row, pos) * 8;
+    voff[i] = row * D + Cfg::swz_v(row, pos) * 8;
   }
   auto issue = [&](int t, int stage) {
     char* sk = smem + stage * 2 * TILE;
@@ -139,7 +120,7 @@ __global__ __launch_bounds__(256, 2) void attn64_kernel_v3(const bf16* __restric
 #pragma unroll
   for (int dvt = 0; dvt < 2; ++dvt) {
     const int col = dvt * 32 + vcol, r0 = 4 * lh + q4;
-    vaddr[dvt] = (unsigned)(size_t)DFOT_LDS_PTR(smem) + TILE + r0 * ROWB + swz_v(r0, col >> 3) * 16 + (col & 7) * 2;
+    vaddr[dvt] = (unsigned)(size_t)DFOT_LDS_PTR(smem) + TILE + r0 * ROWB + Cfg::swz_v(r0, col >> 3) * 16 + (col & 7) * 2;
   }
 
   int cur = 0;
@@ -159,7 +140,7 @@ __global__ __launch_bounds__(256, 2) void attn64_kernel_v3(const bf16* __restric
       const int row = kt2 * 32 + lq;
 #pragma unroll
       for (int ks = 0; ks < D / 16; ++ks) {
-        const bf16x8 kf = *reinterpret_cast<const bf16x8*>(sk + row * ROWB + swz_k(row, ks * 2 + lh) * 16);
+        const bf16x8 kf = *reinterpret_cast<const bf16x8*>(sk + row * ROWB + Cfg::swz_k(row, ks * 2 + lh) * 16);
         sacc[0][kt2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[0][ks], sacc[0][kt2], 0, 0, 0);
         sacc[1][kt2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[1][ks], sacc[1][kt2], 0, 0, 0);
       }
@@ -281,110 +262,7 @@ __global__ __launch_bounds__(256, 2) void attn64_kernel_v3(const bf16* __restric
   }
 }
 
-// combine the key segments of the left-over tiles: O = sum_s 2^(m_s - M) O_s / sum_s 2^(m_s - M) l_s.  One thread per
-// (query row, 4 columns); 16 threads per row.
-__global__ __launch_bounds__(256) void attn64_merge_kernel(const float* __restrict__ part_o, const float* __restrict__ part_ml,
-                                                           bf16* __restrict__ O, long ldo, int N, int heads, int ohs,
-                                                           int full_tiles, int nsplit, int rem_tiles, int qrows, float* __restrict__ lse) {
-  const long gid = (long)blockIdx.x * 256 + threadIdx.x;
-  const long row = gid >> 4;
-  const int c4 = (int)(gid & 15) * 4;
-  if (row >= (long)rem_tiles * qrows) return;
-  const int lt = (int)(row / qrows), rloc = (int)(row % qrows);
-  const int qtiles = N / qrows;
-  float mmax = -INFINITY;
-  for (int s = 0; s < nsplit; ++s) mmax = fmaxf(mmax, part_ml[((long)(lt * nsplit + s) * qrows + rloc) * 2]);
-  float acc[4] = {0.f, 0.f, 0.f, 0.f}, l = 0.f;
-  for (int s = 0; s < nsplit; ++s) {
-    const long pr = (long)(lt * nsplit + s) * qrows + rloc;
-    const float w = exp2f(part_ml[pr * 2] - mmax);
-    l += w * part_ml[pr * 2 + 1];
-    const f32x4 o = *reinterpret_cast<const f32x4*>(part_o + pr * D + c4);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[j] += w * o[j];
-  }
-  const float inv = 1.0f / l;
-  const int tile = full_tiles + lt;
-  const int bh = tile / qtiles, b = bh / heads, hd = bh % heads;
-  bf16x4 o4;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) o4[j] = f2bf(acc[j] * inv);
-  *reinterpret_cast<bf16x4*>(O + ((long)b * N + (tile % qtiles) * qrows + rloc) * ldo + hd * ohs + c4) = o4;
-  if (lse && c4 == 0) lse[(long)bh * N + (tile % qtiles) * qrows + rloc] = mmax + __log2f(l);  // training: log2-domain log-sum-exp of the row
-}
-
 }  // namespace
-
-// wgs_per_cu workgroups of qrows query rows are resident per CU (registers: 2 waves per SIMD)
-AttnSplit attn_plan_split(int batch, int heads, int n, int qrows, int wgs_per_cu) {
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
-  }
-  const int slots = wgs_per_cu * cus;
-  AttnSplit sp;
-  sp.slots = slots;
-  sp.tiles = batch * heads * (n / qrows);
-  sp.rem = sp.tiles % slots;
-  sp.full = sp.tiles - sp.rem;
-  sp.nsplit = 1;
-  if (sp.rem) {
-    const int ntk = n / KV;
-    for (int f = 2; f <= 16 && sp.rem * f <= slots; f *= 2)
-      if (ntk % f == 0 && ntk / f >= 4) sp.nsplit = f;
-  }
-  return sp;
-}
-
-// Process-wide scratch of the op-level entry points (dfot_op_attention, tools): it only ever GROWS by allocating a new block; the
-// blocks it outgrows are kept until the process ends, so a kernel in flight or a captured graph that holds an old pointer stays
-// valid (nothing is freed or synchronised on a launch path).  Backbone handles do not use it: they own an AttnScratch sized in
-// their reserve() and pass it in, so two handles / streams never share partial rows and a reserve on one model cannot pull the
-// buffer from under another model's captured graph.
-AttnScratch* attention_default_scratch() {
-  static AttnScratch g;
-  return &g;
-}
-
-size_t attention_scratch_bytes(int batch, int heads, int n, int d) {
-  if (d == 128) return attention_ks_scratch_bytes(batch, heads, n, d);  // the 8-wave key-split kernel of attention_ks.hip
-  if (d != 64 || n % QROWS != 0) return 0;  // d = 64: the 64-rows-per-wave level-2 kernels (attention_v3 / v5) split their tail
-  const AttnSplit sp = attn_plan_split(batch, heads, n, QROWS, 2);
-  return sp.nsplit == 1 ? 0 : (size_t)sp.rem * sp.nsplit * QROWS * (D + 2) * sizeof(float);
-}
-
-int attn_partials(const AttnSplit& sp, int qrows, float** po, float** pml, AttnScratch* scratch, int dcols) {
-  *po = *pml = nullptr;
-  if (sp.nsplit == 1) return DFOT_OK;
-  const size_t rows = (size_t)sp.rem * sp.nsplit * qrows;
-  const size_t bytes = rows * (dcols + 2) * sizeof(float);
-  if (!scratch) {
-    scratch = attention_default_scratch();
-    if (bytes > scratch->bytes) {  // grow: a NEW block; the old one is deliberately leaked (see above)
-      void* p = nullptr;
-      DFOT_CHECK_HIP(hipMalloc(&p, bytes));
-      scratch->p = reinterpret_cast<float*>(p);
-      scratch->bytes = bytes;
-    }
-  }
-  DFOT_REQUIRE(scratch->p && bytes <= scratch->bytes, DFOT_ERR_STATE,
-               "attention: key-split scratch of %zu bytes, launch needs %zu (reserve the handle for this batch first)", scratch->bytes, bytes);
-  *po = scratch->p;
-  *pml = scratch->p + rows * dcols;
-  return DFOT_OK;
-}
-
-int attn_launch_merge(const AttnSplit& sp, int qrows, const float* po, const float* pml, bf16* o, long ldo, int n, int heads,
-                      hipStream_t stream, float* lse) {
-  if (sp.nsplit == 1) return DFOT_OK;
-  const long threads = (long)sp.rem * qrows * 16;
-  hipLaunchKernelGGL(attn64_merge_kernel, dim3(cdiv(threads, 256)), dim3(256), 0, stream, po, pml, o, ldo, n, heads, D, sp.full,
-                     sp.nsplit, sp.rem, qrows, lse);
-  DFOT_CHECK_HIP(hipGetLastError());
-  return DFOT_OK;
-}
 
 // q, k, v: [B][heads][N][64] bf16, q pre-scaled by log2(e)/sqrt(d); o: row r of batch b, head hd at o[(b*N + r)*ldo + hd*64].
 // nomax: the caller guarantees bounded scores (see the header of this file).
@@ -395,23 +273,20 @@ int launch_attention_v3(const bf16* q, const bf16* k, const bf16* v, bf16* o, lo
   DFOT_REQUIRE(ldo % 4 == 0, DFOT_ERR_SHAPE, "attention: output row stride %ld must be a multiple of 4", ldo);
   const AttnSplit sp = attn_plan_split(batch, heads, n, QROWS, 2);
   float *po = nullptr, *pml = nullptr;
-  int rc0 = attn_partials(sp, QROWS, &po, &pml, scratch);
+  int rc0 = attn_partials(sp, QROWS, D, &po, &pml, scratch);
   if (rc0) return rc0;
   const int lds = 2 * 3 * TILE;
   const int grid = sp.full + sp.rem * sp.nsplit;
-  auto go = [&](auto kern) -> int {
-    static bool attr_set = false;
-    if (!attr_set) {
-      DFOT_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-      attr_set = true;
-    }
+  auto go = [&](auto nomax_c) -> int {
+    constexpr auto kern = attn64_kernel_v3<3, decltype(nomax_c)::value>;
+    if (int rc = ensure_dyn_lds<kern>(lds)) return rc;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, stream, q, k, v, o, ldo, n, heads, D, sp.full, sp.nsplit, po, pml);
     DFOT_CHECK_HIP(hipGetLastError());
     return DFOT_OK;
   };
-  int rc = nomax ? go(attn64_kernel_v3<3, true>) : go(attn64_kernel_v3<3, false>);
+  int rc = nomax ? go(std::true_type{}) : go(std::false_type{});
   if (rc) return rc;
-  return attn_launch_merge(sp, QROWS, po, pml, o, ldo, n, heads, stream);
+  return attn_launch_merge(sp, QROWS, D, po, pml, o, ldo, n, heads, stream);
 }
 
 }  // namespace dfot

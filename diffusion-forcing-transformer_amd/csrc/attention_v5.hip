@@ -1,5 +1,5 @@
 // Level-2 self-attention (d = 64), fourth structure: attention_v3.hip's kernel (64 query rows per wave, no running max, balanced
-// tail) with the key loop SOFTWARE-PIPELINED at half-tile (32-key) granularity inside each wave.
+// tail: attention_split.hip) with the key loop SOFTWARE-PIPELINED at half-tile (32-key) granularity inside each wave.
 //
 // Why: PMC on attention_v3 (profiles/r02_f_*) shows MFMA and VALU work co-executing in only 26 % of the MFMA-busy cycles, and the
 // 8-wave ping-pong experiment (attention_pp.hip) showed that an MFMA-only wave and a VALU-only wave on one SIMD do NOT overlap
@@ -14,7 +14,7 @@
 // asks for 1 MFMA : 4 VALU).  K/V tiles: 3-stage LDS-DMA ring as before; tile t-1's V is last read in iteration 2t and tile
 // t+1's K first read in iteration 2t+1, so ONE barrier per tile between the two (behind vmcnt(0): only tile t+1 is in flight
 // there) covers both hazards, and tile t+2 is issued right after it.
-#include "common.h"
+#include "attention_common.h"
 #include "dfot_hip.h"
 #include "kernels.h"
 
@@ -27,30 +27,9 @@ namespace {
 constexpr int D = 64, KV = 64, ROWB = 128, TILE = KV * ROWB;
 constexpr int QROWS = 256;
 
-__device__ __forceinline__ int swz_k(int row, int c) { return c ^ ((row >> 1) & 7); }
-__device__ __forceinline__ int swz_v(int row, int c) { return c ^ (((row >> 1) & 1) << 2); }
+using Cfg = AttnCfg<D>;  // the K / V bank swizzles of 64-element rows
 
-typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
-
-// ds_read_b64_tr_b16 through inline asm: hipcc (ROCm 7.2) puts `s_waitcnt vmcnt(0)` in front of the builtin form while an
-// LDS-DMA is in flight (it cannot see that the prefetched stage is a different one), which drains the K/V ring every tile.
-// The asm form is invisible to that pass; its completion is awaited by lds_wait() below, which passes the destination
-// registers through the wait so that no consumer can be scheduled above it.
-template <int OFF>
-__device__ __forceinline__ u32x2 lds_read_tr16(unsigned addr) {
-  u32x2 r;
-  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(r) : "v"(addr), "n"(OFF));
-  return r;
-}
-__device__ __forceinline__ void lds_wait(u32x2& a, u32x2& b, u32x2& c, u32x2& d, u32x2& e, u32x2& f, u32x2& g, u32x2& h) {
-  asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e), "+v"(f), "+v"(g), "+v"(h));
-}
-__device__ __forceinline__ bf16x8 as_bf16x8(u32x2 lo, u32x2 hi) {
-  typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-  const u32x4 v = {lo[0], lo[1], hi[0], hi[1]};
-  return __builtin_bit_cast(bf16x8, v);
-}
-
+// K fragments by inline-asm reads as well (lds_read_tr16 / lds_wait in common.h say why), awaited together with the V^T reads
 typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
 template <int OFF>
 __device__ __forceinline__ u32x4 lds_read_b128(unsigned addr) {
@@ -113,8 +92,8 @@ __global__ __launch_bounds__(256, 2) void attn64_kernel_v5(const bf16* __restric
   for (int i = 0; i < 2; ++i) {
     const int inst = wave * 2 + i;
     const int row = inst * 8 + (lane >> 3), pos = lane & 7;
-    koff[i] = row * D + swz_k(row, pos) * 8;
-    voff[i] = row * D + swz_v(row, pos) * 8;
+    koff[i] = row * D + Cfg::swz_k(row, pos) * 8;
+    voff[i] = row * D + Cfg::swz_v(row, pos) * 8;
   }
   auto issue = [&](int t, int stage) {
     char* sk = smem + stage * 2 * TILE;
@@ -156,7 +135,7 @@ __global__ __launch_bounds__(256, 2) void attn64_kernel_v5(const bf16* __restric
 #pragma unroll
   for (int dvt = 0; dvt < 2; ++dvt) {
     const int col = dvt * 32 + vcol, r0 = 4 * lh + q4;
-    vaddr[dvt] = (unsigned)(size_t)DFOT_LDS_PTR(smem) + TILE + r0 * ROWB + swz_v(r0, col >> 3) * 16 + (col & 7) * 2;
+    vaddr[dvt] = (unsigned)(size_t)DFOT_LDS_PTR(smem) + TILE + r0 * ROWB + Cfg::swz_v(r0, col >> 3) * 16 + (col & 7) * 2;
   }
 
 
@@ -332,6 +311,10 @@ __global__ __launch_bounds__(256, 2) void attn64_kernel_v5(const bf16* __restric
 
 }  // namespace
 
+// what the callers test before they pick this kernel over one with a running max: exp2(s) of a score below 64 summed over N keys stays
+// far inside the fp32 / bf16 exponent range (2^64 * N << 2^127).  NaN-safe: only a bound that IS below 64 passes.
+bool attention_v5_applies(int n, int d, float score_bound) { return d == 64 && n % QROWS == 0 && score_bound < 64.0f; }
+
 int launch_attention_v5(const bf16* q, const bf16* k, const bf16* v, bf16* o, long ldo, int batch, int heads, int n, hipStream_t stream,
                         AttnScratch* scratch, float* lse) {
   DFOT_REQUIRE(q && k && v && o, DFOT_ERR_ARG, "attention: null pointer");
@@ -339,22 +322,14 @@ int launch_attention_v5(const bf16* q, const bf16* k, const bf16* v, bf16* o, lo
   DFOT_REQUIRE(ldo % 4 == 0, DFOT_ERR_SHAPE, "attention: output row stride %ld must be a multiple of 4", ldo);
   const AttnSplit sp = attn_plan_split(batch, heads, n, QROWS, 2);
   float *po = nullptr, *pml = nullptr;
-  int rc = attn_partials(sp, QROWS, &po, &pml, scratch);
+  int rc = attn_partials(sp, QROWS, D, &po, &pml, scratch);
   if (rc) return rc;
+  constexpr auto kern = attn64_kernel_v5<3, true>;
   const int lds = 2 * 3 * TILE;
-  auto go = [&](auto kern) -> int {
-    static bool attr_set = false;
-    if (!attr_set) {
-      DFOT_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-      attr_set = true;
-    }
-    hipLaunchKernelGGL(kern, dim3(sp.full + sp.rem * sp.nsplit), dim3(256), lds, stream, q, k, v, o, ldo, n, heads, D, sp.full, sp.nsplit, po, pml, lse);
-    DFOT_CHECK_HIP(hipGetLastError());
-    return DFOT_OK;
-  };
-  rc = go(attn64_kernel_v5<3, true>);
-  if (rc) return rc;
-  return attn_launch_merge(sp, QROWS, po, pml, o, ldo, n, heads, stream, lse);
+  if ((rc = ensure_dyn_lds<kern>(lds))) return rc;
+  hipLaunchKernelGGL(kern, dim3(sp.full + sp.rem * sp.nsplit), dim3(256), lds, stream, q, k, v, o, ldo, n, heads, D, sp.full, sp.nsplit, po, pml, lse);
+  DFOT_CHECK_HIP(hipGetLastError());
+  return attn_launch_merge(sp, QROWS, D, po, pml, o, ldo, n, heads, stream, lse);
 }
 
 }  // namespace dfot

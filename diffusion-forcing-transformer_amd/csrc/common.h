@@ -4,6 +4,8 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include "dfot_hip.h"
+
 namespace dfot {
 
 typedef __bf16 bf16;
@@ -12,6 +14,7 @@ typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
 typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
+typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
 
 #define DFOT_LDS_PTR(p) ((void __attribute__((address_space(3)))*)(p))
 #define DFOT_GLOBAL_PTR(p) ((const void __attribute__((address_space(1)))*)(p))
@@ -32,6 +35,25 @@ __device__ __forceinline__ float silu_f(float x) { return x * __builtin_amdgcn_r
 
 __device__ __forceinline__ float bf2f(bf16 v) { return (float)v; }
 __device__ __forceinline__ bf16 f2bf(float v) { return (bf16)v; }
+
+// ds_read_b64_tr_b16 through inline asm: hipcc (ROCm 7.2) puts `s_waitcnt vmcnt(0)` in front of the builtin form while an
+// LDS-DMA is in flight (it cannot see that the prefetched stage is a different one), which drains the K/V ring every tile.
+// The asm form is invisible to that pass; its completion is awaited by lds_wait() below, which passes the destination
+// registers through the wait so that no consumer can be scheduled above it.
+template <int OFF>
+__device__ __forceinline__ u32x2 lds_read_tr16(unsigned addr) {
+  u32x2 r;
+  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(r) : "v"(addr), "n"(OFF));
+  return r;
+}
+__device__ __forceinline__ void lds_wait(u32x2& a, u32x2& b, u32x2& c, u32x2& d, u32x2& e, u32x2& f, u32x2& g, u32x2& h) {
+  asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e), "+v"(f), "+v"(g), "+v"(h));
+}
+__device__ __forceinline__ bf16x8 as_bf16x8(u32x2 lo, u32x2 hi) {
+  typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
+  const u32x4 v = {lo[0], lo[1], hi[0], hi[1]};
+  return __builtin_bit_cast(bf16x8, v);
+}
 
 int tuning_flag(const char* name, int dflt);  // DFOT_<NAME> environment override, read once (A/B experiments)
 
@@ -57,5 +79,17 @@ const char* get_error();
   } while (0)
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+
+// Allow kernel Kern `bytes` of dynamic LDS (a launch that asks for more than the 64 KiB default fails without it).  Called in front
+// of every launch: the attribute is set once per kernel instantiation, on the first call; afterwards this is one flag test.
+template <auto Kern>
+int ensure_dyn_lds(int bytes) {
+  static bool done = false;
+  if (!done) {
+    DFOT_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    done = true;
+  }
+  return DFOT_OK;
+}
 
 }  // namespace dfot

@@ -105,39 +105,43 @@ int launch_gather_f32(const float* src, float* dst, const int* map, int n, hipSt
 int launch_nhwc_to_nchw(const float* src, float* dst, int bt, int p, int c, hipStream_t s);
 int launch_bf16_nhwc_to_nchw(const bf16* src, float* dst, int bt, int p, int c, hipStream_t s);
 
-// fp32 partial rows (O | m, l) of the key-split tail of the level-2 attention kernels.  A backbone handle owns one, sized by
-// attention_scratch_bytes() in its reserve(); nullptr = the process-wide op-level scratch (grow-only, never freed: attention_v3.hip)
+// ---- attention forward ----
+// fp32 partial rows (O | m, l) of the key-split tail of the level-2 / level-3 attention kernels.  A backbone handle owns one, sized by
+// attention_scratch_bytes() in its reserve(); nullptr = the process-wide op-level scratch (grow-only, never freed: attention_split.hip)
 struct AttnScratch {
   float* p = nullptr;
   size_t bytes = 0;
 };
-size_t attention_scratch_bytes(int batch, int heads, int n, int d);
 int launch_attention(const bf16* q, const bf16* k, const bf16* v, bf16* o, long ldo, int batch, int heads, int n, int d,
                      int variant, hipStream_t stream, AttnScratch* scratch = nullptr);
 // attention_v3.hip: d = 64, 64 query rows per wave, balanced tail (key-split left-over tiles + merge); nomax = caller bounds |score|
 int launch_attention_v3(const bf16* q, const bf16* k, const bf16* v, bf16* o, long ldo, int batch, int heads, int n, bool nomax,
                         hipStream_t stream, AttnScratch* scratch = nullptr);
-// attention_v5.hip: attention_v3's NOMAX kernel with the key loop software-pipelined at half-tile granularity inside each wave
+// attention_v5.hip: attention_v3's NOMAX kernel with the key loop software-pipelined at half-tile granularity inside each wave;
+// attention_v5_applies: the shape fits and the caller's bound of |score| (exp2 domain) allows a kernel without a running max
+bool attention_v5_applies(int n, int d, float score_bound);
 int launch_attention_v5(const bf16* q, const bf16* k, const bf16* v, bf16* o, long ldo, int batch, int heads, int n, hipStream_t stream,
                         AttnScratch* scratch = nullptr, float* lse = nullptr);  // lse: [B][heads][N] log2-domain log-sum-exp (training)
-// shared by the two: balanced tail (left-over query tiles split over the key axis) + merge of the fp32 partials
-struct AttnSplit {
-  int tiles, full, rem, nsplit;
-  int slots;  // resident workgroups of one round: wgs_per_cu x the device's CU count
-};
-AttnSplit attn_plan_split(int batch, int heads, int n, int qrows, int wgs_per_cu);
-int attn_partials(const AttnSplit& sp, int qrows, float** po, float** pml, AttnScratch* scratch, int dcols = 64);
 // attention_ks.hip: 128-element rows, 8 waves per workgroup with the key axis split inside the workgroup (launches of few query tiles)
 bool attention_ks_applies(int batch, int heads, int n, int d);
 size_t attention_ks_scratch_bytes(int batch, int heads, int n, int d);
 int launch_attention_ks(const bf16* q, const bf16* k, const bf16* v, bf16* o, long ldo, int batch, int heads, int n, hipStream_t stream,
                         AttnScratch* scratch = nullptr);
-int attn_launch_merge(const AttnSplit& sp, int qrows, const float* po, const float* pml, bf16* o, long ldo, int n, int heads,
-                      hipStream_t stream, float* lse = nullptr);
 int attention_dstride(int d);
 // lse (optional, training): [B][heads][N] fp32, log2-domain log-sum-exp of every query row
 int launch_attention_padded(const bf16* q, const bf16* k, const bf16* v, bf16* o, long ldo, int batch, int heads, int n, int d,
                             hipStream_t stream, float* lse = nullptr);
+// ---- attention forward: key split of the last round + scratch (attention_split.hip; shared by v3, v5 and ks) ----
+struct AttnSplit {
+  int tiles, full, rem, nsplit;
+  int slots;  // resident workgroups of one round: wgs_per_cu x the device's CU count
+};
+AttnSplit attn_plan_split(int batch, int heads, int n, int qrows, int wgs_per_cu);
+size_t attn_partial_bytes(const AttnSplit& sp, int qrows, int dcols);  // dcols: 64 or 128 columns of O
+size_t attention_scratch_bytes(int batch, int heads, int n, int d);    // what launch_attention(variant 2 / 5 / 6 / 14) needs
+int attn_partials(const AttnSplit& sp, int qrows, int dcols, float** po, float** pml, AttnScratch* scratch);
+int attn_launch_merge(const AttnSplit& sp, int qrows, int dcols, const float* po, const float* pml, bf16* o, long ldo, int n, int heads,
+                      hipStream_t stream, float* lse = nullptr);
 // ---- attention backward (attention_bwd.hip) ----
 // delta[b][head][n] = sum_c d_o * o over the head's columns; o / d_o compact [B*N][ldo] (head hd at column hd*d), d % 8 == 0
 int launch_attention_bwd_delta(const bf16* o, const bf16* d_o, long ldo, float* delta, int batch, int heads, int n, int d, hipStream_t s);

@@ -143,25 +143,12 @@ __global__ __launch_bounds__(256) void wgrad_nt_kernel(const bf16* __restrict__ 
 // (global_load_lds, 16 bytes per lane) in two stages as they lie in memory: a row of the A tile is MW * 128 bytes of LDS, unpadded
 // (the DMA writes wave-contiguous kilobytes), with the 16-byte chunks XOR-swizzled on the SOURCE side so that the four rows a
 // transposed read touches fall into different bank groups.  Fragments: ds_read_b64_tr_b16 as above, through inline asm (the
-// builtin makes hipcc drain the DMA queue, see attention_v3.hip), double-buffered over the four 16-row steps of a tile.
+// builtin makes hipcc drain the DMA queue, see lds_read_tr16 in common.h), double-buffered over the four 16-row steps of a tile.
 // Same LDS bytes per FLOP as the 256 x 256 kernel of gemm.hip; twice the wave count and half the staging traffic of the 128 x 128
 // form above.  Dense operands only (the convolution taps stay on the form above); M, N multiples of 8 (out-of-range chunks are
 // fetched from a zero buffer), rows a multiple of 64.
-typedef __attribute__((ext_vector_type(2))) unsigned w2_u32x2;
-template <int OFF>
-__device__ __forceinline__ w2_u32x2 w2_read_tr16(unsigned addr) {
-  w2_u32x2 r;
-  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(r) : "v"(addr), "n"(OFF));
-  return r;
-}
-__device__ __forceinline__ void w2_wait(w2_u32x2 (&a)[2][2], w2_u32x2 (&b)[2][2]) {
-  asm volatile("s_waitcnt lgkmcnt(0)"
-               : "+v"(a[0][0]), "+v"(a[0][1]), "+v"(a[1][0]), "+v"(a[1][1]), "+v"(b[0][0]), "+v"(b[0][1]), "+v"(b[1][0]), "+v"(b[1][1]));
-}
-__device__ __forceinline__ bf16x8 w2_bf16x8(w2_u32x2 lo, w2_u32x2 hi) {
-  typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-  const u32x4 v = {lo[0], lo[1], hi[0], hi[1]};
-  return __builtin_bit_cast(bf16x8, v);
+__device__ __forceinline__ void w2_wait(u32x2 (&a)[2][2], u32x2 (&b)[2][2]) {
+  lds_wait(a[0][0], a[0][1], a[1][0], a[1][1], b[0][0], b[0][1], b[1][0], b[1][1]);
 }
 // chunk swizzle of a row of F features: 512- and 256-byte rows start on the same bank, so rows r, r+1, r+2, r+3 move by 64 bytes each;
 // 384-byte rows already alternate between the two bank halves, so only the row pairs move
@@ -275,20 +262,20 @@ __global__ __launch_bounds__(MW * NW * 64) void wgrad_nt_big_kernel(const bf16* 
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
-  w2_u32x2 fa[2][2][2], fb[2][2][2];  // [buffer][fragment][rows kb.. | kb + 8..]
+  u32x2 fa[2][2][2], fb[2][2][2];  // [buffer][fragment][rows kb.. | kb + 8..]
 #define W2_READ(KS, BUF, SO)                                                   \
-  fa[BUF][0][0] = w2_read_tr16<(KS) * 16 * RA>(aa[0] + (SO));                  \
-  fa[BUF][0][1] = w2_read_tr16<(KS) * 16 * RA + 8 * RA>(aa[0] + (SO));         \
-  fa[BUF][1][0] = w2_read_tr16<(KS) * 16 * RA>(aa[1] + (SO));                  \
-  fa[BUF][1][1] = w2_read_tr16<(KS) * 16 * RA + 8 * RA>(aa[1] + (SO));         \
-  fb[BUF][0][0] = w2_read_tr16<(KS) * 16 * RB>(ab[0] + (SO));                  \
-  fb[BUF][0][1] = w2_read_tr16<(KS) * 16 * RB + 8 * RB>(ab[0] + (SO));         \
-  fb[BUF][1][0] = w2_read_tr16<(KS) * 16 * RB>(ab[1] + (SO));                  \
-  fb[BUF][1][1] = w2_read_tr16<(KS) * 16 * RB + 8 * RB>(ab[1] + (SO));
+  fa[BUF][0][0] = lds_read_tr16<(KS) * 16 * RA>(aa[0] + (SO));                  \
+  fa[BUF][0][1] = lds_read_tr16<(KS) * 16 * RA + 8 * RA>(aa[0] + (SO));         \
+  fa[BUF][1][0] = lds_read_tr16<(KS) * 16 * RA>(aa[1] + (SO));                  \
+  fa[BUF][1][1] = lds_read_tr16<(KS) * 16 * RA + 8 * RA>(aa[1] + (SO));         \
+  fb[BUF][0][0] = lds_read_tr16<(KS) * 16 * RB>(ab[0] + (SO));                  \
+  fb[BUF][0][1] = lds_read_tr16<(KS) * 16 * RB + 8 * RB>(ab[0] + (SO));         \
+  fb[BUF][1][0] = lds_read_tr16<(KS) * 16 * RB>(ab[1] + (SO));                  \
+  fb[BUF][1][1] = lds_read_tr16<(KS) * 16 * RB + 8 * RB>(ab[1] + (SO));
 #define W2_MMA(BUF)                                                                                        \
   {                                                                                                        \
-    const bf16x8 a0 = w2_bf16x8(fa[BUF][0][0], fa[BUF][0][1]), a1 = w2_bf16x8(fa[BUF][1][0], fa[BUF][1][1]); \
-    const bf16x8 b0 = w2_bf16x8(fb[BUF][0][0], fb[BUF][0][1]), b1 = w2_bf16x8(fb[BUF][1][0], fb[BUF][1][1]); \
+    const bf16x8 a0 = as_bf16x8(fa[BUF][0][0], fa[BUF][0][1]), a1 = as_bf16x8(fa[BUF][1][0], fa[BUF][1][1]); \
+    const bf16x8 b0 = as_bf16x8(fb[BUF][0][0], fb[BUF][0][1]), b1 = as_bf16x8(fb[BUF][1][0], fb[BUF][1][1]); \
     acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b0, acc[0][0], 0, 0, 0);                       \
     acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b1, acc[0][1], 0, 0, 0);                       \
     acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b0, acc[1][0], 0, 0, 0);                       \
@@ -339,12 +326,8 @@ template <int MW, int NW, bool CONV, int KT = 64>
 int launch_big(const bf16* a, long lda, const bf16* b, long ldb, float* out, int m, int n, long rows, int slices, hipStream_t s, int img_h = 0,
                int img_w = 0) {
   constexpr int FA = MW * 64, FB = NW * 64, LDS = 2 * KT * (FA + FB) * 2;
-  auto kern = wgrad_nt_big_kernel<MW, NW, CONV, KT>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    DFOT_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-    attr_set = true;
-  }
+  constexpr auto kern = wgrad_nt_big_kernel<MW, NW, CONV, KT>;
+  if (int rc = ensure_dyn_lds<kern>(LDS)) return rc;
   if (!g_w2_zeros) {
     void* z = nullptr;
     DFOT_CHECK_HIP(hipMalloc(&z, 256));
@@ -369,11 +352,7 @@ int launch_wgrad_nt(const bf16* a, long lda, const bf16* b, long ldb, float* out
                    slices <= rows / WG_TR && (img_h == 0 || (img_w > 0 && rows % ((long)img_h * img_w) == 0)),
                DFOT_ERR_SHAPE, "wgrad_nt: M=%d N=%d must be multiples of 8, rows=%ld of 64 (and whole images in conv mode)", m, n, rows);
   const int lds = 4 * WG_TILE;
-  static bool attr_set = false;
-  if (!attr_set) {
-    DFOT_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_nt_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    attr_set = true;
-  }
+  if (int rc = ensure_dyn_lds<wgrad_nt_kernel>(lds)) return rc;
   DFOT_REQUIRE(!all_taps || img_h > 0, DFOT_ERR_ARG, "wgrad_nt: all_taps needs conv mode");
   hipLaunchKernelGGL(wgrad_nt_kernel, dim3(((m + WG_F - 1) / WG_F) * ((n + WG_F - 1) / WG_F) * slices, all_taps ? 9 : 1), dim3(256), lds, s, a, lda, b,
                      ldb, out, m, n, rows, slices, img_h, img_w, sdy, sdx, all_taps);
