@@ -38,7 +38,11 @@ class DiTConfig(C.Structure):
         ("rope_theta", C.c_float), ("eps", C.c_float),
         ("variant", C.c_int32), ("embed_col_dim", C.c_int32), ("num_col_heads", C.c_int32), ("num_row_heads", C.c_int32),
         ("temporal_mlp_hidden", C.c_int32), ("use_bias", C.c_int32),
+        ("cond_type", C.c_int32), ("cond_dim", C.c_int32), ("num_classes", C.c_int32), ("cond_dropout", C.c_int32),
     ]
+
+
+COND_NONE, COND_ACTION, COND_LABEL = 0, 1, 2  # dfot_dit_config.cond_type
 
 
 _P, _I, _L, _F = C.c_void_p, C.c_int, C.c_int64, C.c_float
@@ -99,6 +103,7 @@ SIGNATURES = {
     "dfot_dit_set_option": (_I, [_P, C.c_char_p, _I]),
     "dfot_dit_attn_timing": (_I, [_P, C.POINTER(C.c_double), C.POINTER(_L)]),
     "dfot_dit_forward": (_I, [_P, _P, _P, _P, _I, _I, _P]),
+    "dfot_dit_forward_cond": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _P]),
     "dfot_dit_read_tap": (_I, [_P, C.c_char_p, _P, C.c_size_t, _P]),
     "dfot_dit_train_create": (_I, [C.POINTER(DiTConfig), C.POINTER(_P)]),
     "dfot_dit_train_destroy": (_I, [_P]),
@@ -112,6 +117,7 @@ SIGNATURES = {
     "dfot_dit_train_reserve": (_I, [_P, _I]),
     "dfot_dit_train_sync_weights": (_I, [_P, _P]),
     "dfot_dit_train_forward": (_I, [_P, _P, _P, _P, _I, _I, _P]),
+    "dfot_dit_train_forward_cond": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _P]),
     "dfot_dit_train_input_grad": (_I, [_P, _P, _P]),
     "dfot_dit_train_backward": (_I, [_P, _P, _P]),
     "dfot_vloss_grad": (_I, [_P] * 7 + [_I, _I, _L, _I, _P]),

@@ -108,6 +108,81 @@ __global__ void make_index_kernel(const int* __restrict__ levels, int* __restric
   idx[i] = lv + ((i % tokens) % 2 == 0 ? lpad : 0);
 }
 
+// External condition embedding (RandomDropoutCondEmbedding / LabelEmbedding, embeddings.py:364-387) of every (video, token) frame, ONE launch:
+//   ce = W2 SiLU(W1 cond + b1) + b2 (action)  |  table[label] (label);   e = base + ce, base = noise-level embedding (+ token-kind
+//   embedding of the difference model); frames of a video whose mask byte is set keep e = base;   semb = bf16(SiLU(e)) is the operand
+//   of the modulation GEMM, so everything after it is the unconditioned path reading a per-frame table instead of the per-level one.
+// One workgroup per frame: the hidden activations of the MLP stay in LDS (hidden floats); fp32 throughout.
+struct CondEmbedArgs {
+  const float* cond = nullptr;      // action: [frames][cond_dim]
+  const int* labels = nullptr;      // label: [frames] table rows (clamped to [0, table_rows))
+  const uint8_t* mask = nullptr;    // optional [batch]: 1 = this video runs without its condition
+  const float *w1 = nullptr, *b1 = nullptr, *w2 = nullptr, *b2 = nullptr, *table = nullptr;
+  const float* base = nullptr;      // [..][hidden]: row levels[f] (clamped to max_level) when levels is given, else row f
+  const int* levels = nullptr;
+  const float* diff_table = nullptr;  // optional [2][hidden]: row 1 for even (difference) tokens, row 0 for odd ones
+  float* e_out = nullptr;           // optional fp32 [frames][hidden] (may alias base when levels == nullptr: each element is read, then written)
+  bf16* semb = nullptr;             // [frames][hidden]
+  float *h1_out = nullptr, *a1_out = nullptr;  // optional (training): pre-activation and SiLU output of the first Linear
+  int* idx = nullptr;               // optional [frames]: idx[f] = f, the row of frame f in the per-frame modulation table
+  int tokens = 0, cond_dim = 0, hidden = 0, table_rows = 0, max_level = 0;
+};
+
+template <bool LABEL>
+__global__ __launch_bounds__(256) void cond_embed_kernel(const CondEmbedArgs a) {
+  extern __shared__ float act[];  // [hidden]: SiLU(W1 cond + b1)
+  const int f = blockIdx.x, b = f / a.tokens, t = f % a.tokens, hidden = a.hidden;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const bool masked = a.mask && a.mask[b];
+  long brow = f;
+  if (a.levels) {
+    int lv = a.levels[f];
+    brow = lv < 0 ? 0 : (lv > a.max_level ? a.max_level : lv);
+  }
+  const float* base = a.base + brow * hidden;
+  const float* diff = a.diff_table ? a.diff_table + (long)(t % 2 == 0 ? 1 : 0) * hidden : nullptr;
+  auto finish = [&](int o, float ce) {
+    float e = base[o];
+    if (diff) e += diff[o];
+    if (!masked) e += ce;
+    if (a.e_out) a.e_out[(long)f * hidden + o] = e;
+    a.semb[(long)f * hidden + o] = f2bf(silu_f(e));
+  };
+  if (threadIdx.x == 0 && a.idx) a.idx[f] = f;
+  if constexpr (LABEL) {
+    int row = a.labels[f];
+    row = row < 0 ? 0 : (row >= a.table_rows ? a.table_rows - 1 : row);
+    for (int o = threadIdx.x; o < hidden; o += 256) finish(o, a.table[(long)row * hidden + o]);
+  } else {
+    const float* cv = a.cond + (long)f * a.cond_dim;
+    for (int o = threadIdx.x; o < hidden; o += 256) {
+      float acc = 0.f;
+      for (int k = 0; k < a.cond_dim; ++k) acc += a.w1[(long)o * a.cond_dim + k] * cv[k];
+      acc += a.b1[o];
+      const float s = silu_f(acc);
+      act[o] = s;
+      if (a.h1_out) a.h1_out[(long)f * hidden + o] = acc;
+      if (a.a1_out) a.a1_out[(long)f * hidden + o] = s;
+    }
+    __syncthreads();
+    for (int o = wave; o < hidden; o += 4) {  // one wave per output channel, as rows_linear_kernel
+      float acc = 0.f;
+      for (int i = lane; i < hidden; i += 64) acc += a.w2[(long)o * hidden + i] * act[i];
+      acc = wave_sum(acc);
+      if (lane == 0) finish(o, acc + a.b2[o]);
+    }
+  }
+}
+
+int launch_cond_embed(const CondEmbedArgs& a, int frames, hipStream_t s) {
+  if (a.labels)
+    hipLaunchKernelGGL(cond_embed_kernel<true>, dim3(frames), dim3(256), 0, s, a);
+  else
+    hipLaunchKernelGGL(cond_embed_kernel<false>, dim3(frames), dim3(256), a.hidden * sizeof(float), s, a);
+  DFOT_CHECK_HIP(hipGetLastError());
+  return DFOT_OK;
+}
+
 // per-frame 2-D transpose of a bf16 matrix: src [frames][R][C] -> dst [frames][C][R]; 64x64 tiles through LDS
 __global__ __launch_bounds__(256) void transpose_bf16_kernel(const bf16* __restrict__ src, bf16* __restrict__ dst, int R, int C) {
   __shared__ bf16 tile[64][66];
@@ -508,6 +583,9 @@ struct dfot_dit_s {
   std::vector<DitBlockW> blocks;
   std::vector<DitMatrixW> tblocks;  // variant 1: one MatrixDiTBlock after every spatial block
   float *diff_table = nullptr, *pos2d = nullptr;
+  float *c_w1 = nullptr, *c_b1 = nullptr, *c_w2 = nullptr, *c_b2 = nullptr, *c_table = nullptr;  // external condition embedding
+  int c_rows = 0;                    // label: rows of the embedding table (num_classes, + 1 null class with dropout)
+  int mod_variant = GEMM_AUTO;       // GEMM tile form finalize() used for mod_table: the per-frame table uses the same one (bit-identical rows)
   long mod_final = 0;
   // derived at finalize
   float *freqs = nullptr, *feat = nullptr, *thid = nullptr, *emb = nullptr, *mod_table = nullptr, *rope_cs = nullptr;
@@ -519,6 +597,11 @@ struct dfot_dit_s {
   bf16 *A = nullptr, *q = nullptr, *k = nullptr, *v = nullptr, *hid = nullptr;
   bf16 *T1 = nullptr, *W1 = nullptr, *W2 = nullptr, *Z = nullptr;  // variant 1: transposes / left-factor products / qkv of frames
   int* idx = nullptr;                                              // variant 1: mod_table row per (video, token)
+  // conditioned forward: per-frame SiLU(embedding), modulation table [fpad][ldt] and its row index; e of the last call (tap "cond_emb")
+  int fpad = 0, last_cond_frames = 0;
+  bf16* csemb = nullptr;
+  float *cmod = nullptr, *cemb = nullptr;
+  int* cidx = nullptr;
   int gemm_variant = GEMM_AUTO;
   bool time_attn = false;
   std::vector<hipEvent_t> ev_start, ev_stop;
@@ -593,6 +676,17 @@ int dit_build(dfot_dit_s* h) {
   if ((rc = dit_add_f32(h, ne + ".linear_1.bias", {hd}, &h->t_b1))) return rc;
   if ((rc = dit_add_f32(h, ne + ".linear_2.weight", {hd, hd}, &h->t_w2))) return rc;
   if ((rc = dit_add_f32(h, ne + ".linear_2.bias", {hd}, &h->t_b2))) return rc;
+  // BaseBackbone builds external_cond_embedding right after the noise-level embedding (base_backbone.py:35-62)
+  if (c.cond_type == DFOT_COND_ACTION) {
+    const std::string ce = std::string("external_cond_embedding") + (c.cond_dropout ? ".embedding" : "");
+    if ((rc = dit_add_f32(h, ce + ".linear_1.weight", {hd, c.cond_dim}, &h->c_w1))) return rc;
+    if ((rc = dit_add_f32(h, ce + ".linear_1.bias", {hd}, &h->c_b1))) return rc;
+    if ((rc = dit_add_f32(h, ce + ".linear_2.weight", {hd, hd}, &h->c_w2))) return rc;
+    if ((rc = dit_add_f32(h, ce + ".linear_2.bias", {hd}, &h->c_b2))) return rc;
+  } else if (c.cond_type == DFOT_COND_LABEL) {
+    h->c_rows = c.num_classes + (c.cond_dropout ? 1 : 0);
+    if ((rc = dit_add_f32(h, "external_cond_embedding.embedding_table.weight", {h->c_rows, hd}, &h->c_table))) return rc;
+  }
   if ((rc = dit_add_f32(h, "patch_embedder.proj.weight", {hd, c.in_channels, c.patch_size, c.patch_size}, &h->pe_w))) return rc;
   if ((rc = dit_add_f32(h, "patch_embedder.proj.bias", {hd}, &h->pe_b))) return rc;
   if (facmat && (rc = dit_add_f32(h, "diff_embedder.embedding_table.weight", {2, hd}, &h->diff_table))) return rc;
@@ -775,6 +869,10 @@ int dfot_dit_create(const dfot_dit_config* cfg, dfot_dit_t* out) {
     DFOT_REQUIRE(c.temporal_mlp_hidden >= 0 && c.temporal_mlp_hidden % 64 == 0 && c.hidden_size % 4 == 0 && (c.hidden_size / 2) % 2 == 0,
                  DFOT_ERR_SHAPE, "temporal_mlp_hidden %d must be a multiple of 64", c.temporal_mlp_hidden);
   }
+  DFOT_REQUIRE(c.cond_type == DFOT_COND_NONE || c.cond_type == DFOT_COND_ACTION || c.cond_type == DFOT_COND_LABEL, DFOT_ERR_ARG,
+               "cond_type %d unknown (0 = none, 1 = action, 2 = label)", c.cond_type);
+  DFOT_REQUIRE(c.cond_type != DFOT_COND_ACTION || (c.cond_dim > 0 && c.cond_dim <= 1024), DFOT_ERR_SHAPE, "action condition: cond_dim %d must be in [1, 1024]", c.cond_dim);
+  DFOT_REQUIRE(c.cond_type != DFOT_COND_LABEL || c.num_classes > 0, DFOT_ERR_SHAPE, "label condition: num_classes %d must be positive", c.num_classes);
   auto* h = new dfot_dit_s();
   h->cfg = c;
   int rc = dit_build(h);
@@ -837,7 +935,8 @@ int dfot_dit_finalize(dfot_dit_t h, void* stream) {
   GemmArgs g;
   g.A = h->semb; g.lda = hd; g.W = h->w_mod; g.M = nflag * h->lpad; g.N = (int)h->ldt; g.K = hd;
   g.bias = h->b_mod; g.out_f32 = h->mod_table; g.ldo = h->ldt;
-  int rc = launch_gemm(A_DENSE, E_F32, GEMM_AUTO, g, s);
+  h->mod_variant = gemm_pick_variant(A_DENSE, g.M, g.N, g.K, true);
+  int rc = launch_gemm(A_DENSE, E_F32, h->mod_variant, g, s);
   if (rc) return rc;
   DFOT_CHECK_HIP(hipStreamSynchronize(s));
   h->finalized = true;
@@ -871,6 +970,15 @@ int dfot_dit_reserve(dfot_dit_t h, int max_batch) {
     if ((rc = dit_alloc(h, &h->W2, frames * c.embed_col_dim * c.hidden_size, true))) return rc;
     if ((rc = dit_alloc(h, &h->Z, frames * c.embed_col_dim * 3 * c.hidden_size, true))) return rc;
     if ((rc = dit_alloc(h, &h->idx, frames, true))) return rc;
+  }
+  if (c.cond_type != DFOT_COND_NONE) {
+    const size_t frames = (size_t)max_batch * c.max_tokens;
+    h->fpad = (int)((frames + 255) / 256 * 256);  // whole row tiles of every GEMM form finalize() may have picked
+    if ((rc = dit_alloc(h, &h->csemb, (size_t)h->fpad * c.hidden_size, true))) return rc;
+    DFOT_CHECK_HIP(hipMemset(h->csemb, 0, (size_t)h->fpad * c.hidden_size * sizeof(bf16)));  // rows past the batch: finite operands
+    if ((rc = dit_alloc(h, &h->cmod, (size_t)h->fpad * h->ldt, true))) return rc;
+    if ((rc = dit_alloc(h, &h->cemb, frames * c.hidden_size, true))) return rc;
+    if ((rc = dit_alloc(h, &h->cidx, frames, true))) return rc;
   }
   h->max_batch = max_batch;
   return DFOT_OK;
@@ -915,7 +1023,11 @@ int dfot_dit_attn_timing(dfot_dit_t h, double* total_ms, int64_t* launches) {
   return DFOT_OK;
 }
 
-int dfot_dit_forward(dfot_dit_t h, const float* x, const int32_t* noise_levels, float* out, int batch, int tokens, void* stream) {
+}  // extern "C"
+
+// the forward of both entry points; cond / labels == nullptr: the per-level modulation table (no condition)
+static int dit_forward_impl(dfot_dit_t h, const float* x, const int32_t* noise_levels, const float* cond, const int32_t* labels,
+                            const uint8_t* cond_mask, float* out, int batch, int tokens, void* stream) {
   DFOT_REQUIRE(h && x && noise_levels && out, DFOT_ERR_ARG, "forward: null argument");
   DFOT_REQUIRE(h->finalized, DFOT_ERR_STATE, "forward: weights not finalized");
   DFOT_REQUIRE(batch > 0 && batch <= h->max_batch, DFOT_ERR_STATE, "forward: batch %d exceeds the reserved %d", batch, h->max_batch);
@@ -930,8 +1042,27 @@ int dfot_dit_forward(dfot_dit_t h, const float* x, const int32_t* noise_levels, 
   DFOT_REQUIRE(!facmat || tokens % 2 == 0, DFOT_ERR_SHAPE, "forward: %d tokens; the difference model takes (difference, frame) pairs", tokens);
   int max_level = c.timesteps - 1;
   const int* lvl = noise_levels;
+  const float* table = h->mod_table;
   int rc = 0;
-  if (facmat) {  // table row = level + lpad * (token kind)
+  if (cond || labels) {
+    // per-frame conditioning: e = noise-level embedding (+ token kind) + condition embedding, then the modulation GEMM over the frames
+    // (same tile form as finalize(): a frame without a condition gets the bits of its mod_table row); the blocks index it by frame
+    CondEmbedArgs a;
+    a.cond = cond; a.labels = labels; a.mask = cond_mask;
+    a.w1 = h->c_w1; a.b1 = h->c_b1; a.w2 = h->c_w2; a.b2 = h->c_b2; a.table = h->c_table;
+    a.base = h->emb; a.levels = noise_levels; a.max_level = c.timesteps - 1; a.diff_table = facmat ? h->diff_table : nullptr;
+    a.e_out = h->cemb; a.semb = h->csemb; a.idx = h->cidx;
+    a.tokens = tokens; a.cond_dim = c.cond_dim; a.hidden = hd; a.table_rows = h->c_rows;
+    if ((rc = launch_cond_embed(a, frames, s))) return rc;
+    GemmArgs g;
+    g.A = h->csemb; g.lda = hd; g.W = h->w_mod; g.M = (frames + 255) / 256 * 256; g.N = (int)h->ldt; g.K = hd;
+    g.bias = h->b_mod; g.out_f32 = h->cmod; g.ldo = h->ldt;
+    if ((rc = launch_gemm(A_DENSE, E_F32, h->mod_variant, g, s))) return rc;
+    h->last_cond_frames = frames;
+    table = h->cmod;
+    lvl = h->cidx;
+    max_level = frames - 1;
+  } else if (facmat) {  // table row = level + lpad * (token kind)
     hipLaunchKernelGGL(make_index_kernel, dim3(cdiv(frames, 256)), dim3(256), 0, s, noise_levels, h->idx, frames, tokens, max_level, h->lpad);
     DFOT_CHECK_HIP(hipGetLastError());
     lvl = h->idx;
@@ -942,13 +1073,13 @@ int dfot_dit_forward(dfot_dit_t h, const float* x, const int32_t* noise_levels, 
   DFOT_CHECK_HIP(hipGetLastError());
   const float qscale = 1.4426950408889634f / sqrtf((float)h->d);  // attention works in the exp2 domain
   auto ln_mod = [&](long off) -> int {
-    return launch_ln_mod(h->X, h->X, h->A, h->mod_table, lvl, h->ldt, off, hd, P, (int)rows, c.eps, max_level, s);
+    return launch_ln_mod(h->X, h->X, h->A, table, lvl, h->ldt, off, hd, P, (int)rows, c.eps, max_level, s);
   };
   auto gated = [&](const bf16* a, int kdim, const bf16* w, const float* bias, int bias_rows, long gate_off) -> int {
     GemmArgs g;  // X <- X + gate * (a W^T + bias), in place
     g.A = a; g.lda = kdim; g.W = w; g.M = (int)rows; g.N = hd; g.K = kdim; g.bias = bias; g.bias_rows = bias_rows;
     g.out_f32 = h->X; g.ldo = hd; g.resid = h->X;
-    g.gate = h->mod_table + gate_off; g.gate_index = lvl; g.ldg = h->ldt; g.gate_rows = P;
+    g.gate = table + gate_off; g.gate_index = lvl; g.ldg = h->ldt; g.gate_rows = P;
     return launch_gemm(A_DENSE, E_F32, h->gemm_variant, g, s);
   };
   auto mlp = [&](long mod2, int hidden_cols, const bf16* w1, const float* b1, const bf16* w2, const float* b2) -> int {
@@ -1016,8 +1147,24 @@ int dfot_dit_forward(dfot_dit_t h, const float* x, const int32_t* noise_levels, 
     if (c.temporal_mlp_hidden && (rc = mlp(t.mod2, c.temporal_mlp_hidden, t.w_fc1, t.b_fc1, t.w_fc2, t.b_fc2))) return rc;
   }
   h->last_rows = (int)rows;
-  return launch_final_layer(h->X, h->mod_table, lvl, h->ldt, h->mod_final, h->fin_w, h->fin_b, out, hd, P, (int)rows, c.eps,
+  return launch_final_layer(h->X, table, lvl, h->ldt, h->mod_final, h->fin_w, h->fin_b, out, hd, P, (int)rows, c.eps,
                             max_level, c.in_channels, c.height, c.width, c.patch_size, s);
+}
+
+extern "C" {
+
+int dfot_dit_forward(dfot_dit_t h, const float* x, const int32_t* noise_levels, float* out, int batch, int tokens, void* stream) {
+  return dit_forward_impl(h, x, noise_levels, nullptr, nullptr, nullptr, out, batch, tokens, stream);
+}
+
+int dfot_dit_forward_cond(dfot_dit_t h, const float* x, const int32_t* noise_levels, const float* cond, const int32_t* labels,
+                          const uint8_t* cond_mask, float* out, int batch, int tokens, void* stream) {
+  DFOT_REQUIRE(h, DFOT_ERR_ARG, "forward_cond: null handle");
+  const int type = h->cfg.cond_type;
+  DFOT_REQUIRE(type != DFOT_COND_NONE, DFOT_ERR_STATE, "forward_cond: this model was built without an external condition embedding");
+  DFOT_REQUIRE(type == DFOT_COND_ACTION ? (cond && !labels) : (labels && !cond), DFOT_ERR_ARG,
+               "forward_cond: an action model takes `cond` [B,T,cond_dim], a label model takes `labels` [B,T]");
+  return dit_forward_impl(h, x, noise_levels, cond, labels, cond_mask, out, batch, tokens, stream);
 }
 
 int dfot_dit_read_tap(dfot_dit_t h, const char* name, float* out, size_t capacity, void* stream) {
@@ -1029,6 +1176,10 @@ int dfot_dit_read_tap(dfot_dit_t h, const char* name, float* out, size_t capacit
     DFOT_REQUIRE(h->finalized, DFOT_ERR_STATE, "read_tap: weights not finalized");
     src = h->emb;
     need = (size_t)h->cfg.timesteps * h->cfg.hidden_size;
+  } else if (!strcmp(name, "cond_emb")) {  // e = noise-level (+ token-kind) + condition embedding of every frame of the last conditioned forward
+    DFOT_REQUIRE(h->last_cond_frames > 0, DFOT_ERR_STATE, "read_tap: no conditioned forward has run");
+    src = h->cemb;
+    need = (size_t)h->last_cond_frames * h->cfg.hidden_size;
   } else if (!strcmp(name, "stream")) {
     DFOT_REQUIRE(h->last_rows > 0, DFOT_ERR_STATE, "read_tap: no forward has run");
     src = h->X;

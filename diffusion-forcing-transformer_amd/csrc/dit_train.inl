@@ -136,10 +136,13 @@ __global__ void gate_combine_kernel(const float* __restrict__ x, float* __restri
 // Row chunks per frame in the per-(frame, channel) reductions.  One thread per channel with 4-byte loads measured FASTER than 16-byte
 // loads per thread (gate_bwd 42 vs 60 us: fewer, fatter threads leave too few loads in flight) and than 16 one-wave chunks (4x the atomics).
 constexpr int TR_CHUNKS = 4;
-// da = dY * gate (bf16) ; dgate[frame][c] += sum_rows dY * a ; dbias[c] += sum_rows da
+// The TR_CHUNKS partial sums of a (frame, channel) are stored with plain stores into their own plane of dmod_part
+// [TR_CHUNKS][frames][ldt] (every modulation column is produced by exactly one launch) and added in a fixed order by dmod_reduce_kernel;
+// the bias partials go to one row per (frame, chunk) and through det_sum.  (They were float atomics: two runs of one step differed.)
+// da = dY * gate (bf16) ; dgate part[chunk][frame][c] = sum_rows dY * a ; dbias part[(frame, chunk)][c] = sum_rows da
 __global__ __launch_bounds__(256) void gate_bwd_kernel(const float* __restrict__ dy, const bf16* __restrict__ a, const float* __restrict__ table,
-                                                       long ldt, long off, bf16* __restrict__ da, float* __restrict__ dmod,
-                                                       float* __restrict__ dbias, int hidden, int rows_per_frame) {
+                                                       long ldt, long off, bf16* __restrict__ da, float* __restrict__ dmod_part,
+                                                       float* __restrict__ dbias_part, int hidden, int rows_per_frame) {
   const int c = blockIdx.y * 256 + threadIdx.x;
   if (c >= hidden) return;
   const long frame = blockIdx.x;
@@ -154,8 +157,14 @@ __global__ __launch_bounds__(256) void gate_bwd_kernel(const float* __restrict__
     sg += d * bf2f(a[e]);
     sb += bf2f(o);
   }
-  atomicAdd(dmod + frame * ldt + off + c, sg);
-  atomicAdd(dbias + c, sb);
+  dmod_part[((long)blockIdx.z * gridDim.x + frame) * ldt + off + c] = sg;
+  dbias_part[(frame * TR_CHUNKS + blockIdx.z) * hidden + c] = sb;
+}
+// dmod[f][col] = sum of the TR_CHUNKS planes of dmod_part in a fixed order (TR_CHUNKS == 4)
+__global__ void dmod_reduce_kernel(const float* __restrict__ part, float* __restrict__ dmod, long n) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  dmod[i] = (part[i] + part[n + i]) + (part[2 * n + i] + part[3 * n + i]);
 }
 
 // LayerNorm + modulation backward, row part: dx = rstd (dxh - mean(dxh) - xhat mean(dxh xhat)), dxh = dm (1 + scale); stats = (mean, rstd)
@@ -206,9 +215,9 @@ __global__ __launch_bounds__(256) void ln_bwd_rows_kernel(const float* __restric
     stats[2 * (long)row + 1] = rstd;
   }
 }
-// frame part: dshift[frame][c] += sum_rows dm ; dscale[frame][c] += sum_rows dm xhat
+// frame part: dshift part[chunk][frame][c] = sum_rows dm ; dscale part[chunk][frame][c] = sum_rows dm xhat
 __global__ __launch_bounds__(256) void ln_bwd_frames_kernel(const float* __restrict__ dm, const float* __restrict__ x,
-                                                            const float* __restrict__ stats, float* __restrict__ dmod, long ldt, long off,
+                                                            const float* __restrict__ stats, float* __restrict__ dmod_part, long ldt, long off,
                                                             int hidden, int rows_per_frame) {
   const int c = blockIdx.y * 256 + threadIdx.x;
   if (c >= hidden) return;
@@ -221,8 +230,9 @@ __global__ __launch_bounds__(256) void ln_bwd_frames_kernel(const float* __restr
     ssh += d;
     ssc += d * (x[row * hidden + c] - stats[2 * row]) * stats[2 * row + 1];
   }
-  atomicAdd(dmod + frame * ldt + off + c, ssh);
-  atomicAdd(dmod + frame * ldt + off + hidden + c, ssc);
+  float* o = dmod_part + ((long)blockIdx.z * gridDim.x + frame) * ldt + off;
+  o[c] = ssh;
+  o[hidden + c] = ssc;
 }
 
 // (dq, dk, dv) [B][heads][ntok][dstride] -> dqkv [rows][3*heads*d] bf16 in the Linear's column order (q | k | v, head-major);
@@ -519,10 +529,18 @@ static int launch_pe_wgrad(const float* dx0, const float* x, float* dW, float* d
 // ---- MatrixDiTBlock (factorized matrix attention, variant 1) ------------------------------------------------------------
 // backward of matrix_attn_kernel: z [B*L*E][3h] (q|k|v), d_o [B*L*E][h] -> dz [B*L*E][3h].  The hn*hd entries of one (video, c, r)
 // head are split over MA_CHUNKS workgroups:
-// pass A (matrix_attn_bwd_scores): partial S = <q_l, k_l'> and dP = <do_l, v_l'> of the chunk, added into sc[head][2][L*L]
+// pass A (matrix_attn_bwd_scores): partial S = <q_l, k_l'> and dP = <do_l, v_l'> of the chunk, stored into scp[chunk][head][2][L*L];
+//   matrix_attn_bwd_reduce adds the MA_CHUNKS partials in chunk order into sc[head][2][L*L] (no atomics: the same bits every run)
 // pass B (matrix_attn_bwd_apply): softmax and dS = P (dP - sum P dP) scale from sc (L x L, recomputed per workgroup), then
 //   dq_l = sum_l' dS[l][l'] k_l', dk_l' = sum_l dS[l][l'] q_l, dv_l' = sum_l P[l][l'] do_l for the chunk's entries (L2 hits)
 constexpr int MA_CHUNKS = 8;
+__global__ void matrix_attn_bwd_reduce_kernel(const float* __restrict__ scp, float* __restrict__ sc, long n) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  float acc = 0.f;
+  for (int ch = 0; ch < MA_CHUNKS; ++ch) acc += scp[ch * n + i];
+  sc[i] = acc;
+}
 __global__ __launch_bounds__(256) void matrix_attn_bwd_scores_kernel(const bf16* __restrict__ z, const bf16* __restrict__ d_o, float* __restrict__ sc,
                                                                      int L, int E, int h, int cc, int rr) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -551,8 +569,9 @@ __global__ __launch_bounds__(256) void matrix_attn_bwd_scores_kernel(const bf16*
     as = wave_sum(as);
     ap = wave_sum(ap);
     if (lane == 0) {
-      atomicAdd(sc + ((long)head * 2) * L * L + pi, as);
-      atomicAdd(sc + ((long)head * 2 + 1) * L * L + pi, ap);
+      float* o = sc + ((long)chunk * gridDim.x + head) * 2 * L * L;  // this chunk's plane
+      o[pi] = as;
+      o[L * L + pi] = ap;
     }
   }
 }
@@ -695,6 +714,30 @@ __global__ void diff_grad_kernel(const float* __restrict__ dc, float* __restrict
   dtable[i] = acc;
 }
 
+// condition embedding backward, input side: dce[f][c] = mask[video of f] ? 0 : dc[f][c]  (a dropped video's embedding was not added)
+__global__ void cond_grad_mask_kernel(const float* __restrict__ dc, const uint8_t* __restrict__ mask, float* __restrict__ dce, int frames,
+                                      int tokens, int hidden) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long)frames * hidden) return;
+  const int f = (int)(i / hidden);
+  dce[i] = (mask && mask[f / tokens]) ? 0.f : dc[i];
+}
+// label table: dtable[row][c] = sum over the frames (in frame order) whose clamped label is `row` of dce[f][c]; one thread per (row, c),
+// every element written exactly once: rows of unused classes are exactly zero and two runs give the same bits
+__global__ void label_grad_kernel(const float* __restrict__ dce, const int* __restrict__ labels, float* __restrict__ dtable, int frames,
+                                  int table_rows, int hidden) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long)table_rows * hidden) return;
+  const int row = (int)(i / hidden), c = (int)(i % hidden);
+  float acc = 0.f;
+  for (int f = 0; f < frames; ++f) {
+    int l = labels[f];
+    l = l < 0 ? 0 : (l >= table_rows ? table_rows - 1 : l);
+    if (l == row) acc += dce[(long)f * hidden + c];
+  }
+  dtable[i] = acc;
+}
+
 int launch_ln_bwd_rows(const float* dm, const float* x, const float* table, long ldt, long off, float* dx, float* stats, int hidden,
                        int rows_per_frame, int rows, float eps, hipStream_t s) {
 #define CALL(V, C) \
@@ -717,6 +760,13 @@ struct dfot_dit_train_s {
   float *params_f32 = nullptr, *grads = nullptr;  // attached flat buffers (owned by the caller)
   long o_t_w1 = 0, o_t_b1 = 0, o_t_w2 = 0, o_t_b2 = 0, o_pe_w = 0, o_pe_b = 0, o_diff = -1, o_fmod_w = 0, o_fmod_b = 0, o_fin_w = 0, o_fin_b = 0;
   long mod_final = 0;
+  // external condition embedding (registered after the noise-level embedding, as the reference module)
+  long o_c_w1 = -1, o_c_b1 = -1, o_c_w2 = -1, o_c_b2 = -1, o_c_table = -1;
+  int c_rows = 0;
+  bool cond_active = false, cond_masked = false;  // the last forward had a condition / a dropout mask
+  float *c_in = nullptr, *c_h1 = nullptr, *c_a1 = nullptr, *c_dce = nullptr, *c_da1 = nullptr, *c_dh1 = nullptr;
+  int* c_labels = nullptr;
+  uint8_t* c_mask = nullptr;
   std::vector<dfot::TrainBlock> blocks;  // execution order (variant 1: spatial 0, temporal 0, spatial 1, ...)
   std::vector<void*> owned, ws_owned;
   size_t ws_bytes = 0;
@@ -733,6 +783,7 @@ struct dfot_dit_train_s {
   dfot::bf16* semb = nullptr;
   float *dX = nullptr, *dX2 = nullptr, *stats = nullptr, *delta = nullptr, *dmod = nullptr, *dsemb = nullptr, *dwf = nullptr;
   float *dc = nullptr, *da1 = nullptr, *dh1 = nullptr, *dbmod = nullptr, *scratch_f = nullptr;
+  float *dmod_part = nullptr, *dbias_part = nullptr;  // per-chunk partial sums of the modulation / bias gradients (fixed-order reduction)
   dfot::bf16 *da = nullptr, *dO = nullptr, *dq = nullptr, *dk = nullptr, *dv = nullptr, *dqkv = nullptr, *dqkvT = nullptr, *T1 = nullptr,
              *T2 = nullptr, *dmod_bf = nullptr, *dmodT = nullptr, *sembT = nullptr, *dyp = nullptr, *dyt = nullptr, *mfin = nullptr, *dh = nullptr;
   // matrix-block workspace
@@ -899,6 +950,9 @@ int dfot_dit_train_create(const dfot_dit_config* cfg, dfot_dit_train_t* out) {
                      (c.hidden_size / c.num_row_heads) % 4 == 0 && c.max_tokens <= 32,
                  DFOT_ERR_ARG, "train_create: matrix attention heads");
   }
+  DFOT_REQUIRE(c.cond_type == DFOT_COND_NONE || (c.cond_type == DFOT_COND_ACTION && c.cond_dim > 0 && c.cond_dim <= 1024) ||
+                   (c.cond_type == DFOT_COND_LABEL && c.num_classes > 0),
+               DFOT_ERR_ARG, "train_create: external condition type %d / cond_dim %d / num_classes %d", c.cond_type, c.cond_dim, c.num_classes);
   auto* h = new dfot_dit_train_s();
   h->cfg = c;
   const int hd = c.hidden_size;
@@ -922,6 +976,16 @@ int dfot_dit_train_create(const dfot_dit_config* cfg, dfot_dit_train_t* out) {
   h->o_t_b1 = tr_add(h, ne + ".linear_1.bias", {hd});
   h->o_t_w2 = tr_add(h, ne + ".linear_2.weight", {hd, hd});
   h->o_t_b2 = tr_add(h, ne + ".linear_2.bias", {hd});
+  if (c.cond_type == DFOT_COND_ACTION) {
+    const std::string ce = std::string("external_cond_embedding") + (c.cond_dropout ? ".embedding" : "");
+    h->o_c_w1 = tr_add(h, ce + ".linear_1.weight", {hd, c.cond_dim});
+    h->o_c_b1 = tr_add(h, ce + ".linear_1.bias", {hd});
+    h->o_c_w2 = tr_add(h, ce + ".linear_2.weight", {hd, hd});
+    h->o_c_b2 = tr_add(h, ce + ".linear_2.bias", {hd});
+  } else if (c.cond_type == DFOT_COND_LABEL) {
+    h->c_rows = c.num_classes + (c.cond_dropout ? 1 : 0);
+    h->o_c_table = tr_add(h, "external_cond_embedding.embedding_table.weight", {h->c_rows, hd});
+  }
   h->o_pe_w = tr_add(h, "patch_embedder.proj.weight", {hd, c.in_channels, c.patch_size, c.patch_size});
   h->o_pe_b = tr_add(h, "patch_embedder.proj.bias", {hd});
   if (facmat) h->o_diff = tr_add(h, "diff_embedder.embedding_table.weight", {2, hd});
@@ -1151,13 +1215,21 @@ int dfot_dit_train_reserve(dfot_dit_train_t h, int max_batch) {
   WS(h->wg_ws, h->wg_ws_floats);
   WS(h->dX, rows * hd); WS(h->dX2, rows * hd); WS(h->stats, rows * 2); WS(h->delta, bhn);
   WS(h->dmod, (size_t)fp * h->ldt); WS(h->dmod_bf, (size_t)fp * h->ldt); WS(h->dmodT, (size_t)fp * h->ldt); WS(h->dbmod, (size_t)h->ldt);
+  WS(h->dmod_part, (size_t)TR_CHUNKS * frames * h->ldt); WS(h->dbias_part, (size_t)TR_CHUNKS * frames * hd);
   WS(h->dsemb, (size_t)fp * hd); WS(h->dwf, (size_t)256 * hd > (size_t)128 * h->P ? (size_t)256 * hd : (size_t)128 * h->P);
   WS(h->dc, (size_t)frames * hd); WS(h->da1, (size_t)frames * hd); WS(h->dh1, (size_t)frames * hd); WS(h->scratch_f, (size_t)hd);
   WS(h->da, rows * hd); WS(h->dO, rows * hd); WS(h->dq, qsz); WS(h->dk, qsz); WS(h->dv, qsz);
   WS(h->dqkv, rows * 3 * hd); WS(h->dqkvT, rows * widest); WS(h->T1, rows * widest); WS(h->T2, rows * hd); WS(h->dyp, rows * 64); WS(h->dyt, (size_t)256 * rows);
   WS(h->mfin, rows * hd);
+  if (c.cond_type != DFOT_COND_NONE) {
+    WS(h->c_dce, (size_t)frames * hd); WS(h->c_mask, (size_t)max_batch); WS(h->c_labels, (size_t)frames);
+    if (c.cond_type == DFOT_COND_ACTION) {
+      WS(h->c_in, (size_t)frames * c.cond_dim); WS(h->c_h1, (size_t)frames * hd); WS(h->c_a1, (size_t)frames * hd);
+      WS(h->c_da1, (size_t)frames * hd); WS(h->c_dh1, (size_t)frames * hd);
+    }
+  }
   if (facmat) {
-    WS(h->ma_sc, (size_t)max_batch * c.num_col_heads * c.num_row_heads * 2 * c.max_tokens * c.max_tokens);
+    WS(h->ma_sc, (size_t)(1 + MA_CHUNKS) * max_batch * c.num_col_heads * c.num_row_heads * 2 * c.max_tokens * c.max_tokens);  // sums, then the chunk planes
     WS(h->mt, rows * hd); WS(h->do2, fe * hd); WS(h->dz, fe * 3 * hd); WS(h->dw1, fe * hd);
     WS(h->perm_a, (size_t)(h->P > 128 ? h->P : 128) * frames * hd); WS(h->perm_b, (size_t)(h->P > 128 ? h->P : 128) * frames * hd);
   }
@@ -1168,7 +1240,10 @@ int dfot_dit_train_reserve(dfot_dit_train_t h, int max_batch) {
 }
 
 // out[B,T,C,H,W] = model(x, levels) with every activation the backward needs kept in the workspace; x must stay alive until backward
-int dfot_dit_train_forward(dfot_dit_train_t h, const float* x, const int32_t* noise_levels, float* out, int batch, int tokens, void* stream) {
+}  // extern "C"
+
+static int dit_train_forward_impl(dfot_dit_train_t h, const float* x, const int32_t* noise_levels, const float* cond, const int32_t* labels,
+                                  const uint8_t* cond_mask, float* out, int batch, int tokens, void* stream) {
   DFOT_REQUIRE(h && x && noise_levels && out, DFOT_ERR_ARG, "train_forward: null argument");
   DFOT_REQUIRE(h->synced, DFOT_ERR_STATE, "train_forward: call dfot_dit_train_sync_weights after attaching / updating the parameters");
   DFOT_REQUIRE(batch > 0 && batch <= h->max_batch, DFOT_ERR_STATE, "train_forward: batch %d exceeds the reserved %d", batch, h->max_batch);
@@ -1194,6 +1269,26 @@ int dfot_dit_train_forward(dfot_dit_train_t h, const float* x, const int32_t* no
   if (facmat)
     hipLaunchKernelGGL(add_diff_kernel, dim3(cdiv((long)frames * hd, 256)), dim3(256), 0, s, h->cemb, p + h->o_diff, h->semb, frames, tokens, hd);
   DFOT_CHECK_HIP(hipGetLastError());
+  h->cond_active = cond || labels;
+  h->cond_masked = h->cond_active && cond_mask;
+  if (h->cond_active) {  // c += condition embedding (dropped videos excepted), semb = bf16(SiLU(c)); the inputs are kept for the backward
+    CondEmbedArgs a;
+    if (cond) {
+      DFOT_CHECK_HIP(hipMemcpyAsync(h->c_in, cond, (size_t)frames * c.cond_dim * sizeof(float), hipMemcpyDeviceToDevice, s));
+      a.cond = h->c_in; a.w1 = p + h->o_c_w1; a.b1 = p + h->o_c_b1; a.w2 = p + h->o_c_w2; a.b2 = p + h->o_c_b2;
+      a.h1_out = h->c_h1; a.a1_out = h->c_a1;
+    } else {
+      DFOT_CHECK_HIP(hipMemcpyAsync(h->c_labels, labels, (size_t)frames * sizeof(int), hipMemcpyDeviceToDevice, s));
+      a.labels = h->c_labels; a.table = p + h->o_c_table;
+    }
+    if (cond_mask) {
+      DFOT_CHECK_HIP(hipMemcpyAsync(h->c_mask, cond_mask, (size_t)batch, hipMemcpyDeviceToDevice, s));
+      a.mask = h->c_mask;
+    }
+    a.base = h->cemb; a.e_out = h->cemb; a.semb = h->semb;
+    a.tokens = tokens; a.cond_dim = c.cond_dim; a.hidden = hd; a.table_rows = h->c_rows;
+    if ((rc = launch_cond_embed(a, frames, s))) return rc;
+  }
   {
     GemmArgs g;
     g.A = h->semb; g.lda = hd; g.W = h->w_mod; g.M = h->fp; g.N = (int)h->ldt; g.K = hd; g.bias = h->b_mod; g.out_f32 = h->mod_table; g.ldo = h->ldt;
@@ -1255,6 +1350,22 @@ int dfot_dit_train_forward(dfot_dit_train_t h, const float* x, const int32_t* no
                             frames - 1, c.in_channels, c.height, c.width, c.patch_size, s);
 }
 
+extern "C" {
+
+int dfot_dit_train_forward(dfot_dit_train_t h, const float* x, const int32_t* noise_levels, float* out, int batch, int tokens, void* stream) {
+  return dit_train_forward_impl(h, x, noise_levels, nullptr, nullptr, nullptr, out, batch, tokens, stream);
+}
+
+int dfot_dit_train_forward_cond(dfot_dit_train_t h, const float* x, const int32_t* noise_levels, const float* cond, const int32_t* labels,
+                                const uint8_t* cond_mask, float* out, int batch, int tokens, void* stream) {
+  DFOT_REQUIRE(h, DFOT_ERR_ARG, "train_forward_cond: null handle");
+  const int type = h->cfg.cond_type;
+  DFOT_REQUIRE(type != DFOT_COND_NONE, DFOT_ERR_STATE, "train_forward_cond: this model was built without an external condition embedding");
+  DFOT_REQUIRE(type == DFOT_COND_ACTION ? (cond && !labels) : (labels && !cond), DFOT_ERR_ARG,
+               "train_forward_cond: an action model takes `cond` [B,T,cond_dim], a label model takes `labels` [B,T]");
+  return dit_train_forward_impl(h, x, noise_levels, cond, labels, cond_mask, out, batch, tokens, stream);
+}
+
 // gradients of every parameter for the upstream gradient d_out [B,T,C,H,W] of the last forward's output; OVERWRITES the grads buffer
 int dfot_dit_train_backward(dfot_dit_train_t h, const float* d_out, void* stream) {
   DFOT_REQUIRE(h && d_out, DFOT_ERR_ARG, "train_backward: null argument");
@@ -1271,6 +1382,7 @@ int dfot_dit_train_backward(dfot_dit_train_t h, const float* d_out, void* stream
   int rc = 0;
   if ((rc = zero_fill(G, (size_t)h->total * sizeof(float), s))) return rc;
   if ((rc = zero_fill(h->dmod, (size_t)fp * h->ldt * sizeof(float), s))) return rc;
+  if ((rc = zero_fill(h->dmod_part, (size_t)TR_CHUNKS * frames * h->ldt * sizeof(float), s))) return rc;
   const dim3 fgrid(frames, cdiv(hd, 256), TR_CHUNKS);
 
   // ---- final layer: out = Linear(mfin), mfin = LN(x_fin)(1 + scale) + shift ----
@@ -1288,15 +1400,15 @@ int dfot_dit_train_backward(dfot_dit_train_t h, const float* d_out, void* stream
   auto ln_bwd = [&](const float* x_in, long off) -> int {  // dY holds dm; leaves dx in dY
     int r = launch_ln_bwd_rows(dY, x_in, h->mod_table, h->ldt, off, dN, h->stats, hd, P, (int)rows, c.eps, s);
     if (r) return r;
-    hipLaunchKernelGGL(ln_bwd_frames_kernel, fgrid, dim3(256), 0, s, dY, x_in, h->stats, h->dmod, h->ldt, off, hd, P);
+    hipLaunchKernelGGL(ln_bwd_frames_kernel, fgrid, dim3(256), 0, s, dY, x_in, h->stats, h->dmod_part, h->ldt, off, hd, P);
     DFOT_CHECK_HIP(hipGetLastError());
     std::swap(dY, dN);
     return DFOT_OK;
   };
   auto gate_bwd = [&](const bf16* a, long gate_off, float* dbias) -> int {  // h->da = dY * gate, dgate into dmod, row sums of da into dbias
-    hipLaunchKernelGGL(gate_bwd_kernel, fgrid, dim3(256), 0, s, dY, a, h->mod_table, h->ldt, gate_off, h->da, h->dmod, dbias, hd, P);
+    hipLaunchKernelGGL(gate_bwd_kernel, fgrid, dim3(256), 0, s, dY, a, h->mod_table, h->ldt, gate_off, h->da, h->dmod_part, h->dbias_part, hd, P);
     DFOT_CHECK_HIP(hipGetLastError());
-    return DFOT_OK;
+    return det_sum(h->dbias_part, hd, frames * TR_CHUNKS, hd, dbias, false, s);
   };
   auto frames_sum = [&](const bf16* src, float* dst, long per_frame) -> int {
     hipLaunchKernelGGL(frames_sum_bf16_kernel, dim3(cdiv(per_frame / 4, 256)), dim3(256), 0, s, src, dst, frames, per_frame);
@@ -1363,9 +1475,10 @@ int dfot_dit_train_backward(dfot_dit_train_t h, const float* d_out, void* stream
       {
         const int hn = E / c.num_col_heads, hdr = hd / c.num_row_heads;
         const int nheads = batch * c.num_col_heads * c.num_row_heads;
-        DFOT_CHECK_HIP(hipMemsetAsync(h->ma_sc, 0, (size_t)nheads * 2 * tokens * tokens * sizeof(float), s));
-        hipLaunchKernelGGL(matrix_attn_bwd_scores_kernel, dim3(nheads, MA_CHUNKS), dim3(256), 0, s, b.z, h->do2, h->ma_sc, tokens, E, hd,
+        const long nsc = (long)nheads * 2 * tokens * tokens;
+        hipLaunchKernelGGL(matrix_attn_bwd_scores_kernel, dim3(nheads, MA_CHUNKS), dim3(256), 0, s, b.z, h->do2, h->ma_sc + nsc, tokens, E, hd,
                            c.num_col_heads, c.num_row_heads);
+        hipLaunchKernelGGL(matrix_attn_bwd_reduce_kernel, dim3(cdiv(nsc, 256)), dim3(256), 0, s, h->ma_sc + nsc, h->ma_sc, nsc);
         hipLaunchKernelGGL(matrix_attn_bwd_apply_kernel, dim3(nheads, MA_CHUNKS), dim3(256), 0, s, b.z, h->do2, h->ma_sc, h->dz, tokens, E, hd,
                            c.num_col_heads, c.num_row_heads, 1.0f / sqrtf((float)hn * (float)hdr));
         DFOT_CHECK_HIP(hipGetLastError());
@@ -1391,6 +1504,8 @@ int dfot_dit_train_backward(dfot_dit_train_t h, const float* d_out, void* stream
   h->d_embed = dY;  // gradient w.r.t. the patch-embedding output: dfot_dit_train_input_grad turns it into d / d x
 
   // ---- modulation Linears: table = SiLU(c) W_mod^T + b_mod over the frames ----
+  static_assert(TR_CHUNKS == 4, "dmod_reduce_kernel adds four planes");
+  hipLaunchKernelGGL(dmod_reduce_kernel, dim3(cdiv((long)frames * h->ldt, 256)), dim3(256), 0, s, h->dmod_part, h->dmod, (long)frames * h->ldt);
   hipLaunchKernelGGL(frames_colsum_kernel, dim3(cdiv(h->ldt, 256)), dim3(256), 0, s, h->dmod, h->dbmod, frames, h->ldt);
   DFOT_CHECK_HIP(hipGetLastError());
   if ((rc = launch_f32_to_bf16(h->dmod, h->dmod_bf, (long)fp * h->ldt, s))) return rc;
@@ -1417,6 +1532,20 @@ int dfot_dit_train_backward(dfot_dit_train_t h, const float* d_out, void* stream
   const long fh = (long)frames * hd;
   hipLaunchKernelGGL(silu_bwd_kernel, dim3(cdiv(fh, 256)), dim3(256), 0, s, h->dsemb, h->cemb, h->dc, fh);
   if (facmat) hipLaunchKernelGGL(diff_grad_kernel, dim3(cdiv(2 * hd, 256)), dim3(256), 0, s, h->dc, G + h->o_diff, frames, tokens, hd);
+  if (h->cond_active) {  // the condition embedding was added to c: its gradient is dc, zero for dropped videos
+    hipLaunchKernelGGL(cond_grad_mask_kernel, dim3(cdiv(fh, 256)), dim3(256), 0, s, h->dc, h->cond_masked ? h->c_mask : (const uint8_t*)nullptr,
+                       h->c_dce, frames, tokens, hd);
+    if (c.cond_type == DFOT_COND_ACTION) {
+      const int cd = c.cond_dim;
+      hipLaunchKernelGGL(small_wgrad_kernel, dim3(cdiv((long)hd * hd, 256)), dim3(256), 0, s, h->c_dce, h->c_a1, G + h->o_c_w2, G + h->o_c_b2, frames, hd, hd);
+      hipLaunchKernelGGL(small_dgrad_kernel, dim3(cdiv(fh, 256)), dim3(256), 0, s, h->c_dce, p + h->o_c_w2, h->c_da1, frames, hd, hd);
+      hipLaunchKernelGGL(silu_bwd_kernel, dim3(cdiv(fh, 256)), dim3(256), 0, s, h->c_da1, h->c_h1, h->c_dh1, fh);
+      hipLaunchKernelGGL(small_wgrad_kernel, dim3(cdiv((long)hd * cd, 256)), dim3(256), 0, s, h->c_dh1, h->c_in, G + h->o_c_w1, G + h->o_c_b1, frames, hd, cd);
+    } else {
+      hipLaunchKernelGGL(label_grad_kernel, dim3(cdiv((long)h->c_rows * hd, 256)), dim3(256), 0, s, h->c_dce, h->c_labels, G + h->o_c_table, frames,
+                         h->c_rows, hd);
+    }
+  }
   hipLaunchKernelGGL(small_wgrad_kernel, dim3(cdiv((long)hd * hd, 256)), dim3(256), 0, s, h->dc, h->a1, G + h->o_t_w2, G + h->o_t_b2, frames, hd, hd);
   hipLaunchKernelGGL(small_dgrad_kernel, dim3(cdiv(fh, 256)), dim3(256), 0, s, h->dc, p + h->o_t_w2, h->da1, frames, hd, hd);
   hipLaunchKernelGGL(silu_bwd_kernel, dim3(cdiv(fh, 256)), dim3(256), 0, s, h->da1, h->h1, h->dh1, fh);

@@ -3,12 +3,12 @@
 Mirrors the reference's plugin contract for this path:
   * constructor keywords of DiscreteDiffusion._build_model (algorithms/dfot/diffusion/discrete_diffusion.py:64-92)
     and DiT3D.__init__ (algorithms/dfot/backbones/dit/dit3d.py:13-83): variant "full", pos_emb_type "rope_3d",
-    no external condition, causal masking rejected exactly as the reference does;
+    external condition "action" / "label" (base_backbone.py:42-62), causal masking rejected exactly as the reference does;
   * ``forward(x, noise_levels, external_cond=None, external_cond_mask=None)`` (dit3d.py:146-192) with integer
     ``noise_levels`` -- the level index DiscreteDiffusion.model_predictions passes (discrete_diffusion.py:173-174);
   * state-dict key names / shapes / order of the reference module, so its checkpoints load with ``load_state_dict``.
 Parameters live here as fp32 ``nn.Parameter``s; the C library keeps packed bf16 copies and a per-level modulation table
-that are rebuilt whenever a parameter changes.  Inference only.
+that are rebuilt whenever a parameter changes.
 """
 from __future__ import annotations
 
@@ -23,6 +23,42 @@ from . import capi, ops
 from .backbone import _Node, _get
 
 
+def configure_condition(c: "capi.DiTConfig", cfg, external_cond_type, external_cond_num_classes, external_cond_dim) -> None:
+    """BaseBackbone._build_external_cond_embedding (base_backbone.py:42-62) -> the engine's condition fields."""
+    c.cond_type, c.cond_dim, c.num_classes, c.cond_dropout = capi.COND_NONE, 0, 0, 0
+    if not external_cond_dim:
+        return
+    c.cond_dropout = int(float(_get(cfg, "external_cond_dropout", 0.0) or 0.0) > 0)
+    if external_cond_type == "label":
+        if not external_cond_num_classes or int(external_cond_num_classes) <= 0:
+            raise ValueError("external_cond_type='label' needs external_cond_num_classes")
+        c.cond_type, c.num_classes = capi.COND_LABEL, int(external_cond_num_classes)
+    elif external_cond_type == "action":
+        c.cond_type, c.cond_dim = capi.COND_ACTION, int(external_cond_dim)
+    else:
+        raise ValueError(f"Unknown external condition type: {external_cond_type}. Supported types are 'label' and 'action'.")
+
+
+def condition_tensors(c: "capi.DiTConfig", external_cond: torch.Tensor, batch: int, tokens: int, difference: bool):
+    """external_cond as the reference's forward consumes it -> what the engine takes: (cond fp32 [B,T,cond_dim] | None, labels int32 [B,T] | None).
+    label, DiT3D: (B, 1) or (B, T) class ids, broadcast over the tokens as ``emb + cond_emb`` does (dit3d.py:171-173);
+    label, DifferenceDiT3D: (B, 2), each repeated over T/2 tokens (``repeat(cond_emb, "b two d -> b (two p) d")``, difference_dit3d.py:203-206)."""
+    if c.cond_type == capi.COND_ACTION:
+        if tuple(external_cond.shape) != (batch, tokens, c.cond_dim):
+            raise ValueError(f"external_cond has shape {tuple(external_cond.shape)}, expected {(batch, tokens, int(c.cond_dim))}")
+        return external_cond.detach().to(torch.float32).contiguous(), None
+    lab = external_cond.detach().long()
+    if difference:
+        if tuple(lab.shape) != (batch, 2):
+            raise ValueError(f"external_cond (labels) has shape {tuple(lab.shape)}, expected {(batch, 2)}")
+        lab = lab.repeat_interleave(tokens // 2, dim=1)
+    else:
+        if lab.ndim != 2 or lab.shape[0] != batch or lab.shape[1] not in (1, tokens):
+            raise ValueError(f"external_cond (labels) has shape {tuple(lab.shape)}, expected {(batch, 1)} or {(batch, tokens)}")
+        lab = lab.expand(batch, tokens)
+    return None, lab.to(torch.int32).contiguous()
+
+
 class DiT3D(nn.Module):
     def __init__(self, cfg, x_shape: Sequence[int], max_tokens: int, external_cond_type: str = "action",
                  external_cond_num_classes: Optional[int] = None, external_cond_dim: int = 0,
@@ -30,11 +66,12 @@ class DiT3D(nn.Module):
         if use_causal_mask:
             raise NotImplementedError("Causal masking is not yet implemented for DiT3D backbone")
         super().__init__()
-        if external_cond_dim:
-            raise ValueError("external conditions are not supported by the DiT3D engine (kinetics_600 has none)")
         self.cfg = cfg
         self.x_shape = tuple(int(v) for v in x_shape)
-        self.external_cond_dim = 0
+        self.external_cond_type = external_cond_type
+        self.external_cond_num_classes = external_cond_num_classes
+        self.external_cond_dim = int(external_cond_dim or 0)
+        self.external_cond_dropout = float(_get(cfg, "external_cond_dropout", 0.0) or 0.0) if self.external_cond_dim else 0.0
         self.use_causal_mask = False
         self.patch_size = int(_get(cfg, "patch_size", 2))
         c = capi.DiTConfig()
@@ -46,6 +83,7 @@ class DiT3D(nn.Module):
         c.timesteps = int(timesteps)
         c.rope_theta = 10000.0
         c.eps = 1e-6
+        configure_condition(c, cfg, external_cond_type, external_cond_num_classes, self.external_cond_dim)
         self._configure(c, cfg, int(max_tokens))
         self.hidden_size = int(c.hidden_size)
         self.max_tokens = int(c.max_tokens)
@@ -65,7 +103,11 @@ class DiT3D(nn.Module):
         self._reserved = 0
         self._op_key: Optional[int] = None
         # training form (autograd): the saved-activation engine of trainer.DiT3DTrainer, built at the first forward under grad
-        self._ctor = dict(max_tokens=int(max_tokens), timesteps=int(timesteps))
+        self._ctor = dict(max_tokens=int(max_tokens), timesteps=int(timesteps), external_cond_type=external_cond_type,
+                          external_cond_num_classes=external_cond_num_classes, external_cond_dim=self.external_cond_dim)
+        # training-time dropout of the condition embedding, per video (RandomEmbeddingDropout: torch.rand(emb.shape[:1]) < p): drawn from
+        # this generator (None: the default CUDA generator) so that a run is reproducible
+        self._dropout_generator: Optional[torch.Generator] = None
         self._trainer = None
         self._trainer_sig = None
         self._train_stamp = 0  # counts training forwards (see backbone.UViT3DPose._train_backward_impl)
@@ -111,7 +153,7 @@ class DiT3D(nn.Module):
             for name, t in self._tensors().items():
                 if name.endswith(("bias", "qkv_bias", "proj_bias")) or ".modulation." in name or name.startswith("dit_base.final_layer.linear"):
                     t.zero_()
-                elif name.startswith(("noise_level_pos_embedding", "diff_embedder")):
+                elif name.startswith(("noise_level_pos_embedding", "diff_embedder", "external_cond_embedding")):  # _mlp_init (dit3d.py:98-107)
                     t.copy_(0.02 * torch.randn(t.shape, generator=g))
                 else:
                     fan_out, fan_in = t.shape[0], math.prod(t.shape[1:])
@@ -169,15 +211,50 @@ class DiT3D(nn.Module):
             self._reserved = batch
             self.reserve_generation = getattr(self, "reserve_generation", 0) + 1  # workspace pointers changed
 
+    def _condition_mask(self, external_cond_mask: Optional[torch.Tensor], batch: int, dev) -> Optional[torch.Tensor]:
+        """which videos run without their condition, as the reference's modules decide it: an action model built with
+        external_cond_dropout == 0 IS a TimestepEmbedding and never sees the mask (embeddings.py:377-378,385-386); with dropout > 0 the
+        mask zeroes the embedding in eval() and a fresh per-video draw does in train() (a mask is refused there, as the reference asserts);
+        label models never receive the mask (dit3d.py:171-173)."""
+        if self._ccfg.cond_type != capi.COND_ACTION or self.external_cond_dropout <= 0:
+            return None
+        if external_cond_mask is not None:
+            assert not self.training, "embedding mask is only allowed during inference"
+            assert external_cond_mask.ndim == 1, "embedding mask should be of shape (B,)"
+            if external_cond_mask.shape[0] != batch:
+                raise ValueError(f"external_cond_mask has shape {tuple(external_cond_mask.shape)}, expected {(batch,)}")
+            return external_cond_mask.detach().to(device=dev, dtype=torch.uint8).contiguous()
+        if self.training:
+            return (torch.rand(batch, device=dev, generator=self._dropout_generator) < self.external_cond_dropout).to(torch.uint8)
+        return None
+
+    def _labels_with_dropout(self, labels: torch.Tensor) -> torch.Tensor:
+        """LabelEmbedding.token_drop in train(): the labels of dropped videos index the extra (null class) row"""
+        if self.training and self.external_cond_dropout > 0:
+            drop = torch.rand(labels.shape[0], device=labels.device, generator=self._dropout_generator) < self.external_cond_dropout
+            labels = torch.where(drop[:, None], torch.full_like(labels, int(self._ccfg.num_classes)), labels)
+        return labels
+
     def forward(self, x: torch.Tensor, noise_levels: torch.Tensor, external_cond: Optional[torch.Tensor] = None,
                 external_cond_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """BaseBackbone.forward; dispatched as the torch operator ``dfot::dit3d_forward`` (ops.py)."""
-        if external_cond is not None:
+        """BaseBackbone.forward; dispatched as the torch operators ``dfot::dit3d_forward`` / ``dfot::dit3d_forward_cond`` (ops.py)."""
+        if external_cond is not None and self._ccfg.cond_type == capi.COND_NONE:
             raise ValueError("this DiT3D was built without an external condition embedding")
         if self._op_key is None:
             self._op_key = ops.register_model(self)
         params = [p for _, p in self.named_parameters()]
-        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params)):
+        train = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params))
+        if external_cond is not None:
+            b, t = x.shape[:2]
+            cond, labels = condition_tensors(self._ccfg, external_cond, b, t, self._ccfg.variant == 1)
+            mask = self._condition_mask(external_cond_mask, b, x.device)
+            if labels is not None:
+                labels = self._labels_with_dropout(labels)
+            c = cond if cond is not None else labels
+            if train:
+                return torch.ops.dfot.dit3d_forward_cond_train(x, noise_levels, c, mask, params, self._op_key)
+            return torch.ops.dfot.dit3d_forward_cond(x, noise_levels, c, mask, self._op_key)
+        if train:
             # the reference's training_step differentiates through `self.model(...)` (discrete_diffusion.py model_predictions ->
             # accelerator.backward): saved-activation forward + the hand-written backward, registered with autograd (ops.py)
             return torch.ops.dfot.dit3d_forward_train(x, noise_levels, params, self._op_key)
@@ -190,7 +267,10 @@ class DiT3D(nn.Module):
         from . import trainer as _trainer
         sig = tuple((t.data_ptr(), t._version) for t in params)
         if self._trainer is None:
-            self._trainer = _trainer.DiT3DTrainer(self.cfg, self.x_shape, self._ctor["max_tokens"], timesteps=self._ctor["timesteps"])
+            self._trainer = _trainer.DiT3DTrainer(self.cfg, self.x_shape, self._ctor["max_tokens"], timesteps=self._ctor["timesteps"],
+                                                  external_cond_type=self._ctor["external_cond_type"],
+                                                  external_cond_num_classes=self._ctor["external_cond_num_classes"],
+                                                  external_cond_dim=self._ctor["external_cond_dim"])
             missing = [n for n in self._trainer.layout if n not in self._train_names]
             if missing:
                 raise RuntimeError(f"the training engine expects parameters the module does not have: {missing[:4]}")
@@ -200,7 +280,7 @@ class DiT3D(nn.Module):
             self._trainer_sig = sig
         return self._trainer
 
-    def _train_forward_impl(self, x, noise_levels, params):
+    def _train_forward_impl(self, x, noise_levels, params, cond=None, cond_mask=None):
         if x.ndim != 5 or tuple(x.shape[2:]) != self.x_shape:
             raise ValueError(f"x has shape {tuple(x.shape)}, expected (B, T, {', '.join(map(str, self.x_shape))})")
         if x.shape[1] > self.max_tokens:
@@ -212,10 +292,10 @@ class DiT3D(nn.Module):
         dev = params[0].device
         if dev.type != "cuda":
             raise RuntimeError(f"the backbone's parameters are on {dev}; move the module to the GPU first (there is no CPU path)")
-        capi.require_device(dev, x=x, noise_levels=noise_levels)
+        capi.require_device(dev, x=x, noise_levels=noise_levels, external_cond=cond, external_cond_mask=cond_mask)
         self._train_stamp += 1
         with torch.no_grad():
-            return self._train_engine(params).forward(x, noise_levels).to(x.dtype)
+            return self._train_engine(params).forward(x, noise_levels, cond, cond_mask).to(x.dtype)
 
     def _train_backward_impl(self, grad_out, params, stamp=None, want_dx=False):
         eng = self._trainer
@@ -233,7 +313,9 @@ class DiT3D(nn.Module):
                 grads.append(eng.input_grad().to(grad_out.dtype))
             return grads
 
-    def _forward_impl(self, x: torch.Tensor, noise_levels: torch.Tensor) -> torch.Tensor:
+    def _forward_impl(self, x: torch.Tensor, noise_levels: torch.Tensor, cond: Optional[torch.Tensor] = None,
+                      cond_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """cond: what condition_tensors returned (fp32 actions or int32 labels per (video, token)); cond_mask: uint8 (B,) or None"""
         if x.ndim != 5 or tuple(x.shape[2:]) != self.x_shape:
             raise ValueError(f"x has shape {tuple(x.shape)}, expected (B, T, {', '.join(map(str, self.x_shape))})")
         b, t = x.shape[:2]
@@ -246,17 +328,29 @@ class DiT3D(nn.Module):
         dev = next(self.parameters()).device
         if dev.type != "cuda":
             raise RuntimeError(f"the backbone's parameters are on {dev}; move the module to the GPU first (there is no CPU path)")
-        capi.require_device(dev, x=x, noise_levels=noise_levels)
+        capi.require_device(dev, x=x, noise_levels=noise_levels, external_cond=cond, external_cond_mask=cond_mask)
         self.sync_weights()
         self.reserve(b)
         xf = x.detach().to(torch.float32).contiguous()
         kf = noise_levels.detach().to(torch.int32).contiguous()
         out = torch.empty_like(xf)
-        capi.check(capi.lib.dfot_dit_forward(self._handle, capi.ptr(xf, torch.float32, "x"), capi.ptr(kf, torch.int32, "noise_levels"),
-                                             capi.ptr(out), b, t, capi.stream_ptr()))
+        if cond is None:
+            capi.check(capi.lib.dfot_dit_forward(self._handle, capi.ptr(xf, torch.float32, "x"), capi.ptr(kf, torch.int32, "noise_levels"),
+                                                 capi.ptr(out), b, t, capi.stream_ptr()))
+            return out.to(x.dtype)
+        action = self._ccfg.cond_type == capi.COND_ACTION
+        want = (b, t, int(self._ccfg.cond_dim)) if action else (b, t)
+        if tuple(cond.shape) != want or (cond_mask is not None and tuple(cond_mask.shape) != (b,)):
+            raise ValueError(f"condition has shape {tuple(cond.shape)}, expected {want} (mask {(b,)})")
+        pc = capi.ptr(cond, torch.float32, "external_cond") if action else None
+        pl = None if action else capi.ptr(cond, torch.int32, "external_cond")
+        capi.check(capi.lib.dfot_dit_forward_cond(self._handle, capi.ptr(xf, torch.float32, "x"), capi.ptr(kf, torch.int32, "noise_levels"),
+                                                  pc, pl, capi.ptr(cond_mask, torch.uint8, "external_cond_mask"), capi.ptr(out), b, t,
+                                                  capi.stream_ptr()))
         return out.to(x.dtype)
 
     def read_tap(self, name: str, rows: int) -> torch.Tensor:
+        """"emb" (rows = timesteps), "stream" (rows = B*T*P), "cond_emb" (rows = B*T of the last conditioned forward)"""
         out = torch.empty(rows, self.hidden_size, device="cuda", dtype=torch.float32)
         capi.check(capi.lib.dfot_dit_read_tap(self._handle, name.encode(), capi.ptr(out), out.numel(), capi.stream_ptr()))
         return out

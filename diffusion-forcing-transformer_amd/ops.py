@@ -7,6 +7,7 @@ FakeTensor tracing, ``torch.compile`` graphs and stream capture treat the HIP ke
     dfot::uvit3d_pose_forward(x, noise_levels, external_cond, external_cond_mask?, model) -> v      [dfot_uvit_forward]
     dfot::uvit3d_pose_forward_train(x, noise_levels, external_cond, mask?, params[], model) -> v    [autograd: dfot_op_* forward/backward]
     dfot::dit3d_forward(x, noise_levels, model) -> v                                                [dfot_dit_forward]
+    dfot::dit3d_forward_cond(x, noise_levels, external_cond, external_cond_mask?, model) -> v       [dfot_dit_forward_cond]
     dfot::ray_encoding(raw_poses, resolution) -> cond                                               [dfot_ray_encode]
     dfot::hg_prepare(x, noise?, qa, qb, nfe) -> x_in                                                [dfot_hg_prepare]
     dfot::ddim_hg_step(x, x_in, v, sa, s1, an, cn, keep, weight, gen, nfe) -> x_next                [dfot_ddim_compose / _tokw]
@@ -116,6 +117,18 @@ def _(x, noise_levels, model):
     return torch.empty_like(x)
 
 
+# the same forward with an external condition per (video, token): fp32 actions (B, T, cond_dim) or int32 labels (B, T), and the
+# optional per-video uint8 mask (B,) of the videos that run without it
+@custom_op("dfot::dit3d_forward_cond", mutates_args=())
+def dit3d_forward_cond(x: Tensor, noise_levels: Tensor, external_cond: Tensor, external_cond_mask: Optional[Tensor], model: int) -> Tensor:
+    return _model(model)._forward_impl(x, noise_levels, external_cond, external_cond_mask)
+
+
+@dit3d_forward_cond.register_fake
+def _(x, noise_levels, external_cond, external_cond_mask, model):
+    return torch.empty_like(x)
+
+
 # DiT3D / DifferenceDiT3D under autograd: as uvit3d_pose_forward_train, backed by trainer.DiT3DTrainer (dfot_dit_train_*)
 @custom_op("dfot::dit3d_forward_train", mutates_args=())
 def dit3d_forward_train(x: Tensor, noise_levels: Tensor, params: List[Tensor], model: int) -> Tensor:
@@ -153,6 +166,31 @@ def _dit_train_backward(ctx, grad_out):
 
 
 dit3d_forward_train.register_autograd(_dit_train_backward, setup_context=_dit_train_setup_context)
+
+
+@custom_op("dfot::dit3d_forward_cond_train", mutates_args=())
+def dit3d_forward_cond_train(x: Tensor, noise_levels: Tensor, external_cond: Tensor, external_cond_mask: Optional[Tensor],
+                             params: List[Tensor], model: int) -> Tensor:
+    return _model(model)._train_forward_impl(x, noise_levels, params, external_cond, external_cond_mask)
+
+
+@dit3d_forward_cond_train.register_fake
+def _(x, noise_levels, external_cond, external_cond_mask, params, model):
+    return torch.empty_like(x)
+
+
+def _dit_cond_train_setup_context(ctx, inputs, output):
+    ctx.params = inputs[4]
+    ctx.model = inputs[5]
+    ctx.stamp = _model(inputs[5])._train_stamp
+
+
+def _dit_cond_train_backward(ctx, grad_out):
+    dx, _, grads, _ = _dit_train_backward(ctx, grad_out)
+    return dx, None, None, None, grads, None
+
+
+dit3d_forward_cond_train.register_autograd(_dit_cond_train_backward, setup_context=_dit_cond_train_setup_context)
 
 
 @custom_op("dfot::ray_encoding", mutates_args=())

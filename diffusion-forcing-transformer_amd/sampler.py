@@ -48,6 +48,11 @@ class SamplerConfig:
     # camera_pose_conditioning of dfot_video_pose.yaml:7-9
     camera_pose_normalize_by: str = "first"
     camera_pose_bound: Optional[float] = None
+    # external condition of the DiT family (dfot_video.yaml: external_cond_type / external_cond_dim / external_cond_processing; set by the
+    # data set: dmlab, minecraft = action with mask_first, cond_ucf_101 = label)
+    external_cond_type: str = "action"
+    external_cond_dim: int = 0
+    external_cond_processing: Optional[str] = None
 
 
 NoiseFn = Callable[[str, tuple], torch.Tensor]
@@ -111,6 +116,23 @@ class DFoTVideoPoseSampler:
         from . import pose
         world = pose.normalize_poses(conditions.detach().float().cpu().numpy(), cfg.camera_pose_normalize_by, cfg.camera_pose_bound, interp)
         return torch.ops.dfot.ray_encoding(torch.from_numpy(world), int(self.x_shape[-1]), True)
+
+    def _select_conditions(self, conditions: Optional[torch.Tensor], index) -> Optional[torch.Tensor]:
+        """the conditions of the tokens `index` (slice or index tensor) of a video"""
+        return None if conditions is None else conditions[:, index]
+
+    def _padded_conditions(self, conditions: Optional[torch.Tensor], index) -> Optional[torch.Tensor]:
+        """the conditions of an interpolation window, padded to max_tokens"""
+        return None if conditions is None else self._pad_to_max_tokens(conditions[:, index])
+
+    def _window_conditions(self, conditions: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+        """what the backbone gets for one window (before the repetition per History-Guidance branch)"""
+        return self._process_conditions(conditions)
+
+    def _check_conditions(self, conditions: Optional[torch.Tensor], length: int) -> None:
+        pass
+
+    _static_graph_cond = False  # True: the captured step loop reads the window's conditions from a static buffer refreshed per window
 
     # ------------------------------------------------------------------ denoising loss (no backward)
     @torch.no_grad()
@@ -227,6 +249,7 @@ class DFoTVideoPoseSampler:
                 raise ValueError("context must be provided if context_mask is given. ")
             if tuple(context.shape[:2]) != tuple(context_mask.shape):
                 raise ValueError("context and context_mask must have the same shape.")
+        self._check_conditions(conditions, length)
         horizon = self.max_tokens
         padding = horizon - length
         f = int(np.prod(x_shape))
@@ -402,7 +425,7 @@ class DFoTVideoPoseSampler:
                     cmask_cache[ckey] = torch.from_numpy(p_["cmask"]).cuda()
                 p_["cmask_dev"] = cmask_cache[ckey]
 
-        cond_full = None if pose_interp else self._process_conditions(conditions)
+        cond_full = None if pose_interp else self._window_conditions(conditions)
         cond_rep, cond_nfe = None, 0
         if pose_interp:
             by_mask: Dict[bytes, torch.Tensor] = {}
@@ -523,6 +546,9 @@ class DFoTVideoPoseSampler:
         hook = getattr(self, "step_hook", None)  # test instrumentation (drift per step); None on every product path
         if (self.use_graph and uniform and not strict and len(plans) > 2 and all(p_["sigma"] is None for p_ in plans) and not self._branch_split_active
                 and rg == 0 and hook is None):
+            if self._static_graph_cond and cond_full is not None:
+                nfe0 = plans[0]["nfe"]
+                plans[0]["cond_src"] = cond_full if nfe0 == 1 else cond_full.repeat_interleave(nfe0, dim=0)
             xs = self._run_steps_graph(plans, xs, draw_noise, step, flat_dev, gens_dev, horizon)
         else:
             for i, p_ in enumerate(plans):
@@ -630,8 +656,9 @@ class DFoTVideoPoseSampler:
         if gen != self._graphs_generation:
             self._graphs.clear()
             self._graphs_generation = gen
+        cond_src = p0.get("cond_src")
         key = (bm, n_steps, nfe, horizon, tuple(xs.shape), need_noise, None if p0["cmask"] is None else p0["cmask"].tobytes(),
-               id(self.model))
+               id(self.model), None if cond_src is None else (tuple(cond_src.shape), cond_src.dtype))
         ent = self._graphs.get(key)
         if ent is None:
             ent = dict(tables=torch.empty(n_steps, 8, bm, horizon, device="cuda", dtype=torch.float32),
@@ -639,7 +666,9 @@ class DFoTVideoPoseSampler:
                        lives=torch.empty(n_steps, bm, horizon, device="cuda", dtype=torch.uint8),
                        fresh=torch.empty(n_steps, bm, horizon, device="cuda", dtype=torch.uint8),
                        noise=torch.empty(n_steps, bm, *xs.shape[1:], device="cuda") if need_noise else None,
-                       xs=torch.empty_like(xs), out=None, graph=None)
+                       xs=torch.empty_like(xs), out=None, graph=None,
+                       # the captured backbone calls read the conditions HERE: every window copies its own in before the replay
+                       cond=None if cond_src is None else torch.empty_like(cond_src))
         ent["tables"].copy_(flat_dev.view(n_steps, 8, bm, horizon))
         ent["gens"].copy_(gens_dev)
         ent["lives"].copy_(gens_dev if nfe == 1 else gens_dev.repeat_interleave(nfe, dim=1))
@@ -652,6 +681,9 @@ class DFoTVideoPoseSampler:
                 else:
                     ent["noise"][i].zero_()
         p_static = dict(p0, weights_dev=ent["weights"])
+        if cond_src is not None:
+            ent["cond"].copy_(cond_src)
+            p_static["cond"] = ent["cond"]
         ent["xs"].copy_(step(p_static, xs, None if not need_noise else ent["noise"][0], ent["tables"][0], ent["gens"][0], live_dev=ent["lives"][0],
                             fresh_dev=ent["fresh"][0]))
         if ent["graph"] is None:
@@ -705,7 +737,7 @@ class DFoTVideoPoseSampler:
             if generated > 0:
                 cmask[:, -generated:] = 2
             cmask = torch.cat([cmask, torch.zeros(batch_size, h, dtype=torch.long)], 1)
-            cond = None if conditions is None else conditions[:, cur - c: cur - c + mt]
+            cond = self._select_conditions(conditions, slice(cur - c, cur - c + mt))
             if hasattr(self.noise_fn, "set_windows"):
                 # key-frame windows are replicated on every rank: key their noise by the sliding-window index (rank-independent),
                 # never by whatever the previous interpolation batch of this rank left behind
@@ -763,7 +795,7 @@ class DFoTVideoPoseSampler:
         for si, stage in enumerate(self._interpolation_plan(context_mask[0].numpy())):
             ctx = torch.cat([self._pad_to_max_tokens(xs[:, w]) for w in stage], 0)
             msk = torch.cat([self._pad_to_max_tokens(known[:, w]) for w in stage], 0)
-            cnd = None if conditions is None else torch.cat([self._pad_to_max_tokens(conditions[:, w]) for w in stage], 0)
+            cnd = None if conditions is None else torch.cat([self._padded_conditions(conditions, w) for w in stage], 0)
 
             def sample_batch(ids, ctx=ctx, msk=msk, cnd=cnd, si=si):
                 if not ids:
@@ -798,7 +830,7 @@ class DFoTVideoPoseSampler:
         n = out.shape[1]
         keys = torch.linspace(0, n - 1, round(density * n)).round().long()
         keys = torch.cat([torch.arange(n_context_tokens), keys]).unique()
-        kc = None if conditions is None else conditions[:, keys]
+        kc = self._select_conditions(conditions, keys)
         if self.branch_parallel and parallel.world_info()[0] > 1 and not (hasattr(self.noise_fn, "set_windows") or getattr(self.noise_fn, "replicated", False)):
             # the gathered v mixes branches evaluated on DIFFERENT ranks: they must all hold bit-identical xs and noise
             raise ValueError("branch_parallel needs a rank-independent noise source: parallel.WindowKeyedNoise (set_windows) or a noise_fn "
@@ -819,12 +851,46 @@ class DFoTVideoPoseSampler:
 
 class DFoTVideoSampler(DFoTVideoPoseSampler):
     """The reference's base algorithm (algorithms/dfot/dfot_video.py: DFoTVideo), used by the un-conditioned video
-    configurations such as Kinetics-600 (DiT3D + DiscreteDiffusion): identical sampling path, no camera poses."""
+    configurations such as Kinetics-600 (DiT3D + DiscreteDiffusion) and by the action / label conditioned ones (dmlab, minecraft,
+    cond_ucf_101): identical sampling path, no camera poses; `conditions` are actions (B, T, dim) or labels (B, 1)."""
 
+    _static_graph_cond = True
+
+    def _cond_type(self) -> str:
+        t = self.cfg.external_cond_type
+        if t not in ("label", "action"):
+            raise ValueError(f"Unknown external condition type: {t}. Supported types are 'label' and 'action'.")
+        return t
+
+    @torch.no_grad()
     def _process_conditions(self, conditions: Optional[torch.Tensor], noise_levels=None) -> Optional[torch.Tensor]:
-        if conditions is not None:
-            raise ValueError("DFoTVideoSampler takes no external conditions; use DFoTVideoPoseSampler for camera poses")
-        return None
+        """BaseVideoAlgo._process_conditions (base_pytorch_video_algo.py:636-664): None passes the conditions on, "mask_first" zeroes
+        the first token's first external_cond_dim values"""
+        if conditions is None:
+            return None
+        proc = self.cfg.external_cond_processing
+        if proc is None:
+            return conditions
+        if proc == "mask_first":
+            mask = torch.ones_like(conditions)
+            mask[:, :1, : self.cfg.external_cond_dim] = 0
+            return conditions * mask
+        raise NotImplementedError(f"External condition processing {proc} is not implemented.")
+
+    def _select_conditions(self, conditions: Optional[torch.Tensor], index) -> Optional[torch.Tensor]:
+        """labels describe the whole video and pass whole; actions are per token (dfot_video.py:141-151,294-306,471-481)"""
+        if conditions is None:
+            return None
+        return conditions if self._cond_type() == "label" else conditions[:, index]
+
+    def _padded_conditions(self, conditions: Optional[torch.Tensor], index) -> Optional[torch.Tensor]:
+        if conditions is None:
+            return None
+        return conditions if self._cond_type() == "label" else self._pad_to_max_tokens(conditions[:, index])
+
+    def _window_conditions(self, conditions: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+        c = self._process_conditions(conditions)
+        return None if c is None else c.to(self.device).contiguous()
 
 
 class DifferenceDFoTVideoSampler(DFoTVideoSampler):
@@ -854,12 +920,25 @@ class DifferenceDFoTVideoSampler(DFoTVideoSampler):
         """inverse of merge_tensors (difference_dfot_video.py:63-75)."""
         return x[:, 0::2], x[:, 1::2]
 
+    def _window_conditions(self, conditions: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+        """the difference algorithm processes the conditions once per video, before merging (_sample_all_videos); its windows repeat
+        them per branch as they are (difference_dfot_video.py:825)"""
+        return None if conditions is None else conditions.to(self.device).contiguous()
+
+    def _check_conditions(self, conditions: Optional[torch.Tensor], length: int) -> None:
+        """difference_dfot_video.py:686-694 (self.max_tokens here already counts the merged tokens)"""
+        if conditions is not None and self._cond_type() == "action" and conditions.shape[1] != self.max_tokens:
+            raise ValueError(f"for noncausal models, conditions length is expected to be {self.max_tokens}, got {conditions.shape[1]}.")
+
     @torch.no_grad()
-    def _sample_all_videos(self, xs: torch.Tensor, n_context_tokens: int) -> Dict[str, torch.Tensor]:
+    def _sample_all_videos(self, xs: torch.Tensor, n_context_tokens: int, conditions: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
         """difference_dfot_video.py:166-212 without the logging/VAE tail: frames -> (difference, frame) tokens -> prediction
-        on the merged sequence with doubled context -> {"prediction", "prediction_diff"}."""
+        on the merged sequence with doubled context -> {"prediction", "prediction_diff"}; the conditions are processed, then merged with
+        themselves (:177-179)."""
         difference = torch.diff(xs, dim=1, prepend=xs[:, :1])
         merged = self.merge_tensors(difference, xs)
-        out = self._predict_videos(merged, n_context_tokens=2 * n_context_tokens, conditions=None)
+        conditions = self._process_conditions(conditions)
+        conditions = self.merge_tensors(conditions, conditions) if conditions is not None else None
+        out = self._predict_videos(merged, n_context_tokens=2 * n_context_tokens, conditions=conditions)
         gen_diff, gen = self.unmerge_tensors(out)
         return {"gt": xs.clone(), "prediction": gen, "prediction_diff": gen_diff}

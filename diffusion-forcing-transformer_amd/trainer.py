@@ -26,9 +26,13 @@ class DiT3DTrainer:
     def __init__(self, cfg, x_shape: Sequence[int], max_tokens: int, timesteps: int = 1000,
                  diffusion: Optional[DiffusionConfig] = None, lr: float = 5e-5, weight_decay: float = 0.01,
                  betas: Tuple[float, float] = (0.9, 0.99), eps: float = 1e-8, max_grad_norm: Optional[float] = 1.0,
-                 loss_weighting: Optional[Dict] = None):
+                 loss_weighting: Optional[Dict] = None, external_cond_type: str = "action",
+                 external_cond_num_classes: Optional[int] = None, external_cond_dim: int = 0):
+        from .dit_backbone import configure_condition
         self.x_shape = tuple(int(v) for v in x_shape)
         c = capi.DiTConfig()
+        configure_condition(c, cfg, external_cond_type, external_cond_num_classes, external_cond_dim)
+        self.external_cond_dropout = float(_get(cfg, "external_cond_dropout", 0.0) or 0.0) if external_cond_dim else 0.0
         c.depth = int(_get(cfg, "depth"))
         c.num_heads = int(_get(cfg, "num_heads"))
         c.patch_size = int(_get(cfg, "patch_size", 2))
@@ -123,7 +127,10 @@ class DiT3DTrainer:
             self._dirty = False
 
     # ------------------------------------------------------------------ forward / backward (the autograd pair)
-    def forward(self, x: torch.Tensor, noise_levels: torch.Tensor) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, noise_levels: torch.Tensor, cond: Optional[torch.Tensor] = None,
+                cond_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """cond: fp32 actions (B, T, cond_dim) or int32 labels (B, T) per (video, token) (dit_backbone.condition_tensors); cond_mask:
+        uint8 (B,), the videos whose condition embedding is dropped"""
         b, t = x.shape[:2]
         if tuple(x.shape[2:]) != self.x_shape:
             raise ValueError(f"x has frame shape {tuple(x.shape[2:])}, expected {self.x_shape}")
@@ -134,7 +141,19 @@ class DiT3DTrainer:
         xd = x.to(device="cuda", dtype=torch.float32).contiguous()
         lv = noise_levels.to(device="cuda", dtype=torch.int32).contiguous()
         out = torch.empty_like(xd)
-        capi.check(capi.lib.dfot_dit_train_forward(self._handle, capi.ptr(xd), capi.ptr(lv), capi.ptr(out), b, t, capi.stream_ptr()))
+        if cond is None:
+            capi.check(capi.lib.dfot_dit_train_forward(self._handle, capi.ptr(xd), capi.ptr(lv), capi.ptr(out), b, t, capi.stream_ptr()))
+        else:
+            action = self._ccfg.cond_type == capi.COND_ACTION
+            if self._ccfg.cond_type == capi.COND_NONE:
+                raise ValueError("this trainer was built without an external condition embedding")
+            want = (b, t, int(self._ccfg.cond_dim)) if action else (b, t)
+            if tuple(cond.shape) != want or (cond_mask is not None and tuple(cond_mask.shape) != (b,)):
+                raise ValueError(f"condition has shape {tuple(cond.shape)}, expected {want} (mask {(b,)})")
+            cd = cond.to(device="cuda", dtype=torch.float32 if action else torch.int32).contiguous()
+            md = None if cond_mask is None else cond_mask.to(device="cuda", dtype=torch.uint8).contiguous()
+            capi.check(capi.lib.dfot_dit_train_forward_cond(self._handle, capi.ptr(xd), capi.ptr(lv), capi.ptr(cd) if action else None,
+                                                            None if action else capi.ptr(cd), capi.ptr(md), capi.ptr(out), b, t, capi.stream_ptr()))
         self._keep = (xd, lv)  # the engine reads x again in backward (patch-embedding gradient)
         return out
 
@@ -149,10 +168,31 @@ class DiT3DTrainer:
         return dx
 
     # ------------------------------------------------------------------ one training step
-    def loss_and_grads(self, xs: torch.Tensor, k: torch.Tensor, noise: torch.Tensor, masks: Optional[torch.Tensor] = None):
+    def _condition(self, conditions: Optional[torch.Tensor], b: int, t: int, generator: Optional[torch.Generator]):
+        """conditions as the reference's training_step passes them to the model -> (cond, per-video dropout mask) of forward().  Dropout
+        (cfg.external_cond_dropout > 0) is drawn per video from `generator` (a CUDA generator; None: the default one): action embeddings of
+        dropped videos are zeroed (RandomEmbeddingDropout), labels of dropped videos index the null-class row (LabelEmbedding.token_drop)."""
+        if conditions is None:
+            return None, None
+        from .dit_backbone import condition_tensors
+        cond, labels = condition_tensors(self._ccfg, conditions.to("cuda"), b, t, self._ccfg.variant == 1)
+        drop = None
+        if self.external_cond_dropout > 0:
+            drop = torch.rand(b, device="cuda", generator=generator) < self.external_cond_dropout
+        if labels is not None:
+            if drop is not None:
+                labels = torch.where(drop[:, None], torch.full_like(labels, int(self._ccfg.num_classes)), labels)
+            return labels, None
+        return cond, None if drop is None else drop.to(torch.uint8)
+
+    def loss_and_grads(self, xs: torch.Tensor, k: torch.Tensor, noise: torch.Tensor, masks: Optional[torch.Tensor] = None,
+                       conditions: Optional[torch.Tensor] = None, dropout_generator: Optional[torch.Generator] = None):
         """DiscreteDiffusion.forward (pred_v) + _reweight_loss + backward: noise every token to its level, one forward, the
-        weighted v-space error averaged over (B, T) with the loss masks, gradients of every parameter.  Returns the loss (device scalar)."""
+        weighted v-space error averaged over (B, T) with the loss masks, gradients of every parameter.  Returns the loss (device scalar).
+        conditions: the external condition of the batch (actions (B, T, dim) / labels (B, 1)), embedded as in DiT3D.forward."""
         b, t = xs.shape[:2]
+        cond, cdrop = self._condition(conditions, b, t, dropout_generator)
+        self.last_cond_dropout = cdrop
         f = int(np.prod(xs.shape[2:]))
         kk = k.detach().cpu().numpy().astype(np.int64)
         sch = self.schedule
@@ -165,7 +205,7 @@ class DiT3DTrainer:
         x_k = torch.empty_like(x)
         s = capi.stream_ptr
         capi.check(capi.lib.dfot_hg_prepare(capi.ptr(x), capi.ptr(eps), capi.ptr(tab[0]), capi.ptr(tab[1]), capi.ptr(x_k), b, 1, t, f, s()))
-        v = self.forward(x_k, k)
+        v = self.forward(x_k, k, cond, cdrop)
         per_token = torch.empty(b, t, device="cuda")
         scratch = torch.empty(int(capi.lib.dfot_vpred_loss_scratch_floats(b, t, f)), device="cuda")
         capi.check(capi.lib.dfot_vspace_loss(capi.ptr(x), capi.ptr(eps), capi.ptr(v), capi.ptr(tab[0]), capi.ptr(tab[1]), capi.ptr(tab[2]),
@@ -176,7 +216,8 @@ class DiT3DTrainer:
         self.backward(dv)
         return (per_token * torch.from_numpy(mk).cuda()).mean()
 
-    def difference_loss_and_grads(self, frames: torch.Tensor, k: torch.Tensor, noise: torch.Tensor, masks: Optional[torch.Tensor] = None):
+    def difference_loss_and_grads(self, frames: torch.Tensor, k: torch.Tensor, noise: torch.Tensor, masks: Optional[torch.Tensor] = None,
+                                  conditions: Optional[torch.Tensor] = None, dropout_generator: Optional[torch.Generator] = None):
         """DifferenceDFoTVideo.training_step (difference_dfot_video.py:80-105): frame differences (first frame against itself) are
         interleaved with the frames (difference first), noise levels and loss masks are doubled the same way, then the ordinary
         denoising loss on the 2T merged tokens.  frames (B,T,C,H,W), k / masks (B,T), noise (B,2T,C,H,W)."""
@@ -187,7 +228,8 @@ class DiT3DTrainer:
         merge = lambda a, b: torch.stack([a, b], dim=2).flatten(1, 2)
         kk = k.to("cuda")
         mk = None if masks is None else merge(masks.to("cuda"), masks.to("cuda"))
-        return self.loss_and_grads(merge(diff, fr), merge(kk, kk), noise, mk)
+        cc = None if conditions is None else merge(conditions.to("cuda"), conditions.to("cuda"))  # merge_tensors(conditions, conditions)
+        return self.loss_and_grads(merge(diff, fr), merge(kk, kk), noise, mk, cc, dropout_generator)
 
     def accumulate(self) -> None:
         """accumulate_grad_batches: add the gradients of the last backward to the running sum used by the next optimizer_step"""
@@ -216,8 +258,9 @@ class DiT3DTrainer:
         self._dirty = True
 
     def training_step(self, xs: torch.Tensor, k: torch.Tensor, noise: torch.Tensor, masks: Optional[torch.Tensor] = None,
-                      world_size: int = 1) -> torch.Tensor:
-        loss = self.loss_and_grads(xs, k, noise, masks)
+                      world_size: int = 1, conditions: Optional[torch.Tensor] = None,
+                      dropout_generator: Optional[torch.Generator] = None) -> torch.Tensor:
+        loss = self.loss_and_grads(xs, k, noise, masks, conditions, dropout_generator)
         self.optimizer_step(world_size)
         return loss
 

@@ -33,6 +33,7 @@ def main():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--out", default="sample_out.npz")
+    ap.add_argument("--cond", help="k600 / k600diff: synthetic external condition, 'action:DIM' (e.g. action:3, as dmlab) or 'label:CLASSES' (label:101)")
     a = ap.parse_args()
     gen = torch.Generator(device="cuda").manual_seed(a.seed)
     noise = dfot_amd.device_noise_fn(gen)
@@ -52,16 +53,25 @@ def main():
         n_ctx = 1
     else:
         diff = a.model == "k600diff"
+        ckw, skw = {}, {}
+        if a.cond:
+            ctype, num = a.cond.split(":")
+            ckw = dict(external_cond_type=ctype, external_cond_dim=int(num) if ctype == "action" else 1,
+                       external_cond_num_classes=int(num) if ctype == "label" else None)
+            skw = dict(external_cond_type=ctype, external_cond_dim=ckw["external_cond_dim"], external_cond_processing="mask_first" if ctype == "action" else None)
+            g = torch.Generator().manual_seed(200 + a.seed)
+            conds = torch.randn(a.batch, 5, int(num), generator=g) if ctype == "action" else torch.randint(0, int(num), (a.batch, 1), generator=g)
         if diff:
             bb = dict(name="difference_dit3d", variant="factorized_matrix_attention", pos_emb_type="sinusoidal_2d", merge_type="interleaved",
                       patch_size=1, embed_col_dim=64, embed_row_dim=1152, num_heads=12, num_col_heads=1, num_row_heads=16, depth=28,
                       mlp_ratio=4.0, spatial_mlp_ratio=4.0, use_bias=True, matrix_block="matrix")
-            model = dfot_amd.DifferenceDiT3D(bb, x_shape=(16, 16, 16), max_tokens=5).cuda()
+            model = dfot_amd.DifferenceDiT3D(bb, x_shape=(16, 16, 16), max_tokens=5, **ckw).cuda()
         else:
             bb = dict(name="dit3d", variant="full", pos_emb_type="rope_3d", patch_size=1, hidden_size=1152, depth=28, num_heads=16)
-            model = dfot_amd.DiT3D(bb, x_shape=(16, 16, 16), max_tokens=5).cuda()
+            model = dfot_amd.DiT3D(bb, x_shape=(16, 16, 16), max_tokens=5, **ckw).cuda()
         cfg = dfot_amd.SamplerConfig(x_shape=(16, 16, 16), max_tokens=10 if diff else 5,
-                                     diffusion=dfot_amd.DiffusionConfig(sampling_timesteps=a.steps, beta_schedule="cosine", is_continuous=False))
+                                     diffusion=dfot_amd.DiffusionConfig(sampling_timesteps=a.steps, beta_schedule="cosine", is_continuous=False),
+                                     prediction_guidance=dict(name="vanilla", guidance_scale=1.5) if a.cond else {"name": "conditional"}, **skw)
         sampler = (dfot_amd.DifferenceDFoTVideoSampler if diff else dfot_amd.DFoTVideoSampler)(cfg, model, noise)
         xs = torch.randn(a.batch, 5, 16, 16, 16, generator=torch.Generator().manual_seed(a.seed))
         n_ctx = 2
@@ -73,13 +83,16 @@ def main():
     if a.inputs:
         data = np.load(a.inputs)
         xs = torch.from_numpy(data["xs"]).float()
-        conds = torch.from_numpy(data["conditions"]).float() if "conditions" in data.files else conds
+        if "conditions" in data.files:
+            conds = torch.from_numpy(data["conditions"])
+            conds = conds.float() if conds.is_floating_point() else conds.long()
     xs = xs.cuda()
     conds = None if conds is None else conds.cuda()
+    model.eval()  # (train() would draw the per-video dropout of a condition embedding)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     if a.model == "k600diff":
-        out = sampler._sample_all_videos(xs, n_context_tokens=n_ctx)["prediction"]
+        out = sampler._sample_all_videos(xs, n_context_tokens=n_ctx, conditions=conds)["prediction"]
     else:
         out = sampler._predict_videos(xs, n_context_tokens=n_ctx, conditions=conds)
     torch.cuda.synchronize()

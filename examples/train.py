@@ -40,6 +40,7 @@ def main():
     ap.add_argument("--lr", type=float, default=5e-5)
     ap.add_argument("--warmup-steps", type=int, default=10000, help="re10k: linear lr warm-up (constant_with_warmup, realestate10k_video_generation.yaml)")
     ap.add_argument("--save")
+    ap.add_argument("--cond", help="k600 / k600diff: train with a synthetic external condition, 'action:DIM' (action:3) or 'label:CLASSES' (label:101)")
     ap.add_argument("--pixels", action="store_true", help="k600 / k600diff: encode synthetic frames online with the VideoVAE encoder")
     ap.add_argument("--vae-ckpt", help="--pixels: reference VideoVAE checkpoint (vae.* keys); random encoder weights otherwise")
     a = ap.parse_args()
@@ -52,18 +53,28 @@ def main():
     if a.model == "re10k":
         return train_re10k(a, rank, world)
     diff = a.model == "k600diff"
+    ctype, cnum, ckw = None, 0, {}
+    if a.cond:
+        ctype, cnum = a.cond.split(":")[0], int(a.cond.split(":")[1])
+        ckw = dict(external_cond_type=ctype, external_cond_dim=cnum if ctype == "action" else 1,
+                   external_cond_num_classes=cnum if ctype == "label" else None)
+    gdrop = torch.Generator(device="cuda").manual_seed(3000 + rank)  # per-video dropout of the condition embedding
     if diff:
         cfg = dict(name="difference_dit3d", variant="factorized_matrix_attention", pos_emb_type="sinusoidal_2d", merge_type="interleaved",
                    patch_size=1, embed_col_dim=64, embed_row_dim=1152, num_heads=12, num_col_heads=1, num_row_heads=16, depth=28,
                    mlp_ratio=4.0, spatial_mlp_ratio=4.0, use_bias=True, matrix_block="matrix")
-        init = dfot_amd.DifferenceDiT3D(cfg, x_shape=(16, 16, 16), max_tokens=5)
+        if a.cond:
+            cfg["external_cond_dropout"] = 0.1
+        init = dfot_amd.DifferenceDiT3D(cfg, x_shape=(16, 16, 16), max_tokens=5, **ckw)
         sampling = dfot_amd.TrainingNoise(noise_level="random_uniform", is_continuous=False, n_context_tokens=2,
                                           variable_context=dfot_amd.ContextTraining(enabled=True, prob=0.25, dropout=0.3))
     else:
         cfg = dict(name="dit3d", variant="full", pos_emb_type="rope_3d", patch_size=1, hidden_size=1152, depth=28, num_heads=16)
-        init = dfot_amd.DiT3D(cfg, x_shape=(16, 16, 16), max_tokens=5)
+        if a.cond:
+            cfg["external_cond_dropout"] = 0.1
+        init = dfot_amd.DiT3D(cfg, x_shape=(16, 16, 16), max_tokens=5, **ckw)
         sampling = dfot_amd.TrainingNoise(noise_level="random_independent", is_continuous=False, n_context_tokens=2)
-    trainer = dfot_amd.DiT3DTrainer(cfg, x_shape=(16, 16, 16), max_tokens=5, lr=a.lr)
+    trainer = dfot_amd.DiT3DTrainer(cfg, x_shape=(16, 16, 16), max_tokens=5, lr=a.lr, **ckw)
     if a.ckpt:
         dfot_amd.load_reference_checkpoint(trainer, a.ckpt)
     else:
@@ -91,7 +102,14 @@ def main():
                 frames = torch.randn(a.batch, 5, 16, 16, 16, generator=g)
             noise = torch.randn(a.batch, 10 if diff else 5, 16, 16, 16, generator=g)
             levels, loss_masks = sampling.sample(a.batch, 5, masks, g, training=True)
-            loss = (trainer.difference_loss_and_grads if diff else trainer.loss_and_grads)(frames, levels, noise, loss_masks)
+            conds = None
+            if ctype == "action":
+                conds = torch.randn(a.batch, 5, cnum, generator=g)
+                conds[:, :1] = 0  # external_cond_processing: mask_first
+            elif ctype == "label":
+                conds = torch.randint(0, cnum, (a.batch, 1), generator=g)
+            loss = (trainer.difference_loss_and_grads if diff else trainer.loss_and_grads)(frames, levels, noise, loss_masks, conditions=conds,
+                                                                                           dropout_generator=gdrop)
             if a.accumulate > 1:
                 trainer.accumulate()
         trainer.optimizer_step(world)

@@ -159,7 +159,17 @@ typedef struct {
   int32_t num_row_heads;        /* 16 */
   int32_t temporal_mlp_hidden;  /* int(hidden * mlp_ratio) of the matrix blocks, 4608 */
   int32_t use_bias;             /* qkv_bias / proj_bias of MatrixAttention present */
+  /* external condition (BaseBackbone._build_external_cond_embedding, base_backbone.py:42-62; dmlab / minecraft: action, cond_ucf_101:
+   * label).  DFOT_COND_NONE registers exactly the parameters of a model without these fields.
+   *   action: external_cond_embedding[.embedding].linear_{1,2}.{weight,bias} = Linear(cond_dim, hidden) -> SiLU -> Linear(hidden, hidden);
+   *           the ".embedding" level exists when cond_dropout != 0 (RandomDropoutCondEmbedding, embeddings.py:364-387)
+   *   label:  external_cond_embedding.embedding_table.weight [num_classes + (cond_dropout != 0)][hidden] (the extra row is the null class) */
+  int32_t cond_type;     /* DFOT_COND_NONE / DFOT_COND_ACTION / DFOT_COND_LABEL */
+  int32_t cond_dim;      /* action: values per (video, token) */
+  int32_t num_classes;   /* label */
+  int32_t cond_dropout;  /* cfg.external_cond_dropout > 0 */
 } dfot_dit_config;
+enum { DFOT_COND_NONE = 0, DFOT_COND_ACTION = 1, DFOT_COND_LABEL = 2 };
 
 int dfot_dit_create(const dfot_dit_config* cfg, dfot_dit_t* out);
 int dfot_dit_destroy(dfot_dit_t h);
@@ -181,8 +191,15 @@ int dfot_dit_attn_timing(dfot_dit_t h, double* total_ms, int64_t* launches);
  * variant 1: x holds the interleaved (difference_0, frame_0, difference_1, ...) tokens, T even, (H/p)*(W/p) % 128 == 0. */
 int dfot_dit_forward(dfot_dit_t h, const float* x, const int32_t* noise_levels, float* out, int batch, int tokens,
                      void* stream);
+/* The same forward with an external condition per (video, token): `cond` fp32 [B,T,cond_dim] (action models) or `labels` int32 [B,T]
+ * (label models; rows outside the table are clamped), the other one NULL.  One kernel forms e = noise-level embedding (+ token kind,
+ * variant 1) + condition embedding per frame; videos whose `cond_mask` byte [B] is set (NULL: none) keep e without the condition and
+ * produce bit-for-bit the output of dfot_dit_forward.  The AdaLN modulations of the frames come from one GEMM over e instead of the
+ * per-level table; nothing after that differs.  No allocation, no host synchronisation: capturable in a graph. */
+int dfot_dit_forward_cond(dfot_dit_t h, const float* x, const int32_t* noise_levels, const float* cond, const int32_t* labels,
+                          const uint8_t* cond_mask, float* out, int batch, int tokens, void* stream);
 /* parity taps after the last forward: "emb" [timesteps][hidden] (noise-level embedding of every level),
- * "stream" [B*T*P][hidden] (residual stream after the last block) */
+ * "stream" [B*T*P][hidden] (residual stream after the last block), "cond_emb" [B*T][hidden] (e of the last conditioned forward) */
 int dfot_dit_read_tap(dfot_dit_t h, const char* name, float* out, size_t capacity_floats, void* stream);
 
 /* ---- DiT3D training path ("full" variant, attention-only blocks) ----------------------------------
@@ -207,6 +224,11 @@ int dfot_dit_train_reserve(dfot_dit_train_t h, int max_batch);
 int dfot_dit_train_sync_weights(dfot_dit_train_t h, void* stream);
 /* out = model(x, levels), saving what backward needs; x must stay valid until backward */
 int dfot_dit_train_forward(dfot_dit_train_t h, const float* x, const int32_t* noise_levels, float* out, int batch, int tokens, void* stream);
+/* dfot_dit_train_forward with the external condition (arguments as dfot_dit_forward_cond; cond_mask [B] is the per-video dropout mask the
+ * caller drew).  cond / labels are copied: only x must stay valid until backward, which then also fills the gradients of the condition
+ * embedding (label table: row-wise sums in frame order, rows of unused classes exactly zero; no floating-point atomics). */
+int dfot_dit_train_forward_cond(dfot_dit_train_t h, const float* x, const int32_t* noise_levels, const float* cond, const int32_t* labels,
+                                const uint8_t* cond_mask, float* out, int batch, int tokens, void* stream);
 /* grads <- d(sum(out * d_out))/d(params) for the last forward (overwrites the attached gradient buffer) */
 int dfot_dit_train_backward(dfot_dit_train_t h, const float* d_out, void* stream);
 /* dx[B,T,C,H,W] <- d(sum(out * d_out))/d(x) of the same forward / backward pair (call after dfot_dit_train_backward): what autograd gives
