@@ -332,6 +332,16 @@ int launch_matrix_attn(const bf16* z, bf16* o, int batch, int L, int E, int h, i
 }
 
 // ---- forward kernels --------------------------------------------------------------------------------------------
+// x[(b, t, p)][:] += tpos[t][:]: the temporal half of sinusoidal_factorized, added once after spatial block 0 (dit_base.py:408-411)
+__global__ __launch_bounds__(256) void add_temporal_pos_kernel(float* __restrict__ x, const float* __restrict__ tpos, int tokens, int P,
+                                                               int hidden4, long total4) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= total4) return;
+  const int c = (int)(i % hidden4), t = (int)((i / ((long)hidden4 * P)) % tokens);
+  float4v* xp = reinterpret_cast<float4v*>(x) + i;
+  *xp = *xp + reinterpret_cast<const float4v*>(tpos)[(long)t * hidden4 + c];
+}
+
 // PatchEmbed (Conv2d k = s = p): x [BT][C][H][W] fp32 -> tokens [BT*gh*gw][hidden] fp32.  8 tokens per workgroup so each
 // weight row is fetched once per 8 tokens; thread = output channels t, t+256, ...
 constexpr int PE_TOK = 8;
@@ -582,7 +592,8 @@ struct dfot_dit_s {
   bf16* w_mod = nullptr;  // every modulation Linear stacked: [ldt][hidden]
   std::vector<DitBlockW> blocks;
   std::vector<DitMatrixW> tblocks;  // variant 1: one MatrixDiTBlock after every spatial block
-  float *diff_table = nullptr, *pos2d = nullptr;
+  std::vector<DitBlockW> fblocks;   // variant 2: one temporal DiTBlock after every spatial block
+  float *diff_table = nullptr, *pos2d = nullptr, *tpos = nullptr;  // tpos: variant 2, temporal sinusoidal table [max_tokens][hidden]
   float *c_w1 = nullptr, *c_b1 = nullptr, *c_w2 = nullptr, *c_b2 = nullptr, *c_table = nullptr;  // external condition embedding
   int c_rows = 0;                    // label: rows of the embedding table (num_classes, + 1 null class with dropout)
   int mod_variant = GEMM_AUTO;       // GEMM tile form finalize() used for mod_table: the per-frame table uses the same one (bit-identical rows)
@@ -665,9 +676,9 @@ int dit_build(dfot_dit_s* h) {
   h->kpatch = c.in_channels * c.patch_size * c.patch_size;
   h->oc = h->kpatch;
   h->lpad = (c.timesteps + 255) / 256 * 256;
-  const bool facmat = c.variant == 1;
+  const bool facmat = c.variant == 1, fac = c.variant == 2;
   const int E = c.embed_col_dim, P = h->P;
-  const int per_block = (c.mlp_hidden ? 6 * hd : 3 * hd) + (facmat ? (c.temporal_mlp_hidden ? 6 * hd : 3 * hd) : 0);
+  const int per_block = (c.mlp_hidden ? 6 * hd : 3 * hd) + (facmat || fac ? (c.temporal_mlp_hidden ? 6 * hd : 3 * hd) : 0);
   h->ldt = (long)c.depth * per_block + 2 * hd;
   int rc = 0;
   // registration order == the reference module's state_dict order
@@ -693,10 +704,14 @@ int dit_build(dfot_dit_s* h) {
   if ((rc = dit_alloc(h, &h->w_mod, (size_t)h->ldt * hd))) return rc;
   if ((rc = dit_alloc(h, &h->b_mod, (size_t)h->ldt))) return rc;
   h->blocks.resize(c.depth);
+  if (fac) h->fblocks.resize(c.depth);
   long off = 0;
-  for (int i = 0; i < c.depth; ++i) {
-    DitBlockW& w = h->blocks[i];
-    const std::string pre = "dit_base.blocks." + std::to_string(i);
+  // spatial blocks first, then (variant 2) the temporal DiTBlocks: same members, MLP width temporal_mlp_hidden
+  for (int bi = 0; bi < (fac ? 2 : 1) * c.depth; ++bi) {
+    const bool temporal = bi >= c.depth;
+    const int i = bi % c.depth, mlp_hidden = temporal ? c.temporal_mlp_hidden : c.mlp_hidden;
+    DitBlockW& w = temporal ? h->fblocks[i] : h->blocks[i];
+    const std::string pre = (temporal ? "dit_base.temporal_blocks." : "dit_base.blocks.") + std::to_string(i);
     w.mod1 = off;
     dit_add_bf16(h, pre + ".norm1.modulation.1.weight", 3 * hd, hd, h->w_mod + off * hd);
     dit_add_slice(h, pre + ".norm1.modulation.1.bias", 3 * hd, h->b_mod + off);
@@ -707,16 +722,16 @@ int dit_build(dfot_dit_s* h) {
     if ((rc = dit_alloc(h, &w.w_proj, (size_t)hd * hd))) return rc;
     dit_add_bf16(h, pre + ".attn.proj.weight", hd, hd, w.w_proj);
     if ((rc = dit_add_f32(h, pre + ".attn.proj.bias", {hd}, &w.b_proj))) return rc;
-    if (c.mlp_hidden) {
+    if (mlp_hidden) {
       w.mod2 = off;
       dit_add_bf16(h, pre + ".norm2.modulation.1.weight", 3 * hd, hd, h->w_mod + off * hd);
       dit_add_slice(h, pre + ".norm2.modulation.1.bias", 3 * hd, h->b_mod + off);
       off += 3 * hd;
-      if ((rc = dit_alloc(h, &w.w_fc1, (size_t)c.mlp_hidden * hd))) return rc;
-      dit_add_bf16(h, pre + ".mlp.fc1.weight", c.mlp_hidden, hd, w.w_fc1);
-      if ((rc = dit_add_f32(h, pre + ".mlp.fc1.bias", {c.mlp_hidden}, &w.b_fc1))) return rc;
-      if ((rc = dit_alloc(h, &w.w_fc2, (size_t)hd * c.mlp_hidden))) return rc;
-      dit_add_bf16(h, pre + ".mlp.fc2.weight", hd, c.mlp_hidden, w.w_fc2);
+      if ((rc = dit_alloc(h, &w.w_fc1, (size_t)mlp_hidden * hd))) return rc;
+      dit_add_bf16(h, pre + ".mlp.fc1.weight", mlp_hidden, hd, w.w_fc1);
+      if ((rc = dit_add_f32(h, pre + ".mlp.fc1.bias", {mlp_hidden}, &w.b_fc1))) return rc;
+      if ((rc = dit_alloc(h, &w.w_fc2, (size_t)hd * mlp_hidden))) return rc;
+      dit_add_bf16(h, pre + ".mlp.fc2.weight", hd, mlp_hidden, w.w_fc2);
       if ((rc = dit_add_f32(h, pre + ".mlp.fc2.bias", {hd}, &w.b_fc2))) return rc;
     }
   }
@@ -783,7 +798,7 @@ int dit_build(dfot_dit_s* h) {
     for (int i = 0; i < half; ++i) f[i] = (float)std::exp(-std::log(10000.0) * (double)i / (double)half);
     DFOT_CHECK_HIP(hipMemcpy(h->freqs, f.data(), f.size() * sizeof(float), hipMemcpyHostToDevice));
   }
-  if (facmat) {
+  if (facmat || fac) {
     // sinusoidal_2d table [P][hidden] (get_nd_sincos_pos_embed, dit_base.py:527-572): np.meshgrid's default "xy" indexing
     // makes flattened entry m use position m % gh for the first half of the channels and m / gh for the second; each half
     // is [sin | cos] of pos * 10000^(-i/(half/2)), computed in float64 like numpy
@@ -800,6 +815,19 @@ int dit_build(dfot_dit_s* h) {
     }
     if ((rc = dit_alloc(h, &h->pos2d, pe.size()))) return rc;
     DFOT_CHECK_HIP(hipMemcpy(h->pos2d, pe.data(), pe.size() * sizeof(float), hipMemcpyHostToDevice));
+    if (fac) {
+      // temporal table [max_tokens][hidden] (SinusoidalPositionalEmbedding of the 1-D shape (max_tokens,), dit_base.py:268-271,552-572):
+      // [sin | cos] of t * 10000^(-i/(hidden/2)), in float64 like numpy
+      std::vector<float> te((size_t)c.max_tokens * hd);
+      for (int t = 0; t < c.max_tokens; ++t)
+        for (int i = 0; i < half; ++i) {
+          const double ang = (double)t / std::pow(10000.0, (double)i / (double)half);
+          te[(size_t)t * hd + i] = (float)std::sin(ang);
+          te[(size_t)t * hd + half + i] = (float)std::cos(ang);
+        }
+      if ((rc = dit_alloc(h, &h->tpos, te.size()))) return rc;
+      DFOT_CHECK_HIP(hipMemcpy(h->tpos, te.data(), te.size() * sizeof(float), hipMemcpyHostToDevice));
+    }
   } else {  // RoPE-3D (cos, sin) table [Tmax*P][d/2][2]; axis split of the head dim as RotaryEmbedding3D (embeddings.py:251-277)
     const int half = h->d / 2, q = half / 3, rem = half % 3;
     int parts[3] = {q, q, q};
@@ -856,7 +884,15 @@ int dfot_dit_create(const dfot_dit_config* cfg, dfot_dit_t* out) {
   DFOT_REQUIRE(c.mlp_hidden >= 0 && c.mlp_hidden % 64 == 0, DFOT_ERR_SHAPE, "mlp_hidden %d must be a multiple of 64", c.mlp_hidden);
   DFOT_REQUIRE(c.noise_dim > 0 && c.noise_dim % 2 == 0 && c.timesteps > 0 && c.max_tokens > 0 && c.depth > 0, DFOT_ERR_SHAPE,
                "bad noise_dim / timesteps / max_tokens / depth");
-  DFOT_REQUIRE(c.variant == 0 || c.variant == 1, DFOT_ERR_ARG, "variant %d unknown (0 = dit3d full/rope_3d, 1 = difference_dit3d factorized matrix)", c.variant);
+  DFOT_REQUIRE(c.variant == 0 || c.variant == 1 || c.variant == 2, DFOT_ERR_ARG,
+               "variant %d unknown (0 = dit3d full/rope_3d, 1 = difference_dit3d factorized matrix, 2 = dit3d factorized attention)", c.variant);
+  if (c.variant == 2) {
+    const int P = (c.height / c.patch_size) * (c.width / c.patch_size);
+    DFOT_REQUIRE(P % 128 == 0, DFOT_ERR_SHAPE, "factorized attention variant: %d patches per frame must be a multiple of 128", P);
+    DFOT_REQUIRE(c.max_tokens <= 32, DFOT_ERR_SHAPE, "factorized attention variant: max_tokens %d exceeds 32", c.max_tokens);
+    DFOT_REQUIRE(c.temporal_mlp_hidden >= 0 && c.temporal_mlp_hidden % 64 == 0, DFOT_ERR_SHAPE, "temporal_mlp_hidden %d must be a multiple of 64",
+                 c.temporal_mlp_hidden);
+  }
   if (c.variant == 1) {
     const int P = (c.height / c.patch_size) * (c.width / c.patch_size);
     DFOT_REQUIRE(P % 128 == 0, DFOT_ERR_SHAPE, "factorized matrix variant: %d patches per frame must be a multiple of 128", P);
@@ -961,7 +997,7 @@ int dfot_dit_reserve(dfot_dit_t h, int max_batch) {
   DFOT_CHECK_HIP(hipMemset(h->q, 0, qkv * sizeof(bf16)));
   DFOT_CHECK_HIP(hipMemset(h->k, 0, qkv * sizeof(bf16)));
   DFOT_CHECK_HIP(hipMemset(h->v, 0, qkv * sizeof(bf16)));
-  const int hid_cols = c.variant == 1 && c.temporal_mlp_hidden > c.mlp_hidden ? c.temporal_mlp_hidden : c.mlp_hidden;
+  const int hid_cols = c.variant != 0 && c.temporal_mlp_hidden > c.mlp_hidden ? c.temporal_mlp_hidden : c.mlp_hidden;
   if (hid_cols && (rc = dit_alloc(h, &h->hid, rows * hid_cols, true))) return rc;
   if (c.variant == 1) {
     const size_t frames = (size_t)max_batch * c.max_tokens;
@@ -1037,7 +1073,7 @@ static int dit_forward_impl(dfot_dit_t h, const float* x, const int32_t* noise_l
   DFOT_REQUIRE(n % 128 == 0, DFOT_ERR_SHAPE, "forward: sequence length %d (tokens x patches) must be a multiple of 128", n);
   hipStream_t s = (hipStream_t)stream;
   const long rows = (long)batch * n;
-  const bool facmat = c.variant == 1;
+  const bool facmat = c.variant == 1, fac = c.variant == 2;
   const int frames = batch * tokens, P = h->P, E = c.embed_col_dim;
   DFOT_REQUIRE(!facmat || tokens % 2 == 0, DFOT_ERR_SHAPE, "forward: %d tokens; the difference model takes (difference, frame) pairs", tokens);
   int max_level = c.timesteps - 1;
@@ -1096,24 +1132,40 @@ static int dit_forward_impl(dfot_dit_t h, const float* x, const int32_t* noise_l
     DFOT_CHECK_HIP(hipGetLastError());
     return DFOT_OK;
   };
-  // attention sequences: the whole video (variant 0) or one frame (variant 1, per-frame spatial blocks without RoPE)
-  const int seq = facmat ? P : n, nseq = facmat ? frames : batch;
-  for (size_t bi = 0; bi < h->blocks.size(); ++bi) {
-    const DitBlockW& w = h->blocks[bi];
-    if ((rc = ln_mod(w.mod1))) return rc;
+  // attention sequences: the whole video (variant 0) or one frame (variants 1 and 2, per-frame spatial blocks without RoPE)
+  const int seq = facmat || fac ? P : n, nseq = facmat || fac ? frames : batch;
+  // one DiTBlock: AdaLN -> q|k|v -> attention (over the sequences above, or over the frames of every patch position) -> gated projection -> MLP
+  auto dit_block = [&](const DitBlockW& w, int mlp_hidden, bool temporal) -> int {
+    int r2 = ln_mod(w.mod1);
+    if (r2) return r2;
     {
       GemmArgs g;
       g.A = h->A; g.lda = hd; g.W = w.w_qkv; g.M = (int)rows; g.N = 3 * hd; g.K = hd; g.bias = w.b_qkv;
-      g.q = h->q; g.k = h->k; g.v = h->v; g.rope_cs = facmat ? nullptr : h->rope_cs; g.heads = c.num_heads; g.d = h->d;
+      g.q = h->q; g.k = h->k; g.v = h->v; g.rope_cs = facmat || fac ? nullptr : h->rope_cs; g.heads = c.num_heads; g.d = h->d;
       g.dstride = h->dstride; g.ntok = seq; g.qscale = qscale;
-      if ((rc = launch_gemm(A_DENSE, E_QKV_DIT, h->gemm_variant, g, s))) return rc;
+      if ((r2 = launch_gemm(A_DENSE, E_QKV_DIT, h->gemm_variant, g, s))) return r2;
     }
     const bool timed = h->time_attn && h->ev_used < h->ev_start.size();
     if (timed) DFOT_CHECK_HIP(hipEventRecord(h->ev_start[h->ev_used], s));
-    if ((rc = launch_attention_padded(h->q, h->k, h->v, h->A, hd, nseq, c.num_heads, seq, h->d, s))) return rc;
+    if (temporal)
+      r2 = launch_attention_temporal(h->q, h->k, h->v, h->A, hd, batch, tokens, P, c.num_heads, h->d, s);
+    else
+      r2 = launch_attention_padded(h->q, h->k, h->v, h->A, hd, nseq, c.num_heads, seq, h->d, s);
+    if (r2) return r2;
     if (timed) DFOT_CHECK_HIP(hipEventRecord(h->ev_stop[h->ev_used++], s));
-    if ((rc = gated(h->A, hd, w.w_proj, w.b_proj, 0, w.mod1 + 2 * hd))) return rc;
-    if (c.mlp_hidden && (rc = mlp(w.mod2, c.mlp_hidden, w.w_fc1, w.b_fc1, w.w_fc2, w.b_fc2))) return rc;
+    if ((r2 = gated(h->A, hd, w.w_proj, w.b_proj, 0, w.mod1 + 2 * hd))) return r2;
+    return mlp_hidden ? mlp(w.mod2, mlp_hidden, w.w_fc1, w.b_fc1, w.w_fc2, w.b_fc2) : DFOT_OK;
+  };
+  for (size_t bi = 0; bi < h->blocks.size(); ++bi) {
+    if ((rc = dit_block(h->blocks[bi], c.mlp_hidden, false))) return rc;
+    if (fac) {
+      if (bi == 0) {  // sinusoidal_factorized: the temporal table enters after spatial block 0 (dit_base.py:408-411)
+        const long total4 = rows * (hd / 4);
+        hipLaunchKernelGGL(add_temporal_pos_kernel, dim3(cdiv(total4, 256)), dim3(256), 0, s, h->X, h->tpos, tokens, P, hd / 4, total4);
+        DFOT_CHECK_HIP(hipGetLastError());
+      }
+      if ((rc = dit_block(h->fblocks[bi], c.temporal_mlp_hidden, true))) return rc;
+    }
     if (!facmat) continue;
 
     // ---- MatrixDiTBlock: every frame is one token; qkv = U^T m V + bias, o = softmax(q k^T) v, out = U'^T o V' + bias' ----

@@ -131,6 +131,10 @@ int attention_dstride(int d);
 // lse (optional, training): [B][heads][N] fp32, log2-domain log-sum-exp of every query row
 int launch_attention_padded(const bf16* q, const bf16* k, const bf16* v, bf16* o, long ldo, int batch, int heads, int n, int d,
                             hipStream_t stream, float* lse = nullptr);
+// attention_temporal.hip: q, k, v [batch*tokens][heads][patches][dstride]; every (video, head, patch position) attends over its `tokens`
+// frames (1 .. 32); o [(video, frame, patch)][ldo] compact.  patches % 128 == 0, d % 4 == 0
+int launch_attention_temporal(const bf16* q, const bf16* k, const bf16* v, bf16* o, long ldo, int batch, int tokens, int patches, int heads,
+                              int d, hipStream_t s);
 // ---- attention forward: key split of the last round + scratch (attention_split.hip; shared by v3, v5 and ks) ----
 struct AttnSplit {
   int tiles, full, rem, nsplit;

@@ -2,7 +2,8 @@
 
 Mirrors the reference's plugin contract for this path:
   * constructor keywords of DiscreteDiffusion._build_model (algorithms/dfot/diffusion/discrete_diffusion.py:64-92)
-    and DiT3D.__init__ (algorithms/dfot/backbones/dit/dit3d.py:13-83): variant "full", pos_emb_type "rope_3d",
+    and DiT3D.__init__ (algorithms/dfot/backbones/dit/dit3d.py:13-83): variant "full" with pos_emb_type "rope_3d", and variant
+    "factorized_attention" with pos_emb_type "sinusoidal_factorized" (spatial + temporal blocks; inference only),
     external condition "action" / "label" (base_backbone.py:42-62), causal masking rejected exactly as the reference does;
   * ``forward(x, noise_levels, external_cond=None, external_cond_mask=None)`` (dit3d.py:146-192) with integer
     ``noise_levels`` -- the level index DiscreteDiffusion.model_predictions passes (discrete_diffusion.py:173-174);
@@ -114,16 +115,32 @@ class DiT3D(nn.Module):
         self._train_names = [n for n, _ in self.named_parameters()]
 
     def _configure(self, c: "capi.DiTConfig", cfg, max_tokens: int) -> None:
-        """dit3d.yaml keys -> engine config (variant 0)."""
-        if _get(cfg, "variant", "full") != "full":
-            raise ValueError(f"unsupported DiT variant {_get(cfg, 'variant')!r}: DiT3D builds 'full' (see DifferenceDiT3D)")
-        if _get(cfg, "pos_emb_type", "rope_3d") != "rope_3d":
-            raise ValueError("only pos_emb_type='rope_3d' is supported")
+        """dit3d.yaml / dit3d_factorized_attention.yaml keys -> engine config (variant 0 / variant 2)."""
+        variant = _get(cfg, "variant", "full")
+        pos = _get(cfg, "pos_emb_type", "rope_3d")
+        supported = "DiT3D builds variant='full' with pos_emb_type='rope_3d' and variant='factorized_attention' with " \
+                    "pos_emb_type='sinusoidal_factorized' (see DifferenceDiT3D for 'factorized_matrix_attention')"
+        if variant not in ("full", "factorized_attention"):
+            raise ValueError(f"unsupported DiT variant {variant!r}: {supported}")
+        if pos != ("rope_3d" if variant == "full" else "sinusoidal_factorized"):
+            raise ValueError(f"unsupported pos_emb_type {pos!r} for variant {variant!r}: {supported}")
         ratio = _get(cfg, "spatial_mlp_ratio", None)
         c.hidden_size = int(_get(cfg, "hidden_size"))
         c.max_tokens = max_tokens
         c.mlp_hidden = int(c.hidden_size * ratio) if ratio else 0
         c.variant = 0
+        if variant == "factorized_attention":
+            # per depth a per-frame spatial DiTBlock (spatial_mlp_ratio) and a temporal DiTBlock (mlp_ratio) over the frames of every
+            # patch position (dit_base.py:197-226, 364-417)
+            tratio = _get(cfg, "mlp_ratio", 4.0)
+            c.variant = 2
+            c.temporal_mlp_hidden = int(c.hidden_size * tratio) if tratio else 0
+            patches = (c.height // c.patch_size) * (c.width // c.patch_size)
+            if patches % 128 != 0:
+                raise ValueError(f"variant 'factorized_attention': x_shape {self.x_shape} with patch_size {c.patch_size} gives {patches} patches "
+                                 "per frame; the per-frame attention kernels need a multiple of 128 (the 64-patch recipes are not supported)")
+            if max_tokens > 32:
+                raise ValueError(f"variant 'factorized_attention': max_tokens {max_tokens} exceeds the temporal attention kernel's 32 frames")
 
     @property
     def in_channels(self) -> int:
@@ -244,6 +261,9 @@ class DiT3D(nn.Module):
             self._op_key = ops.register_model(self)
         params = [p for _, p in self.named_parameters()]
         train = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params))
+        if train and self._ccfg.variant == 2:
+            raise NotImplementedError("variant 'factorized_attention' is inference only: there is no training path and no input gradient "
+                                      "(reconstruction guidance); call it under torch.no_grad() / with parameters that do not require grad")
         if external_cond is not None:
             b, t = x.shape[:2]
             cond, labels = condition_tensors(self._ccfg, external_cond, b, t, self._ccfg.variant == 1)

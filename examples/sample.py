@@ -4,6 +4,7 @@
   python examples/sample.py re10k    [--ckpt DFoT_RE10K.ckpt] [--frames 8] [--steps 50] [--out out.npz]
   python examples/sample.py k600     [--ckpt K600.ckpt] [--batch 8]
   python examples/sample.py k600diff [--ckpt ...]
+  python examples/sample.py facdit   [--ckpt ...]   (FacDiT-XL, the taichikl recipe: 4x32x32 latents, patch 2, 16 frames)
 
 Without --ckpt the backbone gets seeded random weights (there is no network here to fetch the released checkpoints);
 with it, the reference's .ckpt / ema.safetensors is read by dfot_amd.load_reference_checkpoint (keys
@@ -25,7 +26,7 @@ from bench import RE10K, synth_poses  # noqa: E402
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("model", choices=["re10k", "k600", "k600diff"])
+    ap.add_argument("model", choices=["re10k", "k600", "k600diff", "facdit"])
     ap.add_argument("--ckpt")
     ap.add_argument("--inputs")
     ap.add_argument("--frames", type=int, default=8)
@@ -52,7 +53,8 @@ def main():
         conds = synth_poses(a.batch, a.frames, 100 + a.seed)
         n_ctx = 1
     else:
-        diff = a.model == "k600diff"
+        diff, fac = a.model == "k600diff", a.model == "facdit"
+        x_shape, tokens = ((4, 32, 32), 16) if fac else ((16, 16, 16), 5)
         ckw, skw = {}, {}
         if a.cond:
             ctype, num = a.cond.split(":")
@@ -60,20 +62,24 @@ def main():
                        external_cond_num_classes=int(num) if ctype == "label" else None)
             skw = dict(external_cond_type=ctype, external_cond_dim=ckw["external_cond_dim"], external_cond_processing="mask_first" if ctype == "action" else None)
             g = torch.Generator().manual_seed(200 + a.seed)
-            conds = torch.randn(a.batch, 5, int(num), generator=g) if ctype == "action" else torch.randint(0, int(num), (a.batch, 1), generator=g)
+            conds = torch.randn(a.batch, tokens, int(num), generator=g) if ctype == "action" else torch.randint(0, int(num), (a.batch, 1), generator=g)
         if diff:
             bb = dict(name="difference_dit3d", variant="factorized_matrix_attention", pos_emb_type="sinusoidal_2d", merge_type="interleaved",
                       patch_size=1, embed_col_dim=64, embed_row_dim=1152, num_heads=12, num_col_heads=1, num_row_heads=16, depth=28,
                       mlp_ratio=4.0, spatial_mlp_ratio=4.0, use_bias=True, matrix_block="matrix")
             model = dfot_amd.DifferenceDiT3D(bb, x_shape=(16, 16, 16), max_tokens=5, **ckw).cuda()
+        elif fac:  # per depth a per-frame spatial block and a temporal block over the 16 frames of every patch position (inference only)
+            bb = dict(name="dit3d", variant="factorized_attention", pos_emb_type="sinusoidal_factorized", patch_size=2, hidden_size=1152,
+                      depth=28, num_heads=16, mlp_ratio=4.0, spatial_mlp_ratio=0.0)
+            model = dfot_amd.DiT3D(bb, x_shape=x_shape, max_tokens=tokens, **ckw).cuda()
         else:
             bb = dict(name="dit3d", variant="full", pos_emb_type="rope_3d", patch_size=1, hidden_size=1152, depth=28, num_heads=16)
-            model = dfot_amd.DiT3D(bb, x_shape=(16, 16, 16), max_tokens=5, **ckw).cuda()
-        cfg = dfot_amd.SamplerConfig(x_shape=(16, 16, 16), max_tokens=10 if diff else 5,
+            model = dfot_amd.DiT3D(bb, x_shape=x_shape, max_tokens=tokens, **ckw).cuda()
+        cfg = dfot_amd.SamplerConfig(x_shape=x_shape, max_tokens=10 if diff else tokens,
                                      diffusion=dfot_amd.DiffusionConfig(sampling_timesteps=a.steps, beta_schedule="cosine", is_continuous=False),
                                      prediction_guidance=dict(name="vanilla", guidance_scale=1.5) if a.cond else {"name": "conditional"}, **skw)
         sampler = (dfot_amd.DifferenceDFoTVideoSampler if diff else dfot_amd.DFoTVideoSampler)(cfg, model, noise)
-        xs = torch.randn(a.batch, 5, 16, 16, 16, generator=torch.Generator().manual_seed(a.seed))
+        xs = torch.randn(a.batch, tokens, *x_shape, generator=torch.Generator().manual_seed(a.seed))
         n_ctx = 2
     if a.ckpt:
         ignored = dfot_amd.load_reference_checkpoint(model, a.ckpt)

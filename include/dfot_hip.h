@@ -152,12 +152,17 @@ typedef struct {
    *   configurations/algorithm/backbone/difference_dit3d_factorized_matrix.yaml + shortcut/FacMatDiT/group_XL/XL-64-1.yaml):
    *   per depth one per-frame spatial DiTBlock (num_heads heads, MLP mlp_hidden) and one MatrixDiTBlock whose attention
    *   treats every frame as ONE token (a P x hidden matrix projected by left/right factors, dit_blocks.py:211-350);
-   *   max_tokens counts the merged (difference, frame) tokens = 2 x the algorithm's max_tokens; hidden_size = embed_row_dim */
+   *   max_tokens counts the merged (difference, frame) tokens = 2 x the algorithm's max_tokens; hidden_size = embed_row_dim
+   * variant 2: DiT3D "factorized_attention" + sinusoidal_factorized (configurations/algorithm/backbone/dit3d_factorized_attention.yaml
+   *   + shortcut/FacDiT; dit_base.py:197-226,364-417): per depth one per-frame spatial DiTBlock (MLP mlp_hidden, 0 = none) and one
+   *   temporal DiTBlock (MLP temporal_mlp_hidden, 0 = none) whose attention runs over the T frames of one patch position; the 2-D
+   *   sinusoidal table is added at the patch embedding, the 1-D temporal table [max_tokens][hidden] after spatial block 0.
+   *   Uses hidden_size, num_heads, mlp_hidden, temporal_mlp_hidden; (H/p)*(W/p) % 128 == 0, max_tokens <= 32; inference only. */
   int32_t variant;
   int32_t embed_col_dim;        /* 64 */
   int32_t num_col_heads;        /* 1 */
   int32_t num_row_heads;        /* 16 */
-  int32_t temporal_mlp_hidden;  /* int(hidden * mlp_ratio) of the matrix blocks, 4608 */
+  int32_t temporal_mlp_hidden;  /* int(hidden * mlp_ratio) of the matrix blocks (variant 1) / temporal blocks (variant 2), 4608 */
   int32_t use_bias;             /* qkv_bias / proj_bias of MatrixAttention present */
   /* external condition (BaseBackbone._build_external_cond_embedding, base_backbone.py:42-62; dmlab / minecraft: action, cond_ucf_101:
    * label).  DFOT_COND_NONE registers exactly the parameters of a model without these fields.
@@ -188,7 +193,8 @@ int dfot_dit_set_option(dfot_dit_t h, const char* key, int value);
 int dfot_dit_attn_timing(dfot_dit_t h, double* total_ms, int64_t* launches);
 /* out[B,T,C,H,W] = model(x[B,T,C,H,W], noise_levels[B,T]) ; x/out fp32, noise_levels int32 in [0, timesteps)
  * (device pointer; out-of-range levels are clamped), T <= max_tokens with T*(H/p)*(W/p) % 128 == 0.
- * variant 1: x holds the interleaved (difference_0, frame_0, difference_1, ...) tokens, T even, (H/p)*(W/p) % 128 == 0. */
+ * variant 1: x holds the interleaved (difference_0, frame_0, difference_1, ...) tokens, T even, (H/p)*(W/p) % 128 == 0.
+ * variant 2: any 1 <= T <= max_tokens (the temporal table's first T rows are used), (H/p)*(W/p) % 128 == 0. */
 int dfot_dit_forward(dfot_dit_t h, const float* x, const int32_t* noise_levels, float* out, int batch, int tokens,
                      void* stream);
 /* The same forward with an external condition per (video, token): `cond` fp32 [B,T,cond_dim] (action models) or `labels` int32 [B,T]
@@ -341,6 +347,12 @@ int dfot_op_attention(const void* q, const void* k, const void* v, void* o, int 
  * pad columns are zero; o[B,N,heads*d] is compact (row stride ldo) */
 int dfot_op_attention_padded(const void* q, const void* k, const void* v, void* o, int ldo, int batch, int heads, int n,
                              int d, void* stream);
+/* temporal attention of the factorized-attention DiT: q, k, v [batch*tokens][heads][patches][dstride] bf16 as above (what the per-frame
+ * QKV epilogue writes; q pre-scaled); for every (video, head, patch position) the `tokens` frames of the video attend to each other.
+ * o[(video, frame, patch)][heads*d] compact (row stride ldo).  1 <= tokens <= 32, d % 4 == 0, d <= 128, patches % 128 == 0, ldo a
+ * multiple of 8 (4 when d % 8 != 0) covering heads*d; anything else: DFOT_ERR_SHAPE */
+int dfot_op_attention_temporal(const void* q, const void* k, const void* v, void* o, int ldo, int batch, int tokens, int patches,
+                               int heads, int d, void* stream);
 /* training path, test entry: o = attention(q, k, v) as above and, for the upstream gradient d_o [B*N][ldo] (same compact layout as
  * o), dq / dk / dv in the layout of q / k / v; dq is the gradient of the UNSCALED q (q itself is passed pre-multiplied by
  * log2(e)/sqrt(d), as the forward wants it).  Replaces torch autograd through F.scaled_dot_product_attention

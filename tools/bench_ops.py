@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Micro-benchmarks of the C-ABI primitives at the RE10K model shapes (model batch 2), HIP-event timed.
-Usage (GPU box): python tools/bench_ops.py [gemm] [conv] [attn] [vae_encode]"""
+Usage (GPU box): python tools/bench_ops.py [gemm] [conv] [attn] [tattn] [vae_encode]"""
 import ctypes as C
 import math
 import os
@@ -53,6 +53,35 @@ def attn(b, heads, n, d, variant):
     o = torch.empty(b, n, heads * d, device="cuda", dtype=torch.bfloat16)
     ms = timeit(lambda: capi.check(capi.lib.dfot_op_attention(P(q), P(k), P(v), P(o), heads * d, b, heads, n, d, variant, S())))
     return ms, 4.0 * b * heads * n * n * d / ms / 1e9
+
+
+HBM_TBS = 8.0  # the HBM3E rate the repository's rooflines use
+
+
+def tattn(b, heads, tokens, patches, d):
+    """temporal attention of the factorized-attention DiT: us and GB/s against the kernel's algorithmic bytes, (3 dstride + d) * 2 per
+    (row, head): q, k, v rows as the QKV epilogue stores them (pad columns included) read once, the compact output written once"""
+    ds = 64 if d <= 64 else 128
+    q, k, v = (torch.zeros(b * tokens, heads, patches, ds, device="cuda", dtype=torch.bfloat16) for _ in range(3))
+    for t, mul in ((q, 0.2), (k, 1.0), (v, 1.0)):
+        t[..., :d] = (torch.randn(b * tokens, heads, patches, d, device="cuda") * mul).bfloat16()
+    o = torch.empty(b * tokens * patches, heads * d, device="cuda", dtype=torch.bfloat16)
+    ms = timeit(lambda: capi.check(capi.lib.dfot_op_attention_temporal(P(q), P(k), P(v), P(o), heads * d, b, tokens, patches, heads, d, S())),
+                iters=50, warm=5)
+    nbytes = b * tokens * patches * heads * (3 * ds + d) * 2.0
+    return ms, nbytes / ms / 1e6, 4.0 * b * heads * patches * tokens * tokens * d / ms / 1e9
+
+
+def facdit_forward(b):
+    """whole forward of FacDiT-XL at the taichikl shape (4x32x32 latents, patch 2, 16 frames), ms; attention launches timed on their own"""
+    bb = dict(name="dit3d", variant="factorized_attention", pos_emb_type="sinusoidal_factorized", patch_size=2, hidden_size=1152, depth=28,
+              num_heads=16, mlp_ratio=4.0, spatial_mlp_ratio=0.0)
+    model = dfot_amd.DiT3D(bb, x_shape=(4, 32, 32), max_tokens=16).cuda().eval()
+    model.init_random(0)
+    x = torch.randn(b, 16, 4, 32, 32, device="cuda")
+    k = torch.randint(0, 1000, (b, 16), device="cuda")
+    with torch.no_grad():
+        return timeit(lambda: model(x, k), iters=10, warm=3)
 
 
 def vae_encode(b=2, t=17, res=128):
@@ -138,6 +167,14 @@ def main():
             for v in variants:
                 ms, tf = conv(bt, h, w, ci, co, v)
                 print(f"conv {name:8s} {bt}x{h}x{w} {ci}->{co} variant={v}: {ms*1e3:8.1f} us  {tf:7.1f} TF/s", flush=True)
+    if "tattn" in what:
+        for name, (b, hd, t, pn, d) in {"XL B2": (2, 16, 16, 256, 72), "XL B16": (16, 16, 16, 256, 72), "S B2": (2, 6, 16, 256, 64),
+                                        "S B16": (16, 6, 16, 256, 64)}.items():
+            ms, gbs, tf = tattn(b, hd, t, pn, d)
+            print(f"tattn {name:6s} B={b} H={hd} T={t} P={pn} d={d}: {ms*1e3:8.1f} us  {gbs:7.1f} GB/s ({gbs / 1e3 / HBM_TBS:.2f} of {HBM_TBS:.0f} TB/s HBM)  "
+                  f"{tf:6.2f} TF/s", flush=True)
+        for b in (2, 16):
+            print(f"facdit XL forward B={b} x 16 frames x 256 patches: {facdit_forward(b):.3f} ms", flush=True)
     if "attn" in what:
         shapes = {"L2": (2, 9, 8192, 64), "L3": (2, 9, 2048, 128), "L2 Bm8": (8, 9, 8192, 64)}
         if os.environ.get("ATTN_SHAPE"):  # e.g. ATTN_SHAPE=2,8,2048,128: one extra shape (workgroup-count experiments)
