@@ -39,6 +39,7 @@ class DiTConfig(C.Structure):
         ("variant", C.c_int32), ("embed_col_dim", C.c_int32), ("num_col_heads", C.c_int32), ("num_row_heads", C.c_int32),
         ("temporal_mlp_hidden", C.c_int32), ("use_bias", C.c_int32),
         ("cond_type", C.c_int32), ("cond_dim", C.c_int32), ("num_classes", C.c_int32), ("cond_dropout", C.c_int32),
+        ("use_temporal_rope", C.c_int32),
     ]
 
 
@@ -139,6 +140,8 @@ SIGNATURES = {
     "dfot_op_attention": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "dfot_op_attention_padded": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "dfot_op_attention_temporal": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "dfot_op_matrix_attention_rope": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P]),
+    "dfot_op_matrix_attention": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _F, _P]),
     "dfot_op_attention_bwd": (_I, [_P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _P]),
     "dfot_op_conv3x3_bwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "dfot_op_conv3x3_bwd2": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),

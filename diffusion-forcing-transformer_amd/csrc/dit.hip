@@ -591,9 +591,10 @@ struct dfot_dit_s {
         *fin_w = nullptr, *fin_b = nullptr, *b_mod = nullptr;
   bf16* w_mod = nullptr;  // every modulation Linear stacked: [ldt][hidden]
   std::vector<DitBlockW> blocks;
-  std::vector<DitMatrixW> tblocks;  // variant 1: one MatrixDiTBlock after every spatial block
+  std::vector<DitMatrixW> tblocks;  // variants 1 and 3: one MatrixDiTBlock after every spatial block
   std::vector<DitBlockW> fblocks;   // variant 2: one temporal DiTBlock after every spatial block
   float *diff_table = nullptr, *pos2d = nullptr, *tpos = nullptr;  // tpos: variant 2, temporal sinusoidal table [max_tokens][hidden]
+  float* trope = nullptr;  // variant 3 with use_temporal_rope: (cos, sin) [max_tokens][hd/2][2] of the matrix attention's RoPE-1D
   float *c_w1 = nullptr, *c_b1 = nullptr, *c_w2 = nullptr, *c_b2 = nullptr, *c_table = nullptr;  // external condition embedding
   int c_rows = 0;                    // label: rows of the embedding table (num_classes, + 1 null class with dropout)
   int mod_variant = GEMM_AUTO;       // GEMM tile form finalize() used for mod_table: the per-frame table uses the same one (bit-identical rows)
@@ -676,7 +677,7 @@ int dit_build(dfot_dit_s* h) {
   h->kpatch = c.in_channels * c.patch_size * c.patch_size;
   h->oc = h->kpatch;
   h->lpad = (c.timesteps + 255) / 256 * 256;
-  const bool facmat = c.variant == 1, fac = c.variant == 2;
+  const bool diffm = c.variant == 1, facmat = c.variant == 1 || c.variant == 3, fac = c.variant == 2;  // diffm: the difference front end
   const int E = c.embed_col_dim, P = h->P;
   const int per_block = (c.mlp_hidden ? 6 * hd : 3 * hd) + (facmat || fac ? (c.temporal_mlp_hidden ? 6 * hd : 3 * hd) : 0);
   h->ldt = (long)c.depth * per_block + 2 * hd;
@@ -700,7 +701,7 @@ int dit_build(dfot_dit_s* h) {
   }
   if ((rc = dit_add_f32(h, "patch_embedder.proj.weight", {hd, c.in_channels, c.patch_size, c.patch_size}, &h->pe_w))) return rc;
   if ((rc = dit_add_f32(h, "patch_embedder.proj.bias", {hd}, &h->pe_b))) return rc;
-  if (facmat && (rc = dit_add_f32(h, "diff_embedder.embedding_table.weight", {2, hd}, &h->diff_table))) return rc;
+  if (diffm && (rc = dit_add_f32(h, "diff_embedder.embedding_table.weight", {2, hd}, &h->diff_table))) return rc;
   if ((rc = dit_alloc(h, &h->w_mod, (size_t)h->ldt * hd))) return rc;
   if ((rc = dit_alloc(h, &h->b_mod, (size_t)h->ldt))) return rc;
   h->blocks.resize(c.depth);
@@ -789,7 +790,7 @@ int dit_build(dfot_dit_s* h) {
   if ((rc = dit_alloc(h, &h->feat, (size_t)h->lpad * c.noise_dim))) return rc;
   if ((rc = dit_alloc(h, &h->thid, (size_t)h->lpad * hd))) return rc;
   if ((rc = dit_alloc(h, &h->emb, (size_t)h->lpad * hd))) return rc;
-  const int nflag = facmat ? 2 : 1;  // variant 1: the conditioning also depends on the token kind (difference / frame)
+  const int nflag = diffm ? 2 : 1;  // variant 1: the conditioning also depends on the token kind (difference / frame)
   if ((rc = dit_alloc(h, &h->semb, (size_t)nflag * h->lpad * hd))) return rc;
   if ((rc = dit_alloc(h, &h->mod_table, (size_t)nflag * h->lpad * h->ldt))) return rc;
   {
@@ -827,6 +828,20 @@ int dit_build(dfot_dit_s* h) {
         }
       if ((rc = dit_alloc(h, &h->tpos, te.size()))) return rc;
       DFOT_CHECK_HIP(hipMemcpy(h->tpos, te.data(), te.size() * sizeof(float), hipMemcpyHostToDevice));
+    }
+    if (c.variant == 3 && c.use_temporal_rope) {
+      // RotaryEmbedding1D(dim = embed_row_dim / num_row_heads, seq_len = max_tokens) (dit_base.py:297-306; embeddings.py:193-202):
+      // angle = frame * theta^(-2i/dim) for the pair i of every matrix row, in float64
+      const int dim = hd / c.num_row_heads, pairs = dim / 2;
+      std::vector<float> cs((size_t)c.max_tokens * pairs * 2);
+      for (int t = 0; t < c.max_tokens; ++t)
+        for (int i = 0; i < pairs; ++i) {
+          const double ang = (double)t * std::pow((double)c.rope_theta, -2.0 * (double)i / (double)dim);
+          cs[((size_t)t * pairs + i) * 2 + 0] = (float)std::cos(ang);
+          cs[((size_t)t * pairs + i) * 2 + 1] = (float)std::sin(ang);
+        }
+      if ((rc = dit_alloc(h, &h->trope, cs.size()))) return rc;
+      DFOT_CHECK_HIP(hipMemcpy(h->trope, cs.data(), cs.size() * sizeof(float), hipMemcpyHostToDevice));
     }
   } else {  // RoPE-3D (cos, sin) table [Tmax*P][d/2][2]; axis split of the head dim as RotaryEmbedding3D (embeddings.py:251-277)
     const int half = h->d / 2, q = half / 3, rem = half % 3;
@@ -884,8 +899,9 @@ int dfot_dit_create(const dfot_dit_config* cfg, dfot_dit_t* out) {
   DFOT_REQUIRE(c.mlp_hidden >= 0 && c.mlp_hidden % 64 == 0, DFOT_ERR_SHAPE, "mlp_hidden %d must be a multiple of 64", c.mlp_hidden);
   DFOT_REQUIRE(c.noise_dim > 0 && c.noise_dim % 2 == 0 && c.timesteps > 0 && c.max_tokens > 0 && c.depth > 0, DFOT_ERR_SHAPE,
                "bad noise_dim / timesteps / max_tokens / depth");
-  DFOT_REQUIRE(c.variant == 0 || c.variant == 1 || c.variant == 2, DFOT_ERR_ARG,
-               "variant %d unknown (0 = dit3d full/rope_3d, 1 = difference_dit3d factorized matrix, 2 = dit3d factorized attention)", c.variant);
+  DFOT_REQUIRE(c.variant == 0 || c.variant == 1 || c.variant == 2 || c.variant == 3, DFOT_ERR_ARG,
+               "variant %d unknown (0 = dit3d full/rope_3d, 1 = difference_dit3d factorized matrix, 2 = dit3d factorized attention, "
+               "3 = dit3d factorized matrix)", c.variant);
   if (c.variant == 2) {
     const int P = (c.height / c.patch_size) * (c.width / c.patch_size);
     DFOT_REQUIRE(P % 128 == 0, DFOT_ERR_SHAPE, "factorized attention variant: %d patches per frame must be a multiple of 128", P);
@@ -904,6 +920,19 @@ int dfot_dit_create(const dfot_dit_config* cfg, dfot_dit_t* out) {
     DFOT_REQUIRE(c.max_tokens % 2 == 0 && c.max_tokens <= 32, DFOT_ERR_SHAPE, "max_tokens %d must be even (difference, frame pairs) and <= 32", c.max_tokens);
     DFOT_REQUIRE(c.temporal_mlp_hidden >= 0 && c.temporal_mlp_hidden % 64 == 0 && c.hidden_size % 4 == 0 && (c.hidden_size / 2) % 2 == 0,
                  DFOT_ERR_SHAPE, "temporal_mlp_hidden %d must be a multiple of 64", c.temporal_mlp_hidden);
+  }
+  if (c.variant == 3) {
+    const int P = (c.height / c.patch_size) * (c.width / c.patch_size);
+    DFOT_REQUIRE(P % 128 == 0, DFOT_ERR_SHAPE, "factorized matrix variant: %d patches per frame must be a multiple of 128", P);
+    DFOT_REQUIRE(c.embed_col_dim > 0 && c.embed_col_dim % 64 == 0, DFOT_ERR_SHAPE, "embed_col_dim %d must be a multiple of 64", c.embed_col_dim);
+    DFOT_REQUIRE(c.num_col_heads > 0 && c.embed_col_dim % c.num_col_heads == 0 && c.num_row_heads > 0 &&
+                     c.hidden_size % c.num_row_heads == 0 && (c.hidden_size / c.num_row_heads) % 4 == 0,
+                 DFOT_ERR_SHAPE, "matrix attention heads (%d col, %d row) do not divide (%d, %d)", c.num_col_heads, c.num_row_heads,
+                 c.embed_col_dim, c.hidden_size);
+    DFOT_REQUIRE(c.max_tokens <= 32, DFOT_ERR_SHAPE, "factorized matrix variant: max_tokens %d exceeds 32", c.max_tokens);
+    DFOT_REQUIRE(c.temporal_mlp_hidden >= 0 && c.temporal_mlp_hidden % 64 == 0, DFOT_ERR_SHAPE, "temporal_mlp_hidden %d must be a multiple of 64",
+                 c.temporal_mlp_hidden);
+    DFOT_REQUIRE(c.rope_theta > 0.f || !c.use_temporal_rope, DFOT_ERR_ARG, "rope_theta %g must be positive", (double)c.rope_theta);
   }
   DFOT_REQUIRE(c.cond_type == DFOT_COND_NONE || c.cond_type == DFOT_COND_ACTION || c.cond_type == DFOT_COND_LABEL, DFOT_ERR_ARG,
                "cond_type %d unknown (0 = none, 1 = action, 2 = label)", c.cond_type);
@@ -1007,6 +1036,18 @@ int dfot_dit_reserve(dfot_dit_t h, int max_batch) {
     if ((rc = dit_alloc(h, &h->Z, frames * c.embed_col_dim * 3 * c.hidden_size, true))) return rc;
     if ((rc = dit_alloc(h, &h->idx, frames, true))) return rc;
   }
+  if (c.variant == 3) {
+    // the factor GEMMs of the matrix blocks take whole 128-row tiles: frames * E and frames * hidden rows, both multiples of 64, so an odd
+    // frame count runs them on one more frame.  That frame holds the zeros written here or a real frame of an earlier, larger call (the
+    // transposes and the attention kernel touch the real frames only): finite operands whose products are never read.
+    const size_t frames = (size_t)max_batch * c.max_tokens + 1, fe = frames * c.embed_col_dim * c.hidden_size;
+    if ((rc = dit_alloc(h, &h->T1, frames * h->P * c.hidden_size, true))) return rc;
+    if ((rc = dit_alloc(h, &h->W1, fe, true)) || (rc = dit_alloc(h, &h->W2, fe, true)) || (rc = dit_alloc(h, &h->Z, 3 * fe, true))) return rc;
+    DFOT_CHECK_HIP(hipMemset(h->T1, 0, frames * h->P * c.hidden_size * sizeof(bf16)));
+    DFOT_CHECK_HIP(hipMemset(h->W1, 0, fe * sizeof(bf16)));
+    DFOT_CHECK_HIP(hipMemset(h->W2, 0, fe * sizeof(bf16)));
+    DFOT_CHECK_HIP(hipMemset(h->Z, 0, 3 * fe * sizeof(bf16)));
+  }
   if (c.cond_type != DFOT_COND_NONE) {
     const size_t frames = (size_t)max_batch * c.max_tokens;
     h->fpad = (int)((frames + 255) / 256 * 256);  // whole row tiles of every GEMM form finalize() may have picked
@@ -1073,9 +1114,10 @@ static int dit_forward_impl(dfot_dit_t h, const float* x, const int32_t* noise_l
   DFOT_REQUIRE(n % 128 == 0, DFOT_ERR_SHAPE, "forward: sequence length %d (tokens x patches) must be a multiple of 128", n);
   hipStream_t s = (hipStream_t)stream;
   const long rows = (long)batch * n;
-  const bool facmat = c.variant == 1, fac = c.variant == 2;
+  const bool diffm = c.variant == 1, facmat = c.variant == 1 || c.variant == 3, fac = c.variant == 2;
   const int frames = batch * tokens, P = h->P, E = c.embed_col_dim;
-  DFOT_REQUIRE(!facmat || tokens % 2 == 0, DFOT_ERR_SHAPE, "forward: %d tokens; the difference model takes (difference, frame) pairs", tokens);
+  const int gframes = c.variant == 3 ? (frames + 1) & ~1 : frames;  // frames of the matrix blocks' factor GEMMs (see reserve)
+  DFOT_REQUIRE(!diffm || tokens % 2 == 0, DFOT_ERR_SHAPE, "forward: %d tokens; the difference model takes (difference, frame) pairs", tokens);
   int max_level = c.timesteps - 1;
   const int* lvl = noise_levels;
   const float* table = h->mod_table;
@@ -1086,7 +1128,7 @@ static int dit_forward_impl(dfot_dit_t h, const float* x, const int32_t* noise_l
     CondEmbedArgs a;
     a.cond = cond; a.labels = labels; a.mask = cond_mask;
     a.w1 = h->c_w1; a.b1 = h->c_b1; a.w2 = h->c_w2; a.b2 = h->c_b2; a.table = h->c_table;
-    a.base = h->emb; a.levels = noise_levels; a.max_level = c.timesteps - 1; a.diff_table = facmat ? h->diff_table : nullptr;
+    a.base = h->emb; a.levels = noise_levels; a.max_level = c.timesteps - 1; a.diff_table = diffm ? h->diff_table : nullptr;
     a.e_out = h->cemb; a.semb = h->csemb; a.idx = h->cidx;
     a.tokens = tokens; a.cond_dim = c.cond_dim; a.hidden = hd; a.table_rows = h->c_rows;
     if ((rc = launch_cond_embed(a, frames, s))) return rc;
@@ -1098,7 +1140,7 @@ static int dit_forward_impl(dfot_dit_t h, const float* x, const int32_t* noise_l
     table = h->cmod;
     lvl = h->cidx;
     max_level = frames - 1;
-  } else if (facmat) {  // table row = level + lpad * (token kind)
+  } else if (diffm) {  // table row = level + lpad * (token kind)
     hipLaunchKernelGGL(make_index_kernel, dim3(cdiv(frames, 256)), dim3(256), 0, s, noise_levels, h->idx, frames, tokens, max_level, h->lpad);
     DFOT_CHECK_HIP(hipGetLastError());
     lvl = h->idx;
@@ -1174,25 +1216,28 @@ static int dit_forward_impl(dfot_dit_t h, const float* x, const int32_t* noise_l
     if ((rc = transpose(h->A, h->T1, P, hd))) return rc;  // m^T per frame: [hd][P]
     {
       GemmArgs g;  // left factor: w[frame][e][d] = sum_p U[p][e] m[frame][p][d]   (rows (frame, d), K = p, transposed store)
-      g.A = h->T1; g.lda = P; g.W = t.ut; g.M = frames * hd; g.N = E; g.K = P; g.out_bf16 = h->W1; g.ldo = E; g.tr_rows = hd;
+      g.A = h->T1; g.lda = P; g.W = t.ut; g.M = gframes * hd; g.N = E; g.K = P; g.out_bf16 = h->W1; g.ldo = E; g.tr_rows = hd;
       if ((rc = launch_gemm(A_DENSE, E_BF16, h->gemm_variant, g, s))) return rc;
     }
     {
       GemmArgs g;  // right factor + bias[e][k]
-      g.A = h->W1; g.lda = hd; g.W = t.vt; g.M = frames * E; g.N = 3 * hd; g.K = hd; g.bias = t.qkv_bias; g.bias_rows = t.qkv_bias ? E : 0;
+      g.A = h->W1; g.lda = hd; g.W = t.vt; g.M = gframes * E; g.N = 3 * hd; g.K = hd; g.bias = t.qkv_bias; g.bias_rows = t.qkv_bias ? E : 0;
       g.out_bf16 = h->Z; g.ldo = 3 * hd;
       if ((rc = launch_gemm(A_DENSE, E_BF16, h->gemm_variant, g, s))) return rc;
     }
     {
       const int hn = E / c.num_col_heads, hdr = hd / c.num_row_heads;
-      if ((rc = launch_matrix_attn(h->Z, h->W1, batch, tokens, E, hd, c.num_col_heads, c.num_row_heads,
-                                   1.0f / sqrtf((float)hn * (float)hdr), s)))
-        return rc;
+      const float mscale = 1.0f / sqrtf((float)hn * (float)hdr);
+      if (diffm)
+        rc = launch_matrix_attn(h->Z, h->W1, batch, tokens, E, hd, c.num_col_heads, c.num_row_heads, mscale, s);
+      else  // FacMatDiT: any 1 <= tokens <= 32, RoPE-1D over the frame axis when the model has one (trope == nullptr: none)
+        rc = launch_matrix_attn_rope(h->Z, h->W1, h->trope, batch, tokens, E, hd, c.num_col_heads, c.num_row_heads, mscale, s);
+      if (rc) return rc;
     }
     if ((rc = transpose(h->W1, h->W2, E, hd))) return rc;  // o^T per frame: [hd][E]
     {
       GemmArgs g;  // left factor of the projection: s[frame][p][d] = sum_e U'[e][p] o[frame][e][d]
-      g.A = h->W2; g.lda = E; g.W = t.put; g.M = frames * hd; g.N = P; g.K = E; g.out_bf16 = h->T1; g.ldo = P; g.tr_rows = hd;
+      g.A = h->W2; g.lda = E; g.W = t.put; g.M = gframes * hd; g.N = P; g.K = E; g.out_bf16 = h->T1; g.ldo = P; g.tr_rows = hd;
       if ((rc = launch_gemm(A_DENSE, E_BF16, h->gemm_variant, g, s))) return rc;
     }
     if ((rc = gated(h->T1, hd, t.pvt, t.proj_bias, t.proj_bias ? P : 0, t.mod1 + 2 * hd))) return rc;
@@ -1261,6 +1306,12 @@ int dfot_op_attention_bwd(const void* q, const void* k, const void* v, const voi
   (void)hipStreamSynchronize(s);
   (void)hipFree(lse); (void)hipFree(delta);
   return rc;
+}
+
+int dfot_op_matrix_attention(const void* z, void* o, int batch, int L, int E, int h, int cc, int rr, float scale, void* stream) {
+  DFOT_REQUIRE(z && o && batch > 0 && E > 0 && h > 0 && cc > 0 && rr > 0 && E % cc == 0 && h % rr == 0 && (h / rr) % 4 == 0, DFOT_ERR_SHAPE,
+               "matrix attention: batch %d, E %d, h %d, heads (%d, %d)", batch, E, h, cc, rr);
+  return launch_matrix_attn((const bf16*)z, (bf16*)o, batch, L, E, h, cc, rr, scale, (hipStream_t)stream);
 }
 
 int dfot_op_attention_padded(const void* q, const void* k, const void* v, void* o, int ldo, int batch, int heads, int n, int d,

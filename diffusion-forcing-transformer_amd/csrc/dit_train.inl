@@ -935,6 +935,7 @@ int dfot_dit_train_create(const dfot_dit_config* cfg, dfot_dit_train_t* out) {
   DFOT_REQUIRE(cfg && out, DFOT_ERR_ARG, "train_create: null argument");
   const dfot_dit_config& c = *cfg;
   DFOT_REQUIRE(c.variant != 2, DFOT_ERR_ARG, "train_create: variant 2 (factorized attention) has no training path; it is inference only");
+  DFOT_REQUIRE(c.variant != 3, DFOT_ERR_ARG, "train_create: variant 3 (factorized matrix DiT3D, FacMatDiT) has no training path; it is inference only");
   DFOT_REQUIRE(c.variant == 0 || c.variant == 1, DFOT_ERR_ARG, "train_create: unknown variant %d", c.variant);
   const bool facmat = c.variant == 1;
   DFOT_REQUIRE(c.mlp_hidden >= 0 && c.mlp_hidden % 128 == 0 && c.temporal_mlp_hidden >= 0 && c.temporal_mlp_hidden % 128 == 0, DFOT_ERR_ARG,

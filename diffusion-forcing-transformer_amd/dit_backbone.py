@@ -3,7 +3,8 @@
 Mirrors the reference's plugin contract for this path:
   * constructor keywords of DiscreteDiffusion._build_model (algorithms/dfot/diffusion/discrete_diffusion.py:64-92)
     and DiT3D.__init__ (algorithms/dfot/backbones/dit/dit3d.py:13-83): variant "full" with pos_emb_type "rope_3d", and variant
-    "factorized_attention" with pos_emb_type "sinusoidal_factorized" (spatial + temporal blocks; inference only),
+    "factorized_attention" with pos_emb_type "sinusoidal_factorized" (spatial + temporal blocks; inference only), and variant
+    "factorized_matrix_attention" with pos_emb_type "sinusoidal_2d" (FacMatDiT: spatial + matrix blocks, RoPE-1D over the frames; inference only),
     external condition "action" / "label" (base_backbone.py:42-62), causal masking rejected exactly as the reference does;
   * ``forward(x, noise_levels, external_cond=None, external_cond_mask=None)`` (dit3d.py:146-192) with integer
     ``noise_levels`` -- the level index DiscreteDiffusion.model_predictions passes (discrete_diffusion.py:173-174);
@@ -58,6 +59,62 @@ def condition_tensors(c: "capi.DiTConfig", external_cond: torch.Tensor, batch: i
             raise ValueError(f"external_cond (labels) has shape {tuple(lab.shape)}, expected {(batch, 1)} or {(batch, tokens)}")
         lab = lab.expand(batch, tokens)
     return None, lab.to(torch.int32).contiguous()
+
+
+def configure_facmat(c: "capi.DiTConfig", cfg, max_tokens: int) -> None:
+    """dit3d_factorized_matrix.yaml (+ the @FacMatDiT shortcuts) -> engine variant 3: per depth a per-frame spatial DiTBlock (num_heads,
+    spatial_mlp_ratio) and a MatrixDiTBlock (embed_col_dim x embed_row_dim, num_col_heads x num_row_heads, mlp_ratio, use_bias) whose
+    attention rotates q and k with a RoPE-1D over the frame axis when use_temporal_rope is set (dit_base.py:197-226, 297-306;
+    dit_blocks.py:289-342).  c.patch_size / height / width are already set.  Every unsupported key is refused by name."""
+    if _get(cfg, "matrix_block", "matrix") not in (None, "matrix"):
+        raise ValueError(f"matrix_block={_get(cfg, 'matrix_block')!r} is not supported: only matrix_block='matrix'")
+    if _get(cfg, "matrix_multi_token", False):
+        raise ValueError("matrix_multi_token=True is not supported: every frame is one token of the matrix attention")
+    rope = bool(_get(cfg, "use_temporal_rope", False))
+    if rope and _get(cfg, "flatten_matrix_rope", False):
+        raise ValueError("flatten_matrix_rope=True is not supported: the temporal RoPE rotates every row of the head matrix on its own")
+    if _get(cfg, "fixed_u", None):
+        raise ValueError(f"fixed_u={_get(cfg, 'fixed_u')!r} is not supported: the left factors qkv_u / proj_u are learned parameters")
+    ratio, tratio = _get(cfg, "spatial_mlp_ratio", None), _get(cfg, "mlp_ratio", None)
+    if ratio is None:
+        raise AssertionError("spatial_mlp_ratio must be specified for matrix attention")
+    if _get(cfg, "use_bias", None) is None:
+        raise AssertionError("use_bias must be specified for matrix attention")
+    patches = (c.height // c.patch_size) * (c.width // c.patch_size)
+    if patches % 128 != 0:
+        raise ValueError(f"variant 'factorized_matrix_attention': x_shape {(c.in_channels, c.height, c.width)} with patch_size {c.patch_size} gives "
+                         f"{patches} patches per frame; the per-frame kernels need a multiple of 128 (the 64-patch recipes are not supported)")
+    if max_tokens > 32:
+        raise ValueError(f"variant 'factorized_matrix_attention': max_tokens {max_tokens} exceeds the matrix attention kernel's 32 frames")
+    c.hidden_size = int(_get(cfg, "embed_row_dim"))
+    c.max_tokens = max_tokens
+    c.mlp_hidden = int(c.hidden_size * ratio) if ratio else 0
+    c.variant = 3
+    c.embed_col_dim = int(_get(cfg, "embed_col_dim"))
+    c.num_col_heads = int(_get(cfg, "num_col_heads"))
+    c.num_row_heads = int(_get(cfg, "num_row_heads"))
+    c.temporal_mlp_hidden = int(c.hidden_size * tratio) if tratio else 0
+    c.use_bias = int(bool(_get(cfg, "use_bias")))
+    c.use_temporal_rope = int(rope)
+
+
+def _init_random_matrix(tensors, seed: int) -> None:
+    """init_random of the models with matrix blocks: as DiT3D.init_random; the matrix factors are (in, out) matrices (fan-in = rows), their
+    biases ~ N(0, 0.05^2)"""
+    g = torch.Generator().manual_seed(seed)
+    with torch.no_grad():
+        for name, t in tensors.items():
+            leaf = name.rsplit(".", 1)[-1]
+            if leaf in ("bias", "qkv_bias", "proj_bias"):
+                v = 0.05 * torch.randn(t.shape, generator=g)
+            elif leaf in ("qkv_u", "proj_u", "qkv_v", "proj_v"):
+                v = torch.randn(t.shape, generator=g) / math.sqrt(t.shape[0])
+            elif name.startswith("diff_embedder"):
+                v = 0.3 * torch.randn(t.shape, generator=g)
+            else:
+                gain = 0.5 if ".modulation." in name else 1.0
+                v = gain * torch.randn(t.shape, generator=g) / math.sqrt(math.prod(t.shape[1:]))
+            t.copy_(v.to(t.device))
 
 
 class DiT3D(nn.Module):
@@ -115,16 +172,21 @@ class DiT3D(nn.Module):
         self._train_names = [n for n, _ in self.named_parameters()]
 
     def _configure(self, c: "capi.DiTConfig", cfg, max_tokens: int) -> None:
-        """dit3d.yaml / dit3d_factorized_attention.yaml keys -> engine config (variant 0 / variant 2)."""
+        """dit3d.yaml / dit3d_factorized_attention.yaml / dit3d_factorized_matrix.yaml keys -> engine config (variant 0 / 2 / 3)."""
         variant = _get(cfg, "variant", "full")
         pos = _get(cfg, "pos_emb_type", "rope_3d")
-        supported = "DiT3D builds variant='full' with pos_emb_type='rope_3d' and variant='factorized_attention' with " \
-                    "pos_emb_type='sinusoidal_factorized' (see DifferenceDiT3D for 'factorized_matrix_attention')"
-        if variant not in ("full", "factorized_attention"):
+        supported = "DiT3D builds variant='full' with pos_emb_type='rope_3d', variant='factorized_attention' with " \
+                    "pos_emb_type='sinusoidal_factorized' (see DifferenceDiT3D for 'factorized_matrix_attention' over difference tokens), " \
+                    "and variant='factorized_matrix_attention' with pos_emb_type='sinusoidal_2d'"
+        want_pos = {"full": "rope_3d", "factorized_attention": "sinusoidal_factorized", "factorized_matrix_attention": "sinusoidal_2d"}
+        if variant not in want_pos:
             raise ValueError(f"unsupported DiT variant {variant!r}: {supported}")
-        if pos != ("rope_3d" if variant == "full" else "sinusoidal_factorized"):
+        if pos != want_pos[variant]:
             raise ValueError(f"unsupported pos_emb_type {pos!r} for variant {variant!r}: {supported}")
         ratio = _get(cfg, "spatial_mlp_ratio", None)
+        if variant == "factorized_matrix_attention":
+            configure_facmat(c, cfg, max_tokens)
+            return
         c.hidden_size = int(_get(cfg, "hidden_size"))
         c.max_tokens = max_tokens
         c.mlp_hidden = int(c.hidden_size * ratio) if ratio else 0
@@ -181,6 +243,8 @@ class DiT3D(nn.Module):
         """Non-degenerate random weights for benchmarks (the reference zero-inits every modulation and the final
         projection, which makes the output identically zero): weights ~ N(0, 1/fan_in) (modulations at half gain),
         biases ~ N(0, 0.05^2) -- the distribution of oracle.dit.seeded_params."""
+        if self._ccfg.variant == 3:
+            return _init_random_matrix(self._tensors(), seed)
         g = torch.Generator().manual_seed(seed)
         with torch.no_grad():
             for name, t in self._tensors().items():
@@ -261,8 +325,9 @@ class DiT3D(nn.Module):
             self._op_key = ops.register_model(self)
         params = [p for _, p in self.named_parameters()]
         train = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params))
-        if train and self._ccfg.variant == 2:
-            raise NotImplementedError("variant 'factorized_attention' is inference only: there is no training path and no input gradient "
+        if train and self._ccfg.variant in (2, 3):
+            name = "factorized_attention" if self._ccfg.variant == 2 else "factorized_matrix_attention"
+            raise NotImplementedError(f"variant {name!r} is inference only: there is no training path and no input gradient "
                                       "(reconstruction guidance); call it under torch.no_grad() / with parameters that do not require grad")
         if external_cond is not None:
             b, t = x.shape[:2]
@@ -414,17 +479,4 @@ class DifferenceDiT3D(DiT3D):
 
     def init_random(self, seed: int = 0) -> None:
         """As DiT3D.init_random; the matrix factors are (in, out) matrices (fan-in = rows), their biases ~ N(0, 0.05^2)."""
-        g = torch.Generator().manual_seed(seed)
-        with torch.no_grad():
-            for name, t in self._tensors().items():
-                leaf = name.rsplit(".", 1)[-1]
-                if leaf in ("bias", "qkv_bias", "proj_bias"):
-                    v = 0.05 * torch.randn(t.shape, generator=g)
-                elif leaf in ("qkv_u", "proj_u", "qkv_v", "proj_v"):
-                    v = torch.randn(t.shape, generator=g) / math.sqrt(t.shape[0])
-                elif name.startswith("diff_embedder"):
-                    v = 0.3 * torch.randn(t.shape, generator=g)
-                else:
-                    gain = 0.5 if ".modulation." in name else 1.0
-                    v = gain * torch.randn(t.shape, generator=g) / math.sqrt(math.prod(t.shape[1:]))
-                t.copy_(v.to(t.device))
+        _init_random_matrix(self._tensors(), seed)

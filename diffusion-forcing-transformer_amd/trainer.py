@@ -44,6 +44,10 @@ class DiT3DTrainer:
             if _get(cfg, "pos_emb_type", "rope_3d") != "rope_3d":
                 raise ValueError("DiT3DTrainer builds the 'full' DiT3D with pos_emb_type='rope_3d'")
             c.variant, c.hidden_size, c.max_tokens = 0, int(_get(cfg, "hidden_size")), int(max_tokens)
+        elif variant == "factorized_matrix_attention" and _get(cfg, "use_temporal_rope", False):
+            # dit3d_factorized_matrix.yaml (FacMatDiT) shares variant and pos_emb_type with the difference model; building that one
+            # instead would double the tokens and drop the RoPE
+            raise ValueError("no training path for DiT variant 'factorized_matrix_attention' with use_temporal_rope (FacMatDiT): it is inference only")
         elif variant == "factorized_matrix_attention":  # DifferenceDiT3D (bash/k600): as dit_backbone.DifferenceDiT3D._configure
             if _get(cfg, "pos_emb_type") != "sinusoidal_2d" or _get(cfg, "merge_type", "interleaved") != "interleaved":
                 raise ValueError("the difference model trains with pos_emb_type='sinusoidal_2d' and merge_type='interleaved'")

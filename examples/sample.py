@@ -5,6 +5,7 @@
   python examples/sample.py k600     [--ckpt K600.ckpt] [--batch 8]
   python examples/sample.py k600diff [--ckpt ...]
   python examples/sample.py facdit   [--ckpt ...]   (FacDiT-XL, the taichikl recipe: 4x32x32 latents, patch 2, 16 frames)
+  python examples/sample.py facmat   [--ckpt ...]   (FacMatDiT XL-64-1, the same recipe: matrix attention with RoPE over the 16 frames)
 
 Without --ckpt the backbone gets seeded random weights (there is no network here to fetch the released checkpoints);
 with it, the reference's .ckpt / ema.safetensors is read by dfot_amd.load_reference_checkpoint (keys
@@ -26,7 +27,7 @@ from bench import RE10K, synth_poses  # noqa: E402
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("model", choices=["re10k", "k600", "k600diff", "facdit"])
+    ap.add_argument("model", choices=["re10k", "k600", "k600diff", "facdit", "facmat"])
     ap.add_argument("--ckpt")
     ap.add_argument("--inputs")
     ap.add_argument("--frames", type=int, default=8)
@@ -53,8 +54,8 @@ def main():
         conds = synth_poses(a.batch, a.frames, 100 + a.seed)
         n_ctx = 1
     else:
-        diff, fac = a.model == "k600diff", a.model == "facdit"
-        x_shape, tokens = ((4, 32, 32), 16) if fac else ((16, 16, 16), 5)
+        diff, fac, facmat = a.model == "k600diff", a.model == "facdit", a.model == "facmat"
+        x_shape, tokens = ((4, 32, 32), 16) if fac or facmat else ((16, 16, 16), 5)
         ckw, skw = {}, {}
         if a.cond:
             ctype, num = a.cond.split(":")
@@ -71,6 +72,11 @@ def main():
         elif fac:  # per depth a per-frame spatial block and a temporal block over the 16 frames of every patch position (inference only)
             bb = dict(name="dit3d", variant="factorized_attention", pos_emb_type="sinusoidal_factorized", patch_size=2, hidden_size=1152,
                       depth=28, num_heads=16, mlp_ratio=4.0, spatial_mlp_ratio=0.0)
+            model = dfot_amd.DiT3D(bb, x_shape=x_shape, max_tokens=tokens, **ckw).cuda()
+        elif facmat:  # per depth a per-frame spatial block and a matrix block whose attention takes every frame as one token (inference only)
+            bb = dict(name="dit3d", variant="factorized_matrix_attention", pos_emb_type="sinusoidal_2d", use_temporal_rope=True, patch_size=2,
+                      embed_col_dim=64, embed_row_dim=1152, num_heads=16, num_col_heads=1, num_row_heads=16, depth=28, mlp_ratio=4.0,
+                      spatial_mlp_ratio=4.0, use_bias=False, matrix_block="matrix", flatten_matrix_rope=False, matrix_multi_token=False)
             model = dfot_amd.DiT3D(bb, x_shape=x_shape, max_tokens=tokens, **ckw).cuda()
         else:
             bb = dict(name="dit3d", variant="full", pos_emb_type="rope_3d", patch_size=1, hidden_size=1152, depth=28, num_heads=16)

@@ -157,7 +157,12 @@ typedef struct {
    *   + shortcut/FacDiT; dit_base.py:197-226,364-417): per depth one per-frame spatial DiTBlock (MLP mlp_hidden, 0 = none) and one
    *   temporal DiTBlock (MLP temporal_mlp_hidden, 0 = none) whose attention runs over the T frames of one patch position; the 2-D
    *   sinusoidal table is added at the patch embedding, the 1-D temporal table [max_tokens][hidden] after spatial block 0.
-   *   Uses hidden_size, num_heads, mlp_hidden, temporal_mlp_hidden; (H/p)*(W/p) % 128 == 0, max_tokens <= 32; inference only. */
+   *   Uses hidden_size, num_heads, mlp_hidden, temporal_mlp_hidden; (H/p)*(W/p) % 128 == 0, max_tokens <= 32; inference only.
+   * variant 3: DiT3D "factorized_matrix_attention" + sinusoidal_2d (FacMatDiT: configurations/algorithm/backbone/
+   *   dit3d_factorized_matrix.yaml + shortcut/FacMatDiT): the block sequence and parameters of variant 1 without the difference front
+   *   end -- no diff_embedder, the conditioning depends on the noise level only, max_tokens is the caller's (<= 32, odd counts
+   *   allowed) -- and with use_temporal_rope the RoPE-1D over the frame axis (dit_base.py:297-306) on q and k of the matrix attention;
+   *   the (cos, sin) table [max_tokens][hd/2] is built in float64 at create time and is not a parameter.  Inference only. */
   int32_t variant;
   int32_t embed_col_dim;        /* 64 */
   int32_t num_col_heads;        /* 1 */
@@ -173,6 +178,7 @@ typedef struct {
   int32_t cond_dim;      /* action: values per (video, token) */
   int32_t num_classes;   /* label */
   int32_t cond_dropout;  /* cfg.external_cond_dropout > 0 */
+  int32_t use_temporal_rope;  /* variant 3: RoPE-1D over the frame axis on q and k of the matrix attention (0: none; other variants ignore it) */
 } dfot_dit_config;
 enum { DFOT_COND_NONE = 0, DFOT_COND_ACTION = 1, DFOT_COND_LABEL = 2 };
 
@@ -353,6 +359,17 @@ int dfot_op_attention_padded(const void* q, const void* k, const void* v, void* 
  * multiple of 8 (4 when d % 8 != 0) covering heads*d; anything else: DFOT_ERR_SHAPE */
 int dfot_op_attention_temporal(const void* q, const void* k, const void* v, void* o, int ldo, int batch, int tokens, int patches,
                                int heads, int d, void* stream);
+/* MatrixAttention core of the FacMatDiT backbone (DiT3D "factorized_matrix_attention", engine variant 3): every frame is one token whose
+ * q / k / v are (E/cc x h/rr) matrices.  z [batch*L*E][3h] bf16 holds (q|k|v), rows (frame, col head, n), columns (row head, d);
+ * o [batch*L*E][h] in the same order.  Per (video, col head, row head): S[l][l'] = scale * <rope(q_l), rope(k_l')> over the matrix
+ * entries, softmax over l', o = P v.  rope_cs: fp32 [rows >= L][h/rr/2][2] = (cos, sin) of frame l and pair i, applied to the
+ * interleaved pairs (d = 2i, 2i + 1) of every matrix row; NULL = no rotation.  Every q, k, v entry is read once for every L.
+ * 1 <= L <= 32, E % cc == 0, h % rr == 0, (h/rr) % 4 == 0; anything else: DFOT_ERR_SHAPE before any launch */
+int dfot_op_matrix_attention_rope(const void* z, void* o, const float* rope_cs, int batch, int L, int E, int h, int cc, int rr,
+                                  float scale, void* stream);
+/* the DifferenceDiT3D (variant 1) form of the same core, without rotation: register forms for L in {2, 4, 6, 8, 10}, one pair of
+ * tokens per wave pass for every other L <= 32.  Test / measurement entry of the engine's own launcher */
+int dfot_op_matrix_attention(const void* z, void* o, int batch, int L, int E, int h, int cc, int rr, float scale, void* stream);
 /* training path, test entry: o = attention(q, k, v) as above and, for the upstream gradient d_o [B*N][ldo] (same compact layout as
  * o), dq / dk / dv in the layout of q / k / v; dq is the gradient of the UNSCALED q (q itself is passed pre-multiplied by
  * log2(e)/sqrt(d), as the forward wants it).  Replaces torch autograd through F.scaled_dot_product_attention

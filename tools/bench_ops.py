@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Micro-benchmarks of the C-ABI primitives at the RE10K model shapes (model batch 2), HIP-event timed.
-Usage (GPU box): python tools/bench_ops.py [gemm] [conv] [attn] [tattn] [vae_encode]"""
+Usage (GPU box): python tools/bench_ops.py [gemm] [conv] [attn] [tattn] [mattn] [vae_encode]"""
 import ctypes as C
 import math
 import os
@@ -76,6 +76,36 @@ def facdit_forward(b):
     """whole forward of FacDiT-XL at the taichikl shape (4x32x32 latents, patch 2, 16 frames), ms; attention launches timed on their own"""
     bb = dict(name="dit3d", variant="factorized_attention", pos_emb_type="sinusoidal_factorized", patch_size=2, hidden_size=1152, depth=28,
               num_heads=16, mlp_ratio=4.0, spatial_mlp_ratio=0.0)
+    model = dfot_amd.DiT3D(bb, x_shape=(4, 32, 32), max_tokens=16).cuda().eval()
+    model.init_random(0)
+    x = torch.randn(b, 16, 4, 32, 32, device="cuda")
+    k = torch.randint(0, 1000, (b, 16), device="cuda")
+    with torch.no_grad():
+        return timeit(lambda: model(x, k), iters=10, warm=3)
+
+
+def mattn(b, tokens, e, h, cc, rr, rope):
+    """matrix attention of the FacMatDiT backbone on one (q|k|v) matrix: us of dfot_op_matrix_attention_rope (with and without the table) and of
+    the DifferenceDiT3D launcher (dfot_op_matrix_attention: no rotation; one pair of tokens per wave pass at the lengths it has no register form
+    for), GB/s against the algorithmic bytes -- q, k, v read once, o written once"""
+    hd = h // rr
+    z = torch.randn(b * tokens * e, 3 * h, device="cuda").bfloat16()
+    o = torch.empty(b * tokens * e, h, device="cuda", dtype=torch.bfloat16)
+    ang = torch.arange(tokens, dtype=torch.float64)[:, None] * 10000.0 ** (-torch.arange(0, hd, 2, dtype=torch.float64) / hd)[None]
+    table = torch.stack([ang.cos(), ang.sin()], -1).float().cuda().contiguous()
+    scale = 1.0 / math.sqrt((e // cc) * hd)
+    new = lambda t: timeit(lambda: capi.check(capi.lib.dfot_op_matrix_attention_rope(P(z), P(o), P(t) if rope and t is not None else None, b, tokens, e,
+                                                                                      h, cc, rr, scale, S())), iters=50, warm=5)
+    ms_rope, ms_plain = new(table), new(None)
+    ms_old = timeit(lambda: capi.check(capi.lib.dfot_op_matrix_attention(P(z), P(o), b, tokens, e, h, cc, rr, scale, S())), iters=50, warm=5)
+    return ms_rope, ms_plain, ms_old, b * tokens * e * 4.0 * h * 2.0
+
+
+def facmat_forward(b, row=1152, heads=16, depth=28):
+    """whole forward of FacMatDiT (XL-64-1 by default) at the taichikl shape (4x32x32 latents, patch 2, 16 frames), ms"""
+    bb = dict(name="dit3d", variant="factorized_matrix_attention", pos_emb_type="sinusoidal_2d", use_temporal_rope=True, patch_size=2,
+              embed_col_dim=64, embed_row_dim=row, num_heads=heads, num_col_heads=1, num_row_heads=heads, depth=depth, mlp_ratio=4.0,
+              spatial_mlp_ratio=4.0, use_bias=False, matrix_block="matrix")
     model = dfot_amd.DiT3D(bb, x_shape=(4, 32, 32), max_tokens=16).cuda().eval()
     model.init_random(0)
     x = torch.randn(b, 16, 4, 32, 32, device="cuda")
@@ -175,6 +205,19 @@ def main():
                   f"{tf:6.2f} TF/s", flush=True)
         for b in (2, 16):
             print(f"facdit XL forward B={b} x 16 frames x 256 patches: {facdit_forward(b):.3f} ms", flush=True)
+    if "mattn" in what:
+        # @FacMatDiT/S-64-1 (embed_row_dim 384, 6 row heads) and XL-64-1 (1152, 16); embed_col_dim 64, one col head
+        for name, (h, rr) in {"S": (384, 6), "XL": (1152, 16)}.items():
+            for b in (2, 16):
+                for tokens in (16, 17, 32):
+                    ms_rope, ms_plain, ms_old, nbytes = mattn(b, tokens, 64, h, 1, rr, True)
+                    print(f"mattn {name:2s} B={b:2d} L={tokens} E=64 h={h} rr={rr}: rope {ms_rope*1e3:8.1f} us ({nbytes / ms_rope / 1e6:6.1f} GB/s)  "
+                          f"no table {ms_plain*1e3:8.1f} us  variant-1 launcher {ms_old*1e3:8.1f} us  ({ms_old / ms_plain:.1f}x)", flush=True)
+        depth = 28
+        ms = facmat_forward(2, depth=depth)
+        ms_attn = mattn(2, 16, 64, 1152, 1, 16, True)[0]
+        print(f"facmat XL forward B=2 x 16 frames x 256 patches: {ms:.3f} ms; matrix attention {depth} x {ms_attn*1e3:.1f} us = "
+              f"{depth * ms_attn / ms * 100:.1f} % of it", flush=True)
     if "attn" in what:
         shapes = {"L2": (2, 9, 8192, 64), "L3": (2, 9, 2048, 128), "L2 Bm8": (8, 9, 8192, 64)}
         if os.environ.get("ATTN_SHAPE"):  # e.g. ATTN_SHAPE=2,8,2048,128: one extra shape (workgroup-count experiments)
