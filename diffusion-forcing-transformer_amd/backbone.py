@@ -88,6 +88,9 @@ class UViT3DPose(nn.Module):
         self._op_key: Optional[int] = None
         self._cond_key = None
         self._cond_refs = None
+        self._cond_gen = None        # reserve_generation at the time the conditioning cache was keyed
+        self._cond_flag = None       # device int32 the content compare of the conditioning writes (dfot_op_equal_bits)
+        self.cond_cache_stats = {"builds": 0, "identity_hits": 0, "content_hits": 0}  # per forward: how the pose / FiLM cache was found
         self._train_names = None     # parameter names in named_parameters() order (operator input order of the training form)
         self._trainer = None         # uvit_train.UViT3DPoseTrainer on this module's weights, built at the first training forward
         self._trainer_sig = None
@@ -286,6 +289,43 @@ class UViT3DPose(nn.Module):
             out.append(eng.dx_in.to(grad_out.dtype))
         return out
 
+    def _cond_content_equal(self, cond: torch.Tensor, mask: Optional[torch.Tensor]) -> bool:
+        """Second lookup of the conditioning cache, after the identity key missed: do `cond` / `mask` hold the bits the caches were built
+        from?  Only asked when the kept pair is still what was keyed -- the cache was not invalidated (``_cond_key = None``), weights and
+        workspace are the same, neither kept tensor was written in place since -- and when both sides can be compared as raw memory: fp32,
+        contiguous, same device and shape, mask present on both sides or on neither with one element type.  One device-side exact compare
+        per tensor (dfot_op_equal_bits: 2 x 755 MB read at the headline shape, against 2.1 TFLOP for a build) into one flag, and one host
+        read of it.  A host read is illegal while the stream is capturing, so there only identity counts."""
+        if self._cond_key is None or self._cond_refs is None:
+            return False
+        kept, kept_mask = self._cond_refs
+        _, version, shape, synced, mask_key = self._cond_key
+        if synced != self._synced or self._cond_gen != self.reserve_generation:
+            return False
+        if kept._version != version or (kept_mask is not None and kept_mask._version != mask_key[1]):
+            return False  # the kept tensor was mutated in place: it no longer holds what the caches were built from
+        for t in (cond, kept):
+            if t.dtype != torch.float32 or not t.is_contiguous():
+                return False
+        if cond.device != kept.device or tuple(cond.shape) != shape:
+            return False
+        if (mask is None) != (kept_mask is None):
+            return False
+        if mask is not None and (mask.dtype != kept_mask.dtype or mask.shape != kept_mask.shape or mask.device != kept_mask.device
+                                 or not mask.is_contiguous() or not kept_mask.is_contiguous()):
+            return False
+        if torch.cuda.is_current_stream_capturing():
+            return False
+        if self._cond_flag is None or self._cond_flag.device != cond.device:
+            self._cond_flag = torch.zeros(1, dtype=torch.int32, device=cond.device)
+        flag = self._cond_flag
+        flag.zero_()
+        s = capi.stream_ptr()
+        capi.check(capi.lib.dfot_op_equal_bits(capi.ptr(kept), capi.ptr(cond), cond.numel() * cond.element_size(), capi.ptr(flag), s))
+        if mask is not None:
+            capi.check(capi.lib.dfot_op_equal_bits(capi.ptr(kept_mask), capi.ptr(mask), mask.numel() * mask.element_size(), capi.ptr(flag), s))
+        return int(flag.item()) == 0
+
     def _forward_impl(self, x: torch.Tensor, noise_levels: torch.Tensor, external_cond: Optional[torch.Tensor] = None,
                       external_cond_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
         assert x.shape[1] == self.temporal_length, (
@@ -309,17 +349,27 @@ class UViT3DPose(nn.Module):
         self.reserve(b)
         xf = x.detach().to(torch.float32).contiguous()
         kf = noise_levels.detach().to(torch.float32).contiguous()
-        # the pose caches are rebuilt only when the conditioning tensors change (the sampler passes the same
-        # tensors for all DDIM steps of a window)
+        # the pose caches are rebuilt only when the conditioning changes: first by tensor identity (this project's sampler passes the same
+        # tensors for all DDIM steps of a window), then by content (_cond_content_equal)
         key = (external_cond.data_ptr(), external_cond._version, tuple(external_cond.shape), self._synced,
                None if external_cond_mask is None else (external_cond_mask.data_ptr(), external_cond_mask._version))
-        if key != self._cond_key:
-            cf = external_cond.detach().to(torch.float32).contiguous()
-            mf = None if external_cond_mask is None else external_cond_mask.to(torch.uint8).contiguous()
-            capi.check(capi.lib.dfot_uvit_set_conditions(self._handle, capi.ptr(cf, torch.float32, "external_cond"),
-                                                         capi.ptr(mf, torch.uint8, "external_cond_mask"), b, capi.stream_ptr()))
+        if key == self._cond_key:
+            self.cond_cache_stats["identity_hits"] += 1
+        else:
+            # a caller that rebuilds equal conditioning every step (the reference's sampler: a fresh ray encoding per DDIM step) misses the
+            # identity key on every forward; the caches are a function of the bits, so equal bits are a hit too
+            if self._cond_content_equal(external_cond, external_cond_mask):
+                self.cond_cache_stats["content_hits"] += 1
+            else:
+                cf = external_cond.detach().to(torch.float32).contiguous()
+                mf = None if external_cond_mask is None else external_cond_mask.to(torch.uint8).contiguous()
+                capi.check(capi.lib.dfot_uvit_set_conditions(self._handle, capi.ptr(cf, torch.float32, "external_cond"),
+                                                             capi.ptr(mf, torch.uint8, "external_cond_mask"), b, capi.stream_ptr()))
+                self.cond_cache_stats["builds"] += 1
+            # (re-)key to the tensors just passed and drop the old ones: the next forward compares against these, no copy is ever held
             self._cond_key = key
             self._cond_refs = (external_cond, external_cond_mask)  # keep the keyed tensors alive
+            self._cond_gen = self.reserve_generation
         out = torch.empty_like(xf)
         live = self.live_frames
         if live is not None:

@@ -196,6 +196,7 @@ SIGNATURES = {
     "dfot_op_vae_posterior": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "dfot_op_f32_to_bf16": (_I, [_P, _P, _L, _P]),
     "dfot_op_bf16_to_f32": (_I, [_P, _P, _L, _P]),
+    "dfot_op_equal_bits": (_I, [_P, _P, _L, _P, _P]),
 }
 
 

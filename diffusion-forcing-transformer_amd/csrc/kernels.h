@@ -95,6 +95,8 @@ int launch_adamw(float* p, const float* g, float* m, float* v, long n, float lr,
 // ---- casts / weight packing ----
 int launch_f32_to_bf16(const float* src, bf16* dst, long n, hipStream_t s);
 int launch_bf16_to_f32(const bf16* src, float* dst, long n, hipStream_t s);
+// *differs = 1 (device int, zeroed by the caller on the same stream) when the two buffers differ in any bit; bytes == 0 launches nothing
+int launch_equal_bits(const void* a, const void* b, long bytes, int* differs, hipStream_t s);
 // dst[r][col0 + k] (row stride ldd) = src[map ? map[r] : r][k] for k < K ; zero for K <= k < kpad
 int launch_pack_rows(const float* src, bf16* dst, const int* map, int rows, int k, int kpad, long ldd, int col0,
                      hipStream_t s);

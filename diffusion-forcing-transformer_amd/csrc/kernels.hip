@@ -1525,4 +1525,68 @@ int launch_adamw(float* p, const float* g, float* m, float* v, long n, float lr,
   DFOT_CHECK_HIP(hipGetLastError());
   return DFOT_OK;
 }
+
+// --------------------------------------------------------------------------------------------
+// exact (bitwise) comparison of two buffers: the content key of the backbone's pose / FiLM cache (backbone.py)
+// --------------------------------------------------------------------------------------------
+// Streaming read of 2 x bytes, one 4-byte write at most.  Fixed grid, grid-stride loop, four independent loads per buffer in flight per
+// thread; a thread that saw a difference stores 1 to *differs with a plain vector store -- every writer writes the same value, so the
+// stores need no ordering and no atomics.  The caller zeroes the flag on the same stream.  The `rest` bytes behind the n whole words
+// (rest < sizeof(T)) are compared bytewise by the first threads of workgroup 0.
+typedef __attribute__((ext_vector_type(4))) unsigned int uint4v;
+__device__ __forceinline__ unsigned int bits_differ(uint4v x, uint4v y) {
+  const uint4v d = x ^ y;
+  return d[0] | d[1] | d[2] | d[3];
+}
+__device__ __forceinline__ unsigned int bits_differ(unsigned int x, unsigned int y) { return x ^ y; }
+__device__ __forceinline__ unsigned int bits_differ(uint8_t x, uint8_t y) { return (unsigned int)(x ^ y); }
+
+constexpr int EQ_BLOCK = 256, EQ_MAX_GRID = 2048;  // 256 CUs x 8 workgroups
+
+template <typename T>
+__global__ __launch_bounds__(EQ_BLOCK) void equal_bits_kernel(const T* __restrict__ a, const T* __restrict__ b, long n, int rest,
+                                                              int* __restrict__ differs) {
+  const long stride = (long)gridDim.x * EQ_BLOCK;
+  long i = (long)blockIdx.x * EQ_BLOCK + threadIdx.x;
+  unsigned int acc = 0;
+  for (; i + 3 * stride < n; i += 4 * stride) {
+    const T a0 = a[i], a1 = a[i + stride], a2 = a[i + 2 * stride], a3 = a[i + 3 * stride];
+    const T b0 = b[i], b1 = b[i + stride], b2 = b[i + 2 * stride], b3 = b[i + 3 * stride];
+    acc |= bits_differ(a0, b0) | bits_differ(a1, b1) | bits_differ(a2, b2) | bits_differ(a3, b3);
+  }
+  for (; i < n; i += stride) acc |= bits_differ(a[i], b[i]);
+  if (blockIdx.x == 0 && (int)threadIdx.x < rest) {
+    const uint8_t* ta = reinterpret_cast<const uint8_t*>(a + n);
+    const uint8_t* tb = reinterpret_cast<const uint8_t*>(b + n);
+    acc |= bits_differ(ta[threadIdx.x], tb[threadIdx.x]);
+  }
+  if (acc) *differs = 1;
+}
+
+template <typename T>
+static int launch_equal_bits_t(const void* a, const void* b, long bytes, int* differs, hipStream_t s) {
+  const long n = bytes / (long)sizeof(T);
+  const int rest = (int)(bytes - n * (long)sizeof(T));
+  const int grid = n ? (int)(cdiv(n, EQ_BLOCK) < EQ_MAX_GRID ? cdiv(n, EQ_BLOCK) : EQ_MAX_GRID) : 1;
+  hipLaunchKernelGGL(equal_bits_kernel<T>, dim3(grid), dim3(EQ_BLOCK), 0, s, (const T*)a, (const T*)b, n, rest, differs);
+  DFOT_CHECK_HIP(hipGetLastError());
+  return DFOT_OK;
+}
+
+// 16-byte loads when both bases are 16-byte aligned (every tensor a framework allocates); a base that is not takes the scalar path at the
+// widest element both bases are aligned to (4 bytes, else 1)
+int launch_equal_bits(const void* a, const void* b, long bytes, int* differs, hipStream_t s) {
+  DFOT_REQUIRE(differs && ((uintptr_t)differs & 3) == 0, DFOT_ERR_ARG, "equal_bits: the flag is null or not 4-byte aligned");
+  DFOT_REQUIRE(bytes >= 0, DFOT_ERR_ARG, "equal_bits: negative length %ld", bytes);
+  if (bytes == 0) return DFOT_OK;  // empty buffers are equal: nothing to launch
+  DFOT_REQUIRE(a && b, DFOT_ERR_ARG, "equal_bits: null buffer");
+  const uintptr_t al = (uintptr_t)a | (uintptr_t)b;
+  if ((al & 15) == 0) return launch_equal_bits_t<uint4v>(a, b, bytes, differs, s);
+  if ((al & 3) == 0) return launch_equal_bits_t<unsigned int>(a, b, bytes, differs, s);
+  return launch_equal_bits_t<uint8_t>(a, b, bytes, differs, s);
+}
 }  // namespace dfot
+
+extern "C" int dfot_op_equal_bits(const void* a, const void* b, int64_t bytes, int32_t* differs, void* stream) {
+  return dfot::launch_equal_bits(a, b, (long)bytes, differs, (hipStream_t)stream);
+}

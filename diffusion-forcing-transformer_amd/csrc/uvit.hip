@@ -107,6 +107,7 @@ struct dfot_uvit_s {
   uint8_t* cond_mask = nullptr;  // device copy of the external_cond_mask of the cached conditions
   bool have_mask = false;
   int cond_batch = 0;            // batch the pose caches were built for (0 = none)
+  int64_t cond_builds = 0;       // dfot_uvit_set_conditions calls that got past their checks (query "cond_builds")
   bf16 *acond = nullptr, *emb[4] = {nullptr, nullptr, nullptr, nullptr}, *s1 = nullptr, *hbf = nullptr,
        *cat = nullptr, *q = nullptr, *k = nullptr, *v = nullptr;
   AttnScratch attn_scratch;   // key-split partials of the level-2 attention, owned by this handle (sized in reserve)
@@ -862,6 +863,7 @@ int dfot_uvit_query(dfot_uvit_t h, const char* key, double* value) {
   for (const TrW& w : h->up_tr) bound = fmaxf(bound, w.score_bound);
   if (!strcmp(key, "score_bound_l2")) *value = bound;
   else if (!strcmp(key, "attn_kernel_l2")) *value = (bound < 64.0f && !h->attn_force_safe) ? 14 : 5;
+  else if (!strcmp(key, "cond_builds")) *value = (double)h->cond_builds;
   else {
     set_error("query: unknown key '%s'", key);
     return DFOT_ERR_ARG;
@@ -880,6 +882,7 @@ int dfot_uvit_set_conditions(dfot_uvit_t h, const float* external_cond, const ui
   const int bt = batch * h->T, e = h->E;
   int rc = 0;
   h->cond_batch = 0;
+  ++h->cond_builds;
   // pose patch-embed (+bias), then its average-pool pyramid: the pose half of `emb` at every level
   if ((rc = launch_cond_repack(external_cond, h->acond, bt, c.resolution, c.cond_dim, h->kpose, s))) return rc;
   {

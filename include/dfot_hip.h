@@ -87,7 +87,8 @@ int dfot_uvit_set_option(dfot_uvit_t h, const char* key, int value);
 /* also: "attn_force_safe" (1 = level-2 attention always takes the running-max kernel, as weights with a large QK-norm bound would)
  * Read-outs (valid after finalize), by key: "score_bound_l2" = the largest bound of |q.k| log2(e)/sqrt(d) over the level-2 blocks, from
  * their q_norm / k_norm weights (u_vit_blocks.py:255-262); "attn_kernel_l2" = 14 (no running max, bound < 64) or 5 (running max):
- * the level-2 attention kernel forward runs */
+ * the level-2 attention kernel forward runs; "cond_builds" = the number of dfot_uvit_set_conditions calls on this handle (those of
+ * dfot_uvit_forward included) that passed their argument checks: what a caller's conditioning cache did NOT save */
 int dfot_uvit_query(dfot_uvit_t h, const char* key, double* value);
 /* "time_attn" = N > 0 records HIP events (on the launch stream) around the next N level-2 attention launches;
  * this call synchronises on them, returns the summed duration and the number of launches, and resets the count */
@@ -495,6 +496,12 @@ int dfot_op_outgrad_gather(const float* dout, void* dpatch, int bt, int res, int
 /* fp32 <-> bf16 helpers for tests */
 int dfot_op_f32_to_bf16(const float* src, void* dst, int64_t n, void* stream);
 int dfot_op_bf16_to_f32(const void* src, float* dst, int64_t n, void* stream);
+/* exact comparison of two device buffers of `bytes` bytes: *differs (device int32, 4-byte aligned, zeroed by the caller on the same stream)
+ * is set to 1 when any BIT differs -- equal NaN payloads compare equal, +0.0 and -0.0 do not -- and is left untouched otherwise, so several
+ * calls may share one flag.  Reads 2 x bytes in 16-byte loads when both bases are 16-byte aligned (scalar loads otherwise, and for the
+ * tail), writes at most 4 bytes; no atomics.  bytes == 0: equal, nothing is launched.  Null or misaligned flag, null buffer with
+ * bytes > 0, bytes < 0: DFOT_ERR_ARG before any launch.  The content key of the UViT3DPose pose / FiLM cache (backbone.py). */
+int dfot_op_equal_bits(const void* a, const void* b, int64_t bytes, int32_t* differs, void* stream);
 
 /* ---- VideoVAE decoder pieces (algorithms/vae/video_vae/model.py:130-281, algorithms/vae/common/modules/{conv,resnet,attention,
  * updownsample,normalize}.py; called from BaseVideoAlgo._decode, algorithms/common/base_pytorch_video_algo.py:600-629).  Channels-last

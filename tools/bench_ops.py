@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Micro-benchmarks of the C-ABI primitives at the RE10K model shapes (model batch 2), HIP-event timed.
-Usage (GPU box): python tools/bench_ops.py [gemm] [conv] [attn] [tattn] [mattn] [vae_encode]"""
+Usage (GPU box): python tools/bench_ops.py [gemm] [conv] [attn] [tattn] [mattn] [vae_encode] [equal]"""
 import ctypes as C
 import math
 import os
@@ -168,6 +168,17 @@ def vae_encode(b=2, t=17, res=128):
           f"{total_flop / ms / 1e9:.1f} TF/s", flush=True)
 
 
+def equal(nbytes):
+    """dfot_op_equal_bits on two equal buffers (the worst case: nothing ends early, every byte of both is read): us and GB/s of the
+    2 x nbytes it reads"""
+    a = torch.randn(nbytes // 4, device="cuda")
+    b = a.clone()
+    flag = torch.zeros(1, dtype=torch.int32, device="cuda")
+    ms = timeit(lambda: capi.check(capi.lib.dfot_op_equal_bits(P(a), P(b), nbytes, P(flag), S())), iters=50, warm=5)
+    assert int(flag.item()) == 0
+    return ms, 2.0 * nbytes / ms / 1e6
+
+
 def main():
     what = sys.argv[1:] or ["gemm", "conv", "attn"]
     if "vae_encode" in what:
@@ -218,6 +229,11 @@ def main():
         ms_attn = mattn(2, 16, 64, 1152, 1, 16, True)[0]
         print(f"facmat XL forward B=2 x 16 frames x 256 patches: {ms:.3f} ms; matrix attention {depth} x {ms_attn*1e3:.1f} us = "
               f"{depth * ms_attn / ms * 100:.1f} % of it", flush=True)
+    if "equal" in what:
+        # the conditioning of one window at model batch 2 and 8 (B, 8, 180, 256, 256 fp32), and a size that stays in the 256 MiB Infinity Cache
+        for name, nbytes in {"cond Bm2": 2 * 8 * 180 * 256 * 256 * 4, "cond Bm8": 8 * 8 * 180 * 256 * 256 * 4, "64 MiB": 64 << 20}.items():
+            ms, gbs = equal(nbytes)
+            print(f"equal {name:8s} {nbytes / 1e6:8.1f} MB x 2: {ms*1e3:8.1f} us  {gbs:7.1f} GB/s ({gbs / 1e3 / HBM_TBS:.2f} of {HBM_TBS:.0f} TB/s HBM)", flush=True)
     if "attn" in what:
         shapes = {"L2": (2, 9, 8192, 64), "L3": (2, 9, 2048, 128), "L2 Bm8": (8, 9, 8192, 64)}
         if os.environ.get("ATTN_SHAPE"):  # e.g. ATTN_SHAPE=2,8,2048,128: one extra shape (workgroup-count experiments)
