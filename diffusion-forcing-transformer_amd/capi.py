@@ -43,6 +43,12 @@ class DiTConfig(C.Structure):
     ]
 
 
+class DiTConfigF(DiTConfig):
+    """dfot_dit_config_f: dfot_dit_config followed by fourier_noise (a ctypes subclass appends its fields to the base's, so the base fields
+    read and write as on DiTConfig); what dfot_dit_create_f / dfot_dit_train_create_f take"""
+    _fields_ = [("fourier_noise", C.c_int32)]
+
+
 COND_NONE, COND_ACTION, COND_LABEL = 0, 1, 2  # dfot_dit_config.cond_type
 
 
@@ -93,6 +99,7 @@ SIGNATURES = {
     "dfot_uvit_forward_cached_masks": (_I, [_P, _P, _P, _P, _I, _P, _P, _P]),
     "dfot_uvit_read_tap": (_I, [_P, C.c_char_p, _P, C.c_size_t, _P]),
     "dfot_dit_create": (_I, [C.POINTER(DiTConfig), C.POINTER(_P)]),
+    "dfot_dit_create_f": (_I, [C.POINTER(DiTConfigF), C.POINTER(_P)]),
     "dfot_dit_destroy": (_I, [_P]),
     "dfot_dit_num_params": (_I, [_P]),
     "dfot_dit_param_name": (C.c_char_p, [_P, _I]),
@@ -105,8 +112,10 @@ SIGNATURES = {
     "dfot_dit_attn_timing": (_I, [_P, C.POINTER(C.c_double), C.POINTER(_L)]),
     "dfot_dit_forward": (_I, [_P, _P, _P, _P, _I, _I, _P]),
     "dfot_dit_forward_cond": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _P]),
+    "dfot_dit_forward_f": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _P]),
     "dfot_dit_read_tap": (_I, [_P, C.c_char_p, _P, C.c_size_t, _P]),
     "dfot_dit_train_create": (_I, [C.POINTER(DiTConfig), C.POINTER(_P)]),
+    "dfot_dit_train_create_f": (_I, [C.POINTER(DiTConfigF), C.POINTER(_P)]),
     "dfot_dit_train_destroy": (_I, [_P]),
     "dfot_dit_train_num_params": (_I, [_P]),
     "dfot_dit_train_param_name": (C.c_char_p, [_P, _I]),
@@ -119,6 +128,8 @@ SIGNATURES = {
     "dfot_dit_train_sync_weights": (_I, [_P, _P]),
     "dfot_dit_train_forward": (_I, [_P, _P, _P, _P, _I, _I, _P]),
     "dfot_dit_train_forward_cond": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _P]),
+    "dfot_dit_train_load_buffer": (_I, [_P, C.c_char_p, _P, _L, _P]),
+    "dfot_dit_train_forward_f": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _P]),
     "dfot_dit_train_input_grad": (_I, [_P, _P, _P]),
     "dfot_dit_train_backward": (_I, [_P, _P, _P]),
     "dfot_vloss_grad": (_I, [_P] * 7 + [_I, _I, _L, _I, _P]),

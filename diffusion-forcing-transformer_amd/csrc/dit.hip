@@ -183,6 +183,116 @@ int launch_cond_embed(const CondEmbedArgs& a, int frames, hipStream_t s) {
   return DFOT_OK;
 }
 
+// ---- continuous diffusion front end (cfg.fourier_noise) -----------------------------------------------------------------
+// FourierEmbedding (embeddings.py:94-109): sqrt(2) * cos(level * freq + phase), fp32.  The reference forms the argument with one rounded
+// multiply and one rounded add (two torch ops), so no FMA here: at |level * freq| of tens of radians one ulp of the argument is 4e-6.
+// cosf is the accurately range-reduced one (not __cosf); the scale is float(sqrt(2)), as torch multiplies an fp32 tensor by a Python scalar.
+// (__fmul_rn / __fadd_rn are plain operators in HIP's headers and would be contracted: the pragma is what keeps the two roundings.)
+__device__ __forceinline__ float fourier_feature(float level, float freq, float phase) {
+#pragma clang fp contract(off)
+  const float m = level * freq;
+  const float a = m + phase;
+  return cosf(a) * 1.41421356237309515f;
+}
+
+__global__ void fourier_features_kernel(const float* __restrict__ levels, const float* __restrict__ freqs, const float* __restrict__ phases,
+                                        float* __restrict__ feat, int frames, int dim) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long)frames * dim) return;
+  const int c = (int)(i % dim);
+  feat[i] = fourier_feature(levels[i / dim], freqs[c], phases[c]);
+}
+
+// The noise-level embedding of the frames, fp32 on the VALU: features -> Linear -> SiLU (fourier_hidden_kernel) -> Linear (fourier_out_kernel).
+// The two linears run over B*T rows (5..128): a 256-row MFMA tile would be >= 50 % padding and would round the operands to bf16, while the
+// table path this replaces evaluates them in fp32 (rows_linear_kernel), so this keeps its arithmetic -- one wave per output channel, lanes
+// strided over K, xor-shuffle sum, i.e. the summation order of rows_linear_kernel.  A workgroup owns FE_FRAMES frames x FE_COLS output
+// channels, so each weight row is read once per FE_FRAMES frames and the grid (frame groups x channel chunks) covers the chip.  Every
+// frame's sums are formed in an order that does not depend on its neighbours: a video gives the same bits alone and in a batch.
+//   act [frames][hidden] = SiLU(linear_1(feat)) (workspace);  n_out [frames][hidden] = linear_2(act);  feat_out [frames][dim] (tap "noise_feat")
+//   semb != nullptr (no external condition follows): e = n (+ diff_table[token kind]) -> n_out, semb = bf16(SiLU(e)), idx[f] = f
+constexpr int FE_FRAMES = 4, FE_COLS = 32;
+struct FourierEmbedArgs {
+  const float *levels = nullptr, *freqs = nullptr, *phases = nullptr;
+  const float *w1 = nullptr, *b1 = nullptr, *w2 = nullptr, *b2 = nullptr;
+  const float* diff_table = nullptr;  // optional [2][hidden]: row 1 for even (difference) tokens
+  float *feat_out = nullptr, *act = nullptr, *n_out = nullptr;
+  bf16* semb = nullptr;
+  int* idx = nullptr;
+  int frames = 0, tokens = 0, dim = 0, hidden = 0;
+};
+
+// out[r] for the FE_FRAMES rows `in` (LDS, row stride kdim) of output channel o: lane r < FE_FRAMES returns row r's sum
+__device__ __forceinline__ float fe_rows_dot(const float* __restrict__ w, const float* in, int kdim, int lane) {
+  float acc[FE_FRAMES];
+#pragma unroll
+  for (int r = 0; r < FE_FRAMES; ++r) acc[r] = 0.f;
+  for (int i = lane; i < kdim; i += 64) {
+    const float wv = w[i];
+#pragma unroll
+    for (int r = 0; r < FE_FRAMES; ++r) acc[r] += wv * in[r * kdim + i];
+  }
+  float v = 0.f;
+#pragma unroll
+  for (int r = 0; r < FE_FRAMES; ++r) {
+    const float t = wave_sum(acc[r]);
+    v = lane == r ? t : v;
+  }
+  return v;
+}
+
+__global__ __launch_bounds__(256) void fourier_hidden_kernel(const FourierEmbedArgs a) {
+  extern __shared__ float fe_lds[];  // feat [FE_FRAMES][dim]
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int f0 = blockIdx.x * FE_FRAMES, o0 = blockIdx.y * FE_COLS, dim = a.dim, hidden = a.hidden;
+  for (int i = threadIdx.x; i < FE_FRAMES * dim; i += 256) {
+    const int r = i / dim, c = i % dim, f = f0 + r;
+    float v = 0.f;
+    if (f < a.frames) {
+      v = fourier_feature(a.levels[f], a.freqs[c], a.phases[c]);
+      if (blockIdx.y == 0) a.feat_out[(long)f * dim + c] = v;
+    }
+    fe_lds[i] = v;
+  }
+  __syncthreads();
+  for (int o = o0 + wave; o < o0 + FE_COLS && o < hidden; o += 4) {
+    const float v = fe_rows_dot(a.w1 + (long)o * dim, fe_lds, dim, lane);
+    if (lane < FE_FRAMES && f0 + lane < a.frames) a.act[(long)(f0 + lane) * hidden + o] = silu_f(v + a.b1[o]);
+  }
+}
+
+__global__ __launch_bounds__(256) void fourier_out_kernel(const FourierEmbedArgs a) {
+  extern __shared__ float fe_lds[];  // act [FE_FRAMES][hidden]
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int f0 = blockIdx.x * FE_FRAMES, o0 = blockIdx.y * FE_COLS, hidden = a.hidden;
+  for (int i = threadIdx.x; i < FE_FRAMES * hidden; i += 256) {
+    const int f = f0 + i / hidden;
+    fe_lds[i] = f < a.frames ? a.act[(long)f * hidden + i % hidden] : 0.f;
+  }
+  __syncthreads();
+  for (int o = o0 + wave; o < o0 + FE_COLS && o < hidden; o += 4) {
+    const float v = fe_rows_dot(a.w2 + (long)o * hidden, fe_lds, hidden, lane);
+    const int f = f0 + lane;
+    if (lane < FE_FRAMES && f < a.frames) {
+      float e = v + a.b2[o];
+      if (a.semb) {
+        if (a.diff_table) e += a.diff_table[(long)((f % a.tokens) % 2 == 0 ? 1 : 0) * hidden + o];
+        a.semb[(long)f * hidden + o] = f2bf(silu_f(e));
+      }
+      a.n_out[(long)f * hidden + o] = e;
+    }
+  }
+  if (a.idx && blockIdx.y == 0 && threadIdx.x < FE_FRAMES && f0 + threadIdx.x < a.frames) a.idx[f0 + threadIdx.x] = f0 + threadIdx.x;
+}
+
+int launch_fourier_embed(const FourierEmbedArgs& a, hipStream_t s) {
+  const dim3 grid(cdiv(a.frames, FE_FRAMES), cdiv(a.hidden, FE_COLS));  // LDS <= 32 KB: noise_dim <= 2048 and hidden <= 2048 at create
+  hipLaunchKernelGGL(fourier_hidden_kernel, grid, dim3(256), (size_t)FE_FRAMES * a.dim * sizeof(float), s, a);
+  hipLaunchKernelGGL(fourier_out_kernel, grid, dim3(256), (size_t)FE_FRAMES * a.hidden * sizeof(float), s, a);
+  DFOT_CHECK_HIP(hipGetLastError());
+  return DFOT_OK;
+}
+
 // per-frame 2-D transpose of a bf16 matrix: src [frames][R][C] -> dst [frames][C][R]; 64x64 tiles through LDS
 __global__ __launch_bounds__(256) void transpose_bf16_kernel(const bf16* __restrict__ src, bf16* __restrict__ dst, int R, int C) {
   __shared__ bf16 tile[64][66];
@@ -577,8 +687,13 @@ int launch_final_layer(const float* x, const float* table, const int* levels, lo
 
 using namespace dfot;
 
+// the configuration a handle keeps: dfot_dit_config plus what dfot_dit_config_f adds to it
+struct DitCfg : dfot_dit_config {
+  int32_t fourier_noise = 0;
+};
+
 struct dfot_dit_s {
-  dfot_dit_config cfg{};
+  DitCfg cfg{};
   int gh = 0, gw = 0, P = 0, d = 0, dstride = 0, kpatch = 0, oc = 0;
   int lpad = 0;      // level count padded to the GEMM's row tile
   long ldt = 0;      // mod_table row stride (floats) = total modulation outputs
@@ -596,6 +711,7 @@ struct dfot_dit_s {
   float *diff_table = nullptr, *pos2d = nullptr, *tpos = nullptr;  // tpos: variant 2, temporal sinusoidal table [max_tokens][hidden]
   float* trope = nullptr;  // variant 3 with use_temporal_rope: (cos, sin) [max_tokens][hd/2][2] of the matrix attention's RoPE-1D
   float *c_w1 = nullptr, *c_b1 = nullptr, *c_w2 = nullptr, *c_b2 = nullptr, *c_table = nullptr;  // external condition embedding
+  float *fz_freqs = nullptr, *fz_phases = nullptr;  // fourier_noise: the FourierEmbedding buffers [noise_dim]
   int c_rows = 0;                    // label: rows of the embedding table (num_classes, + 1 null class with dropout)
   int mod_variant = GEMM_AUTO;       // GEMM tile form finalize() used for mod_table: the per-frame table uses the same one (bit-identical rows)
   long mod_final = 0;
@@ -614,8 +730,12 @@ struct dfot_dit_s {
   bf16* csemb = nullptr;
   float *cmod = nullptr, *cemb = nullptr;
   int* cidx = nullptr;
+  float* nfeat = nullptr;  // fourier_noise: Fourier features of the last forward [frames][noise_dim] (tap "noise_feat")
+  float* nact = nullptr;   // fourier_noise: SiLU(linear_1(features)) [frames][hidden]
+  int last_feat_frames = 0;
   int gemm_variant = GEMM_AUTO;
   bool time_attn = false;
+  bool front_only = false;  // measurement: forward returns once the modulations of the call are formed (tools/bench_ops.py dit_front)
   std::vector<hipEvent_t> ev_start, ev_stop;
   size_t ev_used = 0;
 };
@@ -667,7 +787,7 @@ int dit_add_slice(dfot_dit_s* h, const std::string& name, int n, float* dst) {
 }
 
 int dit_build(dfot_dit_s* h) {
-  const dfot_dit_config& c = h->cfg;
+  const DitCfg& c = h->cfg;
   const int hd = c.hidden_size;
   h->gh = c.height / c.patch_size;
   h->gw = c.width / c.patch_size;
@@ -684,6 +804,10 @@ int dit_build(dfot_dit_s* h) {
   int rc = 0;
   // registration order == the reference module's state_dict order
   const std::string ne = "noise_level_pos_embedding.embedding";
+  if (c.fourier_noise) {  // FourierEmbedding's persistent buffers: state_dict lists noise_level_pos_embedding.timesteps before .embedding
+    if ((rc = dit_add_f32(h, "noise_level_pos_embedding.timesteps.freqs", {c.noise_dim}, &h->fz_freqs))) return rc;
+    if ((rc = dit_add_f32(h, "noise_level_pos_embedding.timesteps.phases", {c.noise_dim}, &h->fz_phases))) return rc;
+  }
   if ((rc = dit_add_f32(h, ne + ".linear_1.weight", {hd, c.noise_dim}, &h->t_w1))) return rc;
   if ((rc = dit_add_f32(h, ne + ".linear_1.bias", {hd}, &h->t_b1))) return rc;
   if ((rc = dit_add_f32(h, ne + ".linear_2.weight", {hd, hd}, &h->t_w2))) return rc;
@@ -785,19 +909,21 @@ int dit_build(dfot_dit_s* h) {
   if ((rc = dit_add_f32(h, "dit_base.final_layer.linear.weight", {h->oc, hd}, &h->fin_w))) return rc;
   if ((rc = dit_add_f32(h, "dit_base.final_layer.linear.bias", {h->oc}, &h->fin_b))) return rc;
 
-  // derived tables
-  if ((rc = dit_alloc(h, &h->freqs, (size_t)c.noise_dim / 2))) return rc;
-  if ((rc = dit_alloc(h, &h->feat, (size_t)h->lpad * c.noise_dim))) return rc;
-  if ((rc = dit_alloc(h, &h->thid, (size_t)h->lpad * hd))) return rc;
-  if ((rc = dit_alloc(h, &h->emb, (size_t)h->lpad * hd))) return rc;
-  const int nflag = diffm ? 2 : 1;  // variant 1: the conditioning also depends on the token kind (difference / frame)
-  if ((rc = dit_alloc(h, &h->semb, (size_t)nflag * h->lpad * hd))) return rc;
-  if ((rc = dit_alloc(h, &h->mod_table, (size_t)nflag * h->lpad * h->ldt))) return rc;
-  {
-    const int half = c.noise_dim / 2;
-    std::vector<float> f(half);
-    for (int i = 0; i < half; ++i) f[i] = (float)std::exp(-std::log(10000.0) * (double)i / (double)half);
-    DFOT_CHECK_HIP(hipMemcpy(h->freqs, f.data(), f.size() * sizeof(float), hipMemcpyHostToDevice));
+  // derived tables (a fourier_noise model has no finite set of levels: nothing is tabulated, the embedding runs per frame in forward)
+  if (!c.fourier_noise) {
+    if ((rc = dit_alloc(h, &h->freqs, (size_t)c.noise_dim / 2))) return rc;
+    if ((rc = dit_alloc(h, &h->feat, (size_t)h->lpad * c.noise_dim))) return rc;
+    if ((rc = dit_alloc(h, &h->thid, (size_t)h->lpad * hd))) return rc;
+    if ((rc = dit_alloc(h, &h->emb, (size_t)h->lpad * hd))) return rc;
+    const int nflag = diffm ? 2 : 1;  // variant 1: the conditioning also depends on the token kind (difference / frame)
+    if ((rc = dit_alloc(h, &h->semb, (size_t)nflag * h->lpad * hd))) return rc;
+    if ((rc = dit_alloc(h, &h->mod_table, (size_t)nflag * h->lpad * h->ldt))) return rc;
+    {
+      const int half = c.noise_dim / 2;
+      std::vector<float> f(half);
+      for (int i = 0; i < half; ++i) f[i] = (float)std::exp(-std::log(10000.0) * (double)i / (double)half);
+      DFOT_CHECK_HIP(hipMemcpy(h->freqs, f.data(), f.size() * sizeof(float), hipMemcpyHostToDevice));
+    }
   }
   if (facmat || fac) {
     // sinusoidal_2d table [P][hidden] (get_nd_sincos_pos_embed, dit_base.py:527-572): np.meshgrid's default "xy" indexing
@@ -884,9 +1010,7 @@ int dfot_dit_destroy(dfot_dit_t h) {
   return DFOT_OK;
 }
 
-int dfot_dit_create(const dfot_dit_config* cfg, dfot_dit_t* out) {
-  DFOT_REQUIRE(cfg && out, DFOT_ERR_ARG, "dfot_dit_create: null argument");
-  const dfot_dit_config& c = *cfg;
+static int dit_create_impl(const DitCfg& c, dfot_dit_t* out) {
   DFOT_REQUIRE(c.hidden_size > 0 && c.hidden_size % 64 == 0 && c.hidden_size <= 2048, DFOT_ERR_SHAPE,
                "hidden_size %d must be a multiple of 64, <= 2048", c.hidden_size);
   DFOT_REQUIRE(c.num_heads > 0 && c.hidden_size % c.num_heads == 0, DFOT_ERR_SHAPE, "hidden_size %d not divisible by %d heads",
@@ -938,6 +1062,7 @@ int dfot_dit_create(const dfot_dit_config* cfg, dfot_dit_t* out) {
                "cond_type %d unknown (0 = none, 1 = action, 2 = label)", c.cond_type);
   DFOT_REQUIRE(c.cond_type != DFOT_COND_ACTION || (c.cond_dim > 0 && c.cond_dim <= 1024), DFOT_ERR_SHAPE, "action condition: cond_dim %d must be in [1, 1024]", c.cond_dim);
   DFOT_REQUIRE(c.cond_type != DFOT_COND_LABEL || c.num_classes > 0, DFOT_ERR_SHAPE, "label condition: num_classes %d must be positive", c.num_classes);
+  DFOT_REQUIRE(!c.fourier_noise || c.noise_dim <= 2048, DFOT_ERR_SHAPE, "fourier_noise: noise_dim %d exceeds 2048", c.noise_dim);
   auto* h = new dfot_dit_s();
   h->cfg = c;
   int rc = dit_build(h);
@@ -947,6 +1072,21 @@ int dfot_dit_create(const dfot_dit_config* cfg, dfot_dit_t* out) {
   }
   *out = h;
   return DFOT_OK;
+}
+
+int dfot_dit_create(const dfot_dit_config* cfg, dfot_dit_t* out) {
+  DFOT_REQUIRE(cfg && out, DFOT_ERR_ARG, "dfot_dit_create: null argument");
+  DitCfg c;
+  static_cast<dfot_dit_config&>(c) = *cfg;
+  return dit_create_impl(c, out);
+}
+
+int dfot_dit_create_f(const dfot_dit_config_f* cfg, dfot_dit_t* out) {
+  DFOT_REQUIRE(cfg && out, DFOT_ERR_ARG, "dfot_dit_create_f: null argument");
+  DitCfg c;
+  static_cast<dfot_dit_config&>(c) = cfg->base;
+  c.fourier_noise = cfg->fourier_noise;
+  return dit_create_impl(c, out);
 }
 
 int dfot_dit_num_params(dfot_dit_t h) { return h ? (int)h->params.size() : 0; }
@@ -979,8 +1119,14 @@ int dfot_dit_finalize(dfot_dit_t h, void* stream) {
   DFOT_REQUIRE(h, DFOT_ERR_ARG, "finalize: null handle");
   for (const DitParam& p : h->params) DFOT_REQUIRE(p.loaded, DFOT_ERR_STATE, "finalize: missing key '%s'", p.name.c_str());
   hipStream_t s = (hipStream_t)stream;
-  const dfot_dit_config& c = h->cfg;
+  const DitCfg& c = h->cfg;
   const int hd = c.hidden_size, L = c.timesteps;
+  if (c.fourier_noise) {  // nothing to tabulate; the per-frame modulation GEMM takes 256-row tiles whatever the batch (same bits alone / in a batch)
+    h->mod_variant = gemm_pick_variant(A_DENSE, 256, (int)h->ldt, hd, true);
+    DFOT_CHECK_HIP(hipStreamSynchronize(s));
+    h->finalized = true;
+    return DFOT_OK;
+  }
   // embedding of every level: features -> Linear -> SiLU -> Linear (emb) ; semb = bf16(SiLU(emb)) feeds every modulation
   hipLaunchKernelGGL(tstep_features_kernel, dim3(cdiv((long)L * c.noise_dim, 256)), dim3(256), 0, s, h->freqs, h->feat, L, c.noise_dim);
   DFOT_CHECK_HIP(hipGetLastError());
@@ -1015,7 +1161,7 @@ int dfot_dit_reserve(dfot_dit_t h, int max_batch) {
   h->ws_owned.clear();
   h->ws_bytes = 0;
   h->max_batch = 0;
-  const dfot_dit_config& c = h->cfg;
+  const DitCfg& c = h->cfg;
   const size_t rows = (size_t)max_batch * c.max_tokens * h->P;
   const size_t qkv = (size_t)max_batch * c.num_heads * c.max_tokens * h->P * h->dstride;
   int rc = 0;
@@ -1048,8 +1194,9 @@ int dfot_dit_reserve(dfot_dit_t h, int max_batch) {
     DFOT_CHECK_HIP(hipMemset(h->W2, 0, fe * sizeof(bf16)));
     DFOT_CHECK_HIP(hipMemset(h->Z, 0, 3 * fe * sizeof(bf16)));
   }
-  if (c.cond_type != DFOT_COND_NONE) {
+  if (c.cond_type != DFOT_COND_NONE || c.fourier_noise) {
     const size_t frames = (size_t)max_batch * c.max_tokens;
+    if (c.fourier_noise && ((rc = dit_alloc(h, &h->nfeat, frames * c.noise_dim, true)) || (rc = dit_alloc(h, &h->nact, frames * c.hidden_size, true)))) return rc;
     h->fpad = (int)((frames + 255) / 256 * 256);  // whole row tiles of every GEMM form finalize() may have picked
     if ((rc = dit_alloc(h, &h->csemb, (size_t)h->fpad * c.hidden_size, true))) return rc;
     DFOT_CHECK_HIP(hipMemset(h->csemb, 0, (size_t)h->fpad * c.hidden_size * sizeof(bf16)));  // rows past the batch: finite operands
@@ -1067,6 +1214,10 @@ int dfot_dit_set_option(dfot_dit_t h, const char* key, int value) {
   DFOT_REQUIRE(h && key, DFOT_ERR_ARG, "set_option: null argument");
   if (!strcmp(key, "gemm_variant")) {
     h->gemm_variant = value;
+    return DFOT_OK;
+  }
+  if (!strcmp(key, "front_only")) {
+    h->front_only = value != 0;
     return DFOT_OK;
   }
   if (!strcmp(key, "time_attn")) {
@@ -1103,12 +1254,17 @@ int dfot_dit_attn_timing(dfot_dit_t h, double* total_ms, int64_t* launches) {
 }  // extern "C"
 
 // the forward of both entry points; cond / labels == nullptr: the per-level modulation table (no condition)
+// flevels: the float levels of a fourier_noise model (noise_levels == nullptr then)
 static int dit_forward_impl(dfot_dit_t h, const float* x, const int32_t* noise_levels, const float* cond, const int32_t* labels,
-                            const uint8_t* cond_mask, float* out, int batch, int tokens, void* stream) {
-  DFOT_REQUIRE(h && x && noise_levels && out, DFOT_ERR_ARG, "forward: null argument");
+                            const uint8_t* cond_mask, float* out, int batch, int tokens, void* stream, const float* flevels = nullptr) {
+  DFOT_REQUIRE(h && x && (noise_levels || flevels) && out, DFOT_ERR_ARG, "forward: null argument");
+  DFOT_REQUIRE(!h->cfg.fourier_noise || flevels, DFOT_ERR_ARG,
+               "forward: this model embeds float noise levels (fourier_noise); call dfot_dit_forward_f");
+  DFOT_REQUIRE(h->cfg.fourier_noise || !flevels, DFOT_ERR_ARG,
+               "forward_f: this model indexes integer noise levels (no fourier_noise); call dfot_dit_forward / dfot_dit_forward_cond");
   DFOT_REQUIRE(h->finalized, DFOT_ERR_STATE, "forward: weights not finalized");
   DFOT_REQUIRE(batch > 0 && batch <= h->max_batch, DFOT_ERR_STATE, "forward: batch %d exceeds the reserved %d", batch, h->max_batch);
-  const dfot_dit_config& c = h->cfg;
+  const DitCfg& c = h->cfg;
   DFOT_REQUIRE(tokens > 0 && tokens <= c.max_tokens, DFOT_ERR_SHAPE, "forward: %d tokens, max_tokens is %d", tokens, c.max_tokens);
   const int n = tokens * h->P, hd = c.hidden_size;
   DFOT_REQUIRE(n % 128 == 0, DFOT_ERR_SHAPE, "forward: sequence length %d (tokens x patches) must be a multiple of 128", n);
@@ -1122,16 +1278,30 @@ static int dit_forward_impl(dfot_dit_t h, const float* x, const int32_t* noise_l
   const int* lvl = noise_levels;
   const float* table = h->mod_table;
   int rc = 0;
-  if (cond || labels) {
+  if (flevels) {
+    // continuous diffusion: n = MLP(Fourier features) per frame (two launches); without a condition the second also forms e and SiLU(e)
+    FourierEmbedArgs fa;
+    fa.levels = flevels; fa.freqs = h->fz_freqs; fa.phases = h->fz_phases;
+    fa.w1 = h->t_w1; fa.b1 = h->t_b1; fa.w2 = h->t_w2; fa.b2 = h->t_b2;
+    fa.feat_out = h->nfeat; fa.act = h->nact; fa.n_out = h->cemb;
+    fa.frames = frames; fa.tokens = tokens; fa.dim = c.noise_dim; fa.hidden = hd;
+    if (!(cond || labels)) {
+      fa.diff_table = diffm ? h->diff_table : nullptr; fa.semb = h->csemb; fa.idx = h->cidx;
+    }
+    if ((rc = launch_fourier_embed(fa, s))) return rc;
+    h->last_feat_frames = frames;
+  }
+  if (cond || labels || flevels) {
     // per-frame conditioning: e = noise-level embedding (+ token kind) + condition embedding, then the modulation GEMM over the frames
     // (same tile form as finalize(): a frame without a condition gets the bits of its mod_table row); the blocks index it by frame
     CondEmbedArgs a;
     a.cond = cond; a.labels = labels; a.mask = cond_mask;
     a.w1 = h->c_w1; a.b1 = h->c_b1; a.w2 = h->c_w2; a.b2 = h->c_b2; a.table = h->c_table;
-    a.base = h->emb; a.levels = noise_levels; a.max_level = c.timesteps - 1; a.diff_table = diffm ? h->diff_table : nullptr;
-    a.e_out = h->cemb; a.semb = h->csemb; a.idx = h->cidx;
+    a.base = flevels ? h->cemb : h->emb; a.levels = flevels ? nullptr : noise_levels; a.max_level = c.timesteps - 1;
+    a.diff_table = diffm ? h->diff_table : nullptr;
+    a.e_out = h->cemb; a.semb = h->csemb; a.idx = h->cidx;  // (fourier: e overwrites n in place, element by element)
     a.tokens = tokens; a.cond_dim = c.cond_dim; a.hidden = hd; a.table_rows = h->c_rows;
-    if ((rc = launch_cond_embed(a, frames, s))) return rc;
+    if ((cond || labels) && (rc = launch_cond_embed(a, frames, s))) return rc;
     GemmArgs g;
     g.A = h->csemb; g.lda = hd; g.W = h->w_mod; g.M = (frames + 255) / 256 * 256; g.N = (int)h->ldt; g.K = hd;
     g.bias = h->b_mod; g.out_f32 = h->cmod; g.ldo = h->ldt;
@@ -1146,6 +1316,7 @@ static int dit_forward_impl(dfot_dit_t h, const float* x, const int32_t* noise_l
     lvl = h->idx;
     max_level = 2 * h->lpad - 1;
   }
+  if (h->front_only) return DFOT_OK;
   hipLaunchKernelGGL(patch_embed_kernel, dim3(cdiv(rows, PE_TOK)), dim3(256), PE_TOK * h->kpatch * sizeof(float), s, x, h->pe_w,
                      h->pe_b, h->pos2d, h->X, c.in_channels, c.height, c.width, c.patch_size, hd, rows);
   DFOT_CHECK_HIP(hipGetLastError());
@@ -1264,12 +1435,31 @@ int dfot_dit_forward_cond(dfot_dit_t h, const float* x, const int32_t* noise_lev
   return dit_forward_impl(h, x, noise_levels, cond, labels, cond_mask, out, batch, tokens, stream);
 }
 
+int dfot_dit_forward_f(dfot_dit_t h, const float* x, const float* noise_levels, const float* cond, const int32_t* labels,
+                       const uint8_t* cond_mask, float* out, int batch, int tokens, void* stream) {
+  DFOT_REQUIRE(h && noise_levels, DFOT_ERR_ARG, "forward_f: null argument");
+  const int type = h->cfg.cond_type;
+  if (cond || labels) {
+    DFOT_REQUIRE(type != DFOT_COND_NONE, DFOT_ERR_STATE, "forward_f: this model was built without an external condition embedding");
+    DFOT_REQUIRE(type == DFOT_COND_ACTION ? (cond && !labels) : (labels && !cond), DFOT_ERR_ARG,
+                 "forward_f: an action model takes `cond` [B,T,cond_dim], a label model takes `labels` [B,T]");
+  } else {
+    DFOT_REQUIRE(!cond_mask, DFOT_ERR_ARG, "forward_f: cond_mask without a condition");
+  }
+  return dit_forward_impl(h, x, nullptr, cond, labels, cond_mask, out, batch, tokens, stream, noise_levels);
+}
+
 int dfot_dit_read_tap(dfot_dit_t h, const char* name, float* out, size_t capacity, void* stream) {
   DFOT_REQUIRE(h && name && out, DFOT_ERR_ARG, "read_tap: null argument");
   hipStream_t s = (hipStream_t)stream;
   const float* src = nullptr;
   size_t need = 0;
-  if (!strcmp(name, "emb")) {
+  if (!strcmp(name, "noise_feat")) {  // Fourier features of every frame of the last dfot_dit_forward_f
+    DFOT_REQUIRE(h->last_feat_frames > 0, DFOT_ERR_STATE, "read_tap: no float-level forward has run");
+    src = h->nfeat;
+    need = (size_t)h->last_feat_frames * h->cfg.noise_dim;
+  } else if (!strcmp(name, "emb")) {
+    DFOT_REQUIRE(!h->cfg.fourier_noise, DFOT_ERR_ARG, "read_tap: a fourier_noise model keeps no per-level embedding table (tap \"cond_emb\" holds e per frame)");
     DFOT_REQUIRE(h->finalized, DFOT_ERR_STATE, "read_tap: weights not finalized");
     src = h->emb;
     need = (size_t)h->cfg.timesteps * h->cfg.hidden_size;

@@ -752,7 +752,7 @@ int launch_ln_bwd_rows(const float* dm, const float* x, const float* table, long
 }  // namespace dfot
 
 struct dfot_dit_train_s {
-  dfot_dit_config cfg{};
+  DitCfg cfg{};
   int gh = 0, gw = 0, P = 0, d = 0, dstride = 0, kpatch = 0, oc = 0;
   long ldt = 0, total = 0;
   std::vector<dfot::DitParam> params;   // name / shape (load unused)
@@ -773,6 +773,10 @@ struct dfot_dit_train_s {
   // compute copies
   dfot::bf16 *w_mod = nullptr, *w_modT = nullptr, *wfT = nullptr;
   float *b_mod = nullptr, *freqs = nullptr, *rope_cs = nullptr, *pos2d = nullptr;
+  // fourier_noise: FourierEmbedding's freqs / phases [noise_dim].  Buffers, not parameters: they live HERE, outside the flat parameter /
+  // gradient / moment buffers, so the optimizer (weight decay included), the gradient norm and the all-reduce never see them
+  float *fz_freqs = nullptr, *fz_phases = nullptr;
+  bool fz_loaded[2] = {false, false};
   bool synced = false;
   // workspace
   int max_batch = 0, fp = 0, batch = 0, tokens = 0;
@@ -931,9 +935,7 @@ int dfot_dit_train_destroy(dfot_dit_train_t h) {
   return DFOT_OK;
 }
 
-int dfot_dit_train_create(const dfot_dit_config* cfg, dfot_dit_train_t* out) {
-  DFOT_REQUIRE(cfg && out, DFOT_ERR_ARG, "train_create: null argument");
-  const dfot_dit_config& c = *cfg;
+static int dit_train_create_impl(const DitCfg& c, dfot_dit_train_t* out) {
   DFOT_REQUIRE(c.variant != 2, DFOT_ERR_ARG, "train_create: variant 2 (factorized attention) has no training path; it is inference only");
   DFOT_REQUIRE(c.variant != 3, DFOT_ERR_ARG, "train_create: variant 3 (factorized matrix DiT3D, FacMatDiT) has no training path; it is inference only");
   DFOT_REQUIRE(c.variant == 0 || c.variant == 1, DFOT_ERR_ARG, "train_create: unknown variant %d", c.variant);
@@ -1051,6 +1053,7 @@ int dfot_dit_train_create(const dfot_dit_config* cfg, dfot_dit_train_t* out) {
       (rc = tr_alloc(h, &h->b_mod, (size_t)h->ldt)) || (rc = tr_alloc(h, &h->wfT, (size_t)hd * 64)) ||
       (rc = tr_alloc(h, &h->freqs, (size_t)c.noise_dim / 2)))
     return fail(rc);
+  if (c.fourier_noise && ((rc = tr_alloc(h, &h->fz_freqs, (size_t)c.noise_dim)) || (rc = tr_alloc(h, &h->fz_phases, (size_t)c.noise_dim)))) return fail(rc);
   for (TrainBlock& b : h->blocks) {
     if (!b.matrix) {
       if ((rc = tr_alloc(h, &b.w_qkv, (size_t)3 * hd * hd)) || (rc = tr_alloc(h, &b.w_qkvT, (size_t)3 * hd * hd)) ||
@@ -1113,6 +1116,21 @@ int dfot_dit_train_create(const dfot_dit_config* cfg, dfot_dit_train_t* out) {
   return DFOT_OK;
 }
 
+int dfot_dit_train_create(const dfot_dit_config* cfg, dfot_dit_train_t* out) {
+  DFOT_REQUIRE(cfg && out, DFOT_ERR_ARG, "train_create: null argument");
+  DitCfg c;
+  static_cast<dfot_dit_config&>(c) = *cfg;
+  return dit_train_create_impl(c, out);
+}
+
+int dfot_dit_train_create_f(const dfot_dit_config_f* cfg, dfot_dit_train_t* out) {
+  DFOT_REQUIRE(cfg && out, DFOT_ERR_ARG, "train_create_f: null argument");
+  DitCfg c;
+  static_cast<dfot_dit_config&>(c) = cfg->base;
+  c.fourier_noise = cfg->fourier_noise;
+  return dit_train_create_impl(c, out);
+}
+
 int dfot_dit_train_num_params(dfot_dit_train_t h) { return h ? (int)h->params.size() : 0; }
 const char* dfot_dit_train_param_name(dfot_dit_train_t h, int i) {
   return (h && i >= 0 && i < (int)h->params.size()) ? h->params[i].name.c_str() : nullptr;
@@ -1126,6 +1144,19 @@ int dfot_dit_train_param_shape(dfot_dit_train_t h, int i, int64_t shape[4], int*
 int64_t dfot_dit_train_param_offset(dfot_dit_train_t h, int i) { return (h && i >= 0 && i < (int)h->offsets.size()) ? h->offsets[i] : -1; }
 int64_t dfot_dit_train_total_numel(dfot_dit_train_t h) { return h ? h->total : 0; }
 size_t dfot_dit_train_workspace_bytes(dfot_dit_train_t h) { return h ? h->ws_bytes : 0; }
+
+int dfot_dit_train_load_buffer(dfot_dit_train_t h, const char* name, const float* data, int64_t numel, void* stream) {
+  DFOT_REQUIRE(h && name && data, DFOT_ERR_ARG, "train_load_buffer: null argument");
+  DFOT_REQUIRE(h->cfg.fourier_noise, DFOT_ERR_NAME, "train_load_buffer: unexpected key '%s' (the model has no Fourier noise embedding)", name);
+  int which = -1;
+  if (!strcmp(name, "noise_level_pos_embedding.timesteps.freqs")) which = 0;
+  if (!strcmp(name, "noise_level_pos_embedding.timesteps.phases")) which = 1;
+  DFOT_REQUIRE(which >= 0, DFOT_ERR_NAME, "train_load_buffer: unexpected key '%s'", name);
+  DFOT_REQUIRE(numel == h->cfg.noise_dim, DFOT_ERR_SHAPE, "train_load_buffer: size mismatch for '%s'", name);
+  DFOT_CHECK_HIP(hipMemcpyAsync(which ? h->fz_phases : h->fz_freqs, data, (size_t)numel * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  h->fz_loaded[which] = true;
+  return DFOT_OK;
+}
 
 int dfot_dit_train_attach(dfot_dit_train_t h, float* params, float* grads) {
   DFOT_REQUIRE(h && params && grads, DFOT_ERR_ARG, "train_attach: null argument");
@@ -1185,7 +1216,7 @@ int dfot_dit_train_reserve(dfot_dit_train_t h, int max_batch) {
   h->ws_owned.clear();
   h->ws_bytes = 0;
   h->max_batch = 0;
-  const dfot_dit_config& c = h->cfg;
+  const DitCfg& c = h->cfg;
   const bool facmat = c.variant == 1;
   const int hd = c.hidden_size, nd = c.noise_dim, E = c.embed_col_dim;
   const size_t rows = (size_t)max_batch * c.max_tokens * h->P;
@@ -1245,11 +1276,17 @@ int dfot_dit_train_reserve(dfot_dit_train_t h, int max_batch) {
 }  // extern "C"
 
 static int dit_train_forward_impl(dfot_dit_train_t h, const float* x, const int32_t* noise_levels, const float* cond, const int32_t* labels,
-                                  const uint8_t* cond_mask, float* out, int batch, int tokens, void* stream) {
-  DFOT_REQUIRE(h && x && noise_levels && out, DFOT_ERR_ARG, "train_forward: null argument");
+                                  const uint8_t* cond_mask, float* out, int batch, int tokens, void* stream, const float* flevels = nullptr) {
+  DFOT_REQUIRE(h && x && (noise_levels || flevels) && out, DFOT_ERR_ARG, "train_forward: null argument");
+  DFOT_REQUIRE(!h->cfg.fourier_noise || flevels, DFOT_ERR_ARG,
+               "train_forward: this model embeds float noise levels (fourier_noise); call dfot_dit_train_forward_f");
+  DFOT_REQUIRE(h->cfg.fourier_noise || !flevels, DFOT_ERR_ARG,
+               "train_forward_f: this model indexes integer noise levels (no fourier_noise); call dfot_dit_train_forward / dfot_dit_train_forward_cond");
+  DFOT_REQUIRE(!flevels || (h->fz_loaded[0] && h->fz_loaded[1]), DFOT_ERR_STATE,
+               "train_forward_f: load noise_level_pos_embedding.timesteps.freqs / .phases with dfot_dit_train_load_buffer first");
   DFOT_REQUIRE(h->synced, DFOT_ERR_STATE, "train_forward: call dfot_dit_train_sync_weights after attaching / updating the parameters");
   DFOT_REQUIRE(batch > 0 && batch <= h->max_batch, DFOT_ERR_STATE, "train_forward: batch %d exceeds the reserved %d", batch, h->max_batch);
-  const dfot_dit_config& c = h->cfg;
+  const DitCfg& c = h->cfg;
   const bool facmat = c.variant == 1;
   DFOT_REQUIRE(tokens > 0 && tokens <= c.max_tokens, DFOT_ERR_SHAPE, "train_forward: %d tokens, max_tokens is %d", tokens, c.max_tokens);
   DFOT_REQUIRE(!facmat || tokens % 2 == 0, DFOT_ERR_SHAPE, "train_forward: %d tokens; the difference model takes (difference, frame) pairs", tokens);
@@ -1263,7 +1300,10 @@ static int dit_train_forward_impl(dfot_dit_train_t h, const float* x, const int3
   h->d_embed = nullptr;
   // ---- conditioning: c = Linear2(SiLU(Linear1(features(level)))) [+ diff embedding] per frame; table = Linear_mod(SiLU(c)) ----
   hipLaunchKernelGGL(iota_kernel, dim3(cdiv(frames, 256)), dim3(256), 0, s, h->idx, frames);
-  hipLaunchKernelGGL(tr_features_kernel, dim3(cdiv((long)frames * nd, 256)), dim3(256), 0, s, h->freqs, noise_levels, h->feat, frames, nd, c.timesteps - 1);
+  if (flevels)  // continuous diffusion: Fourier features of the float level; everything after them (and their role in the backward) is unchanged
+    hipLaunchKernelGGL(fourier_features_kernel, dim3(cdiv((long)frames * nd, 256)), dim3(256), 0, s, flevels, h->fz_freqs, h->fz_phases, h->feat, frames, nd);
+  else
+    hipLaunchKernelGGL(tr_features_kernel, dim3(cdiv((long)frames * nd, 256)), dim3(256), 0, s, h->freqs, noise_levels, h->feat, frames, nd, c.timesteps - 1);
   hipLaunchKernelGGL(rows_linear_kernel<0>, dim3(cdiv(hd, 4), frames), dim3(256), 0, s, h->feat, p + h->o_t_w1, p + h->o_t_b1, h->h1, (bf16*)nullptr, nd, hd);
   hipLaunchKernelGGL(silu_fwd_kernel, dim3(cdiv((long)frames * hd, 256)), dim3(256), 0, s, h->h1, h->a1, (long)frames * hd);
   DFOT_CHECK_HIP(hipMemsetAsync(h->semb, 0, (size_t)h->fp * hd * sizeof(bf16), s));
@@ -1368,11 +1408,25 @@ int dfot_dit_train_forward_cond(dfot_dit_train_t h, const float* x, const int32_
   return dit_train_forward_impl(h, x, noise_levels, cond, labels, cond_mask, out, batch, tokens, stream);
 }
 
+int dfot_dit_train_forward_f(dfot_dit_train_t h, const float* x, const float* noise_levels, const float* cond, const int32_t* labels,
+                             const uint8_t* cond_mask, float* out, int batch, int tokens, void* stream) {
+  DFOT_REQUIRE(h && noise_levels, DFOT_ERR_ARG, "train_forward_f: null argument");
+  const int type = h->cfg.cond_type;
+  if (cond || labels) {
+    DFOT_REQUIRE(type != DFOT_COND_NONE, DFOT_ERR_STATE, "train_forward_f: this model was built without an external condition embedding");
+    DFOT_REQUIRE(type == DFOT_COND_ACTION ? (cond && !labels) : (labels && !cond), DFOT_ERR_ARG,
+                 "train_forward_f: an action model takes `cond` [B,T,cond_dim], a label model takes `labels` [B,T]");
+  } else {
+    DFOT_REQUIRE(!cond_mask, DFOT_ERR_ARG, "train_forward_f: cond_mask without a condition");
+  }
+  return dit_train_forward_impl(h, x, nullptr, cond, labels, cond_mask, out, batch, tokens, stream, noise_levels);
+}
+
 // gradients of every parameter for the upstream gradient d_out [B,T,C,H,W] of the last forward's output; OVERWRITES the grads buffer
 int dfot_dit_train_backward(dfot_dit_train_t h, const float* d_out, void* stream) {
   DFOT_REQUIRE(h && d_out, DFOT_ERR_ARG, "train_backward: null argument");
   DFOT_REQUIRE(h->batch > 0 && h->x_saved, DFOT_ERR_STATE, "train_backward: no forward to differentiate");
-  const dfot_dit_config& c = h->cfg;
+  const DitCfg& c = h->cfg;
   const bool facmat = c.variant == 1;
   const int batch = h->batch, tokens = h->tokens, n = tokens * h->P, hd = c.hidden_size, P = h->P, frames = batch * tokens, nd = c.noise_dim;
   const int fp = h->fp, E = c.embed_col_dim;
@@ -1562,7 +1616,7 @@ int dfot_dit_train_backward(dfot_dit_train_t h, const float* d_out, void* stream
 int dfot_dit_train_input_grad(dfot_dit_train_t h, float* dx, void* stream) {
   DFOT_REQUIRE(h && dx, DFOT_ERR_ARG, "train_input_grad: null argument");
   DFOT_REQUIRE(h->batch > 0 && h->d_embed, DFOT_ERR_STATE, "train_input_grad: run dfot_dit_train_backward first");
-  const dfot_dit_config& c = h->cfg;
+  const DitCfg& c = h->cfg;
   const long rows = (long)h->batch * h->tokens * h->P;
   const int kdim = c.in_channels * c.patch_size * c.patch_size;
   hipLaunchKernelGGL(pe_dgrad_kernel, dim3(cdiv(rows * kdim, 256)), dim3(256), 0, (hipStream_t)stream, h->d_embed, h->params_f32 + h->o_pe_w, dx,

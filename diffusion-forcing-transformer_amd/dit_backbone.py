@@ -11,6 +11,10 @@ Mirrors the reference's plugin contract for this path:
   * state-dict key names / shapes / order of the reference module, so its checkpoints load with ``load_state_dict``.
 Parameters live here as fp32 ``nn.Parameter``s; the C library keeps packed bf16 copies and a per-level modulation table
 that are rebuilt whenever a parameter changes.
+
+With ``use_fourier_noise_embedding: true`` (``@diffusion/continuous``, base_backbone.py:35-39) the model runs under ContinuousDiffusion:
+``noise_levels`` are floating ``precond_scale * logsnr`` values, ``noise_level_pos_embedding.timesteps.{freqs,phases}`` are persistent
+buffers (FourierEmbedding, embeddings.py:94-109) and no per-level table exists: the embedding is evaluated per frame in every forward.
 """
 from __future__ import annotations
 
@@ -23,6 +27,10 @@ from torch import nn
 
 from . import capi, ops
 from .backbone import _Node, _get
+
+
+# FourierEmbedding's persistent buffers, in the reference's state_dict order (before noise_level_pos_embedding.embedding.*)
+FOURIER_BUFFERS = ("noise_level_pos_embedding.timesteps.freqs", "noise_level_pos_embedding.timesteps.phases")
 
 
 def configure_condition(c: "capi.DiTConfig", cfg, external_cond_type, external_cond_num_classes, external_cond_dim) -> None:
@@ -132,7 +140,7 @@ class DiT3D(nn.Module):
         self.external_cond_dropout = float(_get(cfg, "external_cond_dropout", 0.0) or 0.0) if self.external_cond_dim else 0.0
         self.use_causal_mask = False
         self.patch_size = int(_get(cfg, "patch_size", 2))
-        c = capi.DiTConfig()
+        c = capi.DiTConfigF()
         c.depth = int(_get(cfg, "depth"))
         c.num_heads = int(_get(cfg, "num_heads"))
         c.patch_size = self.patch_size
@@ -142,13 +150,15 @@ class DiT3D(nn.Module):
         c.rope_theta = 10000.0
         c.eps = 1e-6
         configure_condition(c, cfg, external_cond_type, external_cond_num_classes, self.external_cond_dim)
+        self.use_fourier_noise_embedding = bool(_get(cfg, "use_fourier_noise_embedding", False))
+        c.fourier_noise = int(self.use_fourier_noise_embedding)
         self._configure(c, cfg, int(max_tokens))
         self.hidden_size = int(c.hidden_size)
         self.max_tokens = int(c.max_tokens)
         self._ccfg = c
         self.num_patches = (c.height // c.patch_size) * (c.width // c.patch_size)
         self._handle = C.c_void_p()
-        capi.check(capi.lib.dfot_dit_create(C.byref(c), C.byref(self._handle)))
+        capi.check(capi.lib.dfot_dit_create_f(C.byref(c), C.byref(self._handle)))
         self._names = []
         shape = (C.c_int64 * 4)()
         ndim = C.c_int()
@@ -219,10 +229,19 @@ class DiT3D(nn.Module):
             if part not in node._modules:
                 node.add_module(part, _Node())
             node = node._modules[part]
-        node.register_parameter(leaf, nn.Parameter(torch.zeros(shape, dtype=torch.float32)))
+        if name == FOURIER_BUFFERS[0]:  # drawn as FourierEmbedding.__init__ draws them (bandwidth 1), from torch's default generator
+            node.register_buffer(leaf, 2 * math.pi * torch.randn(shape))
+        elif name == FOURIER_BUFFERS[1]:
+            node.register_buffer(leaf, 2 * math.pi * torch.rand(shape))
+        else:
+            node.register_parameter(leaf, nn.Parameter(torch.zeros(shape, dtype=torch.float32)))
 
     def _tensors(self) -> Dict[str, torch.Tensor]:
         return dict(self.named_parameters())
+
+    def _engine_tensors(self) -> Dict[str, torch.Tensor]:
+        """everything the engine loads: the parameters and, on a Fourier model, the two buffers"""
+        return {**dict(self.named_parameters()), **dict(self.named_buffers())}
 
     def reset_parameters(self, seed: int = 0) -> None:
         """The reference's init (dit3d.py:92-109, dit_blocks.py:392-395,422-425,476-486,528-531): xavier-uniform Linear
@@ -256,13 +275,13 @@ class DiT3D(nn.Module):
                 t.copy_(v.to(t.device))
 
     def _signature(self) -> Tuple:
-        return tuple((t.data_ptr(), t._version) for t in self._tensors().values())
+        return tuple((t.data_ptr(), t._version) for t in self._engine_tensors().values())
 
     def sync_weights(self, force: bool = False) -> None:
         sig = self._signature()
         if not force and sig == self._synced:
             return
-        tensors = self._tensors()
+        tensors = self._engine_tensors()
         s = capi.stream_ptr()
         for name in self._names:
             t = tensors[name]
@@ -329,6 +348,7 @@ class DiT3D(nn.Module):
             name = "factorized_attention" if self._ccfg.variant == 2 else "factorized_matrix_attention"
             raise NotImplementedError(f"variant {name!r} is inference only: there is no training path and no input gradient "
                                       "(reconstruction guidance); call it under torch.no_grad() / with parameters that do not require grad")
+        c = mask = None
         if external_cond is not None:
             b, t = x.shape[:2]
             cond, labels = condition_tensors(self._ccfg, external_cond, b, t, self._ccfg.variant == 1)
@@ -336,6 +356,11 @@ class DiT3D(nn.Module):
             if labels is not None:
                 labels = self._labels_with_dropout(labels)
             c = cond if cond is not None else labels
+        if self.use_fourier_noise_embedding:  # float levels (ContinuousDiffusion): one operator pair, the condition optional
+            if train:
+                return torch.ops.dfot.dit3d_forward_f_train(x, noise_levels, c, mask, params, self._op_key)
+            return torch.ops.dfot.dit3d_forward_f(x, noise_levels, c, mask, self._op_key)
+        if external_cond is not None:
             if train:
                 return torch.ops.dfot.dit3d_forward_cond_train(x, noise_levels, c, mask, params, self._op_key)
             return torch.ops.dfot.dit3d_forward_cond(x, noise_levels, c, mask, self._op_key)
@@ -350,20 +375,31 @@ class DiT3D(nn.Module):
         """trainer.DiT3DTrainer on the module's CURRENT weights: built once; its flat parameter buffer is refreshed (and the bf16
         compute copies re-packed) whenever a parameter changed since the last training forward."""
         from . import trainer as _trainer
-        sig = tuple((t.data_ptr(), t._version) for t in params)
+        from .diffusion import DiffusionConfig
+        buffers = dict(self.named_buffers())
+        sig = tuple((t.data_ptr(), t._version) for t in (*params, *buffers.values()))
         if self._trainer is None:
             self._trainer = _trainer.DiT3DTrainer(self.cfg, self.x_shape, self._ctor["max_tokens"], timesteps=self._ctor["timesteps"],
                                                   external_cond_type=self._ctor["external_cond_type"],
                                                   external_cond_num_classes=self._ctor["external_cond_num_classes"],
-                                                  external_cond_dim=self._ctor["external_cond_dim"])
+                                                  external_cond_dim=self._ctor["external_cond_dim"],
+                                                  diffusion=DiffusionConfig(is_continuous=True) if self.use_fourier_noise_embedding else None)
             missing = [n for n in self._trainer.layout if n not in self._train_names]
             if missing:
                 raise RuntimeError(f"the training engine expects parameters the module does not have: {missing[:4]}")
         if sig != self._trainer_sig:
             with torch.no_grad():
-                self._trainer.load_state_dict({n: t for n, t in zip(self._train_names, params) if n in self._trainer.layout})
+                self._trainer.load_state_dict({**{n: t for n, t in zip(self._train_names, params) if n in self._trainer.layout}, **buffers})
             self._trainer_sig = sig
         return self._trainer
+
+    def _check_level_dtype(self, noise_levels: torch.Tensor) -> None:
+        if self.use_fourier_noise_embedding:
+            if not noise_levels.is_floating_point():
+                raise TypeError("this DiT3D was built with use_fourier_noise_embedding: it takes floating noise levels "
+                                "(ContinuousDiffusion passes precond_scale * logsnr)")
+        elif noise_levels.is_floating_point():
+            raise TypeError("DiT3D takes integer noise levels (DiscreteDiffusion passes the level index)")
 
     def _train_forward_impl(self, x, noise_levels, params, cond=None, cond_mask=None):
         if x.ndim != 5 or tuple(x.shape[2:]) != self.x_shape:
@@ -372,8 +408,7 @@ class DiT3D(nn.Module):
             raise ValueError(f"{x.shape[1]} tokens exceed max_tokens={self.max_tokens}")
         if tuple(noise_levels.shape) != tuple(x.shape[:2]):
             raise ValueError(f"noise_levels has shape {tuple(noise_levels.shape)}, expected {tuple(x.shape[:2])}")
-        if noise_levels.is_floating_point():
-            raise TypeError("DiT3D takes integer noise levels (DiscreteDiffusion passes the level index)")
+        self._check_level_dtype(noise_levels)
         dev = params[0].device
         if dev.type != "cuda":
             raise RuntimeError(f"the backbone's parameters are on {dev}; move the module to the GPU first (there is no CPU path)")
@@ -408,8 +443,7 @@ class DiT3D(nn.Module):
             raise ValueError(f"{t} tokens exceed max_tokens={self.max_tokens}")
         if tuple(noise_levels.shape) != (b, t):
             raise ValueError(f"noise_levels has shape {tuple(noise_levels.shape)}, expected {(b, t)}")
-        if noise_levels.is_floating_point():
-            raise TypeError("DiT3D takes integer noise levels (DiscreteDiffusion passes the level index)")
+        self._check_level_dtype(noise_levels)
         dev = next(self.parameters()).device
         if dev.type != "cuda":
             raise RuntimeError(f"the backbone's parameters are on {dev}; move the module to the GPU first (there is no CPU path)")
@@ -417,8 +451,22 @@ class DiT3D(nn.Module):
         self.sync_weights()
         self.reserve(b)
         xf = x.detach().to(torch.float32).contiguous()
-        kf = noise_levels.detach().to(torch.int32).contiguous()
         out = torch.empty_like(xf)
+        if self.use_fourier_noise_embedding:
+            kf = noise_levels.detach().to(torch.float32).contiguous()
+            pc = pl = None
+            if cond is not None:
+                action = self._ccfg.cond_type == capi.COND_ACTION
+                want = (b, t, int(self._ccfg.cond_dim)) if action else (b, t)
+                if tuple(cond.shape) != want or (cond_mask is not None and tuple(cond_mask.shape) != (b,)):
+                    raise ValueError(f"condition has shape {tuple(cond.shape)}, expected {want} (mask {(b,)})")
+                pc = capi.ptr(cond, torch.float32, "external_cond") if action else None
+                pl = None if action else capi.ptr(cond, torch.int32, "external_cond")
+            capi.check(capi.lib.dfot_dit_forward_f(self._handle, capi.ptr(xf, torch.float32, "x"), capi.ptr(kf, torch.float32, "noise_levels"),
+                                                   pc, pl, capi.ptr(cond_mask if cond is not None else None, torch.uint8, "external_cond_mask"),
+                                                   capi.ptr(out), b, t, capi.stream_ptr()))
+            return out.to(x.dtype)
+        kf = noise_levels.detach().to(torch.int32).contiguous()
         if cond is None:
             capi.check(capi.lib.dfot_dit_forward(self._handle, capi.ptr(xf, torch.float32, "x"), capi.ptr(kf, torch.int32, "noise_levels"),
                                                  capi.ptr(out), b, t, capi.stream_ptr()))
@@ -435,8 +483,9 @@ class DiT3D(nn.Module):
         return out.to(x.dtype)
 
     def read_tap(self, name: str, rows: int) -> torch.Tensor:
-        """"emb" (rows = timesteps), "stream" (rows = B*T*P), "cond_emb" (rows = B*T of the last conditioned forward)"""
-        out = torch.empty(rows, self.hidden_size, device="cuda", dtype=torch.float32)
+        """"emb" (rows = timesteps; not on a Fourier model), "stream" (rows = B*T*P), "cond_emb" (rows = B*T of the last per-frame forward),
+        "noise_feat" (rows = B*T of the last float-level forward, noise_level_dim columns)"""
+        out = torch.empty(rows, self.noise_level_dim if name == "noise_feat" else self.hidden_size, device="cuda", dtype=torch.float32)
         capi.check(capi.lib.dfot_dit_read_tap(self._handle, name.encode(), capi.ptr(out), out.numel(), capi.stream_ptr()))
         return out
 

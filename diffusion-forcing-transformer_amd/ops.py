@@ -8,6 +8,8 @@ FakeTensor tracing, ``torch.compile`` graphs and stream capture treat the HIP ke
     dfot::uvit3d_pose_forward_train(x, noise_levels, external_cond, mask?, params[], model) -> v    [autograd: dfot_op_* forward/backward]
     dfot::dit3d_forward(x, noise_levels, model) -> v                                                [dfot_dit_forward]
     dfot::dit3d_forward_cond(x, noise_levels, external_cond, external_cond_mask?, model) -> v       [dfot_dit_forward_cond]
+    dfot::dit3d_forward_f(x, noise_levels (float), external_cond?, external_cond_mask?, model) -> v [dfot_dit_forward_f]
+    dfot::dit3d_forward_f_train(x, noise_levels (float), external_cond?, mask?, params[], model) -> v  [autograd: dfot_dit_train_forward_f]
     dfot::ray_encoding(raw_poses, resolution) -> cond                                               [dfot_ray_encode]
     dfot::hg_prepare(x, noise?, qa, qb, nfe) -> x_in                                                [dfot_hg_prepare]
     dfot::ddim_hg_step(x, x_in, v, sa, s1, an, cn, keep, weight, gen, nfe) -> x_next                [dfot_ddim_compose / _tokw]
@@ -191,6 +193,32 @@ def _dit_cond_train_backward(ctx, grad_out):
 
 
 dit3d_forward_cond_train.register_autograd(_dit_cond_train_backward, setup_context=_dit_cond_train_setup_context)
+
+
+# ---- float noise levels (a DiT3D / DifferenceDiT3D built with use_fourier_noise_embedding, under ContinuousDiffusion): one operator
+# for the unconditioned and the conditioned call (external_cond None / given), and its training form with the backward of the int ops
+@custom_op("dfot::dit3d_forward_f", mutates_args=())
+def dit3d_forward_f(x: Tensor, noise_levels: Tensor, external_cond: Optional[Tensor], external_cond_mask: Optional[Tensor], model: int) -> Tensor:
+    return _model(model)._forward_impl(x, noise_levels, external_cond, external_cond_mask)
+
+
+@dit3d_forward_f.register_fake
+def _(x, noise_levels, external_cond, external_cond_mask, model):
+    return torch.empty_like(x)
+
+
+@custom_op("dfot::dit3d_forward_f_train", mutates_args=())
+def dit3d_forward_f_train(x: Tensor, noise_levels: Tensor, external_cond: Optional[Tensor], external_cond_mask: Optional[Tensor],
+                          params: List[Tensor], model: int) -> Tensor:
+    return _model(model)._train_forward_impl(x, noise_levels, params, external_cond, external_cond_mask)
+
+
+@dit3d_forward_f_train.register_fake
+def _(x, noise_levels, external_cond, external_cond_mask, params, model):
+    return torch.empty_like(x)
+
+
+dit3d_forward_f_train.register_autograd(_dit_cond_train_backward, setup_context=_dit_cond_train_setup_context)
 
 
 @custom_op("dfot::ray_encoding", mutates_args=())

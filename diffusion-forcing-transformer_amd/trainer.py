@@ -8,6 +8,13 @@ Mirrors, for the DiT3D "full" / rope_3d model (README ``@DiT/XL``, attention-onl
   * ``BasePytorchAlgo.configure_optimizers``        AdamW(lr, weight_decay, betas) + Lightning's gradient_clip_val
   * DDP gradient averaging                          experiments (Lightning ``ddp`` strategy)
 No autograd and no torch kernels on the path: torch provides device memory, the stream and the collective.
+
+Continuous diffusion (``@diffusion/continuous``): built with ``diffusion=DiffusionConfig(is_continuous=True, ...)`` and a cfg with
+``use_fourier_noise_embedding: true`` the same trainer runs ``ContinuousDiffusion.forward`` (continuous_diffusion.py:140-167): levels are
+t in [0, 1], the backbone receives ``precond_scale * logsnr(t)`` as floats, the loss is the sigmoid-weighted one of ``dfot_vpred_loss``.
+FourierEmbedding's ``freqs`` / ``phases`` are buffers: they are kept OUT of the flat parameter / gradient / moment buffers (``self.buffers``),
+so they have no gradient, no optimizer state, no weight decay and no entry in ``grad_dict()``; ``state_dict()`` lists them first, where
+the reference's does.
 """
 from __future__ import annotations
 
@@ -28,9 +35,9 @@ class DiT3DTrainer:
                  betas: Tuple[float, float] = (0.9, 0.99), eps: float = 1e-8, max_grad_norm: Optional[float] = 1.0,
                  loss_weighting: Optional[Dict] = None, external_cond_type: str = "action",
                  external_cond_num_classes: Optional[int] = None, external_cond_dim: int = 0):
-        from .dit_backbone import configure_condition
+        from .dit_backbone import FOURIER_BUFFERS, configure_condition
         self.x_shape = tuple(int(v) for v in x_shape)
-        c = capi.DiTConfig()
+        c = capi.DiTConfigF()
         configure_condition(c, cfg, external_cond_type, external_cond_num_classes, external_cond_dim)
         self.external_cond_dropout = float(_get(cfg, "external_cond_dropout", 0.0) or 0.0) if external_cond_dim else 0.0
         c.depth = int(_get(cfg, "depth"))
@@ -64,10 +71,17 @@ class DiT3DTrainer:
         else:
             raise ValueError(f"no training path for DiT variant {variant!r}")
         c.mlp_hidden = int(c.hidden_size * ratio) if ratio else 0
+        fourier = bool(_get(cfg, "use_fourier_noise_embedding", False))
+        continuous = bool(diffusion is not None and diffusion.is_continuous)
+        if fourier != continuous:
+            raise ValueError(f"use_fourier_noise_embedding={fourier} with DiffusionConfig(is_continuous={continuous}): continuous diffusion "
+                             "needs the Fourier noise-level embedding (float levels) and discrete diffusion the indexed one")
+        self.is_continuous = continuous
+        c.fourier_noise = int(fourier)
         self._ccfg = c
         self.max_tokens = int(c.max_tokens)
         self._handle = C.c_void_p()
-        capi.check(capi.lib.dfot_dit_train_create(C.byref(c), C.byref(self._handle)))
+        capi.check(capi.lib.dfot_dit_train_create_f(C.byref(c), C.byref(self._handle)))
         lib, h = capi.lib, self._handle
         self.numel = int(lib.dfot_dit_train_total_numel(h))
         shape, ndim = (C.c_int64 * 4)(), C.c_int()
@@ -83,6 +97,12 @@ class DiT3DTrainer:
         self.exp_avg_sq = torch.zeros_like(self.params)
         self._sumsq = torch.zeros(1, device="cuda", dtype=torch.float32)
         capi.check(lib.dfot_dit_train_attach(h, capi.ptr(self.params), capi.ptr(self.grads)))
+        # FourierEmbedding's buffers (reference draw: 2 pi N(0,1), 2 pi U[0,1)); tensors of their own, never part of the flat buffers
+        self.buffers: Dict[str, torch.Tensor] = {}
+        if fourier:
+            self.buffers = {FOURIER_BUFFERS[0]: (2 * np.pi * torch.randn(int(c.noise_dim))).cuda(),
+                            FOURIER_BUFFERS[1]: (2 * np.pi * torch.rand(int(c.noise_dim))).cuda()}
+            self._load_buffers()
         self.lr, self.weight_decay, self.betas, self.eps, self.max_grad_norm = lr, weight_decay, tuple(betas), eps, max_grad_norm
         self.step_count = 0
         self.schedule = Schedule(diffusion or DiffusionConfig(beta_schedule="cosine", is_continuous=False, timesteps=timesteps))
@@ -106,11 +126,21 @@ class DiT3DTrainer:
         off, shape = self.layout[name]
         return (self.params if buf is None else buf)[off: off + int(np.prod(shape))].view(shape)
 
+    def _load_buffers(self) -> None:
+        for k, t in self.buffers.items():
+            capi.check(capi.lib.dfot_dit_train_load_buffer(self._handle, k.encode(), capi.ptr(t, torch.float32, k), t.numel(), capi.stream_ptr()))
+
     def load_state_dict(self, state: Dict[str, torch.Tensor], strict: bool = True) -> None:
-        missing = [k for k in self.layout if k not in state]
-        extra = [k for k in state if k not in self.layout]
+        missing = [k for k in (*self.buffers, *self.layout) if k not in state]
+        extra = [k for k in state if k not in self.layout and k not in self.buffers]
         if strict and (missing or extra):
             raise KeyError(f"state_dict mismatch: missing {missing[:4]}, unexpected {extra[:4]}")
+        for k in self.buffers:
+            if k in state:
+                if tuple(state[k].shape) != tuple(self.buffers[k].shape):
+                    raise ValueError(f"{k}: shape {tuple(state[k].shape)} != {tuple(self.buffers[k].shape)}")
+                self.buffers[k].copy_(state[k].to(device="cuda", dtype=torch.float32))
+        self._load_buffers()
         for k in self.layout:
             if k in state:
                 t = state[k]
@@ -120,7 +150,7 @@ class DiT3DTrainer:
         self._dirty = True
 
     def state_dict(self) -> Dict[str, torch.Tensor]:
-        return {k: self.view(k).detach().clone() for k in self.layout}
+        return {**{k: t.detach().clone() for k, t in self.buffers.items()}, **{k: self.view(k).detach().clone() for k in self.layout}}
 
     def grad_dict(self) -> Dict[str, torch.Tensor]:
         return {k: self.view(k, self.grads).detach().clone() for k in self.layout}
@@ -143,9 +173,25 @@ class DiT3DTrainer:
             self._reserved = b
         self._sync()
         xd = x.to(device="cuda", dtype=torch.float32).contiguous()
-        lv = noise_levels.to(device="cuda", dtype=torch.int32).contiguous()
+        if self.is_continuous != bool(noise_levels.is_floating_point()):
+            raise TypeError("a continuous-diffusion trainer takes floating noise levels (precond_scale * logsnr)" if self.is_continuous
+                            else "DiT3DTrainer takes integer noise levels (DiscreteDiffusion passes the level index)")
+        lv = noise_levels.to(device="cuda", dtype=torch.float32 if self.is_continuous else torch.int32).contiguous()
         out = torch.empty_like(xd)
-        if cond is None:
+        if self.is_continuous:
+            pc = pl = pm = None
+            if cond is not None:
+                action = self._ccfg.cond_type == capi.COND_ACTION
+                if self._ccfg.cond_type == capi.COND_NONE:
+                    raise ValueError("this trainer was built without an external condition embedding")
+                want = (b, t, int(self._ccfg.cond_dim)) if action else (b, t)
+                if tuple(cond.shape) != want or (cond_mask is not None and tuple(cond_mask.shape) != (b,)):
+                    raise ValueError(f"condition has shape {tuple(cond.shape)}, expected {want} (mask {(b,)})")
+                cd = cond.to(device="cuda", dtype=torch.float32 if action else torch.int32).contiguous()
+                md = None if cond_mask is None else cond_mask.to(device="cuda", dtype=torch.uint8).contiguous()
+                pc, pl, pm = (capi.ptr(cd) if action else None), (None if action else capi.ptr(cd)), capi.ptr(md)
+            capi.check(capi.lib.dfot_dit_train_forward_f(self._handle, capi.ptr(xd), capi.ptr(lv), pc, pl, pm, capi.ptr(out), b, t, capi.stream_ptr()))
+        elif cond is None:
             capi.check(capi.lib.dfot_dit_train_forward(self._handle, capi.ptr(xd), capi.ptr(lv), capi.ptr(out), b, t, capi.stream_ptr()))
         else:
             action = self._ccfg.cond_type == capi.COND_ACTION
@@ -198,6 +244,8 @@ class DiT3DTrainer:
         cond, cdrop = self._condition(conditions, b, t, dropout_generator)
         self.last_cond_dropout = cdrop
         f = int(np.prod(xs.shape[2:]))
+        if self.is_continuous:
+            return self._continuous_loss_and_grads(xs, k, noise, masks, cond, cdrop)
         kk = k.detach().cpu().numpy().astype(np.int64)
         sch = self.schedule
         w = sch.loss_weights(kk, **self.loss_weighting).astype(np.float32)
@@ -219,6 +267,32 @@ class DiT3DTrainer:
                                             capi.ptr(dv), b, t, f, 1, s()))
         self.backward(dv)
         return (per_token * torch.from_numpy(mk).cuda()).mean()
+
+    def _continuous_loss_and_grads(self, xs, t_levels, noise, masks, cond, cdrop):
+        """ContinuousDiffusion.forward (continuous_diffusion.py:140-167) + _reweight_loss: k in [0, 1] per token -> cosine logSNR with the
+        configured shift (DiffusionConfig.training_logsnr_tables, the helper the U-ViT loss paths use), x_t = alpha x + sigma eps, the
+        backbone at precond_scale * logsnr, sigmoid-weighted error (dfot_vpred_loss) averaged over (B, T) with the loss masks; backward."""
+        dcfg = self.schedule.cfg
+        b, t = xs.shape[:2]
+        f = int(np.prod(xs.shape[2:]))
+        logsnr, alpha, sigma, weight = dcfg.training_logsnr_tables(t_levels)
+        mk = torch.ones(b, t) if masks is None else masks.detach().float().cpu().view(b, t)
+        tab = torch.stack([alpha, sigma, weight, float(dcfg.precond_scale) * logsnr, 2.0 * weight * mk / (f * b * t)]).float().cuda().contiguous()
+        x = xs.to(device="cuda", dtype=torch.float32).contiguous()
+        eps = noise.to(device="cuda", dtype=torch.float32).clamp(-dcfg.clip_noise, dcfg.clip_noise).contiguous()
+        x_t = torch.empty_like(x)
+        s = capi.stream_ptr
+        capi.check(capi.lib.dfot_hg_prepare(capi.ptr(x), capi.ptr(eps), capi.ptr(tab[0]), capi.ptr(tab[1]), capi.ptr(x_t), b, 1, t, f, s()))
+        v = self.forward(x_t, tab[3], cond, cdrop)
+        per_token = torch.empty(b, t, device="cuda")
+        scratch = torch.empty(int(capi.lib.dfot_vpred_loss_scratch_floats(b, t, f)), device="cuda")
+        capi.check(capi.lib.dfot_vpred_loss(capi.ptr(x), capi.ptr(eps), capi.ptr(v), capi.ptr(tab[0]), capi.ptr(tab[1]), capi.ptr(tab[2]),
+                                            None, capi.ptr(scratch), capi.ptr(per_token), b, t, f, s()))
+        dv = torch.empty_like(x)
+        capi.check(capi.lib.dfot_vloss_grad(capi.ptr(x), capi.ptr(eps), capi.ptr(v), capi.ptr(tab[0]), capi.ptr(tab[1]), capi.ptr(tab[4]),
+                                            capi.ptr(dv), b, t, f, 0, s()))
+        self.backward(dv)
+        return (per_token * mk.cuda()).mean()
 
     def difference_loss_and_grads(self, frames: torch.Tensor, k: torch.Tensor, noise: torch.Tensor, masks: Optional[torch.Tensor] = None,
                                   conditions: Optional[torch.Tensor] = None, dropout_generator: Optional[torch.Generator] = None):

@@ -36,6 +36,9 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--out", default="sample_out.npz")
     ap.add_argument("--cond", help="k600 / k600diff: synthetic external condition, 'action:DIM' (e.g. action:3, as dmlab) or 'label:CLASSES' (label:101)")
+    ap.add_argument("--continuous", action="store_true",
+                    help="k600 / k600diff / facdit / facmat: continuous diffusion as @diffusion/continuous (Fourier noise-level embedding, float levels, "
+                         "cosine_simple_diffusion shifted 0.125), the way the dmlab / Minecraft DiT recipes run")
     a = ap.parse_args()
     gen = torch.Generator(device="cuda").manual_seed(a.seed)
     noise = dfot_amd.device_noise_fn(gen)
@@ -68,21 +71,22 @@ def main():
             bb = dict(name="difference_dit3d", variant="factorized_matrix_attention", pos_emb_type="sinusoidal_2d", merge_type="interleaved",
                       patch_size=1, embed_col_dim=64, embed_row_dim=1152, num_heads=12, num_col_heads=1, num_row_heads=16, depth=28,
                       mlp_ratio=4.0, spatial_mlp_ratio=4.0, use_bias=True, matrix_block="matrix")
-            model = dfot_amd.DifferenceDiT3D(bb, x_shape=(16, 16, 16), max_tokens=5, **ckw).cuda()
+            model = dfot_amd.DifferenceDiT3D(dict(bb, use_fourier_noise_embedding=a.continuous), x_shape=(16, 16, 16), max_tokens=5, **ckw).cuda()
         elif fac:  # per depth a per-frame spatial block and a temporal block over the 16 frames of every patch position (inference only)
             bb = dict(name="dit3d", variant="factorized_attention", pos_emb_type="sinusoidal_factorized", patch_size=2, hidden_size=1152,
                       depth=28, num_heads=16, mlp_ratio=4.0, spatial_mlp_ratio=0.0)
-            model = dfot_amd.DiT3D(bb, x_shape=x_shape, max_tokens=tokens, **ckw).cuda()
+            model = dfot_amd.DiT3D(dict(bb, use_fourier_noise_embedding=a.continuous), x_shape=x_shape, max_tokens=tokens, **ckw).cuda()
         elif facmat:  # per depth a per-frame spatial block and a matrix block whose attention takes every frame as one token (inference only)
             bb = dict(name="dit3d", variant="factorized_matrix_attention", pos_emb_type="sinusoidal_2d", use_temporal_rope=True, patch_size=2,
                       embed_col_dim=64, embed_row_dim=1152, num_heads=16, num_col_heads=1, num_row_heads=16, depth=28, mlp_ratio=4.0,
                       spatial_mlp_ratio=4.0, use_bias=False, matrix_block="matrix", flatten_matrix_rope=False, matrix_multi_token=False)
-            model = dfot_amd.DiT3D(bb, x_shape=x_shape, max_tokens=tokens, **ckw).cuda()
+            model = dfot_amd.DiT3D(dict(bb, use_fourier_noise_embedding=a.continuous), x_shape=x_shape, max_tokens=tokens, **ckw).cuda()
         else:
             bb = dict(name="dit3d", variant="full", pos_emb_type="rope_3d", patch_size=1, hidden_size=1152, depth=28, num_heads=16)
-            model = dfot_amd.DiT3D(bb, x_shape=x_shape, max_tokens=tokens, **ckw).cuda()
+            model = dfot_amd.DiT3D(dict(bb, use_fourier_noise_embedding=a.continuous), x_shape=x_shape, max_tokens=tokens, **ckw).cuda()
         cfg = dfot_amd.SamplerConfig(x_shape=x_shape, max_tokens=10 if diff else tokens,
-                                     diffusion=dfot_amd.DiffusionConfig(sampling_timesteps=a.steps, beta_schedule="cosine", is_continuous=False),
+                                     diffusion=(dfot_amd.DiffusionConfig(sampling_timesteps=a.steps, is_continuous=True) if a.continuous else
+                                                dfot_amd.DiffusionConfig(sampling_timesteps=a.steps, beta_schedule="cosine", is_continuous=False)),
                                      prediction_guidance=dict(name="vanilla", guidance_scale=1.5) if a.cond else {"name": "conditional"}, **skw)
         sampler = (dfot_amd.DifferenceDFoTVideoSampler if diff else dfot_amd.DFoTVideoSampler)(cfg, model, noise)
         xs = torch.randn(a.batch, tokens, *x_shape, generator=torch.Generator().manual_seed(a.seed))

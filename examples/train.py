@@ -41,6 +41,9 @@ def main():
     ap.add_argument("--warmup-steps", type=int, default=10000, help="re10k: linear lr warm-up (constant_with_warmup, realestate10k_video_generation.yaml)")
     ap.add_argument("--save")
     ap.add_argument("--cond", help="k600 / k600diff: train with a synthetic external condition, 'action:DIM' (action:3) or 'label:CLASSES' (label:101)")
+    ap.add_argument("--continuous", action="store_true",
+                    help="k600 / k600diff: continuous diffusion as @diffusion/continuous (Fourier noise-level embedding, levels in [0, 1], cosine "
+                         "training schedule shifted 0.125, sigmoid loss weighting)")
     ap.add_argument("--pixels", action="store_true", help="k600 / k600diff: encode synthetic frames online with the VideoVAE encoder")
     ap.add_argument("--vae-ckpt", help="--pixels: reference VideoVAE checkpoint (vae.* keys); random encoder weights otherwise")
     a = ap.parse_args()
@@ -63,18 +66,21 @@ def main():
         cfg = dict(name="difference_dit3d", variant="factorized_matrix_attention", pos_emb_type="sinusoidal_2d", merge_type="interleaved",
                    patch_size=1, embed_col_dim=64, embed_row_dim=1152, num_heads=12, num_col_heads=1, num_row_heads=16, depth=28,
                    mlp_ratio=4.0, spatial_mlp_ratio=4.0, use_bias=True, matrix_block="matrix")
+        cfg["use_fourier_noise_embedding"] = a.continuous
         if a.cond:
             cfg["external_cond_dropout"] = 0.1
         init = dfot_amd.DifferenceDiT3D(cfg, x_shape=(16, 16, 16), max_tokens=5, **ckw)
-        sampling = dfot_amd.TrainingNoise(noise_level="random_uniform", is_continuous=False, n_context_tokens=2,
+        sampling = dfot_amd.TrainingNoise(noise_level="random_uniform", is_continuous=a.continuous, n_context_tokens=2,
                                           variable_context=dfot_amd.ContextTraining(enabled=True, prob=0.25, dropout=0.3))
     else:
         cfg = dict(name="dit3d", variant="full", pos_emb_type="rope_3d", patch_size=1, hidden_size=1152, depth=28, num_heads=16)
+        cfg["use_fourier_noise_embedding"] = a.continuous
         if a.cond:
             cfg["external_cond_dropout"] = 0.1
         init = dfot_amd.DiT3D(cfg, x_shape=(16, 16, 16), max_tokens=5, **ckw)
-        sampling = dfot_amd.TrainingNoise(noise_level="random_independent", is_continuous=False, n_context_tokens=2)
-    trainer = dfot_amd.DiT3DTrainer(cfg, x_shape=(16, 16, 16), max_tokens=5, lr=a.lr, **ckw)
+        sampling = dfot_amd.TrainingNoise(noise_level="random_independent", is_continuous=a.continuous, n_context_tokens=2)
+    trainer = dfot_amd.DiT3DTrainer(cfg, x_shape=(16, 16, 16), max_tokens=5, lr=a.lr,
+                                    diffusion=dfot_amd.DiffusionConfig(is_continuous=True) if a.continuous else None, **ckw)
     if a.ckpt:
         dfot_amd.load_reference_checkpoint(trainer, a.ckpt)
     else:

@@ -183,7 +183,19 @@ typedef struct {
 } dfot_dit_config;
 enum { DFOT_COND_NONE = 0, DFOT_COND_ACTION = 1, DFOT_COND_LABEL = 2 };
 
+/* dfot_dit_config with one trailing field, as its own type: dfot_dit_config keeps its size and its last field, so callers built against
+ * it (and dfot_dit_create / dfot_dit_train_create, which read exactly that many bytes) stay valid.
+ * fourier_noise = backbone.use_fourier_noise_embedding (ContinuousDiffusion, shortcut/diffusion/continuous.yaml): the noise level is a float
+ * (precond_scale * logsnr) embedded by FourierEmbedding (embeddings.py:94-109) -> TimestepEmbedding.  Registers the two persistent buffers
+ * noise_level_pos_embedding.timesteps.{freqs,phases} [noise_dim] before embedding.linear_1 (the reference's state_dict position), builds
+ * no per-level table, and is driven through the *_forward_f entry points only.  0: exactly the model dfot_dit_create builds from `base`. */
+typedef struct {
+  dfot_dit_config base;
+  int32_t fourier_noise;
+} dfot_dit_config_f;
+
 int dfot_dit_create(const dfot_dit_config* cfg, dfot_dit_t* out);
+int dfot_dit_create_f(const dfot_dit_config_f* cfg, dfot_dit_t* out);
 int dfot_dit_destroy(dfot_dit_t h);
 int dfot_dit_num_params(dfot_dit_t h);
 const char* dfot_dit_param_name(dfot_dit_t h, int index);
@@ -195,7 +207,8 @@ int dfot_dit_load_weight(dfot_dit_t h, const char* name, const float* data, cons
 int dfot_dit_finalize(dfot_dit_t h, void* stream);
 int dfot_dit_reserve(dfot_dit_t h, int max_batch);
 size_t dfot_dit_workspace_bytes(dfot_dit_t h);
-/* "gemm_variant" (-1 auto), "time_attn" (as for dfot_uvit_set_option) */
+/* "gemm_variant" (-1 auto), "time_attn" (as for dfot_uvit_set_option), "front_only" (1: a forward stops once the AdaLN modulations
+ * of the call are formed and leaves `out` untouched -- for timing the front end alone) */
 int dfot_dit_set_option(dfot_dit_t h, const char* key, int value);
 int dfot_dit_attn_timing(dfot_dit_t h, double* total_ms, int64_t* launches);
 /* out[B,T,C,H,W] = model(x[B,T,C,H,W], noise_levels[B,T]) ; x/out fp32, noise_levels int32 in [0, timesteps)
@@ -211,8 +224,18 @@ int dfot_dit_forward(dfot_dit_t h, const float* x, const int32_t* noise_levels, 
  * per-level table; nothing after that differs.  No allocation, no host synchronisation: capturable in a graph. */
 int dfot_dit_forward_cond(dfot_dit_t h, const float* x, const int32_t* noise_levels, const float* cond, const int32_t* labels,
                           const uint8_t* cond_mask, float* out, int batch, int tokens, void* stream);
-/* parity taps after the last forward: "emb" [timesteps][hidden] (noise-level embedding of every level),
- * "stream" [B*T*P][hidden] (residual stream after the last block), "cond_emb" [B*T][hidden] (e of the last conditioned forward) */
+/* Continuous diffusion (a model of dfot_dit_create_f with fourier_noise != 0): out = model(x, noise_levels[B,T] fp32).  One kernel forms, per frame and in fp32,
+ * feat[j] = sqrt(2) * cos(level * freqs[j] + phases[j]) (one rounded multiply, one rounded add, accurately range-reduced cosine) and
+ * n = linear_2(SiLU(linear_1(feat))); e = n (+ token kind, variant 1) (+ condition embedding unless the video's cond_mask byte is set) then
+ * feeds the per-frame modulation GEMM of dfot_dit_forward_cond, and nothing after it differs.  cond / labels / cond_mask as in
+ * dfot_dit_forward_cond; all NULL runs without a condition term (the only form an unconditioned model takes).  No allocation, no host
+ * synchronisation; a video gives the same bits alone and in a batch.  On a model without fourier_noise this returns DFOT_ERR_ARG, as
+ * dfot_dit_forward / dfot_dit_forward_cond do on a model with it. */
+int dfot_dit_forward_f(dfot_dit_t h, const float* x, const float* noise_levels, const float* cond, const int32_t* labels,
+                       const uint8_t* cond_mask, float* out, int batch, int tokens, void* stream);
+/* parity taps after the last forward: "emb" [timesteps][hidden] (noise-level embedding of every level; DFOT_ERR_ARG on a fourier_noise
+ * model, which tabulates nothing), "stream" [B*T*P][hidden] (residual stream after the last block), "cond_emb" [B*T][hidden] (e of the
+ * last per-frame forward), "noise_feat" [B*T][noise_dim] (Fourier features of the last dfot_dit_forward_f) */
 int dfot_dit_read_tap(dfot_dit_t h, const char* name, float* out, size_t capacity_floats, void* stream);
 
 /* ---- DiT3D training path ("full" variant, attention-only blocks) ----------------------------------
@@ -225,6 +248,7 @@ int dfot_dit_read_tap(dfot_dit_t h, const char* name, float* out, size_t capacit
  *         -> sync_weights */
 typedef struct dfot_dit_train_s* dfot_dit_train_t;
 int dfot_dit_train_create(const dfot_dit_config* cfg, dfot_dit_train_t* out);
+int dfot_dit_train_create_f(const dfot_dit_config_f* cfg, dfot_dit_train_t* out);  /* with dfot_dit_config_f.fourier_noise (see dfot_dit_create_f) */
 int dfot_dit_train_destroy(dfot_dit_train_t h);
 int dfot_dit_train_num_params(dfot_dit_train_t h);
 const char* dfot_dit_train_param_name(dfot_dit_train_t h, int i);
@@ -242,6 +266,14 @@ int dfot_dit_train_forward(dfot_dit_train_t h, const float* x, const int32_t* no
  * embedding (label table: row-wise sums in frame order, rows of unused classes exactly zero; no floating-point atomics). */
 int dfot_dit_train_forward_cond(dfot_dit_train_t h, const float* x, const int32_t* noise_levels, const float* cond, const int32_t* labels,
                                 const uint8_t* cond_mask, float* out, int batch, int tokens, void* stream);
+/* fourier_noise models: freqs / phases are buffers, not parameters -- they are NOT part of the flat parameter / gradient / moment buffers
+ * (no gradient, no optimizer state, no weight decay can reach them).  Load each once: name = the reference's state_dict key
+ * ("noise_level_pos_embedding.timesteps.freqs" / ".phases"), data = device fp32 [noise_dim]. */
+int dfot_dit_train_load_buffer(dfot_dit_train_t h, const char* name, const float* data, int64_t numel, void* stream);
+/* dfot_dit_train_forward / _cond for a fourier_noise model: float levels [B,T]; cond / labels / cond_mask all NULL on an unconditioned
+ * model (or to run without the condition term).  The backward is dfot_dit_train_backward, with the Fourier features as linear_1's input. */
+int dfot_dit_train_forward_f(dfot_dit_train_t h, const float* x, const float* noise_levels, const float* cond, const int32_t* labels,
+                             const uint8_t* cond_mask, float* out, int batch, int tokens, void* stream);
 /* grads <- d(sum(out * d_out))/d(params) for the last forward (overwrites the attached gradient buffer) */
 int dfot_dit_train_backward(dfot_dit_train_t h, const float* d_out, void* stream);
 /* dx[B,T,C,H,W] <- d(sum(out * d_out))/d(x) of the same forward / backward pair (call after dfot_dit_train_backward): what autograd gives

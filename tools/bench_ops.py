@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Micro-benchmarks of the C-ABI primitives at the RE10K model shapes (model batch 2), HIP-event timed.
-Usage (GPU box): python tools/bench_ops.py [gemm] [conv] [attn] [tattn] [mattn] [vae_encode] [equal]"""
+Usage (GPU box): python tools/bench_ops.py [gemm] [conv] [attn] [tattn] [mattn] [vae_encode] [equal] [dit_front]"""
 import ctypes as C
 import math
 import os
@@ -53,6 +53,37 @@ def attn(b, heads, n, d, variant):
     o = torch.empty(b, n, heads * d, device="cuda", dtype=torch.bfloat16)
     ms = timeit(lambda: capi.check(capi.lib.dfot_op_attention(P(q), P(k), P(v), P(o), heads * d, b, heads, n, d, variant, S())))
     return ms, 4.0 * b * heads * n * n * d / ms / 1e9
+
+
+def dit_front(name, bb, cls, x_shape, max_tokens, batch, tokens):
+    """front end (everything up to and including the modulation GEMM) and whole forward of one DiT shape on three paths: float levels
+    (Fourier model), the conditioned int-level path (dfot_dit_forward_cond, the yardstick: the same downstream work) and the unconditioned
+    per-level table.  HIP events, 5 warm-up + 50 timed launches each."""
+    kw = dict(external_cond_type="action", external_cond_dim=4)
+    models = {"float": cls(dict(bb, use_fourier_noise_embedding=True), x_shape=x_shape, max_tokens=max_tokens, **kw),
+              "int cond": cls(bb, x_shape=x_shape, max_tokens=max_tokens, **kw)}
+    x = torch.randn(batch, tokens, *x_shape, device="cuda")
+    cond = torch.randn(batch, tokens, 4, device="cuda")
+    levels = {"float": 2.5 * torch.randn(batch, tokens, device="cuda"), "int cond": torch.randint(0, 1000, (batch, tokens), device="cuda")}
+    rows = []
+    with torch.no_grad():
+        for tag, m in models.items():
+            m.cuda().eval()
+            m.init_random(0)
+            calls = {tag: lambda m=m, tag=tag: m(x, levels[tag], cond)}
+            if tag == "int cond":
+                calls["int table"] = lambda m=m: m(x, levels["int cond"])
+            for path, fn in calls.items():
+                fn()
+                m.set_option("front_only", 1)
+                front = timeit(fn, iters=50, warm=5)
+                m.set_option("front_only", 0)
+                whole = timeit(fn, iters=50, warm=5)
+                rows.append((path, front, whole))
+    for path, front, whole in rows:
+        print(f"dit_front {name:10s} B={batch} T={tokens} {path:9s}: front end {front*1e3:8.1f} us  forward {whole:8.3f} ms", flush=True)
+    f, c = rows[0], rows[1]
+    print(f"dit_front {name:10s} float - int cond: front end {(f[1]-c[1])*1e3:+.1f} us, forward {(f[2]-c[2])*1e3:+.1f} us", flush=True)
 
 
 HBM_TBS = 8.0  # the HBM3E rate the repository's rooflines use (DESIGN.md)
@@ -200,6 +231,13 @@ def main():
                 w = torch.randn(n, k, device="cuda").bfloat16()
                 ms = timeit(lambda: torch.nn.functional.linear(a, w))
                 print(f"gemm {name:12s} M={m:6d} N={n:5d} K={k:5d} torch/hipBLASLt: {ms*1e3:8.1f} us  {2.0*m*n*k/ms/1e9:7.1f} TF/s", flush=True)
+    if "dit_front" in what:
+        xl = dict(name="dit3d", variant="full", pos_emb_type="rope_3d", patch_size=1, hidden_size=1152, depth=28, num_heads=16)
+        dit_front("XL K600", xl, dfot_amd.DiT3D, (16, 16, 16), 5, 8, 5)  # @DiT/XL at the K600 latents: B = 8, T = 5, P = 256
+        b = dict(name="dit3d", variant="full", pos_emb_type="rope_3d", patch_size=2, hidden_size=768, depth=12, num_heads=12)
+        # @DiT/B width, 16 tokens x 16 patches, B = 16.  8 latent channels: at hidden 768 the final layer stages its (p*p*C x hidden) fp32 weight in
+        # LDS and refuses the 32-channel dmlab / Minecraft latents (393 KB); the front end does not depend on the channel count
+        dit_front("DiT/B", b, dfot_amd.DiT3D, (8, 8, 8), 16, 16, 16)
     if "conv" in what:
         for name, (bt, h, w, ci, co) in {"L0 res": (16, 128, 128, 128, 128), "L1 res": (16, 64, 64, 256, 256),
                                          "down0": (16, 64, 64, 128, 256), "down1": (16, 32, 32, 256, 576),
