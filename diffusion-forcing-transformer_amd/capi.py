@@ -205,6 +205,9 @@ SIGNATURES = {
     "dfot_op_conv3t_f32": (_I, [_P, _P, _P, _P, _P] + [_I] * 9 + [_P]),
     "dfot_op_vae_pixels": (_I, [_P, _L, _L, _L, _L, _L, _F, _F, _P, _I, _I, _I, _I, _P]),
     "dfot_op_vae_posterior": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "dfot_op_ivae_attention": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
+    "dfot_op_conv3x3_s2_f32": (_I, [_P, _P, _P, _P] + [_I] * 5 + [_P]),
+    "dfot_op_upconv3x3_f32": (_I, [_P, _P, _P, _P] + [_I] * 5 + [_P]),
     "dfot_op_f32_to_bf16": (_I, [_P, _P, _L, _P]),
     "dfot_op_bf16_to_f32": (_I, [_P, _P, _L, _P]),
     "dfot_op_equal_bits": (_I, [_P, _P, _L, _P, _P]),

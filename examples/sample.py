@@ -6,6 +6,7 @@
   python examples/sample.py k600diff [--ckpt ...]
   python examples/sample.py facdit   [--ckpt ...]   (FacDiT-XL, the taichikl recipe: 4x32x32 latents, patch 2, 16 frames)
   python examples/sample.py facmat   [--ckpt ...]   (FacMatDiT XL-64-1, the same recipe: matrix attention with RoPE over the 16 frames)
+  python examples/sample.py k600 --continuous --decode-image-vae   (latents -> frames through a random-weight per-frame ImageVAE)
 
 Without --ckpt the backbone gets seeded random weights (there is no network here to fetch the released checkpoints);
 with it, the reference's .ckpt / ema.safetensors is read by dfot_amd.load_reference_checkpoint (keys
@@ -39,6 +40,9 @@ def main():
     ap.add_argument("--continuous", action="store_true",
                     help="k600 / k600diff / facdit / facmat: continuous diffusion as @diffusion/continuous (Fourier noise-level embedding, float levels, "
                          "cosine_simple_diffusion shifted 0.125), the way the dmlab / Minecraft DiT recipes run")
+    ap.add_argument("--decode-image-vae", action="store_true",
+                    help="decode the sampled latents with a random-weight ImageVAE (image_vae.yaml widths, z_channels = the latent channels), the "
+                         "per-frame autoencoder of the dmlab / Minecraft recipes; latents of 8x8 or 16x16 (the mid attention's sizes)")
     a = ap.parse_args()
     gen = torch.Generator(device="cuda").manual_seed(a.seed)
     noise = dfot_amd.device_noise_fn(gen)
@@ -116,6 +120,16 @@ def main():
     gen_frames = (out.shape[1] - n_ctx) * out.shape[0]
     print(f"{a.model}: {tuple(out.shape)} in {dt:.2f} s  ({gen_frames / dt:.2f} generated frames/s, "
           f"{sampler.window_forwards} backbone forwards of one window)")
+    if a.decode_image_vae:
+        zc, lh, _ = out.shape[2:]
+        vae = dfot_amd.ImageVAEDecoder(ch=128, out_ch=3, ch_mult=(1, 2, 4, 4), num_res_blocks=2, z_channels=zc, embed_dim=zc, resolution=8 * lh).cuda()
+        vae.init_random(seed=a.seed)
+        dfot_amd.decode_image_latents(vae, out[:1], vae_batch_size=1)   # packs the weights, loads the kernels
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        frames = dfot_amd.decode_image_latents(vae, out, vae_batch_size=2)
+        torch.cuda.synchronize()
+        print(f"ImageVAE decode (random weights): {tuple(out.shape)} -> {tuple(frames.shape)} in {(time.perf_counter() - t0) * 1e3:.1f} ms")
     np.savez_compressed(a.out, out=out.cpu().numpy())
 
 

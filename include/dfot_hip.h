@@ -569,6 +569,21 @@ int dfot_op_vae_pixels(const float* x, int64_t sb, int64_t sc, int64_t st, int64
 int dfot_op_vae_posterior(const float* moments, int ld, const float* eps, const float* data_mean, const float* data_std, float* mean, float* logvar,
                           float* std_, float* z, int batch, int frames, int hw, int zc, void* stream);
 
+/* ---- ImageVAE pieces (algorithms/vae/image_vae/model.py:18-245; AttnBlock attention.py:39-83, Upsample / Downsample
+ * updownsample.py:10-45): per-frame layers on channels-last [frames][H][W][C] activations. ------------------------------------------- */
+/* o bf16 [frames*n][c] = softmax(q k^T / sqrt(c)) v per frame: ONE head over the n positions of a frame with all c channels, every frame in
+ * one launch, no score matrix in memory (fp32 softmax with the row max subtracted, P rounded to bf16).  q, k, v bf16 [frames*n][c].
+ * n in {64, 256}, c a multiple of 128 up to 1024; other shapes: DFOT_ERR_SHAPE. */
+int dfot_op_ivae_attention(const void* q, const void* k, const void* v, void* o, int frames, int n, int c, void* stream);
+/* y fp32 [frames][h_in/2][w_in/2][cout] (+ bias) = Conv2d(k 3, s 2, p 0) of F.pad(x, (0, 1, 0, 1)): zero padding on the right and bottom only.
+ * x bf16 [frames][h_in][w_in][cin], w bf16 [cout][9][cin] (dfot_op_pack_conv3).  h_in, w_in even, cin % 64 == 0, cout % 128 == 0. */
+int dfot_op_conv3x3_s2_f32(const void* x, const void* w, const float* bias, float* y, int frames, int h_in, int w_in, int cin, int cout,
+                           void* stream);
+/* y fp32 [frames][2 h_in][2 w_in][cout] (+ bias) = Conv2d(k 3, s 1, p 1) of the nearest-2x upsampled x, the upsampling fused into the
+ * gather (source pixel ((y + dy - 1) >> 1, (x + dx - 1) >> 1)).  Operands as dfot_op_conv3x3_s2_f32. */
+int dfot_op_upconv3x3_f32(const void* x, const void* w, const float* bias, float* y, int frames, int h_in, int w_in, int cin, int cout,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Micro-benchmarks of the C-ABI primitives at the RE10K model shapes (model batch 2), HIP-event timed.
-Usage (GPU box): python tools/bench_ops.py [gemm] [conv] [attn] [tattn] [mattn] [vae_encode] [equal] [dit_front]"""
+Usage (GPU box): python tools/bench_ops.py [gemm] [conv] [attn] [tattn] [mattn] [vae_encode] [equal] [dit_front] [ivae]"""
 import ctypes as C
 import math
 import os
@@ -210,8 +210,53 @@ def equal(nbytes):
     return ms, 2.0 * nbytes / ms / 1e6
 
 
+def ivae():
+    """the three ImageVAE ops (csrc/image_vae.hip) at the image_vae.yaml recipe's shapes, the per-frame loop of existing ops that the
+    fused attention replaces (vae.py:_attn), and a whole decode / encode of 16 frames at 128 x 128.  Each figure: the median of 7 repeats of
+    (3 warm-up + 20 timed launches between two HIP events)."""
+    import statistics
+    med = lambda fn: statistics.median(timeit(fn) for _ in range(7))
+    n, c = 256, 512
+    for frames in (16, 128):
+        q, k, v = (torch.randn(frames * n, c, device="cuda").bfloat16() for _ in range(3))
+        o = torch.empty_like(q)
+        ms = med(lambda: capi.check(capi.lib.dfot_op_ivae_attention(P(q), P(k), P(v), P(o), frames, n, c, S())))
+        scores, probs = torch.empty(n, n, device="cuda"), torch.empty(n, n, dtype=torch.bfloat16, device="cuda")
+        vt, o2 = torch.empty(c, n, dtype=torch.bfloat16, device="cuda"), torch.empty_like(q)
+
+        def loop():
+            for f in range(frames):
+                qf, kf, vf, of = (a[f * n:(f + 1) * n] for a in (q, k, v, o2))
+                capi.check(capi.lib.dfot_op_gemm_f32(P(qf), c, P(kf), None, None, P(scores), n, n, n, c, S()))
+                capi.check(capi.lib.dfot_op_softmax_rows(P(scores), P(probs), n, n, float(c) ** -0.5, S()))
+                capi.check(capi.lib.dfot_op_transpose_bf16(P(vf), P(vt), n, c, S()))
+                capi.check(capi.lib.dfot_op_gemm_bf16(P(probs), n, P(vt), None, P(of), c, n, c, n, S()))
+        ms_loop = med(loop)
+        diff = ((o.float() - o2.float()).norm() / o2.float().norm()).item()
+        flop = 4.0 * frames * n * n * c
+        print(f"ivae attention {frames:3d} frames N={n} C={c}: fused {ms*1e3:8.1f} us ({flop / ms / 1e9:6.1f} TF/s)  per-frame loop of 4 launches "
+              f"{ms_loop*1e3:9.1f} us  ({ms_loop / ms:.1f}x; rel-L2 between them {diff:.1e})", flush=True)
+    for name, entry, (frames, h, w, ci, co), up in (("upsample-conv 512->512 16^2 -> 32^2", capi.lib.dfot_op_upconv3x3_f32, (16, 16, 16, 512, 512), True),
+                                                    ("downsample 128->128 128^2 -> 64^2", capi.lib.dfot_op_conv3x3_s2_f32, (16, 128, 128, 128, 128), False)):
+        x = torch.randn(frames, h, w, ci, device="cuda").bfloat16()
+        wt = (torch.randn(co, 9 * ci, device="cuda") / math.sqrt(9 * ci)).bfloat16()
+        ho, wo = (2 * h, 2 * w) if up else (h // 2, w // 2)
+        out = torch.empty(frames, ho, wo, co, device="cuda")
+        ms = med(lambda: capi.check(entry(P(x), P(wt), None, P(out), frames, h, w, ci, co, S())))
+        print(f"ivae {name}, {frames} frames: {ms*1e3:8.1f} us  {2.0 * frames * ho * wo * co * 9 * ci / ms / 1e9:6.1f} TF/s", flush=True)
+    cfg = dict(ch=128, out_ch=3, ch_mult=(1, 2, 4, 4), num_res_blocks=2, z_channels=4, embed_dim=4, resolution=128)
+    dec, enc = dfot_amd.ImageVAEDecoder(**cfg).cuda(), dfot_amd.ImageVAEEncoder(**cfg).cuda()
+    dec.init_random(0)
+    enc.init_random(1)
+    z, y = torch.randn(16, 4, 16, 16, device="cuda"), torch.rand(16, 3, 128, 128, device="cuda") * 2 - 1
+    print(f"ivae decode 16 frames 4x16x16 -> 3x128x128 (image_vae.yaml): {med(lambda: dec.decode(z)):.3f} ms", flush=True)
+    print(f"ivae encode 16 frames 3x128x128 -> moments (image_vae.yaml): {med(lambda: enc.encode(y)):.3f} ms", flush=True)
+
+
 def main():
     what = sys.argv[1:] or ["gemm", "conv", "attn"]
+    if "ivae" in what:
+        ivae()
     if "vae_encode" in what:
         vae_encode()
     variants = [int(x) for x in os.environ.get("VARIANTS", "1").split(",")]

@@ -264,3 +264,18 @@ def install_vae():
          download_pretrained=lambda p: p)
     model = importlib.import_module("algorithms.vae.video_vae.model")   # imports algorithms.vae.common(.modules) for real
     return model.VideoVAE
+
+
+def install_image_vae():
+    """The reference's ImageVAE building blocks (algorithms/vae/image_vae/model.py and algorithms/vae/common/modules/*) importable on their
+    own: image_vae/__init__.py and trainer.py pull Lightning / lpips, so the namespace packages skip them.  Returns (Encoder, Decoder); the
+    ImageVAE wrapper around them (trainer.py:281-345) is two nn.Conv2d(.., 1) that tools/make_golden_image_vae.py states itself."""
+    if REF not in sys.path:
+        sys.path.insert(0, REF)
+    sys.dont_write_bytecode = True
+    for name, rel in [("algorithms", "algorithms"), ("algorithms.vae", "algorithms/vae"), ("algorithms.vae.image_vae", "algorithms/vae/image_vae"),
+                      ("utils", "utils")]:
+        if name not in sys.modules:
+            _ns(name, f"{REF}/{rel}")
+    model = importlib.import_module("algorithms.vae.image_vae.model")   # imports algorithms.vae.common.modules for real
+    return model.Encoder, model.Decoder
