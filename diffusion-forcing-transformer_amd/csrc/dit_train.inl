@@ -1629,11 +1629,10 @@ int dfot_dit_train_input_grad(dfot_dit_train_t h, float* dx, void* stream) {
 int dfot_vloss_grad(const float* x, const float* noise, const float* v, const float* a, const float* sigma, const float* coef, float* dv,
                     int batch, int tokens, int64_t frame_elems, int vspace, void* stream) {
   DFOT_REQUIRE(x && noise && v && a && sigma && coef && dv, DFOT_ERR_ARG, "vloss_grad: null argument");
-  return launch_vloss_grad(x, noise, v, a, sigma, coef, dv, batch * tokens, frame_elems, vspace != 0, (hipStream_t)stream);
+  return launch_vloss_grad(x, noise, v, a, sigma, coef, dv, batch, tokens, (long)frame_elems, vspace != 0, (hipStream_t)stream);
 }
 int dfot_sumsq(const float* x, int64_t n, float* out, void* stream) {
   DFOT_REQUIRE(x && out && n > 0, DFOT_ERR_ARG, "sumsq: bad argument");
-  DFOT_CHECK_HIP(hipMemsetAsync(out, 0, sizeof(float), (hipStream_t)stream));
   return launch_sumsq(x, n, out, (hipStream_t)stream);
 }
 int dfot_adamw_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1, float beta2,

@@ -74,7 +74,7 @@ int launch_ddim_noise(const float* noise, const float* sigma, const float* weigh
 // v-prediction loss: partial = scratch [bt][vloss_chunks(f)], loss[bt] = mean over the frame of w*(eps_hat-eps)^2
 int vloss_chunks(long f);
 int launch_vloss(const float* x, const float* noise, const float* v, const float* a, const float* sg, const float* w,
-                 float* x_pred, float* partial, float* loss, int bt, long f, bool vspace, hipStream_t s);
+                 float* x_pred, float* partial, float* loss, int batch, int tokens, long f, bool vspace, hipStream_t s);
 // ---- weight-gradient GEMM over the token axis (wgrad.hip): out[slices][M][N] = partial sums of A^T B, A [rows][lda], B [rows][ldb] ----
 int launch_wgrad_nt(const bf16* a, long lda, const bf16* b, long ldb, float* out, int m, int n, long rows, int slices, hipStream_t s, int img_h = 0,
                     int img_w = 0, int sdy = 0, int sdx = 0, int all_taps = 0);
@@ -88,7 +88,7 @@ int wgrad_conv_tiles(int co, int ci, int* target);
 int launch_wgrad_nt_plan(const bf16* a, long lda, const bf16* b, long ldb, float* out, int m, int n, long rows, WgradPlan plan, hipStream_t s);
 // ---- training: loss gradient, gradient norm, AdamW (flat fp32 buffers) ----
 int launch_vloss_grad(const float* x, const float* noise, const float* v, const float* a, const float* sg, const float* coef, float* dv,
-                      int bt, long f, bool vspace, hipStream_t s);
+                      int batch, int tokens, long f, bool vspace, hipStream_t s);
 int launch_sumsq(const float* x, long n, float* out, hipStream_t s);
 int launch_adamw(float* p, const float* g, float* m, float* v, long n, float lr, float b1, float b2, float eps, float wd, int step,
                  const float* sumsq, float max_norm, float* ema, float ema_decay, hipStream_t s);

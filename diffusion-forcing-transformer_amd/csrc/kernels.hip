@@ -1170,6 +1170,8 @@ __global__ void hg_prepare_kernel(const float* __restrict__ x, const float* __re
 }
 int launch_hg_prepare(const float* x, const float* noise, const float* qa, const float* qb, float* x_in, int batch,
                       int nfe, int tokens, long f, hipStream_t s) {
+  DFOT_REQUIRE(batch > 0 && nfe > 0 && tokens > 0 && f > 0, DFOT_ERR_SHAPE, "hg_prepare: batch %d, branches %d, tokens %d, frame elements %ld must be positive",
+               batch, nfe, tokens, f);
   DFOT_REQUIRE(f % 4 == 0, DFOT_ERR_SHAPE, "hg_prepare: frame elements %ld must be a multiple of 4", f);
   const long total4 = (long)batch * nfe * tokens * (f / 4);
   DFOT_REQUIRE(total4 < (1L << 31), DFOT_ERR_SHAPE, "hg_prepare: %ld work items exceed the 32-bit index range", total4);
@@ -1217,6 +1219,8 @@ __global__ void ddim_compose_kernel(const float* __restrict__ x, const float* __
 int launch_ddim_compose(const float* x, const float* x_in, const float* v, const float* sa, const float* s1,
                         const float* an, const float* cn, const float* keep, const float* weight, const uint8_t* gen,
                         float* x_next, int batch, int nfe, int tokens, long f, bool weight_per_token, hipStream_t s) {
+  DFOT_REQUIRE(batch > 0 && nfe > 0 && tokens > 0 && f > 0, DFOT_ERR_SHAPE, "ddim_compose: batch %d, branches %d, tokens %d, frame elements %ld must be positive",
+               batch, nfe, tokens, f);
   DFOT_REQUIRE(f % 4 == 0, DFOT_ERR_SHAPE, "ddim_compose: frame elements %ld must be a multiple of 4", f);
   const long total4 = (long)batch * tokens * (f / 4);
   DFOT_REQUIRE(total4 < (1L << 31), DFOT_ERR_SHAPE, "ddim_compose: %ld work items exceed the 32-bit index range", total4);
@@ -1251,6 +1255,8 @@ __global__ void ddim_noise_kernel(const float* __restrict__ noise, const float* 
 }
 int launch_ddim_noise(const float* noise, const float* sigma, const float* weight, const uint8_t* gen, float* x_next, int batch, int nfe,
                       int tokens, long f, bool weight_per_token, hipStream_t s) {
+  DFOT_REQUIRE(batch > 0 && nfe > 0 && tokens > 0 && f > 0, DFOT_ERR_SHAPE, "ddim_noise: batch %d, branches %d, tokens %d, frame elements %ld must be positive",
+               batch, nfe, tokens, f);
   DFOT_REQUIRE(f % 4 == 0, DFOT_ERR_SHAPE, "ddim_noise: frame elements %ld must be a multiple of 4", f);
   const long total4 = (long)batch * tokens * (f / 4);
   DFOT_REQUIRE(total4 < (1L << 31), DFOT_ERR_SHAPE, "ddim_noise: %ld work items exceed the 32-bit index range", total4);
@@ -1301,8 +1307,12 @@ __global__ void vloss_finalize_kernel(const float* __restrict__ partial, float* 
 }
 int vloss_chunks(long f) { return cdiv(f, VL_CHUNK); }
 int launch_vloss(const float* x, const float* noise, const float* v, const float* a, const float* sg, const float* w,
-                 float* x_pred, float* partial, float* loss, int bt, long f, bool vspace, hipStream_t s) {
+                 float* x_pred, float* partial, float* loss, int batch, int tokens, long f, bool vspace, hipStream_t s) {
+  DFOT_REQUIRE(batch > 0 && tokens > 0 && f > 0, DFOT_ERR_SHAPE, "vloss: batch %d, tokens %d, frame elements %ld must be positive", batch, tokens, f);
   DFOT_REQUIRE(f % 4 == 0, DFOT_ERR_SHAPE, "vloss: frame elements %ld must be a multiple of 4", f);
+  // one workgroup row per (video, token): gridDim.y holds at most 65535
+  DFOT_REQUIRE((long)batch * tokens <= 65535, DFOT_ERR_SHAPE, "vloss: %ld (video, token) rows exceed the 65535 the launch grid holds", (long)batch * tokens);
+  const int bt = batch * tokens;
   const int chunks = vloss_chunks(f);
   if (vspace)
     hipLaunchKernelGGL(vloss_partial_kernel<true>, dim3(chunks, bt), dim3(256), 0, s, x, noise, v, a, sg, w, x_pred, partial, f);
@@ -1449,9 +1459,10 @@ __global__ void vloss_grad_kernel(const float* __restrict__ x, const float* __re
   *reinterpret_cast<float4v*>(dv + i * 4) = d;
 }
 int launch_vloss_grad(const float* x, const float* noise, const float* v, const float* a, const float* sg, const float* coef, float* dv,
-                      int bt, long f, bool vspace, hipStream_t s) {
+                      int batch, int tokens, long f, bool vspace, hipStream_t s) {
+  DFOT_REQUIRE(batch > 0 && tokens > 0 && f > 0, DFOT_ERR_SHAPE, "vloss_grad: batch %d, tokens %d, frame elements %ld must be positive", batch, tokens, f);
   DFOT_REQUIRE(f % 4 == 0, DFOT_ERR_SHAPE, "vloss_grad: frame elements %ld must be a multiple of 4", f);
-  const long total4 = (long)bt * (f / 4);
+  const long total4 = (long)batch * tokens * (f / 4);
   if (vspace) hipLaunchKernelGGL(vloss_grad_kernel<true>, dim3(cdiv(total4, 256)), dim3(256), 0, s, x, noise, v, a, sg, coef, dv, f / 4, total4);
   else hipLaunchKernelGGL(vloss_grad_kernel<false>, dim3(cdiv(total4, 256)), dim3(256), 0, s, x, noise, v, a, sg, coef, dv, f / 4, total4);
   DFOT_CHECK_HIP(hipGetLastError());
@@ -1520,7 +1531,9 @@ __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
 int launch_adamw(float* p, const float* g, float* m, float* v, long n, float lr, float b1, float b2, float eps, float wd, int step,
                  const float* sumsq, float max_norm, float* ema, float ema_decay, hipStream_t s) {
   DFOT_REQUIRE(step >= 1, DFOT_ERR_ARG, "adamw: step counts from 1");
-  const float c1 = 1.f - powf(b1, (float)step), c2 = 1.f - powf(b2, (float)step);
+  // bias corrections in double, as torch.optim.AdamW computes them on the host: 1 - powf(b2, step) in fp32 loses the low bits of a
+  // difference of order 1e-3 (b2 = 0.999, steps 2 and 3: of order 1e-5 relative in c2, a few 1e-6 in every update)
+  const float c1 = (float)(1.0 - pow((double)b1, (double)step)), c2 = (float)(1.0 - pow((double)b2, (double)step));
   hipLaunchKernelGGL(adamw_kernel, dim3(cdiv(n, 256)), dim3(256), 0, s, p, g, m, v, n, lr, b1, b2, eps, wd, c1, c2, sumsq, max_norm, ema, ema_decay);
   DFOT_CHECK_HIP(hipGetLastError());
   return DFOT_OK;
