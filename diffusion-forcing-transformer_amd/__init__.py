@@ -5,6 +5,7 @@ there is no CPU fallback."""
 from . import capi  # noqa: F401  (raises ImportError when libdfot_hip.so is missing)
 from . import ops  # noqa: F401  (registers the torch.library operators dfot::*)
 from .backbone import UViT3DPose  # noqa: F401
+from .uvit3d_backbone import UViT3D  # noqa: F401
 from .dit_backbone import DiT3D, DifferenceDiT3D  # noqa: F401
 from .diffusion import DiffusionConfig, Schedule  # noqa: F401
 from .guidance import HistoryGuidance  # noqa: F401

@@ -30,6 +30,11 @@ class UViTConfig(C.Structure):
     ]
 
 
+class UViT3DConfig(C.Structure):
+    """dfot_uvit3d_config: the geometry fields of dfot_uvit_config (cond_dim = the action dimension, 0 = none) + cond_dropout"""
+    _fields_ = UViTConfig._fields_ + [("cond_dropout", C.c_int32)]
+
+
 class DiTConfig(C.Structure):
     _fields_ = [
         ("hidden_size", C.c_int32), ("depth", C.c_int32), ("num_heads", C.c_int32), ("patch_size", C.c_int32),
@@ -98,6 +103,12 @@ SIGNATURES = {
     "dfot_uvit_forward_cached_live": (_I, [_P, _P, _P, _P, _I, _P, _P]),
     "dfot_uvit_forward_cached_masks": (_I, [_P, _P, _P, _P, _I, _P, _P, _P]),
     "dfot_uvit_read_tap": (_I, [_P, C.c_char_p, _P, C.c_size_t, _P]),
+    "dfot_uvit3d_create": (_I, [C.POINTER(UViT3DConfig), C.POINTER(_P)]),
+    "dfot_uvit3d_config_bytes": (_L, []),
+    "dfot_uvit3d_forward": (_I, [_P, _P, _P, _P, _P, _P, _I, _P]),
+    "dfot_uvit3d_forward_live": (_I, [_P, _P, _P, _P, _P, _P, _I, _P, _P]),
+    "dfot_op_gn_film_silu": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "dfot_op_rms_film": (_I, [_P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _F, _P]),
     "dfot_dit_create": (_I, [C.POINTER(DiTConfig), C.POINTER(_P)]),
     "dfot_dit_create_f": (_I, [C.POINTER(DiTConfigF), C.POINTER(_P)]),
     "dfot_dit_destroy": (_I, [_P]),

@@ -1,6 +1,6 @@
 """Checkpoint ingestion for the HIP backbone.
 
-Reads what the reference writes and maps it onto ``UViT3DPose.load_state_dict``:
+Reads what the reference writes and maps it onto ``load_state_dict`` of the U-ViT mirrors (``UViT3DPose``, ``UViT3D``):
   * Lightning ``.ckpt`` files: ``checkpoint["state_dict"]`` with keys ``diffusion_model.model.*`` (only those are
     kept, algorithms/common/base_pytorch_video_algo.py:1112-1125), optionally with the ``torch.compile`` prefix
     ``diffusion_model._orig_mod.model.*`` (:1096-1110);
@@ -23,7 +23,8 @@ PREFIXES = ("diffusion_model._orig_mod.model.", "diffusion_model.model.")
 
 def reference_parameter_order(model) -> List[str]:
     """Names in the order of the reference's ``named_parameters()``: UViT3D creates down_blocks and up_blocks before
-    mid_blocks (u_vit3d.py:113-185), so up_blocks.* precede mid_blocks.*"""
+    mid_blocks (u_vit3d.py:113-185), so up_blocks.* precede mid_blocks.*  (UViT3DPose registers mid_blocks first and is reordered here;
+    UViT3D already lists its parameters in the reference's order, which this stable partition keeps)"""
     names = [k for k, _ in model.named_parameters()]
     head = [k for k in names if not k.startswith(("mid_blocks", "up_blocks"))]
     return head + [k for k in names if k.startswith("up_blocks")] + [k for k in names if k.startswith("mid_blocks")]

@@ -7,6 +7,10 @@ namespace dfot {
 // ---- embeddings ----
 int launch_noise_emb(const float* k, const float* freqs, const float* phases, const float* w1, const float* b1,
                      const float* w2, const float* b2, float* hidden, float* out, int bt, int ndim, int e, hipStream_t s);
+// the pose-free UViT3D's per-frame embedding in one launch: Fourier noise-level MLP + (cond != nullptr, video not masked) action MLP
+int launch_uvit3d_emb(const float* k, const float* freqs, const float* phases, const float* w1, const float* b1, const float* w2,
+                      const float* b2, const float* cond, const uint8_t* cond_mask, const float* a_w1, const float* a_b1,
+                      const float* a_w2, const float* a_b2, float* out, int bt, int ndim, int cdim, int e, int tokens, hipStream_t s);
 int launch_embed_input(const float* x, const float* w, const float* b, float* out, int bt, int res, int cin, int c0,
                        hipStream_t s);
 int launch_cond_repack(const float* cond, bf16* a, int bt, int res, int cdim, int kpad, hipStream_t s);
@@ -32,6 +36,7 @@ struct FilmChunk {
   int rows;        // 2C of the owning block
 };
 int launch_film_vec(const FilmChunk* table, int chunks, const float* nemb, float* sv, int bt, int e, hipStream_t s);
+// fcache == nullptr (here and in launch_rms_film*): the pose-free instantiation -- FiLM from sv alone, no fcache / cond_mask loads
 int launch_gn_film_silu(const bf16* h, const float* stats, const float* gamma, const float* beta, const bf16* fcache,
                         const float* sv, const uint8_t* cond_mask, bf16* out, int bt, int pixels, int c, int tokens,
                         hipStream_t s, const uint8_t* live = nullptr);

@@ -52,6 +52,78 @@ int launch_noise_emb(const float* k, const float* freqs, const float* phases, co
   return DFOT_OK;
 }
 
+// --------------------------------------------------------------------------------------------
+// per-frame embedding of the pose-free UViT3D in ONE launch (u_vit3d.py:306-310):
+//   emb[bt] = Linear(SiLU(Linear(fourier(k[bt]))))  +  [video not masked] Linear(SiLU(Linear(cond[bt])))
+// One workgroup per frame; the layer inputs live in LDS, one wave per output row with the summation order of noise_mlp_kernel
+// (lane-strided products, then the wave reduction), so the noise term has the bits of launch_noise_emb.  The action term of a
+// masked video (RandomEmbeddingDropout, embeddings.py:345-361) is not computed: emb is the noise term alone, as torch.where(mask, 0, e)
+// gives.  a_w1 == nullptr: a model without external_cond_embedding.  ndim, cdim, e <= EMB_MAX (checked by the launcher).
+// --------------------------------------------------------------------------------------------
+constexpr int EMB_MAX = 1024;
+constexpr int EMB_THREADS = 512;
+__device__ __forceinline__ float emb_row_dot(const float* __restrict__ wrow, const float* in, int kdim, int lane) {
+  float acc = 0.f;
+  for (int i = lane; i < kdim; i += 64) acc += wrow[i] * in[i];
+  return wave_sum(acc);
+}
+__global__ __launch_bounds__(EMB_THREADS) void uvit3d_emb_kernel(const float* __restrict__ k, const float* __restrict__ freqs,
+                                                                 const float* __restrict__ phases, const float* __restrict__ w1,
+                                                                 const float* __restrict__ b1, const float* __restrict__ w2,
+                                                                 const float* __restrict__ b2, const float* __restrict__ cond,
+                                                                 const uint8_t* __restrict__ cond_mask, const float* __restrict__ a_w1,
+                                                                 const float* __restrict__ a_b1, const float* __restrict__ a_w2,
+                                                                 const float* __restrict__ a_b2, float* __restrict__ out, int ndim,
+                                                                 int cdim, int e, int tokens) {
+  __shared__ float s_in[EMB_MAX], s_hid[EMB_MAX], s_out[EMB_MAX];
+  constexpr int WAVES = EMB_THREADS / 64;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int bt = blockIdx.x;
+  const float level = k[bt];
+  for (int i = threadIdx.x; i < ndim; i += EMB_THREADS)
+    s_in[i] = cosf(__fadd_rn(__fmul_rn(level, freqs[i]), phases[i])) * 1.41421356237309515f;
+  __syncthreads();
+  for (int row = wave; row < e; row += WAVES) {
+    const float acc = emb_row_dot(w1 + (long)row * ndim, s_in, ndim, lane);
+    if (lane == 0) s_hid[row] = silu_f(acc + b1[row]);
+  }
+  __syncthreads();
+  // the noise term waits in LDS; a row is written, updated and stored by lane 0 of the one wave that owns it (program order, no barrier)
+  for (int row = wave; row < e; row += WAVES) {
+    const float acc = emb_row_dot(w2 + (long)row * e, s_hid, e, lane);
+    if (lane == 0) s_out[row] = acc + b2[row];
+  }
+  const bool action = cond && !(cond_mask && cond_mask[(unsigned)bt / (unsigned)tokens]);  // workgroup-uniform
+  if (action) {
+    __syncthreads();
+    for (int i = threadIdx.x; i < cdim; i += EMB_THREADS) s_in[i] = cond[(long)bt * cdim + i];
+    __syncthreads();
+    for (int row = wave; row < e; row += WAVES) {
+      const float acc = emb_row_dot(a_w1 + (long)row * cdim, s_in, cdim, lane);
+      if (lane == 0) s_hid[row] = silu_f(acc + a_b1[row]);
+    }
+    __syncthreads();
+    for (int row = wave; row < e; row += WAVES) {
+      const float acc = emb_row_dot(a_w2 + (long)row * e, s_hid, e, lane);
+      if (lane == 0) s_out[row] += acc + a_b2[row];
+    }
+  }
+  for (int row = wave; row < e; row += WAVES)
+    if (lane == 0) out[(long)bt * e + row] = s_out[row];
+}
+
+int launch_uvit3d_emb(const float* k, const float* freqs, const float* phases, const float* w1, const float* b1, const float* w2,
+                      const float* b2, const float* cond, const uint8_t* cond_mask, const float* a_w1, const float* a_b1,
+                      const float* a_w2, const float* a_b2, float* out, int bt, int ndim, int cdim, int e, int tokens, hipStream_t s) {
+  DFOT_REQUIRE(ndim > 0 && ndim <= EMB_MAX && e > 0 && e <= EMB_MAX && cdim >= 0 && cdim <= EMB_MAX, DFOT_ERR_SHAPE,
+               "uvit3d embedding: noise_dim %d, cond_dim %d and emb_channels %d must be <= %d", ndim, cdim, e, EMB_MAX);
+  DFOT_REQUIRE(!cond || (a_w1 && a_b1 && a_w2 && a_b2 && cdim > 0), DFOT_ERR_ARG, "uvit3d embedding: a condition needs the action MLP");
+  hipLaunchKernelGGL(uvit3d_emb_kernel, dim3(bt), dim3(EMB_THREADS), 0, s, k, freqs, phases, w1, b1, w2, b2, cond, cond_mask, a_w1, a_b1,
+                     a_w2, a_b2, out, ndim, cdim, e, tokens);
+  DFOT_CHECK_HIP(hipGetLastError());
+  return DFOT_OK;
+}
+
 // The residual stream of the ResBlock levels is fp32 (training ops, tests of single ops) or bf16 (the inference engine: what
 // torch.autocast(bf16) keeps there in the reference): stream accessors for either element type
 template <typename T>
@@ -754,6 +826,9 @@ int launch_film_vec(const FilmChunk* table, int chunks, const float* nemb, float
 }
 
 // ResBlock: out = SiLU( GroupNorm(h) * (1 + scale) + shift ), bf16 in/out; thread = 8 channels of one pixel
+// POSE = false (every norm kernel below has the flag): the pose-free UViT3D, whose FiLM input is the per-frame vector alone -- the kernel
+// takes no fcache / cond_mask, forms none of their addresses and issues no load for them; the arithmetic is that of a masked video
+template <bool POSE>
 __global__ void gn_film_silu_kernel(const bf16* __restrict__ h, const float* __restrict__ stats,
                                     const float* __restrict__ gamma, const float* __restrict__ beta,
                                     const bf16* __restrict__ fcache, const float* __restrict__ sv,
@@ -777,14 +852,16 @@ __global__ void gn_film_silu_kernel(const bf16* __restrict__ h, const float* __r
     sc[j] = svp[j];
     sh[j] = svp[32 + j];
   }
-  const bool use_pose = !(cond_mask && cond_mask[(unsigned)bt / (unsigned)tokens]);
-  if (use_pose) {
-    const bf16x8 fs = *reinterpret_cast<const bf16x8*>(fcache + pix * 2 * c + col);
-    const bf16x8 fh = *reinterpret_cast<const bf16x8*>(fcache + pix * 2 * c + col + 32);
+  if constexpr (POSE) {
+    const bool use_pose = !(cond_mask && cond_mask[(unsigned)bt / (unsigned)tokens]);
+    if (use_pose) {
+      const bf16x8 fs = *reinterpret_cast<const bf16x8*>(fcache + pix * 2 * c + col);
+      const bf16x8 fh = *reinterpret_cast<const bf16x8*>(fcache + pix * 2 * c + col + 32);
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      sc[j] += bf2f(fs[j]);
-      sh[j] += bf2f(fh[j]);
+      for (int j = 0; j < 8; ++j) {
+        sc[j] += bf2f(fs[j]);
+        sh[j] += bf2f(fh[j]);
+      }
     }
   }
   bf16x8 o;
@@ -799,7 +876,7 @@ __global__ void gn_film_silu_kernel(const bf16* __restrict__ h, const float* __r
   *reinterpret_cast<bf16x8*>(out + pix * c + c0) = o;
 }
 // streaming form (see gn_apply_silu_rows_kernel): constants of the thread's 8 channels in registers, GN_ROWS_IT pixels per thread
-template <int C>
+template <int C, bool POSE>
 __global__ __launch_bounds__(256) void gn_film_silu_rows_kernel(const bf16* __restrict__ h, const float* __restrict__ stats,
                                                                 const float* __restrict__ gamma, const float* __restrict__ beta,
                                                                 const bf16* __restrict__ fcache, const float* __restrict__ sv,
@@ -824,9 +901,10 @@ __global__ __launch_bounds__(256) void gn_film_silu_rows_kernel(const bf16* __re
       svh[j] = j < 4 ? h0[j] : h1[j - 4];
     }
   }
-  const bool use_pose = !(cond_mask && cond_mask[(unsigned)bt / (unsigned)tokens]);  // workgroup-uniform
+  bool use_pose = false;
+  if constexpr (POSE) use_pose = !(cond_mask && cond_mask[(unsigned)bt / (unsigned)tokens]);  // workgroup-uniform
   long pix = (long)bt * pixels + (long)(blockIdx.x % wg_per_bt) * (PPI * GN_ROWS_IT) + threadIdx.x / TPP;
-  if (use_pose) {
+  if (POSE && use_pose) {
 #pragma unroll 4
     for (int it = 0; it < GN_ROWS_IT; ++it, pix += PPI) {
       const bf16x8 hv = *reinterpret_cast<const bf16x8*>(h + pix * C + c0);
@@ -852,24 +930,32 @@ __global__ __launch_bounds__(256) void gn_film_silu_rows_kernel(const bf16* __re
   }
 }
 
-int launch_gn_film_silu(const bf16* h, const float* stats, const float* gamma, const float* beta, const bf16* fcache,
-                        const float* sv, const uint8_t* cond_mask, bf16* out, int bt, int pixels, int c, int tokens,
-                        hipStream_t s, const uint8_t* live) {
+template <bool POSE>
+static int launch_gn_film_silu_t(const bf16* h, const float* stats, const float* gamma, const float* beta, const bf16* fcache,
+                                 const float* sv, const uint8_t* cond_mask, bf16* out, int bt, int pixels, int c, int tokens,
+                                 hipStream_t s, const uint8_t* live) {
   if ((c == 128 || c == 256) && pixels % ((256 / (c / 8)) * GN_ROWS_IT) == 0) {
     const int grid = bt * (pixels / ((256 / (c / 8)) * GN_ROWS_IT));
     if (c == 128)
-      hipLaunchKernelGGL(gn_film_silu_rows_kernel<128>, dim3(grid), dim3(256), 0, s, h, stats, gamma, beta, fcache, sv, cond_mask, out, pixels, tokens, live);
+      hipLaunchKernelGGL((gn_film_silu_rows_kernel<128, POSE>), dim3(grid), dim3(256), 0, s, h, stats, gamma, beta, fcache, sv, cond_mask, out, pixels, tokens, live);
     else
-      hipLaunchKernelGGL(gn_film_silu_rows_kernel<256>, dim3(grid), dim3(256), 0, s, h, stats, gamma, beta, fcache, sv, cond_mask, out, pixels, tokens, live);
+      hipLaunchKernelGGL((gn_film_silu_rows_kernel<256, POSE>), dim3(grid), dim3(256), 0, s, h, stats, gamma, beta, fcache, sv, cond_mask, out, pixels, tokens, live);
     DFOT_CHECK_HIP(hipGetLastError());
     return DFOT_OK;
   }
   const long total8 = (long)bt * pixels * (c / 8);
   DFOT_REQUIRE(total8 < (1L << 31), DFOT_ERR_SHAPE, "groupnorm apply: %ld work items exceed the 32-bit index range", total8);
-  hipLaunchKernelGGL(gn_film_silu_kernel, dim3(cdiv(total8, 256)), dim3(256), 0, s, h, stats, gamma, beta, fcache, sv,
+  hipLaunchKernelGGL(gn_film_silu_kernel<POSE>, dim3(cdiv(total8, 256)), dim3(256), 0, s, h, stats, gamma, beta, fcache, sv,
                      cond_mask, out, total8, pixels, c, tokens, live);
   DFOT_CHECK_HIP(hipGetLastError());
   return DFOT_OK;
+}
+// fcache == nullptr selects the pose-free instantiations (cond_mask is then not read either)
+int launch_gn_film_silu(const bf16* h, const float* stats, const float* gamma, const float* beta, const bf16* fcache,
+                        const float* sv, const uint8_t* cond_mask, bf16* out, int bt, int pixels, int c, int tokens,
+                        hipStream_t s, const uint8_t* live) {
+  return fcache ? launch_gn_film_silu_t<true>(h, stats, gamma, beta, fcache, sv, cond_mask, out, bt, pixels, c, tokens, s, live)
+                : launch_gn_film_silu_t<false>(h, stats, gamma, beta, nullptr, sv, nullptr, out, bt, pixels, c, tokens, s, live);
 }
 
 // TransformerBlock: xn = RMSNorm(x) * w * (1 + scale) + shift, fp32 stream in -> bf16 out; one wave per token
@@ -877,7 +963,7 @@ int launch_gn_film_silu(const bf16* h, const float* stats, const float* gamma, c
 // applied here (and written back) instead of in a pass of its own
 // TS: element type of the residual stream (fp32, or bf16: the value written back by PEND is then the bf16 rounding of the sum, and the
 // norm is taken of that rounded value -- what the next reader of the stream sees)
-template <int MAXCH, bool PEND, typename TS>
+template <int MAXCH, bool PEND, typename TS, bool POSE>
 __global__ __launch_bounds__(256) void rms_film_kernel(const TS* x, const float* __restrict__ w,
                                                        const bf16* __restrict__ fcache, const float* __restrict__ sv,
                                                        const uint8_t* __restrict__ cond_mask, bf16* __restrict__ out,
@@ -919,7 +1005,8 @@ __global__ __launch_bounds__(256) void rms_film_kernel(const TS* x, const float*
   ss = wave_sum(ss);
   const float rs = rsqrtf(ss / (float)c + eps);
   const int bt = (int)(row / rows_per_bt);
-  const bool use_pose = !(cond_mask && cond_mask[(unsigned)bt / (unsigned)tokens]);
+  bool use_pose = false;
+  if constexpr (POSE) use_pose = !(cond_mask && cond_mask[(unsigned)bt / (unsigned)tokens]);
 #pragma unroll
   for (int k = 0; k < MAXCH; ++k) {
     const int ch = lane + 64 * k;
@@ -933,7 +1020,7 @@ __global__ __launch_bounds__(256) void rms_film_kernel(const TS* x, const float*
         sc[j] = svp[j];
         sh[j] = svp[32 + j];
       }
-      if (use_pose) {
+      if (POSE && use_pose) {
         const bf16x8 fs = *reinterpret_cast<const bf16x8*>(fcache + row * 2 * c + col);
         const bf16x8 fh = *reinterpret_cast<const bf16x8*>(fcache + row * 2 * c + col + 32);
 #pragma unroll
@@ -949,12 +1036,12 @@ __global__ __launch_bounds__(256) void rms_film_kernel(const TS* x, const float*
     }
   }
 }
-template <typename TS>
-static int launch_rms_film_t(const TS* x, const float* w, const bf16* fcache, const float* sv, const uint8_t* cond_mask, bf16* out,
+template <typename TS, bool POSE>
+static int launch_rms_film_p(const TS* x, const float* w, const bf16* fcache, const float* sv, const uint8_t* cond_mask, bf16* out,
                              long m, int c, int rows_per_bt, int tokens, float eps, hipStream_t s, const RmsPending* pend) {
   DFOT_REQUIRE(c % 8 == 0 && c <= 8 * 64 * 3, DFOT_ERR_SHAPE, "rms_film: channels %d unsupported", c);
 #define RMS_CALL(MC, P)                                                                                                             \
-  hipLaunchKernelGGL((rms_film_kernel<MC, P, TS>), dim3(cdiv(m, 4)), dim3(256), 0, s, x, w, fcache, sv, cond_mask, out, m, c, rows_per_bt, \
+  hipLaunchKernelGGL((rms_film_kernel<MC, P, TS, POSE>), dim3(cdiv(m, 4)), dim3(256), 0, s, x, w, fcache, sv, cond_mask, out, m, c, rows_per_bt, \
                      tokens, eps, P ? (TS*)pend->x : nullptr, P ? pend->bias : nullptr, P ? pend->s0 : nullptr, P ? pend->s1 : nullptr, P ? pend->s2 : nullptr)
   if (pend) {
     // x is read, x + bias + slices is normalised AND written to pend->x (the same buffer, or X[l] when the stream still sits in the skip tensor)
@@ -966,6 +1053,13 @@ static int launch_rms_film_t(const TS* x, const float* w, const bf16* fcache, co
 #undef RMS_CALL
   DFOT_CHECK_HIP(hipGetLastError());
   return DFOT_OK;
+}
+// fcache == nullptr selects the pose-free instantiations (cond_mask is then not read either)
+template <typename TS>
+static int launch_rms_film_t(const TS* x, const float* w, const bf16* fcache, const float* sv, const uint8_t* cond_mask, bf16* out,
+                             long m, int c, int rows_per_bt, int tokens, float eps, hipStream_t s, const RmsPending* pend) {
+  return fcache ? launch_rms_film_p<TS, true>(x, w, fcache, sv, cond_mask, out, m, c, rows_per_bt, tokens, eps, s, pend)
+                : launch_rms_film_p<TS, false>(x, w, nullptr, sv, nullptr, out, m, c, rows_per_bt, tokens, eps, s, pend);
 }
 int launch_rms_film(const float* x, const float* w, const bf16* fcache, const float* sv, const uint8_t* cond_mask, bf16* out,
                     long m, int c, int rows_per_bt, int tokens, float eps, hipStream_t s, const RmsPending* pend) {

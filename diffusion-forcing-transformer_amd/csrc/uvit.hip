@@ -78,6 +78,12 @@ struct dfot_uvit_s {
   dfot_uvit_config cfg{};
   int T = 0, E = 0, heads = 0, r[4] = {0, 0, 0, 0}, ch[4] = {0, 0, 0, 0};
   int kpose = 0;  // padded K of the pose patch-embed GEMM
+  // pose-free form (dfot_uvit3d_create: the reference's UViT3D): no pose patch embedding, no per-window FiLM caches (every fcache stays
+  // nullptr, which selects the pose-free norm kernels); the per-frame embedding may carry an action MLP instead
+  bool posefree = false;
+  int act_dim = 0;          // external_cond_dim of the action MLP, 0 = the model has no external_cond_embedding
+  bool act_dropout = false; // external_cond_dropout > 0: the keys sit under ".embedding." and the per-video mask is honoured
+  float *ac_w1 = nullptr, *ac_b1 = nullptr, *ac_w2 = nullptr, *ac_b2 = nullptr;
   std::vector<Param> params;
   std::map<std::string, int> index;
   std::vector<void*> owned;  // every hipMalloc'ed block
@@ -292,14 +298,22 @@ static int build(dfot_uvit_s* h) {
   if ((rc = add_f32(h, ne + "embedding.linear_1.bias", {e}, &h->ne_b1))) return rc;
   if ((rc = add_f32(h, ne + "embedding.linear_2.weight", {e, e}, &h->ne_w2))) return rc;
   if ((rc = add_f32(h, ne + "embedding.linear_2.bias", {e}, &h->ne_b2))) return rc;
-  if ((rc = dev_alloc(h, &h->pose_w, (size_t)e * h->kpose))) return rc;
-  {
+  if (h->posefree) {
+    if (h->act_dim > 0) {  // RandomDropoutCondEmbedding: a TimestepEmbedding itself (dropout 0) or one under .embedding (embeddings.py:364-387)
+      const std::string ce = h->act_dropout ? "external_cond_embedding.embedding." : "external_cond_embedding.";
+      if ((rc = add_f32(h, ce + "linear_1.weight", {e, h->act_dim}, &h->ac_w1))) return rc;
+      if ((rc = add_f32(h, ce + "linear_1.bias", {e}, &h->ac_b1))) return rc;
+      if ((rc = add_f32(h, ce + "linear_2.weight", {e, e}, &h->ac_w2))) return rc;
+      if ((rc = add_f32(h, ce + "linear_2.bias", {e}, &h->ac_b2))) return rc;
+    }
+  } else {
+    if ((rc = dev_alloc(h, &h->pose_w, (size_t)e * h->kpose))) return rc;
     bf16* pw = h->pose_w;
     const int k = c.cond_dim * 4, kp = h->kpose;
     add_param(h, "external_cond_embedding.patch_embedder.proj.weight", {e, c.cond_dim, 2, 2},
               [=](const float* src, hipStream_t s) { return launch_pack_rows(src, pw, nullptr, e, k, kp, kp, 0, s); });
+    if ((rc = add_f32(h, "external_cond_embedding.patch_embedder.proj.bias", {e}, &h->pose_b))) return rc;
   }
-  if ((rc = add_f32(h, "external_cond_embedding.patch_embedder.proj.bias", {e}, &h->pose_b))) return rc;
   if ((rc = add_f32(h, "embed_input.proj.weight", {h->ch[0], c.in_channels, 2, 2}, &h->ein_w))) return rc;
   if ((rc = add_f32(h, "embed_input.proj.bias", {h->ch[0]}, &h->ein_b))) return rc;
   if ((rc = add_f32(h, "project_output.proj.weight", {h->ch[0], c.in_channels, 2, 2}, &h->pout_w))) return rc;
@@ -319,9 +333,15 @@ static int build(dfot_uvit_s* h) {
     }
     if ((rc = add_conv(h, pre + std::to_string(n) + ".conv", h->ch[l], h->ch[l + 1], &h->down_conv[l]))) return rc;
   }
-  h->mid_tr.resize(c.num_mid_blocks);
-  for (int i = 0; i < c.num_mid_blocks; ++i)
-    if ((rc = add_tr_block(h, "mid_blocks." + std::to_string(i), 3, &h->mid_tr[i]))) return rc;
+  auto add_mid = [&]() -> int {
+    h->mid_tr.resize(c.num_mid_blocks);
+    for (int i = 0; i < c.num_mid_blocks; ++i)
+      if ((rc = add_tr_block(h, "mid_blocks." + std::to_string(i), 3, &h->mid_tr[i]))) return rc;
+    return DFOT_OK;
+  };
+  // the pose model keeps its historical inventory order (down, mid, up); the pose-free one lists its keys as the reference's
+  // state_dict() does: UViT3D creates up_blocks before mid_blocks (u_vit3d.py:113-185)
+  if (!h->posefree && (rc = add_mid())) return rc;
   for (int j = 0; j < 3; ++j) {
     const int l = 2 - j;
     const int n = c.num_updown_blocks[l];
@@ -337,6 +357,7 @@ static int build(dfot_uvit_s* h) {
         if ((rc = add_tr_block(h, pre + std::to_string(i + 1), l, &h->up_tr[i]))) return rc;
     }
   }
+  if (h->posefree && (rc = add_mid())) return rc;
   return DFOT_OK;
 }
 
@@ -615,6 +636,9 @@ static int run_up(dfot_uvit_s* h, int l, int bt, hipStream_t s, const uint8_t* l
 
 }  // namespace dfot
 
+static int forward_from_emb(dfot_uvit_s* h, const float* x, float* out, int batch, const uint8_t* live_frames, const uint8_t* fresh_frames,
+                            hipStream_t s);
+
 // ------------------------------------------------------------------------------------------
 // C ABI
 // ------------------------------------------------------------------------------------------
@@ -658,6 +682,46 @@ int dfot_uvit_destroy(dfot_uvit_t h) {
   delete h;
   return DFOT_OK;
 }
+
+int dfot_uvit3d_create(const dfot_uvit3d_config* cfg, dfot_uvit_t* out) {
+  DFOT_REQUIRE(cfg && out, DFOT_ERR_ARG, "dfot_uvit3d_create: null argument");
+  DFOT_REQUIRE(cfg->resolution % 16 == 0 && cfg->resolution >= 32, DFOT_ERR_SHAPE, "resolution %d must be a multiple of 16", cfg->resolution);
+  DFOT_REQUIRE(cfg->emb_channels % 64 == 0 && cfg->emb_channels <= 1024, DFOT_ERR_SHAPE,
+               "emb_channels %d must be a multiple of 64 and at most 1024", cfg->emb_channels);
+  DFOT_REQUIRE(cfg->in_channels >= 1 && cfg->in_channels <= 3, DFOT_ERR_SHAPE, "in_channels %d unsupported (1 .. 3)", cfg->in_channels);
+  DFOT_REQUIRE(cfg->cond_dim >= 0 && cfg->cond_dim <= 1024, DFOT_ERR_SHAPE, "cond_dim %d unsupported: the action embedding takes 0 (none) .. 1024 values", cfg->cond_dim);
+  DFOT_REQUIRE(cfg->noise_dim > 0 && cfg->noise_dim <= 1024, DFOT_ERR_SHAPE, "noise_dim %d must be 1 .. 1024", cfg->noise_dim);
+  for (int l = 0; l < 4; ++l)
+    DFOT_REQUIRE(cfg->channels[l] > 0 && cfg->channels[l] % 64 == 0, DFOT_ERR_SHAPE, "channels[%d]=%d must be a multiple of 64", l, cfg->channels[l]);
+  DFOT_REQUIRE(cfg->channels[0] % 128 == 0 && cfg->channels[1] % 128 == 0, DFOT_ERR_SHAPE, "ResBlock channels must be multiples of 128");
+  DFOT_REQUIRE(cfg->num_heads > 0 && cfg->max_tokens > 0 && cfg->num_mid_blocks >= 0, DFOT_ERR_SHAPE, "num_heads / max_tokens must be positive");
+  for (int l = 2; l < 4; ++l) {
+    const int d = cfg->channels[l] / cfg->num_heads;
+    DFOT_REQUIRE(d * cfg->num_heads == cfg->channels[l] && (d == 64 || d == 128), DFOT_ERR_SHAPE,
+                 "level %d head dim %d must be 64 or 128 (channels %d / num_heads %d)", l, d, cfg->channels[l], cfg->num_heads);
+  }
+  const int r3 = cfg->resolution / 16;
+  DFOT_REQUIRE((cfg->max_tokens * r3 * r3) % 128 == 0, DFOT_ERR_SHAPE, "tokens at the coarsest level (%d) must be a multiple of 128", cfg->max_tokens * r3 * r3);
+  auto* h = new dfot_uvit_s();
+  dfot_uvit_config& c = h->cfg;
+  for (int l = 0; l < 4; ++l) c.channels[l] = cfg->channels[l];
+  for (int l = 0; l < 3; ++l) c.num_updown_blocks[l] = cfg->num_updown_blocks[l];
+  c.emb_channels = cfg->emb_channels; c.num_mid_blocks = cfg->num_mid_blocks; c.num_heads = cfg->num_heads;
+  c.in_channels = cfg->in_channels; c.resolution = cfg->resolution; c.max_tokens = cfg->max_tokens;
+  c.cond_dim = 0;  // the pose model's field: no pose patch embedding here
+  c.noise_dim = cfg->noise_dim; c.rope_theta = cfg->rope_theta; c.eps = cfg->eps;
+  h->posefree = true;
+  h->act_dim = cfg->cond_dim;
+  h->act_dropout = cfg->cond_dim > 0 && cfg->cond_dropout != 0;
+  int rc = build(h);
+  if (rc) {
+    dfot_uvit_destroy(h);
+    return rc;
+  }
+  *out = h;
+  return DFOT_OK;
+}
+int64_t dfot_uvit3d_config_bytes(void) { return (int64_t)sizeof(dfot_uvit3d_config); }
 
 int dfot_uvit_num_params(dfot_uvit_t h) { return h ? (int)h->params.size() : 0; }
 const char* dfot_uvit_param_name(dfot_uvit_t h, int i) {
@@ -745,12 +809,14 @@ int dfot_uvit_reserve(dfot_uvit_t h, int max_batch) {
     if ((rc = dev_alloc(h, &h->XB[l], bt * pix[l] * h->ch[l], true))) return rc;
     // fp32 scratch of a transformer level (the out-projection's fallback path, run_tr_block)
     if (l >= 2 && (rc = dev_alloc(h, &h->X[l], bt * pix[l] * h->ch[l], true))) return rc;
-    if ((rc = dev_alloc(h, &h->emb[l], bt * pix[l] * h->E, true))) return rc;
+    if (!h->posefree && (rc = dev_alloc(h, &h->emb[l], bt * pix[l] * h->E, true))) return rc;
   }
   for (int l = 0; l < 3; ++l)
     if ((rc = dev_alloc(h, &h->HSA[l], bt * pix[l + 1] * h->ch[l + 1], true))) return rc;
-  if ((rc = dev_alloc(h, &h->acond, bt * pix[0] * h->kpose, true))) return rc;
-  DFOT_CHECK_HIP(hipMemset(h->acond, 0, bt * pix[0] * h->kpose * sizeof(bf16)));
+  if (!h->posefree) {
+    if ((rc = dev_alloc(h, &h->acond, bt * pix[0] * h->kpose, true))) return rc;
+    DFOT_CHECK_HIP(hipMemset(h->acond, 0, bt * pix[0] * h->kpose * sizeof(bf16)));
+  }
   size_t act = 0, tmpn = 0;
   for (int l = 0; l < 4; ++l) act = std::max(act, bt * pix[l] * h->ch[l]);
   for (int l = 0; l < 3; ++l) tmpn = std::max(tmpn, bt * pix[l + 1] * h->ch[l]);
@@ -771,7 +837,7 @@ int dfot_uvit_reserve(dfot_uvit_t h, int max_batch) {
     std::vector<FilmChunk> table;
     long sv_off = 0;
     auto add = [&](bf16** fc, long* off, const bf16* wf, const float* bf_, int c, int lvl) -> int {
-      int r2 = dev_alloc(h, fc, bt * pix[lvl] * 2 * c, true);
+      int r2 = h->posefree ? DFOT_OK : dev_alloc(h, fc, bt * pix[lvl] * 2 * c, true);  // pose-free: no cache, fcache stays nullptr
       if (r2) return r2;
       *off = sv_off;
       for (int r0 = 0; r0 < 2 * c; r0 += 64) table.push_back(FilmChunk{wf + (long)r0 * h->E, bf_ + r0, sv_off + r0, 2 * c});
@@ -874,6 +940,7 @@ int dfot_uvit_query(dfot_uvit_t h, const char* key, double* value) {
 int dfot_uvit_set_conditions(dfot_uvit_t h, const float* external_cond, const uint8_t* external_cond_mask, int batch,
                              void* stream) {
   DFOT_REQUIRE(h, DFOT_ERR_ARG, "set_conditions: null handle");
+  DFOT_REQUIRE(!h->posefree, DFOT_ERR_STATE, "set_conditions: a pose-free handle (dfot_uvit3d_create) has no pose caches; call dfot_uvit3d_forward");
   DFOT_REQUIRE(external_cond != nullptr, DFOT_ERR_ARG, "External condition (camera pose) is required for U-ViT3DPose model.");
   DFOT_REQUIRE(h->finalized, DFOT_ERR_STATE, "set_conditions: weights not finalized");
   DFOT_REQUIRE(batch > 0 && batch <= h->max_batch, DFOT_ERR_STATE, "set_conditions: batch %d exceeds reserved %d", batch, h->max_batch);
@@ -927,6 +994,7 @@ int dfot_uvit_forward_cached_masks(dfot_uvit_t h, const float* x, const float* n
   DFOT_REQUIRE(!fresh_frames || h->last_batch == batch, DFOT_ERR_STATE,
                "forward: frozen frames need the previous forward of this handle to have run the same batch (%d, now %d)", h->last_batch, batch);
   DFOT_REQUIRE(!fresh_frames || live_frames, DFOT_ERR_ARG, "forward: frozen frames must also be dead frames (live_frames is null)");
+  DFOT_REQUIRE(!h->posefree, DFOT_ERR_STATE, "forward_cached: a pose-free handle (dfot_uvit3d_create) runs through dfot_uvit3d_forward");
   DFOT_REQUIRE(h->finalized, DFOT_ERR_STATE, "forward: weights not finalized");
   DFOT_REQUIRE(batch > 0 && batch == h->cond_batch, DFOT_ERR_STATE,
                "forward_cached: batch %d does not match the cached conditions (%d)", batch, h->cond_batch);
@@ -937,6 +1005,17 @@ int dfot_uvit_forward_cached_masks(dfot_uvit_t h, const float* x, const float* n
   if ((rc = launch_noise_emb(noise_levels, h->ne_freqs, h->ne_phases, h->ne_w1, h->ne_b1, h->ne_w2, h->ne_b2, h->nhid,
                              h->nemb, bt, c.noise_dim, e, s)))
     return rc;
+  return forward_from_emb(h, x, out, batch, live_frames, fresh_frames, s);
+}
+
+}  // extern "C"
+
+// everything after the per-frame embedding h->nemb: shared by the pose model (per-window caches) and the pose-free one (none)
+static int forward_from_emb(dfot_uvit_s* h, const float* x, float* out, int batch, const uint8_t* live_frames, const uint8_t* fresh_frames,
+                            hipStream_t s) {
+  const dfot_uvit_config& c = h->cfg;
+  const int bt = batch * h->T, e = h->E;
+  int rc = 0;
   if ((rc = launch_film_vec(h->film_table, h->film_chunks, h->nemb, h->sv, bt, e, s))) return rc;
   if ((rc = launch_embed_input_bf16(x, h->ein_w, h->ein_b, h->XB[0], bt, c.resolution, c.in_channels, h->ch[0], s))) return rc;
   h->gn1_nblk = 0;
@@ -980,6 +1059,8 @@ int dfot_uvit_forward_cached_masks(dfot_uvit_t h, const float* x, const float* n
   return launch_project_output_bf16(h->XB[0], h->pout_w, h->pout_b, out, bt, c.resolution, h->ch[0], c.in_channels, s, live_frames);
 }
 
+extern "C" {
+
 int dfot_uvit_forward(dfot_uvit_t h, const float* x, const float* noise_levels, const float* external_cond,
                       const uint8_t* external_cond_mask, float* out, int batch, void* stream) {
   DFOT_REQUIRE(h && x && noise_levels && out, DFOT_ERR_ARG, "forward: null argument");
@@ -988,11 +1069,58 @@ int dfot_uvit_forward(dfot_uvit_t h, const float* x, const float* noise_levels, 
   return dfot_uvit_forward_cached(h, x, noise_levels, out, batch, stream);
 }
 
+int dfot_uvit3d_forward_live(dfot_uvit_t h, const float* x, const float* noise_levels, const float* external_cond,
+                             const uint8_t* external_cond_mask, float* out, int batch, const uint8_t* live_frames, void* stream) {
+  DFOT_REQUIRE(h && x && noise_levels && out, DFOT_ERR_ARG, "uvit3d_forward: null argument");
+  DFOT_REQUIRE(h->posefree, DFOT_ERR_STATE, "uvit3d_forward: the handle is a pose model (dfot_uvit_create); call dfot_uvit_forward");
+  DFOT_REQUIRE(h->finalized, DFOT_ERR_STATE, "uvit3d_forward: weights not finalized");
+  DFOT_REQUIRE(batch > 0 && batch <= h->max_batch, DFOT_ERR_STATE, "uvit3d_forward: batch %d exceeds reserved %d", batch, h->max_batch);
+  DFOT_REQUIRE(!external_cond || h->act_dim > 0, DFOT_ERR_ARG,
+               "uvit3d_forward: external_cond given, but the model was built with cond_dim 0 (no external_cond_embedding)");
+  hipStream_t s = (hipStream_t)stream;
+  // a model built with dropout 0 IS a TimestepEmbedding and never sees the mask (embeddings.py:377-378,385-386)
+  const uint8_t* mask = (external_cond && h->act_dropout) ? external_cond_mask : nullptr;
+  int rc = launch_uvit3d_emb(noise_levels, h->ne_freqs, h->ne_phases, h->ne_w1, h->ne_b1, h->ne_w2, h->ne_b2, external_cond, mask, h->ac_w1,
+                             h->ac_b1, h->ac_w2, h->ac_b2, h->nemb, batch * h->T, h->cfg.noise_dim, h->act_dim, h->E, h->T, s);
+  if (rc) return rc;
+  h->have_mask = false;  // the mask acts inside the embedding; the norm kernels run their pose-free form (fcache == nullptr)
+  return forward_from_emb(h, x, out, batch, live_frames, nullptr, s);
+}
+
+int dfot_uvit3d_forward(dfot_uvit_t h, const float* x, const float* noise_levels, const float* external_cond,
+                        const uint8_t* external_cond_mask, float* out, int batch, void* stream) {
+  return dfot_uvit3d_forward_live(h, x, noise_levels, external_cond, external_cond_mask, out, batch, nullptr, stream);
+}
+
+// ---- op-level test entry points of the inference norm kernels (fcache == NULL: the pose-free instantiations) ----
+int dfot_op_gn_film_silu(const void* h, const float* stats, const float* gamma, const float* beta, const void* fcache, const float* sv,
+                         const uint8_t* cond_mask, void* out, int bt, int pixels, int c, int tokens, void* stream) {
+  DFOT_REQUIRE(h && stats && gamma && beta && sv && out, DFOT_ERR_ARG, "op_gn_film_silu: null argument");
+  DFOT_REQUIRE(bt > 0 && pixels > 0 && tokens > 0 && c > 0 && c % 32 == 0, DFOT_ERR_SHAPE,
+               "op_gn_film_silu: bt %d, pixels %d, tokens %d must be positive and channels %d a multiple of 32", bt, pixels, tokens, c);
+  return launch_gn_film_silu((const bf16*)h, stats, gamma, beta, (const bf16*)fcache, sv, cond_mask, (bf16*)out, bt, pixels, c, tokens,
+                             (hipStream_t)stream);
+}
+int dfot_op_rms_film(const void* x, const float* w, const void* fcache, const float* sv, const uint8_t* cond_mask, void* out, int64_t m,
+                     int c, int rows_per_bt, int tokens, float eps, void* stream) {
+  DFOT_REQUIRE(x && w && sv && out, DFOT_ERR_ARG, "op_rms_film: null argument");
+  DFOT_REQUIRE(m > 0 && rows_per_bt > 0 && tokens > 0 && c > 0 && c % 32 == 0 && m % rows_per_bt == 0, DFOT_ERR_SHAPE,
+               "op_rms_film: rows %ld must be a positive multiple of rows_per_bt %d, channels %d a multiple of 32", (long)m, rows_per_bt, c);
+  return launch_rms_film_bf16((const bf16*)x, w, (const bf16*)fcache, sv, cond_mask, (bf16*)out, (long)m, c, rows_per_bt, tokens, eps,
+                              (hipStream_t)stream);
+}
+
 int dfot_uvit_read_tap(dfot_uvit_t h, const char* name, float* out, size_t capacity, void* stream) {
   DFOT_REQUIRE(h && name && out, DFOT_ERR_ARG, "read_tap: null argument");
   DFOT_REQUIRE(h->last_batch > 0, DFOT_ERR_STATE, "read_tap: no forward has run");
   hipStream_t s = (hipStream_t)stream;
   const int bt = h->last_batch * h->T;
+  if (!strcmp(name, "nemb")) {  // the per-frame embedding the FiLM vectors were formed from, [B*T][E]
+    const size_t need = (size_t)bt * h->E;
+    DFOT_REQUIRE(capacity >= need, DFOT_ERR_SHAPE, "read_tap: need %zu floats, got %zu", need, capacity);
+    return copy_f32(out, h->nemb, need, s);
+  }
+  DFOT_REQUIRE(!(h->posefree && !strcmp(name, "pose_emb0")), DFOT_ERR_NAME, "read_tap: a pose-free handle has no tap 'pose_emb0'");
   auto pixels = [&](int l) { return h->r[l] * h->r[l]; };
   struct Tap { const char* n; int lvl; int c; const float* f; const bf16* b; };
   const Tap taps[] = {

@@ -6,6 +6,7 @@ FakeTensor tracing, ``torch.compile`` graphs and stream capture treat the HIP ke
 
     dfot::uvit3d_pose_forward(x, noise_levels, external_cond, external_cond_mask?, model) -> v      [dfot_uvit_forward]
     dfot::uvit3d_pose_forward_train(x, noise_levels, external_cond, mask?, params[], model) -> v    [autograd: dfot_op_* forward/backward]
+    dfot::uvit3d_forward(x, noise_levels (float), external_cond?, external_cond_mask?, model) -> v  [dfot_uvit3d_forward_live]
     dfot::dit3d_forward(x, noise_levels, model) -> v                                                [dfot_dit_forward]
     dfot::dit3d_forward_cond(x, noise_levels, external_cond, external_cond_mask?, model) -> v       [dfot_dit_forward_cond]
     dfot::dit3d_forward_f(x, noise_levels (float), external_cond?, external_cond_mask?, model) -> v [dfot_dit_forward_f]
@@ -15,7 +16,7 @@ FakeTensor tracing, ``torch.compile`` graphs and stream capture treat the HIP ke
     dfot::ddim_hg_step(x, x_in, v, sa, s1, an, cn, keep, weight, gen, nfe) -> x_next                [dfot_ddim_compose / _tokw]
 
 ``model`` is an integer key of a live backbone module (``register_model``): operators take tensors and scalars only.
-The nn.Module mirrors (`UViT3DPose`, `DiT3D`, `DifferenceDiT3D`) dispatch their ``forward`` through these operators and the
+The nn.Module mirrors (`UViT3DPose`, `UViT3D`, `DiT3D`, `DifferenceDiT3D`) dispatch their ``forward`` through these operators and the
 sampler's ``_process_conditions`` through ``dfot::ray_encoding``; the sampler's step loop calls the same C entry points
 directly (it re-uses its output buffers across steps), ``dfot::hg_prepare`` / ``dfot::ddim_hg_step`` are the functional forms
 for a host that drives the step itself.
@@ -54,6 +55,17 @@ def uvit3d_pose_forward(x: Tensor, noise_levels: Tensor, external_cond: Tensor, 
 
 
 @uvit3d_pose_forward.register_fake
+def _(x, noise_levels, external_cond, external_cond_mask, model):
+    return torch.empty_like(x)
+
+
+# the pose-free U-ViT (uvit3d_backbone.UViT3D): float levels, optional actions (B, T, dim) and the optional per-video uint8 mask (B,)
+@custom_op("dfot::uvit3d_forward", mutates_args=())
+def uvit3d_forward(x: Tensor, noise_levels: Tensor, external_cond: Optional[Tensor], external_cond_mask: Optional[Tensor], model: int) -> Tensor:
+    return _model(model)._forward_impl(x, noise_levels, external_cond, external_cond_mask)
+
+
+@uvit3d_forward.register_fake
 def _(x, noise_levels, external_cond, external_cond_mask, model):
     return torch.empty_like(x)
 

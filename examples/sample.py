@@ -6,6 +6,7 @@
   python examples/sample.py k600diff [--ckpt ...]
   python examples/sample.py facdit   [--ckpt ...]   (FacDiT-XL, the taichikl recipe: 4x32x32 latents, patch 2, 16 frames)
   python examples/sample.py facmat   [--ckpt ...]   (FacMatDiT XL-64-1, the same recipe: matrix attention with RoPE over the 16 frames)
+  python examples/sample.py uvit3d   [--cond action:4]   (the pose-free U-ViT at the RE10K widths, 256x256 frames, continuous diffusion)
   python examples/sample.py k600 --continuous --decode-image-vae   (latents -> frames through a random-weight per-frame ImageVAE)
 
 Without --ckpt the backbone gets seeded random weights (there is no network here to fetch the released checkpoints);
@@ -28,7 +29,7 @@ from bench import RE10K, synth_poses  # noqa: E402
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("model", choices=["re10k", "k600", "k600diff", "facdit", "facmat"])
+    ap.add_argument("model", choices=["re10k", "uvit3d", "k600", "k600diff", "facdit", "facmat"])
     ap.add_argument("--ckpt")
     ap.add_argument("--inputs")
     ap.add_argument("--frames", type=int, default=8)
@@ -60,6 +61,22 @@ def main():
         xs = torch.randn(a.batch, a.frames, 3, 256, 256, generator=torch.Generator().manual_seed(a.seed))
         conds = synth_poses(a.batch, a.frames, 100 + a.seed)
         n_ctx = 1
+    elif a.model == "uvit3d":  # UViT3DPose's parent class: no poses; unconditioned, or actions (B, T, DIM) as dmlab / Minecraft pass them
+        dim = 0
+        if a.cond:
+            ctype, num = a.cond.split(":")
+            if ctype != "action":
+                raise SystemExit("uvit3d takes --cond action:DIM only")
+            dim = int(num)
+            conds = torch.randn(a.batch, 8, dim, generator=torch.Generator().manual_seed(200 + a.seed))
+        ucfg = {k: v for k, v in RE10K.items() if k != "conditioning"}
+        model = dfot_amd.UViT3D(ucfg, x_shape=(3, 256, 256), max_tokens=8, external_cond_dim=dim, use_causal_mask=False).cuda()
+        cfg = dfot_amd.SamplerConfig(x_shape=(3, 256, 256), max_tokens=8, diffusion=dfot_amd.DiffusionConfig(sampling_timesteps=a.steps, is_continuous=True),
+                                     prediction_guidance=dict(name="vanilla", guidance_scale=1.5) if dim else {"name": "conditional"},
+                                     external_cond_type="action", external_cond_dim=dim, external_cond_processing="mask_first" if dim else None)
+        sampler = dfot_amd.DFoTVideoSampler(cfg, model, noise)
+        xs = torch.randn(a.batch, 8, 3, 256, 256, generator=torch.Generator().manual_seed(a.seed))
+        n_ctx = 2
     else:
         diff, fac, facmat = a.model == "k600diff", a.model == "facdit", a.model == "facmat"
         x_shape, tokens = ((4, 32, 32), 16) if fac or facmat else ((16, 16, 16), 5)

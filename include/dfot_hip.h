@@ -128,6 +128,51 @@ int dfot_uvit_forward_cached_masks(dfot_uvit_t h, const float* x, const float* n
  * "down2","mid","up2","up1","up0" in the oracle's NCHW layout. */
 int dfot_uvit_read_tap(dfot_uvit_t h, const char* name, float* out, size_t capacity_floats, void* stream);
 
+/* ---- pose-free U-ViT (the reference's UViT3D, algorithms/dfot/backbones/u_vit/u_vit3d.py:22-335) ----------------------------
+ * UViT3DPose's parent class: the same U-Net, but the embedding every block's FiLM reads is a per-frame vector only,
+ *   emb[b,t] = noise_level_pos_embedding(k[b,t]) (+ external_cond_embedding(cond[b,t]), zeroed for masked videos),
+ * so there is no pose patch embedding, no set_conditions step, no per-window FiLM cache and no per-window state.  The geometry
+ * fields mean what they mean in dfot_uvit_config and carry the same limits (head dim 64 or 128 at both transformer levels, ResBlock
+ * channels multiples of 128, coarsest-level tokens a multiple of 128, RoPE, Fourier noise embedding); emb_channels, noise_dim <= 1024. */
+typedef struct {
+  int32_t channels[4];
+  int32_t emb_channels;
+  int32_t num_updown_blocks[3];
+  int32_t num_mid_blocks;
+  int32_t num_heads;
+  int32_t in_channels;
+  int32_t resolution;
+  int32_t max_tokens;
+  int32_t cond_dim;      /* external_cond_dim of the action embedding Linear(cond_dim, E) - SiLU - Linear(E, E); 0 = none; <= 1024 */
+  int32_t noise_dim;     /* 256 */
+  float rope_theta;
+  float eps;
+  int32_t cond_dropout;  /* non-zero: external_cond_dropout > 0 -- the keys are external_cond_embedding.embedding.linear_*, and
+                          * external_cond_mask is honoured; zero: external_cond_embedding.linear_*, the mask is ignored (embeddings.py:364-387) */
+} dfot_uvit3d_config;
+/* The handle is a dfot_uvit_t: inventory (keys in the reference's state_dict() order: up_blocks before mid_blocks), load_weight, finalize,
+ * reserve, workspace_bytes, set_option, query, attn_timing, read_tap (also "nemb": the per-frame embedding [B*T][E]; no "pose_emb0") and
+ * destroy are the dfot_uvit_* calls above.  dfot_uvit_set_conditions / dfot_uvit_forward* refuse such a handle (DFOT_ERR_STATE), and
+ * dfot_uvit3d_forward* refuse a pose handle. */
+int dfot_uvit3d_create(const dfot_uvit3d_config* cfg, dfot_uvit_t* out);
+int64_t dfot_uvit3d_config_bytes(void);  /* sizeof(dfot_uvit3d_config), for binding checks */
+/* out[B,T,C,H,W] = model(x, noise_levels[B,T] fp32, external_cond[B,T,cond_dim] fp32 or NULL, external_cond_mask[B] bytes or NULL).
+ * NULL external_cond: the noise embedding alone (unconditioned video).  external_cond on a model of cond_dim 0: DFOT_ERR_ARG. */
+int dfot_uvit3d_forward(dfot_uvit_t h, const float* x, const float* noise_levels, const float* external_cond,
+                        const uint8_t* external_cond_mask, float* out, int batch, void* stream);
+/* ... with live_frames as in dfot_uvit_forward_cached_live (device uint8 [batch * T] or NULL): the frame-local tail skips dead frames */
+int dfot_uvit3d_forward_live(dfot_uvit_t h, const float* x, const float* noise_levels, const float* external_cond,
+                             const uint8_t* external_cond_mask, float* out, int batch, const uint8_t* live_frames, void* stream);
+/* The inference engine's FiLM norm kernels at op level.  h / out: bf16 [bt*pixels][c]; stats [bt][32][2] = (mean, rstd); sv fp32
+ * [bt][2c] and fcache bf16 [rows][2c] in the engine's column order (per 64 columns: 32 scale, then the 32 matching shift columns);
+ * cond_mask: NULL or one byte per video of `tokens` frames.  fcache == NULL runs the pose-free instantiation (FiLM from sv alone; cond_mask is
+ * not read). */
+int dfot_op_gn_film_silu(const void* h, const float* stats, const float* gamma, const float* beta, const void* fcache, const float* sv,
+                         const uint8_t* cond_mask, void* out, int bt, int pixels, int c, int tokens, void* stream);
+/* x / out: bf16 [m][c], w fp32 [c]: out = RMSNorm(x) * w * (1 + scale) + shift */
+int dfot_op_rms_film(const void* x, const float* w, const void* fcache, const float* sv, const uint8_t* cond_mask, void* out, int64_t m,
+                     int c, int rows_per_bt, int tokens, float eps, void* stream);
+
 /* ---- DiT3D backbone (Kinetics-600 path) --------------------------------------------------------------------- */
 typedef struct dfot_dit_s* dfot_dit_t;
 

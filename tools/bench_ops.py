@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Micro-benchmarks of the C-ABI primitives at the RE10K model shapes (model batch 2), HIP-event timed.
-Usage (GPU box): python tools/bench_ops.py [gemm] [conv] [attn] [tattn] [mattn] [vae_encode] [equal] [dit_front] [ivae]"""
+Usage (GPU box): python tools/bench_ops.py [gemm] [conv] [attn] [tattn] [mattn] [vae_encode] [equal] [dit_front] [ivae] [uvit3d]"""
 import ctypes as C
 import math
 import os
@@ -113,6 +113,26 @@ def facdit_forward(b):
     k = torch.randint(0, 1000, (b, 16), device="cuda")
     with torch.no_grad():
         return timeit(lambda: model(x, k), iters=10, warm=3)
+
+
+def uvit3d_forward(b=2):
+    """whole forward of the pose-free UViT3D next to UViT3DPose.forward_cached (the pose caches built once, outside the timed region) at the
+    RE10K widths, 256x256 frames, 8 tokens, model batch b, same process: (ms pose-free, ms pose)"""
+    from bench import RE10K
+    x = torch.randn(b, 8, 3, 256, 256, device="cuda")
+    k = torch.randn(b, 8, device="cuda")
+    out = []
+    with torch.no_grad():
+        free = dfot_amd.UViT3D({n: v for n, v in RE10K.items() if n != "conditioning"}, x_shape=(3, 256, 256), max_tokens=8, external_cond_dim=0).cuda().eval()
+        free.init_random(0)
+        out.append(timeit(lambda: free(x, k), iters=10, warm=3))
+        del free
+        torch.cuda.empty_cache()
+        pose = dfot_amd.UViT3DPose(RE10K, x_shape=(3, 256, 256), max_tokens=8).cuda().eval()
+        pose.init_random(0)
+        cond = torch.randn(b, 8, 180, 256, 256, device="cuda")
+        out.append(timeit(lambda: pose(x, k, cond), iters=10, warm=3))  # the same cond tensor every call: the cache hits by identity
+    return tuple(out)
 
 
 def mattn(b, tokens, e, h, cc, rr, rope):
@@ -276,6 +296,9 @@ def main():
                 w = torch.randn(n, k, device="cuda").bfloat16()
                 ms = timeit(lambda: torch.nn.functional.linear(a, w))
                 print(f"gemm {name:12s} M={m:6d} N={n:5d} K={k:5d} torch/hipBLASLt: {ms*1e3:8.1f} us  {2.0*m*n*k/ms/1e9:7.1f} TF/s", flush=True)
+    if "uvit3d" in what:
+        free, pose = uvit3d_forward(2)
+        print(f"uvit3d forward 256x256 Bm=2 T=8: UViT3D {free:.2f} ms, UViT3DPose.forward_cached {pose:.2f} ms, ratio {free / pose:.3f}")
     if "dit_front" in what:
         xl = dict(name="dit3d", variant="full", pos_emb_type="rope_3d", patch_size=1, hidden_size=1152, depth=28, num_heads=16)
         dit_front("XL K600", xl, dfot_amd.DiT3D, (16, 16, 16), 5, 8, 5)  # @DiT/XL at the K600 latents: B = 8, T = 5, P = 256

@@ -242,7 +242,7 @@ def install():
     diff_algo = imp("algorithms.dfot.difference_dfot_video")
     geo = imp("utils.geometry_utils")
     return {
-        "UViT3DPose": uvit_pose.UViT3DPose, "blocks": blocks, "DiscreteDiffusion": dd.DiscreteDiffusion,
+        "UViT3D": uvit.UViT3D, "UViT3DPose": uvit_pose.UViT3DPose, "blocks": blocks, "DiscreteDiffusion": dd.DiscreteDiffusion,
         "ContinuousDiffusion": cd.ContinuousDiffusion, "HistoryGuidance": hgm.HistoryGuidance,
         "DFoTVideoPose": pose_algo.DFoTVideoPose, "DFoTVideo": video_algo.DFoTVideo, "DiT3D": dit3d.DiT3D,
         "DifferenceDiT3D": diffdit.DifferenceDiT3D, "DifferenceDFoTVideo": diff_algo.DifferenceDFoTVideo,
