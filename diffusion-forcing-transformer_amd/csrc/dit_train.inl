@@ -1,5 +1,6 @@
 // Training path of the DiT backbones: DiT3D ("full", rope_3d: the README @DiT/XL K600 model, with or without the MLP branch) and
-// DifferenceDiT3D (factorized matrix attention, the bash/k600 model):
+// DifferenceDiT3D (factorized matrix attention, the bash/k600 model), and the FacMatDiT (DiT3D factorized matrix attention with the temporal
+// RoPE-1D, variant 3: the blocks of the difference model without its front end, matrix attention backward in attention_matrix_bwd.hip):
 // forward with saved activations, hand-written backward, gradients in one flat fp32 buffer (reference parameter order).
 // Included at the end of dit.hip (same translation unit: shares its kernels).
 //
@@ -773,6 +774,7 @@ struct dfot_dit_train_s {
   // compute copies
   dfot::bf16 *w_mod = nullptr, *w_modT = nullptr, *wfT = nullptr;
   float *b_mod = nullptr, *freqs = nullptr, *rope_cs = nullptr, *pos2d = nullptr;
+  float* trope = nullptr;  // variant 3 with use_temporal_rope: (cos, sin) [max_tokens][hd/2][2] of the matrix attention's RoPE-1D
   // fourier_noise: FourierEmbedding's freqs / phases [noise_dim].  Buffers, not parameters: they live HERE, outside the flat parameter /
   // gradient / moment buffers, so the optimizer (weight decay included), the gradient norm and the all-reduce never see them
   float *fz_freqs = nullptr, *fz_phases = nullptr;
@@ -935,11 +937,15 @@ int dfot_dit_train_destroy(dfot_dit_train_t h) {
   return DFOT_OK;
 }
 
-static int dit_train_create_impl(const DitCfg& c, dfot_dit_train_t* out) {
+// facmat_entry: the call comes from dfot_facmat_train_create, the only entry that builds variant 3
+static int dit_train_create_impl(const DitCfg& c, dfot_dit_train_t* out, bool facmat_entry = false) {
   DFOT_REQUIRE(c.variant != 2, DFOT_ERR_ARG, "train_create: variant 2 (factorized attention) has no training path; it is inference only");
-  DFOT_REQUIRE(c.variant != 3, DFOT_ERR_ARG, "train_create: variant 3 (factorized matrix DiT3D, FacMatDiT) has no training path; it is inference only");
-  DFOT_REQUIRE(c.variant == 0 || c.variant == 1, DFOT_ERR_ARG, "train_create: unknown variant %d", c.variant);
-  const bool facmat = c.variant == 1;
+  DFOT_REQUIRE(c.variant != 3 || facmat_entry, DFOT_ERR_ARG,
+               "train_create: variant 3 (factorized matrix DiT3D, FacMatDiT) is not built here; its trainer is dfot_facmat_train_create");
+  DFOT_REQUIRE(c.variant == 0 || c.variant == 1 || c.variant == 3, DFOT_ERR_ARG, "train_create: unknown variant %d", c.variant);
+  const bool diffm = c.variant == 1, facmat = c.variant == 1 || c.variant == 3;  // diffm: the difference front end
+  DFOT_REQUIRE(c.variant != 3 || !c.use_temporal_rope || c.rope_theta > 0.f, DFOT_ERR_ARG, "train_create: rope_theta %g must be positive",
+               (double)c.rope_theta);
   DFOT_REQUIRE(c.mlp_hidden >= 0 && c.mlp_hidden % 128 == 0 && c.temporal_mlp_hidden >= 0 && c.temporal_mlp_hidden % 128 == 0, DFOT_ERR_ARG,
                "train_create: MLP widths %d / %d must be multiples of 128", c.mlp_hidden, c.temporal_mlp_hidden);
   DFOT_REQUIRE(c.hidden_size % 128 == 0 && c.num_heads > 0 && c.hidden_size % c.num_heads == 0, DFOT_ERR_ARG,
@@ -992,7 +998,7 @@ static int dit_train_create_impl(const DitCfg& c, dfot_dit_train_t* out) {
   }
   h->o_pe_w = tr_add(h, "patch_embedder.proj.weight", {hd, c.in_channels, c.patch_size, c.patch_size});
   h->o_pe_b = tr_add(h, "patch_embedder.proj.bias", {hd});
-  if (facmat) h->o_diff = tr_add(h, "diff_embedder.embedding_table.weight", {2, hd});
+  if (diffm) h->o_diff = tr_add(h, "diff_embedder.embedding_table.weight", {2, hd});
   std::vector<TrainBlock> spatial(c.depth), temporal(facmat ? c.depth : 0);
   long off = 0;
   auto add_mlp = [&](TrainBlock& b, const std::string& pre, int width) {
@@ -1089,6 +1095,18 @@ static int dit_train_create_impl(const DitCfg& c, dfot_dit_train_t* out) {
     }
     if ((rc = tr_alloc(h, &h->pos2d, pe.size()))) return fail(rc);
     if (hipMemcpy(h->pos2d, pe.data(), pe.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return fail(DFOT_ERR_HIP);
+    if (c.variant == 3 && c.use_temporal_rope) {  // RotaryEmbedding1D over the frame axis, in float64 as dit_build
+      const int dim = hd / c.num_row_heads, pairs = dim / 2;
+      std::vector<float> cs((size_t)c.max_tokens * pairs * 2);
+      for (int t = 0; t < c.max_tokens; ++t)
+        for (int i = 0; i < pairs; ++i) {
+          const double ang = (double)t * std::pow((double)c.rope_theta, -2.0 * (double)i / (double)dim);
+          cs[((size_t)t * pairs + i) * 2 + 0] = (float)std::cos(ang);
+          cs[((size_t)t * pairs + i) * 2 + 1] = (float)std::sin(ang);
+        }
+      if ((rc = tr_alloc(h, &h->trope, cs.size()))) return fail(rc);
+      if (hipMemcpy(h->trope, cs.data(), cs.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return fail(DFOT_ERR_HIP);
+    }
   } else {  // RoPE-3D table, as dit_build
     const int half = h->d / 2, q = half / 3, rem = half % 3;
     int parts[3] = {q, q, q};
@@ -1129,6 +1147,17 @@ int dfot_dit_train_create_f(const dfot_dit_config_f* cfg, dfot_dit_train_t* out)
   static_cast<dfot_dit_config&>(c) = cfg->base;
   c.fourier_noise = cfg->fourier_noise;
   return dit_train_create_impl(c, out);
+}
+
+int dfot_facmat_train_create(const dfot_dit_config_f* cfg, dfot_dit_train_t* out) {
+  DFOT_REQUIRE(cfg && out, DFOT_ERR_ARG, "facmat_train_create: null argument");
+  DFOT_REQUIRE(cfg->base.variant == 3, DFOT_ERR_ARG,
+               "facmat_train_create: variant %d; this entry builds variant 3 (DiT3D factorized matrix) only, dfot_dit_train_create[_f] build 0 and 1",
+               cfg->base.variant);
+  DFOT_REQUIRE(!cfg->fourier_noise, DFOT_ERR_ARG, "facmat_train_create: fourier_noise (continuous diffusion) is not supported for variant 3");
+  DitCfg c;
+  static_cast<dfot_dit_config&>(c) = cfg->base;
+  return dit_train_create_impl(c, out, true);
 }
 
 int dfot_dit_train_num_params(dfot_dit_train_t h) { return h ? (int)h->params.size() : 0; }
@@ -1217,14 +1246,16 @@ int dfot_dit_train_reserve(dfot_dit_train_t h, int max_batch) {
   h->ws_bytes = 0;
   h->max_batch = 0;
   const DitCfg& c = h->cfg;
-  const bool facmat = c.variant == 1;
+  const bool diffm = c.variant == 1, facmat = c.variant == 1 || c.variant == 3;
   const int hd = c.hidden_size, nd = c.noise_dim, E = c.embed_col_dim;
   const size_t rows = (size_t)max_batch * c.max_tokens * h->P;
   const int frames = max_batch * c.max_tokens;
   const int fp = (frames + 255) / 256 * 256;
   const size_t bhn = (size_t)max_batch * c.num_heads * c.max_tokens * h->P;
   const size_t qsz = bhn * h->dstride;
-  const size_t fe = (size_t)frames * E;
+  // variant 3 runs odd frame totals: the two right-factor GEMMs over frames * E rows (E = 64) then take one more, zero-filled frame
+  // (whole 128-row tiles) whose output rows nothing reads; every contraction over the (frame, e) rows uses the exact count
+  const size_t fe = (size_t)(frames + (c.variant == 3 ? 1 : 0)) * E;
   int widest = 3 * hd;
   for (const TrainBlock& b : h->blocks) widest = b.mh > widest ? b.mh : widest;
   int rc = 0;
@@ -1261,8 +1292,10 @@ int dfot_dit_train_reserve(dfot_dit_train_t h, int max_batch) {
       WS(h->c_da1, (size_t)frames * hd); WS(h->c_dh1, (size_t)frames * hd);
     }
   }
-  if (facmat) {
+  if (diffm) {
     WS(h->ma_sc, (size_t)(1 + MA_CHUNKS) * max_batch * c.num_col_heads * c.num_row_heads * 2 * c.max_tokens * c.max_tokens);  // sums, then the chunk planes
+  }
+  if (facmat) {
     WS(h->mt, rows * hd); WS(h->do2, fe * hd); WS(h->dz, fe * 3 * hd); WS(h->dw1, fe * hd);
     WS(h->perm_a, (size_t)(h->P > 128 ? h->P : 128) * frames * hd); WS(h->perm_b, (size_t)(h->P > 128 ? h->P : 128) * frames * hd);
   }
@@ -1287,9 +1320,9 @@ static int dit_train_forward_impl(dfot_dit_train_t h, const float* x, const int3
   DFOT_REQUIRE(h->synced, DFOT_ERR_STATE, "train_forward: call dfot_dit_train_sync_weights after attaching / updating the parameters");
   DFOT_REQUIRE(batch > 0 && batch <= h->max_batch, DFOT_ERR_STATE, "train_forward: batch %d exceeds the reserved %d", batch, h->max_batch);
   const DitCfg& c = h->cfg;
-  const bool facmat = c.variant == 1;
+  const bool diffm = c.variant == 1, facmat = c.variant == 1 || c.variant == 3;
   DFOT_REQUIRE(tokens > 0 && tokens <= c.max_tokens, DFOT_ERR_SHAPE, "train_forward: %d tokens, max_tokens is %d", tokens, c.max_tokens);
-  DFOT_REQUIRE(!facmat || tokens % 2 == 0, DFOT_ERR_SHAPE, "train_forward: %d tokens; the difference model takes (difference, frame) pairs", tokens);
+  DFOT_REQUIRE(!diffm || tokens % 2 == 0, DFOT_ERR_SHAPE, "train_forward: %d tokens; the difference model takes (difference, frame) pairs", tokens);
   const int n = tokens * h->P, hd = c.hidden_size, P = h->P, frames = batch * tokens, nd = c.noise_dim, E = c.embed_col_dim;
   DFOT_REQUIRE(n % 128 == 0, DFOT_ERR_SHAPE, "train_forward: sequence length %d (tokens x patches) must be a multiple of 128", n);
   hipStream_t s = (hipStream_t)stream;
@@ -1308,7 +1341,7 @@ static int dit_train_forward_impl(dfot_dit_train_t h, const float* x, const int3
   hipLaunchKernelGGL(silu_fwd_kernel, dim3(cdiv((long)frames * hd, 256)), dim3(256), 0, s, h->h1, h->a1, (long)frames * hd);
   DFOT_CHECK_HIP(hipMemsetAsync(h->semb, 0, (size_t)h->fp * hd * sizeof(bf16), s));
   hipLaunchKernelGGL(rows_linear_kernel<0>, dim3(cdiv(hd, 4), frames), dim3(256), 0, s, h->a1, p + h->o_t_w2, p + h->o_t_b2, h->cemb, h->semb, hd, hd);
-  if (facmat)
+  if (diffm)
     hipLaunchKernelGGL(add_diff_kernel, dim3(cdiv((long)frames * hd, 256)), dim3(256), 0, s, h->cemb, p + h->o_diff, h->semb, frames, tokens, hd);
   DFOT_CHECK_HIP(hipGetLastError());
   h->cond_active = cond || labels;
@@ -1343,6 +1376,7 @@ static int dit_train_forward_impl(dfot_dit_train_t h, const float* x, const int3
   const float qscale = 1.4426950408889634f / sqrtf((float)h->d);
   // attention sequences: the whole video with RoPE-3D (variant 0) or one frame without RoPE (variant 1 spatial blocks)
   const int seq = facmat ? P : n, nseq = facmat ? frames : batch;
+  const int gfe = (c.variant == 3 ? (frames + 1) & ~1 : frames) * E;  // rows of the right-factor GEMMs (see reserve)
   auto combine = [&](const bf16* a, long gate_off, float* dst) -> int {
     hipLaunchKernelGGL(gate_combine_kernel, dim3(cdiv(rows * hd / 4, 256)), dim3(256), 0, s, h->X, dst, a, h->mod_table, h->ldt, gate_off, hd, P,
                        rows * hd / 4);
@@ -1366,10 +1400,15 @@ static int dit_train_forward_impl(dfot_dit_train_t h, const float* x, const int3
       const bool bias = b.o_qkv_bias >= 0;
       if ((rc = tr_transpose(b.m, h->mt, P, hd, s, frames))) return rc;                                                    // m^T per frame [hd][P]
       if ((rc = tr_gemm_bf16(h->mt, P, b.u_t, frames * hd, E, P, nullptr, b.w1, E, s, 0, hd))) return rc;                   // w1[f][e][d] = sum_p U[p][e] m[f][p][d]
-      if ((rc = tr_gemm_bf16(b.w1, hd, b.v_t, frames * E, 3 * hd, hd, bias ? p + b.o_qkv_bias : nullptr, b.z, 3 * hd, s, bias ? E : 0))) return rc;
+      if ((rc = tr_gemm_bf16(b.w1, hd, b.v_t, gfe, 3 * hd, hd, bias ? p + b.o_qkv_bias : nullptr, b.z, 3 * hd, s, bias ? E : 0))) return rc;
       {
         const int hn = E / c.num_col_heads, hdr = hd / c.num_row_heads;
-        if ((rc = launch_matrix_attn(b.z, b.o2, batch, tokens, E, hd, c.num_col_heads, c.num_row_heads, 1.0f / sqrtf((float)hn * (float)hdr), s))) return rc;
+        const float mscale = 1.0f / sqrtf((float)hn * (float)hdr);
+        if (diffm)
+          rc = launch_matrix_attn(b.z, b.o2, batch, tokens, E, hd, c.num_col_heads, c.num_row_heads, mscale, s);
+        else  // FacMatDiT: any 1 <= tokens <= 32, RoPE-1D over the frame axis when the model has one (trope == nullptr: none)
+          rc = launch_matrix_attn_rope(b.z, b.o2, h->trope, batch, tokens, E, hd, c.num_col_heads, c.num_row_heads, mscale, s);
+        if (rc) return rc;
       }
       if ((rc = tr_transpose(b.o2, h->mt, E, hd, s, frames))) return rc;                                                   // o^T per frame [hd][E]
       if ((rc = tr_gemm_bf16(h->mt, E, b.pu_t, frames * hd, P, E, nullptr, b.sfac, P, s, 0, hd))) return rc;                // s[f][p][d] = sum_e U'[e][p] o[f][e][d]
@@ -1427,7 +1466,7 @@ int dfot_dit_train_backward(dfot_dit_train_t h, const float* d_out, void* stream
   DFOT_REQUIRE(h && d_out, DFOT_ERR_ARG, "train_backward: null argument");
   DFOT_REQUIRE(h->batch > 0 && h->x_saved, DFOT_ERR_STATE, "train_backward: no forward to differentiate");
   const DitCfg& c = h->cfg;
-  const bool facmat = c.variant == 1;
+  const bool diffm = c.variant == 1, facmat = c.variant == 1 || c.variant == 3;
   const int batch = h->batch, tokens = h->tokens, n = tokens * h->P, hd = c.hidden_size, P = h->P, frames = batch * tokens, nd = c.noise_dim;
   const int fp = h->fp, E = c.embed_col_dim;
   const int seq = facmat ? P : n, nseq = facmat ? frames : batch;
@@ -1513,7 +1552,8 @@ int dfot_dit_train_backward(dfot_dit_train_t h, const float* d_out, void* stream
       if ((rc = wgrad(h->dqkv, 3 * hd, b.m, hd, rows, G + b.o_qkv_w))) return rc;  // dWqkv = dqkv^T m
     } else {
       const bool bias = b.o_qkv_bias >= 0;
-      const int fe = frames * E;
+      const int fe = frames * E;                                                   // the exact (frame, e) row count: every contraction uses it
+      const int gfe = (c.variant == 3 ? (frames + 1) & ~1 : frames) * E;            // rows of the right-factor GEMM (see reserve)
       const long fk = (long)frames * hd;  // contraction length of the left-factor gradients
       // a = s V' + bias'[p] ; s[f][p][d] = sum_e U'[e][p] o[f][e][d]
       if ((rc = gate_bwd(b.a, b.mod + 2 * hd, h->scratch_f))) return rc;
@@ -1528,7 +1568,12 @@ int dfot_dit_train_backward(dfot_dit_train_t h, const float* d_out, void* stream
       if ((rc = tr_wgrad(h->perm_a, h->perm_b, 128, P, (int)fk, h->dwf, s, h->wg_ws, h->wg_ws_floats))) return rc;
       DFOT_CHECK_HIP(hipMemcpyAsync(G + b.o_proj_u, h->dwf, (size_t)E * P * sizeof(float), hipMemcpyDeviceToDevice, s));
       // attention over the frames
-      {
+      if (!diffm) {  // FacMatDiT: one launch, any token count, with the rotation and its inverse
+        const int hn = E / c.num_col_heads, hdr = hd / c.num_row_heads;
+        if ((rc = launch_matrix_attn_rope_bwd(b.z, h->do2, h->trope, h->dz, batch, tokens, E, hd, c.num_col_heads, c.num_row_heads,
+                                              1.0f / sqrtf((float)hn * (float)hdr), s)))
+          return rc;
+      } else {
         const int hn = E / c.num_col_heads, hdr = hd / c.num_row_heads;
         const int nheads = batch * c.num_col_heads * c.num_row_heads;
         const long nsc = (long)nheads * 2 * tokens * tokens;
@@ -1541,7 +1586,7 @@ int dfot_dit_train_backward(dfot_dit_train_t h, const float* d_out, void* stream
       }
       // z = w1 V + bias[e] ; w1[f][e][d] = sum_p U[p][e] m[f][p][d]
       if (bias && (rc = frames_sum(h->dz, G + b.o_qkv_bias, (long)E * 3 * hd))) return rc;
-      if ((rc = tr_gemm_bf16(h->dz, 3 * hd, b.v_s, fe, hd, 3 * hd, nullptr, h->dw1, hd, s))) return rc;           // dw1 = dz V^T  (V stored (in, out))
+      if ((rc = tr_gemm_bf16(h->dz, 3 * hd, b.v_s, gfe, hd, 3 * hd, nullptr, h->dw1, hd, s))) return rc;          // dw1 = dz V^T  (V stored (in, out))
       if ((rc = wgrad(b.w1, hd, h->dz, 3 * hd, fe, G + b.o_qkv_v))) return rc;                                   // dV[in][out] = w1^T dz
       if ((rc = tr_transpose(h->dw1, h->mt, E, hd, s, frames))) return rc;                                       // dw1^T per frame [hd][E]
       if ((rc = tr_gemm_bf16(h->mt, E, b.u_s, frames * hd, P, E, nullptr, h->dO, P, s, 0, hd))) return rc;         // dm[f][p][d] = sum_e U[p][e] dw1[f][e][d]
@@ -1587,7 +1632,7 @@ int dfot_dit_train_backward(dfot_dit_train_t h, const float* d_out, void* stream
   // ---- noise-level embedding MLP (frames x hidden, fp32) ----
   const long fh = (long)frames * hd;
   hipLaunchKernelGGL(silu_bwd_kernel, dim3(cdiv(fh, 256)), dim3(256), 0, s, h->dsemb, h->cemb, h->dc, fh);
-  if (facmat) hipLaunchKernelGGL(diff_grad_kernel, dim3(cdiv(2 * hd, 256)), dim3(256), 0, s, h->dc, G + h->o_diff, frames, tokens, hd);
+  if (diffm) hipLaunchKernelGGL(diff_grad_kernel, dim3(cdiv(2 * hd, 256)), dim3(256), 0, s, h->dc, G + h->o_diff, frames, tokens, hd);
   if (h->cond_active) {  // the condition embedding was added to c: its gradient is dc, zero for dropped videos
     hipLaunchKernelGGL(cond_grad_mask_kernel, dim3(cdiv(fh, 256)), dim3(256), 0, s, h->dc, h->cond_masked ? h->c_mask : (const uint8_t*)nullptr,
                        h->c_dce, frames, tokens, hd);

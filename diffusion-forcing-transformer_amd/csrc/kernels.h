@@ -146,6 +146,9 @@ int launch_attention_temporal(const bf16* q, const bf16* k, const bf16* v, bf16*
 // (video, col head, row head), 1 <= L <= 32, (h / rr) % 4 == 0; rope_cs: [>= L][h/rr/2][2] (cos, sin) per frame, nullptr = no rotation
 int launch_matrix_attn_rope(const bf16* z, bf16* o, const float* rope_cs, int batch, int L, int E, int h, int cc, int rr, float scale,
                             hipStream_t s);
+// attention_matrix_bwd.hip: backward of launch_matrix_attn_rope; d_o [batch*L*E][h], dz [batch*L*E][3h] (dq|dk|dv); same shape rules
+int launch_matrix_attn_rope_bwd(const bf16* z, const bf16* d_o, const float* rope_cs, bf16* dz, int batch, int L, int E, int h, int cc, int rr,
+                                float scale, hipStream_t s);
 // ---- attention forward: key split of the last round + scratch (attention_split.hip; shared by v3, v5 and ks) ----
 struct AttnSplit {
   int tiles, full, rem, nsplit;

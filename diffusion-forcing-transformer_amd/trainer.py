@@ -45,32 +45,7 @@ class DiT3DTrainer:
         c.patch_size = int(_get(cfg, "patch_size", 2))
         c.in_channels, c.height, c.width = self.x_shape
         c.noise_dim, c.timesteps, c.rope_theta, c.eps = 256, int(timesteps), 10000.0, 1e-6
-        ratio = _get(cfg, "spatial_mlp_ratio", None)
-        variant = _get(cfg, "variant", "full")
-        if variant == "full":  # DiT3D (dit3d.yaml)
-            if _get(cfg, "pos_emb_type", "rope_3d") != "rope_3d":
-                raise ValueError("DiT3DTrainer builds the 'full' DiT3D with pos_emb_type='rope_3d'")
-            c.variant, c.hidden_size, c.max_tokens = 0, int(_get(cfg, "hidden_size")), int(max_tokens)
-        elif variant == "factorized_matrix_attention" and _get(cfg, "use_temporal_rope", False):
-            # dit3d_factorized_matrix.yaml (FacMatDiT) shares variant and pos_emb_type with the difference model; building that one
-            # instead would double the tokens and drop the RoPE
-            raise ValueError("no training path for DiT variant 'factorized_matrix_attention' with use_temporal_rope (FacMatDiT): it is inference only")
-        elif variant == "factorized_matrix_attention":  # DifferenceDiT3D (bash/k600): as dit_backbone.DifferenceDiT3D._configure
-            if _get(cfg, "pos_emb_type") != "sinusoidal_2d" or _get(cfg, "merge_type", "interleaved") != "interleaved":
-                raise ValueError("the difference model trains with pos_emb_type='sinusoidal_2d' and merge_type='interleaved'")
-            if _get(cfg, "matrix_block", "matrix") != "matrix" or _get(cfg, "matrix_multi_token", False) or _get(cfg, "fixed_u", None):
-                raise ValueError("only matrix_block='matrix' with learned factors and multi_token=False is supported")
-            if ratio is None:
-                raise AssertionError("spatial_mlp_ratio must be specified for matrix attention")
-            tratio = _get(cfg, "mlp_ratio", None)
-            c.variant, c.hidden_size, c.max_tokens = 1, int(_get(cfg, "embed_row_dim")), 2 * int(max_tokens)
-            c.embed_col_dim = int(_get(cfg, "embed_col_dim"))
-            c.num_col_heads, c.num_row_heads = int(_get(cfg, "num_col_heads")), int(_get(cfg, "num_row_heads"))
-            c.temporal_mlp_hidden = int(c.hidden_size * tratio) if tratio else 0
-            c.use_bias = int(bool(_get(cfg, "use_bias")))
-        else:
-            raise ValueError(f"no training path for DiT variant {variant!r}")
-        c.mlp_hidden = int(c.hidden_size * ratio) if ratio else 0
+        self._configure(c, cfg, int(max_tokens))
         fourier = bool(_get(cfg, "use_fourier_noise_embedding", False))
         continuous = bool(diffusion is not None and diffusion.is_continuous)
         if fourier != continuous:
@@ -81,7 +56,7 @@ class DiT3DTrainer:
         self._ccfg = c
         self.max_tokens = int(c.max_tokens)
         self._handle = C.c_void_p()
-        capi.check(capi.lib.dfot_dit_train_create_f(C.byref(c), C.byref(self._handle)))
+        self._create(c)
         lib, h = capi.lib, self._handle
         self.numel = int(lib.dfot_dit_train_total_numel(h))
         shape, ndim = (C.c_int64 * 4)(), C.c_int()
@@ -114,6 +89,39 @@ class DiT3DTrainer:
         self._acc_n = 0
         self._dirty = True
         self._last: Optional[dict] = None
+
+    def _configure(self, c: "capi.DiTConfigF", cfg, max_tokens: int) -> None:
+        """backbone keys -> the engine config's model fields (variant, widths, heads, max_tokens); the subclass hook of the constructor"""
+        ratio = _get(cfg, "spatial_mlp_ratio", None)
+        variant = _get(cfg, "variant", "full")
+        if variant == "full":  # DiT3D (dit3d.yaml)
+            if _get(cfg, "pos_emb_type", "rope_3d") != "rope_3d":
+                raise ValueError("DiT3DTrainer builds the 'full' DiT3D with pos_emb_type='rope_3d'")
+            c.variant, c.hidden_size, c.max_tokens = 0, int(_get(cfg, "hidden_size")), max_tokens
+        elif variant == "factorized_matrix_attention" and _get(cfg, "use_temporal_rope", False):
+            # dit3d_factorized_matrix.yaml (FacMatDiT) shares variant and pos_emb_type with the difference model; building that one
+            # instead would double the tokens and drop the RoPE
+            raise ValueError("no training path for DiT variant 'factorized_matrix_attention' with use_temporal_rope (FacMatDiT): it is inference only")
+        elif variant == "factorized_matrix_attention":  # DifferenceDiT3D (bash/k600): as dit_backbone.DifferenceDiT3D._configure
+            if _get(cfg, "pos_emb_type") != "sinusoidal_2d" or _get(cfg, "merge_type", "interleaved") != "interleaved":
+                raise ValueError("the difference model trains with pos_emb_type='sinusoidal_2d' and merge_type='interleaved'")
+            if _get(cfg, "matrix_block", "matrix") != "matrix" or _get(cfg, "matrix_multi_token", False) or _get(cfg, "fixed_u", None):
+                raise ValueError("only matrix_block='matrix' with learned factors and multi_token=False is supported")
+            if ratio is None:
+                raise AssertionError("spatial_mlp_ratio must be specified for matrix attention")
+            tratio = _get(cfg, "mlp_ratio", None)
+            c.variant, c.hidden_size, c.max_tokens = 1, int(_get(cfg, "embed_row_dim")), 2 * max_tokens
+            c.embed_col_dim = int(_get(cfg, "embed_col_dim"))
+            c.num_col_heads, c.num_row_heads = int(_get(cfg, "num_col_heads")), int(_get(cfg, "num_row_heads"))
+            c.temporal_mlp_hidden = int(c.hidden_size * tratio) if tratio else 0
+            c.use_bias = int(bool(_get(cfg, "use_bias")))
+        else:
+            raise ValueError(f"no training path for DiT variant {variant!r}")
+        c.mlp_hidden = int(c.hidden_size * ratio) if ratio else 0
+
+    def _create(self, c: "capi.DiTConfigF") -> None:
+        """the engine handle of the configured model; the other subclass hook"""
+        capi.check(capi.lib.dfot_dit_train_create_f(C.byref(c), C.byref(self._handle)))
 
     def __del__(self):
         h = getattr(self, "_handle", None)
@@ -378,3 +386,24 @@ class DiT3DTrainer:
     def grad_norm(self) -> float:
         capi.check(capi.lib.dfot_sumsq(capi.ptr(self.grads), self.numel, capi.ptr(self._sumsq), capi.stream_ptr()))
         return float(self._sumsq.sqrt().item())
+
+
+class FacMatDiTTrainer(DiT3DTrainer):
+    """Trainer of the FacMatDiT backbone: ``name: dit3d`` with ``variant: factorized_matrix_attention``, ``pos_emb_type: sinusoidal_2d``, with
+    or without ``use_temporal_rope`` (dit3d_factorized_matrix.yaml + the @FacMatDiT shortcuts; the reference's bash/taichikl recipes).  Same
+    constructor keywords and methods as DiT3DTrainer; max_tokens is the algorithm's (not doubled: there are no difference tokens), any
+    1 <= T <= max_tokens <= 32 trains.  The matrix attention and its backward run with the RoPE-1D over the frame axis
+    (csrc/attention_matrix.hip, csrc/attention_matrix_bwd.hip).  Discrete diffusion only."""
+
+    def _configure(self, c: "capi.DiTConfigF", cfg, max_tokens: int) -> None:
+        from .dit_backbone import configure_facmat
+        variant, pos = _get(cfg, "variant", "full"), _get(cfg, "pos_emb_type", "rope_3d")
+        if variant != "factorized_matrix_attention" or pos != "sinusoidal_2d":
+            raise ValueError(f"FacMatDiTTrainer builds variant='factorized_matrix_attention' with pos_emb_type='sinusoidal_2d', not "
+                             f"{variant!r} / {pos!r} (DiT3DTrainer trains the 'full' DiT3D and the difference model)")
+        if _get(cfg, "use_fourier_noise_embedding", False):
+            raise ValueError("use_fourier_noise_embedding=True is not supported by FacMatDiTTrainer: it trains under discrete diffusion only")
+        configure_facmat(c, cfg, max_tokens)  # refuses matrix_multi_token, flatten_matrix_rope, fixed_u, matrix_block, patches, max_tokens by name
+
+    def _create(self, c: "capi.DiTConfigF") -> None:
+        capi.check(capi.lib.dfot_facmat_train_create(C.byref(c), C.byref(self._handle)))

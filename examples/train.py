@@ -4,6 +4,7 @@
   python examples/train.py k600     [--ckpt K600.ckpt] [--steps 100] [--batch 8] [--save out.ckpt]
   python examples/train.py k600 --pixels [--vae-ckpt VideoVAE_K600.ckpt]                # online latents: frames -> VideoVAE encoder -> step
   python examples/train.py k600diff [--accumulate 2]                                  # the model bash/k600/*.sh train
+  python examples/train.py facmat   [--xl] [--batch 8]                                # FacMatDiT (dit3d_factorized_matrix.yaml); --xl: XL-64-1, taichikl shape
   python examples/train.py re10k    [--batch 8]                                       # RE10K UViT3DPose (BASELINE config 5), synthetic frames + poses
   python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 examples/train.py k600   # data parallel, one rank per GPU
 
@@ -32,7 +33,7 @@ K600_DATA_STD = [5.591, 5.257, 7.033, 6.401, 6.091, 11.233, 5.608, 7.5, 5.277, 5
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("model", choices=["k600", "k600diff", "re10k"])
+    ap.add_argument("model", choices=["k600", "k600diff", "facmat", "re10k"])
     ap.add_argument("--ckpt")
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--batch", type=int, default=8)
@@ -44,6 +45,8 @@ def main():
     ap.add_argument("--continuous", action="store_true",
                     help="k600 / k600diff: continuous diffusion as @diffusion/continuous (Fourier noise-level embedding, levels in [0, 1], cosine "
                          "training schedule shifted 0.125, sigmoid loss weighting)")
+    ap.add_argument("--xl", action="store_true", help="facmat: @FacMatDiT/XL-64-1 at the taichikl shape (4x32x32 latents, patch 2, 16 frames) "
+                                                      "instead of the tiny default (row width 128, depth 2, 4x16x8 latents, 5 frames)")
     ap.add_argument("--pixels", action="store_true", help="k600 / k600diff: encode synthetic frames online with the VideoVAE encoder")
     ap.add_argument("--vae-ckpt", help="--pixels: reference VideoVAE checkpoint (vae.* keys); random encoder weights otherwise")
     a = ap.parse_args()
@@ -55,6 +58,8 @@ def main():
         dist.init_process_group("nccl", device_id=torch.device("cuda", torch.cuda.current_device()))
     if a.model == "re10k":
         return train_re10k(a, rank, world)
+    if a.model == "facmat":
+        return train_facmat(a, rank, world)
     diff = a.model == "k600diff"
     ctype, cnum, ckw = None, 0, {}
     if a.cond:
@@ -125,6 +130,64 @@ def main():
         torch.save({"state_dict": {"diffusion_model.model." + k: v.cpu() for k, v in trainer.state_dict().items()}}, a.save)
         print("saved", a.save)
     if world > 1:
+        dist.barrier()
+        dist.destroy_process_group()
+
+
+def train_facmat(a, rank, world):
+    """DFoTVideo training of the FacMatDiT backbone (bash/taichikl/train_dfot_facmat-*): DiT3D with factorized matrix attention and the
+    temporal RoPE, discrete diffusion, random_independent levels, fused-min-SNR v-loss"""
+    if a.continuous or a.pixels:
+        raise SystemExit("facmat trains on synthetic latents under discrete diffusion")
+    if a.xl:
+        x_shape, tokens = (4, 32, 32), 16
+        cfg = dict(patch_size=2, embed_col_dim=64, embed_row_dim=1152, num_heads=16, num_col_heads=1, num_row_heads=16, depth=28)
+    else:
+        x_shape, tokens = (4, 16, 8), 5
+        cfg = dict(patch_size=1, embed_col_dim=64, embed_row_dim=128, num_heads=4, num_col_heads=1, num_row_heads=4, depth=2)
+    cfg.update(name="dit3d", variant="factorized_matrix_attention", pos_emb_type="sinusoidal_2d", use_temporal_rope=True, mlp_ratio=4.0,
+               spatial_mlp_ratio=4.0, use_bias=True, matrix_block="matrix")
+    ckw = {}
+    if a.cond:
+        ctype, cnum = a.cond.split(":")[0], int(a.cond.split(":")[1])
+        if ctype != "action":
+            raise SystemExit("facmat: --cond action:DIM")
+        ckw = dict(external_cond_type="action", external_cond_dim=cnum)
+        cfg["external_cond_dropout"] = 0.1
+    trainer = dfot_amd.FacMatDiTTrainer(cfg, x_shape=x_shape, max_tokens=tokens, lr=a.lr,
+                                        loss_weighting=dict(strategy="fused_min_snr", cum_snr_decay=0.96), **ckw)
+    if a.ckpt:
+        dfot_amd.load_reference_checkpoint(trainer, a.ckpt)
+    else:
+        init = dfot_amd.DiT3D(cfg, x_shape=x_shape, max_tokens=tokens, **ckw)
+        init.init_random(seed=0)  # the same on every rank
+        trainer.load_state_dict({k: v.detach() for k, v in init.state_dict().items()})
+        del init
+    sampling = dfot_amd.TrainingNoise(noise_level="random_independent", is_continuous=False, n_context_tokens=2)
+    g = torch.Generator().manual_seed(1000 + rank)
+    gdrop = torch.Generator(device="cuda").manual_seed(3000 + rank)
+    masks = torch.ones(a.batch, tokens, dtype=torch.bool)
+    t0 = time.perf_counter()
+    for step in range(a.steps):
+        for _ in range(a.accumulate):
+            frames = torch.randn(a.batch, tokens, *x_shape, generator=g)
+            noise = torch.randn(a.batch, tokens, *x_shape, generator=g)
+            levels, loss_masks = sampling.sample(a.batch, tokens, masks, g, training=True)
+            conds = None
+            if a.cond:
+                conds = torch.randn(a.batch, tokens, cnum, generator=g)
+                conds[:, :1] = 0  # external_cond_processing: mask_first
+            loss = trainer.loss_and_grads(frames, levels, noise, loss_masks, conditions=conds, dropout_generator=gdrop)
+            if a.accumulate > 1:
+                trainer.accumulate()
+        trainer.optimizer_step(world)
+        if rank == 0 and (step % 5 == 0 or step == a.steps - 1):
+            print(f"step {step:4d}  loss {float(loss.item()):.4f}  {(time.perf_counter() - t0) / (step + 1) * 1e3:.1f} ms/step", flush=True)
+    if a.save and rank == 0:
+        torch.save({"state_dict": {"diffusion_model.model." + k: v.cpu() for k, v in trainer.state_dict().items()}}, a.save)
+        print("saved", a.save)
+    if world > 1:
+        import torch.distributed as dist
         dist.barrier()
         dist.destroy_process_group()
 

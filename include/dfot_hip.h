@@ -208,7 +208,8 @@ typedef struct {
    *   dit3d_factorized_matrix.yaml + shortcut/FacMatDiT): the block sequence and parameters of variant 1 without the difference front
    *   end -- no diff_embedder, the conditioning depends on the noise level only, max_tokens is the caller's (<= 32, odd counts
    *   allowed) -- and with use_temporal_rope the RoPE-1D over the frame axis (dit_base.py:297-306) on q and k of the matrix attention;
-   *   the (cos, sin) table [max_tokens][hd/2] is built in float64 at create time and is not a parameter.  Inference only. */
+   *   the (cos, sin) table [max_tokens][hd/2] is built in float64 at create time and is not a parameter.  Trained through
+   *   dfot_facmat_train_create; dfot_dit_train_create[_f] refuse it. */
   int32_t variant;
   int32_t embed_col_dim;        /* 64 */
   int32_t num_col_heads;        /* 1 */
@@ -294,6 +295,12 @@ int dfot_dit_read_tap(dfot_dit_t h, const char* name, float* out, size_t capacit
 typedef struct dfot_dit_train_s* dfot_dit_train_t;
 int dfot_dit_train_create(const dfot_dit_config* cfg, dfot_dit_train_t* out);
 int dfot_dit_train_create_f(const dfot_dit_config_f* cfg, dfot_dit_train_t* out);  /* with dfot_dit_config_f.fourier_noise (see dfot_dit_create_f) */
+/* trainer of the DiT3D factorized-matrix model (FacMatDiT: variant 3 only, any other variant: DFOT_ERR_ARG; fourier_noise != 0:
+ * DFOT_ERR_ARG).  The handle is a dfot_dit_train_t: every other dfot_dit_train_* function takes it.  Parameters in the reference's
+ * registration order (no diff_embedder), any 1 <= T <= max_tokens <= 32 (odd frame totals included), the temporal RoPE table built in
+ * float64 when use_temporal_rope is set; actions / labels through dfot_dit_train_forward_cond.  dfot_dit_train_create[_f] keep refusing
+ * variant 3 and name this function. */
+int dfot_facmat_train_create(const dfot_dit_config_f* cfg, dfot_dit_train_t* out);
 int dfot_dit_train_destroy(dfot_dit_train_t h);
 int dfot_dit_train_num_params(dfot_dit_train_t h);
 const char* dfot_dit_train_param_name(dfot_dit_train_t h, int i);
@@ -445,6 +452,12 @@ int dfot_op_attention_temporal(const void* q, const void* k, const void* v, void
  * 1 <= L <= 32, E % cc == 0, h % rr == 0, (h/rr) % 4 == 0; anything else: DFOT_ERR_SHAPE before any launch */
 int dfot_op_matrix_attention_rope(const void* z, void* o, const float* rope_cs, int batch, int L, int E, int h, int cc, int rr,
                                   float scale, void* stream);
+/* backward of dfot_op_matrix_attention_rope: dz [batch*L*E][3h] bf16 (dq|dk|dv) for the upstream gradient d_o [batch*L*E][h] bf16 of o, in
+ * the forward's layouts.  q and k are rotated as the forward rotates them (S is the forward's S) and dq / dk are rotated back with the
+ * angle of their own frame.  Fixed summation order, no atomics: a video gives the same bits alone, in a batch and on repeat.  Same shape
+ * rules and error codes as the forward, checked before any launch; dz must not alias z or d_o (DFOT_ERR_ARG); rope_cs NULL = no rotation */
+int dfot_op_matrix_attention_rope_bwd(const void* z, const void* d_o, const float* rope_cs, void* dz, int batch, int L, int E, int h, int cc,
+                                      int rr, float scale, void* stream);
 /* the DifferenceDiT3D (variant 1) form of the same core, without rotation: register forms for L in {2, 4, 6, 8, 10}, one pair of
  * tokens per wave pass for every other L <= 32.  Test / measurement entry of the engine's own launcher */
 int dfot_op_matrix_attention(const void* z, void* o, int batch, int L, int E, int h, int cc, int rr, float scale, void* stream);

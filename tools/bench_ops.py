@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Micro-benchmarks of the C-ABI primitives at the RE10K model shapes (model batch 2), HIP-event timed.
-Usage (GPU box): python tools/bench_ops.py [gemm] [conv] [attn] [tattn] [mattn] [vae_encode] [equal] [dit_front] [ivae] [uvit3d]"""
+Usage (GPU box): python tools/bench_ops.py [gemm] [conv] [attn] [tattn] [mattn] [mattn_bwd] [facmat_train] [vae_encode] [equal] [dit_front] [ivae] [uvit3d]"""
 import ctypes as C
 import math
 import os
@@ -163,6 +163,39 @@ def facmat_forward(b, row=1152, heads=16, depth=28):
     k = torch.randint(0, 1000, (b, 16), device="cuda")
     with torch.no_grad():
         return timeit(lambda: model(x, k), iters=10, warm=3)
+
+
+def mattn_bwd(b, tokens, e, h, cc, rr):
+    """backward of the FacMatDiT matrix attention on one (q|k|v) matrix and a unit-normal d_o: us of dfot_op_matrix_attention_rope_bwd with and
+    without the table, us of the forward on the same input, and the algorithmic bytes -- q, k, v, d_o read once, dq, dk, dv written once"""
+    hd = h // rr
+    z = torch.randn(b * tokens * e, 3 * h, device="cuda").bfloat16()
+    d_o = torch.randn(b * tokens * e, h, device="cuda").bfloat16()
+    dz, o = torch.empty_like(z), torch.empty_like(d_o)
+    ang = torch.arange(tokens, dtype=torch.float64)[:, None] * 10000.0 ** (-torch.arange(0, hd, 2, dtype=torch.float64) / hd)[None]
+    table = torch.stack([ang.cos(), ang.sin()], -1).float().cuda().contiguous()
+    scale = 1.0 / math.sqrt((e // cc) * hd)
+    bwd = lambda t: timeit(lambda: capi.check(capi.lib.dfot_op_matrix_attention_rope_bwd(P(z), P(d_o), None if t is None else P(t), P(dz), b, tokens, e,
+                                                                                          h, cc, rr, scale, S())), iters=50, warm=5)
+    ms_rope, ms_plain = bwd(table), bwd(None)
+    ms_fwd = timeit(lambda: capi.check(capi.lib.dfot_op_matrix_attention_rope(P(z), P(o), P(table), b, tokens, e, h, cc, rr, scale, S())), iters=50, warm=5)
+    return ms_rope, ms_plain, ms_fwd, b * tokens * e * 7.0 * h * 2.0
+
+
+def facmat_train(b, row=1152, heads=16, depth=28):
+    """one training step (loss, backward, AdamW) of FacMatDiT (XL-64-1 by default: use_bias, both MLP ratios 4) at the taichikl shape
+    (4x32x32 latents, patch 2, 16 frames), ms"""
+    bb = dict(name="dit3d", variant="factorized_matrix_attention", pos_emb_type="sinusoidal_2d", use_temporal_rope=True, patch_size=2,
+              embed_col_dim=64, embed_row_dim=row, num_heads=heads, num_col_heads=1, num_row_heads=heads, depth=depth, mlp_ratio=4.0,
+              spatial_mlp_ratio=4.0, use_bias=True, matrix_block="matrix")
+    tr = dfot_amd.FacMatDiTTrainer(bb, x_shape=(4, 32, 32), max_tokens=16, loss_weighting=dict(strategy="fused_min_snr", cum_snr_decay=0.96))
+    model = dfot_amd.DiT3D(bb, x_shape=(4, 32, 32), max_tokens=16)  # for its init_random only
+    model.init_random(0)
+    tr.load_state_dict({n: t.detach() for n, t in model.state_dict().items()})
+    del model
+    xs, noise = torch.randn(b, 16, 4, 32, 32, device="cuda"), torch.randn(b, 16, 4, 32, 32, device="cuda")
+    k = torch.randint(0, 1000, (b, 16))
+    return timeit(lambda: tr.training_step(xs, k, noise), iters=5, warm=2)
 
 
 def vae_encode(b=2, t=17, res=128):
@@ -335,6 +368,27 @@ def main():
         ms_attn = mattn(2, 16, 64, 1152, 1, 16, True)[0]
         print(f"facmat XL forward B=2 x 16 frames x 256 patches: {ms:.3f} ms; matrix attention {depth} x {ms_attn*1e3:.1f} us = "
               f"{depth * ms_attn / ms * 100:.1f} % of it", flush=True)
+    if "mattn_bwd" in what:
+        for name, (h, rr) in {"S": (384, 6), "XL": (1152, 16)}.items():
+            for b in (2, 8, 16):
+                for tokens in (16, 17, 32):
+                    ms_rope, ms_plain, ms_fwd, nbytes = mattn_bwd(b, tokens, 64, h, 1, rr)
+                    gbs = nbytes / ms_rope / 1e6
+                    print(f"mattn_bwd {name:2s} B={b:2d} L={tokens} E=64 h={h} rr={rr} ({b * rr:3d} workgroups): rope {ms_rope*1e3:8.1f} us ({gbs:6.1f} GB/s, "
+                          f"{gbs / 1e3 / HBM_TBS:.3f} of {HBM_TBS:.0f} TB/s HBM)  no table {ms_plain*1e3:8.1f} us  forward {ms_fwd*1e3:8.1f} us", flush=True)
+    if "facmat_train" in what:
+        depth = 28
+        for b in (8, 4, 2, 1):  # the largest of these batches that fits
+            try:
+                ms = facmat_train(b, depth=depth)
+            except (torch.cuda.OutOfMemoryError, capi.DfotError) as err:
+                print(f"facmat_train XL B={b}: does not fit ({type(err).__name__})", flush=True)
+                torch.cuda.empty_cache()
+                continue
+            ms_attn = mattn_bwd(b, 16, 64, 1152, 1, 16)[0]
+            print(f"facmat_train XL-64-1 B={b} x 16 frames x 256 patches: {ms:.2f} ms per training step; matrix attention backward {depth} x "
+                  f"{ms_attn*1e3:.1f} us = {depth * ms_attn / ms * 100:.1f} % of it", flush=True)
+            break
     if "equal" in what:
         # the conditioning of one window at model batch 2 and 8 (B, 8, 180, 256, 256 fp32), and a size that stays in the 256 MiB Infinity Cache
         for name, nbytes in {"cond Bm2": 2 * 8 * 180 * 256 * 256 * 4, "cond Bm8": 8 * 8 * 180 * 256 * 256 * 4, "64 MiB": 64 << 20}.items():
