@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "dfot_hip.h"
+#include "dit_model.h"
 #include "gemm.h"
 #include "kernels.h"
 
@@ -30,18 +31,12 @@ struct DitParam {
   bool loaded = false;
 };
 
-struct DitBlockW {
+struct DitBlockW {  // DiTBlock (attn.qkv / attn.proj) or MatrixDiTBlock (the attention factors); norm1, norm2 and the MLP are common
   bf16 *w_qkv = nullptr, *w_proj = nullptr, *w_fc1 = nullptr, *w_fc2 = nullptr;
   float *b_qkv = nullptr, *b_proj = nullptr, *b_fc1 = nullptr, *b_fc2 = nullptr;
   long mod1 = 0, mod2 = 0;  // column offsets of this block's (shift|scale|gate) triples inside a mod_table row
-};
-
-struct DitMatrixW {  // MatrixDiTBlock (temporal block of the factorized-matrix variant)
   bf16 *ut = nullptr, *vt = nullptr, *put = nullptr, *pvt = nullptr;  // qkv_u^T [E][P], qkv_v^T [3h][h], proj_u^T [P][E], proj_v^T [h][h]
   float *qkv_bias = nullptr, *proj_bias = nullptr;                      // [E][3h], [P][h]
-  bf16 *w_fc1 = nullptr, *w_fc2 = nullptr;
-  float *b_fc1 = nullptr, *b_fc2 = nullptr;
-  long mod1 = 0, mod2 = 0;
 };
 
 __device__ __forceinline__ float wave_sum(float v) {
@@ -687,16 +682,9 @@ int launch_final_layer(const float* x, const float* table, const int* levels, lo
 
 using namespace dfot;
 
-// the configuration a handle keeps: dfot_dit_config plus what dfot_dit_config_f adds to it
-struct DitCfg : dfot_dit_config {
-  int32_t fourier_noise = 0;
-};
-
-struct dfot_dit_s {
+struct dfot_dit_s : DitGeom {  // the geometry of cfg (dit_model.h): gh, gw, P, d, dstride, kpatch, oc, c_rows, ldt, mod_final
   DitCfg cfg{};
-  int gh = 0, gw = 0, P = 0, d = 0, dstride = 0, kpatch = 0, oc = 0;
   int lpad = 0;      // level count padded to the GEMM's row tile
-  long ldt = 0;      // mod_table row stride (floats) = total modulation outputs
   std::vector<DitParam> params;
   std::map<std::string, int> index;
   std::vector<void*> owned, ws_owned;
@@ -706,15 +694,13 @@ struct dfot_dit_s {
         *fin_w = nullptr, *fin_b = nullptr, *b_mod = nullptr;
   bf16* w_mod = nullptr;  // every modulation Linear stacked: [ldt][hidden]
   std::vector<DitBlockW> blocks;
-  std::vector<DitMatrixW> tblocks;  // variants 1 and 3: one MatrixDiTBlock after every spatial block
+  std::vector<DitBlockW> tblocks;   // variants 1 and 3: one MatrixDiTBlock after every spatial block
   std::vector<DitBlockW> fblocks;   // variant 2: one temporal DiTBlock after every spatial block
   float *diff_table = nullptr, *pos2d = nullptr, *tpos = nullptr;  // tpos: variant 2, temporal sinusoidal table [max_tokens][hidden]
   float* trope = nullptr;  // variant 3 with use_temporal_rope: (cos, sin) [max_tokens][hd/2][2] of the matrix attention's RoPE-1D
   float *c_w1 = nullptr, *c_b1 = nullptr, *c_w2 = nullptr, *c_b2 = nullptr, *c_table = nullptr;  // external condition embedding
   float *fz_freqs = nullptr, *fz_phases = nullptr;  // fourier_noise: the FourierEmbedding buffers [noise_dim]
-  int c_rows = 0;                    // label: rows of the embedding table (num_classes, + 1 null class with dropout)
   int mod_variant = GEMM_AUTO;       // GEMM tile form finalize() used for mod_table: the per-frame table uses the same one (bit-identical rows)
-  long mod_final = 0;
   // derived at finalize
   float *freqs = nullptr, *feat = nullptr, *thid = nullptr, *emb = nullptr, *mod_table = nullptr, *rope_cs = nullptr;
   bf16* semb = nullptr;
@@ -759,238 +745,126 @@ void dit_add(dfot_dit_s* h, const std::string& name, std::vector<int64_t> shape,
   h->params.push_back(DitParam{name, std::move(shape), std::move(load), false});
 }
 
-int dit_add_f32(dfot_dit_s* h, const std::string& name, std::vector<int64_t> shape, float** dst) {
-  size_t n = 1;
-  for (auto d : shape) n *= (size_t)d;
-  int rc = dit_alloc(h, dst, n);
+// the loaders of an inventory entry (dit_model.h): fp32 as given, at dst / in storage allocated here ...
+void dit_add_slice(dfot_dit_s* h, const DitTensor& t, float* dst) {
+  const size_t n = (size_t)t.numel();
+  dit_add(h, t.name, t.shape, [=](const float* src, hipStream_t s) {
+    DFOT_CHECK_HIP(hipMemcpyAsync(dst, src, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+    return DFOT_OK;
+  });
+}
+int dit_add_f32(dfot_dit_s* h, const DitTensor& t, float** dst) {
+  int rc = dit_alloc(h, dst, (size_t)t.numel());
+  if (!rc) dit_add_slice(h, t, *dst);
+  return rc;
+}
+
+// ... Linear weight [rows][k] fp32 -> bf16 at dst (row stride k) / in storage allocated here ...
+void dit_add_bf16(dfot_dit_s* h, const DitTensor& t, bf16* dst) {
+  const int rows = (int)t.shape[0], k = (int)t.shape[1];
+  dit_add(h, t.name, t.shape, [=](const float* src, hipStream_t s) { return launch_pack_rows(src, dst, nullptr, rows, k, k, k, 0, s); });
+}
+int dit_add_linear(dfot_dit_s* h, const DitTensor& t, bf16** dst) {
+  int rc = dit_alloc(h, dst, (size_t)t.numel());
+  if (!rc) dit_add_bf16(h, t, *dst);
+  return rc;
+}
+
+// ... dst[c][r] bf16 = src[r][c]: the matrix factors are stored (in, out); the GEMMs want [out][in]
+int dit_add_transposed(dfot_dit_s* h, const DitTensor& t, bf16** dst) {
+  int rc = dit_alloc(h, dst, (size_t)t.numel());
   if (rc) return rc;
-  float* d = *dst;
-  dit_add(h, name, shape, [d, n](const float* src, hipStream_t s) {
-    DFOT_CHECK_HIP(hipMemcpyAsync(d, src, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+  bf16* d = *dst;
+  const int rows = (int)t.shape[0], cols = (int)t.shape[1];
+  dit_add(h, t.name, t.shape, [=](const float* src, hipStream_t s) {
+    hipLaunchKernelGGL(pack_transpose_kernel, dim3(cdiv((long)rows * cols, 256)), dim3(256), 0, s, src, d, rows, cols);
+    DFOT_CHECK_HIP(hipGetLastError());
     return DFOT_OK;
   });
   return DFOT_OK;
 }
 
-// Linear weight [rows][k] fp32 -> bf16 at dst (row stride k)
-int dit_add_bf16(dfot_dit_s* h, const std::string& name, int rows, int k, bf16* dst) {
-  dit_add(h, name, {rows, k}, [=](const float* src, hipStream_t s) { return launch_pack_rows(src, dst, nullptr, rows, k, k, k, 0, s); });
-  return DFOT_OK;
-}
-
-int dit_add_slice(dfot_dit_s* h, const std::string& name, int n, float* dst) {
-  dit_add(h, name, {n}, [=](const float* src, hipStream_t s) {
-    DFOT_CHECK_HIP(hipMemcpyAsync(dst, src, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, s));
-    return DFOT_OK;
-  });
+int dit_upload(dfot_dit_s* h, float** dst, const std::vector<float>& table) {
+  int rc = dit_alloc(h, dst, table.size());
+  if (rc) return rc;
+  DFOT_CHECK_HIP(hipMemcpy(*dst, table.data(), table.size() * sizeof(float), hipMemcpyHostToDevice));
   return DFOT_OK;
 }
 
 int dit_build(dfot_dit_s* h) {
   const DitCfg& c = h->cfg;
+  static_cast<DitGeom&>(*h) = dit_geometry(c);
   const int hd = c.hidden_size;
-  h->gh = c.height / c.patch_size;
-  h->gw = c.width / c.patch_size;
-  h->P = h->gh * h->gw;
-  h->d = hd / c.num_heads;
-  h->dstride = attention_dstride(h->d);
-  h->kpatch = c.in_channels * c.patch_size * c.patch_size;
-  h->oc = h->kpatch;
   h->lpad = (c.timesteps + 255) / 256 * 256;
-  const bool diffm = c.variant == 1, facmat = c.variant == 1 || c.variant == 3, fac = c.variant == 2;  // diffm: the difference front end
-  const int E = c.embed_col_dim, P = h->P;
-  const int per_block = (c.mlp_hidden ? 6 * hd : 3 * hd) + (facmat || fac ? (c.temporal_mlp_hidden ? 6 * hd : 3 * hd) : 0);
-  h->ldt = (long)c.depth * per_block + 2 * hd;
   int rc = 0;
-  // registration order == the reference module's state_dict order
-  const std::string ne = "noise_level_pos_embedding.embedding";
-  if (c.fourier_noise) {  // FourierEmbedding's persistent buffers: state_dict lists noise_level_pos_embedding.timesteps before .embedding
-    if ((rc = dit_add_f32(h, "noise_level_pos_embedding.timesteps.freqs", {c.noise_dim}, &h->fz_freqs))) return rc;
-    if ((rc = dit_add_f32(h, "noise_level_pos_embedding.timesteps.phases", {c.noise_dim}, &h->fz_phases))) return rc;
-  }
-  if ((rc = dit_add_f32(h, ne + ".linear_1.weight", {hd, c.noise_dim}, &h->t_w1))) return rc;
-  if ((rc = dit_add_f32(h, ne + ".linear_1.bias", {hd}, &h->t_b1))) return rc;
-  if ((rc = dit_add_f32(h, ne + ".linear_2.weight", {hd, hd}, &h->t_w2))) return rc;
-  if ((rc = dit_add_f32(h, ne + ".linear_2.bias", {hd}, &h->t_b2))) return rc;
-  // BaseBackbone builds external_cond_embedding right after the noise-level embedding (base_backbone.py:35-62)
-  if (c.cond_type == DFOT_COND_ACTION) {
-    const std::string ce = std::string("external_cond_embedding") + (c.cond_dropout ? ".embedding" : "");
-    if ((rc = dit_add_f32(h, ce + ".linear_1.weight", {hd, c.cond_dim}, &h->c_w1))) return rc;
-    if ((rc = dit_add_f32(h, ce + ".linear_1.bias", {hd}, &h->c_b1))) return rc;
-    if ((rc = dit_add_f32(h, ce + ".linear_2.weight", {hd, hd}, &h->c_w2))) return rc;
-    if ((rc = dit_add_f32(h, ce + ".linear_2.bias", {hd}, &h->c_b2))) return rc;
-  } else if (c.cond_type == DFOT_COND_LABEL) {
-    h->c_rows = c.num_classes + (c.cond_dropout ? 1 : 0);
-    if ((rc = dit_add_f32(h, "external_cond_embedding.embedding_table.weight", {h->c_rows, hd}, &h->c_table))) return rc;
-  }
-  if ((rc = dit_add_f32(h, "patch_embedder.proj.weight", {hd, c.in_channels, c.patch_size, c.patch_size}, &h->pe_w))) return rc;
-  if ((rc = dit_add_f32(h, "patch_embedder.proj.bias", {hd}, &h->pe_b))) return rc;
-  if (diffm && (rc = dit_add_f32(h, "diff_embedder.embedding_table.weight", {2, hd}, &h->diff_table))) return rc;
-  if ((rc = dit_alloc(h, &h->w_mod, (size_t)h->ldt * hd))) return rc;
-  if ((rc = dit_alloc(h, &h->b_mod, (size_t)h->ldt))) return rc;
+  if ((rc = dit_alloc(h, &h->w_mod, (size_t)h->ldt * hd)) || (rc = dit_alloc(h, &h->b_mod, (size_t)h->ldt))) return rc;
   h->blocks.resize(c.depth);
-  if (fac) h->fblocks.resize(c.depth);
-  long off = 0;
-  // spatial blocks first, then (variant 2) the temporal DiTBlocks: same members, MLP width temporal_mlp_hidden
-  for (int bi = 0; bi < (fac ? 2 : 1) * c.depth; ++bi) {
-    const bool temporal = bi >= c.depth;
-    const int i = bi % c.depth, mlp_hidden = temporal ? c.temporal_mlp_hidden : c.mlp_hidden;
-    DitBlockW& w = temporal ? h->fblocks[i] : h->blocks[i];
-    const std::string pre = (temporal ? "dit_base.temporal_blocks." : "dit_base.blocks.") + std::to_string(i);
-    w.mod1 = off;
-    dit_add_bf16(h, pre + ".norm1.modulation.1.weight", 3 * hd, hd, h->w_mod + off * hd);
-    dit_add_slice(h, pre + ".norm1.modulation.1.bias", 3 * hd, h->b_mod + off);
-    off += 3 * hd;
-    if ((rc = dit_alloc(h, &w.w_qkv, (size_t)3 * hd * hd))) return rc;
-    dit_add_bf16(h, pre + ".attn.qkv.weight", 3 * hd, hd, w.w_qkv);
-    if ((rc = dit_add_f32(h, pre + ".attn.qkv.bias", {3 * hd}, &w.b_qkv))) return rc;
-    if ((rc = dit_alloc(h, &w.w_proj, (size_t)hd * hd))) return rc;
-    dit_add_bf16(h, pre + ".attn.proj.weight", hd, hd, w.w_proj);
-    if ((rc = dit_add_f32(h, pre + ".attn.proj.bias", {hd}, &w.b_proj))) return rc;
-    if (mlp_hidden) {
-      w.mod2 = off;
-      dit_add_bf16(h, pre + ".norm2.modulation.1.weight", 3 * hd, hd, h->w_mod + off * hd);
-      dit_add_slice(h, pre + ".norm2.modulation.1.bias", 3 * hd, h->b_mod + off);
-      off += 3 * hd;
-      if ((rc = dit_alloc(h, &w.w_fc1, (size_t)mlp_hidden * hd))) return rc;
-      dit_add_bf16(h, pre + ".mlp.fc1.weight", mlp_hidden, hd, w.w_fc1);
-      if ((rc = dit_add_f32(h, pre + ".mlp.fc1.bias", {mlp_hidden}, &w.b_fc1))) return rc;
-      if ((rc = dit_alloc(h, &w.w_fc2, (size_t)hd * mlp_hidden))) return rc;
-      dit_add_bf16(h, pre + ".mlp.fc2.weight", hd, mlp_hidden, w.w_fc2);
-      if ((rc = dit_add_f32(h, pre + ".mlp.fc2.bias", {hd}, &w.b_fc2))) return rc;
+  if (h->fac) h->fblocks.resize(c.depth);
+  if (h->facmat) h->tblocks.resize(c.depth);
+  // registration order == the inventory's == the reference module's state_dict order
+  for (const DitTensor& t : dit_inventory(c)) {
+    DitBlockW* w = t.block < 0 ? nullptr : &(!t.temporal ? h->blocks : h->fac ? h->fblocks : h->tblocks)[t.block];
+    if (t.col >= 0) {  // a modulation Linear: rows [col, col + out) of the stacked weight, the same columns of the stacked bias
+      if (t.kind == DIT_MOD1_W) w->mod1 = t.col;
+      if (t.kind == DIT_MOD2_W) w->mod2 = t.col;
+      if (t.shape.size() == 2) dit_add_bf16(h, t, h->w_mod + t.col * hd);
+      else dit_add_slice(h, t, h->b_mod + t.col);
+      continue;
     }
-  }
-  // dst[c][r] bf16 = src[r][c]: the matrix factors are stored (in, out); the GEMMs want [out][in]
-  auto add_transposed = [&](const std::string& name, int rows, int cols, bf16* dst) {
-    dit_add(h, name, {rows, cols}, [=](const float* src, hipStream_t s) {
-      hipLaunchKernelGGL(pack_transpose_kernel, dim3(cdiv((long)rows * cols, 256)), dim3(256), 0, s, src, dst, rows, cols);
-      DFOT_CHECK_HIP(hipGetLastError());
-      return DFOT_OK;
-    });
-  };
-  if (facmat) {
-    h->tblocks.resize(c.depth);
-    for (int i = 0; i < c.depth; ++i) {
-      DitMatrixW& w = h->tblocks[i];
-      const std::string pre = "dit_base.temporal_blocks." + std::to_string(i);
-      w.mod1 = off;
-      dit_add_bf16(h, pre + ".norm1.modulation.1.weight", 3 * hd, hd, h->w_mod + off * hd);
-      dit_add_slice(h, pre + ".norm1.modulation.1.bias", 3 * hd, h->b_mod + off);
-      off += 3 * hd;
-      if ((rc = dit_alloc(h, &w.ut, (size_t)E * P)) || (rc = dit_alloc(h, &w.put, (size_t)P * E)) ||
-          (rc = dit_alloc(h, &w.vt, (size_t)3 * hd * hd)) || (rc = dit_alloc(h, &w.pvt, (size_t)hd * hd)))
-        return rc;
-      add_transposed(pre + ".attn.qkv_u", P, E, w.ut);
-      add_transposed(pre + ".attn.proj_u", E, P, w.put);
-      add_transposed(pre + ".attn.qkv_v", hd, 3 * hd, w.vt);
-      add_transposed(pre + ".attn.proj_v", hd, hd, w.pvt);
-      if (c.use_bias) {
-        if ((rc = dit_add_f32(h, pre + ".attn.qkv_bias", {E, 3 * hd}, &w.qkv_bias))) return rc;
-        if ((rc = dit_add_f32(h, pre + ".attn.proj_bias", {P, hd}, &w.proj_bias))) return rc;
-      }
-      if (c.temporal_mlp_hidden) {
-        const int th = c.temporal_mlp_hidden;
-        w.mod2 = off;
-        dit_add_bf16(h, pre + ".norm2.modulation.1.weight", 3 * hd, hd, h->w_mod + off * hd);
-        dit_add_slice(h, pre + ".norm2.modulation.1.bias", 3 * hd, h->b_mod + off);
-        off += 3 * hd;
-        if ((rc = dit_alloc(h, &w.w_fc1, (size_t)th * hd))) return rc;
-        dit_add_bf16(h, pre + ".mlp.fc1.weight", th, hd, w.w_fc1);
-        if ((rc = dit_add_f32(h, pre + ".mlp.fc1.bias", {th}, &w.b_fc1))) return rc;
-        if ((rc = dit_alloc(h, &w.w_fc2, (size_t)hd * th))) return rc;
-        dit_add_bf16(h, pre + ".mlp.fc2.weight", hd, th, w.w_fc2);
-        if ((rc = dit_add_f32(h, pre + ".mlp.fc2.bias", {hd}, &w.b_fc2))) return rc;
-      }
+    switch (t.kind) {
+      case DIT_FZ_FREQS: rc = dit_add_f32(h, t, &h->fz_freqs); break;
+      case DIT_FZ_PHASES: rc = dit_add_f32(h, t, &h->fz_phases); break;
+      case DIT_T_W1: rc = dit_add_f32(h, t, &h->t_w1); break;
+      case DIT_T_B1: rc = dit_add_f32(h, t, &h->t_b1); break;
+      case DIT_T_W2: rc = dit_add_f32(h, t, &h->t_w2); break;
+      case DIT_T_B2: rc = dit_add_f32(h, t, &h->t_b2); break;
+      case DIT_C_W1: rc = dit_add_f32(h, t, &h->c_w1); break;
+      case DIT_C_B1: rc = dit_add_f32(h, t, &h->c_b1); break;
+      case DIT_C_W2: rc = dit_add_f32(h, t, &h->c_w2); break;
+      case DIT_C_B2: rc = dit_add_f32(h, t, &h->c_b2); break;
+      case DIT_C_TABLE: rc = dit_add_f32(h, t, &h->c_table); break;
+      case DIT_PE_W: rc = dit_add_f32(h, t, &h->pe_w); break;
+      case DIT_PE_B: rc = dit_add_f32(h, t, &h->pe_b); break;
+      case DIT_DIFF: rc = dit_add_f32(h, t, &h->diff_table); break;
+      case DIT_QKV_W: rc = dit_add_linear(h, t, &w->w_qkv); break;
+      case DIT_QKV_B: rc = dit_add_f32(h, t, &w->b_qkv); break;
+      case DIT_PROJ_W: rc = dit_add_linear(h, t, &w->w_proj); break;
+      case DIT_PROJ_B: rc = dit_add_f32(h, t, &w->b_proj); break;
+      case DIT_QKV_U: rc = dit_add_transposed(h, t, &w->ut); break;
+      case DIT_PROJ_U: rc = dit_add_transposed(h, t, &w->put); break;
+      case DIT_QKV_V: rc = dit_add_transposed(h, t, &w->vt); break;
+      case DIT_PROJ_V: rc = dit_add_transposed(h, t, &w->pvt); break;
+      case DIT_QKV_BIAS: rc = dit_add_f32(h, t, &w->qkv_bias); break;
+      case DIT_PROJ_BIAS: rc = dit_add_f32(h, t, &w->proj_bias); break;
+      case DIT_FC1_W: rc = dit_add_linear(h, t, &w->w_fc1); break;
+      case DIT_FC1_B: rc = dit_add_f32(h, t, &w->b_fc1); break;
+      case DIT_FC2_W: rc = dit_add_linear(h, t, &w->w_fc2); break;
+      case DIT_FC2_B: rc = dit_add_f32(h, t, &w->b_fc2); break;
+      case DIT_FIN_W: rc = dit_add_f32(h, t, &h->fin_w); break;
+      case DIT_FIN_B: rc = dit_add_f32(h, t, &h->fin_b); break;
+      default: break;  // the modulation kinds: bound above by their column
     }
+    if (rc) return rc;
   }
-  h->mod_final = off;
-  dit_add_bf16(h, "dit_base.final_layer.norm_final.modulation.1.weight", 2 * hd, hd, h->w_mod + off * hd);
-  dit_add_slice(h, "dit_base.final_layer.norm_final.modulation.1.bias", 2 * hd, h->b_mod + off);
-  if ((rc = dit_add_f32(h, "dit_base.final_layer.linear.weight", {h->oc, hd}, &h->fin_w))) return rc;
-  if ((rc = dit_add_f32(h, "dit_base.final_layer.linear.bias", {h->oc}, &h->fin_b))) return rc;
 
   // derived tables (a fourier_noise model has no finite set of levels: nothing is tabulated, the embedding runs per frame in forward)
   if (!c.fourier_noise) {
-    if ((rc = dit_alloc(h, &h->freqs, (size_t)c.noise_dim / 2))) return rc;
+    if ((rc = dit_upload(h, &h->freqs, dit_timestep_freqs(c)))) return rc;
     if ((rc = dit_alloc(h, &h->feat, (size_t)h->lpad * c.noise_dim))) return rc;
     if ((rc = dit_alloc(h, &h->thid, (size_t)h->lpad * hd))) return rc;
     if ((rc = dit_alloc(h, &h->emb, (size_t)h->lpad * hd))) return rc;
-    const int nflag = diffm ? 2 : 1;  // variant 1: the conditioning also depends on the token kind (difference / frame)
+    const int nflag = h->diffm ? 2 : 1;  // variant 1: the conditioning also depends on the token kind (difference / frame)
     if ((rc = dit_alloc(h, &h->semb, (size_t)nflag * h->lpad * hd))) return rc;
     if ((rc = dit_alloc(h, &h->mod_table, (size_t)nflag * h->lpad * h->ldt))) return rc;
-    {
-      const int half = c.noise_dim / 2;
-      std::vector<float> f(half);
-      for (int i = 0; i < half; ++i) f[i] = (float)std::exp(-std::log(10000.0) * (double)i / (double)half);
-      DFOT_CHECK_HIP(hipMemcpy(h->freqs, f.data(), f.size() * sizeof(float), hipMemcpyHostToDevice));
-    }
   }
-  if (facmat || fac) {
-    // sinusoidal_2d table [P][hidden] (get_nd_sincos_pos_embed, dit_base.py:527-572): np.meshgrid's default "xy" indexing
-    // makes flattened entry m use position m % gh for the first half of the channels and m / gh for the second; each half
-    // is [sin | cos] of pos * 10000^(-i/(half/2)), computed in float64 like numpy
-    const int half = hd / 2, quarter = half / 2;
-    std::vector<float> pe((size_t)P * hd);
-    for (int m = 0; m < P; ++m) {
-      const int pos[2] = {m % h->gh, m / h->gh};
-      for (int a = 0; a < 2; ++a)
-        for (int i = 0; i < quarter; ++i) {
-          const double ang = (double)pos[a] / std::pow(10000.0, (double)i / (double)quarter);
-          pe[(size_t)m * hd + a * half + i] = (float)std::sin(ang);
-          pe[(size_t)m * hd + a * half + quarter + i] = (float)std::cos(ang);
-        }
-    }
-    if ((rc = dit_alloc(h, &h->pos2d, pe.size()))) return rc;
-    DFOT_CHECK_HIP(hipMemcpy(h->pos2d, pe.data(), pe.size() * sizeof(float), hipMemcpyHostToDevice));
-    if (fac) {
-      // temporal table [max_tokens][hidden] (SinusoidalPositionalEmbedding of the 1-D shape (max_tokens,), dit_base.py:268-271,552-572):
-      // [sin | cos] of t * 10000^(-i/(hidden/2)), in float64 like numpy
-      std::vector<float> te((size_t)c.max_tokens * hd);
-      for (int t = 0; t < c.max_tokens; ++t)
-        for (int i = 0; i < half; ++i) {
-          const double ang = (double)t / std::pow(10000.0, (double)i / (double)half);
-          te[(size_t)t * hd + i] = (float)std::sin(ang);
-          te[(size_t)t * hd + half + i] = (float)std::cos(ang);
-        }
-      if ((rc = dit_alloc(h, &h->tpos, te.size()))) return rc;
-      DFOT_CHECK_HIP(hipMemcpy(h->tpos, te.data(), te.size() * sizeof(float), hipMemcpyHostToDevice));
-    }
-    if (c.variant == 3 && c.use_temporal_rope) {
-      // RotaryEmbedding1D(dim = embed_row_dim / num_row_heads, seq_len = max_tokens) (dit_base.py:297-306; embeddings.py:193-202):
-      // angle = frame * theta^(-2i/dim) for the pair i of every matrix row, in float64
-      const int dim = hd / c.num_row_heads, pairs = dim / 2;
-      std::vector<float> cs((size_t)c.max_tokens * pairs * 2);
-      for (int t = 0; t < c.max_tokens; ++t)
-        for (int i = 0; i < pairs; ++i) {
-          const double ang = (double)t * std::pow((double)c.rope_theta, -2.0 * (double)i / (double)dim);
-          cs[((size_t)t * pairs + i) * 2 + 0] = (float)std::cos(ang);
-          cs[((size_t)t * pairs + i) * 2 + 1] = (float)std::sin(ang);
-        }
-      if ((rc = dit_alloc(h, &h->trope, cs.size()))) return rc;
-      DFOT_CHECK_HIP(hipMemcpy(h->trope, cs.data(), cs.size() * sizeof(float), hipMemcpyHostToDevice));
-    }
-  } else {  // RoPE-3D (cos, sin) table [Tmax*P][d/2][2]; axis split of the head dim as RotaryEmbedding3D (embeddings.py:251-277)
-    const int half = h->d / 2, q = half / 3, rem = half % 3;
-    int parts[3] = {q, q, q};
-    if (rem == 1) parts[0] = q + 1;
-    if (rem == 2) parts[1] = parts[2] = q + 1;
-    const int n = c.max_tokens * h->P;
-    std::vector<float> cs((size_t)n * half * 2);
-    for (int tok = 0; tok < n; ++tok) {
-      const int pos[3] = {tok / h->P, (tok / h->gw) % h->gh, tok % h->gw};
-      int pair = 0;
-      for (int ax = 0; ax < 3; ++ax) {
-        const int dim = 2 * parts[ax];
-        for (int j = 0; j < parts[ax]; ++j, ++pair) {
-          const float inv = 1.0f / powf(c.rope_theta, (float)(2 * j) / (float)dim);
-          const float ang = (float)pos[ax] * inv;
-          cs[((size_t)tok * half + pair) * 2 + 0] = cosf(ang);
-          cs[((size_t)tok * half + pair) * 2 + 1] = sinf(ang);
-        }
-      }
-    }
-    if ((rc = dit_alloc(h, &h->rope_cs, cs.size()))) return rc;
-    DFOT_CHECK_HIP(hipMemcpy(h->rope_cs, cs.data(), cs.size() * sizeof(float), hipMemcpyHostToDevice));
+  // positional tables (dit_model.h): sinusoidal_2d at the patch embedding of the factorized variants (+ the temporal table of variant 2,
+  // the RoPE-1D of variant 3's matrix attention), RoPE-3D of the full-attention variant
+  if (h->facmat || h->fac) {
+    if ((rc = dit_upload(h, &h->pos2d, dit_sinusoidal_2d(c, *h)))) return rc;
+    if (h->fac && (rc = dit_upload(h, &h->tpos, dit_sinusoidal_1d(c)))) return rc;
+    if (c.variant == 3 && c.use_temporal_rope && (rc = dit_upload(h, &h->trope, dit_rope_1d(c)))) return rc;
+  } else if ((rc = dit_upload(h, &h->rope_cs, dit_rope_3d(c, *h)))) {
+    return rc;
   }
   return DFOT_OK;
 }
@@ -1033,7 +907,7 @@ static int dit_create_impl(const DitCfg& c, dfot_dit_t* out) {
     DFOT_REQUIRE(c.temporal_mlp_hidden >= 0 && c.temporal_mlp_hidden % 64 == 0, DFOT_ERR_SHAPE, "temporal_mlp_hidden %d must be a multiple of 64",
                  c.temporal_mlp_hidden);
   }
-  if (c.variant == 1) {
+  if (c.variant == 1 || c.variant == 3) {  // the models with matrix blocks
     const int P = (c.height / c.patch_size) * (c.width / c.patch_size);
     DFOT_REQUIRE(P % 128 == 0, DFOT_ERR_SHAPE, "factorized matrix variant: %d patches per frame must be a multiple of 128", P);
     DFOT_REQUIRE(c.embed_col_dim > 0 && c.embed_col_dim % 64 == 0, DFOT_ERR_SHAPE, "embed_col_dim %d must be a multiple of 64", c.embed_col_dim);
@@ -1041,22 +915,12 @@ static int dit_create_impl(const DitCfg& c, dfot_dit_t* out) {
                      c.hidden_size % c.num_row_heads == 0 && (c.hidden_size / c.num_row_heads) % 4 == 0,
                  DFOT_ERR_SHAPE, "matrix attention heads (%d col, %d row) do not divide (%d, %d)", c.num_col_heads, c.num_row_heads,
                  c.embed_col_dim, c.hidden_size);
-    DFOT_REQUIRE(c.max_tokens % 2 == 0 && c.max_tokens <= 32, DFOT_ERR_SHAPE, "max_tokens %d must be even (difference, frame pairs) and <= 32", c.max_tokens);
-    DFOT_REQUIRE(c.temporal_mlp_hidden >= 0 && c.temporal_mlp_hidden % 64 == 0 && c.hidden_size % 4 == 0 && (c.hidden_size / 2) % 2 == 0,
-                 DFOT_ERR_SHAPE, "temporal_mlp_hidden %d must be a multiple of 64", c.temporal_mlp_hidden);
-  }
-  if (c.variant == 3) {
-    const int P = (c.height / c.patch_size) * (c.width / c.patch_size);
-    DFOT_REQUIRE(P % 128 == 0, DFOT_ERR_SHAPE, "factorized matrix variant: %d patches per frame must be a multiple of 128", P);
-    DFOT_REQUIRE(c.embed_col_dim > 0 && c.embed_col_dim % 64 == 0, DFOT_ERR_SHAPE, "embed_col_dim %d must be a multiple of 64", c.embed_col_dim);
-    DFOT_REQUIRE(c.num_col_heads > 0 && c.embed_col_dim % c.num_col_heads == 0 && c.num_row_heads > 0 &&
-                     c.hidden_size % c.num_row_heads == 0 && (c.hidden_size / c.num_row_heads) % 4 == 0,
-                 DFOT_ERR_SHAPE, "matrix attention heads (%d col, %d row) do not divide (%d, %d)", c.num_col_heads, c.num_row_heads,
-                 c.embed_col_dim, c.hidden_size);
-    DFOT_REQUIRE(c.max_tokens <= 32, DFOT_ERR_SHAPE, "factorized matrix variant: max_tokens %d exceeds 32", c.max_tokens);
+    DFOT_REQUIRE(c.variant != 1 || (c.max_tokens % 2 == 0 && c.max_tokens <= 32), DFOT_ERR_SHAPE,
+                 "max_tokens %d must be even (difference, frame pairs) and <= 32", c.max_tokens);
+    DFOT_REQUIRE(c.variant != 3 || c.max_tokens <= 32, DFOT_ERR_SHAPE, "factorized matrix variant: max_tokens %d exceeds 32", c.max_tokens);
     DFOT_REQUIRE(c.temporal_mlp_hidden >= 0 && c.temporal_mlp_hidden % 64 == 0, DFOT_ERR_SHAPE, "temporal_mlp_hidden %d must be a multiple of 64",
                  c.temporal_mlp_hidden);
-    DFOT_REQUIRE(c.rope_theta > 0.f || !c.use_temporal_rope, DFOT_ERR_ARG, "rope_theta %g must be positive", (double)c.rope_theta);
+    DFOT_REQUIRE(c.variant != 3 || c.rope_theta > 0.f || !c.use_temporal_rope, DFOT_ERR_ARG, "rope_theta %g must be positive", (double)c.rope_theta);
   }
   DFOT_REQUIRE(c.cond_type == DFOT_COND_NONE || c.cond_type == DFOT_COND_ACTION || c.cond_type == DFOT_COND_LABEL, DFOT_ERR_ARG,
                "cond_type %d unknown (0 = none, 1 = action, 2 = label)", c.cond_type);
@@ -1076,17 +940,12 @@ static int dit_create_impl(const DitCfg& c, dfot_dit_t* out) {
 
 int dfot_dit_create(const dfot_dit_config* cfg, dfot_dit_t* out) {
   DFOT_REQUIRE(cfg && out, DFOT_ERR_ARG, "dfot_dit_create: null argument");
-  DitCfg c;
-  static_cast<dfot_dit_config&>(c) = *cfg;
-  return dit_create_impl(c, out);
+  return dit_create_impl(dit_cfg(*cfg), out);
 }
 
 int dfot_dit_create_f(const dfot_dit_config_f* cfg, dfot_dit_t* out) {
   DFOT_REQUIRE(cfg && out, DFOT_ERR_ARG, "dfot_dit_create_f: null argument");
-  DitCfg c;
-  static_cast<dfot_dit_config&>(c) = cfg->base;
-  c.fourier_noise = cfg->fourier_noise;
-  return dit_create_impl(c, out);
+  return dit_create_impl(dit_cfg(cfg->base, cfg->fourier_noise), out);
 }
 
 int dfot_dit_num_params(dfot_dit_t h) { return h ? (int)h->params.size() : 0; }
@@ -1382,7 +1241,7 @@ static int dit_forward_impl(dfot_dit_t h, const float* x, const int32_t* noise_l
     if (!facmat) continue;
 
     // ---- MatrixDiTBlock: every frame is one token; qkv = U^T m V + bias, o = softmax(q k^T) v, out = U'^T o V' + bias' ----
-    const DitMatrixW& t = h->tblocks[bi];
+    const DitBlockW& t = h->tblocks[bi];
     if ((rc = ln_mod(t.mod1))) return rc;
     if ((rc = transpose(h->A, h->T1, P, hd))) return rc;  // m^T per frame: [hd][P]
     {

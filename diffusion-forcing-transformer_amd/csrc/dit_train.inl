@@ -752,18 +752,14 @@ int launch_ln_bwd_rows(const float* dm, const float* x, const float* table, long
 }  // namespace
 }  // namespace dfot
 
-struct dfot_dit_train_s {
+struct dfot_dit_train_s : dfot::DitGeom {  // the geometry of cfg (dit_model.h): gh, gw, P, d, dstride, kpatch, oc, c_rows, ldt, mod_final
   DitCfg cfg{};
-  int gh = 0, gw = 0, P = 0, d = 0, dstride = 0, kpatch = 0, oc = 0;
-  long ldt = 0, total = 0;
-  std::vector<dfot::DitParam> params;   // name / shape (load unused)
-  std::vector<long> offsets;
+  long total = 0;
+  std::vector<dfot::DitTensor> params;  // the inventory's parameters (dit_model.h), offsets into the flat buffers set
   float *params_f32 = nullptr, *grads = nullptr;  // attached flat buffers (owned by the caller)
   long o_t_w1 = 0, o_t_b1 = 0, o_t_w2 = 0, o_t_b2 = 0, o_pe_w = 0, o_pe_b = 0, o_diff = -1, o_fmod_w = 0, o_fmod_b = 0, o_fin_w = 0, o_fin_b = 0;
-  long mod_final = 0;
   // external condition embedding (registered after the noise-level embedding, as the reference module)
   long o_c_w1 = -1, o_c_b1 = -1, o_c_w2 = -1, o_c_b2 = -1, o_c_table = -1;
-  int c_rows = 0;
   bool cond_active = false, cond_masked = false;  // the last forward had a condition / a dropout mask
   float *c_in = nullptr, *c_h1 = nullptr, *c_a1 = nullptr, *c_dce = nullptr, *c_da1 = nullptr, *c_dh1 = nullptr;
   int* c_labels = nullptr;
@@ -811,19 +807,6 @@ int tr_alloc(dfot_dit_train_s* h, T** out, size_t count, bool workspace = false)
   if (workspace) h->ws_bytes += count * sizeof(T);
   *out = (T*)p;
   return DFOT_OK;
-}
-
-long tr_add(dfot_dit_train_s* h, const std::string& name, std::vector<int64_t> shape) {
-  DitParam p;
-  p.name = name;
-  p.shape = shape;
-  long n = 1;
-  for (int64_t v : shape) n *= v;
-  const long off = h->total;
-  h->params.push_back(p);
-  h->offsets.push_back(off);
-  h->total += (n + 3) / 4 * 4;  // every tensor starts 16-byte aligned
-  return off;
 }
 
 // [batches][R][C] -> [batches][C][R]
@@ -943,7 +926,7 @@ static int dit_train_create_impl(const DitCfg& c, dfot_dit_train_t* out, bool fa
   DFOT_REQUIRE(c.variant != 3 || facmat_entry, DFOT_ERR_ARG,
                "train_create: variant 3 (factorized matrix DiT3D, FacMatDiT) is not built here; its trainer is dfot_facmat_train_create");
   DFOT_REQUIRE(c.variant == 0 || c.variant == 1 || c.variant == 3, DFOT_ERR_ARG, "train_create: unknown variant %d", c.variant);
-  const bool diffm = c.variant == 1, facmat = c.variant == 1 || c.variant == 3;  // diffm: the difference front end
+  const bool facmat = c.variant == 1 || c.variant == 3;
   DFOT_REQUIRE(c.variant != 3 || !c.use_temporal_rope || c.rope_theta > 0.f, DFOT_ERR_ARG, "train_create: rope_theta %g must be positive",
                (double)c.rope_theta);
   DFOT_REQUIRE(c.mlp_hidden >= 0 && c.mlp_hidden % 128 == 0 && c.temporal_mlp_hidden >= 0 && c.temporal_mlp_hidden % 128 == 0, DFOT_ERR_ARG,
@@ -965,99 +948,76 @@ static int dit_train_create_impl(const DitCfg& c, dfot_dit_train_t* out, bool fa
                DFOT_ERR_ARG, "train_create: external condition type %d / cond_dim %d / num_classes %d", c.cond_type, c.cond_dim, c.num_classes);
   auto* h = new dfot_dit_train_s();
   h->cfg = c;
-  const int hd = c.hidden_size;
-  h->gh = c.height / c.patch_size;
-  h->gw = c.width / c.patch_size;
-  h->P = h->gh * h->gw;
-  h->d = hd / c.num_heads;
-  h->dstride = attention_dstride(h->d);
-  h->kpatch = c.in_channels * c.patch_size * c.patch_size;
-  h->oc = h->kpatch;
-  const int mh = c.mlp_hidden, th = facmat ? c.temporal_mlp_hidden : 0, E = c.embed_col_dim, P = h->P;
-  h->ldt = (long)c.depth * ((mh ? 6 : 3) + (facmat ? (th ? 6 : 3) : 0)) * hd + 2 * hd;
+  static_cast<DitGeom&>(*h) = dit_geometry(c);
+  const int hd = c.hidden_size, E = c.embed_col_dim, P = h->P;
   if (h->P % TR_CHUNKS != 0 || (facmat && h->P % 128 != 0)) {
     set_error("train_create: %d patches per frame must be a multiple of %d", h->P, facmat ? 128 : TR_CHUNKS);
     delete h;
     return DFOT_ERR_ARG;
   }
-  // registration order == the reference module's state_dict order (as dit_build): all spatial blocks, then all temporal blocks
-  const std::string ne = "noise_level_pos_embedding.embedding";
-  h->o_t_w1 = tr_add(h, ne + ".linear_1.weight", {hd, c.noise_dim});
-  h->o_t_b1 = tr_add(h, ne + ".linear_1.bias", {hd});
-  h->o_t_w2 = tr_add(h, ne + ".linear_2.weight", {hd, hd});
-  h->o_t_b2 = tr_add(h, ne + ".linear_2.bias", {hd});
-  if (c.cond_type == DFOT_COND_ACTION) {
-    const std::string ce = std::string("external_cond_embedding") + (c.cond_dropout ? ".embedding" : "");
-    h->o_c_w1 = tr_add(h, ce + ".linear_1.weight", {hd, c.cond_dim});
-    h->o_c_b1 = tr_add(h, ce + ".linear_1.bias", {hd});
-    h->o_c_w2 = tr_add(h, ce + ".linear_2.weight", {hd, hd});
-    h->o_c_b2 = tr_add(h, ce + ".linear_2.bias", {hd});
-  } else if (c.cond_type == DFOT_COND_LABEL) {
-    h->c_rows = c.num_classes + (c.cond_dropout ? 1 : 0);
-    h->o_c_table = tr_add(h, "external_cond_embedding.embedding_table.weight", {h->c_rows, hd});
-  }
-  h->o_pe_w = tr_add(h, "patch_embedder.proj.weight", {hd, c.in_channels, c.patch_size, c.patch_size});
-  h->o_pe_b = tr_add(h, "patch_embedder.proj.bias", {hd});
-  if (diffm) h->o_diff = tr_add(h, "diff_embedder.embedding_table.weight", {2, hd});
+  // the flat buffers hold the inventory's parameters (dit_model.h) in its order, the reference module's; the Fourier buffers stay outside
+  std::vector<DitTensor> inv = dit_inventory(c);
+  h->total = dit_flat_layout(inv);
   std::vector<TrainBlock> spatial(c.depth), temporal(facmat ? c.depth : 0);
-  long off = 0;
-  auto add_mlp = [&](TrainBlock& b, const std::string& pre, int width) {
-    b.mh = width;
-    if (!width) return;
-    b.mod2 = off;
-    off += 3 * hd;
-    b.o_mod2_w = tr_add(h, pre + ".norm2.modulation.1.weight", {3 * hd, hd});
-    b.o_mod2_b = tr_add(h, pre + ".norm2.modulation.1.bias", {3 * hd});
-    b.o_fc1_w = tr_add(h, pre + ".mlp.fc1.weight", {width, hd});
-    b.o_fc1_b = tr_add(h, pre + ".mlp.fc1.bias", {width});
-    b.o_fc2_w = tr_add(h, pre + ".mlp.fc2.weight", {hd, width});
-    b.o_fc2_b = tr_add(h, pre + ".mlp.fc2.bias", {hd});
-  };
-  for (int i = 0; i < c.depth; ++i) {
-    TrainBlock& b = spatial[i];
-    const std::string pre = "dit_base.blocks." + std::to_string(i);
-    b.mod = off;
-    off += 3 * hd;
-    b.o_mod_w = tr_add(h, pre + ".norm1.modulation.1.weight", {3 * hd, hd});
-    b.o_mod_b = tr_add(h, pre + ".norm1.modulation.1.bias", {3 * hd});
-    b.o_qkv_w = tr_add(h, pre + ".attn.qkv.weight", {3 * hd, hd});
-    b.o_qkv_b = tr_add(h, pre + ".attn.qkv.bias", {3 * hd});
-    b.o_proj_w = tr_add(h, pre + ".attn.proj.weight", {hd, hd});
-    b.o_proj_b = tr_add(h, pre + ".attn.proj.bias", {hd});
-    add_mlp(b, pre, mh);
-  }
-  for (int i = 0; i < (int)temporal.size(); ++i) {
-    TrainBlock& b = temporal[i];
-    b.matrix = true;
-    const std::string pre = "dit_base.temporal_blocks." + std::to_string(i);
-    b.mod = off;
-    off += 3 * hd;
-    b.o_mod_w = tr_add(h, pre + ".norm1.modulation.1.weight", {3 * hd, hd});
-    b.o_mod_b = tr_add(h, pre + ".norm1.modulation.1.bias", {3 * hd});
-    b.o_qkv_u = tr_add(h, pre + ".attn.qkv_u", {P, E});
-    b.o_proj_u = tr_add(h, pre + ".attn.proj_u", {E, P});
-    b.o_qkv_v = tr_add(h, pre + ".attn.qkv_v", {hd, 3 * hd});
-    b.o_proj_v = tr_add(h, pre + ".attn.proj_v", {hd, hd});
-    if (c.use_bias) {
-      b.o_qkv_bias = tr_add(h, pre + ".attn.qkv_bias", {E, 3 * hd});
-      b.o_proj_bias = tr_add(h, pre + ".attn.proj_bias", {P, hd});
+  for (TrainBlock& b : spatial) b.mh = c.mlp_hidden;
+  for (TrainBlock& b : temporal) b.matrix = true, b.mh = c.temporal_mlp_hidden;
+  for (const DitTensor& t : inv) {
+    if (t.buffer) continue;
+    h->params.push_back(t);
+    TrainBlock* b = t.block < 0 ? nullptr : &(t.temporal ? temporal : spatial)[t.block];
+    const long o = t.offset;
+    switch (t.kind) {
+      case DIT_T_W1: h->o_t_w1 = o; break;
+      case DIT_T_B1: h->o_t_b1 = o; break;
+      case DIT_T_W2: h->o_t_w2 = o; break;
+      case DIT_T_B2: h->o_t_b2 = o; break;
+      case DIT_C_W1: h->o_c_w1 = o; break;
+      case DIT_C_B1: h->o_c_b1 = o; break;
+      case DIT_C_W2: h->o_c_w2 = o; break;
+      case DIT_C_B2: h->o_c_b2 = o; break;
+      case DIT_C_TABLE: h->o_c_table = o; break;
+      case DIT_PE_W: h->o_pe_w = o; break;
+      case DIT_PE_B: h->o_pe_b = o; break;
+      case DIT_DIFF: h->o_diff = o; break;
+      case DIT_MOD1_W: b->o_mod_w = o, b->mod = t.col; break;
+      case DIT_MOD1_B: b->o_mod_b = o; break;
+      case DIT_QKV_W: b->o_qkv_w = o; break;
+      case DIT_QKV_B: b->o_qkv_b = o; break;
+      case DIT_PROJ_W: b->o_proj_w = o; break;
+      case DIT_PROJ_B: b->o_proj_b = o; break;
+      case DIT_QKV_U: b->o_qkv_u = o; break;
+      case DIT_PROJ_U: b->o_proj_u = o; break;
+      case DIT_QKV_V: b->o_qkv_v = o; break;
+      case DIT_PROJ_V: b->o_proj_v = o; break;
+      case DIT_QKV_BIAS: b->o_qkv_bias = o; break;
+      case DIT_PROJ_BIAS: b->o_proj_bias = o; break;
+      case DIT_MOD2_W: b->o_mod2_w = o, b->mod2 = t.col; break;
+      case DIT_MOD2_B: b->o_mod2_b = o; break;
+      case DIT_FC1_W: b->o_fc1_w = o; break;
+      case DIT_FC1_B: b->o_fc1_b = o; break;
+      case DIT_FC2_W: b->o_fc2_w = o; break;
+      case DIT_FC2_B: b->o_fc2_b = o; break;
+      case DIT_FMOD_W: h->o_fmod_w = o; break;
+      case DIT_FMOD_B: h->o_fmod_b = o; break;
+      case DIT_FIN_W: h->o_fin_w = o; break;
+      case DIT_FIN_B: h->o_fin_b = o; break;
+      default: break;  // the Fourier buffers: skipped above
     }
-    add_mlp(b, pre, th);
   }
-  for (int i = 0; i < c.depth; ++i) {
+  for (int i = 0; i < c.depth; ++i) {  // execution order
     h->blocks.push_back(spatial[i]);
     if (facmat) h->blocks.push_back(temporal[i]);
   }
-  h->mod_final = off;
-  h->o_fmod_w = tr_add(h, "dit_base.final_layer.norm_final.modulation.1.weight", {2 * hd, hd});
-  h->o_fmod_b = tr_add(h, "dit_base.final_layer.norm_final.modulation.1.bias", {2 * hd});
-  h->o_fin_w = tr_add(h, "dit_base.final_layer.linear.weight", {h->oc, hd});
-  h->o_fin_b = tr_add(h, "dit_base.final_layer.linear.bias", {h->oc});
   int rc = 0;
   auto fail = [&](int code) { dfot_dit_train_destroy(h); return code; };
+  auto upload = [&](float** dst, const std::vector<float>& table) {  // a host table of dit_model.h
+    int r = tr_alloc(h, dst, table.size());
+    if (r) return r;
+    return hipMemcpy(*dst, table.data(), table.size() * sizeof(float), hipMemcpyHostToDevice) == hipSuccess ? (int)DFOT_OK : (int)DFOT_ERR_HIP;
+  };
   if ((rc = tr_alloc(h, &h->w_mod, (size_t)h->ldt * hd)) || (rc = tr_alloc(h, &h->w_modT, (size_t)h->ldt * hd)) ||
       (rc = tr_alloc(h, &h->b_mod, (size_t)h->ldt)) || (rc = tr_alloc(h, &h->wfT, (size_t)hd * 64)) ||
-      (rc = tr_alloc(h, &h->freqs, (size_t)c.noise_dim / 2)))
+      (rc = upload(&h->freqs, dit_timestep_freqs(c))))
     return fail(rc);
   if (c.fourier_noise && ((rc = tr_alloc(h, &h->fz_freqs, (size_t)c.noise_dim)) || (rc = tr_alloc(h, &h->fz_phases, (size_t)c.noise_dim)))) return fail(rc);
   for (TrainBlock& b : h->blocks) {
@@ -1075,60 +1035,11 @@ static int dit_train_create_impl(const DitCfg& c, dfot_dit_train_t* out, bool fa
                  (rc = tr_alloc(h, &b.w_fc2, (size_t)b.mh * hd)) || (rc = tr_alloc(h, &b.w_fc2T, (size_t)b.mh * hd))))
       return fail(rc);
   }
-  {
-    const int half = c.noise_dim / 2;
-    std::vector<float> f(half);
-    for (int i = 0; i < half; ++i) f[i] = (float)std::exp(-std::log(10000.0) * (double)i / (double)half);
-    if (hipMemcpy(h->freqs, f.data(), f.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return fail(DFOT_ERR_HIP);
-  }
-  if (facmat) {  // sinusoidal_2d table, as dit_build
-    const int half = hd / 2, quarter = half / 2;
-    std::vector<float> pe((size_t)P * hd);
-    for (int m = 0; m < P; ++m) {
-      const int pos[2] = {m % h->gh, m / h->gh};
-      for (int a = 0; a < 2; ++a)
-        for (int i = 0; i < quarter; ++i) {
-          const double ang = (double)pos[a] / std::pow(10000.0, (double)i / (double)quarter);
-          pe[(size_t)m * hd + a * half + i] = (float)std::sin(ang);
-          pe[(size_t)m * hd + a * half + quarter + i] = (float)std::cos(ang);
-        }
-    }
-    if ((rc = tr_alloc(h, &h->pos2d, pe.size()))) return fail(rc);
-    if (hipMemcpy(h->pos2d, pe.data(), pe.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return fail(DFOT_ERR_HIP);
-    if (c.variant == 3 && c.use_temporal_rope) {  // RotaryEmbedding1D over the frame axis, in float64 as dit_build
-      const int dim = hd / c.num_row_heads, pairs = dim / 2;
-      std::vector<float> cs((size_t)c.max_tokens * pairs * 2);
-      for (int t = 0; t < c.max_tokens; ++t)
-        for (int i = 0; i < pairs; ++i) {
-          const double ang = (double)t * std::pow((double)c.rope_theta, -2.0 * (double)i / (double)dim);
-          cs[((size_t)t * pairs + i) * 2 + 0] = (float)std::cos(ang);
-          cs[((size_t)t * pairs + i) * 2 + 1] = (float)std::sin(ang);
-        }
-      if ((rc = tr_alloc(h, &h->trope, cs.size()))) return fail(rc);
-      if (hipMemcpy(h->trope, cs.data(), cs.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return fail(DFOT_ERR_HIP);
-    }
-  } else {  // RoPE-3D table, as dit_build
-    const int half = h->d / 2, q = half / 3, rem = half % 3;
-    int parts[3] = {q, q, q};
-    if (rem == 1) parts[0] = q + 1;
-    if (rem == 2) parts[1] = parts[2] = q + 1;
-    const int n = c.max_tokens * h->P;
-    std::vector<float> cs((size_t)n * half * 2);
-    for (int tok = 0; tok < n; ++tok) {
-      const int pos[3] = {tok / h->P, (tok / h->gw) % h->gh, tok % h->gw};
-      int pair = 0;
-      for (int ax = 0; ax < 3; ++ax) {
-        const int dim = 2 * parts[ax];
-        for (int j = 0; j < parts[ax]; ++j, ++pair) {
-          const float inv = 1.0f / powf(c.rope_theta, (float)(2 * j) / (float)dim);
-          const float ang = (float)pos[ax] * inv;
-          cs[((size_t)tok * half + pair) * 2 + 0] = cosf(ang);
-          cs[((size_t)tok * half + pair) * 2 + 1] = sinf(ang);
-        }
-      }
-    }
-    if ((rc = tr_alloc(h, &h->rope_cs, cs.size()))) return fail(rc);
-    if (hipMemcpy(h->rope_cs, cs.data(), cs.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return fail(DFOT_ERR_HIP);
+  if (facmat) {  // sinusoidal_2d at the patch embedding; variant 3: the RoPE-1D of the matrix attention over the frame axis
+    if ((rc = upload(&h->pos2d, dit_sinusoidal_2d(c, *h)))) return fail(rc);
+    if (c.variant == 3 && c.use_temporal_rope && (rc = upload(&h->trope, dit_rope_1d(c)))) return fail(rc);
+  } else if ((rc = upload(&h->rope_cs, dit_rope_3d(c, *h)))) {
+    return fail(rc);
   }
   *out = h;
   return DFOT_OK;
@@ -1136,17 +1047,12 @@ static int dit_train_create_impl(const DitCfg& c, dfot_dit_train_t* out, bool fa
 
 int dfot_dit_train_create(const dfot_dit_config* cfg, dfot_dit_train_t* out) {
   DFOT_REQUIRE(cfg && out, DFOT_ERR_ARG, "train_create: null argument");
-  DitCfg c;
-  static_cast<dfot_dit_config&>(c) = *cfg;
-  return dit_train_create_impl(c, out);
+  return dit_train_create_impl(dit_cfg(*cfg), out);
 }
 
 int dfot_dit_train_create_f(const dfot_dit_config_f* cfg, dfot_dit_train_t* out) {
   DFOT_REQUIRE(cfg && out, DFOT_ERR_ARG, "train_create_f: null argument");
-  DitCfg c;
-  static_cast<dfot_dit_config&>(c) = cfg->base;
-  c.fourier_noise = cfg->fourier_noise;
-  return dit_train_create_impl(c, out);
+  return dit_train_create_impl(dit_cfg(cfg->base, cfg->fourier_noise), out);
 }
 
 int dfot_facmat_train_create(const dfot_dit_config_f* cfg, dfot_dit_train_t* out) {
@@ -1155,9 +1061,7 @@ int dfot_facmat_train_create(const dfot_dit_config_f* cfg, dfot_dit_train_t* out
                "facmat_train_create: variant %d; this entry builds variant 3 (DiT3D factorized matrix) only, dfot_dit_train_create[_f] build 0 and 1",
                cfg->base.variant);
   DFOT_REQUIRE(!cfg->fourier_noise, DFOT_ERR_ARG, "facmat_train_create: fourier_noise (continuous diffusion) is not supported for variant 3");
-  DitCfg c;
-  static_cast<dfot_dit_config&>(c) = cfg->base;
-  return dit_train_create_impl(c, out, true);
+  return dit_train_create_impl(dit_cfg(cfg->base), out, true);
 }
 
 int dfot_dit_train_num_params(dfot_dit_train_t h) { return h ? (int)h->params.size() : 0; }
@@ -1170,7 +1074,7 @@ int dfot_dit_train_param_shape(dfot_dit_train_t h, int i, int64_t shape[4], int*
   for (int j = 0; j < *ndim; ++j) shape[j] = h->params[i].shape[j];
   return DFOT_OK;
 }
-int64_t dfot_dit_train_param_offset(dfot_dit_train_t h, int i) { return (h && i >= 0 && i < (int)h->offsets.size()) ? h->offsets[i] : -1; }
+int64_t dfot_dit_train_param_offset(dfot_dit_train_t h, int i) { return (h && i >= 0 && i < (int)h->params.size()) ? h->params[i].offset : -1; }
 int64_t dfot_dit_train_total_numel(dfot_dit_train_t h) { return h ? h->total : 0; }
 size_t dfot_dit_train_workspace_bytes(dfot_dit_train_t h) { return h ? h->ws_bytes : 0; }
 
