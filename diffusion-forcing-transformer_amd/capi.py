@@ -128,6 +128,7 @@ SIGNATURES = {
     "dfot_dit_train_create": (_I, [C.POINTER(DiTConfig), C.POINTER(_P)]),
     "dfot_dit_train_create_f": (_I, [C.POINTER(DiTConfigF), C.POINTER(_P)]),
     "dfot_facmat_train_create": (_I, [C.POINTER(DiTConfigF), C.POINTER(_P)]),
+    "dfot_facdit_train_create": (_I, [C.POINTER(DiTConfigF), C.POINTER(_P)]),
     "dfot_dit_train_destroy": (_I, [_P]),
     "dfot_dit_train_num_params": (_I, [_P]),
     "dfot_dit_train_param_name": (C.c_char_p, [_P, _I]),
@@ -163,6 +164,7 @@ SIGNATURES = {
     "dfot_op_attention": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "dfot_op_attention_padded": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "dfot_op_attention_temporal": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "dfot_op_attention_temporal_bwd": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "dfot_op_matrix_attention_rope": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P]),
     "dfot_op_matrix_attention_rope_bwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P]),
     "dfot_op_matrix_attention": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _F, _P]),

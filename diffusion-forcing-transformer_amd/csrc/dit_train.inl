@@ -1,6 +1,8 @@
 // Training path of the DiT backbones: DiT3D ("full", rope_3d: the README @DiT/XL K600 model, with or without the MLP branch) and
 // DifferenceDiT3D (factorized matrix attention, the bash/k600 model), and the FacMatDiT (DiT3D factorized matrix attention with the temporal
-// RoPE-1D, variant 3: the blocks of the difference model without its front end, matrix attention backward in attention_matrix_bwd.hip):
+// RoPE-1D, variant 3: the blocks of the difference model without its front end, matrix attention backward in attention_matrix_bwd.hip),
+// and the FacDiT (DiT3D factorized attention, variant 2: per depth a per-frame spatial DiTBlock and a temporal DiTBlock whose attention runs
+// over the frames of one patch position, backward in attention_temporal_bwd.hip; everything else of that block is row-wise and shared):
 // forward with saved activations, hand-written backward, gradients in one flat fp32 buffer (reference parameter order).
 // Included at the end of dit.hip (same translation unit: shares its kernels).
 //
@@ -17,6 +19,7 @@ namespace {
 
 struct TrainBlock {
   bool matrix = false;  // false: DiTBlock (token attention); true: MatrixDiTBlock (every frame is one token, factorized projections)
+  bool temporal = false;  // DiTBlock of variant 2 whose attention runs over the T frames of one patch position: keeps q, k, v, no lse
   int mh = 0;           // width of the block's MLP branch (0: none)
   long o_mod_w = 0, o_mod_b = 0, o_qkv_w = 0, o_qkv_b = 0, o_proj_w = 0, o_proj_b = 0;  // offsets into the flat parameter / gradient buffers
   long mod = 0;                                                 // column of this block's (shift|scale|gate) in the table
@@ -764,12 +767,13 @@ struct dfot_dit_train_s : dfot::DitGeom {  // the geometry of cfg (dit_model.h):
   float *c_in = nullptr, *c_h1 = nullptr, *c_a1 = nullptr, *c_dce = nullptr, *c_da1 = nullptr, *c_dh1 = nullptr;
   int* c_labels = nullptr;
   uint8_t* c_mask = nullptr;
-  std::vector<dfot::TrainBlock> blocks;  // execution order (variant 1: spatial 0, temporal 0, spatial 1, ...)
+  std::vector<dfot::TrainBlock> blocks;  // execution order (variants 1, 2, 3: spatial 0, temporal 0, spatial 1, ...)
   std::vector<void*> owned, ws_owned;
   size_t ws_bytes = 0;
   // compute copies
   dfot::bf16 *w_mod = nullptr, *w_modT = nullptr, *wfT = nullptr;
   float *b_mod = nullptr, *freqs = nullptr, *rope_cs = nullptr, *pos2d = nullptr;
+  float* tpos = nullptr;   // variant 2: temporal sinusoidal table [max_tokens][hidden], added once after spatial block 0; not a parameter
   float* trope = nullptr;  // variant 3 with use_temporal_rope: (cos, sin) [max_tokens][hd/2][2] of the matrix attention's RoPE-1D
   // fourier_noise: FourierEmbedding's freqs / phases [noise_dim].  Buffers, not parameters: they live HERE, outside the flat parameter /
   // gradient / moment buffers, so the optimizer (weight decay included), the gradient norm and the all-reduce never see them
@@ -920,13 +924,15 @@ int dfot_dit_train_destroy(dfot_dit_train_t h) {
   return DFOT_OK;
 }
 
-// facmat_entry: the call comes from dfot_facmat_train_create, the only entry that builds variant 3
-static int dit_train_create_impl(const DitCfg& c, dfot_dit_train_t* out, bool facmat_entry = false) {
-  DFOT_REQUIRE(c.variant != 2, DFOT_ERR_ARG, "train_create: variant 2 (factorized attention) has no training path; it is inference only");
-  DFOT_REQUIRE(c.variant != 3 || facmat_entry, DFOT_ERR_ARG,
+// entry: the variant the calling entry point is dedicated to -- 2 from dfot_facdit_train_create, 3 from dfot_facmat_train_create, the only
+// entries that build those variants; 0 from dfot_dit_train_create[_f], which build variants 0 and 1
+static int dit_train_create_impl(const DitCfg& c, dfot_dit_train_t* out, int entry = 0) {
+  DFOT_REQUIRE(c.variant != 2 || entry == 2, DFOT_ERR_ARG,
+               "train_create: variant 2 (factorized attention DiT3D, FacDiT) is not built here; its trainer is dfot_facdit_train_create");
+  DFOT_REQUIRE(c.variant != 3 || entry == 3, DFOT_ERR_ARG,
                "train_create: variant 3 (factorized matrix DiT3D, FacMatDiT) is not built here; its trainer is dfot_facmat_train_create");
-  DFOT_REQUIRE(c.variant == 0 || c.variant == 1 || c.variant == 3, DFOT_ERR_ARG, "train_create: unknown variant %d", c.variant);
-  const bool facmat = c.variant == 1 || c.variant == 3;
+  DFOT_REQUIRE(c.variant >= 0 && c.variant <= 3, DFOT_ERR_ARG, "train_create: unknown variant %d", c.variant);
+  const bool facmat = c.variant == 1 || c.variant == 3, fac = c.variant == 2;
   DFOT_REQUIRE(c.variant != 3 || !c.use_temporal_rope || c.rope_theta > 0.f, DFOT_ERR_ARG, "train_create: rope_theta %g must be positive",
                (double)c.rope_theta);
   DFOT_REQUIRE(c.mlp_hidden >= 0 && c.mlp_hidden % 128 == 0 && c.temporal_mlp_hidden >= 0 && c.temporal_mlp_hidden % 128 == 0, DFOT_ERR_ARG,
@@ -943,6 +949,7 @@ static int dit_train_create_impl(const DitCfg& c, dfot_dit_train_t* out, bool fa
                      (c.hidden_size / c.num_row_heads) % 4 == 0 && c.max_tokens <= 32,
                  DFOT_ERR_ARG, "train_create: matrix attention heads");
   }
+  DFOT_REQUIRE(!fac || c.max_tokens <= 32, DFOT_ERR_ARG, "train_create: max_tokens %d; the temporal attention takes at most 32 frames", c.max_tokens);
   DFOT_REQUIRE(c.cond_type == DFOT_COND_NONE || (c.cond_type == DFOT_COND_ACTION && c.cond_dim > 0 && c.cond_dim <= 1024) ||
                    (c.cond_type == DFOT_COND_LABEL && c.num_classes > 0),
                DFOT_ERR_ARG, "train_create: external condition type %d / cond_dim %d / num_classes %d", c.cond_type, c.cond_dim, c.num_classes);
@@ -950,17 +957,17 @@ static int dit_train_create_impl(const DitCfg& c, dfot_dit_train_t* out, bool fa
   h->cfg = c;
   static_cast<DitGeom&>(*h) = dit_geometry(c);
   const int hd = c.hidden_size, E = c.embed_col_dim, P = h->P;
-  if (h->P % TR_CHUNKS != 0 || (facmat && h->P % 128 != 0)) {
-    set_error("train_create: %d patches per frame must be a multiple of %d", h->P, facmat ? 128 : TR_CHUNKS);
+  if (h->P % TR_CHUNKS != 0 || ((facmat || fac) && h->P % 128 != 0)) {
+    set_error("train_create: %d patches per frame must be a multiple of %d", h->P, facmat || fac ? 128 : TR_CHUNKS);
     delete h;
     return DFOT_ERR_ARG;
   }
   // the flat buffers hold the inventory's parameters (dit_model.h) in its order, the reference module's; the Fourier buffers stay outside
   std::vector<DitTensor> inv = dit_inventory(c);
   h->total = dit_flat_layout(inv);
-  std::vector<TrainBlock> spatial(c.depth), temporal(facmat ? c.depth : 0);
+  std::vector<TrainBlock> spatial(c.depth), temporal(facmat || fac ? c.depth : 0);
   for (TrainBlock& b : spatial) b.mh = c.mlp_hidden;
-  for (TrainBlock& b : temporal) b.matrix = true, b.mh = c.temporal_mlp_hidden;
+  for (TrainBlock& b : temporal) b.matrix = facmat, b.temporal = fac, b.mh = c.temporal_mlp_hidden;
   for (const DitTensor& t : inv) {
     if (t.buffer) continue;
     h->params.push_back(t);
@@ -1006,7 +1013,7 @@ static int dit_train_create_impl(const DitCfg& c, dfot_dit_train_t* out, bool fa
   }
   for (int i = 0; i < c.depth; ++i) {  // execution order
     h->blocks.push_back(spatial[i]);
-    if (facmat) h->blocks.push_back(temporal[i]);
+    if (facmat || fac) h->blocks.push_back(temporal[i]);
   }
   int rc = 0;
   auto fail = [&](int code) { dfot_dit_train_destroy(h); return code; };
@@ -1038,6 +1045,8 @@ static int dit_train_create_impl(const DitCfg& c, dfot_dit_train_t* out, bool fa
   if (facmat) {  // sinusoidal_2d at the patch embedding; variant 3: the RoPE-1D of the matrix attention over the frame axis
     if ((rc = upload(&h->pos2d, dit_sinusoidal_2d(c, *h)))) return fail(rc);
     if (c.variant == 3 && c.use_temporal_rope && (rc = upload(&h->trope, dit_rope_1d(c)))) return fail(rc);
+  } else if (fac) {  // sinusoidal_factorized: the 2-D table at the patch embedding, the 1-D temporal table after spatial block 0
+    if ((rc = upload(&h->pos2d, dit_sinusoidal_2d(c, *h))) || (rc = upload(&h->tpos, dit_sinusoidal_1d(c)))) return fail(rc);
   } else if ((rc = upload(&h->rope_cs, dit_rope_3d(c, *h)))) {
     return fail(rc);
   }
@@ -1061,7 +1070,17 @@ int dfot_facmat_train_create(const dfot_dit_config_f* cfg, dfot_dit_train_t* out
                "facmat_train_create: variant %d; this entry builds variant 3 (DiT3D factorized matrix) only, dfot_dit_train_create[_f] build 0 and 1",
                cfg->base.variant);
   DFOT_REQUIRE(!cfg->fourier_noise, DFOT_ERR_ARG, "facmat_train_create: fourier_noise (continuous diffusion) is not supported for variant 3");
-  return dit_train_create_impl(dit_cfg(cfg->base), out, true);
+  return dit_train_create_impl(dit_cfg(cfg->base), out, 3);
+}
+
+int dfot_facdit_train_create(const dfot_dit_config_f* cfg, dfot_dit_train_t* out) {
+  DFOT_REQUIRE(cfg && out, DFOT_ERR_ARG, "facdit_train_create: null argument");
+  DFOT_REQUIRE(cfg->base.variant == 2, DFOT_ERR_ARG,
+               "facdit_train_create: variant %d; this entry builds variant 2 (DiT3D factorized attention) only, dfot_dit_train_create[_f] build "
+               "0 and 1, dfot_facmat_train_create builds 3",
+               cfg->base.variant);
+  DFOT_REQUIRE(!cfg->fourier_noise, DFOT_ERR_ARG, "facdit_train_create: fourier_noise (continuous diffusion) is not supported for variant 2");
+  return dit_train_create_impl(dit_cfg(cfg->base), out, 2);
 }
 
 int dfot_dit_train_num_params(dfot_dit_train_t h) { return h ? (int)h->params.size() : 0; }
@@ -1172,7 +1191,8 @@ int dfot_dit_train_reserve(dfot_dit_train_t h, int max_batch) {
   for (TrainBlock& b : h->blocks) {
     WS(b.x_in, rows * hd); WS(b.m, rows * hd); WS(b.a, rows * hd);
     if (!b.matrix) {
-      WS(b.q, qsz); WS(b.k, qsz); WS(b.v, qsz); WS(b.o, rows * hd); WS(b.lse, bhn);
+      WS(b.q, qsz); WS(b.k, qsz); WS(b.v, qsz); WS(b.o, rows * hd);
+      if (!b.temporal) { WS(b.lse, bhn); }  // the temporal backward recomputes its T x T problem
     } else {
       WS(b.w1, fe * hd); WS(b.z, fe * 3 * hd); WS(b.o2, fe * hd); WS(b.sfac, rows * hd);
     }
@@ -1224,7 +1244,7 @@ static int dit_train_forward_impl(dfot_dit_train_t h, const float* x, const int3
   DFOT_REQUIRE(h->synced, DFOT_ERR_STATE, "train_forward: call dfot_dit_train_sync_weights after attaching / updating the parameters");
   DFOT_REQUIRE(batch > 0 && batch <= h->max_batch, DFOT_ERR_STATE, "train_forward: batch %d exceeds the reserved %d", batch, h->max_batch);
   const DitCfg& c = h->cfg;
-  const bool diffm = c.variant == 1, facmat = c.variant == 1 || c.variant == 3;
+  const bool diffm = c.variant == 1, facmat = c.variant == 1 || c.variant == 3, fac = c.variant == 2;
   DFOT_REQUIRE(tokens > 0 && tokens <= c.max_tokens, DFOT_ERR_SHAPE, "train_forward: %d tokens, max_tokens is %d", tokens, c.max_tokens);
   DFOT_REQUIRE(!diffm || tokens % 2 == 0, DFOT_ERR_SHAPE, "train_forward: %d tokens; the difference model takes (difference, frame) pairs", tokens);
   const int n = tokens * h->P, hd = c.hidden_size, P = h->P, frames = batch * tokens, nd = c.noise_dim, E = c.embed_col_dim;
@@ -1278,8 +1298,8 @@ static int dit_train_forward_impl(dfot_dit_train_t h, const float* x, const int3
                      p + h->o_pe_b, (const float*)h->pos2d, h->blocks[0].x_in, c.in_channels, c.height, c.width, c.patch_size, hd, rows);
   DFOT_CHECK_HIP(hipGetLastError());
   const float qscale = 1.4426950408889634f / sqrtf((float)h->d);
-  // attention sequences: the whole video with RoPE-3D (variant 0) or one frame without RoPE (variant 1 spatial blocks)
-  const int seq = facmat ? P : n, nseq = facmat ? frames : batch;
+  // attention sequences: the whole video with RoPE-3D (variant 0) or one frame without RoPE (the spatial blocks of variants 1, 2, 3)
+  const int seq = facmat || fac ? P : n, nseq = facmat || fac ? frames : batch;
   const int gfe = (c.variant == 3 ? (frames + 1) & ~1 : frames) * E;  // rows of the right-factor GEMMs (see reserve)
   auto combine = [&](const bf16* a, long gate_off, float* dst) -> int {
     hipLaunchKernelGGL(gate_combine_kernel, dim3(cdiv(rows * hd / 4, 256)), dim3(256), 0, s, h->X, dst, a, h->mod_table, h->ldt, gate_off, hd, P,
@@ -1291,14 +1311,24 @@ static int dit_train_forward_impl(dfot_dit_train_t h, const float* x, const int3
     TrainBlock& b = h->blocks[bi];
     float* next = bi + 1 < h->blocks.size() ? h->blocks[bi + 1].x_in : h->x_fin;
     float* after_attn = b.mh ? b.x_mid : next;
+    if (fac && bi == 1) {  // sinusoidal_factorized: the first `tokens` rows of the temporal table enter after spatial block 0
+      // (dit_base.py:407-408), in place on temporal block 0's x_in: the buffer then holds what that block's LayerNorm backward needs
+      const long total4 = rows * (hd / 4);
+      hipLaunchKernelGGL(add_temporal_pos_kernel, dim3(cdiv(total4, 256)), dim3(256), 0, s, b.x_in, h->tpos, tokens, P, hd / 4, total4);
+      DFOT_CHECK_HIP(hipGetLastError());
+    }
     if ((rc = launch_ln_mod(b.x_in, h->X, b.m, h->mod_table, h->idx, h->ldt, b.mod, hd, P, (int)rows, c.eps, frames - 1, s))) return rc;
     if (!b.matrix) {
       GemmArgs g;
       g.A = b.m; g.lda = hd; g.W = b.w_qkv; g.M = (int)rows; g.N = 3 * hd; g.K = hd; g.bias = p + b.o_qkv_b;
-      g.q = b.q; g.k = b.k; g.v = b.v; g.rope_cs = facmat ? nullptr : h->rope_cs; g.heads = c.num_heads; g.d = h->d; g.dstride = h->dstride; g.ntok = seq;
+      g.q = b.q; g.k = b.k; g.v = b.v; g.rope_cs = facmat || fac ? nullptr : h->rope_cs; g.heads = c.num_heads; g.d = h->d; g.dstride = h->dstride; g.ntok = seq;
       g.qscale = qscale;
       if ((rc = launch_gemm(A_DENSE, E_QKV_DIT, GEMM_AUTO, g, s))) return rc;
-      if ((rc = launch_attention_padded(b.q, b.k, b.v, b.o, hd, nseq, c.num_heads, seq, h->d, s, b.lse))) return rc;
+      if (b.temporal)  // over the frames of every patch position, on the operands of the per-frame layout
+        rc = launch_attention_temporal(b.q, b.k, b.v, b.o, hd, batch, tokens, P, c.num_heads, h->d, s);
+      else
+        rc = launch_attention_padded(b.q, b.k, b.v, b.o, hd, nseq, c.num_heads, seq, h->d, s, b.lse);
+      if (rc) return rc;
       if ((rc = tr_gemm_bf16(b.o, hd, b.w_proj, (int)rows, hd, hd, p + b.o_proj_b, b.a, hd, s))) return rc;
     } else {
       const bool bias = b.o_qkv_bias >= 0;
@@ -1370,10 +1400,10 @@ int dfot_dit_train_backward(dfot_dit_train_t h, const float* d_out, void* stream
   DFOT_REQUIRE(h && d_out, DFOT_ERR_ARG, "train_backward: null argument");
   DFOT_REQUIRE(h->batch > 0 && h->x_saved, DFOT_ERR_STATE, "train_backward: no forward to differentiate");
   const DitCfg& c = h->cfg;
-  const bool diffm = c.variant == 1, facmat = c.variant == 1 || c.variant == 3;
+  const bool diffm = c.variant == 1, facmat = c.variant == 1 || c.variant == 3, fac = c.variant == 2;
   const int batch = h->batch, tokens = h->tokens, n = tokens * h->P, hd = c.hidden_size, P = h->P, frames = batch * tokens, nd = c.noise_dim;
   const int fp = h->fp, E = c.embed_col_dim;
-  const int seq = facmat ? P : n, nseq = facmat ? frames : batch;
+  const int seq = facmat || fac ? P : n, nseq = facmat || fac ? frames : batch;
   hipStream_t s = (hipStream_t)stream;
   const long rows = (long)batch * n;
   const float* p = h->params_f32;
@@ -1446,10 +1476,14 @@ int dfot_dit_train_backward(dfot_dit_train_t h, const float* d_out, void* stream
       if ((rc = gate_bwd(b.a, b.mod + 2 * hd, G + b.o_proj_b))) return rc;
       if ((rc = tr_gemm_bf16(h->da, hd, b.w_projT, (int)rows, hd, hd, nullptr, h->dO, hd, s))) return rc;      // dO = da Wp
       if ((rc = wgrad(h->da, hd, b.o, hd, rows, G + b.o_proj_w))) return rc;  // dWp = da^T o
-      if ((rc = launch_attention_bwd_delta(b.o, h->dO, hd, h->delta, nseq, c.num_heads, seq, h->d, s))) return rc;
-      if ((rc = launch_attention_bwd(b.q, b.k, b.v, h->dO, hd, b.lse, h->delta, h->dq, h->dk, h->dv, nseq, c.num_heads, seq, h->d, s))) return rc;
+      if (b.temporal) {  // one launch, no lse / delta: dq, dk, dv in the per-frame layout the pack kernel reads
+        if ((rc = launch_attention_temporal_bwd(b.q, b.k, b.v, h->dO, hd, h->dq, h->dk, h->dv, batch, tokens, P, c.num_heads, h->d, s))) return rc;
+      } else {
+        if ((rc = launch_attention_bwd_delta(b.o, h->dO, hd, h->delta, nseq, c.num_heads, seq, h->d, s))) return rc;
+        if ((rc = launch_attention_bwd(b.q, b.k, b.v, h->dO, hd, b.lse, h->delta, h->dq, h->dk, h->dv, nseq, c.num_heads, seq, h->d, s))) return rc;
+      }
       hipLaunchKernelGGL(qkv_grad_pack_kernel, dim3(cdiv(rows * (3 * hd / 8), 256)), dim3(256), 0, s, h->dq, h->dk, h->dv,
-                         facmat ? (const float*)nullptr : h->rope_cs, h->dqkv, rows, seq, c.num_heads, h->d, h->dstride);
+                         facmat || fac ? (const float*)nullptr : h->rope_cs, h->dqkv, rows, seq, c.num_heads, h->d, h->dstride);
       launch_colsum_bf16(h->dqkv, G + b.o_qkv_b, rows, 3 * hd, (long)3 * hd, s);
       DFOT_CHECK_HIP(hipGetLastError());
       if ((rc = tr_gemm_f32(h->dqkv, 3 * hd, b.w_qkvT, (int)rows, hd, 3 * hd, dY, hd, dY, s))) return rc;       // dm = dY + dqkv Wqkv (in place)

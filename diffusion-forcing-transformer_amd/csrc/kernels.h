@@ -142,6 +142,11 @@ int launch_attention_padded(const bf16* q, const bf16* k, const bf16* v, bf16* o
 // frames (1 .. 32); o [(video, frame, patch)][ldo] compact.  patches % 128 == 0, d % 4 == 0
 int launch_attention_temporal(const bf16* q, const bf16* k, const bf16* v, bf16* o, long ldo, int batch, int tokens, int patches, int heads,
                               int d, hipStream_t s);
+// attention_temporal_bwd.hip: backward of launch_attention_temporal, the T x T problem recomputed (no lse, no delta); d_o compact
+// [(video, frame, patch)][ldo]; dq / dk / dv in the layout of q / k / v under the contract of launch_attention_bwd below (dq: gradient of
+// the UNSCALED q), live columns only.  The forward's shape rules with d % 8 == 0
+int launch_attention_temporal_bwd(const bf16* q, const bf16* k, const bf16* v, const bf16* d_o, long ldo, bf16* dq, bf16* dk, bf16* dv,
+                                  int batch, int tokens, int patches, int heads, int d, hipStream_t s);
 // attention_matrix.hip: MatrixAttention core of the FacMatDiT backbone; z [batch*L*E][3h] (q|k|v), o [batch*L*E][h], one problem per
 // (video, col head, row head), 1 <= L <= 32, (h / rr) % 4 == 0; rope_cs: [>= L][h/rr/2][2] (cos, sin) per frame, nullptr = no rotation
 int launch_matrix_attn_rope(const bf16* z, bf16* o, const float* rope_cs, int batch, int L, int E, int h, int cc, int rr, float scale,

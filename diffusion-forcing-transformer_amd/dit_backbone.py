@@ -3,7 +3,7 @@
 Mirrors the reference's plugin contract for this path:
   * constructor keywords of DiscreteDiffusion._build_model (algorithms/dfot/diffusion/discrete_diffusion.py:64-92)
     and DiT3D.__init__ (algorithms/dfot/backbones/dit/dit3d.py:13-83): variant "full" with pos_emb_type "rope_3d", and variant
-    "factorized_attention" with pos_emb_type "sinusoidal_factorized" (spatial + temporal blocks; inference only), and variant
+    "factorized_attention" with pos_emb_type "sinusoidal_factorized" (spatial + temporal blocks; trained by trainer.FacDiTTrainer), and variant
     "factorized_matrix_attention" with pos_emb_type "sinusoidal_2d" (FacMatDiT: spatial + matrix blocks, RoPE-1D over the frames; inference only),
     external condition "action" / "label" (base_backbone.py:42-62), causal masking rejected exactly as the reference does;
   * ``forward(x, noise_levels, external_cond=None, external_cond_mask=None)`` (dit3d.py:146-192) with integer
@@ -106,6 +106,25 @@ def configure_facmat(c: "capi.DiTConfig", cfg, max_tokens: int) -> None:
     c.use_temporal_rope = int(rope)
 
 
+def configure_fac(c: "capi.DiTConfig", cfg, max_tokens: int) -> None:
+    """dit3d_factorized_attention.yaml (+ the @FacDiT shortcuts) -> engine variant 2: per depth a per-frame spatial DiTBlock
+    (spatial_mlp_ratio) and a temporal DiTBlock (mlp_ratio) over the frames of every patch position (dit_base.py:197-226, 364-417).
+    c.patch_size / height / width are already set.  Shared by DiT3D and trainer.FacDiTTrainer."""
+    ratio, tratio = _get(cfg, "spatial_mlp_ratio", None), _get(cfg, "mlp_ratio", 4.0)
+    c.hidden_size = int(_get(cfg, "hidden_size"))
+    c.max_tokens = max_tokens
+    c.mlp_hidden = int(c.hidden_size * ratio) if ratio else 0
+    c.variant = 2
+    c.temporal_mlp_hidden = int(c.hidden_size * tratio) if tratio else 0
+    patches = (c.height // c.patch_size) * (c.width // c.patch_size)
+    if patches % 128 != 0:
+        raise ValueError(f"variant 'factorized_attention': x_shape {(c.in_channels, c.height, c.width)} with patch_size {c.patch_size} gives "
+                         f"{patches} patches per frame; the per-frame attention kernels need a multiple of 128 (the 64-patch recipes are not "
+                         "supported)")
+    if max_tokens > 32:
+        raise ValueError(f"variant 'factorized_attention': max_tokens {max_tokens} exceeds the temporal attention kernel's 32 frames")
+
+
 def _init_random_matrix(tensors, seed: int) -> None:
     """init_random of the models with matrix blocks: as DiT3D.init_random; the matrix factors are (in, out) matrices (fan-in = rows), their
     biases ~ N(0, 0.05^2)"""
@@ -197,22 +216,13 @@ class DiT3D(nn.Module):
         if variant == "factorized_matrix_attention":
             configure_facmat(c, cfg, max_tokens)
             return
+        if variant == "factorized_attention":
+            configure_fac(c, cfg, max_tokens)
+            return
         c.hidden_size = int(_get(cfg, "hidden_size"))
         c.max_tokens = max_tokens
         c.mlp_hidden = int(c.hidden_size * ratio) if ratio else 0
         c.variant = 0
-        if variant == "factorized_attention":
-            # per depth a per-frame spatial DiTBlock (spatial_mlp_ratio) and a temporal DiTBlock (mlp_ratio) over the frames of every
-            # patch position (dit_base.py:197-226, 364-417)
-            tratio = _get(cfg, "mlp_ratio", 4.0)
-            c.variant = 2
-            c.temporal_mlp_hidden = int(c.hidden_size * tratio) if tratio else 0
-            patches = (c.height // c.patch_size) * (c.width // c.patch_size)
-            if patches % 128 != 0:
-                raise ValueError(f"variant 'factorized_attention': x_shape {self.x_shape} with patch_size {c.patch_size} gives {patches} patches "
-                                 "per frame; the per-frame attention kernels need a multiple of 128 (the 64-patch recipes are not supported)")
-            if max_tokens > 32:
-                raise ValueError(f"variant 'factorized_attention': max_tokens {max_tokens} exceeds the temporal attention kernel's 32 frames")
 
     @property
     def in_channels(self) -> int:

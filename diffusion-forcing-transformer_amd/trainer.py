@@ -407,3 +407,26 @@ class FacMatDiTTrainer(DiT3DTrainer):
 
     def _create(self, c: "capi.DiTConfigF") -> None:
         capi.check(capi.lib.dfot_facmat_train_create(C.byref(c), C.byref(self._handle)))
+
+
+class FacDiTTrainer(DiT3DTrainer):
+    """Trainer of the FacDiT backbone: ``name: dit3d`` with ``variant: factorized_attention``, ``pos_emb_type: sinusoidal_factorized``
+    (dit3d_factorized_attention.yaml + the @FacDiT shortcuts; the reference's bash/taichikl train_dfot_facdit-* recipes).  Same constructor
+    keywords and methods as DiT3DTrainer; ``spatial_mlp_ratio`` is the spatial blocks' MLP (0 / None: none), ``mlp_ratio`` the temporal
+    blocks'; ``use_gradient_checkpointing`` is ignored (the engine keeps every activation its backward needs).  Any 1 <= T <= max_tokens <= 32
+    trains, with the first T rows of the temporal table.  The temporal attention and its backward run over the frames of every patch
+    position (csrc/attention_temporal.hip, csrc/attention_temporal_bwd.hip).  Discrete diffusion only; patches per frame a multiple of 128."""
+
+    def _configure(self, c: "capi.DiTConfigF", cfg, max_tokens: int) -> None:
+        from .dit_backbone import configure_fac
+        variant, pos = _get(cfg, "variant", "full"), _get(cfg, "pos_emb_type", "rope_3d")
+        if variant != "factorized_attention" or pos != "sinusoidal_factorized":
+            raise ValueError(f"FacDiTTrainer builds variant='factorized_attention' with pos_emb_type='sinusoidal_factorized', not "
+                             f"{variant!r} / {pos!r} (DiT3DTrainer trains the 'full' DiT3D and the difference model, FacMatDiTTrainer the "
+                             "factorized-matrix DiT3D)")
+        if _get(cfg, "use_fourier_noise_embedding", False):
+            raise ValueError("use_fourier_noise_embedding=True is not supported by FacDiTTrainer: it trains under discrete diffusion only")
+        configure_fac(c, cfg, max_tokens)  # refuses the patch count and max_tokens by name, as DiT3D does
+
+    def _create(self, c: "capi.DiTConfigF") -> None:
+        capi.check(capi.lib.dfot_facdit_train_create(C.byref(c), C.byref(self._handle)))

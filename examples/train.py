@@ -5,6 +5,7 @@
   python examples/train.py k600 --pixels [--vae-ckpt VideoVAE_K600.ckpt]                # online latents: frames -> VideoVAE encoder -> step
   python examples/train.py k600diff [--accumulate 2]                                  # the model bash/k600/*.sh train
   python examples/train.py facmat   [--xl] [--batch 8]                                # FacMatDiT (dit3d_factorized_matrix.yaml); --xl: XL-64-1, taichikl shape
+  python examples/train.py facdit   [--xl] [--batch 8]                                # FacDiT (dit3d_factorized_attention.yaml); --xl: @DiT/XL widths, taichikl shape
   python examples/train.py re10k    [--batch 8]                                       # RE10K UViT3DPose (BASELINE config 5), synthetic frames + poses
   python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 examples/train.py k600   # data parallel, one rank per GPU
 
@@ -33,7 +34,7 @@ K600_DATA_STD = [5.591, 5.257, 7.033, 6.401, 6.091, 11.233, 5.608, 7.5, 5.277, 5
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("model", choices=["k600", "k600diff", "facmat", "re10k"])
+    ap.add_argument("model", choices=["k600", "k600diff", "facmat", "facdit", "re10k"])
     ap.add_argument("--ckpt")
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--batch", type=int, default=8)
@@ -45,8 +46,8 @@ def main():
     ap.add_argument("--continuous", action="store_true",
                     help="k600 / k600diff: continuous diffusion as @diffusion/continuous (Fourier noise-level embedding, levels in [0, 1], cosine "
                          "training schedule shifted 0.125, sigmoid loss weighting)")
-    ap.add_argument("--xl", action="store_true", help="facmat: @FacMatDiT/XL-64-1 at the taichikl shape (4x32x32 latents, patch 2, 16 frames) "
-                                                      "instead of the tiny default (row width 128, depth 2, 4x16x8 latents, 5 frames)")
+    ap.add_argument("--xl", action="store_true", help="facmat / facdit: @FacMatDiT/XL-64-1 / @DiT/XL widths at the taichikl shape (4x32x32 latents, "
+                                                      "patch 2, 16 frames) instead of the tiny default (width 128, depth 2, 4x16x8 latents, 5 frames)")
     ap.add_argument("--pixels", action="store_true", help="k600 / k600diff: encode synthetic frames online with the VideoVAE encoder")
     ap.add_argument("--vae-ckpt", help="--pixels: reference VideoVAE checkpoint (vae.* keys); random encoder weights otherwise")
     a = ap.parse_args()
@@ -58,8 +59,8 @@ def main():
         dist.init_process_group("nccl", device_id=torch.device("cuda", torch.cuda.current_device()))
     if a.model == "re10k":
         return train_re10k(a, rank, world)
-    if a.model == "facmat":
-        return train_facmat(a, rank, world)
+    if a.model in ("facmat", "facdit"):
+        return train_factorized(a, rank, world)
     diff = a.model == "k600diff"
     ctype, cnum, ckw = None, 0, {}
     if a.cond:
@@ -134,28 +135,33 @@ def main():
         dist.destroy_process_group()
 
 
-def train_facmat(a, rank, world):
-    """DFoTVideo training of the FacMatDiT backbone (bash/taichikl/train_dfot_facmat-*): DiT3D with factorized matrix attention and the
-    temporal RoPE, discrete diffusion, random_independent levels, fused-min-SNR v-loss"""
+def train_factorized(a, rank, world):
+    """DFoTVideo training of the two factorized DiT3D backbones, discrete diffusion, random_independent levels, fused-min-SNR v-loss:
+    facmat (bash/taichikl/train_dfot_facmat-*): factorized matrix attention with the temporal RoPE, FacMatDiTTrainer;
+    facdit (bash/taichikl/train_dfot_facdit-*): factorized attention, sinusoidal_factorized, FacDiTTrainer -- the baseline of the former"""
     if a.continuous or a.pixels:
-        raise SystemExit("facmat trains on synthetic latents under discrete diffusion")
-    if a.xl:
-        x_shape, tokens = (4, 32, 32), 16
-        cfg = dict(patch_size=2, embed_col_dim=64, embed_row_dim=1152, num_heads=16, num_col_heads=1, num_row_heads=16, depth=28)
+        raise SystemExit(f"{a.model} trains on synthetic latents under discrete diffusion")
+    x_shape, tokens = ((4, 32, 32), 16) if a.xl else ((4, 16, 8), 5)
+    if a.model == "facdit":
+        cfg = dict(patch_size=2, hidden_size=1152, num_heads=16, depth=28) if a.xl else dict(patch_size=1, hidden_size=128, num_heads=4, depth=2)
+        cfg.update(name="dit3d", variant="factorized_attention", pos_emb_type="sinusoidal_factorized", mlp_ratio=4.0, spatial_mlp_ratio=4.0)
+        trainer_cls = dfot_amd.FacDiTTrainer
     else:
-        x_shape, tokens = (4, 16, 8), 5
-        cfg = dict(patch_size=1, embed_col_dim=64, embed_row_dim=128, num_heads=4, num_col_heads=1, num_row_heads=4, depth=2)
-    cfg.update(name="dit3d", variant="factorized_matrix_attention", pos_emb_type="sinusoidal_2d", use_temporal_rope=True, mlp_ratio=4.0,
-               spatial_mlp_ratio=4.0, use_bias=True, matrix_block="matrix")
+        if a.xl:
+            cfg = dict(patch_size=2, embed_col_dim=64, embed_row_dim=1152, num_heads=16, num_col_heads=1, num_row_heads=16, depth=28)
+        else:
+            cfg = dict(patch_size=1, embed_col_dim=64, embed_row_dim=128, num_heads=4, num_col_heads=1, num_row_heads=4, depth=2)
+        cfg.update(name="dit3d", variant="factorized_matrix_attention", pos_emb_type="sinusoidal_2d", use_temporal_rope=True, mlp_ratio=4.0,
+                   spatial_mlp_ratio=4.0, use_bias=True, matrix_block="matrix")
+        trainer_cls = dfot_amd.FacMatDiTTrainer
     ckw = {}
     if a.cond:
         ctype, cnum = a.cond.split(":")[0], int(a.cond.split(":")[1])
         if ctype != "action":
-            raise SystemExit("facmat: --cond action:DIM")
+            raise SystemExit(f"{a.model}: --cond action:DIM")
         ckw = dict(external_cond_type="action", external_cond_dim=cnum)
         cfg["external_cond_dropout"] = 0.1
-    trainer = dfot_amd.FacMatDiTTrainer(cfg, x_shape=x_shape, max_tokens=tokens, lr=a.lr,
-                                        loss_weighting=dict(strategy="fused_min_snr", cum_snr_decay=0.96), **ckw)
+    trainer = trainer_cls(cfg, x_shape=x_shape, max_tokens=tokens, lr=a.lr, loss_weighting=dict(strategy="fused_min_snr", cum_snr_decay=0.96), **ckw)
     if a.ckpt:
         dfot_amd.load_reference_checkpoint(trainer, a.ckpt)
     else:

@@ -203,7 +203,8 @@ typedef struct {
    *   + shortcut/FacDiT; dit_base.py:197-226,364-417): per depth one per-frame spatial DiTBlock (MLP mlp_hidden, 0 = none) and one
    *   temporal DiTBlock (MLP temporal_mlp_hidden, 0 = none) whose attention runs over the T frames of one patch position; the 2-D
    *   sinusoidal table is added at the patch embedding, the 1-D temporal table [max_tokens][hidden] after spatial block 0.
-   *   Uses hidden_size, num_heads, mlp_hidden, temporal_mlp_hidden; (H/p)*(W/p) % 128 == 0, max_tokens <= 32; inference only.
+   *   Uses hidden_size, num_heads, mlp_hidden, temporal_mlp_hidden; (H/p)*(W/p) % 128 == 0, max_tokens <= 32.  Trained through
+   *   dfot_facdit_train_create; dfot_dit_train_create[_f] refuse it.
    * variant 3: DiT3D "factorized_matrix_attention" + sinusoidal_2d (FacMatDiT: configurations/algorithm/backbone/
    *   dit3d_factorized_matrix.yaml + shortcut/FacMatDiT): the block sequence and parameters of variant 1 without the difference front
    *   end -- no diff_embedder, the conditioning depends on the noise level only, max_tokens is the caller's (<= 32, odd counts
@@ -301,6 +302,13 @@ int dfot_dit_train_create_f(const dfot_dit_config_f* cfg, dfot_dit_train_t* out)
  * float64 when use_temporal_rope is set; actions / labels through dfot_dit_train_forward_cond.  dfot_dit_train_create[_f] keep refusing
  * variant 3 and name this function. */
 int dfot_facmat_train_create(const dfot_dit_config_f* cfg, dfot_dit_train_t* out);
+/* trainer of the DiT3D factorized-attention model (FacDiT: variant 2 only, any other variant: DFOT_ERR_ARG; fourier_noise != 0:
+ * DFOT_ERR_ARG).  The handle is a dfot_dit_train_t: every other dfot_dit_train_* function takes it.  Parameters in the reference's
+ * registration order (all spatial blocks, then all temporal blocks), executed spatial i, temporal i; any 1 <= T <= max_tokens <= 32 (the
+ * first T rows of the temporal sinusoidal table, which is built at create time and is not a parameter); (H/p)*(W/p) % 128 == 0, MLP
+ * widths multiples of 128, head dim a multiple of 8; actions / labels through dfot_dit_train_forward_cond.  dfot_dit_train_create[_f]
+ * keep refusing variant 2 and name this function. */
+int dfot_facdit_train_create(const dfot_dit_config_f* cfg, dfot_dit_train_t* out);
 int dfot_dit_train_destroy(dfot_dit_train_t h);
 int dfot_dit_train_num_params(dfot_dit_train_t h);
 const char* dfot_dit_train_param_name(dfot_dit_train_t h, int i);
@@ -444,6 +452,14 @@ int dfot_op_attention_padded(const void* q, const void* k, const void* v, void* 
  * multiple of 8 (4 when d % 8 != 0) covering heads*d; anything else: DFOT_ERR_SHAPE */
 int dfot_op_attention_temporal(const void* q, const void* k, const void* v, void* o, int ldo, int batch, int tokens, int patches,
                                int heads, int d, void* stream);
+/* backward of dfot_op_attention_temporal for the upstream gradient d_o [(video, frame, patch)][heads*d] bf16 (row stride ldo) of o: dq,
+ * dk, dv in the layout of q, k, v (live columns only; pad columns are not written).  Scores, softmax (with the forward's bf16-rounded
+ * probabilities), dP and dS are recomputed: no log-sum-exp, no delta buffer.  dq is the gradient of the UNSCALED q (factor 1/sqrt(d)) and
+ * dk carries ln 2, as dfot_op_attention_bwd.  Fixed summation order, no atomics: a video gives the same bits alone, in a batch and on
+ * repeat.  1 <= tokens <= 32, d % 8 == 0, d <= 128, patches % 128 == 0, ldo a multiple of 8 covering heads*d, batch and heads <= 65535;
+ * anything else: DFOT_ERR_SHAPE (null pointer: DFOT_ERR_ARG) before any launch, nothing written */
+int dfot_op_attention_temporal_bwd(const void* q, const void* k, const void* v, const void* d_o, int ldo, void* dq, void* dk, void* dv,
+                                   int batch, int tokens, int patches, int heads, int d, void* stream);
 /* MatrixAttention core of the FacMatDiT backbone (DiT3D "factorized_matrix_attention", engine variant 3): every frame is one token whose
  * q / k / v are (E/cc x h/rr) matrices.  z [batch*L*E][3h] bf16 holds (q|k|v), rows (frame, col head, n), columns (row head, d);
  * o [batch*L*E][h] in the same order.  Per (video, col head, row head): S[l][l'] = scale * <rope(q_l), rope(k_l')> over the matrix

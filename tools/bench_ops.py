@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Micro-benchmarks of the C-ABI primitives at the RE10K model shapes (model batch 2), HIP-event timed.
-Usage (GPU box): python tools/bench_ops.py [gemm] [conv] [attn] [tattn] [mattn] [mattn_bwd] [facmat_train] [vae_encode] [equal] [dit_front] [ivae] [uvit3d]"""
+Usage (GPU box): python tools/bench_ops.py [gemm] [conv] [attn] [tattn] [mattn] [tattn_bwd] [facdit_train] [mattn_bwd] [facmat_train] [vae_encode] [equal] [dit_front] [ivae] [uvit3d]"""
 import ctypes as C
 import math
 import os
@@ -113,6 +113,39 @@ def facdit_forward(b):
     k = torch.randint(0, 1000, (b, 16), device="cuda")
     with torch.no_grad():
         return timeit(lambda: model(x, k), iters=10, warm=3)
+
+
+def tattn_bwd(b, heads, tokens, patches, d):
+    """backward of the temporal attention on unit-normal operands: ms of dfot_op_attention_temporal_bwd, ms of the forward on the same q, k,
+    v in the same process, and the backward's algorithmic bytes, (6 dstride + d) * 2 per (row, head): q, k, v rows read once (pad columns
+    included) and dq, dk, dv rows counted whole, the compact d_o read once"""
+    ds = 64 if d <= 64 else 128
+    q, k, v = (torch.zeros(b * tokens, heads, patches, ds, device="cuda", dtype=torch.bfloat16) for _ in range(3))
+    for t, mul in ((q, 0.2), (k, 1.0), (v, 1.0)):
+        t[..., :d] = (torch.randn(b * tokens, heads, patches, d, device="cuda") * mul).bfloat16()
+    d_o = torch.randn(b * tokens * patches, heads * d, device="cuda").bfloat16()
+    o = torch.empty_like(d_o)
+    dq, dk, dv = (torch.zeros_like(q) for _ in range(3))
+    ms_bwd = timeit(lambda: capi.check(capi.lib.dfot_op_attention_temporal_bwd(P(q), P(k), P(v), P(d_o), heads * d, P(dq), P(dk), P(dv), b, tokens,
+                                                                              patches, heads, d, S())), iters=50, warm=5)
+    ms_fwd = timeit(lambda: capi.check(capi.lib.dfot_op_attention_temporal(P(q), P(k), P(v), P(o), heads * d, b, tokens, patches, heads, d, S())),
+                    iters=50, warm=5)
+    return ms_bwd, ms_fwd, b * tokens * patches * heads * (6 * ds + d) * 2.0
+
+
+def facdit_train(b, depth=28):
+    """one training step (loss, backward, AdamW) of FacDiT-XL (@DiT/XL widths, both MLP ratios 4) at the taichikl shape (4x32x32 latents,
+    patch 2, 16 frames), ms"""
+    bb = dict(name="dit3d", variant="factorized_attention", pos_emb_type="sinusoidal_factorized", patch_size=2, hidden_size=1152, depth=depth,
+              num_heads=16, mlp_ratio=4.0, spatial_mlp_ratio=4.0)
+    tr = dfot_amd.FacDiTTrainer(bb, x_shape=(4, 32, 32), max_tokens=16, loss_weighting=dict(strategy="fused_min_snr", cum_snr_decay=0.96))
+    model = dfot_amd.DiT3D(bb, x_shape=(4, 32, 32), max_tokens=16)  # for its init_random only
+    model.init_random(0)
+    tr.load_state_dict({n: t.detach() for n, t in model.state_dict().items()})
+    del model
+    xs, noise = torch.randn(b, 16, 4, 32, 32, device="cuda"), torch.randn(b, 16, 4, 32, 32, device="cuda")
+    k = torch.randint(0, 1000, (b, 16))
+    return timeit(lambda: tr.training_step(xs, k, noise), iters=5, warm=2)
 
 
 def uvit3d_forward(b=2):
@@ -355,6 +388,26 @@ def main():
                   f"{tf:6.2f} TF/s", flush=True)
         for b in (2, 16):
             print(f"facdit XL forward B={b} x 16 frames x 256 patches: {facdit_forward(b):.3f} ms", flush=True)
+    if "tattn_bwd" in what:
+        for name, (b, hd, t, pn, d) in {"XL B2": (2, 16, 16, 256, 72), "XL B16": (16, 16, 16, 256, 72), "S B2": (2, 6, 16, 256, 64),
+                                        "S B16": (16, 6, 16, 256, 64)}.items():
+            ms_bwd, ms_fwd, nbytes = tattn_bwd(b, hd, t, pn, d)
+            gbs = nbytes / ms_bwd / 1e6
+            print(f"tattn_bwd {name:6s} B={b} H={hd} T={t} P={pn} d={d}: backward {ms_bwd*1e3:8.1f} us  {gbs:7.1f} GB/s ({gbs / 1e3 / HBM_TBS:.2f} of "
+                  f"{HBM_TBS:.0f} TB/s HBM)  forward {ms_fwd*1e3:8.1f} us  backward / forward {ms_bwd / ms_fwd:.2f}", flush=True)
+    if "facdit_train" in what:
+        depth = 28
+        for b in (2, 8):
+            try:
+                ms = facdit_train(b, depth=depth)
+            except (torch.cuda.OutOfMemoryError, capi.DfotError) as err:
+                print(f"facdit_train XL B={b}: does not fit ({type(err).__name__})", flush=True)
+                torch.cuda.empty_cache()
+                continue
+            ms_attn = tattn_bwd(b, 16, 16, 256, 72)[0]
+            print(f"facdit_train XL B={b} x 16 frames x 256 patches: {ms:.2f} ms per training step; temporal attention backward {depth} x "
+                  f"{ms_attn*1e3:.1f} us = {depth * ms_attn / ms * 100:.1f} % of it", flush=True)
+            torch.cuda.empty_cache()
     if "mattn" in what:
         # @FacMatDiT/S-64-1 (embed_row_dim 384, 6 row heads) and XL-64-1 (1152, 16); embed_col_dim 64, one col head
         for name, (h, rr) in {"S": (384, 6), "XL": (1152, 16)}.items():
