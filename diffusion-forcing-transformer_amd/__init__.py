@@ -16,6 +16,7 @@ from .training import ContextTraining, TrainingNoise, training_step_forward  # n
 from .checkpoint import load_reference_checkpoint  # noqa: F401,E402
 from .trainer import DiT3DTrainer, FacDiTTrainer, FacMatDiTTrainer  # noqa: F401,E402
 from . import uvit_train  # noqa: F401,E402
+from .uvit_train import UViT3DPoseTrainer, UViT3DTrainer  # noqa: F401,E402
 from .vae import VideoVAEDecoder, VideoVAEEncoder, VideoVAEPosterior, decode_latents, encode_videos  # noqa: F401,E402
 from .image_vae import (ImageVAEDecoder, ImageVAEEncoder, ImageVAEPosterior, decode_image_latents,  # noqa: F401,E402
                         encode_image_frames)  # noqa: F401,E402

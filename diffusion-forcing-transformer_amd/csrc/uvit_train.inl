@@ -1397,3 +1397,405 @@ int dfot_op_outgrad_gather(const float* dout, void* dpatch, int bt, int res, int
   return DFOT_OK;
 }
 }  // extern "C"
+
+// ---- per-frame FiLM forms of the four training norm kernels (pose-free UViT3D: u_vit3d.py:306-310, u_vit_blocks.py:89) ------------------
+// The pose-free model's embedding is ONE vector per frame, so (scale | shift) = film_vec [frames][ld] fp32 (columns 0..C | C..2C of the
+// block's column block) replaces the [rows][2C] bf16 FiLM matrix, and the backward leaves the FiLM gradient already summed over the frame's
+// rows: dfilm_vec [frames][ld] fp32, dscale[f][c] = sum_rows dz (xhat gamma + beta), dshift[f][c] = sum_rows dz.  A workgroup only ever
+// touches rows of one frame; it stores one partial row with plain stores and det_sum adds a frame's partial rows in a fixed order (its
+// batch form: one batch per frame) -- no float atomics, bit-reproducible.  Per-channel constants (gamma, beta, the frame's scale / shift,
+// the group statistics) are loaded once per thread and kept in registers over the thread's pixels.
+namespace dfot {
+namespace {
+
+// thread layout shared by the three GroupNorm kernels: C / 4 lanes cover a pixel row with 16-byte accesses, the 256 / (C / 4) lane groups take
+// alternate pixels of the workgroup's chunk.  grid = (frame, pixel chunk)
+__global__ __launch_bounds__(256) void gn_silu_fwd_frame_kernel(const float* __restrict__ x, const float* __restrict__ stats,
+                                                                const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                                const float* __restrict__ film_vec, long ldv, bf16* __restrict__ out, int P, int C,
+                                                                int chunk) {
+  typedef __attribute__((ext_vector_type(4))) float f4;
+  const int bt = blockIdx.x, p0 = blockIdx.y * chunk;
+  const int cq = C / 4, cpg = C / 32;
+  const int lanes = cq < 256 ? cq : 256, groups = 256 / lanes;
+  const int lane = threadIdx.x % lanes, rg = threadIdx.x / lanes;
+  const int c = lane * 4, grp = c / cpg;
+  const float mean = stats[((long)bt * 32 + grp) * 2], rstd = stats[((long)bt * 32 + grp) * 2 + 1];
+  const f4 ga = *reinterpret_cast<const f4*>(gamma + c), be = *reinterpret_cast<const f4*>(beta + c);
+  const f4 sc = *reinterpret_cast<const f4*>(film_vec + (long)bt * ldv + c), sh = *reinterpret_cast<const f4*>(film_vec + (long)bt * ldv + C + c);
+  const int p1 = p0 + chunk < P ? p0 + chunk : P;
+#pragma unroll 4
+  for (int p = p0 + rg; p < p1; p += groups) {
+    const long e = ((long)bt * P + p) * C + c;
+    const f4 xv = *reinterpret_cast<const f4*>(x + e);
+    bf16x4 o;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float z = ((xv[j] - mean) * rstd * ga[j] + be[j]) * (1.0f + sc[j]) + sh[j];
+      o[j] = f2bf(silu_f(z));
+    }
+    *reinterpret_cast<bf16x4*>(out + e) = o;
+  }
+}
+
+// pass 1 of the backward: the workgroup's partial row  dgamma [C] | dbeta [C] | (sum dxhat, sum dxhat xhat) [32][2] | dscale [C] | dshift [C]
+__global__ __launch_bounds__(256) void gn_bwd_reduce_frame_kernel(const float* __restrict__ x, const bf16* __restrict__ dy, const float* __restrict__ stats,
+                                                                  const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                                  const float* __restrict__ film_vec, long ldv, float* __restrict__ part, int P, int C,
+                                                                  int chunk) {
+  typedef __attribute__((ext_vector_type(4))) float f4;
+  __shared__ f4 red[6][256];  // [quantity][thread]
+  const int bt = blockIdx.x, p0 = blockIdx.y * chunk;
+  const int cq = C / 4, cpg = C / 32;
+  const int lanes = cq < 256 ? cq : 256, groups = 256 / lanes;
+  const int lane = threadIdx.x % lanes, rg = threadIdx.x / lanes;
+  const int c = lane * 4, grp = c / cpg;
+  const float mean = stats[((long)bt * 32 + grp) * 2], rstd = stats[((long)bt * 32 + grp) * 2 + 1];
+  const f4 ga = *reinterpret_cast<const f4*>(gamma + c), be = *reinterpret_cast<const f4*>(beta + c);
+  const f4 sc = *reinterpret_cast<const f4*>(film_vec + (long)bt * ldv + c), sh = *reinterpret_cast<const f4*>(film_vec + (long)bt * ldv + C + c);
+  f4 dgm = {0.f, 0.f, 0.f, 0.f}, dbt = dgm, s1 = dgm, s2 = dgm, dsc = dgm, dsh = dgm;
+  const int p1 = p0 + chunk < P ? p0 + chunk : P;
+#pragma unroll 4
+  for (int p = p0 + rg; p < p1; p += groups) {
+    const long e = ((long)bt * P + p) * C + c;
+    const f4 xv = *reinterpret_cast<const f4*>(x + e), dv = gn_load_dy4(dy + e);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float xh = (xv[j] - mean) * rstd;
+      const float gv = xh * ga[j] + be[j];
+      const float mul = 1.0f + sc[j];
+      const float dz = dv[j] * silu_grad(gv * mul + sh[j]);
+      const float dg = dz * mul;
+      dsc[j] += dz * gv;
+      dsh[j] += dz;
+      dgm[j] += dg * xh;
+      dbt[j] += dg;
+      s1[j] += dg * ga[j];
+      s2[j] += dg * ga[j] * xh;
+    }
+  }
+  red[0][threadIdx.x] = dgm; red[1][threadIdx.x] = dbt; red[2][threadIdx.x] = s1; red[3][threadIdx.x] = s2;
+  red[4][threadIdx.x] = dsc; red[5][threadIdx.x] = dsh;
+  __syncthreads();
+  if (threadIdx.x < lanes) {
+    for (int g = 1; g < groups; ++g) {
+      const int t = g * lanes + lane;
+      dgm += red[0][t]; dbt += red[1][t]; s1 += red[2][t]; s2 += red[3][t]; dsc += red[4][t]; dsh += red[5][t];
+    }
+    float* prow = part + ((long)bt * gridDim.y + blockIdx.y) * (4L * C + 64);
+    *reinterpret_cast<f4*>(prow + c) = dgm;
+    *reinterpret_cast<f4*>(prow + C + c) = dbt;
+    *reinterpret_cast<f4*>(prow + 2L * C + 64 + c) = dsc;
+    *reinterpret_cast<f4*>(prow + 3L * C + 64 + c) = dsh;
+    float a1 = (s1[0] + s1[1]) + (s1[2] + s1[3]), a2 = (s2[0] + s2[1]) + (s2[2] + s2[3]);
+    const int lpg = cpg / 4;  // lanes per group: 1, 2, 4 or 8 consecutive lanes
+    for (int o = 1; o < lpg; o <<= 1) {
+      a1 += __shfl_xor(a1, o);
+      a2 += __shfl_xor(a2, o);
+    }
+    if (lane % lpg == 0) {
+      prow[2L * C + grp * 2] = a1;
+      prow[2L * C + grp * 2 + 1] = a2;
+    }
+  }
+}
+
+// pass 2: dx = (dres ? dres : 0) + the norm's input gradient, as fp32 (dx) and / or bf16 (dx_bf); no FiLM-gradient store
+__global__ __launch_bounds__(256) void gn_bwd_apply_frame_kernel(const float* __restrict__ x, const bf16* __restrict__ dy, const float* __restrict__ stats,
+                                                                 const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                                 const float* __restrict__ film_vec, long ldv, const float* __restrict__ sums,
+                                                                 const float* __restrict__ dres, float* __restrict__ dx, bf16* __restrict__ dx_bf, int P,
+                                                                 int C, int chunk) {
+  typedef __attribute__((ext_vector_type(4))) float f4;
+  const int bt = blockIdx.x, p0 = blockIdx.y * chunk;
+  const int cq = C / 4, cpg = C / 32;
+  const int lanes = cq < 256 ? cq : 256, groups = 256 / lanes;
+  const int lane = threadIdx.x % lanes, rg = threadIdx.x / lanes;
+  const int c = lane * 4, grp = c / cpg;
+  const float mean = stats[((long)bt * 32 + grp) * 2], rstd = stats[((long)bt * 32 + grp) * 2 + 1];
+  const float inv_n = 1.0f / ((float)P * (float)cpg);
+  const float s1 = sums[((long)bt * 32 + grp) * 2] * inv_n, s2 = sums[((long)bt * 32 + grp) * 2 + 1] * inv_n;
+  const f4 ga = *reinterpret_cast<const f4*>(gamma + c), be = *reinterpret_cast<const f4*>(beta + c);
+  const f4 sc = *reinterpret_cast<const f4*>(film_vec + (long)bt * ldv + c), sh = *reinterpret_cast<const f4*>(film_vec + (long)bt * ldv + C + c);
+  const int p1 = p0 + chunk < P ? p0 + chunk : P;
+#pragma unroll 4
+  for (int p = p0 + rg; p < p1; p += groups) {
+    const long e = ((long)bt * P + p) * C + c;
+    const f4 xv = *reinterpret_cast<const f4*>(x + e), dv = gn_load_dy4(dy + e);
+    f4 v;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float xh = (xv[j] - mean) * rstd;
+      const float gv = xh * ga[j] + be[j];
+      const float mul = 1.0f + sc[j];
+      const float dz = dv[j] * silu_grad(gv * mul + sh[j]);
+      v[j] = rstd * (dz * mul * ga[j] - s1 - xh * s2);
+    }
+    if (dres) v += *reinterpret_cast<const f4*>(dres + e);
+    if (dx) *reinterpret_cast<f4*>(dx + e) = v;
+    if (dx_bf) {
+      bf16x4 o;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) o[j] = f2bf(v[j]);
+      *reinterpret_cast<bf16x4*>(dx_bf + e) = o;
+    }
+  }
+}
+
+inline int gn_frame_chunk(int P) { return P >= 4096 ? 512 : 64; }  // pixels per workgroup, as gn_silu_backward
+
+// NormalizeWithCond with a per-frame vector.  grid = (row chunk of a frame, frame); a wave keeps w, 1 + scale and shift of ITS frame in
+// registers and walks the chunk's rows (wave w takes rows w, w + 4, ...: a chunk shorter than 4 rows leaves waves idle, never a wrong frame)
+template <int VEC, int CNT>
+__global__ __launch_bounds__(256) void rms_film_fwd_frame_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                                 const float* __restrict__ film_vec, long ldv, bf16* __restrict__ out, int rpf, int chunk,
+                                                                 float eps) {
+  typedef typename VecT<VEC>::type V;
+  constexpr int C = 64 * VEC * CNT;
+  const int lane = threadIdx.x & 63;
+  const long frame = blockIdx.y;
+  const int r0 = blockIdx.x * chunk, r1 = r0 + chunk < rpf ? r0 + chunk : rpf;
+  const float* fv = film_vec + frame * ldv;
+  V wv[CNT], sc1[CNT], sh[CNT];
+#pragma unroll
+  for (int i = 0; i < CNT; ++i) {
+    const int c0 = (i * 64 + lane) * VEC;
+    wv[i] = *reinterpret_cast<const V*>(w + c0);
+    sc1[i] = *reinterpret_cast<const V*>(fv + c0) + 1.0f;
+    sh[i] = *reinterpret_cast<const V*>(fv + C + c0);
+  }
+  for (int rr = r0 + (threadIdx.x >> 6); rr < r1; rr += 4) {
+    const long row = frame * rpf + rr;
+    const float* xr = x + row * C;
+    V xv[CNT];
+    float ss = 0.f;
+#pragma unroll
+    for (int i = 0; i < CNT; ++i) {
+      xv[i] = *reinterpret_cast<const V*>(xr + (i * 64 + lane) * VEC);
+      ss += vdot<VEC>(xv[i], xv[i]);
+    }
+    const float r = rsqrtf(wave_sum(ss) / (float)C + eps);
+#pragma unroll
+    for (int i = 0; i < CNT; ++i) {
+      const int c0 = (i * 64 + lane) * VEC;
+      const V y = xv[i] * r * wv[i] * sc1[i] + sh[i];
+#pragma unroll
+      for (int j = 0; j < VEC; ++j) {
+        float yj;
+        if constexpr (VEC == 1) yj = y; else yj = y[j];
+        out[row * C + c0 + j] = f2bf(yj);
+      }
+    }
+  }
+}
+
+// backward: dx = dres + the norm's input gradient (+ bf16 copy); the workgroup's partial row  dw [C] | dscale [C] | dshift [C]  of its frame.
+// With the frame's scale fixed over the chunk, dw and dscale are two multiples of ONE sum a[c] = sum_rows dxn x r:
+//   dw[c] += (1 + scale[c]) a[c],  dscale[c] = w[c] a[c]   (products, never a division by 1 + scale)
+template <int VEC, int CNT>
+__global__ __launch_bounds__(256) void rms_film_bwd_frame_kernel(const float* __restrict__ x, const float* __restrict__ dxn, const float* __restrict__ w,
+                                                                 const float* __restrict__ film_vec, long ldv, const float* __restrict__ dres,
+                                                                 float* __restrict__ dx, bf16* __restrict__ dx_bf, float* __restrict__ part, int rpf,
+                                                                 int chunk, float eps) {
+  typedef typename VecT<VEC>::type V;
+  constexpr int C = 64 * VEC * CNT;
+  __shared__ float red[4][C];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const long frame = blockIdx.y;
+  const int r0 = blockIdx.x * chunk, r1 = r0 + chunk < rpf ? r0 + chunk : rpf;
+  const float* fv = film_vec + frame * ldv;
+  V gw[CNT];  // (1 + scale) w: the factor between dxn and the gradient of x r
+  float aacc[CNT * VEC], sacc[CNT * VEC];
+#pragma unroll
+  for (int i = 0; i < CNT; ++i) {
+    const int c0 = (i * 64 + lane) * VEC;
+    gw[i] = (*reinterpret_cast<const V*>(fv + c0) + 1.0f) * *reinterpret_cast<const V*>(w + c0);
+  }
+#pragma unroll
+  for (int i = 0; i < CNT * VEC; ++i) aacc[i] = sacc[i] = 0.f;
+  for (int rr = r0 + wave; rr < r1; rr += 4) {
+    const long row = frame * rpf + rr;
+    const float* xr = x + row * C;
+    const float* gr = dxn + row * C;
+    V xv[CNT], gv[CNT];
+    float ss = 0.f;
+#pragma unroll
+    for (int i = 0; i < CNT; ++i) {
+      xv[i] = *reinterpret_cast<const V*>(xr + (i * 64 + lane) * VEC);
+      ss += vdot<VEC>(xv[i], xv[i]);
+    }
+    const float r = rsqrtf(wave_sum(ss) / (float)C + eps);
+    float gx = 0.f;
+#pragma unroll
+    for (int i = 0; i < CNT; ++i) {
+      const int c0 = (i * 64 + lane) * VEC;
+      const V d = *reinterpret_cast<const V*>(gr + c0);
+      gv[i] = d * gw[i];
+      gx += vdot<VEC>(gv[i], xv[i]);
+#pragma unroll
+      for (int j = 0; j < VEC; ++j) {
+        float dj, xj;
+        if constexpr (VEC == 1) { dj = d; xj = xv[i]; } else { dj = d[j]; xj = xv[i][j]; }
+        aacc[i * VEC + j] += dj * xj * r;
+        sacc[i * VEC + j] += dj;
+      }
+    }
+    const float m = wave_sum(gx) / (float)C * r * r;
+#pragma unroll
+    for (int i = 0; i < CNT; ++i) {
+      const int c0 = (i * 64 + lane) * VEC;
+      const V o = (gv[i] - xv[i] * m) * r + *reinterpret_cast<const V*>(dres + row * C + c0);
+      *reinterpret_cast<V*>(dx + row * C + c0) = o;
+      if (dx_bf) {
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) {
+          float oj;
+          if constexpr (VEC == 1) oj = o; else oj = o[j];
+          dx_bf[row * C + c0 + j] = f2bf(oj);
+        }
+      }
+    }
+  }
+  float* prow = part + (frame * gridDim.x + blockIdx.x) * (3L * C);
+#pragma unroll
+  for (int i = 0; i < CNT; ++i)
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) red[wave][(i * 64 + lane) * VEC + j] = aacc[i * VEC + j];
+  __syncthreads();
+  for (int c = threadIdx.x; c < C; c += 256) {
+    const float a = (red[0][c] + red[1][c]) + (red[2][c] + red[3][c]);
+    prow[c] = a * (1.0f + fv[c]);
+    prow[C + c] = a * w[c];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i < CNT; ++i)
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) red[wave][(i * 64 + lane) * VEC + j] = sacc[i * VEC + j];
+  __syncthreads();
+  for (int c = threadIdx.x; c < C; c += 256) prow[2L * C + c] = (red[0][c] + red[1][c]) + (red[2][c] + red[3][c]);
+}
+
+inline bool rms_width_ok(int hidden) {  // the widths DIT_LN_DISPATCH has an instance for
+  if (hidden <= 0 || hidden % 64) return false;
+  if (hidden % 128 == 0) return hidden / 128 <= 10 || hidden / 128 == 12 || hidden / 128 == 16;
+  return hidden / 64 <= 9;
+}
+inline bool frame_vec_ok(const float* v, int64_t ld, int channels) { return v && ld >= 2L * channels && ld % 4 == 0 && ((uintptr_t)v & 15) == 0; }
+
+}  // namespace
+}  // namespace dfot
+
+extern "C" {
+using namespace dfot;
+
+int dfot_op_gn_silu_fwd_frame(const float* x, const float* gamma, const float* beta, const float* film_vec, int64_t film_ld, float eps, void* out,
+                              float* stats, int bt, int pixels, int channels, void* stream) {
+  DFOT_REQUIRE(x && gamma && beta && film_vec && out && stats && bt > 0 && pixels > 0, DFOT_ERR_ARG, "op_gn_silu_fwd_frame: null argument or empty shape");
+  DFOT_REQUIRE(channels == 128 || channels == 256 || channels == 512 || channels == 1024, DFOT_ERR_SHAPE,
+               "op_gn_silu_fwd_frame: channels %d must be 128, 256, 512 or 1024", channels);
+  DFOT_REQUIRE(frame_vec_ok(film_vec, film_ld, channels), DFOT_ERR_ARG,
+               "op_gn_silu_fwd_frame: film_vec needs a row stride >= 2C that is a multiple of 4 floats (got %ld) and 16-byte alignment", (long)film_ld);
+  hipStream_t s = (hipStream_t)stream;
+  const int chunk = gn_frame_chunk(pixels), chunks = cdiv(pixels, chunk);
+  DFOT_REQUIRE(chunks <= 65535, DFOT_ERR_SHAPE, "op_gn_silu_fwd_frame: %d pixels per frame", pixels);
+  void* part = nullptr;
+  const int nblk = gn_partial_blocks(pixels);
+  int rc = op_scratch(6, (size_t)bt * nblk * 64 * sizeof(float), &part);
+  if (rc) return rc;
+  if ((rc = launch_gn_partial_f32(x, (float*)part, bt, pixels, channels, s))) return rc;
+  if ((rc = launch_gn_finalize((const float*)part, stats, bt, nblk, pixels, channels, eps, s))) return rc;
+  hipLaunchKernelGGL(gn_silu_fwd_frame_kernel, dim3(bt, chunks), dim3(256), 0, s, x, stats, gamma, beta, film_vec, (long)film_ld, (bf16*)out, pixels,
+                     channels, chunk);
+  DFOT_CHECK_HIP(hipGetLastError());
+  return DFOT_OK;
+}
+
+int dfot_op_gn_silu_bwd_frame(const float* x, const void* dy_bf, const float* stats, const float* gamma, const float* beta, const float* film_vec,
+                              int64_t film_ld, const float* dres, float* dx, void* dx_bf, float* dfilm_vec, int64_t dfilm_ld, float* dgamma,
+                              float* dbeta, int bt, int pixels, int channels, void* stream) {
+  DFOT_REQUIRE(x && dy_bf && stats && gamma && beta && film_vec && (dx || dx_bf) && dfilm_vec && dgamma && dbeta && (!dres || dres != dx) && bt > 0 &&
+                   pixels > 0,
+               DFOT_ERR_ARG, "op_gn_silu_bwd_frame: null or aliased argument, or empty shape");
+  DFOT_REQUIRE(channels == 128 || channels == 256 || channels == 512 || channels == 1024, DFOT_ERR_SHAPE,
+               "op_gn_silu_bwd_frame: channels %d must be 128, 256, 512 or 1024", channels);
+  DFOT_REQUIRE(frame_vec_ok(film_vec, film_ld, channels) && dfilm_ld >= 2L * channels, DFOT_ERR_ARG,
+               "op_gn_silu_bwd_frame: film_vec / dfilm_vec need row strides >= 2C (got %ld, %ld; film_vec's a multiple of 4 floats, 16-byte aligned)",
+               (long)film_ld, (long)dfilm_ld);
+  hipStream_t s = (hipStream_t)stream;
+  const int C = channels, chunk = gn_frame_chunk(pixels), chunks = cdiv(pixels, chunk);
+  DFOT_REQUIRE(chunks <= 65535, DFOT_ERR_SHAPE, "op_gn_silu_bwd_frame: %d pixels per frame", pixels);
+  void* sums = nullptr;
+  int rc = op_scratch(4, (size_t)bt * 64 * sizeof(float), &sums);
+  if (rc) return rc;
+  const long rowlen = 4L * C + 64;
+  float* part = nullptr;
+  if ((rc = det_scratch(2, (size_t)bt * chunks * rowlen, &part))) return rc;
+  const dim3 grid(bt, chunks);
+  hipLaunchKernelGGL(gn_bwd_reduce_frame_kernel, grid, dim3(256), 0, s, x, (const bf16*)dy_bf, stats, gamma, beta, film_vec, (long)film_ld, part, pixels, C,
+                     chunk);
+  DFOT_CHECK_HIP(hipGetLastError());
+  // fixed-order sums of the partial rows: group sums and the FiLM gradient per frame (batch form), dgamma / dbeta over all frames
+  if ((rc = det_sum(part + 2L * C, rowlen, chunks, 64, (float*)sums, false, s, bt, (long)chunks * rowlen, 64))) return rc;
+  if ((rc = det_sum(part + 2L * C + 64, rowlen, chunks, 2 * C, dfilm_vec, false, s, bt, (long)chunks * rowlen, (long)dfilm_ld))) return rc;
+  if ((rc = det_sum(part, rowlen, bt * chunks, C, dgamma, false, s))) return rc;
+  if ((rc = det_sum(part + C, rowlen, bt * chunks, C, dbeta, false, s))) return rc;
+  hipLaunchKernelGGL(gn_bwd_apply_frame_kernel, grid, dim3(256), 0, s, x, (const bf16*)dy_bf, stats, gamma, beta, film_vec, (long)film_ld,
+                     (const float*)sums, dres, dx, (bf16*)dx_bf, pixels, C, chunk);
+  DFOT_CHECK_HIP(hipGetLastError());
+  return DFOT_OK;
+}
+
+int dfot_op_rms_film_fwd_frame(const float* x, const float* w, const float* film_vec, int64_t film_ld, float eps, void* out, int64_t rows,
+                               int64_t rows_per_frame, int channels, void* stream) {
+  DFOT_REQUIRE(x && w && film_vec && out && rows > 0 && rows_per_frame > 0 && rows % rows_per_frame == 0, DFOT_ERR_ARG,
+               "op_rms_film_fwd_frame: null argument, or %ld rows are not whole frames of %ld", (long)rows, (long)rows_per_frame);
+  DFOT_REQUIRE(rms_width_ok(channels), DFOT_ERR_SHAPE, "op_rms_film_fwd_frame: width %d has no kernel instance", channels);
+  DFOT_REQUIRE(frame_vec_ok(film_vec, film_ld, channels), DFOT_ERR_ARG,
+               "op_rms_film_fwd_frame: film_vec needs a row stride >= 2C that is a multiple of 4 floats (got %ld) and 16-byte alignment", (long)film_ld);
+  const long frames = rows / rows_per_frame;
+  DFOT_REQUIRE(frames <= 65535 && rows_per_frame <= (1L << 30), DFOT_ERR_SHAPE, "op_rms_film_fwd_frame: %ld frames of %ld rows", frames, (long)rows_per_frame);
+  hipStream_t s = (hipStream_t)stream;
+  const int hidden = channels, rpf = (int)rows_per_frame, chunk = 32, chunks = cdiv(rpf, chunk);  // 8 rows per wave
+#define CALL(V, C) \
+  hipLaunchKernelGGL((rms_film_fwd_frame_kernel<V, C>), dim3(chunks, (int)frames), dim3(256), 0, s, x, w, film_vec, (long)film_ld, (bf16*)out, rpf, chunk, eps)
+  DIT_LN_DISPATCH(CALL)
+#undef CALL
+  DFOT_CHECK_HIP(hipGetLastError());
+  return DFOT_OK;
+}
+
+int dfot_op_rms_film_bwd_frame(const float* x, const float* dxn, const float* w, const float* film_vec, int64_t film_ld, float eps, const float* dres,
+                               float* dx, void* dx_bf, float* dfilm_vec, int64_t dfilm_ld, float* dw, int64_t rows, int64_t rows_per_frame, int channels,
+                               void* stream) {
+  DFOT_REQUIRE(x && dxn && w && film_vec && dres && dx && dfilm_vec && dw && dres != dx && rows > 0 && rows_per_frame > 0 && rows % rows_per_frame == 0,
+               DFOT_ERR_ARG, "op_rms_film_bwd_frame: null or aliased argument, or %ld rows are not whole frames of %ld", (long)rows, (long)rows_per_frame);
+  DFOT_REQUIRE(rms_width_ok(channels), DFOT_ERR_SHAPE, "op_rms_film_bwd_frame: width %d has no kernel instance", channels);
+  DFOT_REQUIRE(frame_vec_ok(film_vec, film_ld, channels) && dfilm_ld >= 2L * channels, DFOT_ERR_ARG,
+               "op_rms_film_bwd_frame: film_vec / dfilm_vec need row strides >= 2C (got %ld, %ld; film_vec's a multiple of 4 floats, 16-byte aligned)",
+               (long)film_ld, (long)dfilm_ld);
+  const long frames = rows / rows_per_frame;
+  DFOT_REQUIRE(frames <= 65535 && rows_per_frame <= (1L << 30), DFOT_ERR_SHAPE, "op_rms_film_bwd_frame: %ld frames of %ld rows", frames, (long)rows_per_frame);
+  hipStream_t s = (hipStream_t)stream;
+  const int hidden = channels, rpf = (int)rows_per_frame;
+  // row chunks per frame: ~1024 workgroups in all, at least 4 rows (one per wave) each
+  int chunks = (int)(1024 / frames);
+  if (chunks > cdiv(rpf, 4)) chunks = cdiv(rpf, 4);
+  if (chunks < 1) chunks = 1;
+  const int chunk = cdiv(rpf, chunks);
+  chunks = cdiv(rpf, chunk);
+  float* part = nullptr;
+  int rc = det_scratch(2, (size_t)frames * chunks * 3 * hidden, &part);
+  if (rc) return rc;
+#define CALL(V, C)                                                                                                                                  \
+  hipLaunchKernelGGL((rms_film_bwd_frame_kernel<V, C>), dim3(chunks, (int)frames), dim3(256), 0, s, x, dxn, w, film_vec, (long)film_ld, dres, dx, \
+                     (bf16*)dx_bf, part, rpf, chunk, eps)
+  DIT_LN_DISPATCH(CALL)
+#undef CALL
+  DFOT_CHECK_HIP(hipGetLastError());
+  const long rowlen = 3L * hidden;
+  if ((rc = det_sum(part, rowlen, (int)(frames * chunks), hidden, dw, false, s))) return rc;
+  return det_sum(part + hidden, rowlen, chunks, 2 * hidden, dfilm_vec, false, s, (int)frames, (long)chunks * rowlen, (long)dfilm_ld);
+}
+
+}  // extern "C"

@@ -7,6 +7,7 @@
   python examples/train.py facmat   [--xl] [--batch 8]                                # FacMatDiT (dit3d_factorized_matrix.yaml); --xl: XL-64-1, taichikl shape
   python examples/train.py facdit   [--xl] [--batch 8]                                # FacDiT (dit3d_factorized_attention.yaml); --xl: @DiT/XL widths, taichikl shape
   python examples/train.py re10k    [--batch 8]                                       # RE10K UViT3DPose (BASELINE config 5), synthetic frames + poses
+  python examples/train.py uvit3d   [--cond action:4] [--full] [--batch 2]            # pose-free UViT3D (u_vit3d.yaml); --full: its widths, 8 heads, 256 x 256
   python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 examples/train.py k600   # data parallel, one rank per GPU
 
 Data are synthetic latents (no dataset offline), or with --pixels synthetic 17 x 128 x 128 frames encoded online the way the K600
@@ -34,7 +35,7 @@ K600_DATA_STD = [5.591, 5.257, 7.033, 6.401, 6.091, 11.233, 5.608, 7.5, 5.277, 5
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("model", choices=["k600", "k600diff", "facmat", "facdit", "re10k"])
+    ap.add_argument("model", choices=["k600", "k600diff", "facmat", "facdit", "re10k", "uvit3d"])
     ap.add_argument("--ckpt")
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--batch", type=int, default=8)
@@ -48,6 +49,9 @@ def main():
                          "training schedule shifted 0.125, sigmoid loss weighting)")
     ap.add_argument("--xl", action="store_true", help="facmat / facdit: @FacMatDiT/XL-64-1 / @DiT/XL widths at the taichikl shape (4x32x32 latents, "
                                                       "patch 2, 16 frames) instead of the tiny default (width 128, depth 2, 4x16x8 latents, 5 frames)")
+    ap.add_argument("--full", action="store_true", help="uvit3d: the widths, depths and dropouts of u_vit3d.yaml with num_heads 8 (its 4 heads give head "
+                                                        "dim 256, which the attention kernels do not take) on 8 frames of 3 x 256 x 256, instead of the "
+                                                        "tiny default (channels 128/128/128/256, 2 heads, one block per level, 8 frames of 3 x 64 x 64)")
     ap.add_argument("--pixels", action="store_true", help="k600 / k600diff: encode synthetic frames online with the VideoVAE encoder")
     ap.add_argument("--vae-ckpt", help="--pixels: reference VideoVAE checkpoint (vae.* keys); random encoder weights otherwise")
     a = ap.parse_args()
@@ -59,6 +63,8 @@ def main():
         dist.init_process_group("nccl", device_id=torch.device("cuda", torch.cuda.current_device()))
     if a.model == "re10k":
         return train_re10k(a, rank, world)
+    if a.model == "uvit3d":
+        return train_uvit3d(a, rank, world)
     if a.model in ("facmat", "facdit"):
         return train_factorized(a, rank, world)
     diff = a.model == "k600diff"
@@ -225,6 +231,72 @@ def train_re10k(a, rank, world):
         loss = trainer.loss_and_grads(frames, cond, levels, noise, loss_masks, diffusion=dcfg, reducer=reducer)
         lr = lr_at_step(step, a.lr, "constant_with_warmup", a.warmup_steps)  # realestate10k_video_generation.yaml:19-22
         trainer.optimizer_step(lr=lr, world_size=world)
+        if rank == 0 and (step % 5 == 0 or step == a.steps - 1):
+            print(f"step {step:4d}  loss {float(loss.item()):.4f}  {(time.perf_counter() - t0) / (step + 1) * 1e3:.1f} ms/step", flush=True)
+    if a.save and rank == 0:
+        torch.save({"state_dict": {"diffusion_model.model." + k: v.cpu() for k, v in trainer.state_dict().items()}}, a.save)
+        print("saved", a.save)
+    if world > 1:
+        import torch.distributed as dist
+        dist.barrier()
+        dist.destroy_process_group()
+
+
+UVIT3D_TINY = dict(channels=[128, 128, 128, 256], emb_channels=128, block_dropouts=[0.0, 0.0, 0.0, 0.0], num_updown_blocks=[1, 1, 1], num_mid_blocks=1,
+                   num_heads=2)
+UVIT3D_FULL = dict(channels=[128, 256, 512, 1024], emb_channels=1024, block_dropouts=[0.0, 0.0, 0.1, 0.1], num_updown_blocks=[3, 3, 3], num_mid_blocks=16,
+                   num_heads=8)
+
+
+def uvit3d_cfg(full: bool, cond_dim: int = 0):
+    """(backbone configuration, frame resolution) of the uvit3d entry; shared with tools/bench_ops.py"""
+    cfg = dict(UVIT3D_FULL if full else UVIT3D_TINY, name="u_vit3d", patch_size=2, pos_emb_type="rope", use_checkpointing=[False] * 4,
+               block_types=["ResBlock", "ResBlock", "TransformerBlock", "TransformerBlock"], use_fourier_noise_embedding=True)
+    if cond_dim:
+        cfg["external_cond_dropout"] = 0.1
+    return cfg, (256 if full else 64)
+
+
+def train_uvit3d(a, rank, world):
+    """DFoTVideo training of the pose-free U-ViT under continuous diffusion on the op-by-op UViT3DTrainer: unconditioned, or with a synthetic
+    action sequence (--cond action:DIM, per-video dropout 0.1 of the action embedding)"""
+    from dfot_amd import parallel
+    cdim = 0
+    if a.cond:
+        ctype, cdim = a.cond.split(":")[0], int(a.cond.split(":")[1])
+        if ctype != "action":
+            raise SystemExit("uvit3d: --cond action:DIM")
+    cfg, res = uvit3d_cfg(a.full, cdim)
+    tokens = 8
+    dcfg = dfot_amd.DiffusionConfig()  # training schedule (cosine, shift 0.125), sigmoid loss weighting (bias -1), precond_scale 0.125
+    init = dfot_amd.UViT3D(cfg, x_shape=(3, res, res), max_tokens=tokens, external_cond_dim=cdim)
+    if a.ckpt:
+        dfot_amd.load_reference_checkpoint(init, a.ckpt)
+    else:
+        init.init_random(seed=0)  # the same on every rank
+    trainer = dfot_amd.UViT3DTrainer({k: v.detach() for k, v in init.state_dict().items()},
+                                     dict(cfg, resolution=res, max_tokens=tokens, in_channels=3, cond_dim=cdim))
+    del init
+    trainer.dropout_generator = torch.Generator(device="cuda").manual_seed(4000 + rank)  # block_dropouts of the MLP branches
+    sampling = dfot_amd.TrainingNoise(noise_level="random_independent", is_continuous=True, n_context_tokens=1)
+    g = torch.Generator().manual_seed(1000 + rank)
+    masks = torch.ones(a.batch, tokens, dtype=torch.bool)
+    t0 = time.perf_counter()
+    for step in range(a.steps):
+        for _ in range(a.accumulate):
+            frames = torch.randn(a.batch, tokens, 3, res, res, generator=g)
+            noise = torch.randn(a.batch, tokens, 3, res, res, generator=g)
+            levels, loss_masks = sampling.sample(a.batch, tokens, masks, g, training=True)
+            conds = drop = None
+            if cdim:
+                conds = torch.randn(a.batch, tokens, cdim, generator=g)
+                conds[:, :1] = 0  # external_cond_processing: mask_first
+                drop = torch.rand(a.batch, generator=g) < 0.1
+            reducer = parallel.OverlappedGradReducer() if world > 1 and a.accumulate == 1 else None
+            loss = trainer.loss_and_grads(frames, conds, levels, noise, loss_masks, diffusion=dcfg, cond_drop=drop, reducer=reducer)
+            if a.accumulate > 1:
+                trainer.accumulate()
+        trainer.optimizer_step(lr=a.lr, world_size=world)
         if rank == 0 and (step % 5 == 0 or step == a.steps - 1):
             print(f"step {step:4d}  loss {float(loss.item()):.4f}  {(time.perf_counter() - t0) / (step + 1) * 1e3:.1f} ms/step", flush=True)
     if a.save and rank == 0:

@@ -571,6 +571,23 @@ int dfot_op_gn_silu_fwd2(const float* x, const float* gamma, const float* beta, 
 int dfot_op_gn_silu_bwd6(const float* x, const void* dy_bf, const float* stats, const float* gamma, const float* beta, const void* film,
                          int64_t film_ld, const float* dres, float* dx, void* dx_bf, void* dfilm, int64_t dfilm_ld, float* dgamma, float* dbeta, int bt,
                          int pixels, int channels, void* stream);
+/* Per-frame FiLM forms of the four training norm ops (pose-free UViT3D: the conditioning embedding is one vector per frame, u_vit3d.py:306-310).
+ * film_vec fp32 [frames][film_ld] holds the block's (scale | shift) in columns 0..C | C..2C and may be a column block of a level-wide table
+ * (film_ld >= 2C, a multiple of 4 floats; the pointer 16-byte aligned).  The backward writes the FiLM gradient already summed over each frame's
+ * rows, dfilm_vec fp32 [frames][dfilm_ld]: dscale[f][c] = sum_rows dz (xhat gamma + beta) | dshift[f][c] = sum_rows dz -- fixed-order fp32 sums of
+ * per-workgroup partial rows (no atomics: bit-reproducible), no [rows][2C] tensor read or written.  dgamma / dbeta / dw are written, not
+ * accumulated.  Shapes: channels 128, 256, 512 or 1024 (GroupNorm), a width with a LayerNorm kernel instance (RMS: 64 k, k odd <= 9, or 128 k,
+ * k <= 10, 12, 16), rows a multiple of rows_per_frame; anything else returns DFOT_ERR_SHAPE or DFOT_ERR_ARG before any launch. */
+int dfot_op_gn_silu_fwd_frame(const float* x, const float* gamma, const float* beta, const float* film_vec, int64_t film_ld, float eps, void* out,
+                              float* stats, int bt, int pixels, int channels, void* stream);
+int dfot_op_gn_silu_bwd_frame(const float* x, const void* dy_bf, const float* stats, const float* gamma, const float* beta, const float* film_vec,
+                              int64_t film_ld, const float* dres, float* dx, void* dx_bf, float* dfilm_vec, int64_t dfilm_ld, float* dgamma,
+                              float* dbeta, int bt, int pixels, int channels, void* stream);
+int dfot_op_rms_film_fwd_frame(const float* x, const float* w, const float* film_vec, int64_t film_ld, float eps, void* out, int64_t rows,
+                               int64_t rows_per_frame, int channels, void* stream);
+int dfot_op_rms_film_bwd_frame(const float* x, const float* dxn, const float* w, const float* film_vec, int64_t film_ld, float eps, const float* dres,
+                               float* dx, void* dx_bf, float* dfilm_vec, int64_t dfilm_ld, float* dw, int64_t rows, int64_t rows_per_frame, int channels,
+                               void* stream);
 /* out [bt][n] fp32 = per-frame column sums of src bf16 [bt * pixels][ld] (the gradient of the per-frame FiLM table from the FiLM gradients) */
 int dfot_op_frame_sums_bf16(const void* src, int64_t ld, float* out, int bt, int pixels, int n, void* stream);
 /* x fp32 = hi + lo, both bf16 (lo carries the next 8 mantissa bits): three bf16 products Ah Bh + Ah Bl + Al Bh with fp32 accumulation

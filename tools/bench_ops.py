@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Micro-benchmarks of the C-ABI primitives at the RE10K model shapes (model batch 2), HIP-event timed.
-Usage (GPU box): python tools/bench_ops.py [gemm] [conv] [attn] [tattn] [mattn] [tattn_bwd] [facdit_train] [mattn_bwd] [facmat_train] [vae_encode] [equal] [dit_front] [ivae] [uvit3d]"""
+Usage (GPU box): python tools/bench_ops.py [gemm] [conv] [attn] [tattn] [mattn] [tattn_bwd] [facdit_train] [mattn_bwd] [facmat_train] [vae_encode] [equal] [dit_front] [ivae] [uvit3d] [gnfilm_frame] [uvit3d_train]"""
 import ctypes as C
 import math
 import os
@@ -166,6 +166,74 @@ def uvit3d_forward(b=2):
         cond = torch.randn(b, 8, 180, 256, 256, device="cuda")
         out.append(timeit(lambda: pose(x, k, cond), iters=10, warm=3))  # the same cond tensor every call: the cache hits by identity
     return tuple(out)
+
+
+def uvit3d_train(b):
+    """one training step (loss, backward, clipped AdamW) of UViT3DTrainer at the `examples/train.py uvit3d --full` shape (u_vit3d.yaml widths,
+    8 heads, 8 frames of 3 x 256 x 256), MLP dropout on: (ms per step, peak device memory in GiB).  The FiLM path is the process's
+    DFOT_UVIT3D_TRAIN_ROW_FILM (1 = the per-row yardstick), so the two paths are timed in alternating processes"""
+    sys.path.insert(0, os.path.join(ROOT, "examples"))
+    from train import uvit3d_cfg
+    cfg, res = uvit3d_cfg(True)
+    init = dfot_amd.UViT3D(cfg, x_shape=(3, res, res), max_tokens=8, external_cond_dim=0)
+    init.init_random(seed=0)
+    tr = dfot_amd.UViT3DTrainer({k: v.detach() for k, v in init.state_dict().items()}, dict(cfg, resolution=res, max_tokens=8, in_channels=3, cond_dim=0))
+    del init
+    tr.dropout_generator = torch.Generator(device="cuda").manual_seed(0)
+    g = torch.Generator().manual_seed(1)
+    xs, noise = torch.randn(b, 8, 3, res, res, generator=g), torch.randn(b, 8, 3, res, res, generator=g)
+    t = torch.rand(b, 8, generator=g)
+
+    def step():
+        tr.loss_and_grads(xs, None, t, noise)
+        tr.optimizer_step(lr=5e-5)
+    torch.cuda.reset_peak_memory_stats()
+    ms = timeit(step, iters=5, warm=2)
+    return ms, torch.cuda.max_memory_allocated() / 2 ** 30, tr.row_film
+
+
+def gnfilm_frame(bt=64):
+    """the four per-frame FiLM norm ops next to their per-row counterparts at levels 0-3 of the `uvit3d --full` shape with B 8, T 8
+    (64 frames; GroupNorm at 128 / 256 channels, RMS at 512 / 1024): [(level, op, us frame, us row)].  The per-row backward is timed with the
+    frame_sums pass it needs for the same result"""
+    L = capi.lib
+    BF = torch.bfloat16
+    out = []
+    for lvl, (c, r) in enumerate(((128, 128), (256, 64), (512, 32), (1024, 16))):
+        P_, rows = r * r, bt * r * r
+        x = torch.randn(rows, c, device="cuda")
+        tab = torch.randn(bt, 2 * c, device="cuda") * 0.3
+        film = tab.to(BF).repeat_interleave(P_, 0).contiguous()
+        o = torch.empty(rows, c, dtype=BF, device="cuda")
+        dx, dxb = torch.empty(rows, c, device="cuda"), torch.empty(rows, c, dtype=BF, device="cuda")
+        dfilm, dtab, sums = torch.empty(rows, 2 * c, dtype=BF, device="cuda"), torch.empty(bt, 2 * c, device="cuda"), torch.empty(bt, 2 * c, device="cuda")
+        v1, v2, v3 = (torch.randn(c, device="cuda") for _ in range(3))
+        fs = lambda: capi.check(L.dfot_op_frame_sums_bf16(P(dfilm), 2 * c, P(sums), bt, P_, 2 * c, S()))
+        if lvl < 2:
+            stats = torch.empty(bt, 32, 2, device="cuda")
+            dy = torch.randn(rows, c, device="cuda").to(BF)
+            pairs = {
+                "gn_silu_fwd": (lambda: capi.check(L.dfot_op_gn_silu_fwd_frame(P(x), P(v1), P(v2), P(tab), 2 * c, 1e-6, P(o), P(stats), bt, P_, c, S())),
+                                lambda: capi.check(L.dfot_op_gn_silu_fwd2(P(x), P(v1), P(v2), P(film), 2 * c, 1e-6, P(o), P(stats), bt, P_, c, S()))),
+                "gn_silu_bwd": (lambda: capi.check(L.dfot_op_gn_silu_bwd_frame(P(x), P(dy), P(stats), P(v1), P(v2), P(tab), 2 * c, None, None, P(dxb), P(dtab),
+                                                                              2 * c, P(v3), P(v3), bt, P_, c, S())),
+                                lambda: (capi.check(L.dfot_op_gn_silu_bwd6(P(x), P(dy), P(stats), P(v1), P(v2), P(film), 2 * c, None, None, P(dxb), P(dfilm),
+                                                                          2 * c, P(v3), P(v3), bt, P_, c, S())), fs())),
+            }
+        else:
+            dxn, dres = torch.randn(rows, c, device="cuda"), torch.randn(rows, c, device="cuda")
+            pairs = {
+                "rms_film_fwd": (lambda: capi.check(L.dfot_op_rms_film_fwd_frame(P(x), P(v1), P(tab), 2 * c, 1e-6, P(o), rows, P_, c, S())),
+                                 lambda: capi.check(L.dfot_op_rms_film_fwd(P(x), P(v1), P(film), 1e-6, P(o), rows, c, S()))),
+                "rms_film_bwd": (lambda: capi.check(L.dfot_op_rms_film_bwd_frame(P(x), P(dxn), P(v1), P(tab), 2 * c, 1e-6, P(dres), P(dx), P(dxb), P(dtab), 2 * c,
+                                                                                P(v3), rows, P_, c, S())),
+                                 lambda: (capi.check(L.dfot_op_rms_film_bwd_res(P(x), P(dxn), P(v1), P(film), 1e-6, P(dres), P(dx), P(dxb), P(dfilm), P(v3),
+                                                                               rows, c, S())), fs())),
+            }
+        for name, (frame, row) in pairs.items():
+            for _ in range(3):  # alternate the two forms
+                out.append((lvl, name, c, rows, timeit(frame, iters=20, warm=3) * 1e3, timeit(row, iters=20, warm=3) * 1e3))
+    return out
 
 
 def mattn(b, tokens, e, h, cc, rr, rope):
@@ -365,6 +433,21 @@ def main():
     if "uvit3d" in what:
         free, pose = uvit3d_forward(2)
         print(f"uvit3d forward 256x256 Bm=2 T=8: UViT3D {free:.2f} ms, UViT3DPose.forward_cached {pose:.2f} ms, ratio {free / pose:.3f}")
+    if "gnfilm_frame" in what:
+        for lvl, name, c, rows, us_frame, us_row in gnfilm_frame():
+            print(f"gnfilm_frame L{lvl} {name:13s} C={c:4d} rows={rows:7d} (64 frames): per-frame {us_frame:8.1f} us  per-row {us_row:8.1f} us  "
+                  f"ratio {us_frame / us_row:.3f}", flush=True)
+    if "uvit3d_train" in what:
+        for b in (8, 4, 2, 1):  # the largest of these batches that fits
+            try:
+                ms, gib, row = uvit3d_train(b)
+            except (torch.cuda.OutOfMemoryError, capi.DfotError) as err:
+                print(f"uvit3d_train B={b}: does not fit ({type(err).__name__})", flush=True)
+                torch.cuda.empty_cache()
+                continue
+            print(f"uvit3d_train full widths B={b} T=8 256x256, {'per-row' if row else 'per-frame'} FiLM: {ms:.2f} ms per training step, peak memory "
+                  f"{gib:.2f} GiB", flush=True)
+            break
     if "dit_front" in what:
         xl = dict(name="dit3d", variant="full", pos_emb_type="rope_3d", patch_size=1, hidden_size=1152, depth=28, num_heads=16)
         dit_front("XL K600", xl, dfot_amd.DiT3D, (16, 16, 16), 5, 8, 5)  # @DiT/XL at the K600 latents: B = 8, T = 5, P = 256
