@@ -11,6 +11,8 @@ Mirrors (host logic only; the arithmetic on frames runs in libdfot_hip.so):
   * _generate_scheduling_matrix                     algorithms/common/base_pytorch_video_algo.py:877-913
 Everything here is numpy on the host, evaluated once per sampling call; the device kernels
 only ever see small fp32 coefficient tables (one row per (branch-batch, token)).
+The one noised forward + loss (+ loss gradient) of training and validation is at the end: ``denoising_tables`` (host) and
+``denoising_loss`` (device), for both diffusions.
 """
 from __future__ import annotations
 
@@ -231,3 +233,71 @@ class Schedule:
         else:
             raise ValueError(f"unknown loss weighting strategy {strategy}")
         return (eps_w * snr / (snr + f32(1))).astype(f32)
+
+
+# ---- the denoising loss of training and validation: DiscreteDiffusion.forward (discrete_diffusion.py:345-377, pred_v) and
+# ContinuousDiffusion.forward (continuous_diffusion.py:140-167), each followed by _reweight_loss (base_pytorch_video_algo.py:684-693) ----
+ALPHA, SIGMA, WEIGHT, LEVEL, COEF = range(5)  # rows of denoising_tables
+
+
+def denoising_tables(diffusion, levels, f: int, masks=None, grad: bool = False, loss_weighting: Optional[dict] = None):
+    """Per (video, token) rows of one denoising loss, (4 or 5, B, T) fp32 torch on the host: x_t = ALPHA x + SIGMA eps, the loss WEIGHT,
+    the LEVEL the model receives and, with `grad`, COEF = 2 w mask / (f B T): d mean(mask * per-token loss) / d error for f values per token.
+    `diffusion` decides which: a Schedule is discrete diffusion (levels: integer k; its tables and loss_weights(k, **loss_weighting), in
+    numpy fp32; LEVEL = k), a DiffusionConfig continuous diffusion (levels: t in [0, 1]; training_logsnr_tables in torch fp32;
+    LEVEL = precond_scale * logsnr)."""
+    import torch
+    b, t = levels.shape
+    if isinstance(diffusion, Schedule):
+        kk = levels.detach().cpu().numpy().astype(np.int64)
+        w = diffusion.loss_weights(kk, **(loss_weighting or {})).astype(np.float32)
+        rows = [diffusion.sqrt_alphas_cumprod[kk], diffusion.sqrt_one_minus_alphas_cumprod[kk], w, kk.astype(np.float32)]
+        if grad:
+            mk = np.ones((b, t), np.float32) if masks is None else masks.detach().cpu().numpy().astype(np.float32).reshape(b, t)
+            rows.append(2.0 * w * mk / (f * b * t))
+        return torch.from_numpy(np.stack(rows).astype(np.float32))
+    logsnr, alpha, sigma, weight = diffusion.training_logsnr_tables(levels)
+    rows = [alpha, sigma, weight, float(diffusion.precond_scale) * logsnr]
+    if grad:
+        mk = torch.ones(b, t) if masks is None else masks.detach().float().cpu().view(b, t)
+        rows.append(2.0 * weight * mk / (f * b * t))
+    return torch.stack(rows).float()
+
+
+def denoising_loss(diffusion, model, xs, levels, noise, masks=None, loss_weighting: Optional[dict] = None, want_x_pred: bool = False,
+                   want_grad: bool = False):
+    """One noised forward and its per-token loss on the device: clamp the noise, x_t = alpha x + sigma eps, v = model(x_t, LEVEL row),
+    the weighted squared error per token (dfot_vspace_loss for a Schedule, dfot_vpred_loss for a DiffusionConfig: see denoising_tables) and,
+    when asked for, the predicted x and d loss / d v of the masked mean.  xs, noise (B, T, ...); levels (B, T).
+    Returns (v, per_token (B, T), x_pred or None, dv or None); the loss is masked_mean(per_token, masks)."""
+    import torch
+    from . import capi
+    P, S, lib = capi.ptr, capi.stream_ptr, capi.lib
+    discrete = isinstance(diffusion, Schedule)
+    clip = float((diffusion.cfg if discrete else diffusion).clip_noise)
+    b, t = xs.shape[:2]
+    f = int(np.prod(xs.shape[2:]))
+    tab = denoising_tables(diffusion, levels, f, masks, want_grad, loss_weighting).cuda().contiguous()
+    x = xs.to(device="cuda", dtype=torch.float32).contiguous()
+    eps = noise.to(device="cuda", dtype=torch.float32).clamp(-clip, clip).contiguous()
+    x_t = torch.empty_like(x)
+    capi.check(lib.dfot_hg_prepare(P(x), P(eps), P(tab[ALPHA]), P(tab[SIGMA]), P(x_t), b, 1, t, f, S()))
+    v = model(x_t, tab[LEVEL].to(torch.int32) if discrete else tab[LEVEL]).contiguous()
+    x_pred = torch.empty_like(x) if want_x_pred else None
+    per_token = torch.empty(b, t, device="cuda")
+    scratch = torch.empty(int(lib.dfot_vpred_loss_scratch_floats(b, t, f)), device="cuda")
+    loss_fn = lib.dfot_vspace_loss if discrete else lib.dfot_vpred_loss
+    capi.check(loss_fn(P(x), P(eps), P(v), P(tab[ALPHA]), P(tab[SIGMA]), P(tab[WEIGHT]), P(x_pred), P(scratch), P(per_token), b, t, f, S()))
+    dv = None
+    if want_grad:
+        dv = torch.empty_like(x)
+        capi.check(lib.dfot_vloss_grad(P(x), P(eps), P(v), P(tab[ALPHA]), P(tab[SIGMA]), P(tab[COEF]), P(dv), b, t, f, int(discrete), S()))
+    return v, per_token, x_pred, dv
+
+
+def masked_mean(per_token, masks=None):
+    """_reweight_loss: the loss masks (B, T) multiply the per-token loss before the mean.  Returns (loss, masked per-token loss)."""
+    import torch
+    if masks is not None:
+        per_token = per_token * masks.to(device="cuda", dtype=torch.float32).reshape(per_token.shape)
+    return per_token.mean(), per_token

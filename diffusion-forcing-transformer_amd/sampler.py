@@ -26,7 +26,7 @@ import numpy as np
 import torch
 
 from . import capi, parallel
-from .diffusion import DiffusionConfig, Schedule
+from .diffusion import DiffusionConfig, Schedule, denoising_loss, masked_mean
 from .guidance import HistoryGuidance
 
 
@@ -143,31 +143,13 @@ class DFoTVideoPoseSampler:
         (algorithms/common/base_pytorch_video_algo.py:684-693) -- what ``training_step`` and the validation
         denoising loss evaluate (dfot_video.py:41-75).  t: (B,T) in [0,1] per-token noise levels.
         Returns (x_pred, loss scalar, per-token loss (B,T))."""
-        b, tk = xs.shape[:2]
-        f = int(np.prod(xs.shape[2:]))
-        # cosine logSNR schedule of the reference in fp32 (CosineNoiseSchedule, continuous_diffusion.py:46-92), limits / shift / loss
-        # weighting from the DiffusionConfig this sampler was built with (the same object the sampling Schedule honours)
-        logsnr, alpha, sigma, weight = self.cfg.diffusion.training_logsnr_tables(t)
-        tab = torch.stack([alpha, sigma, weight, self.cfg.diffusion.precond_scale * logsnr]).float().cuda().contiguous()
-        x = xs.to(device="cuda", dtype=torch.float32).contiguous()
         if noise is None:
-            noise = self.noise_fn("train", tuple(x.shape))
-        eps = noise.to(device="cuda", dtype=torch.float32).clamp(-self.cfg.diffusion.clip_noise, self.cfg.diffusion.clip_noise).contiguous()
-        ones = torch.ones(b, tk, device="cuda")
-        x_t = torch.empty_like(x)
-        capi.check(capi.lib.dfot_hg_prepare(capi.ptr(x), capi.ptr(eps), capi.ptr(tab[0]), capi.ptr(tab[1]), capi.ptr(x_t),
-                                            b, 1, tk, f, capi.stream_ptr()))
-        v = self.model(x_t, tab[3], self._process_conditions(conditions), None)
-        x_pred = torch.empty_like(x)
-        per_token = torch.empty(b, tk, device="cuda")
-        scratch = torch.empty(int(capi.lib.dfot_vpred_loss_scratch_floats(b, tk, f)), device="cuda")
-        capi.check(capi.lib.dfot_vpred_loss(capi.ptr(x), capi.ptr(eps), capi.ptr(v), capi.ptr(tab[0]), capi.ptr(tab[1]),
-                                            capi.ptr(tab[2]), capi.ptr(x_pred), capi.ptr(scratch), capi.ptr(per_token), b, tk, f,
-                                            capi.stream_ptr()))
-        del ones
-        if masks is not None:
-            per_token = per_token * masks.to(device="cuda", dtype=torch.float32).view(b, tk)
-        return x_pred, per_token.mean(), per_token
+            noise = self.noise_fn("train", tuple(xs.shape))
+        # schedule limits / shift / loss weighting from the DiffusionConfig this sampler was built with (the one the sampling Schedule honours)
+        _, per_token, x_pred, _ = denoising_loss(self.cfg.diffusion, lambda x_t, lv: self.model(x_t, lv, self._process_conditions(conditions), None),
+                                                 xs, t, noise, want_x_pred=True)
+        loss, per_token = masked_mean(per_token, masks)
+        return x_pred, loss, per_token
 
     @torch.no_grad()
     def discrete_denoising_loss(self, xs: torch.Tensor, k: torch.Tensor, noise: Optional[torch.Tensor] = None,
@@ -178,30 +160,12 @@ class DFoTVideoPoseSampler:
         Returns (x_pred, loss scalar, per-token loss (B,T))."""
         if self.cfg.diffusion.is_continuous:
             raise ValueError("discrete_denoising_loss needs DiffusionConfig(is_continuous=False)")
-        b, tk = xs.shape[:2]
-        f = int(np.prod(xs.shape[2:]))
-        kk = k.detach().cpu().numpy().astype(np.int64)
-        sch = self.schedule
-        tab = np.stack([sch.sqrt_alphas_cumprod[kk], sch.sqrt_one_minus_alphas_cumprod[kk],
-                        sch.loss_weights(kk, **(loss_weighting or {}))]).astype(np.float32)
-        tab = torch.from_numpy(tab).cuda().contiguous()
-        x = xs.to(device="cuda", dtype=torch.float32).contiguous()
         if noise is None:
-            noise = self.noise_fn("train", tuple(x.shape))
-        eps = noise.to(device="cuda", dtype=torch.float32).clamp(-self.cfg.diffusion.clip_noise, self.cfg.diffusion.clip_noise).contiguous()
-        x_k = torch.empty_like(x)
-        capi.check(capi.lib.dfot_hg_prepare(capi.ptr(x), capi.ptr(eps), capi.ptr(tab[0]), capi.ptr(tab[1]), capi.ptr(x_k),
-                                            b, 1, tk, f, capi.stream_ptr()))
-        v = self.model(x_k, k.to(device="cuda", dtype=torch.int32), None, None)
-        x_pred = torch.empty_like(x)
-        per_token = torch.empty(b, tk, device="cuda")
-        scratch = torch.empty(int(capi.lib.dfot_vpred_loss_scratch_floats(b, tk, f)), device="cuda")
-        capi.check(capi.lib.dfot_vspace_loss(capi.ptr(x), capi.ptr(eps), capi.ptr(v), capi.ptr(tab[0]), capi.ptr(tab[1]),
-                                             capi.ptr(tab[2]), capi.ptr(x_pred), capi.ptr(scratch), capi.ptr(per_token), b, tk, f,
-                                             capi.stream_ptr()))
-        if masks is not None:
-            per_token = per_token * masks.to(device="cuda", dtype=torch.float32).view(b, tk)
-        return x_pred, per_token.mean(), per_token
+            noise = self.noise_fn("train", tuple(xs.shape))
+        _, per_token, x_pred, _ = denoising_loss(self.schedule, lambda x_k, lv: self.model(x_k, lv, None, None), xs, k, noise,
+                                                 loss_weighting=loss_weighting, want_x_pred=True)
+        loss, per_token = masked_mean(per_token, masks)
+        return x_pred, loss, per_token
 
     # data (un)normalisation of the reference (algorithms/common/base_pytorch_video_algo.py:491-502)
     def _normalize_x(self, xs: torch.Tensor, mean, std) -> torch.Tensor:

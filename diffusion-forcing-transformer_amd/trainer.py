@@ -1,5 +1,5 @@
 """Training of the DiT3D backbone on the MI355X engine: hand-written forward-with-saved-activations and backward
-(``csrc/dit_train.inl``), fused AdamW with gradient-norm clipping on flat fp32 buffers, data parallelism by ONE all-reduce of
+(``csrc/dit_train.inl``), fused AdamW with gradient-norm clipping on flat fp32 buffers (``flat_optim.FlatAdamW``), data parallelism by ONE all-reduce of
 the flat gradient buffer per step (RCCL through ``torch.distributed``; the buffer is a torch tensor).
 
 Mirrors, for the DiT3D "full" / rope_3d model (README ``@DiT/XL``, attention-only blocks in this fork):
@@ -24,12 +24,15 @@ from typing import Dict, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import capi, parallel
+from . import capi
 from .backbone import _get
-from .diffusion import DiffusionConfig, Schedule
+from .diffusion import DiffusionConfig, Schedule, denoising_loss, masked_mean
+from .flat_optim import FlatAdamW, FlatAdamWOwner, alias
 
 
-class DiT3DTrainer:
+class DiT3DTrainer(FlatAdamWOwner):
+    params, grads = alias("params"), alias("grads")
+
     def __init__(self, cfg, x_shape: Sequence[int], max_tokens: int, timesteps: int = 1000,
                  diffusion: Optional[DiffusionConfig] = None, lr: float = 5e-5, weight_decay: float = 0.01,
                  betas: Tuple[float, float] = (0.9, 0.99), eps: float = 1e-8, max_grad_norm: Optional[float] = 1.0,
@@ -66,11 +69,7 @@ class DiT3DTrainer:
             self.layout[lib.dfot_dit_train_param_name(h, i).decode()] = (
                 int(lib.dfot_dit_train_param_offset(h, i)), tuple(int(shape[k]) for k in range(ndim.value)))
         # flat buffers: torch owns them (the gradient buffer is what torch.distributed all-reduces)
-        self.params = torch.zeros(self.numel, device="cuda", dtype=torch.float32)
-        self.grads = torch.zeros_like(self.params)
-        self.exp_avg = torch.zeros_like(self.params)
-        self.exp_avg_sq = torch.zeros_like(self.params)
-        self._sumsq = torch.zeros(1, device="cuda", dtype=torch.float32)
+        self.opt = FlatAdamW(self.layout, self.numel)
         capi.check(lib.dfot_dit_train_attach(h, capi.ptr(self.params), capi.ptr(self.grads)))
         # FourierEmbedding's buffers (reference draw: 2 pi N(0,1), 2 pi U[0,1)); tensors of their own, never part of the flat buffers
         self.buffers: Dict[str, torch.Tensor] = {}
@@ -79,14 +78,9 @@ class DiT3DTrainer:
                             FOURIER_BUFFERS[1]: (2 * np.pi * torch.rand(int(c.noise_dim))).cuda()}
             self._load_buffers()
         self.lr, self.weight_decay, self.betas, self.eps, self.max_grad_norm = lr, weight_decay, tuple(betas), eps, max_grad_norm
-        self.step_count = 0
         self.schedule = Schedule(diffusion or DiffusionConfig(beta_schedule="cosine", is_continuous=False, timesteps=timesteps))
         self.loss_weighting = dict(loss_weighting or {})
         self._reserved = 0
-        self.ema: Optional[torch.Tensor] = None  # EMAModel shadow weights (flat), updated inside the optimizer kernel
-        self.ema_decay = 0.0
-        self._acc: Optional[torch.Tensor] = None
-        self._acc_n = 0
         self._dirty = True
         self._last: Optional[dict] = None
 
@@ -130,10 +124,6 @@ class DiT3DTrainer:
             self._handle = None
 
     # ------------------------------------------------------------------ parameters (reference state_dict names)
-    def view(self, name: str, buf: Optional[torch.Tensor] = None) -> torch.Tensor:
-        off, shape = self.layout[name]
-        return (self.params if buf is None else buf)[off: off + int(np.prod(shape))].view(shape)
-
     def _load_buffers(self) -> None:
         for k, t in self.buffers.items():
             capi.check(capi.lib.dfot_dit_train_load_buffer(self._handle, k.encode(), capi.ptr(t, torch.float32, k), t.numel(), capi.stream_ptr()))
@@ -186,22 +176,8 @@ class DiT3DTrainer:
                             else "DiT3DTrainer takes integer noise levels (DiscreteDiffusion passes the level index)")
         lv = noise_levels.to(device="cuda", dtype=torch.float32 if self.is_continuous else torch.int32).contiguous()
         out = torch.empty_like(xd)
-        if self.is_continuous:
-            pc = pl = pm = None
-            if cond is not None:
-                action = self._ccfg.cond_type == capi.COND_ACTION
-                if self._ccfg.cond_type == capi.COND_NONE:
-                    raise ValueError("this trainer was built without an external condition embedding")
-                want = (b, t, int(self._ccfg.cond_dim)) if action else (b, t)
-                if tuple(cond.shape) != want or (cond_mask is not None and tuple(cond_mask.shape) != (b,)):
-                    raise ValueError(f"condition has shape {tuple(cond.shape)}, expected {want} (mask {(b,)})")
-                cd = cond.to(device="cuda", dtype=torch.float32 if action else torch.int32).contiguous()
-                md = None if cond_mask is None else cond_mask.to(device="cuda", dtype=torch.uint8).contiguous()
-                pc, pl, pm = (capi.ptr(cd) if action else None), (None if action else capi.ptr(cd)), capi.ptr(md)
-            capi.check(capi.lib.dfot_dit_train_forward_f(self._handle, capi.ptr(xd), capi.ptr(lv), pc, pl, pm, capi.ptr(out), b, t, capi.stream_ptr()))
-        elif cond is None:
-            capi.check(capi.lib.dfot_dit_train_forward(self._handle, capi.ptr(xd), capi.ptr(lv), capi.ptr(out), b, t, capi.stream_ptr()))
-        else:
+        pc = pl = pm = None
+        if cond is not None:
             action = self._ccfg.cond_type == capi.COND_ACTION
             if self._ccfg.cond_type == capi.COND_NONE:
                 raise ValueError("this trainer was built without an external condition embedding")
@@ -210,8 +186,14 @@ class DiT3DTrainer:
                 raise ValueError(f"condition has shape {tuple(cond.shape)}, expected {want} (mask {(b,)})")
             cd = cond.to(device="cuda", dtype=torch.float32 if action else torch.int32).contiguous()
             md = None if cond_mask is None else cond_mask.to(device="cuda", dtype=torch.uint8).contiguous()
-            capi.check(capi.lib.dfot_dit_train_forward_cond(self._handle, capi.ptr(xd), capi.ptr(lv), capi.ptr(cd) if action else None,
-                                                            None if action else capi.ptr(cd), capi.ptr(md), capi.ptr(out), b, t, capi.stream_ptr()))
+            pc, pl, pm = (capi.ptr(cd) if action else None), (None if action else capi.ptr(cd)), capi.ptr(md)
+        lib, h, s = capi.lib, self._handle, capi.stream_ptr()
+        if self.is_continuous:
+            capi.check(lib.dfot_dit_train_forward_f(h, capi.ptr(xd), capi.ptr(lv), pc, pl, pm, capi.ptr(out), b, t, s))
+        elif cond is None:
+            capi.check(lib.dfot_dit_train_forward(h, capi.ptr(xd), capi.ptr(lv), capi.ptr(out), b, t, s))
+        else:
+            capi.check(lib.dfot_dit_train_forward_cond(h, capi.ptr(xd), capi.ptr(lv), pc, pl, pm, capi.ptr(out), b, t, s))
         self._keep = (xd, lv)  # the engine reads x again in backward (patch-embedding gradient)
         return out
 
@@ -245,62 +227,17 @@ class DiT3DTrainer:
 
     def loss_and_grads(self, xs: torch.Tensor, k: torch.Tensor, noise: torch.Tensor, masks: Optional[torch.Tensor] = None,
                        conditions: Optional[torch.Tensor] = None, dropout_generator: Optional[torch.Generator] = None):
-        """DiscreteDiffusion.forward (pred_v) + _reweight_loss + backward: noise every token to its level, one forward, the
-        weighted v-space error averaged over (B, T) with the loss masks, gradients of every parameter.  Returns the loss (device scalar).
+        """DiscreteDiffusion.forward (pred_v; k: integer levels) or, in a continuous-diffusion trainer, ContinuousDiffusion.forward (k in
+        [0, 1]) + _reweight_loss + backward (diffusion.denoising_loss): noise every token to its level, one forward, the weighted error
+        averaged over (B, T) with the loss masks, gradients of every parameter.  Returns the loss (device scalar).
         conditions: the external condition of the batch (actions (B, T, dim) / labels (B, 1)), embedded as in DiT3D.forward."""
         b, t = xs.shape[:2]
         cond, cdrop = self._condition(conditions, b, t, dropout_generator)
         self.last_cond_dropout = cdrop
-        f = int(np.prod(xs.shape[2:]))
-        if self.is_continuous:
-            return self._continuous_loss_and_grads(xs, k, noise, masks, cond, cdrop)
-        kk = k.detach().cpu().numpy().astype(np.int64)
-        sch = self.schedule
-        w = sch.loss_weights(kk, **self.loss_weighting).astype(np.float32)
-        mk = np.ones((b, t), np.float32) if masks is None else masks.detach().cpu().numpy().astype(np.float32).reshape(b, t)
-        tab = np.stack([sch.sqrt_alphas_cumprod[kk], sch.sqrt_one_minus_alphas_cumprod[kk], w, 2.0 * w * mk / (f * b * t)]).astype(np.float32)
-        tab = torch.from_numpy(tab).cuda().contiguous()
-        x = xs.to(device="cuda", dtype=torch.float32).contiguous()
-        eps = noise.to(device="cuda", dtype=torch.float32).clamp(-self.schedule.cfg.clip_noise, self.schedule.cfg.clip_noise).contiguous()
-        x_k = torch.empty_like(x)
-        s = capi.stream_ptr
-        capi.check(capi.lib.dfot_hg_prepare(capi.ptr(x), capi.ptr(eps), capi.ptr(tab[0]), capi.ptr(tab[1]), capi.ptr(x_k), b, 1, t, f, s()))
-        v = self.forward(x_k, k, cond, cdrop)
-        per_token = torch.empty(b, t, device="cuda")
-        scratch = torch.empty(int(capi.lib.dfot_vpred_loss_scratch_floats(b, t, f)), device="cuda")
-        capi.check(capi.lib.dfot_vspace_loss(capi.ptr(x), capi.ptr(eps), capi.ptr(v), capi.ptr(tab[0]), capi.ptr(tab[1]), capi.ptr(tab[2]),
-                                             None, capi.ptr(scratch), capi.ptr(per_token), b, t, f, s()))
-        dv = torch.empty_like(x)
-        capi.check(capi.lib.dfot_vloss_grad(capi.ptr(x), capi.ptr(eps), capi.ptr(v), capi.ptr(tab[0]), capi.ptr(tab[1]), capi.ptr(tab[3]),
-                                            capi.ptr(dv), b, t, f, 1, s()))
+        _, per_token, _, dv = denoising_loss(self.schedule.cfg if self.is_continuous else self.schedule, lambda x_k, lv: self.forward(x_k, lv, cond, cdrop),
+                                             xs, k, noise, masks, self.loss_weighting, want_grad=True)
         self.backward(dv)
-        return (per_token * torch.from_numpy(mk).cuda()).mean()
-
-    def _continuous_loss_and_grads(self, xs, t_levels, noise, masks, cond, cdrop):
-        """ContinuousDiffusion.forward (continuous_diffusion.py:140-167) + _reweight_loss: k in [0, 1] per token -> cosine logSNR with the
-        configured shift (DiffusionConfig.training_logsnr_tables, the helper the U-ViT loss paths use), x_t = alpha x + sigma eps, the
-        backbone at precond_scale * logsnr, sigmoid-weighted error (dfot_vpred_loss) averaged over (B, T) with the loss masks; backward."""
-        dcfg = self.schedule.cfg
-        b, t = xs.shape[:2]
-        f = int(np.prod(xs.shape[2:]))
-        logsnr, alpha, sigma, weight = dcfg.training_logsnr_tables(t_levels)
-        mk = torch.ones(b, t) if masks is None else masks.detach().float().cpu().view(b, t)
-        tab = torch.stack([alpha, sigma, weight, float(dcfg.precond_scale) * logsnr, 2.0 * weight * mk / (f * b * t)]).float().cuda().contiguous()
-        x = xs.to(device="cuda", dtype=torch.float32).contiguous()
-        eps = noise.to(device="cuda", dtype=torch.float32).clamp(-dcfg.clip_noise, dcfg.clip_noise).contiguous()
-        x_t = torch.empty_like(x)
-        s = capi.stream_ptr
-        capi.check(capi.lib.dfot_hg_prepare(capi.ptr(x), capi.ptr(eps), capi.ptr(tab[0]), capi.ptr(tab[1]), capi.ptr(x_t), b, 1, t, f, s()))
-        v = self.forward(x_t, tab[3], cond, cdrop)
-        per_token = torch.empty(b, t, device="cuda")
-        scratch = torch.empty(int(capi.lib.dfot_vpred_loss_scratch_floats(b, t, f)), device="cuda")
-        capi.check(capi.lib.dfot_vpred_loss(capi.ptr(x), capi.ptr(eps), capi.ptr(v), capi.ptr(tab[0]), capi.ptr(tab[1]), capi.ptr(tab[2]),
-                                            None, capi.ptr(scratch), capi.ptr(per_token), b, t, f, s()))
-        dv = torch.empty_like(x)
-        capi.check(capi.lib.dfot_vloss_grad(capi.ptr(x), capi.ptr(eps), capi.ptr(v), capi.ptr(tab[0]), capi.ptr(tab[1]), capi.ptr(tab[4]),
-                                            capi.ptr(dv), b, t, f, 0, s()))
-        self.backward(dv)
-        return (per_token * mk.cuda()).mean()
+        return masked_mean(per_token, masks)[0]
 
     def difference_loss_and_grads(self, frames: torch.Tensor, k: torch.Tensor, noise: torch.Tensor, masks: Optional[torch.Tensor] = None,
                                   conditions: Optional[torch.Tensor] = None, dropout_generator: Optional[torch.Generator] = None):
@@ -317,30 +254,17 @@ class DiT3DTrainer:
         cc = None if conditions is None else merge(conditions.to("cuda"), conditions.to("cuda"))  # merge_tensors(conditions, conditions)
         return self.loss_and_grads(merge(diff, fr), merge(kk, kk), noise, mk, cc, dropout_generator)
 
-    def accumulate(self) -> None:
-        """accumulate_grad_batches: add the gradients of the last backward to the running sum used by the next optimizer_step"""
-        if self._acc is None:
-            self._acc = torch.zeros_like(self.grads)
-        self._acc.add_(self.grads)
-        self._acc_n += 1
+    @property
+    def _hyper(self) -> Dict:
+        return dict(lr=self.lr, betas=self.betas, eps=self.eps, weight_decay=self.weight_decay)
+
+    @_hyper.setter
+    def _hyper(self, h: Dict) -> None:
+        self.lr, self.betas, self.eps, self.weight_decay = h["lr"], h["betas"], h["eps"], h["weight_decay"]
 
     def optimizer_step(self, world_size: int = 1) -> None:
         """[all-reduce + average the flat gradient buffer] -> global-norm clip -> AdamW -> refresh the bf16 compute weights"""
-        if self._acc_n:
-            self.grads.copy_(self._acc).mul_(1.0 / self._acc_n)
-            self._acc.zero_()
-            self._acc_n = 0
-        if world_size > 1:
-            parallel.allreduce_mean_(self.grads)
-        self.step_count += 1
-        s = capi.stream_ptr
-        sumsq = None
-        if self.max_grad_norm is not None:
-            capi.check(capi.lib.dfot_sumsq(capi.ptr(self.grads), self.numel, capi.ptr(self._sumsq), s()))
-            sumsq = self._sumsq
-        capi.check(capi.lib.dfot_adamw_step(capi.ptr(self.params), capi.ptr(self.grads), capi.ptr(self.exp_avg), capi.ptr(self.exp_avg_sq),
-                                            self.numel, self.lr, self.betas[0], self.betas[1], self.eps, self.weight_decay, self.step_count,
-                                            capi.ptr(sumsq), float(self.max_grad_norm or 0.0), capi.ptr(self.ema), float(self.ema_decay), s()))
+        self.opt.step(self.lr, self.betas, self.eps, self.weight_decay, self.max_grad_norm, world_size)
         self._dirty = True
 
     def training_step(self, xs: torch.Tensor, k: torch.Tensor, noise: torch.Tensor, masks: Optional[torch.Tensor] = None,
@@ -349,43 +273,6 @@ class DiT3DTrainer:
         loss = self.loss_and_grads(xs, k, noise, masks, conditions, dropout_generator)
         self.optimizer_step(world_size)
         return loss
-
-    # ------------------------------------------------------------------ EMA and optimizer state (checkpoint / resume)
-    def enable_ema(self, decay: float) -> None:
-        """experiment.ema (algorithms/common/ema.py): shadow weights start as a copy of the parameters"""
-        self.ema, self.ema_decay = self.params.clone(), float(decay)
-
-    def ema_state_dict(self) -> Dict[str, torch.Tensor]:
-        if self.ema is None:
-            raise RuntimeError("EMA is not enabled")
-        return {k: self.view(k, self.ema).detach().clone() for k in self.layout}
-
-    def optimizer_state_dict(self) -> Dict:
-        """torch.optim.AdamW.state_dict() layout (parameter index = position in the reference's parameter order)"""
-        state = {i: {"step": torch.tensor(float(self.step_count)), "exp_avg": self.view(k, self.exp_avg).clone(),
-                     "exp_avg_sq": self.view(k, self.exp_avg_sq).clone()} for i, k in enumerate(self.layout)} if self.step_count else {}
-        group = dict(lr=self.lr, betas=self.betas, eps=self.eps, weight_decay=self.weight_decay, amsgrad=False,
-                     params=list(range(len(self.layout))))
-        return {"state": state, "param_groups": [group]}
-
-    def load_optimizer_state_dict(self, sd: Dict) -> None:
-        names = list(self.layout)
-        steps = set()
-        for i, st in sd.get("state", {}).items():
-            k = names[int(i)]
-            self.view(k, self.exp_avg).copy_(st["exp_avg"].to("cuda"))
-            self.view(k, self.exp_avg_sq).copy_(st["exp_avg_sq"].to("cuda"))
-            steps.add(int(float(st["step"])))
-        if len(steps) > 1:
-            raise ValueError("per-parameter step counts differ: the flat optimizer keeps one")
-        self.step_count = steps.pop() if steps else 0
-        if sd.get("param_groups"):
-            g0 = sd["param_groups"][0]
-            self.lr, self.betas, self.eps, self.weight_decay = g0["lr"], tuple(g0["betas"]), g0["eps"], g0["weight_decay"]
-
-    def grad_norm(self) -> float:
-        capi.check(capi.lib.dfot_sumsq(capi.ptr(self.grads), self.numel, capi.ptr(self._sumsq), capi.stream_ptr()))
-        return float(self._sumsq.sqrt().item())
 
 
 class FacMatDiTTrainer(DiT3DTrainer):

@@ -18,6 +18,8 @@ import numpy as np
 import torch
 
 from . import capi
+from .diffusion import DiffusionConfig, denoising_loss, masked_mean
+from .flat_optim import FlatAdamW, FlatAdamWOwner, alias
 
 BF = torch.bfloat16
 _S = capi.stream_ptr
@@ -467,15 +469,17 @@ def _silu(src: torch.Tensor, grad: Optional[torch.Tensor] = None) -> torch.Tenso
     return out
 
 
-class _UViTTrainerBase:
+class _UViTTrainerBase(FlatAdamWOwner):
     """What the trainers of the two U-ViT backbones share (u_vit3d.py:30-185 is the parent class of u_vit3d_pose.py in the reference too): the
-    flat parameter / gradient / optimizer-state buffers in the reference's parameter order, the block lists, the noise-level MLP, the U
+    flat parameter / gradient / optimizer-state buffers in the reference's parameter order (one flat_optim.FlatAdamW), the block lists, the noise-level MLP, the U
     traversal forward and backward (skip arithmetic, resampling convolutions, per-level dropout and checkpointing, the overlapped gradient
     reducer), the per-level FiLM bookkeeping (W_e of a level's blocks concatenated, the per-frame FiLM table and its gradients), the training
     step, clipped AdamW, EMA, accumulation and the state dicts.  A subclass supplies the conditioning: how the per-frame embedding vector is
     formed, how a block receives its FiLM, and what the FiLM gradients turn into."""
 
     COND_DIM_DEFAULT = 0
+    flat, flat_grads = alias("params"), alias("grads")
+    _view = FlatAdamWOwner.view
 
     def _configure(self, g) -> None:
         """read the configuration and refuse what is not built -- on the host, before any device work"""
@@ -502,18 +506,14 @@ class _UViTTrainerBase:
             self.layout[n] = (off, tuple(params[n].shape))
             off += -(-params[n].numel() // 4) * 4
         self.numel = off
-        self.flat = torch.zeros(off, device="cuda", dtype=torch.float32)
-        self.flat_grads = torch.zeros_like(self.flat)
-        self.exp_avg, self.exp_avg_sq = torch.zeros_like(self.flat), torch.zeros_like(self.flat)
-        self._sumsq = torch.zeros(1, device="cuda")
-        self.step_count = 0
+        self.opt = FlatAdamW(self.layout, off)
+        self._hyper = dict(lr=5e-5, betas=(0.9, 0.99), eps=1e-8, weight_decay=0.01)  # of the last optimizer_step: the state dict's parameter group
+        self._grads_reduced = False  # the last loss_and_grads left the MEANS over the ranks in the flat gradient (its reducer)
         self.p = {}
         for n, t in params.items():
             if n in self.layout:
-                o, shp = self.layout[n]
-                v = self.flat[o: o + t.numel()].view(shp)
-                v.copy_(t.detach().to(device="cuda", dtype=torch.float32))
-                self.p[n] = v
+                self.p[n] = self.view(n)
+                self.p[n].copy_(t.detach().to(device="cuda", dtype=torch.float32))
             else:
                 self.p[n] = t.detach().to(device="cuda", dtype=torch.float32).contiguous()
         rope = {l: rope_table(self.ch[l] // self.heads, (self.T, self.r[l], self.r[l]), theta) for l in range(4) if self.types[l] == "TransformerBlock"}
@@ -536,11 +536,6 @@ class _UViTTrainerBase:
         # use_checkpointing of u_vit3d.yaml, per level ([false, false, false, true] for RE10K training, realestate10k_video_generation.yaml:44):
         # the blocks of such a level keep only their inputs and are run forward again inside the backward
         self.use_checkpointing = [bool(v) for v in g("use_checkpointing", [False] * 4)]
-        # optional trainer state (experiments/simple_video_generation.py): EMA shadow weights, gradient accumulation
-        self.ema: Optional[torch.Tensor] = None
-        self.ema_decay = 0.0
-        self._acc: Optional[torch.Tensor] = None
-        self._acc_n = 0
         self.sync()
 
     def sync(self, own_step: Optional[Dict] = None) -> None:
@@ -704,6 +699,7 @@ class _UViTTrainerBase:
         lib, p, e, r, ch, bt = capi.lib, self.p, self.e, self.r, self.ch, self.bt
         G: Dict[str, torch.Tensor] = {}
         handed = set()
+        flat_grads = self.flat_grads
 
         def hand_over():
             if reducer is None:
@@ -712,7 +708,7 @@ class _UViTTrainerBase:
                 if n not in handed:
                     handed.add(n)
                     o, shp = self.layout[n]
-                    reducer.add(self.flat_grads[o: o + gv.numel()], gv)
+                    reducer.add(flat_grads[o: o + gv.numel()], gv)
         # FiLM gradients: every block leaves its own where the subclass wants them (_begin_backward / _block_backward); _finish_level turns
         # a level's into weight-sized gradients and its share of dc, the gradient of the per-frame embedding vector, as soon as the level's
         # last block is done
@@ -819,125 +815,25 @@ class _UViTTrainerBase:
         actions (B,T,cond_dim) or None).  `diffusion`: the DiffusionConfig whose training schedule
         (logsnr_min/max, training_schedule_shift), loss weighting (loss_sigmoid_bias), precond_scale and clip_noise apply (default: the
         reference's RE10K values).  Returns the loss (device scalar)."""
-        from .diffusion import DiffusionConfig
         dcfg = diffusion if diffusion is not None else DiffusionConfig()  # schedule limits / shift / loss weighting / preconditioning from the config
-        precond_scale, clip_noise = float(dcfg.precond_scale), float(dcfg.clip_noise)
-        b, tk = xs.shape[:2]
-        f = int(xs[0, 0].numel())
-        logsnr, alpha, sigma, weight = dcfg.training_logsnr_tables(t)
-        mk = torch.ones(b, tk) if masks is None else masks.detach().float().cpu().view(b, tk)
-        tab = torch.stack([alpha, sigma, weight, precond_scale * logsnr, 2.0 * weight * mk / (f * b * tk)]).float().cuda().contiguous()
-        x = xs.to(device="cuda", dtype=torch.float32).contiguous()
-        eps = noise.to(device="cuda", dtype=torch.float32).clamp(-clip_noise, clip_noise).contiguous()
-        x_t = torch.empty_like(x)
-        lib = capi.lib
-        capi.check(lib.dfot_hg_prepare(_P(x), _P(eps), _P(tab[0]), _P(tab[1]), _P(x_t), b, 1, tk, f, _S()))
-        v = self.forward(x_t, tab[3], cond, cond_drop).contiguous()
-        per_token = torch.empty(b, tk, device="cuda")
-        scratch = torch.empty(int(lib.dfot_vpred_loss_scratch_floats(b, tk, f)), device="cuda")
-        capi.check(lib.dfot_vpred_loss(_P(x), _P(eps), _P(v), _P(tab[0]), _P(tab[1]), _P(tab[2]), None, _P(scratch), _P(per_token), b, tk, f, _S()))
-        dv = torch.empty_like(x)
-        capi.check(lib.dfot_vloss_grad(_P(x), _P(eps), _P(v), _P(tab[0]), _P(tab[1]), _P(tab[4]), _P(dv), b, tk, f, 0, _S()))
+        _, per_token, _, dv = denoising_loss(dcfg, lambda x_t, lv: self.forward(x_t, lv, cond, cond_drop), xs, t, noise, masks, want_grad=True)
         grads = self.backward(dv, reducer)
+        self._grads_reduced = reducer is not None
         if reducer is not None:  # data parallel with the exchange overlapped: the flat buffer receives the MEANS over the ranks
             reducer.finish()
-            self._grads_reduced = True
         else:
             # one multi-tensor copy instead of ~430 separate ones (18 us each: 4 ms of launch tails per step)
-            dst = [self.flat_grads[o: o + grads[n].numel()] for n, (o, shp) in self.layout.items()]
+            flat_grads = self.flat_grads
+            dst = [flat_grads[o: o + grads[n].numel()] for n, (o, shp) in self.layout.items()]
             src = [grads[n].reshape(-1) for n in self.layout]
             torch._foreach_copy_(dst, src)
-            self._grads_reduced = False
-        return (per_token * mk.cuda()).mean()
-
-    def accumulate(self) -> None:
-        """accumulate_grad_batches (accelerator.accumulate, simple_video_generation.py:260): add the gradients of the last
-        loss_and_grads to the running sum; the next optimizer_step uses the MEAN over the accumulated micro-batches"""
-        if self._acc is None:
-            self._acc = torch.zeros_like(self.flat_grads)
-        if self._acc_n == 0:
-            self._acc_reduced = True
-        # the reference reduces once per optimizer step (accelerator.accumulate runs the micro-batches under no_sync); micro-batches whose
-        # gradients were already averaged over the ranks (loss_and_grads with a reducer) need no second exchange -- but only if ALL were
-        self._acc_reduced = self._acc_reduced and bool(getattr(self, "_grads_reduced", False))
-        self._acc.add_(self.flat_grads)
-        self._acc_n += 1
+        return masked_mean(per_token, masks)[0]
 
     def optimizer_step(self, lr: float = 5e-5, betas=(0.9, 0.99), eps: float = 1e-8, weight_decay: float = 0.01, max_grad_norm: Optional[float] = 1.0,
                        world_size: int = 1) -> None:
-        from . import parallel
-        if self._acc_n:
-            self.flat_grads.copy_(self._acc).mul_(1.0 / self._acc_n)
-            self._acc.zero_()
-            self._acc_n = 0
-            self._grads_reduced = self._acc_reduced  # local micro-batch gradients: ONE exchange of the accumulated mean, here
-        if world_size > 1 and not getattr(self, "_grads_reduced", False):
-            parallel.allreduce_mean_(self.flat_grads)
-        self.step_count += 1
-        self._opt = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay)
-        lib = capi.lib
-        sumsq = None
-        if max_grad_norm is not None:
-            capi.check(lib.dfot_sumsq(_P(self.flat_grads), self.numel, _P(self._sumsq), _S()))
-            sumsq = self._sumsq
-        # EMA shadow weights (algorithms/common/ema.py:21-33: shadow = decay * shadow + (1 - decay) * param after every optimizer step) are
-        # updated by the same kernel pass that writes the new parameters
-        capi.check(lib.dfot_adamw_step(_P(self.flat), _P(self.flat_grads), _P(self.exp_avg), _P(self.exp_avg_sq), self.numel, lr, betas[0], betas[1], eps,
-                                       weight_decay, self.step_count, _P(sumsq), float(max_grad_norm or 0.0), _P(self.ema), float(self.ema_decay), _S()))
+        self._hyper = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay)
+        self.opt.step(lr, betas, eps, weight_decay, max_grad_norm, world_size, self._grads_reduced)
         self.sync(own_step=dict(lr=lr, betas=tuple(betas), weight_decay=weight_decay))
-
-    # ------------------------------------------------------------------ EMA and optimizer state (checkpoint / resume), as trainer.DiT3DTrainer
-    def enable_ema(self, decay: float) -> None:
-        """experiment.ema (algorithms/common/ema.py): shadow weights start as a copy of the parameters"""
-        self.ema, self.ema_decay = self.flat.clone(), float(decay)
-
-    def _view(self, name: str, flat: torch.Tensor) -> torch.Tensor:
-        o, shp = self.layout[name]
-        n = 1
-        for d in shp:
-            n *= d
-        return flat[o: o + n].view(shp)
-
-    def ema_state_dict(self) -> Dict[str, torch.Tensor]:
-        """what the reference writes to ema.safetensors (simple_video_generation.py:653-657): the shadow of every trainable parameter"""
-        if self.ema is None:
-            raise RuntimeError("EMA is not enabled")
-        return {k: self._view(k, self.ema).detach().clone() for k in self.layout}
-
-    def load_ema_state_dict(self, sd: Dict[str, torch.Tensor]) -> None:
-        if self.ema is None:
-            raise RuntimeError("EMA is not enabled")
-        if set(sd.keys()) != set(self.layout.keys()):
-            raise ValueError("The provided state_dict does not match the structure of the EMA model.")
-        for k, t in sd.items():
-            self._view(k, self.ema).copy_(t.to(device="cuda", dtype=torch.float32))
-
-    def optimizer_state_dict(self) -> Dict:
-        """torch.optim.AdamW.state_dict() layout (parameter index = position in the reference's parameter order)"""
-        opt = getattr(self, "_opt", dict(lr=5e-5, betas=(0.9, 0.99), eps=1e-8, weight_decay=0.01))
-        state = {i: {"step": torch.tensor(float(self.step_count)), "exp_avg": self._view(k, self.exp_avg).clone(),
-                     "exp_avg_sq": self._view(k, self.exp_avg_sq).clone()} for i, k in enumerate(self.layout)} if self.step_count else {}
-        group = dict(lr=opt["lr"], betas=opt["betas"], eps=opt["eps"], weight_decay=opt["weight_decay"], amsgrad=False, params=list(range(len(self.layout))))
-        return {"state": state, "param_groups": [group]}
-
-    def load_optimizer_state_dict(self, sd: Dict) -> None:
-        names = list(self.layout)
-        steps = set()
-        for i, st in sd.get("state", {}).items():
-            k = names[int(i)]
-            self._view(k, self.exp_avg).copy_(st["exp_avg"].to("cuda"))
-            self._view(k, self.exp_avg_sq).copy_(st["exp_avg_sq"].to("cuda"))
-            steps.add(int(float(st["step"])))
-        if len(steps) > 1:
-            raise ValueError("per-parameter step counts differ: the flat optimizer keeps one")
-        self.step_count = steps.pop() if steps else 0
-        if sd.get("param_groups"):
-            g0 = sd["param_groups"][0]
-            self._opt = dict(lr=g0["lr"], betas=tuple(g0["betas"]), eps=g0["eps"], weight_decay=g0["weight_decay"])
-
-    def grad_norm(self) -> float:
-        capi.check(capi.lib.dfot_sumsq(_P(self.flat_grads), self.numel, _P(self._sumsq), _S()))
-        return float(self._sumsq.sqrt().item())
 
     def state_dict(self) -> Dict[str, torch.Tensor]:
         return {n: t.detach().clone() for n, t in self.p.items()}

@@ -398,6 +398,29 @@ def test_ema_and_optimizer_state_round_trip():
     torch.testing.assert_close(tr2.params, tr.params, rtol=1e-5, atol=1e-6)
 
 
+def test_dit_ema_resumes_from_its_state_dict():
+    """the EMA shadow after one training step, exported by ema_state_dict, lands bit for bit in a fresh trainer's shadow through
+    load_ema_state_dict; a state dict with other keys is refused (the U-ViT trainers' behaviour: one flat optimizer state serves both)"""
+    _, _, tr = _tiny_trainer(depth=1)
+    tr.enable_ema(0.9)
+    g = torch.Generator().manual_seed(8)
+    xs = torch.randn(2, 5, 4, 16, 8, generator=g)
+    k = torch.randint(0, 1000, (2, 5), generator=g)
+    tr.training_step(xs, k, torch.randn(2, 5, 4, 16, 8, generator=g))
+    assert not torch.equal(tr.ema, tr.params)  # the step moved the parameters away from their shadow
+    sd = tr.ema_state_dict()
+    _, _, fresh = _tiny_trainer(depth=1)
+    with pytest.raises(RuntimeError, match="EMA is not enabled"):
+        fresh.load_ema_state_dict(sd)
+    fresh.enable_ema(0.9)
+    assert not torch.equal(fresh.ema, tr.ema)
+    fresh.load_ema_state_dict(sd)
+    assert torch.equal(fresh.ema, tr.ema)
+    with pytest.raises(ValueError, match="does not match the structure of the EMA model"):
+        fresh.load_ema_state_dict({"nope": torch.zeros(1)})
+    assert torch.equal(fresh.ema, tr.ema)  # a refused dict changes nothing
+
+
 @pytest.mark.parametrize("bt,h,w,cin,cout", [(2, 16, 16, 128, 128), (3, 8, 16, 64, 192), (1, 32, 32, 256, 128), (2, 16, 16, 256, 256),
                                              (1, 16, 16, 576, 256), (8, 32, 32, 128, 128), (16, 32, 32, 256, 256)])
 def test_conv3x3_backward(bt, h, w, cin, cout):
