@@ -55,6 +55,7 @@ class DiTConfigF(DiTConfig):
 
 
 COND_NONE, COND_ACTION, COND_LABEL = 0, 1, 2  # dfot_dit_config.cond_type
+ATTN_MAP_OFF, ATTN_MAP_FRAME, ATTN_MAP_FULL = -1, 0, 1  # DFOT_ATTN_MAP_*
 
 
 _P, _I, _L, _F = C.c_void_p, C.c_int, C.c_int64, C.c_float
@@ -125,6 +126,9 @@ SIGNATURES = {
     "dfot_dit_forward_cond": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _P]),
     "dfot_dit_forward_f": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _P]),
     "dfot_dit_read_tap": (_I, [_P, C.c_char_p, _P, C.c_size_t, _P]),
+    "dfot_dit_capture_attention": (_I, [_P, C.POINTER(_I32), _I, _I, C.c_size_t]),
+    "dfot_dit_attention_map_shape": (_I, [_P, _I, C.POINTER(_L), C.POINTER(_I)]),
+    "dfot_dit_read_attention_map": (_I, [_P, _I, _P, C.c_size_t, _P]),
     "dfot_dit_train_create": (_I, [C.POINTER(DiTConfig), C.POINTER(_P)]),
     "dfot_dit_train_create_f": (_I, [C.POINTER(DiTConfigF), C.POINTER(_P)]),
     "dfot_facmat_train_create": (_I, [C.POINTER(DiTConfigF), C.POINTER(_P)]),
@@ -167,6 +171,10 @@ SIGNATURES = {
     "dfot_op_attention_temporal_bwd": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "dfot_op_matrix_attention_rope": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P]),
     "dfot_op_matrix_attention_rope_bwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P]),
+    "dfot_op_attention_map_workspace_bytes": (C.c_size_t, [_I, _I, _I, _I, _I]),
+    "dfot_op_attention_map": (_I, [_P, _P, _P, _P, C.c_size_t, _I, _I, _I, _I, _I, _I, _P]),
+    "dfot_op_attention_temporal_map": (_I, [_P, _P, _P, _P, C.c_size_t, _I, _I, _I, _I, _I, _P]),
+    "dfot_op_matrix_attention_map": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P]),
     "dfot_op_matrix_attention": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _F, _P]),
     "dfot_op_attention_bwd": (_I, [_P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _P]),
     "dfot_op_conv3x3_bwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),

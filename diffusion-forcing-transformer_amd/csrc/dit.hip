@@ -724,6 +724,13 @@ struct dfot_dit_s : DitGeom {  // the geometry of cfg (dit_model.h): gh, gw, P, 
   bool front_only = false;  // measurement: forward returns once the modulations of the call are formed (tools/bench_ops.py dit_front)
   std::vector<hipEvent_t> ev_start, ev_stop;
   size_t ev_used = 0;
+  // attention-map capture (dfot_dit_capture_attention); off unless cap_form >= 0.  The buffers are owned apart from the workspace
+  int cap_form = DFOT_ATTN_MAP_OFF;
+  std::vector<int> cap_blocks;        // selected frame-mixing blocks, ascending
+  size_t cap_max_bytes = 0, cap_bytes = 0;
+  std::vector<float*> cap_maps;       // one per selected block, sized for max_batch x max_tokens
+  float* cap_part = nullptr;          // partial sums of the frame form (shared by the blocks: same stream)
+  int cap_batch = 0, cap_tokens = 0;  // batch / tokens of the last forward that captured (0: none yet)
 };
 
 namespace dfot {
@@ -782,6 +789,53 @@ int dit_add_transposed(dfot_dit_s* h, const DitTensor& t, bf16** dst) {
     return DFOT_OK;
   });
   return DFOT_OK;
+}
+
+// ---- attention-map capture: sizes, buffers ----
+size_t dit_cap_map_floats(const dfot_dit_s* h, int form, int batch, int tokens) {
+  const DitCfg& c = h->cfg;
+  if (c.variant == 3) return (size_t)batch * c.num_col_heads * c.num_row_heads * tokens * tokens;
+  if (c.variant == 0 && form == DFOT_ATTN_MAP_FULL) return (size_t)batch * c.num_heads * tokens * h->P * tokens * h->P;
+  return (size_t)batch * c.num_heads * tokens * tokens;
+}
+size_t dit_cap_part_floats(const dfot_dit_s* h, int form, int batch, int tokens) {
+  const DitCfg& c = h->cfg;
+  if (c.variant == 2) return attention_temporal_map_part_floats(batch, c.num_heads, tokens, h->P);
+  if (c.variant == 0 && form == DFOT_ATTN_MAP_FRAME) return attention_map_part_floats(batch, c.num_heads, tokens * h->P, tokens);
+  return 0;
+}
+size_t dit_cap_bytes(const dfot_dit_s* h, int form, size_t nblocks, int batch) {
+  return sizeof(float) * (nblocks * dit_cap_map_floats(h, form, batch, h->cfg.max_tokens) + dit_cap_part_floats(h, form, batch, h->cfg.max_tokens));
+}
+void dit_cap_release(dfot_dit_s* h) {
+  for (float* p : h->cap_maps) (void)hipFree(p);
+  h->cap_maps.clear();
+  if (h->cap_part) (void)hipFree(h->cap_part);
+  h->cap_part = nullptr;
+  h->cap_bytes = 0;
+  h->cap_batch = h->cap_tokens = 0;
+}
+int dit_cap_alloc(dfot_dit_s* h, int max_batch) {
+  dit_cap_release(h);
+  const size_t map_bytes = sizeof(float) * dit_cap_map_floats(h, h->cap_form, max_batch, h->cfg.max_tokens);
+  const size_t part_bytes = sizeof(float) * dit_cap_part_floats(h, h->cap_form, max_batch, h->cfg.max_tokens);
+  for (size_t i = 0; i < h->cap_blocks.size(); ++i) {
+    void* p = nullptr;
+    DFOT_CHECK_HIP(hipMalloc(&p, map_bytes));
+    h->cap_maps.push_back((float*)p);
+    h->cap_bytes += map_bytes;
+  }
+  if (part_bytes) {
+    DFOT_CHECK_HIP(hipMalloc((void**)&h->cap_part, part_bytes));
+    h->cap_bytes += part_bytes;
+  }
+  return DFOT_OK;
+}
+int dit_cap_slot(const dfot_dit_s* h, int block) {
+  if (h->cap_form == DFOT_ATTN_MAP_OFF) return -1;
+  for (size_t i = 0; i < h->cap_blocks.size(); ++i)
+    if (h->cap_blocks[i] == block) return (int)i;
+  return -1;
 }
 
 int dit_upload(dfot_dit_s* h, float** dst, const std::vector<float>& table) {
@@ -878,6 +932,7 @@ int dfot_dit_destroy(dfot_dit_t h) {
   if (!h) return DFOT_OK;
   for (void* p : h->owned) (void)hipFree(p);
   for (void* p : h->ws_owned) (void)hipFree(p);
+  dit_cap_release(h);
   for (hipEvent_t e : h->ev_start) (void)hipEventDestroy(e);
   for (hipEvent_t e : h->ev_stop) (void)hipEventDestroy(e);
   delete h;
@@ -1016,6 +1071,12 @@ int dfot_dit_finalize(dfot_dit_t h, void* stream) {
 int dfot_dit_reserve(dfot_dit_t h, int max_batch) {
   DFOT_REQUIRE(h && max_batch > 0, DFOT_ERR_ARG, "reserve: bad argument");
   if (max_batch <= h->max_batch) return DFOT_OK;
+  if (h->cap_form != DFOT_ATTN_MAP_OFF) {  // refused before anything is freed
+    const size_t need = dit_cap_bytes(h, h->cap_form, h->cap_blocks.size(), max_batch);
+    DFOT_REQUIRE(need <= h->cap_max_bytes, DFOT_ERR_SHAPE,
+                 "reserve: the captured attention maps of %zu blocks need %zu bytes at batch %d x %d tokens, above max_bytes %zu", h->cap_blocks.size(),
+                 need, max_batch, h->cfg.max_tokens, h->cap_max_bytes);
+  }
   for (void* p : h->ws_owned) (void)hipFree(p);
   h->ws_owned.clear();
   h->ws_bytes = 0;
@@ -1063,11 +1124,12 @@ int dfot_dit_reserve(dfot_dit_t h, int max_batch) {
     if ((rc = dit_alloc(h, &h->cemb, frames * c.hidden_size, true))) return rc;
     if ((rc = dit_alloc(h, &h->cidx, frames, true))) return rc;
   }
+  if (h->cap_form != DFOT_ATTN_MAP_OFF && (rc = dit_cap_alloc(h, max_batch))) return rc;
   h->max_batch = max_batch;
   return DFOT_OK;
 }
 
-size_t dfot_dit_workspace_bytes(dfot_dit_t h) { return h ? h->ws_bytes : 0; }
+size_t dfot_dit_workspace_bytes(dfot_dit_t h) { return h ? h->ws_bytes + h->cap_bytes : 0; }
 
 int dfot_dit_set_option(dfot_dit_t h, const char* key, int value) {
   DFOT_REQUIRE(h && key, DFOT_ERR_ARG, "set_option: null argument");
@@ -1207,7 +1269,7 @@ static int dit_forward_impl(dfot_dit_t h, const float* x, const int32_t* noise_l
   // attention sequences: the whole video (variant 0) or one frame (variants 1 and 2, per-frame spatial blocks without RoPE)
   const int seq = facmat || fac ? P : n, nseq = facmat || fac ? frames : batch;
   // one DiTBlock: AdaLN -> q|k|v -> attention (over the sequences above, or over the frames of every patch position) -> gated projection -> MLP
-  auto dit_block = [&](const DitBlockW& w, int mlp_hidden, bool temporal) -> int {
+  auto dit_block = [&](const DitBlockW& w, int mlp_hidden, bool temporal, int map_slot) -> int {
     int r2 = ln_mod(w.mod1);
     if (r2) return r2;
     {
@@ -1225,18 +1287,27 @@ static int dit_forward_impl(dfot_dit_t h, const float* x, const int32_t* noise_l
       r2 = launch_attention_padded(h->q, h->k, h->v, h->A, hd, nseq, c.num_heads, seq, h->d, s);
     if (r2) return r2;
     if (timed) DFOT_CHECK_HIP(hipEventRecord(h->ev_stop[h->ev_used++], s));
+    if (map_slot >= 0) {  // capture: the map of the q, k the attention kernel just read
+      if (temporal)
+        r2 = launch_attention_temporal_map(h->q, h->k, h->cap_maps[map_slot], h->cap_part, batch, tokens, P, c.num_heads, h->d, s);
+      else
+        r2 = launch_attention_map(h->q, h->k, h->cap_maps[map_slot], h->cap_part, h->cap_form == DFOT_ATTN_MAP_FULL, batch, c.num_heads, n, tokens,
+                                  h->d, s);
+      if (r2) return r2;
+    }
     if ((r2 = gated(h->A, hd, w.w_proj, w.b_proj, 0, w.mod1 + 2 * hd))) return r2;
     return mlp_hidden ? mlp(w.mod2, mlp_hidden, w.w_fc1, w.b_fc1, w.w_fc2, w.b_fc2) : DFOT_OK;
   };
   for (size_t bi = 0; bi < h->blocks.size(); ++bi) {
-    if ((rc = dit_block(h->blocks[bi], c.mlp_hidden, false))) return rc;
+    const int map_slot = dit_cap_slot(h, (int)bi);  // of the block's frame-mixing attention: the block itself only in variant 0
+    if ((rc = dit_block(h->blocks[bi], c.mlp_hidden, false, c.variant == 0 ? map_slot : -1))) return rc;
     if (fac) {
       if (bi == 0) {  // sinusoidal_factorized: the temporal table enters after spatial block 0 (dit_base.py:408-411)
         const long total4 = rows * (hd / 4);
         hipLaunchKernelGGL(add_temporal_pos_kernel, dim3(cdiv(total4, 256)), dim3(256), 0, s, h->X, h->tpos, tokens, P, hd / 4, total4);
         DFOT_CHECK_HIP(hipGetLastError());
       }
-      if ((rc = dit_block(h->fblocks[bi], c.temporal_mlp_hidden, true))) return rc;
+      if ((rc = dit_block(h->fblocks[bi], c.temporal_mlp_hidden, true, map_slot))) return rc;
     }
     if (!facmat) continue;
 
@@ -1263,6 +1334,9 @@ static int dit_forward_impl(dfot_dit_t h, const float* x, const int32_t* noise_l
       else  // FacMatDiT: any 1 <= tokens <= 32, RoPE-1D over the frame axis when the model has one (trope == nullptr: none)
         rc = launch_matrix_attn_rope(h->Z, h->W1, h->trope, batch, tokens, E, hd, c.num_col_heads, c.num_row_heads, mscale, s);
       if (rc) return rc;
+      if (!diffm && map_slot >= 0 &&
+          (rc = launch_matrix_attn_map(h->Z, h->trope, h->cap_maps[map_slot], batch, tokens, E, hd, c.num_col_heads, c.num_row_heads, mscale, s)))
+        return rc;
     }
     if ((rc = transpose(h->W1, h->W2, E, hd))) return rc;  // o^T per frame: [hd][E]
     {
@@ -1274,6 +1348,10 @@ static int dit_forward_impl(dfot_dit_t h, const float* x, const int32_t* noise_l
     if (c.temporal_mlp_hidden && (rc = mlp(t.mod2, c.temporal_mlp_hidden, t.w_fc1, t.b_fc1, t.w_fc2, t.b_fc2))) return rc;
   }
   h->last_rows = (int)rows;
+  if (h->cap_form != DFOT_ATTN_MAP_OFF) {
+    h->cap_batch = batch;
+    h->cap_tokens = tokens;
+  }
   return launch_final_layer(h->X, table, lvl, h->ldt, h->mod_final, h->fin_w, h->fin_b, out, hd, P, (int)rows, c.eps,
                             max_level, c.in_channels, c.height, c.width, c.patch_size, s);
 }
@@ -1336,6 +1414,93 @@ int dfot_dit_read_tap(dfot_dit_t h, const char* name, float* out, size_t capacit
   }
   DFOT_REQUIRE(capacity >= need, DFOT_ERR_SHAPE, "read_tap: need %zu floats, got %zu", need, capacity);
   DFOT_CHECK_HIP(hipMemcpyAsync(out, src, need * sizeof(float), hipMemcpyDeviceToDevice, s));
+  return DFOT_OK;
+}
+
+int dfot_dit_capture_attention(dfot_dit_t h, const int32_t* blocks, int count, int form, size_t max_bytes) {
+  DFOT_REQUIRE(h, DFOT_ERR_ARG, "capture_attention: null handle");
+  if (form == DFOT_ATTN_MAP_OFF) {
+    DFOT_CHECK_HIP(hipDeviceSynchronize());  // a forward that writes the buffers may still be running
+    dit_cap_release(h);
+    h->cap_form = DFOT_ATTN_MAP_OFF;
+    h->cap_blocks.clear();
+    return DFOT_OK;
+  }
+  const DitCfg& c = h->cfg;
+  DFOT_REQUIRE(form == DFOT_ATTN_MAP_FRAME || form == DFOT_ATTN_MAP_FULL, DFOT_ERR_ARG, "capture_attention: form %d unknown (-1 = off, 0 = frame, 1 = full)",
+               form);
+  DFOT_REQUIRE(c.variant != 1, DFOT_ERR_ARG, "capture_attention: the difference model (variant 1, difference_dit3d) is not supported");
+  DFOT_REQUIRE(!(c.variant == 2 && form == DFOT_ATTN_MAP_FULL), DFOT_ERR_ARG,
+               "capture_attention: form 'full' on the factorized attention variant: a temporal block has one T x T map per patch position and only "
+               "their mean, the frame map, is formed");
+  if (c.variant == 0)
+    DFOT_REQUIRE(h->P % 64 == 0 && c.max_tokens <= 32, DFOT_ERR_SHAPE,
+                 "capture_attention: the map kernel needs patches per frame %% 64 == 0 and max_tokens <= 32 (have %d patches, max_tokens %d)", h->P,
+                 c.max_tokens);
+  DFOT_REQUIRE(count >= 0 && (blocks || count == 0), DFOT_ERR_ARG, "capture_attention: %d blocks without a list", count);
+  std::vector<int> sel;
+  if (!blocks) {
+    for (int i = 0; i < c.depth; ++i) sel.push_back(i);
+  } else {
+    for (int i = 0; i < count; ++i) {
+      DFOT_REQUIRE(blocks[i] >= 0 && blocks[i] < c.depth, DFOT_ERR_ARG, "capture_attention: block index %d outside 0 .. %d", blocks[i], c.depth - 1);
+      DFOT_REQUIRE(i == 0 || blocks[i] > blocks[i - 1], DFOT_ERR_ARG, "capture_attention: block indices must ascend (%d after %d)", blocks[i],
+                   blocks[i - 1]);
+      sel.push_back(blocks[i]);
+    }
+  }
+  const size_t cap = max_bytes ? max_bytes : (size_t)1 << 30;
+  const int at_batch = h->max_batch > 0 ? h->max_batch : 1;
+  const size_t need = dit_cap_bytes(h, form, sel.size(), at_batch);
+  DFOT_REQUIRE(need <= cap, DFOT_ERR_SHAPE, "capture_attention: the %s maps of %zu blocks need %zu bytes at batch %d x %d tokens, above max_bytes %zu",
+               form == DFOT_ATTN_MAP_FULL ? "full" : "frame", sel.size(), need, at_batch, c.max_tokens, cap);
+  DFOT_CHECK_HIP(hipDeviceSynchronize());
+  dit_cap_release(h);
+  h->cap_form = form;
+  h->cap_blocks = sel;
+  h->cap_max_bytes = cap;
+  if (h->max_batch > 0) {
+    int rc = dit_cap_alloc(h, h->max_batch);
+    if (rc) {
+      dit_cap_release(h);
+      h->cap_form = DFOT_ATTN_MAP_OFF;
+      h->cap_blocks.clear();
+      return rc;
+    }
+  }
+  return DFOT_OK;
+}
+
+int dfot_dit_attention_map_shape(dfot_dit_t h, int slot, int64_t shape[5], int* ndim) {
+  DFOT_REQUIRE(h && shape && ndim, DFOT_ERR_ARG, "attention_map_shape: null argument");
+  DFOT_REQUIRE(h->cap_form != DFOT_ATTN_MAP_OFF, DFOT_ERR_STATE, "attention_map_shape: attention capture is off");
+  DFOT_REQUIRE(slot >= 0 && slot < (int)h->cap_blocks.size(), DFOT_ERR_ARG, "attention_map_shape: slot %d of %zu captured blocks", slot, h->cap_blocks.size());
+  DFOT_REQUIRE(h->cap_batch > 0, DFOT_ERR_STATE, "attention_map_shape: no forward has run with the capture on");
+  const DitCfg& c = h->cfg;
+  const int64_t t = h->cap_tokens;
+  int k = 0;
+  shape[k++] = h->cap_batch;
+  if (c.variant == 3) {
+    shape[k++] = c.num_col_heads;
+    shape[k++] = c.num_row_heads;
+  } else {
+    shape[k++] = c.num_heads;
+  }
+  const int64_t side = c.variant == 0 && h->cap_form == DFOT_ATTN_MAP_FULL ? t * h->P : t;
+  shape[k++] = side;
+  shape[k++] = side;
+  *ndim = k;
+  return DFOT_OK;
+}
+
+int dfot_dit_read_attention_map(dfot_dit_t h, int slot, float* out, size_t capacity, void* stream) {
+  DFOT_REQUIRE(h && out, DFOT_ERR_ARG, "read_attention_map: null argument");
+  DFOT_REQUIRE(h->cap_form != DFOT_ATTN_MAP_OFF, DFOT_ERR_STATE, "read_attention_map: attention capture is off");
+  DFOT_REQUIRE(slot >= 0 && slot < (int)h->cap_blocks.size(), DFOT_ERR_ARG, "read_attention_map: slot %d of %zu captured blocks", slot, h->cap_blocks.size());
+  DFOT_REQUIRE(h->cap_batch > 0 && slot < (int)h->cap_maps.size(), DFOT_ERR_STATE, "read_attention_map: no forward has run with the capture on");
+  const size_t need = dit_cap_map_floats(h, h->cap_form, h->cap_batch, h->cap_tokens);
+  DFOT_REQUIRE(capacity >= need, DFOT_ERR_SHAPE, "read_attention_map: need %zu floats, got %zu", need, capacity);
+  DFOT_CHECK_HIP(hipMemcpyAsync(out, h->cap_maps[slot], need * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
   return DFOT_OK;
 }
 

@@ -154,6 +154,19 @@ int launch_matrix_attn_rope(const bf16* z, bf16* o, const float* rope_cs, int ba
 // attention_matrix_bwd.hip: backward of launch_matrix_attn_rope; d_o [batch*L*E][h], dz [batch*L*E][3h] (dq|dk|dv); same shape rules
 int launch_matrix_attn_rope_bwd(const bf16* z, const bf16* d_o, const float* rope_cs, bf16* dz, int batch, int L, int E, int h, int cc, int rr,
                                 float scale, hipStream_t s);
+// ---- attention maps (attention_map.hip): fp32 softmax probabilities recomputed from the forward's q / k; read-only on q / k ----
+// launch_attention_map: q, k as launch_attention_padded takes them, n = tokens * patches, patches % 64 == 0, 1 <= tokens <= 32.
+//   full: out [B][heads][n][n] (part unused);  frame: out [B][heads][tokens][tokens], part = attention_map_part_floats() floats of scratch
+size_t attention_map_part_floats(int batch, int heads, int n, int tokens);
+int launch_attention_map(const bf16* q, const bf16* k, float* out, float* part, bool full, int batch, int heads, int n, int tokens, int d,
+                         hipStream_t s);
+// q, k as launch_attention_temporal takes them (patches % 64 == 0 suffices); out [B][heads][tokens][tokens] = mean over the patches
+size_t attention_temporal_map_part_floats(int batch, int heads, int tokens, int patches);
+int launch_attention_temporal_map(const bf16* q, const bf16* k, float* out, float* part, int batch, int tokens, int patches, int heads, int d,
+                                  hipStream_t s);
+// z, rope_cs, scale as launch_matrix_attn_rope takes them; out [B][cc][rr][L][L]
+int launch_matrix_attn_map(const bf16* z, const float* rope_cs, float* out, int batch, int L, int E, int h, int cc, int rr, float scale,
+                           hipStream_t s);
 // ---- attention forward: key split of the last round + scratch (attention_split.hip; shared by v3, v5 and ks) ----
 struct AttnSplit {
   int tiles, full, rem, nsplit;

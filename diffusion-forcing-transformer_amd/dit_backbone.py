@@ -20,7 +20,8 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-from typing import Dict, Optional, Sequence, Tuple
+from collections import OrderedDict
+from typing import Dict, Optional, Sequence, Tuple, Union
 
 import torch
 from torch import nn
@@ -199,6 +200,7 @@ class DiT3D(nn.Module):
         self._trainer_sig = None
         self._train_stamp = 0  # counts training forwards (see backbone.UViT3DPose._train_backward_impl)
         self._train_names = [n for n, _ in self.named_parameters()]
+        self._capture_names: Tuple[str, ...] = ()  # attention-map capture: the selected module names, in block order; () = off
 
     def _configure(self, c: "capi.DiTConfig", cfg, max_tokens: int) -> None:
         """dit3d.yaml / dit3d_factorized_attention.yaml / dit3d_factorized_matrix.yaml keys -> engine config (variant 0 / 2 / 3)."""
@@ -317,7 +319,12 @@ class DiT3D(nn.Module):
     def reserve(self, batch: int) -> None:
         if batch > self._reserved:
             torch.cuda.synchronize()
-            capi.check(capi.lib.dfot_dit_reserve(self._handle, int(batch)))
+            try:
+                capi.check(capi.lib.dfot_dit_reserve(self._handle, int(batch)))
+            except capi.DfotError as e:
+                if self._capture_names and e.code == capi.ERR_SHAPE:  # the captured maps at this batch exceed max_bytes
+                    raise ValueError(str(e)) from None
+                raise
             self._reserved = batch
             self.reserve_generation = getattr(self, "reserve_generation", 0) + 1  # workspace pointers changed
 
@@ -497,6 +504,86 @@ class DiT3D(nn.Module):
         "noise_feat" (rows = B*T of the last float-level forward, noise_level_dim columns)"""
         out = torch.empty(rows, self.noise_level_dim if name == "noise_feat" else self.hidden_size, device="cuda", dtype=torch.float32)
         capi.check(capi.lib.dfot_dit_read_tap(self._handle, name.encode(), capi.ptr(out), out.numel(), capi.stream_ptr()))
+        return out
+
+    # ------------------------------------------------------------------ attention maps (the reference's attn_hook)
+    def attention_block_names(self) -> Tuple[str, ...]:
+        """the reference's module names of the blocks whose attention mixes frames -- the keys of the hook's ``attn_maps[timestep]``:
+        ``dit_base.blocks.{i}.attn`` (variant "full"), ``dit_base.temporal_blocks.{i}.attn`` (the two factorized variants)"""
+        stem = "dit_base.blocks" if self._ccfg.variant == 0 else "dit_base.temporal_blocks"
+        return tuple(f"{stem}.{i}.attn" for i in range(int(self._ccfg.depth)))
+
+    def capture_attention(self, blocks: Union[None, bool, Sequence[str]] = None, form: str = "frame", max_bytes: int = 1 << 30) -> None:
+        """Record, in every later forward, the attention map of the named blocks (None: every frame-mixing block); ``capture_attention(False)``
+        turns it off and releases the buffers.  form "frame": per head, query frame x key frame (rows sum to 1); "full": the N x N softmax
+        matrix of variant "full" (refused above ``max_bytes``); on "factorized_matrix_attention" every frame is one token and both forms are
+        the (B, col heads, row heads, T, T) map.  One map launch per selected block is added to the forward; its outputs do not change.
+        Not to be called while a graph is being captured: it synchronises the device and (re)allocates."""
+        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("capture_attention: capture settings cannot change while a graph is being captured")
+        if blocks is False:
+            capi.check(capi.lib.dfot_dit_capture_attention(self._handle, None, 0, capi.ATTN_MAP_OFF, 0))
+            self._capture_names = ()
+            self.reserve_generation = getattr(self, "reserve_generation", 0) + 1  # captured graphs hold the map launches
+            return
+        if self._ccfg.variant == 1:
+            raise NotImplementedError("capture_attention: DifferenceDiT3D (the difference model) is not supported")
+        if form not in ("frame", "full"):
+            raise ValueError(f"capture_attention: form {form!r} is not one of 'frame', 'full'")
+        if form == "full" and self._ccfg.variant == 2:
+            raise ValueError("capture_attention: form='full' is not available on variant 'factorized_attention': a temporal block has one "
+                             "T x T map per patch position and only their mean, the frame map, is formed")
+        names = self.attention_block_names()
+        if blocks is None or blocks is True:
+            chosen = list(range(len(names)))
+        else:
+            if isinstance(blocks, str):
+                blocks = [blocks]
+            chosen = []
+            for b in blocks:
+                if b not in names:
+                    stem, _, leaf = str(b).rpartition(".")
+                    if self._ccfg.variant != 0 and leaf == "attn" and stem.startswith("dit_base.blocks.") and stem[16:].isdigit() \
+                            and int(stem[16:]) < len(names):
+                        raise ValueError(f"capture_attention: {b!r} is a spatial block: its attention runs inside one frame and has no frame "
+                                         f"axis; the frame-mixing blocks are {names[0]!r} .. {names[-1]!r}")
+                    raise ValueError(f"capture_attention: unknown block {b!r}; the frame-mixing blocks are {names[0]!r} .. {names[-1]!r}")
+                chosen.append(names.index(b))
+            chosen = sorted(set(chosen))
+        arr = (C.c_int32 * len(chosen))(*chosen)
+        code = capi.ATTN_MAP_FULL if form == "full" else capi.ATTN_MAP_FRAME
+        try:
+            capi.check(capi.lib.dfot_dit_capture_attention(self._handle, arr, len(chosen), code, int(max_bytes)))
+        except capi.DfotError as e:
+            if e.code == capi.ERR_SHAPE:
+                raise ValueError(str(e)) from None
+            raise
+        self._capture_names = tuple(names[i] for i in chosen)
+        self._capture_max_bytes = int(max_bytes)
+        self.reserve_generation = getattr(self, "reserve_generation", 0) + 1
+
+    @property
+    def capturing_attention(self) -> bool:
+        return bool(self._capture_names)
+
+    def attention_maps(self) -> "OrderedDict[str, torch.Tensor]":
+        """name -> fp32 device tensor of the last forward, in block order.  Rows follow the model batch: under History Guidance one row per
+        (video, branch), in ``HistoryGuidance.prepare``'s order."""
+        if not self._capture_names:
+            raise RuntimeError("attention_maps: attention capture is off (call capture_attention first)")
+        out: "OrderedDict[str, torch.Tensor]" = OrderedDict()
+        shape = (C.c_int64 * 5)()
+        ndim = C.c_int()
+        for slot, name in enumerate(self._capture_names):
+            try:
+                capi.check(capi.lib.dfot_dit_attention_map_shape(self._handle, slot, shape, C.byref(ndim)))
+            except capi.DfotError as e:
+                if e.code == capi.ERR_STATE:
+                    raise RuntimeError("attention_maps: no forward has run since capture_attention was called") from None
+                raise
+            t = torch.empty(tuple(shape[k] for k in range(ndim.value)), device="cuda", dtype=torch.float32)
+            capi.check(capi.lib.dfot_dit_read_attention_map(self._handle, slot, capi.ptr(t), t.numel(), capi.stream_ptr()))
+            out[name] = t
         return out
 
     def __del__(self):

@@ -53,6 +53,11 @@ class SamplerConfig:
     external_cond_type: str = "action"
     external_cond_dim: int = 0
     external_cond_processing: Optional[str] = None
+    # step indices of a window (0 = its first denoising step) at which the backbone's attention maps are collected into
+    # sampler.attention_maps -- the counterpart of attn_hook's attn_maps[timestep][name].  Empty (the default): nothing changes.  A window
+    # that collects runs the eager step loop; the backbone's own capture_attention() choice (blocks, form) is used when it is on, else
+    # every frame-mixing block in frame form for the duration of the window.  DiT3D backbones only.
+    attention_map_steps: Tuple[int, ...] = ()
 
 
 NoiseFn = Callable[[str, tuple], torch.Tensor]
@@ -93,6 +98,8 @@ class DFoTVideoPoseSampler:
         self.graph_captures = 0
         self._graphs: Dict[tuple, dict] = {}
         self._graphs_generation = 0
+        # {step: {"noise_levels": (model batch, tokens), block name: map}} of the last window, for cfg.attention_map_steps
+        self.attention_maps: Dict[int, dict] = {}
         if cfg.diffusion.sampling_timesteps > cfg.diffusion.timesteps:
             raise ValueError("sampling_timesteps must be <= timesteps")
 
@@ -421,6 +428,13 @@ class DFoTVideoPoseSampler:
         # frame-local down-path activations are still in the backbone's workspace (backbone.fresh_frames, _fresh_flags below)
         skip_frozen = skip_dead and self.skip_frozen_frames and hasattr(self.model, "fresh_frames")
 
+        map_steps = set(int(i) for i in (getattr(cfg, "attention_map_steps", None) or ()))
+        collect_at: Optional[int] = None  # the step whose maps the next model call leaves behind
+        if map_steps and not self.dry_run:
+            if not hasattr(self.model, "capture_attention"):
+                raise NotImplementedError(f"attention_map_steps: {type(self.model).__name__} has no attention-map capture (DiT3D backbones only)")
+            self.attention_maps = {}
+
         def step(p_, xs, noise, tables, gen_dev, xs_next=None, live_dev=None, fresh_dev=None):
             nonlocal cond_rep, cond_nfe
             nfe, bm = p_["nfe"], p_["bm"]
@@ -469,6 +483,8 @@ class DFoTVideoPoseSampler:
                         self.model.live_frames = None
                     if skip_frozen:
                         self.model.fresh_frames = None
+            if collect_at is not None:  # rows follow the model batch: (video, branch) in prepare's order
+                self.attention_maps[collect_at] = {"noise_levels": lvl.clone(), **self.model.attention_maps()}
             step_noise = None
             if strict or p_["sigma"] is not None:  # the reference draws it every step; with sigma = 0 it is multiplied by 0
                 step_noise = self.noise_fn("ddim", (bm, horizon, *x_shape))
@@ -508,17 +524,28 @@ class DFoTVideoPoseSampler:
         uniform = all(p_["bm"] == plans[0]["bm"] and p_["cmask_dev"] is plans[0]["cmask_dev"]
                       and p_["weights_dev"] is plans[0]["weights_dev"] and p_.get("cond") is plans[0].get("cond") for p_ in plans)
         hook = getattr(self, "step_hook", None)  # test instrumentation (drift per step); None on every product path
+        collecting = bool(map_steps) and not self.dry_run
         if (self.use_graph and uniform and not strict and len(plans) > 2 and all(p_["sigma"] is None for p_ in plans) and not self._branch_split_active
-                and rg == 0 and hook is None):
+                and rg == 0 and hook is None and not collecting):
             if self._static_graph_cond and cond_full is not None:
                 nfe0 = plans[0]["nfe"]
                 plans[0]["cond_src"] = cond_full if nfe0 == 1 else cond_full.repeat_interleave(nfe0, dim=0)
             xs = self._run_steps_graph(plans, xs, draw_noise, step, flat_dev, gens_dev, horizon)
         else:
-            for i, p_ in enumerate(plans):
-                xs = step(p_, xs, draw_noise(p_), p_["tables_dev"], p_["gen_dev"])
-                if hook is not None:
-                    hook(i, xs)
+            # capture settings change here, outside any graph capture, and are restored when the window is done
+            own_capture = collecting and not self.model.capturing_attention
+            if own_capture:
+                self.model.capture_attention()
+            try:
+                for i, p_ in enumerate(plans):
+                    collect_at = i if collecting and i in map_steps else None
+                    xs = step(p_, xs, draw_noise(p_), p_["tables_dev"], p_["gen_dev"])
+                    if hook is not None:
+                        hook(i, xs)
+            finally:
+                collect_at = None
+                if own_capture:
+                    self.model.capture_attention(False)
         self.window_forwards += sum(p_["bm"] for p_ in plans)
         if padding > 0:
             xs = xs[:, :-padding]

@@ -197,6 +197,11 @@ class DiT3DTrainer(FlatAdamWOwner):
         self._keep = (xd, lv)  # the engine reads x again in backward (patch-embedding gradient)
         return out
 
+    def capture_attention(self, *args, **kwargs) -> None:
+        """attention maps are a read-out of the inference engine (DiT3D.capture_attention); the training handles do not form them"""
+        raise NotImplementedError(f"capture_attention: {type(self).__name__} is a training engine; attention maps are captured on the "
+                                  "inference model (DiT3D.capture_attention) with the same weights")
+
     def backward(self, d_out: torch.Tensor) -> None:
         g = d_out.to(device="cuda", dtype=torch.float32).contiguous()
         capi.check(capi.lib.dfot_dit_train_backward(self._handle, capi.ptr(g), capi.stream_ptr()))

@@ -6,6 +6,7 @@
   python examples/sample.py k600diff [--ckpt ...]
   python examples/sample.py facdit   [--ckpt ...]   (FacDiT-XL, the taichikl recipe: 4x32x32 latents, patch 2, 16 frames)
   python examples/sample.py facmat   [--ckpt ...]   (FacMatDiT XL-64-1, the same recipe: matrix attention with RoPE over the 16 frames)
+  python examples/sample.py <k600|facdit|facmat> --attention-maps maps.npz [--attention-steps 0 25 49]   (which frame attends to which)
   python examples/sample.py uvit3d   [--cond action:4]   (the pose-free U-ViT at the RE10K widths, 256x256 frames, continuous diffusion)
   python examples/sample.py k600 --continuous --decode-image-vae   (latents -> frames through a random-weight per-frame ImageVAE)
 
@@ -44,7 +45,13 @@ def main():
     ap.add_argument("--decode-image-vae", action="store_true",
                     help="decode the sampled latents with a random-weight ImageVAE (image_vae.yaml widths, z_channels = the latent channels), the "
                          "per-frame autoencoder of the dmlab / Minecraft recipes; latents of 8x8 or 16x16 (the mid attention's sizes)")
+    ap.add_argument("--attention-maps", metavar="OUT.npz",
+                    help="k600 / facdit / facmat: write the frame-to-frame attention maps of every frame-mixing block (per head, query frame x key "
+                         "frame; rows follow the model batch) at the steps of --attention-steps, as '<step>/<block name>' and '<step>/noise_levels'")
+    ap.add_argument("--attention-steps", type=int, nargs="*", default=None, help="step indices of the window (default: first, middle, last)")
     a = ap.parse_args()
+    if a.attention_maps and a.model not in ("k600", "facdit", "facmat"):
+        raise SystemExit("--attention-maps: the DiT3D models k600, facdit and facmat only")
     gen = torch.Generator(device="cuda").manual_seed(a.seed)
     noise = dfot_amd.device_noise_fn(gen)
     conds = None
@@ -126,6 +133,9 @@ def main():
     xs = xs.cuda()
     conds = None if conds is None else conds.cuda()
     model.eval()  # (train() would draw the per-video dropout of a condition embedding)
+    if a.attention_maps:
+        steps = a.attention_steps if a.attention_steps else sorted({0, a.steps // 2, a.steps - 1})
+        sampler.cfg.attention_map_steps = tuple(steps)  # the window that collects runs the eager step loop
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     if a.model == "k600diff":
@@ -148,6 +158,10 @@ def main():
         torch.cuda.synchronize()
         print(f"ImageVAE decode (random weights): {tuple(out.shape)} -> {tuple(frames.shape)} in {(time.perf_counter() - t0) * 1e3:.1f} ms")
     np.savez_compressed(a.out, out=out.cpu().numpy())
+    if a.attention_maps:  # plotting is the caller's: the hook's picture of a block is its map summed over the heads
+        maps = {f"{step}/{name}": t.cpu().numpy() for step, rec in sampler.attention_maps.items() for name, t in rec.items()}
+        np.savez_compressed(a.attention_maps, **maps)
+        print(f"attention maps of steps {sorted(sampler.attention_maps)} ({len(maps)} arrays) -> {a.attention_maps}")
 
 
 if __name__ == "__main__":

@@ -285,6 +285,28 @@ int dfot_dit_forward_f(dfot_dit_t h, const float* x, const float* noise_levels, 
  * last per-frame forward), "noise_feat" [B*T][noise_dim] (Fourier features of the last dfot_dit_forward_f) */
 int dfot_dit_read_tap(dfot_dit_t h, const char* name, float* out, size_t capacity_floats, void* stream);
 
+/* ---- attention maps (the read-out of the reference's attn_hook: algorithms/common/attn_hook/hook.py, dit_blocks.py:100-118) ----
+ * Which frame attends to which, per head, of the blocks whose attention mixes frames: the blocks of variant 0 (full 3-D attention), the
+ * temporal blocks of variant 2 and the matrix blocks of variant 3.  The forward kernels never form the score matrix; with a capture on,
+ * every selected block adds one map launch (plus its finalize) to dfot_dit_forward* on the caller's stream, which recomputes the
+ * softmax from the q and k (bf16, after RoPE, pre-scaled) the block's attention kernel read.  Off (the default): no launch, no buffer.
+ *   frame form: F[b][head][tq][tk] = (1/P) sum_{i in frame tq} sum_{j in frame tk} softmax_j(q_i . k_j); rows sum to 1.
+ *               variant 0 / 2: [batch][num_heads][T][T];  variant 3: [batch][num_col_heads][num_row_heads][T][T]
+ *   full form:  variant 0: A [batch][num_heads][T*P][T*P];  variant 3: every frame is one token, so the full map is the frame map;
+ *               variant 2: refused (DFOT_ERR_ARG): a temporal block has one T x T map per patch position and only their mean is formed. */
+enum { DFOT_ATTN_MAP_OFF = -1, DFOT_ATTN_MAP_FRAME = 0, DFOT_ATTN_MAP_FULL = 1 };
+/* Select the blocks (`count` ascending indices into the variant's frame-mixing blocks, each < depth; blocks == NULL: all of them) and the
+ * form; form DFOT_ATTN_MAP_OFF releases the buffers and turns the capture off.  The buffers (one map per selected block at max_batch x
+ * max_tokens) are allocated here when a workspace is reserved and in every later dfot_dit_reserve.  max_bytes (0: 1 GiB) caps them: a
+ * capture that needs more is refused with DFOT_ERR_SHAPE and a message naming the size -- here (the earlier setting stays), or in the
+ * dfot_dit_reserve that would grow them (the workspace stays as it was).  Variant 1 (the difference model) is refused with DFOT_ERR_ARG.  Synchronises the device; not for use during graph capture. */
+int dfot_dit_capture_attention(dfot_dit_t h, const int32_t* blocks, int count, int form, size_t max_bytes);
+/* shape (ndim <= 5) of the map of selected block `slot` (0 .. count-1) as the last forward wrote it; DFOT_ERR_STATE until a forward has
+ * run with the capture on */
+int dfot_dit_attention_map_shape(dfot_dit_t h, int slot, int64_t shape[5], int* ndim);
+/* copy that map (fp32, device to device, on `stream`); same DFOT_ERR_STATE rule */
+int dfot_dit_read_attention_map(dfot_dit_t h, int slot, float* out, size_t capacity_floats, void* stream);
+
 /* ---- DiT3D training path ("full" variant, attention-only blocks) ----------------------------------
  * Replaces torch autograd through DiT3D.forward (algorithms/dfot/backbones/dit/dit3d.py:153-192, dit_blocks.py:408-542) and the
  * optimizer step of DFoTVideo.training_step / configure_optimizers (dfot_video.py:41-75, base_pytorch_algo: AdamW).
@@ -477,6 +499,22 @@ int dfot_op_matrix_attention_rope_bwd(const void* z, const void* d_o, const floa
 /* the DifferenceDiT3D (variant 1) form of the same core, without rotation: register forms for L in {2, 4, 6, 8, 10}, one pair of
  * tokens per wave pass for every other L <= 32.  Test / measurement entry of the engine's own launcher */
 int dfot_op_matrix_attention(const void* z, void* o, int batch, int L, int E, int h, int cc, int rr, float scale, void* stream);
+/* Attention-map kernels (test / measurement entries; see the dfot_dit_capture_attention section).  All outputs fp32; fixed summation order, no
+ * atomics: two calls give the same bits.  None of them writes q, k or z.
+ * Full attention: q, k as dfot_op_attention_padded takes them, n = tokens * patches with n % 128 == 0, patches % 64 == 0, 1 <= tokens <= 32.
+ * form DFOT_ATTN_MAP_FULL: out [batch][heads][n][n]; DFOT_ATTN_MAP_FRAME: out [batch][heads][tokens][tokens], and `workspace` holds at least
+ * the bytes the query below returns (temporal = 0).  Anything else: DFOT_ERR_SHAPE before any device work */
+size_t dfot_op_attention_map_workspace_bytes(int temporal, int batch, int heads, int tokens, int patches);
+int dfot_op_attention_map(const void* q, const void* k, void* out, void* workspace, size_t workspace_bytes, int form, int batch, int heads,
+                          int n, int tokens, int d, void* stream);
+/* Temporal attention: q, k as dfot_op_attention_temporal takes them; out [batch][heads][tokens][tokens] = the mean over the patch positions of
+ * the T x T softmax of every (video, head, patch).  patches % 64 == 0, 1 <= tokens <= 32, d % 4 == 0, d <= 128; workspace: the query with
+ * temporal = 1 */
+int dfot_op_attention_temporal_map(const void* q, const void* k, void* out, void* workspace, size_t workspace_bytes, int batch, int tokens,
+                                   int patches, int heads, int d, void* stream);
+/* Matrix attention: z, rope_cs (NULL = no rotation), scale and the shape rules of dfot_op_matrix_attention_rope; out [batch][cc][rr][L][L] */
+int dfot_op_matrix_attention_map(const void* z, const float* rope_cs, void* out, int batch, int L, int E, int h, int cc, int rr, float scale,
+                                 void* stream);
 /* training path, test entry: o = attention(q, k, v) as above and, for the upstream gradient d_o [B*N][ldo] (same compact layout as
  * o), dq / dk / dv in the layout of q / k / v; dq is the gradient of the UNSCALED q (q itself is passed pre-multiplied by
  * log2(e)/sqrt(d), as the forward wants it).  Replaces torch autograd through F.scaled_dot_product_attention

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Micro-benchmarks of the C-ABI primitives at the RE10K model shapes (model batch 2), HIP-event timed.
-Usage (GPU box): python tools/bench_ops.py [gemm] [conv] [attn] [tattn] [mattn] [tattn_bwd] [facdit_train] [mattn_bwd] [facmat_train] [vae_encode] [equal] [dit_front] [ivae] [uvit3d] [gnfilm_frame] [uvit3d_train]"""
+Usage (GPU box): python tools/bench_ops.py [gemm] [conv] [attn] [tattn] [mattn] [tattn_bwd] [facdit_train] [mattn_bwd] [facmat_train] [vae_encode] [equal] [dit_front] [ivae] [uvit3d] [gnfilm_frame] [uvit3d_train] [attnmap]"""
 import ctypes as C
 import math
 import os
@@ -101,6 +101,51 @@ def tattn(b, heads, tokens, patches, d):
                 iters=50, warm=5)
     nbytes = b * tokens * patches * heads * (3 * ds + d) * 2.0
     return ms, nbytes / ms / 1e6, 4.0 * b * heads * patches * tokens * tokens * d / ms / 1e9
+
+
+def attnmap():
+    """the attention-map launches next to the forward attention launch whose q, k they re-read, at the K600 shape (DiT/XL full attention: 16
+    heads, d 72, 5 frames x 256 patches) and the taichikl shapes (FacDiT temporal blocks: 16 frames x 256 patches; FacMatDiT XL-64-1 matrix
+    blocks: 16 frames, E 64, h 1152, 1 x 16 heads); model batch 2.  us per launch (the frame forms include their finalize)."""
+    b, heads, d, ds = 2, 16, 72, 128
+
+    def padded(shape):
+        t = torch.zeros(*shape, ds, device="cuda", dtype=torch.bfloat16)
+        t[..., :d] = torch.randn(*shape, d, device="cuda").bfloat16()
+        return t
+    tokens, patches = 5, 256
+    n = tokens * patches
+    q, k, v = padded((b, heads, n)) * 0.2, padded((b, heads, n)), padded((b, heads, n))
+    o = torch.empty(b * n, heads * d, device="cuda", dtype=torch.bfloat16)
+    ws = torch.empty(capi.lib.dfot_op_attention_map_workspace_bytes(0, b, heads, tokens, patches) // 4, device="cuda")
+    frame, full = torch.empty(b, heads, tokens, tokens, device="cuda"), torch.empty(b, heads, n, n, device="cuda")
+    fwd = timeit(lambda: capi.check(capi.lib.dfot_op_attention_padded(P(q), P(k), P(v), P(o), heads * d, b, heads, n, d, S())), iters=50, warm=5)
+    t_frame = timeit(lambda: capi.check(capi.lib.dfot_op_attention_map(P(q), P(k), P(frame), P(ws), ws.numel() * 4, capi.ATTN_MAP_FRAME, b, heads, n,
+                                                                     tokens, d, S())), iters=50, warm=5)
+    t_full = timeit(lambda: capi.check(capi.lib.dfot_op_attention_map(P(q), P(k), P(full), None, 0, capi.ATTN_MAP_FULL, b, heads, n, tokens, d, S())),
+                    iters=50, warm=5)
+    print(f"attnmap K600 full attention B={b} N={n} d={d}: forward {fwd*1e3:8.1f} us  frame map {t_frame*1e3:8.1f} us  full map {t_full*1e3:8.1f} us "
+          f"({full.numel() * 4 / 1e6:.0f} MB written)", flush=True)
+    tokens = 16
+    q, k, v = padded((b * tokens, heads, patches)) * 0.2, padded((b * tokens, heads, patches)), padded((b * tokens, heads, patches))
+    o = torch.empty(b * tokens * patches, heads * d, device="cuda", dtype=torch.bfloat16)
+    ws = torch.empty(capi.lib.dfot_op_attention_map_workspace_bytes(1, b, heads, tokens, patches) // 4, device="cuda")
+    frame = torch.empty(b, heads, tokens, tokens, device="cuda")
+    fwd = timeit(lambda: capi.check(capi.lib.dfot_op_attention_temporal(P(q), P(k), P(v), P(o), heads * d, b, tokens, patches, heads, d, S())),
+                 iters=50, warm=5)
+    t_frame = timeit(lambda: capi.check(capi.lib.dfot_op_attention_temporal_map(P(q), P(k), P(frame), P(ws), ws.numel() * 4, b, tokens, patches, heads,
+                                                                              d, S())), iters=50, warm=5)
+    print(f"attnmap taichikl temporal B={b} T={tokens} P={patches} d={d}: forward {fwd*1e3:8.1f} us  frame map {t_frame*1e3:8.1f} us", flush=True)
+    e, h, cc, rr = 64, 1152, 1, 16
+    z = torch.randn(b * tokens * e, 3 * h, device="cuda").bfloat16()
+    o = torch.empty(b * tokens * e, h, device="cuda", dtype=torch.bfloat16)
+    ang = torch.arange(tokens, dtype=torch.float64)[:, None] / (10000.0 ** (torch.arange(0, h // rr, 2, dtype=torch.float64) / (h // rr)))
+    table = torch.stack([ang.cos(), ang.sin()], -1).float().contiguous().cuda()
+    m = torch.empty(b, cc, rr, tokens, tokens, device="cuda")
+    scale = 1.0 / math.sqrt((e // cc) * (h // rr))
+    fwd = timeit(lambda: capi.check(capi.lib.dfot_op_matrix_attention_rope(P(z), P(o), P(table), b, tokens, e, h, cc, rr, scale, S())), iters=50, warm=5)
+    t_map = timeit(lambda: capi.check(capi.lib.dfot_op_matrix_attention_map(P(z), P(table), P(m), b, tokens, e, h, cc, rr, scale, S())), iters=50, warm=5)
+    print(f"attnmap taichikl matrix B={b} L={tokens} E={e} h={h}: forward {fwd*1e3:8.1f} us  map {t_map*1e3:8.1f} us", flush=True)
 
 
 def facdit_forward(b):
@@ -409,6 +454,8 @@ def ivae():
 
 def main():
     what = sys.argv[1:] or ["gemm", "conv", "attn"]
+    if "attnmap" in what:
+        attnmap()
     if "ivae" in what:
         ivae()
     if "vae_encode" in what:
