@@ -21,4 +21,5 @@ from . import uvit_train  # noqa: F401,E402
 from .uvit_train import UViT3DPoseTrainer, UViT3DTrainer  # noqa: F401,E402
 from .vae import VideoVAEDecoder, VideoVAEEncoder, VideoVAEPosterior, decode_latents, encode_videos  # noqa: F401,E402
 from .image_vae import (ImageVAEDecoder, ImageVAEEncoder, ImageVAEPosterior, decode_image_latents,  # noqa: F401,E402
-                        encode_image_frames)  # noqa: F401,E402
+                        encode_image_frames, ddconfig_from_diffusers, diffusers_to_reference_keys,  # noqa: F401,E402
+                        load_diffusers_checkpoint)  # noqa: F401,E402

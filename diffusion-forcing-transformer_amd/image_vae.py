@@ -9,6 +9,10 @@ Mirrors, for this model family:
   * ``BaseVideoAlgo._run_vae`` / ``_encode`` / ``_decode``   algorithms/common/base_pytorch_video_algo.py:553-629  (ImageVAE branch:
     ``b c t h w -> (b t) c h w``, chunks of ``vae.batch_size`` videos, ``encode(2 y - 1).sample()``, ``decode(z) * 0.5 + 0.5``)
 The modules register the reference's state-dict names (``decoder.*`` / ``post_quant_conv.*``, ``encoder.*`` / ``quant_conv.*``).
+The KL-f8 autoencoder of the taichikl recipes (``stabilityai/sd-vae-ft-ema``, a diffusers ``AutoencoderKL``, which ``_encode`` /
+``_decode`` call the same way, :590-591,605-609) is this architecture under other key names: ``load_diffusers_state_dict`` /
+``load_diffusers_checkpoint`` / ``diffusers_to_reference_keys`` / ``ddconfig_from_diffusers`` below.  The mid attention takes 64, 256 or a
+multiple of 256 positions from 512 to 4096 per frame (8x8 ... 64x64 maps: 64x64 ... 512x512 frames at f8).
 
 Every value is computed by a HIP kernel behind the C ABI; host code only sequences the calls.  No CPU fallback.  Activations are
 channels-last [frames][H][W][C].  Stride-1 3x3 convolutions run on the strided implicit-GEMM entry with one temporal tap
@@ -23,7 +27,7 @@ do not fill the tiles are REFUSED at call time (no internal padding): the ``Valu
 from __future__ import annotations
 
 import math
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, List, Mapping, Optional, Sequence, Tuple
 
 import torch
 
@@ -31,7 +35,12 @@ from . import capi
 from .vae import BF, _P, _S, _VideoVAEModule, _channel_vector, _pad_to
 
 _WIDTHS = (128, 256, 512, 1024)
-_ATTN_N = (64, 256)
+
+
+def _attn_rows_ok(n: int) -> bool:
+    """dfot_op_ivae_attention's rule on the positions per frame: the register-resident kernels at 64 and 256, the streaming one at a
+    multiple of 256 in [512, 4096] (1024 = a 256x256 frame at f8, 4096 = a 512x512 one)"""
+    return n in (64, 256) or (512 <= n <= 4096 and n % 256 == 0)
 
 
 def _refuse(kind: str, attn_resolutions, use_linear_attn, attn_type, resamp_with_conv, tanh_out=False, give_pre_end=False) -> None:
@@ -125,10 +134,16 @@ class _ImageVAEModule(_VideoVAEModule):
                                              _P(out), c, f * n, c, c, _S()))
         return out
 
+    def load_diffusers_state_dict(self, state_dict: Mapping[str, torch.Tensor]) -> List[str]:
+        """a diffusers ``AutoencoderKL`` state dict (see ``diffusers_to_reference_keys``): renamed, then loaded as strictly as
+        ``load_reference_state_dict`` loads; returns the ignored keys under their reference names (the other half of the autoencoder)"""
+        return self.load_reference_state_dict(diffusers_to_reference_keys(state_dict, self.levels))
+
     def _check_rows(self, frames: int, h: int, w: int, what: str) -> None:
         """(h, w): the coarsest map (the mid blocks').  Every finer level has 4x the rows, so this one decides."""
-        if h * w not in _ATTN_N:
-            raise ValueError(f"{what}: the mid attention runs over {h}x{w} = {h * w} positions per frame; supported: {list(_ATTN_N)}")
+        if not _attn_rows_ok(h * w):
+            raise ValueError(f"{what}: the mid attention runs over {h}x{w} = {h * w} positions per frame; supported: 64, 256 and the "
+                             "multiples of 256 from 512 to 4096")
         need = 128 // math.gcd(128, h * w)
         if frames % need:
             raise ValueError(f"{what}: {frames} frames of {h}x{w} at the coarsest level are {frames * h * w} GEMM rows, not whole 128-row tiles; "
@@ -330,6 +345,131 @@ class ImageVAEEncoder(_ImageVAEModule):
         self._check(x)
         sf, sc, sh, sw = x.stride()
         return ImageVAEPosterior(self._moments(x, x.shape[0], 1, (sf, sc, 0, sh, sw), 1.0, 0.0), self.embed)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# diffusers-layout checkpoints (``AutoencoderKL``: stabilityai/sd-vae-ft-ema and the VAEs fine-tuned from it).  The map is stated from
+# the format's public key layout; the library itself is not a dependency.
+_DIFFUSERS_ATTN = {"to_q": "q", "to_k": "k", "to_v": "v", "to_out.0": "proj_out",          # current spelling (Linear projections)
+                   "query": "q", "key": "k", "value": "v", "proj_attn": "proj_out",        # legacy hub checkpoints
+                   "group_norm": "norm"}
+_DIFFUSERS_RES = {"norm1": "norm1", "conv1": "conv1", "norm2": "norm2", "conv2": "conv2", "conv_shortcut": "nin_shortcut"}
+
+
+def _diffusers_key(key: str, levels: int) -> Optional[str]:
+    """one diffusers ``AutoencoderKL`` key -> the reference's (ldm) name, None when the key is not one of the format's"""
+    stem, dot, leaf = key.rpartition(".")
+    if not dot or leaf not in ("weight", "bias"):
+        return None
+    if stem in ("quant_conv", "post_quant_conv"):
+        return key
+    side, _, rest = stem.partition(".")
+    if side not in ("encoder", "decoder"):
+        return None
+    if rest in ("conv_in", "conv_out"):
+        return key
+    if rest == "conv_norm_out":
+        return f"{side}.norm_out.{leaf}"
+    parts = rest.split(".")
+    if parts[0] == "mid_block" and len(parts) >= 4:
+        if parts[1] == "resnets" and parts[2] in ("0", "1") and len(parts) == 4 and parts[3] in _DIFFUSERS_RES and parts[3] != "conv_shortcut":
+            return f"{side}.mid.block_{int(parts[2]) + 1}.{_DIFFUSERS_RES[parts[3]]}.{leaf}"
+        if parts[1] == "attentions" and parts[2] == "0" and ".".join(parts[3:]) in _DIFFUSERS_ATTN:
+            return f"{side}.mid.attn_1.{_DIFFUSERS_ATTN['.'.join(parts[3:])]}.{leaf}"
+        return None
+    blocks, ref = ("down_blocks", "down") if side == "encoder" else ("up_blocks", "up")
+    if parts[0] != blocks or len(parts) != 5 or not parts[1].isdigit() or int(parts[1]) >= levels:
+        return None
+    lvl = int(parts[1]) if side == "encoder" else levels - 1 - int(parts[1])
+    if parts[2] == "resnets" and parts[3].isdigit() and parts[4] in _DIFFUSERS_RES:
+        return f"{side}.{ref}.{lvl}.block.{int(parts[3])}.{_DIFFUSERS_RES[parts[4]]}.{leaf}"
+    if parts[2:] == (["downsamplers", "0", "conv"] if side == "encoder" else ["upsamplers", "0", "conv"]):
+        return f"{side}.{ref}.{lvl}.{'downsample' if side == 'encoder' else 'upsample'}.conv.{leaf}"
+    return None
+
+
+def diffusers_to_reference_keys(state: Mapping[str, torch.Tensor], levels: int) -> Dict[str, torch.Tensor]:
+    """A diffusers ``AutoencoderKL`` state dict under the reference's names (``levels = len(block_out_channels)``):
+    ``down_blocks.{i}.resnets.{j}`` -> ``down.{i}.block.{j}``, ``up_blocks.{i}`` -> ``up.{levels - 1 - i}`` (diffusers counts the up
+    blocks from the coarsest), ``mid_block.resnets.{0,1}`` -> ``mid.block_{1,2}``, ``mid_block.attentions.0`` -> ``mid.attn_1`` with
+    ``to_q / to_k / to_v / to_out.0`` (or the legacy ``query / key / value / proj_attn``) -> ``q / k / v / proj_out``, ``conv_shortcut`` ->
+    ``nin_shortcut``, ``conv_norm_out`` -> ``norm_out``, ``downsamplers.0`` / ``upsamplers.0`` -> ``downsample`` / ``upsample``.  The
+    attention projections are Linear layers there: their [C, C] weights become the reference's 1x1 convolutions [C, C, 1, 1].
+    A key that is not one of the format's raises ``ValueError`` naming it, as do two keys that map to one name."""
+    out: Dict[str, torch.Tensor] = {}
+    for key, t in state.items():
+        name = _diffusers_key(key, int(levels))
+        if name is None:
+            raise ValueError(f"unknown key in a diffusers AutoencoderKL state dict with {levels} levels: {key}")
+        if name in out:
+            raise ValueError(f"two keys of the diffusers state dict map to {name}: {key} is the second")
+        if ".mid.attn_1." in name and name.endswith(".weight") and not name.endswith(".norm.weight") and t.ndim == 2:
+            t = t.reshape(*t.shape, 1, 1)
+        out[name] = t
+    return out
+
+
+def ddconfig_from_diffusers(config: Mapping) -> Dict[str, object]:
+    """The constructor keywords of ``ImageVAEDecoder`` / ``ImageVAEEncoder`` from a diffusers ``AutoencoderKL`` config (the mapping of its
+    config.json).  Whatever the engine does not run is refused by the field's name."""
+    def bad(field: str, why: str):
+        return NotImplementedError(f"diffusers AutoencoderKL config: {field}={config.get(field)!r} is not supported ({why})")
+    if "block_out_channels" not in config:
+        raise ValueError("diffusers AutoencoderKL config: block_out_channels is missing")
+    if config.get("norm_num_groups", 32) != 32:
+        raise bad("norm_num_groups", "GroupNorm(32) only")
+    if config.get("act_fn", "silu") != "silu":
+        raise bad("act_fn", "SiLU only")
+    boc = [int(c) for c in config["block_out_channels"]]
+    if any(t != "DownEncoderBlock2D" for t in config.get("down_block_types", ["DownEncoderBlock2D"] * len(boc))):
+        raise bad("down_block_types", "DownEncoderBlock2D only")
+    if any(t != "UpDecoderBlock2D" for t in config.get("up_block_types", ["UpDecoderBlock2D"] * len(boc))):
+        raise bad("up_block_types", "UpDecoderBlock2D only")
+    for field in ("down_block_types", "up_block_types"):
+        if field in config and len(config[field]) != len(boc):
+            raise bad(field, f"one block type per entry of block_out_channels={boc}")
+    for field in ("use_quant_conv", "use_post_quant_conv"):
+        if not config.get(field, True):
+            raise bad(field, "the 1x1 quant_conv / post_quant_conv are part of the engine's path")
+    if not config.get("mid_block_add_attention", True):
+        raise bad("mid_block_add_attention", "the mid block runs with its attention")
+    ch = boc[0]
+    if any(c % ch for c in boc):
+        raise bad("block_out_channels", "every width must be a multiple of the first")
+    zc = int(config.get("latent_channels", 4))
+    return dict(ch=ch, ch_mult=[c // ch for c in boc], num_res_blocks=int(config.get("layers_per_block", 1)), z_channels=zc, embed_dim=zc,
+                in_channels=int(config.get("in_channels", 3)), out_ch=int(config.get("out_channels", 3)),
+                resolution=int(config.get("sample_size", 32)))
+
+
+def load_diffusers_checkpoint(path: str, config: Optional[Mapping] = None) -> Tuple[Dict[str, object], Dict[str, torch.Tensor]]:
+    """A diffusers-layout VAE from disk -> (constructor keywords, state dict under the reference's names).  ``path`` is a directory with
+    ``config.json`` and one ``*.safetensors`` file (``diffusion_pytorch_model.safetensors`` if several), or one ``.safetensors`` file, whose
+    ``config`` (the mapping of config.json) must then be given.
+
+        dd, sd = load_diffusers_checkpoint("sd-vae-ft-ema")
+        dec = ImageVAEDecoder(**dd).cuda(); dec.load_reference_state_dict(sd)"""
+    import glob
+    import json
+    import os
+    from safetensors.torch import load_file
+    if os.path.isdir(path):
+        if config is None:
+            with open(os.path.join(path, "config.json")) as fh:
+                config = json.load(fh)
+        files = sorted(glob.glob(os.path.join(path, "*.safetensors")))
+        if not files:
+            raise FileNotFoundError(f"no *.safetensors file in {path}")
+        if len(files) > 1:
+            named = [f for f in files if os.path.basename(f) == "diffusion_pytorch_model.safetensors"]
+            if len(named) != 1:
+                raise ValueError(f"{path} holds {len(files)} *.safetensors files and no diffusion_pytorch_model.safetensors; name the file")
+            files = named
+        path = files[0]
+    elif config is None:
+        raise ValueError(f"{path} is a single file: its AutoencoderKL config (the mapping of config.json) must be given")
+    dd = ddconfig_from_diffusers(config)
+    return dd, diffusers_to_reference_keys(load_file(path), len(dd["ch_mult"]))
 
 
 def _chunks(x: torch.Tensor, vae_batch_size: int):

@@ -9,6 +9,8 @@
   python examples/sample.py <k600|facdit|facmat> --attention-maps maps.npz [--attention-steps 0 25 49]   (which frame attends to which)
   python examples/sample.py uvit3d   [--cond action:4]   (the pose-free U-ViT at the RE10K widths, 256x256 frames, continuous diffusion)
   python examples/sample.py k600 --continuous --decode-image-vae   (latents -> frames through a random-weight per-frame ImageVAE)
+  python examples/sample.py facdit --decode-image-vae [--image-vae-ckpt sd-vae-ft-ema/]   (the taichikl recipe's KL-f8 autoencoder:
+                                                     4x32x32 latents -> 256x256 frames; the checkpoint in the diffusers layout)
 
 Without --ckpt the backbone gets seeded random weights (there is no network here to fetch the released checkpoints);
 with it, the reference's .ckpt / ema.safetensors is read by dfot_amd.load_reference_checkpoint (keys
@@ -43,8 +45,12 @@ def main():
                     help="k600 / k600diff / facdit / facmat: continuous diffusion as @diffusion/continuous (Fourier noise-level embedding, float levels, "
                          "cosine_simple_diffusion shifted 0.125), the way the dmlab / Minecraft DiT recipes run")
     ap.add_argument("--decode-image-vae", action="store_true",
-                    help="decode the sampled latents with a random-weight ImageVAE (image_vae.yaml widths, z_channels = the latent channels), the "
-                         "per-frame autoencoder of the dmlab / Minecraft recipes; latents of 8x8 or 16x16 (the mid attention's sizes)")
+                    help="decode the sampled latents with an ImageVAE (image_vae.yaml widths, z_channels = the latent channels; random weights "
+                         "unless --image-vae-ckpt is given), the per-frame autoencoder of the dmlab / Minecraft / taichikl recipes; latents of "
+                         "8x8, 16x16 (k600) or 32x32 (facdit / facmat: 256x256 frames), the mid attention's sizes")
+    ap.add_argument("--image-vae-ckpt", metavar="PATH",
+                    help="with --decode-image-vae: a VAE in the diffusers layout (a folder with config.json and a .safetensors file, e.g. "
+                         "stabilityai/sd-vae-ft-ema or the fine-tuned Taichi VAE), read by dfot_amd.load_diffusers_checkpoint")
     ap.add_argument("--attention-maps", metavar="OUT.npz",
                     help="k600 / facdit / facmat: write the frame-to-frame attention maps of every frame-mixing block (per head, query frame x key "
                          "frame; rows follow the model batch) at the steps of --attention-steps, as '<step>/<block name>' and '<step>/noise_levels'")
@@ -149,14 +155,22 @@ def main():
           f"{sampler.window_forwards} backbone forwards of one window)")
     if a.decode_image_vae:
         zc, lh, _ = out.shape[2:]
-        vae = dfot_amd.ImageVAEDecoder(ch=128, out_ch=3, ch_mult=(1, 2, 4, 4), num_res_blocks=2, z_channels=zc, embed_dim=zc, resolution=8 * lh).cuda()
-        vae.init_random(seed=a.seed)
+        if a.image_vae_ckpt:
+            dd, sd = dfot_amd.load_diffusers_checkpoint(a.image_vae_ckpt)
+            if dd["embed_dim"] != zc:
+                raise SystemExit(f"--image-vae-ckpt: the VAE has {dd['embed_dim']} latent channels, the sampled latents {zc}")
+            vae = dfot_amd.ImageVAEDecoder(**dd).cuda()
+            vae.load_reference_state_dict(sd)
+        else:
+            vae = dfot_amd.ImageVAEDecoder(ch=128, out_ch=3, ch_mult=(1, 2, 4, 4), num_res_blocks=2, z_channels=zc, embed_dim=zc,
+                                           resolution=8 * lh).cuda()
+            vae.init_random(seed=a.seed)
         dfot_amd.decode_image_latents(vae, out[:1], vae_batch_size=1)   # packs the weights, loads the kernels
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         frames = dfot_amd.decode_image_latents(vae, out, vae_batch_size=2)
         torch.cuda.synchronize()
-        print(f"ImageVAE decode (random weights): {tuple(out.shape)} -> {tuple(frames.shape)} in {(time.perf_counter() - t0) * 1e3:.1f} ms")
+        print(f"ImageVAE decode ({a.image_vae_ckpt or 'random weights'}): {tuple(out.shape)} -> {tuple(frames.shape)} in {(time.perf_counter() - t0) * 1e3:.1f} ms")
     np.savez_compressed(a.out, out=out.cpu().numpy())
     if a.attention_maps:  # plotting is the caller's: the hook's picture of a block is its map summed over the heads
         maps = {f"{step}/{name}": t.cpu().numpy() for step, rec in sampler.attention_maps.items() for name, t in rec.items()}

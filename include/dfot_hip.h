@@ -702,7 +702,9 @@ int dfot_op_vae_posterior(const float* moments, int ld, const float* eps, const 
  * updownsample.py:10-45): per-frame layers on channels-last [frames][H][W][C] activations. ------------------------------------------- */
 /* o bf16 [frames*n][c] = softmax(q k^T / sqrt(c)) v per frame: ONE head over the n positions of a frame with all c channels, every frame in
  * one launch, no score matrix in memory (fp32 softmax with the row max subtracted, P rounded to bf16).  q, k, v bf16 [frames*n][c].
- * n in {64, 256}, c a multiple of 128 up to 1024; other shapes: DFOT_ERR_SHAPE. */
+ * n in {64, 256} (all scores of a row in registers) or a multiple of 256 in [512, 4096] (keys streamed in blocks of 128 with a running
+ * max and sum: 1024 = a 256 x 256 frame at f8, 4096 = a 512 x 512 one), c a multiple of 128 up to 1024; other shapes: DFOT_ERR_SHAPE
+ * before any device work.  One fixed summation order per (n, c): a frame's bits do not depend on the launch it is part of. */
 int dfot_op_ivae_attention(const void* q, const void* k, const void* v, void* o, int frames, int n, int c, void* stream);
 /* y fp32 [frames][h_in/2][w_in/2][cout] (+ bias) = Conv2d(k 3, s 2, p 0) of F.pad(x, (0, 1, 0, 1)): zero padding on the right and bottom only.
  * x bf16 [frames][h_in][w_in][cin], w bf16 [cout][9][cin] (dfot_op_pack_conv3).  h_in, w_in even, cin % 64 == 0, cout % 128 == 0. */

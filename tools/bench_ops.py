@@ -411,12 +411,13 @@ def equal(nbytes):
 
 def ivae():
     """the three ImageVAE ops (csrc/image_vae.hip) at the image_vae.yaml recipe's shapes, the per-frame loop of existing ops that the
-    fused attention replaces (vae.py:_attn), and a whole decode / encode of 16 frames at 128 x 128.  Each figure: the median of 7 repeats of
-    (3 warm-up + 20 timed launches between two HIP events)."""
+    fused attention replaces (vae.py:_attn), and a whole decode / encode of 16 frames at 128 x 128 and at 256 x 256.  The attention runs
+    at N = 256 (a 128 x 128 frame: the register-resident kernel) and at N = 1024 (a 256 x 256 frame: the streaming kernel).  Each figure:
+    the median of 7 repeats of (3 warm-up + 20 timed launches between two HIP events)."""
     import statistics
     med = lambda fn: statistics.median(timeit(fn) for _ in range(7))
-    n, c = 256, 512
-    for frames in (16, 128):
+    c = 512
+    for n, frames in ((256, 16), (256, 128), (1024, 16), (1024, 128)):
         q, k, v = (torch.randn(frames * n, c, device="cuda").bfloat16() for _ in range(3))
         o = torch.empty_like(q)
         ms = med(lambda: capi.check(capi.lib.dfot_op_ivae_attention(P(q), P(k), P(v), P(o), frames, n, c, S())))
@@ -447,9 +448,10 @@ def ivae():
     dec, enc = dfot_amd.ImageVAEDecoder(**cfg).cuda(), dfot_amd.ImageVAEEncoder(**cfg).cuda()
     dec.init_random(0)
     enc.init_random(1)
-    z, y = torch.randn(16, 4, 16, 16, device="cuda"), torch.rand(16, 3, 128, 128, device="cuda") * 2 - 1
-    print(f"ivae decode 16 frames 4x16x16 -> 3x128x128 (image_vae.yaml): {med(lambda: dec.decode(z)):.3f} ms", flush=True)
-    print(f"ivae encode 16 frames 3x128x128 -> moments (image_vae.yaml): {med(lambda: enc.encode(y)):.3f} ms", flush=True)
+    for r in (128, 256):    # the frame size is the caller's: the same modules run both
+        z, y = torch.randn(16, 4, r // 8, r // 8, device="cuda"), torch.rand(16, 3, r, r, device="cuda") * 2 - 1
+        print(f"ivae decode 16 frames 4x{r // 8}x{r // 8} -> 3x{r}x{r} (image_vae.yaml): {med(lambda: dec.decode(z)):.3f} ms", flush=True)
+        print(f"ivae encode 16 frames 3x{r}x{r} -> moments (image_vae.yaml): {med(lambda: enc.encode(y)):.3f} ms", flush=True)
 
 
 def main():
