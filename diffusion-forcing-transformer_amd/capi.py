@@ -235,6 +235,11 @@ SIGNATURES = {
     "dfot_op_ivae_attention": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
     "dfot_op_conv3x3_s2_f32": (_I, [_P, _P, _P, _P] + [_I] * 5 + [_P]),
     "dfot_op_upconv3x3_f32": (_I, [_P, _P, _P, _P] + [_I] * 5 + [_P]),
+    "dfot_op_mha_packed": (_I, [_P, _L, _P, _I, _I, _I, _P]),
+    "dfot_op_mha_packed_max_len": (_I, []),
+    "dfot_op_layernorm": (_I, [_P, _P, _P, _F, _P, _P, _L, _I, _I, _I, _I, _P]),
+    "dfot_op_bias_act_bf16": (_I, [_P, _L, _P, _P, _L, _I, _I, _P]),
+    "dfot_op_titok_tokens": (_I, [_P] * 9 + [_F, _P] + [_I] * 6 + [_P]),
     "dfot_op_f32_to_bf16": (_I, [_P, _P, _L, _P]),
     "dfot_op_bf16_to_f32": (_I, [_P, _P, _L, _P]),
     "dfot_op_equal_bits": (_I, [_P, _P, _L, _P, _P]),

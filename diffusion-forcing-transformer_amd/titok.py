@@ -1,0 +1,334 @@
+"""TiTok-KL decoder on the MI355X engine: the 1-D token autoencoder whose latent space the taichi recipes run in
+(``algorithm/vae=titok_kl_preprocessor``: 32 tokens of 4 channels per frame, latents ``[4, 1, 32]``).  Forward only, decoder only.
+
+Mirrors:
+  * ``TiTok_KL.decode``                         algorithms/vae/tiktok_kl/titok_kl.py:100-109  (F.normalize, decoder, channel softmax,
+    ``pixel_quantize_conv``, ``pixel_decoder``)
+  * ``TiTokDecoder`` / ``ResidualAttentionBlock``   algorithms/vae/tiktok_kl/blocks_kl.py:39-88, 169-245  (a ViT over
+    ``[cls | grid^2 mask tokens | 32 latent tokens]``: 289 tokens for a 256x256 frame)
+  * ``Decoder`` / ``ResnetBlock`` / ``UpsamplingBlock``   algorithms/vae/tiktok_kl/maskgit_vqgan.py:53-90, 122-154, 197-245
+  * ``BaseVideoAlgo._run_vae`` / ``_decode``    algorithms/common/base_pytorch_video_algo.py:553-629  (TiTok branch :611-617: chunks of
+    ``vae.batch_size`` videos, ``decode(y)`` returned as it is)
+The module registers the reference's state-dict names (``decoder.*``, ``pixel_quantize_conv.*``, ``pixel_decoder.*``); the encoder's keys
+(``encoder.*``, ``latent_tokens``) are ignored on load and returned.
+
+Every value is computed by a HIP kernel behind the C ABI; host code only sequences the calls.  No CPU fallback.  The token assembly,
+LayerNorm, the ragged multi-head attention and bias + GELU / tanh are the kernels of csrc/titok.hip (the attention applies the
+``log2(e) / 8`` scale itself; the packed ``in_proj`` rows are left as the checkpoint has them); every Linear and 1x1 convolution is an MFMA
+GEMM on bf16 operands with fp32 accumulation, the residual stream stays fp32.  The pixel decoder runs channels-last on the ops of the
+ImageVAE (dfot_op_conv3t_f32 with one temporal tap, dfot_op_upconv3x3_f32, dfot_op_groupnorm).  Two quirks of its ``ResnetBlock`` are kept:
+its convolutions and ``nin_shortcut`` have no bias (a null bias pointer), and with a channel change the block returns
+``h + nin_shortcut(h)`` with h the conv2 output -- the block's input is dropped (a GEMM whose residual is its own operand's fp32 source).
+
+GEMM rows: ANY frame count >= 1 runs.  ``frames * 289`` token rows are no multiple of the 128-row GEMM tile, so the token buffers are
+padded to whole tiles inside (and the pixel decoder's frame count to whole tiles of its coarsest map).  This differs from the ImageVAE,
+which refuses such inputs.  Pad rows are zero-initialised, each GEMM row depends on its own operand row only, and the attention and the
+gathering ``ln_post`` never load a row their sequence does not own: a pad row cannot reach a real row's result.  Nothing mixes frames and
+every summation order is decided from one frame's shape, so a frame decodes to the same bits whatever batch it is part of.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Dict, List, Mapping, Optional, Tuple
+
+import torch
+
+from . import capi
+from .vae import BF, _P, _S, _VideoVAEModule, _pad_to
+
+PRESETS = {"small": (512, 8, 8), "base": (768, 12, 12), "large": (1024, 24, 16)}     # width, layers, heads (head dim 64)
+_PIXEL_UP = ((4, 512, 512), (3, 512, 256), (2, 256, 256), (1, 256, 128), (0, 128, 128))  # (block index, in, out) in run order
+_GEMM_KS2 = 8             # dfot_op_gemm variant: 128x128 tile with K split inside the workgroup
+_ACT_GELU, _ACT_TANH = 0, 1
+
+
+def max_sequence_length() -> int:
+    """L_max of dfot_op_mha_packed"""
+    return int(capi.lib.dfot_op_mha_packed_max_len())
+
+
+class TiTokDecoder(_VideoVAEModule):
+    """The decoder half of the reference ``TiTok_KL`` with its constructor keywords; encoder-only keywords (``vit_enc_model_size``,
+    ``vit_enc_patch_size``, ``use_checkpoint``, ...) are accepted and ignored.  Any frame count >= 1 decodes (see the module docstring)."""
+
+    def __init__(self, image_size: int = 256, token_size: int = 4, use_l2_norm: bool = True, vit_dec_model_size: str = "large",
+                 vit_dec_patch_size: int = 16, num_latent_tokens: int = 32, **encoder_only_keywords_ignored):
+        super().__init__()
+        if vit_dec_model_size not in PRESETS:
+            raise ValueError(f"vit_dec_model_size='{vit_dec_model_size}' is not one of {sorted(PRESETS)}")
+        if int(vit_dec_patch_size) != 16:
+            raise NotImplementedError(f"vit_dec_patch_size={vit_dec_patch_size} is not supported: the pixel decoder upsamples by 16 (the reference "
+                                      "hard-wires it)")
+        if int(image_size) < 16 or int(image_size) % 16:
+            raise ValueError(f"image_size={image_size} must be a positive multiple of 16")
+        if not 1 <= int(token_size) <= 64:
+            raise ValueError(f"token_size={token_size} must be in [1, 64]")
+        if int(num_latent_tokens) < 1:
+            raise ValueError(f"num_latent_tokens={num_latent_tokens} must be positive")
+        self.image_size, self.token_size, self.l2norm = int(image_size), int(token_size), bool(use_l2_norm)
+        self.size, self.nlat = vit_dec_model_size, int(num_latent_tokens)
+        self.width, self.layers, self.heads = PRESETS[vit_dec_model_size]
+        self.grid = self.image_size // 16
+        self.seq = 1 + self.grid ** 2 + self.nlat
+        if self.seq > max_sequence_length():
+            raise ValueError(f"image_size={image_size} gives sequences of {self.seq} tokens; the attention kernel takes up to {max_sequence_length()}")
+        w = self.width
+        sp: List[Tuple[str, Tuple[int, ...]]] = [
+            ("decoder.class_embedding", (1, w)), ("decoder.positional_embedding", (self.grid ** 2 + 1, w)), ("decoder.mask_token", (1, 1, w)),
+            ("decoder.latent_token_positional_embedding", (self.nlat, w)),
+            ("decoder.decoder_embed.weight", (w, self.token_size)), ("decoder.decoder_embed.bias", (w,)),
+            ("decoder.ln_pre.weight", (w,)), ("decoder.ln_pre.bias", (w,))]
+        for i in range(self.layers):
+            r = f"decoder.transformer.{i}"
+            sp += [(f"{r}.ln_1.weight", (w,)), (f"{r}.ln_1.bias", (w,)), (f"{r}.attn.in_proj_weight", (3 * w, w)), (f"{r}.attn.in_proj_bias", (3 * w,)),
+                   (f"{r}.attn.out_proj.weight", (w, w)), (f"{r}.attn.out_proj.bias", (w,)), (f"{r}.ln_2.weight", (w,)), (f"{r}.ln_2.bias", (w,)),
+                   (f"{r}.mlp.c_fc.weight", (4 * w, w)), (f"{r}.mlp.c_fc.bias", (4 * w,)), (f"{r}.mlp.c_proj.weight", (w, 4 * w)),
+                   (f"{r}.mlp.c_proj.bias", (w,))]
+        sp += [("decoder.ln_post.weight", (w,)), ("decoder.ln_post.bias", (w,)), ("decoder.ffn.0.weight", (2 * w, w, 1, 1)),
+               ("decoder.ffn.0.bias", (2 * w,)), ("decoder.ffn.2.weight", (1024, 2 * w, 1, 1)), ("decoder.ffn.2.bias", (1024,)),
+               ("pixel_quantize_conv.weight", (256, 1024, 1, 1)), ("pixel_quantize_conv.bias", (256,)),
+               ("pixel_decoder.conv_in.weight", (512, 256, 3, 3)), ("pixel_decoder.conv_in.bias", (512,))]
+
+        def res(name, ci, co):
+            out = [(f"{name}.norm1.weight", (ci,)), (f"{name}.norm1.bias", (ci,)), (f"{name}.conv1.weight", (co, ci, 3, 3)),
+                   (f"{name}.norm2.weight", (co,)), (f"{name}.norm2.bias", (co,)), (f"{name}.conv2.weight", (co, co, 3, 3))]
+            return out + ([(f"{name}.nin_shortcut.weight", (co, co, 1, 1))] if ci != co else [])
+        for i in range(2):
+            sp += res(f"pixel_decoder.mid.{i}", 512, 512)
+        for idx, ci, co in sorted(_PIXEL_UP):          # the reference registers up.0 first
+            sp += res(f"pixel_decoder.up.{idx}.block.0", ci, co) + res(f"pixel_decoder.up.{idx}.block.1", co, co)
+            if idx != 0:
+                sp += [(f"pixel_decoder.up.{idx}.upsample_conv.weight", (co, co, 3, 3)), (f"pixel_decoder.up.{idx}.upsample_conv.bias", (co,))]
+        sp += [("pixel_decoder.norm_out.weight", (128,)), ("pixel_decoder.norm_out.bias", (128,)),
+               ("pixel_decoder.conv_out.weight", (3, 128, 3, 3)), ("pixel_decoder.conv_out.bias", (3,))]
+        self._specs = sp
+        self._register()
+
+    # ------------------------------------------------------------------ weights -> bf16 GEMM operands
+    def _sync(self) -> None:
+        """every matrix weight (Linear [out][in], in_proj_weight, 1x1 and 3x3 convolutions) packed to its bf16 GEMM operand, once per weight
+        change; biases, norm weights and the embeddings are read in fp32 as they stand"""
+        params = dict(self.named_parameters())
+        sig = tuple((t.data_ptr(), t._version) for t in params.values())
+        if sig == self._sig:
+            return
+        pk: Dict[str, torch.Tensor] = {}
+        for name, t in params.items():
+            if not t.is_cuda:
+                raise RuntimeError(f"parameter {name} is on {t.device}; move the module to the GPU first (there is no CPU path)")
+            w = t.detach().float()
+            if name.endswith("weight") and w.ndim == 2 and name != "decoder.decoder_embed.weight":
+                pk[name] = w.to(BF).contiguous()
+            elif w.ndim == 4 and w.shape[2:] == (1, 1):
+                pk[name] = w.reshape(w.shape[0], w.shape[1]).to(BF).contiguous()
+            elif w.ndim == 4:
+                co, ci = w.shape[:2]
+                cop = _pad_to(co, 64)
+                w2 = torch.zeros(cop, ci, 3, 3, device=w.device)
+                w2[:co] = w
+                out = torch.empty(cop, 9 * ci, dtype=BF, device=w.device)
+                capi.check(capi.lib.dfot_op_pack_conv3(_P(w2.contiguous()), _P(out), cop, ci, 0, _S()))
+                pk[name] = out
+                if name[:-6] + "bias" in params:
+                    b = torch.zeros(cop, device=w.device)
+                    b[:co] = params[name[:-6] + "bias"].detach().float()
+                    pk[name[:-6] + "bias"] = b
+        self._packed, self._sig = pk, sig
+
+    def _par(self, name: str) -> torch.Tensor:
+        return self.get_parameter(name).detach()
+
+    # ------------------------------------------------------------------ building blocks
+    def _gemm(self, a: torch.Tensor, wname: str, bias: Optional[torch.Tensor], resid: Optional[torch.Tensor], rows1: int) -> torch.Tensor:
+        """fp32 [M][N] = a bf16 [M][K] w^T (+ bias) (+ resid).  Whether K is split inside the workgroup (the one tile form with another
+        summation order, picked for few tiles and a long K) is decided from ONE frame's padded rows `rows1`, so a frame's bits do not
+        depend on the batch."""
+        w = self._packed[wname]
+        m, (n, k) = a.shape[0], w.shape
+        out = torch.empty(m, n, device=a.device)
+        if k >= 2048 and (_pad_to(rows1, 128) // 128) * (-(-n // 128)) <= 256:
+            d = capi.GemmDesc()
+            d.qscale, d.eps, d.ksplit, d.variant = 1.0, 1e-6, 1, _GEMM_KS2
+            d.A, d.lda, d.W, d.M, d.N, d.K = a.data_ptr(), k, w.data_ptr(), m, n, k
+            d.bias, d.resid = (bias.data_ptr() if bias is not None else None), (resid.data_ptr() if resid is not None else None)
+            d.out_f32, d.ldo = out.data_ptr(), n
+            capi.check(capi.lib.dfot_op_gemm_ex(C.byref(d), _S()))
+        else:   # here the shape-picked form never splits K: a frame's tile count only grows with the batch
+            capi.check(capi.lib.dfot_op_gemm_f32(_P(a), k, _P(w), _P(bias), _P(resid), _P(out), n, m, n, k, _S()))
+        return out
+
+    def _ln(self, x: torch.Tensor, name: str, rows: int, gather: Tuple[int, int, int] = (0, 0, 0), out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """LayerNorm(eps 1e-5) of the first `rows` rows -> bf16 GEMM operand (rows past `rows` of `out` stay as they are: zero)"""
+        if out is None:
+            out = torch.zeros(x.shape, dtype=BF, device=x.device)
+        capi.check(capi.lib.dfot_op_layernorm(_P(x), _P(self._par(name + ".weight")), _P(self._par(name + ".bias")), 1e-5, _P(out), None, rows,
+                                              self.width, *gather, _S()))
+        return out
+
+    def _bias_act(self, x: torch.Tensor, bias: torch.Tensor, act: int) -> torch.Tensor:
+        out = torch.empty(x.shape, dtype=BF, device=x.device)
+        capi.check(capi.lib.dfot_op_bias_act_bf16(_P(x), x.shape[1], _P(bias), _P(out), x.shape[0], x.shape[1], act, _S()))
+        return out
+
+    def _check(self, z: torch.Tensor) -> torch.device:
+        if z.ndim != 4 or tuple(z.shape[1:]) != (self.token_size, 1, self.nlat):
+            raise ValueError(f"z has shape {tuple(z.shape)}, expected (F, {self.token_size}, 1, {self.nlat})")
+        if z.shape[0] < 1:
+            raise ValueError("z holds no frame")
+        if not z.is_cuda:
+            raise ValueError(f"latents are on {z.device}: the decoder runs on the GPU only (there is no CPU path)")
+        dev = next(self.parameters()).device
+        capi.require_device(dev, z=z)
+        return dev
+
+    def _frames_padded(self, f: int) -> int:
+        """frames the grid-shaped part runs on: whole 128-row tiles of the coarsest map"""
+        import math
+        return _pad_to(f, 128 // math.gcd(128, self.grid ** 2))
+
+    def _transformer(self, z: torch.Tensor) -> torch.Tensor:
+        """steps 1-3 and the ffn: z (F, token_size, 1, nlat) -> logits fp32 [Fp * grid^2][1024], rows of frames >= F are padding"""
+        dev = self._check(z)
+        self._sync()
+        f, w, L, g2 = z.shape[0], self.width, self.seq, self.grid ** 2
+        rows, rows1 = f * L, L
+        mp = _pad_to(rows, 128)
+        p = self._par
+        x = torch.zeros(mp, w, device=dev)
+        zf = z.detach().float().contiguous()                  # (a local: the op takes a raw pointer)
+        capi.check(capi.lib.dfot_op_titok_tokens(
+            _P(zf), _P(p("decoder.decoder_embed.weight")), _P(p("decoder.decoder_embed.bias")),
+            _P(p("decoder.latent_token_positional_embedding")), _P(p("decoder.class_embedding")), _P(p("decoder.mask_token")),
+            _P(p("decoder.positional_embedding")), _P(p("decoder.ln_pre.weight")), _P(p("decoder.ln_pre.bias")), 1e-5, _P(x), f, g2, self.nlat,
+            self.token_size, w, int(self.l2norm), _S()))
+        h = torch.zeros(mp, w, dtype=BF, device=dev)          # LayerNorm output: pad rows stay zero
+        o = torch.zeros(mp, w, dtype=BF, device=dev)          # attention output: rows >= F * L are never written
+        qkv = torch.empty(mp, 3 * w, dtype=BF, device=dev)
+        for i in range(self.layers):
+            r = f"decoder.transformer.{i}"
+            self._ln(x, r + ".ln_1", rows, out=h)
+            capi.check(capi.lib.dfot_op_gemm_bf16(_P(h), w, _P(self._packed[r + ".attn.in_proj_weight"]), _P(p(r + ".attn.in_proj_bias")), _P(qkv), 3 * w,
+                                                  mp, 3 * w, w, _S()))
+            capi.check(capi.lib.dfot_op_mha_packed(_P(qkv), 3 * w, _P(o), f, L, self.heads, _S()))
+            x = self._gemm(o, r + ".attn.out_proj.weight", p(r + ".attn.out_proj.bias"), x, rows1)
+            self._ln(x, r + ".ln_2", rows, out=h)
+            u = self._gemm(h, r + ".mlp.c_fc.weight", None, None, rows1)
+            x = self._gemm(self._bias_act(u, p(r + ".mlp.c_fc.bias"), _ACT_GELU), r + ".mlp.c_proj.weight", p(r + ".mlp.c_proj.bias"), x, rows1)
+        fp = self._frames_padded(f)
+        y = torch.zeros(fp * g2, w, dtype=BF, device=dev)     # ln_post of rows 1 .. grid^2 of every sequence, compact
+        self._ln(x, "decoder.ln_post", f * g2, gather=(L, 1, g2), out=y)
+        u = self._gemm(y, "decoder.ffn.0.weight", None, None, g2)
+        return self._gemm(self._bias_act(u, p("decoder.ffn.0.bias"), _ACT_TANH), "decoder.ffn.2.weight", p("decoder.ffn.2.bias"), None, g2)
+
+    def _pixel_input(self, lg: torch.Tensor) -> torch.Tensor:
+        """softmax over the 1024 channels + pixel_quantize_conv: fp32 [rows][1024] -> fp32 [rows][256]"""
+        probs = torch.empty(lg.shape, dtype=BF, device=lg.device)
+        capi.check(capi.lib.dfot_op_softmax_rows(_P(lg), _P(probs), lg.shape[0], 1024, 1.0, _S()))
+        return self._gemm(probs, "pixel_quantize_conv.weight", self._par("pixel_quantize_conv.bias"), None, self.grid ** 2)
+
+    def _conv(self, x: torch.Tensor, name: str, resid: Optional[torch.Tensor] = None, up: bool = False) -> torch.Tensor:
+        """Conv2dSame(k 3) = Conv2d(k 3, s 1, p 1) on a bf16 [F][H][W][Ci] operand -> fp32 [F][H'][W'][Co]; up: nearest 2x fused in front"""
+        wp, bias = self._packed[name + ".weight"], self._packed.get(name + ".bias")
+        f, h, w, ci = x.shape
+        co = wp.shape[0]
+        if up:
+            out = torch.empty(f, 2 * h, 2 * w, co, device=x.device)
+            capi.check(capi.lib.dfot_op_upconv3x3_f32(_P(x), _P(wp), _P(bias), _P(out), f, h, w, ci, co, _S()))
+        else:
+            out = torch.empty(f, h, w, co, device=x.device)
+            capi.check(capi.lib.dfot_op_conv3t_f32(_P(x), _P(wp), _P(bias), _P(resid), _P(out), f, 1, h, w, ci, co, 1, 1, 1, _S()))
+        return out
+
+    def _res(self, x: torch.Tensor, name: str, ci: int, co: int, b: int) -> torch.Tensor:
+        h = self._conv(self._gn(x, name + ".norm1", True, b), name + ".conv1")
+        if ci == co:
+            return self._conv(self._gn(h, name + ".norm2", True, b), name + ".conv2", resid=x)
+        h = self._conv(self._gn(h, name + ".norm2", True, b), name + ".conv2")
+        f, hh, ww, _ = h.shape                                # h + nin_shortcut(h): the block's input is dropped
+        return self._gemm(self._bf(h).reshape(f * hh * ww, co), name + ".nin_shortcut.weight", None, h.reshape(f * hh * ww, co),
+                          hh * ww).reshape(f, hh, ww, co)
+
+    def _pixel_decoder(self, lat: torch.Tensor) -> torch.Tensor:
+        """maskgit_vqgan.Decoder on fp32 channels-last [Fp][g][g][256] -> fp32 [Fp][16 g][16 g][64] (channels >= 3 are 0)"""
+        f = lat.shape[0]
+        h = self._conv(self._bf(lat), "pixel_decoder.conv_in")
+        for i in range(2):
+            h = self._res(h, f"pixel_decoder.mid.{i}", 512, 512, f)
+        for idx, ci, co in _PIXEL_UP:
+            h = self._res(h, f"pixel_decoder.up.{idx}.block.0", ci, co, f)
+            h = self._res(h, f"pixel_decoder.up.{idx}.block.1", co, co, f)
+            if idx != 0:
+                h = self._conv(self._bf(h), f"pixel_decoder.up.{idx}.upsample_conv", up=True)
+        return self._conv(self._gn(h, "pixel_decoder.norm_out", True, f), "pixel_decoder.conv_out")
+
+    def _to_nchw(self, rows: torch.Tensor, f: int, c: int) -> torch.Tensor:
+        g = self.grid
+        return rows[: f * g * g, :c].reshape(f, g, g, c).permute(0, 3, 1, 2).contiguous()
+
+    # ------------------------------------------------------------------ public entry points
+    @torch.no_grad()
+    def decode_logits(self, z: torch.Tensor) -> torch.Tensor:
+        """``TiTokDecoder.forward``: z (F, token_size, 1, num_latent_tokens) -> logits (F, 1024, grid, grid)"""
+        return self._to_nchw(self._transformer(z), z.shape[0], 1024)
+
+    @torch.no_grad()
+    def decode_pixel_input(self, z: torch.Tensor) -> torch.Tensor:
+        """``pixel_quantize_conv(decoder(z).softmax(1))``: the pixel decoder's input (F, 256, grid, grid)"""
+        return self._to_nchw(self._pixel_input(self._transformer(z)), z.shape[0], 256)
+
+    @torch.no_grad()
+    def decode_pixels(self, lat: torch.Tensor) -> torch.Tensor:
+        """the pixel decoder alone: (F, 256, grid, grid) fp32 -> frames (F, 3, 16 grid, 16 grid)"""
+        g = self.grid
+        if lat.ndim != 4 or tuple(lat.shape[1:]) != (256, g, g):
+            raise ValueError(f"the pixel decoder's input has shape {tuple(lat.shape)}, expected (F, 256, {g}, {g})")
+        if not lat.is_cuda:
+            raise ValueError(f"the pixel decoder's input is on {lat.device}: the decoder runs on the GPU only (there is no CPU path)")
+        capi.require_device(next(self.parameters()).device, lat=lat)
+        self._sync()
+        f = lat.shape[0]
+        cl = torch.zeros(self._frames_padded(f), g, g, 256, device=lat.device)
+        cl[:f] = lat.detach().float().permute(0, 2, 3, 1)
+        return self._pixel_decoder(cl)[:f, :, :, :3].permute(0, 3, 1, 2).contiguous()
+
+    @torch.no_grad()
+    def decode(self, z: torch.Tensor) -> torch.Tensor:
+        """``TiTok_KL.decode``: z (F, token_size, 1, num_latent_tokens) -> frames (F, 3, image_size, image_size)"""
+        f, g = z.shape[0], self.grid
+        lat = self._pixel_input(self._transformer(z))
+        return self._pixel_decoder(lat.reshape(-1, g, g, 256))[:f, :, :, :3].permute(0, 3, 1, 2).contiguous()
+
+    def load_reference_state_dict(self, state_dict: Mapping[str, torch.Tensor]) -> List[str]:
+        """keys of a reference ``TiTok_KL`` (optionally ``vae.``-prefixed): the decoder's own keys are loaded strictly (every one present,
+        with its shape); the encoder's (``encoder.*``, ``latent_tokens``) are ignored and returned.  Any other key raises ``ValueError``."""
+        own = set(self._names)
+        for k in state_dict:
+            n = k[4:] if k.startswith("vae.") else k
+            if n not in own and not (n.startswith("encoder.") or n == "latent_tokens"):
+                raise ValueError(f"unexpected key in a TiTok_KL state dict: {k}")
+        return super().load_reference_state_dict(dict(state_dict))
+
+
+def load_titok_checkpoint(path: str) -> Dict[str, torch.Tensor]:
+    """The recipe's ``model.safetensors`` (a ``TiTok_KL`` state dict) from disk:
+
+        vae = TiTokDecoder(image_size=256, token_size=4).cuda(); vae.load_reference_state_dict(load_titok_checkpoint("model.safetensors"))"""
+    from safetensors.torch import load_file
+    return load_file(path)
+
+
+@torch.no_grad()
+def decode_titok_latents(vae: TiTokDecoder, latents: torch.Tensor, vae_batch_size: int = 2, shape: str = "b t c h w") -> torch.Tensor:
+    """``BaseVideoAlgo._decode`` for a TiTok_KL (base_pytorch_video_algo.py:553-629): latents in the sampler's ``b t c h w`` layout
+    (``(B, T, 4, 1, 32)``), chunks of ``vae.batch_size`` videos whose frames go to the batch, ``decode(y)`` as it is (no rescaling, unlike the
+    ImageVAE branch), result ``(B, T, 3, H, W)``.  Frames are independent, so the chunking does not change a bit of the result."""
+    if shape != "b t c h w":
+        raise ValueError("only the 'b t c h w' layout of the sampling path is supported")
+    if latents.ndim != 5:
+        raise ValueError(f"latents have shape {tuple(latents.shape)}, expected (B, T, C, 1, tokens)")
+    outs = []
+    for ch in torch.chunk(latents, (latents.shape[0] + vae_batch_size - 1) // vae_batch_size, 0):
+        b, t = ch.shape[:2]
+        y = vae.decode(ch.reshape(b * t, *ch.shape[2:]))
+        outs.append(y.reshape(b, t, *y.shape[1:]))
+    return torch.cat(outs, 0)

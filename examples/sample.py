@@ -11,6 +11,8 @@
   python examples/sample.py k600 --continuous --decode-image-vae   (latents -> frames through a random-weight per-frame ImageVAE)
   python examples/sample.py facdit --decode-image-vae [--image-vae-ckpt sd-vae-ft-ema/]   (the taichikl recipe's KL-f8 autoencoder:
                                                      4x32x32 latents -> 256x256 frames; the checkpoint in the diffusers layout)
+  python examples/sample.py taichi --decode-titok [--titok-ckpt model.safetensors]   (DiT-XL on the 1-D token latents 4x1x32 of the taichi
+                                                     recipe, patch 1, 16 frames; TiTok-KL decoder: 32 tokens -> a 256x256 frame)
 
 Without --ckpt the backbone gets seeded random weights (there is no network here to fetch the released checkpoints);
 with it, the reference's .ckpt / ema.safetensors is read by dfot_amd.load_reference_checkpoint (keys
@@ -32,7 +34,7 @@ from bench import RE10K, synth_poses  # noqa: E402
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("model", choices=["re10k", "uvit3d", "k600", "k600diff", "facdit", "facmat"])
+    ap.add_argument("model", choices=["re10k", "uvit3d", "k600", "k600diff", "facdit", "facmat", "taichi"])
     ap.add_argument("--ckpt")
     ap.add_argument("--inputs")
     ap.add_argument("--frames", type=int, default=8)
@@ -51,6 +53,11 @@ def main():
     ap.add_argument("--image-vae-ckpt", metavar="PATH",
                     help="with --decode-image-vae: a VAE in the diffusers layout (a folder with config.json and a .safetensors file, e.g. "
                          "stabilityai/sd-vae-ft-ema or the fine-tuned Taichi VAE), read by dfot_amd.load_diffusers_checkpoint")
+    ap.add_argument("--decode-titok", action="store_true",
+                    help="taichi: decode the sampled 4x1x32 token latents with the TiTok-KL decoder (the `large` preset at 256x256, as "
+                         "titok_kl_preprocessor; random weights unless --titok-ckpt is given)")
+    ap.add_argument("--titok-ckpt", metavar="model.safetensors",
+                    help="with --decode-titok: the recipe's TiTok_KL checkpoint, read by dfot_amd.load_titok_checkpoint")
     ap.add_argument("--attention-maps", metavar="OUT.npz",
                     help="k600 / facdit / facmat: write the frame-to-frame attention maps of every frame-mixing block (per head, query frame x key "
                          "frame; rows follow the model batch) at the steps of --attention-steps, as '<step>/<block name>' and '<step>/noise_levels'")
@@ -58,6 +65,8 @@ def main():
     a = ap.parse_args()
     if a.attention_maps and a.model not in ("k600", "facdit", "facmat"):
         raise SystemExit("--attention-maps: the DiT3D models k600, facdit and facmat only")
+    if a.decode_titok and a.model != "taichi":
+        raise SystemExit("--decode-titok: the taichi model only (latents of 4x1x32 tokens)")
     gen = torch.Generator(device="cuda").manual_seed(a.seed)
     noise = dfot_amd.device_noise_fn(gen)
     conds = None
@@ -92,7 +101,7 @@ def main():
         n_ctx = 2
     else:
         diff, fac, facmat = a.model == "k600diff", a.model == "facdit", a.model == "facmat"
-        x_shape, tokens = ((4, 32, 32), 16) if fac or facmat else ((16, 16, 16), 5)
+        x_shape, tokens = ((4, 32, 32), 16) if fac or facmat else ((4, 1, 32), 16) if a.model == "taichi" else ((16, 16, 16), 5)
         ckw, skw = {}, {}
         if a.cond:
             ctype, num = a.cond.split(":")
@@ -171,6 +180,19 @@ def main():
         frames = dfot_amd.decode_image_latents(vae, out, vae_batch_size=2)
         torch.cuda.synchronize()
         print(f"ImageVAE decode ({a.image_vae_ckpt or 'random weights'}): {tuple(out.shape)} -> {tuple(frames.shape)} in {(time.perf_counter() - t0) * 1e3:.1f} ms")
+    if a.decode_titok:
+        vae = dfot_amd.TiTokDecoder(image_size=256, token_size=out.shape[2], vit_dec_model_size="large", num_latent_tokens=out.shape[4]).cuda()
+        if a.titok_ckpt:
+            ignored = vae.load_reference_state_dict(dfot_amd.load_titok_checkpoint(a.titok_ckpt))
+            print(f"loaded {a.titok_ckpt} ({len(ignored)} encoder keys ignored)")
+        else:
+            vae.init_random(seed=a.seed)
+        dfot_amd.decode_titok_latents(vae, out[:1, :1], vae_batch_size=1)   # packs the weights, loads the kernels
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        frames = dfot_amd.decode_titok_latents(vae, out, vae_batch_size=2)
+        torch.cuda.synchronize()
+        print(f"TiTok decode ({a.titok_ckpt or 'random weights'}): {tuple(out.shape)} -> {tuple(frames.shape)} in {(time.perf_counter() - t0) * 1e3:.1f} ms")
     np.savez_compressed(a.out, out=out.cpu().numpy())
     if a.attention_maps:  # plotting is the caller's: the hook's picture of a block is its map summed over the heads
         maps = {f"{step}/{name}": t.cpu().numpy() for step, rec in sampler.attention_maps.items() for name, t in rec.items()}

@@ -715,6 +715,31 @@ int dfot_op_conv3x3_s2_f32(const void* x, const void* w, const float* bias, floa
 int dfot_op_upconv3x3_f32(const void* x, const void* w, const float* bias, float* y, int frames, int h_in, int w_in, int cin, int cout,
                           void* stream);
 
+/* ---- TiTok-KL decoder pieces (algorithms/vae/tiktok_kl/{titok_kl,blocks_kl}.py: the ViT over [cls | grid^2 mask tokens | latent tokens];
+ * its GEMMs, the channel softmax and the pixel decoder are the ops above). ------------------------------------------------------------ */
+/* The core of nn.MultiheadAttention on the packed in-projection output, for ragged sequences.  qkv bf16 [rows][ld]: columns q | k | v, each
+ * heads adjacent groups of 64 channels (ld >= 3 * heads * 64, a multiple of 8); `seqs` sequences of `len` rows back to back (sequence s owns
+ * rows s * len .. s * len + len - 1); o bf16 [rows][heads * 64] = softmax(q k^T / 8) v per sequence and head.  Any 1 <= len <= the value of
+ * the max_len query (4160), 1 <= heads <= 64; anything else: DFOT_ERR_SHAPE before any device work.  The log2(e) / 8 scale is applied inside
+ * the kernel (exp2 domain, fp32 softmax with the row max subtracted, P rounded to bf16).  Keys past len are masked by select; rows the
+ * sequence does not own (another sequence's, the rows that pad `rows` to a GEMM tile) are never loaded for it, and rows of o outside the
+ * seqs * len owned ones are not written.  One fixed summation order per (len, heads): a sequence's bits do not depend on seqs. */
+int dfot_op_mha_packed(const void* qkv, int64_t ld, void* o, int seqs, int len, int heads, void* stream);
+int dfot_op_mha_packed_max_len(void);
+/* nn.LayerNorm (affine) of fp32 rows [rows][channels], channels in {512, 768, 1024}: out_bf16 and / or out_f32 (either may be NULL, not
+ * both; out_f32 may be x itself in the plain form).  seq_len == 0: row r reads x row r (first = take = 0).  Gather form, seq_len > 0: output
+ * row r reads x row (r / take) * seq_len + first + r % take, rows a multiple of take, first + take <= seq_len. */
+int dfot_op_layernorm(const float* x, const float* gamma, const float* beta, float eps, void* out_bf16, float* out_f32, int64_t rows, int channels,
+                      int seq_len, int first, int take, void* stream);
+/* out bf16 [rows][n] = act(x[rows][ld] + bias[n]); act 0 = GELU in the exact erf form (nn.GELU()), 1 = tanh.  n, ld multiples of 4. */
+int dfot_op_bias_act_bf16(const float* x, int64_t ld, const float* bias, void* out, int64_t rows, int n, int act, void* stream);
+/* The decoder's token sequence in one launch (blocks_kl.py:219-234): out fp32 [frames * (1 + grid2 + num_latent)][channels] = ln_pre of
+ * [cls + pos[0] | mask_token + pos[1 .. grid2] | decoder_embed(z_n[:, t]) + latent_pos[t]], z fp32 (frames, token_size, 1, num_latent),
+ * z_n = F.normalize(z, dim=1) when l2norm (x / max(|x|, 1e-12)), embed_w [channels][token_size].  token_size <= 64. */
+int dfot_op_titok_tokens(const float* z, const float* embed_w, const float* embed_b, const float* latent_pos, const float* cls, const float* mask_token,
+                         const float* pos, const float* gamma, const float* beta, float eps, float* out, int frames, int grid2, int num_latent,
+                         int token_size, int channels, int l2norm, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Micro-benchmarks of the C-ABI primitives at the RE10K model shapes (model batch 2), HIP-event timed.
-Usage (GPU box): python tools/bench_ops.py [gemm] [conv] [attn] [tattn] [mattn] [tattn_bwd] [facdit_train] [mattn_bwd] [facmat_train] [vae_encode] [equal] [dit_front] [ivae] [uvit3d] [gnfilm_frame] [uvit3d_train] [attnmap]"""
+Usage (GPU box): python tools/bench_ops.py [gemm] [conv] [attn] [tattn] [mattn] [tattn_bwd] [facdit_train] [mattn_bwd] [facmat_train] [vae_encode] [equal] [dit_front] [ivae] [uvit3d] [gnfilm_frame] [uvit3d_train] [attnmap] [titok]"""
 import ctypes as C
 import math
 import os
@@ -454,8 +454,33 @@ def ivae():
         print(f"ivae encode 16 frames 3x{r}x{r} -> moments (image_vae.yaml): {med(lambda: enc.encode(y)):.3f} ms", flush=True)
 
 
+def titok():
+    """the TiTok-KL decoder of the taichi recipes: the ragged attention launch alone at the production shape (16 frames of 289 tokens, the
+    `large` preset's 16 heads) and a whole decode of 16 frames at 256 x 256 through the `large` decoder (and the `small` one).  Each figure:
+    the median of 7 repeats of (3 warm-up + 20 timed launches between two HIP events)."""
+    import statistics
+    med = lambda fn, **kw: statistics.median(timeit(fn, **kw) for _ in range(7))
+    for seqs, length, heads in ((16, 289, 16), (1, 289, 16), (16, 1057, 16)):
+        rows = -(-seqs * length // 128) * 128
+        qkv = torch.randn(rows, 3 * heads * 64, device="cuda").bfloat16()
+        o = torch.zeros(rows, heads * 64, dtype=torch.bfloat16, device="cuda")
+        ms = med(lambda: capi.check(capi.lib.dfot_op_mha_packed(P(qkv), 3 * heads * 64, P(o), seqs, length, heads, S())))
+        flop = 4.0 * seqs * heads * length * length * 64
+        print(f"titok mha_packed seqs {seqs:2d} len {length:4d} heads {heads}: {ms*1e3:8.1f} us ({flop / ms / 1e9:6.1f} TF/s)", flush=True)
+    for size in ("large", "small"):
+        dec = dfot_amd.TiTokDecoder(image_size=256, token_size=4, vit_dec_model_size=size).cuda()
+        dec.init_random(0)
+        z = torch.randn(16, 4, 1, 32, device="cuda")
+        ms_t = med(lambda: dec.decode_pixel_input(z), iters=5, warm=1)
+        ms = med(lambda: dec.decode(z), iters=5, warm=1)
+        print(f"titok decode 16 frames 4x1x32 -> 3x256x256 ({size}): {ms:.3f} ms, of which the transformer up to the pixel decoder's input "
+              f"{ms_t:.3f} ms", flush=True)
+
+
 def main():
     what = sys.argv[1:] or ["gemm", "conv", "attn"]
+    if "titok" in what:
+        titok()
     if "attnmap" in what:
         attnmap()
     if "ivae" in what:

@@ -279,3 +279,20 @@ def install_image_vae():
             _ns(name, f"{REF}/{rel}")
     model = importlib.import_module("algorithms.vae.image_vae.model")   # imports algorithms.vae.common.modules for real
     return model.Encoder, model.Decoder
+
+
+def install_titok():
+    """The reference's TiTok_KL (algorithms/vae/tiktok_kl/{titok_kl,blocks_kl,maskgit_vqgan}.py) importable on its own: namespace packages
+    skip algorithms/vae/__init__.py and tiktok_kl/__init__.py (they pull the trainers), ``OmegaConf.create`` is the AttrDict stand-in above
+    (the pixel decoder only reads attributes of its config).  Returns the TiTok_KL class."""
+    if REF not in sys.path:
+        sys.path.insert(0, REF)
+    sys.dont_write_bytecode = True
+    for name, rel in [("algorithms", "algorithms"), ("algorithms.vae", "algorithms/vae"), ("algorithms.vae.tiktok_kl", "algorithms/vae/tiktok_kl"),
+                      ("utils", "utils")]:
+        if name not in sys.modules:
+            _ns(name, f"{REF}/{rel}")
+    if "omegaconf" not in sys.modules:
+        _mod("omegaconf", DictConfig=AttrDict, OmegaConf=types.SimpleNamespace(to_container=_to_container, create=AttrDict))
+    model = importlib.import_module("algorithms.vae.tiktok_kl.titok_kl")   # imports algorithms.vae.common.distribution for real
+    return model.TiTok_KL
