@@ -243,6 +243,8 @@ SIGNATURES = {
     "dfot_op_f32_to_bf16": (_I, [_P, _P, _L, _P]),
     "dfot_op_bf16_to_f32": (_I, [_P, _P, _L, _P]),
     "dfot_op_equal_bits": (_I, [_P, _P, _L, _P, _P]),
+    "dfot_op_dit_final_layer": (_I, [_P, _P, _P, _L, _L, _P, _P, _P, _I, _I, _I, _F] + [_I] * 6 + [_P]),
+    "dfot_op_dit_final_layer_chunked": (_I, [_P, _P, _P, _L, _L, _P, _P, _P, _I, _I, _I, _F] + [_I] * 6 + [_P]),
 }
 
 

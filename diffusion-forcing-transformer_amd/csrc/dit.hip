@@ -582,6 +582,7 @@ __global__ __launch_bounds__(256) void ln_mod_kernel(const float* xin, float* xo
 // Final layer: AdaLN (shift|scale) -> Linear(hidden, p*p*C) -> unpatchify to [BT][C][H][W] (dit3d.py:129-144).
 // One wave per token row; the weight (oc x hidden fp32, 72 KB at K600) is staged in LDS once per workgroup of FIN_ROWS rows.
 constexpr int FIN_ROWS = 16;
+constexpr int FIN_LDS_BYTES = 160 * 1024;  // the whole LDS of a CU
 template <int VEC, int CNT>
 __global__ __launch_bounds__(256) void final_layer_kernel(const float* __restrict__ x, const float* __restrict__ table,
                                                           const int* __restrict__ levels, long ldt, long off,
@@ -620,8 +621,57 @@ __global__ __launch_bounds__(256) void final_layer_kernel(const float* __restric
   }
 }
 
+// The same layer for a weight that does not fit in LDS (DiT/B at the 32-channel Minecraft / dmlab latents: 128 x 768 fp32 = 384 KB): the
+// weight streams through LDS in chunks of `chunk` output rows, each chunk used by all FIN_ROWS rows of the workgroup.  The row loop is
+// final_layer_kernel's own, statement for statement, so that the compiler forms the same multiplies and adds (which products it fuses
+// follows the loop's shape: with a wave's four rows held in registers across the chunks it fused differently and outputs moved by an
+// ulp); a row is therefore normalised again for every chunk, one more read of a row that is in L2.  Same bits as final_layer_kernel.
+template <int VEC, int CNT>
+__global__ __launch_bounds__(256) void final_layer_chunked_kernel(const float* __restrict__ x, const float* __restrict__ table,
+                                                                  const int* __restrict__ levels, long ldt, long off,
+                                                                  const float* __restrict__ w, const float* __restrict__ b,
+                                                                  float* __restrict__ out, int rows_per_frame, int rows, float eps,
+                                                                  int max_level, int c, int hh, int ww, int ps, int chunk) {
+  typedef typename VecT<VEC>::type V;
+  constexpr int hidden = 64 * VEC * CNT;
+  extern __shared__ float wl[];  // [chunk][hidden]
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int oc = ps * ps * c;
+  const int gw = ww / ps;
+  for (int o0 = 0; o0 < oc; o0 += chunk) {
+    const int n = oc - o0 < chunk ? oc - o0 : chunk;
+    if (o0) __syncthreads();  // every wave is done with the previous chunk
+    const float* wc = w + (long)o0 * hidden;
+    for (int i = threadIdx.x * 4; i < n * hidden; i += 1024)
+      *reinterpret_cast<float4v*>(wl + i) = *reinterpret_cast<const float4v*>(wc + i);
+    __syncthreads();
+    for (int rr = wave; rr < FIN_ROWS; rr += 4) {
+      const int row = blockIdx.x * FIN_ROWS + rr;
+      if (row >= rows) break;
+      const int bt = row / rows_per_frame;
+      int lv = levels[bt];
+      lv = lv < 0 ? 0 : (lv > max_level ? max_level : lv);
+      V v[CNT];
+      ln_mod_row<VEC, CNT>(x + (long)row * hidden, table + (long)lv * ldt + off, hidden, eps, lane, v);
+      const int g = row % rows_per_frame, gy = g / gw, gx = g % gw;
+      for (int oo = 0; oo < n; ++oo) {
+        const int o = o0 + oo;  // o = (p, q, channel), channel fastest
+        const float* wr = wl + oo * hidden;
+        float acc = 0.f;
+#pragma unroll
+        for (int i = 0; i < CNT; ++i) acc += vdot<VEC>(v[i], *reinterpret_cast<const V*>(wr + (i * 64 + lane) * VEC));
+        acc = wave_sum(acc);
+        if (lane == 0) {
+          const int ch = o % c, pq = o / c, py = pq / ps, px = pq % ps;
+          out[(((long)bt * c + ch) * hh + gy * ps + py) * ww + gx * ps + px] = acc + b[o];
+        }
+      }
+    }
+  }
+}
+
 // hidden = 64 * VEC * CNT with VEC = 2 when hidden % 128 == 0 (8-byte accesses), else 1
-#define DIT_LN_DISPATCH(CALL)                                  \
+#define DIT_LN_DISPATCH(CALL)                                 \
   switch (hidden % 128 == 0 ? hidden / 128 : hidden % 64 == 0 ? -(hidden / 64) : 0) { \
     case 1: CALL(2, 1); break;                                 \
     case 2: CALL(2, 2); break;                                 \
@@ -657,10 +707,37 @@ int launch_ln_mod(const float* xin, float* x, bf16* obf, const float* table, con
 
 int launch_final_layer(const float* x, const float* table, const int* levels, long ldt, long off, const float* w, const float* b,
                        float* out, int hidden, int rows_per_frame, int rows, float eps, int max_level, int c, int hh, int ww, int ps,
-                       hipStream_t s) {
-  const int lds = ps * ps * c * hidden * (int)sizeof(float);
-  DFOT_REQUIRE(lds <= 160 * 1024, DFOT_ERR_SHAPE, "final layer: weight (%d B) does not fit in LDS", lds);
+                       hipStream_t s, int form = 0, int chunk = 0) {
+  // form 0: the LDS-resident kernel whenever the weight fits (every model that ran before the chunked form existed launches what it
+  // launched then), else the chunked one; 1: LDS-resident or an error; 2: chunked, `chunk` output rows at a time (0 = what fits)
+  const int oc = ps * ps * c;
+  const int lds = oc * hidden * (int)sizeof(float);
+  if (form == 2 || (form == 0 && lds > FIN_LDS_BYTES)) {
+    DFOT_REQUIRE(hidden > 0 && (long)hidden * sizeof(float) <= FIN_LDS_BYTES, DFOT_ERR_SHAPE, "final layer: hidden size %d", hidden);
+    const int fit = FIN_LDS_BYTES / (hidden * (int)sizeof(float));
+    DFOT_REQUIRE(chunk >= 0 && chunk <= fit, DFOT_ERR_ARG, "final layer: chunk of %d output rows (at most %d fit in LDS)", chunk, fit);
+    int ch = chunk ? chunk : fit;
+    ch = ch < oc ? ch : oc;
+    const int clds = ch * hidden * (int)sizeof(float);
 #define CALL(V, C)                                                                                                          \
+  {                                                                                                                         \
+    auto kern = final_layer_chunked_kernel<V, C>;                                                                           \
+    static int lds_set = 0; /* once per instantiation and size (not inside a captured step) */                                \
+    if (lds_set < clds) {                                                                                                   \
+      DFOT_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, clds)); \
+      lds_set = clds;                                                                                                       \
+    }                                                                                                                       \
+    hipLaunchKernelGGL(kern, dim3(cdiv(rows, FIN_ROWS)), dim3(256), clds, s, x, table, levels, ldt, off, w, b, out, rows_per_frame, \
+                       rows, eps, max_level, c, hh, ww, ps, ch);                                                            \
+  }
+    DIT_LN_DISPATCH(CALL)
+#undef CALL
+    DFOT_CHECK_HIP(hipGetLastError());
+    return DFOT_OK;
+  }
+  DFOT_REQUIRE(form == 0 || form == 1, DFOT_ERR_ARG, "final layer: form %d (0 = automatic, 1 = LDS-resident, 2 = chunked)", form);
+  DFOT_REQUIRE(lds <= FIN_LDS_BYTES, DFOT_ERR_SHAPE, "final layer: weight (%d B) does not fit in LDS", lds);
+#define CALL(V, C)                                                                                                        \
   {                                                                                                                         \
     auto kern = final_layer_kernel<V, C>;                                                                                   \
     static int lds_set = 0; /* once per instantiation and size (not inside a captured step) */                                \
@@ -1531,6 +1608,31 @@ int dfot_op_matrix_attention(const void* z, void* o, int batch, int L, int E, in
 int dfot_op_attention_padded(const void* q, const void* k, const void* v, void* o, int ldo, int batch, int heads, int n, int d,
                              void* stream) {
   return launch_attention_padded((const bf16*)q, (const bf16*)k, (const bf16*)v, (bf16*)o, ldo, batch, heads, n, d, (hipStream_t)stream);
+}
+
+static int op_final_layer(const float* x, const float* table, const int32_t* levels, int64_t ldt, int64_t off, const float* w, const float* b,
+                          float* out, int hidden, int rows_per_frame, int rows, float eps, int max_level, int c, int hh, int ww, int patch,
+                          int form, int chunk, void* stream) {
+  DFOT_REQUIRE(x && table && levels && w && b && out, DFOT_ERR_ARG, "final layer: null argument");
+  DFOT_REQUIRE(c > 0 && patch > 0 && hh > 0 && ww > 0 && hh % patch == 0 && ww % patch == 0 && rows_per_frame == (hh / patch) * (ww / patch) &&
+                   rows > 0 && rows % rows_per_frame == 0,
+               DFOT_ERR_SHAPE, "final layer: %d rows of %d per frame for %d x %d frames in patches of %d", rows, rows_per_frame, hh, ww, patch);
+  DFOT_REQUIRE((long)c * patch * patch <= 256, DFOT_ERR_SHAPE, "patch vector too long");
+  DFOT_REQUIRE(hidden > 0 && hidden <= 2048 && max_level >= 0 && off >= 0 && ldt >= off + 2L * hidden, DFOT_ERR_ARG,
+               "final layer: hidden %d, table row of %ld with (shift | scale) at %ld, max_level %d", hidden, (long)ldt, (long)off, max_level);
+  return launch_final_layer(x, table, levels, ldt, off, w, b, out, hidden, rows_per_frame, rows, eps, max_level, c, hh, ww, patch,
+                            (hipStream_t)stream, form, chunk);
+}
+int dfot_op_dit_final_layer(const float* x, const float* table, const int32_t* levels, int64_t ldt, int64_t off, const float* w, const float* b,
+                            float* out, int hidden, int rows_per_frame, int rows, float eps, int max_level, int c, int h, int width, int patch,
+                            int form, void* stream) {
+  return op_final_layer(x, table, levels, ldt, off, w, b, out, hidden, rows_per_frame, rows, eps, max_level, c, h, width, patch, form, 0, stream);
+}
+int dfot_op_dit_final_layer_chunked(const float* x, const float* table, const int32_t* levels, int64_t ldt, int64_t off, const float* w,
+                                    const float* b, float* out, int hidden, int rows_per_frame, int rows, float eps, int max_level, int c, int h,
+                                    int width, int patch, int chunk, void* stream) {
+  DFOT_REQUIRE(chunk > 0, DFOT_ERR_ARG, "final layer: chunk of %d output rows", chunk);
+  return op_final_layer(x, table, levels, ldt, off, w, b, out, hidden, rows_per_frame, rows, eps, max_level, c, h, width, patch, 2, chunk, stream);
 }
 
 }  // extern "C"

@@ -397,10 +397,10 @@ static int launch_colsum_bf16(const bf16* src, float* out, long rows, int n, lon
   return det_sum(part, n, ny, n, out, true, s);
 }
 
-// gradient of the unpatchified output [BT][C][H][W] gathered per token: dyp [rows][64] bf16 (columns >= oc stay zero) and its
-// transpose dyt [.. >= oc rows][rows] (rows >= oc stay zero)
+// gradient of the unpatchified output [BT][C][H][W] gathered per token: dyp [rows][ocp] bf16 (ocp = oc rounded up to 64; columns >= oc
+// stay zero) and its transpose dyt [.. >= oc rows][rows] (rows >= oc stay zero)
 __global__ void final_gather_kernel(const float* __restrict__ dout, bf16* __restrict__ dyp, bf16* __restrict__ dyt, long rows, int c, int hh,
-                                    int ww, int ps) {
+                                    int ww, int ps, int ocp) {
   const int oc = ps * ps * c, gw = ww / ps, P = (hh / ps) * gw;
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= rows * oc) return;
@@ -410,15 +410,16 @@ __global__ void final_gather_kernel(const float* __restrict__ dout, bf16* __rest
   const int g = (int)(row % P), gy = g / gw, gx = g % gw;
   const int ch = o % c, pq = o / c, py = pq / ps, px = pq % ps;
   const bf16 v = f2bf(dout[((bt * c + ch) * hh + gy * ps + py) * ww + gx * ps + px]);
-  dyp[row * 64 + o] = v;
+  dyp[row * ocp + o] = v;
   dyt[(long)o * rows + row] = v;
 }
 
 // PatchEmbed weight gradient: dW[o][kk] += sum_rows dx0[row][o] patch[row][kk], db[o] += sum_rows dx0[row][o].  One workgroup owns
-// 64 * chunks consecutive rows, staged 64 at a time through LDS; for kdim <= 16 (every model here: 3..4 channels x 2x2 patches) the
+// 64 * chunks consecutive rows, staged 64 at a time through LDS; for kdim <= 16 (3..4 channels x 2x2 patches, the K600 latents) the
 // products stay in registers over all chunks, so a workgroup issues hidden * (kdim + 1) atomics once (a 64-row workgroup per launch
-// put 25 M atomics on the 1536 addresses of the 128-wide RE10K embedding: 4.9 ms).  hidden < 256 dividing 256: the 256 / hidden
-// thread groups take alternate rows.
+// put 25 M atomics on the 1536 addresses of the 128-wide RE10K embedding: 4.9 ms).  kdim > 16 (the 32-channel Minecraft / dmlab latents
+// at patch 2: kdim 128, up to 256): one 64-row chunk per workgroup, 16 columns of the patch vector per pass over the chunk, every
+// element of the partial row stored once.  hidden < 256 dividing 256: the 256 / hidden thread groups take alternate rows.
 __global__ __launch_bounds__(256) void pe_wgrad_kernel(const float* __restrict__ dx0, const float* __restrict__ x, float* __restrict__ part,
                                                        int c, int hh, int ww, int ps, int hidden, long rows, int chunks) {
   extern __shared__ float patch[];  // [64][kdim]
@@ -757,6 +758,7 @@ int launch_ln_bwd_rows(const float* dm, const float* x, const float* table, long
 
 struct dfot_dit_train_s : dfot::DitGeom {  // the geometry of cfg (dit_model.h): gh, gw, P, d, dstride, kpatch, oc, c_rows, ldt, mod_final
   DitCfg cfg{};
+  int ocp = 64;  // oc rounded up to the 64-column GEMM tile: row stride of dyp and wfT, K of the d mfin GEMM
   long total = 0;
   std::vector<dfot::DitTensor> params;  // the inventory's parameters (dit_model.h), offsets into the flat buffers set
   float *params_f32 = nullptr, *grads = nullptr;  // attached flat buffers (owned by the caller)
@@ -941,7 +943,8 @@ static int dit_train_create_impl(const DitCfg& c, dfot_dit_train_t* out, int ent
                "train_create: hidden_size %d must be a multiple of 128 and of num_heads", c.hidden_size);
   DFOT_REQUIRE((c.hidden_size / c.num_heads) % 8 == 0 && c.hidden_size / c.num_heads <= 128, DFOT_ERR_ARG, "train_create: head dim must be a multiple of 8, <= 128");
   DFOT_REQUIRE(c.patch_size > 0 && c.height % c.patch_size == 0 && c.width % c.patch_size == 0, DFOT_ERR_ARG, "train_create: patch size");
-  DFOT_REQUIRE(c.in_channels * c.patch_size * c.patch_size <= 64, DFOT_ERR_ARG, "train_create: patch_size^2 * channels must be <= 64");
+  DFOT_REQUIRE(c.in_channels * c.patch_size * c.patch_size <= 256, DFOT_ERR_SHAPE, "train_create: patch vector too long (patch_size^2 * channels = %d, at most 256)",
+               c.in_channels * c.patch_size * c.patch_size);
   DFOT_REQUIRE(c.noise_dim > 0 && c.noise_dim % 2 == 0 && c.depth > 0 && c.timesteps > 0 && c.max_tokens > 0, DFOT_ERR_ARG, "train_create: bad config");
   if (facmat) {
     DFOT_REQUIRE(c.embed_col_dim > 0 && c.embed_col_dim % 64 == 0 && c.embed_col_dim <= 128, DFOT_ERR_ARG, "train_create: embed_col_dim %d must be 64 or 128", c.embed_col_dim);
@@ -956,6 +959,7 @@ static int dit_train_create_impl(const DitCfg& c, dfot_dit_train_t* out, int ent
   auto* h = new dfot_dit_train_s();
   h->cfg = c;
   static_cast<DitGeom&>(*h) = dit_geometry(c);
+  h->ocp = (h->oc + 63) / 64 * 64;
   const int hd = c.hidden_size, E = c.embed_col_dim, P = h->P;
   if (h->P % TR_CHUNKS != 0 || ((facmat || fac) && h->P % 128 != 0)) {
     set_error("train_create: %d patches per frame must be a multiple of %d", h->P, facmat || fac ? 128 : TR_CHUNKS);
@@ -1023,7 +1027,7 @@ static int dit_train_create_impl(const DitCfg& c, dfot_dit_train_t* out, int ent
     return hipMemcpy(*dst, table.data(), table.size() * sizeof(float), hipMemcpyHostToDevice) == hipSuccess ? (int)DFOT_OK : (int)DFOT_ERR_HIP;
   };
   if ((rc = tr_alloc(h, &h->w_mod, (size_t)h->ldt * hd)) || (rc = tr_alloc(h, &h->w_modT, (size_t)h->ldt * hd)) ||
-      (rc = tr_alloc(h, &h->b_mod, (size_t)h->ldt)) || (rc = tr_alloc(h, &h->wfT, (size_t)hd * 64)) ||
+      (rc = tr_alloc(h, &h->b_mod, (size_t)h->ldt)) || (rc = tr_alloc(h, &h->wfT, (size_t)hd * h->ocp)) ||
       (rc = upload(&h->freqs, dit_timestep_freqs(c))))
     return fail(rc);
   if (c.fourier_noise && ((rc = tr_alloc(h, &h->fz_freqs, (size_t)c.noise_dim)) || (rc = tr_alloc(h, &h->fz_phases, (size_t)c.noise_dim)))) return fail(rc);
@@ -1152,10 +1156,10 @@ int dfot_dit_train_sync_weights(dfot_dit_train_t h, void* stream) {
   }
   if ((rc = mod(h->o_fmod_w, h->o_fmod_b, h->mod_final, 2 * hd))) return rc;
   if ((rc = tr_transpose(h->w_mod, h->w_modT, (int)h->ldt, hd, s))) return rc;
-  // wfT[c][o] = fin_w[o][c] (bf16, rows of 64, zero padded)
-  DFOT_CHECK_HIP(hipMemsetAsync(h->wfT, 0, (size_t)hd * 64 * sizeof(bf16), s));
+  // wfT[c][o] = fin_w[o][c] (bf16, rows of ocp, zero padded)
+  DFOT_CHECK_HIP(hipMemsetAsync(h->wfT, 0, (size_t)hd * h->ocp * sizeof(bf16), s));
   for (int o = 0; o < h->oc; ++o)
-    if ((rc = launch_pack_rows(p + h->o_fin_w + (long)o * hd, h->wfT, nullptr, hd, 1, 1, 64, o, s))) return rc;
+    if ((rc = launch_pack_rows(p + h->o_fin_w + (long)o * hd, h->wfT, nullptr, hd, 1, 1, h->ocp, o, s))) return rc;
   h->synced = true;
   return DFOT_OK;
 }
@@ -1207,7 +1211,7 @@ int dfot_dit_train_reserve(dfot_dit_train_t h, int max_batch) {
   WS(h->dsemb, (size_t)fp * hd); WS(h->dwf, (size_t)256 * hd > (size_t)128 * h->P ? (size_t)256 * hd : (size_t)128 * h->P);
   WS(h->dc, (size_t)frames * hd); WS(h->da1, (size_t)frames * hd); WS(h->dh1, (size_t)frames * hd); WS(h->scratch_f, (size_t)hd);
   WS(h->da, rows * hd); WS(h->dO, rows * hd); WS(h->dq, qsz); WS(h->dk, qsz); WS(h->dv, qsz);
-  WS(h->dqkv, rows * 3 * hd); WS(h->dqkvT, rows * widest); WS(h->T1, rows * widest); WS(h->T2, rows * hd); WS(h->dyp, rows * 64); WS(h->dyt, (size_t)256 * rows);
+  WS(h->dqkv, rows * 3 * hd); WS(h->dqkvT, rows * widest); WS(h->T1, rows * widest); WS(h->T2, rows * hd); WS(h->dyp, rows * h->ocp); WS(h->dyt, (size_t)256 * rows);
   WS(h->mfin, rows * hd);
   if (c.cond_type != DFOT_COND_NONE) {
     WS(h->c_dce, (size_t)frames * hd); WS(h->c_mask, (size_t)max_batch); WS(h->c_labels, (size_t)frames);
@@ -1415,17 +1419,17 @@ int dfot_dit_train_backward(dfot_dit_train_t h, const float* d_out, void* stream
   const dim3 fgrid(frames, cdiv(hd, 256), TR_CHUNKS);
 
   // ---- final layer: out = Linear(mfin), mfin = LN(x_fin)(1 + scale) + shift ----
-  if ((rc = zero_fill(h->dyp, (size_t)rows * 64 * sizeof(bf16), s)) || (rc = zero_fill(h->dyt, (size_t)256 * rows * sizeof(bf16), s))) return rc;
+  if ((rc = zero_fill(h->dyp, (size_t)rows * h->ocp * sizeof(bf16), s)) || (rc = zero_fill(h->dyt, (size_t)256 * rows * sizeof(bf16), s))) return rc;
   hipLaunchKernelGGL(final_gather_kernel, dim3(cdiv(rows * h->oc, 256)), dim3(256), 0, s, d_out, h->dyp, h->dyt, rows, c.in_channels, c.height,
-                     c.width, c.patch_size);
-  launch_colsum_bf16(h->dyp, G + h->o_fin_b, rows, h->oc, 64L, s);
+                     c.width, c.patch_size, h->ocp);
+  launch_colsum_bf16(h->dyp, G + h->o_fin_b, rows, h->oc, (long)h->ocp, s);
   DFOT_CHECK_HIP(hipGetLastError());
   float *dY = h->dX, *dN = h->dX2;  // gradient of the current block's output / scratch for the next one
   if ((rc = launch_ln_mod(h->x_fin, dN, h->mfin, h->mod_table, h->idx, h->ldt, h->mod_final, hd, P, (int)rows, c.eps, frames - 1, s))) return rc;
   if ((rc = tr_transpose(h->mfin, h->T2, (int)rows, hd, s))) return rc;                                   // mfin^T [hd][rows]
   if ((rc = tr_wgrad(h->dyt, h->T2, 256, hd, (int)rows, h->dwf, s, h->wg_ws, h->wg_ws_floats))) return rc;   // dWf in the first oc rows (18 tiles: K split)
   DFOT_CHECK_HIP(hipMemcpyAsync(G + h->o_fin_w, h->dwf, (size_t)h->oc * hd * sizeof(float), hipMemcpyDeviceToDevice, s));
-  if ((rc = tr_gemm_f32(h->dyp, 64, h->wfT, (int)rows, hd, 64, dY, hd, nullptr, s))) return rc;             // d mfin
+  if ((rc = tr_gemm_f32(h->dyp, h->ocp, h->wfT, (int)rows, hd, h->ocp, dY, hd, nullptr, s))) return rc;             // d mfin
   auto ln_bwd = [&](const float* x_in, long off) -> int {  // dY holds dm; leaves dx in dY
     int r = launch_ln_bwd_rows(dY, x_in, h->mod_table, h->ldt, off, dN, h->stats, hd, P, (int)rows, c.eps, s);
     if (r) return r;

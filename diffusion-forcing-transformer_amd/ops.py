@@ -14,6 +14,7 @@ FakeTensor tracing, ``torch.compile`` graphs and stream capture treat the HIP ke
     dfot::ray_encoding(raw_poses, resolution) -> cond                                               [dfot_ray_encode]
     dfot::hg_prepare(x, noise?, qa, qb, nfe) -> x_in                                                [dfot_hg_prepare]
     dfot::ddim_hg_step(x, x_in, v, sa, s1, an, cn, keep, weight, gen, nfe) -> x_next                [dfot_ddim_compose / _tokw]
+    dfot::dit_final_layer(x, table, levels, off, weight, bias, eps, c, h, w, patch, form) -> out    [dfot_op_dit_final_layer]
 
 ``model`` is an integer key of a live backbone module (``register_model``): operators take tensors and scalars only.
 The nn.Module mirrors (`UViT3DPose`, `UViT3D`, `DiT3D`, `DifferenceDiT3D`) dispatch their ``forward`` through these operators and the
@@ -302,3 +303,32 @@ def ddim_hg_step(x: Tensor, x_in: Tensor, v: Tensor, sa: Tensor, s1: Tensor, an:
 @ddim_hg_step.register_fake
 def _(x, x_in, v, sa, s1, an, cn, keep, weight, gen, nfe):
     return torch.empty_like(x)
+
+
+# the DiT final layer alone (AdaLN -> Linear -> unpatchify): x [rows][hidden], table [levels][ldt] with (shift | scale) at column `off`,
+# levels int32 [frames], weight [patch * patch * channels][hidden] -> [frames][channels][height][width].  form 0 = the engine's choice,
+# 1 = the LDS-resident kernel (an error when the weight does not fit), 2 = the chunked kernel
+@custom_op("dfot::dit_final_layer", mutates_args=())
+def dit_final_layer(x: Tensor, table: Tensor, levels: Tensor, off: int, weight: Tensor, bias: Tensor, eps: float, channels: int, height: int,
+                    width: int, patch: int, form: int) -> Tensor:
+    F32 = torch.float32
+    if x.ndim != 2 or weight.ndim != 2 or table.ndim != 2 or weight.shape[1] != x.shape[1]:
+        raise ValueError(f"x {tuple(x.shape)}, table {tuple(table.shape)}, weight {tuple(weight.shape)}: expected (rows, hidden), (levels, ldt), (oc, hidden)")
+    oc = patch * patch * channels
+    if tuple(weight.shape) != (oc, x.shape[1]) or tuple(bias.shape) != (oc,):
+        raise ValueError(f"weight {tuple(weight.shape)} / bias {tuple(bias.shape)}, expected {(oc, x.shape[1])} / {(oc,)}")
+    per_frame = (height // patch) * (width // patch)
+    if per_frame <= 0 or x.shape[0] % per_frame != 0 or tuple(levels.shape) != (x.shape[0] // per_frame,):
+        raise ValueError(f"{x.shape[0]} rows of {per_frame} per frame need levels of shape {(x.shape[0] // max(per_frame, 1),)}, got {tuple(levels.shape)}")
+    frames = x.shape[0] // per_frame
+    out = torch.empty(frames, channels, height, width, device=x.device, dtype=F32)
+    capi.check(capi.lib.dfot_op_dit_final_layer(capi.ptr(x, F32, "x"), capi.ptr(table, F32, "table"), capi.ptr(levels, torch.int32, "levels"),
+                                                table.shape[1], off, capi.ptr(weight, F32, "weight"), capi.ptr(bias, F32, "bias"), capi.ptr(out),
+                                                x.shape[1], per_frame, x.shape[0], eps, table.shape[0] - 1, channels, height, width, patch, form,
+                                                capi.stream_ptr()))
+    return out
+
+
+@dit_final_layer.register_fake
+def _(x, table, levels, off, weight, bias, eps, channels, height, width, patch, form):
+    return x.new_empty((levels.shape[0], channels, height, width))

@@ -847,6 +847,16 @@ class DFoTVideoSampler(DFoTVideoPoseSampler):
 
     _static_graph_cond = True
 
+    def __init__(self, cfg: SamplerConfig, backbone, noise_fn: Optional[NoiseFn] = None):
+        super().__init__(cfg, backbone, noise_fn)
+        # Every window reaches the backbone at max_tokens (_sample_sequence pads shorter ones), so that is the one sequence length the DiT
+        # forward sees; its kernels take tokens x patches in multiples of 128.  With 16 patches per frame (the 32-channel Minecraft / dmlab
+        # latents at patch 2) that leaves max_tokens 8, 16, ...: refuse anything else here, not in the middle of a sample.
+        patches = getattr(backbone, "num_patches", None)
+        if isinstance(patches, int) and (cfg.max_tokens * patches) % 128 != 0:
+            raise ValueError(f"max_tokens {cfg.max_tokens} with {patches} patches per frame gives windows of {cfg.max_tokens * patches} "
+                             "tokens x patches; the DiT forward needs a multiple of 128")
+
     def _cond_type(self) -> str:
         t = self.cfg.external_cond_type
         if t not in ("label", "action"):

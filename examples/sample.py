@@ -11,6 +11,8 @@
   python examples/sample.py k600 --continuous --decode-image-vae   (latents -> frames through a random-weight per-frame ImageVAE)
   python examples/sample.py facdit --decode-image-vae [--image-vae-ckpt sd-vae-ft-ema/]   (the taichikl recipe's KL-f8 autoencoder:
                                                      4x32x32 latents -> 256x256 frames; the checkpoint in the diffusers layout)
+  python examples/sample.py mcraft   [--ckpt ...]   (the Minecraft / dmlab DiT recipe: @DiT/B on 32x8x8 latents, patch 2, 16 frames, actions of
+                                                     dim 4 with mask_first, continuous diffusion; --decode-image-vae decodes the 8x8 latents)
   python examples/sample.py taichi --decode-titok [--titok-ckpt model.safetensors]   (DiT-XL on the 1-D token latents 4x1x32 of the taichi
                                                      recipe, patch 1, 16 frames; TiTok-KL decoder: 32 tokens -> a 256x256 frame)
 
@@ -34,7 +36,7 @@ from bench import RE10K, synth_poses  # noqa: E402
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("model", choices=["re10k", "uvit3d", "k600", "k600diff", "facdit", "facmat", "taichi"])
+    ap.add_argument("model", choices=["re10k", "uvit3d", "k600", "k600diff", "facdit", "facmat", "taichi", "mcraft"])
     ap.add_argument("--ckpt")
     ap.add_argument("--inputs")
     ap.add_argument("--frames", type=int, default=8)
@@ -99,6 +101,18 @@ def main():
         sampler = dfot_amd.DFoTVideoSampler(cfg, model, noise)
         xs = torch.randn(a.batch, 8, 3, 256, 256, generator=torch.Generator().manual_seed(a.seed))
         n_ctx = 2
+    elif a.model == "mcraft":  # `dataset=minecraft algorithm=dfot_video @diffusion/continuous @DiT/B`: a 128-wide patch vector, 256 tokens per video
+        x_shape, tokens, dim = (32, 8, 8), 16, 4
+        bb = dict(name="dit3d", variant="full", pos_emb_type="rope_3d", patch_size=2, hidden_size=768, depth=12, num_heads=12, mlp_ratio=4.0,
+                  external_cond_dropout=0.1, use_fourier_noise_embedding=True)
+        model = dfot_amd.DiT3D(bb, x_shape=x_shape, max_tokens=tokens, external_cond_type="action", external_cond_dim=dim).cuda()
+        cfg = dfot_amd.SamplerConfig(x_shape=x_shape, max_tokens=tokens, diffusion=dfot_amd.DiffusionConfig(sampling_timesteps=a.steps, is_continuous=True),
+                                     prediction_guidance=dict(name="vanilla", guidance_scale=1.5), external_cond_type="action", external_cond_dim=dim,
+                                     external_cond_processing="mask_first")
+        sampler = dfot_amd.DFoTVideoSampler(cfg, model, noise)
+        xs = torch.randn(a.batch, tokens, *x_shape, generator=torch.Generator().manual_seed(a.seed))
+        conds = torch.randn(a.batch, tokens, dim, generator=torch.Generator().manual_seed(200 + a.seed))
+        n_ctx = 4
     else:
         diff, fac, facmat = a.model == "k600diff", a.model == "facdit", a.model == "facmat"
         x_shape, tokens = ((4, 32, 32), 16) if fac or facmat else ((4, 1, 32), 16) if a.model == "taichi" else ((16, 16, 16), 5)

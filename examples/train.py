@@ -6,6 +6,8 @@
   python examples/train.py k600diff [--accumulate 2]                                  # the model bash/k600/*.sh train
   python examples/train.py facmat   [--xl] [--batch 8]                                # FacMatDiT (dit3d_factorized_matrix.yaml); --xl: XL-64-1, taichikl shape
   python examples/train.py facdit   [--xl] [--batch 8]                                # FacDiT (dit3d_factorized_attention.yaml); --xl: @DiT/XL widths, taichikl shape
+  python examples/train.py mcraft   [--b] [--batch 8]                                 # the Minecraft / dmlab DiT recipe (32x8x8 latents, patch 2, 16 frames,
+                                                                                      # actions of dim 4, continuous); --b: @DiT/B, else width 384, depth 2
   python examples/train.py re10k    [--batch 8]                                       # RE10K UViT3DPose (BASELINE config 5), synthetic frames + poses
   python examples/train.py uvit3d   [--cond action:4] [--full] [--batch 2]            # pose-free UViT3D (u_vit3d.yaml); --full: its widths, 8 heads, 256 x 256
   python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 examples/train.py k600   # data parallel, one rank per GPU
@@ -35,7 +37,7 @@ K600_DATA_STD = [5.591, 5.257, 7.033, 6.401, 6.091, 11.233, 5.608, 7.5, 5.277, 5
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("model", choices=["k600", "k600diff", "facmat", "facdit", "re10k", "uvit3d"])
+    ap.add_argument("model", choices=["k600", "k600diff", "facmat", "facdit", "re10k", "uvit3d", "mcraft"])
     ap.add_argument("--ckpt")
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--batch", type=int, default=8)
@@ -49,6 +51,7 @@ def main():
                          "training schedule shifted 0.125, sigmoid loss weighting)")
     ap.add_argument("--xl", action="store_true", help="facmat / facdit: @FacMatDiT/XL-64-1 / @DiT/XL widths at the taichikl shape (4x32x32 latents, "
                                                       "patch 2, 16 frames) instead of the tiny default (width 128, depth 2, 4x16x8 latents, 5 frames)")
+    ap.add_argument("--b", action="store_true", help="mcraft: @DiT/B (hidden 768, depth 12, 12 heads) instead of the tiny default (hidden 384, depth 2, 6 heads)")
     ap.add_argument("--full", action="store_true", help="uvit3d: the widths, depths and dropouts of u_vit3d.yaml with num_heads 8 (its 4 heads give head "
                                                         "dim 256, which the attention kernels do not take) on 8 frames of 3 x 256 x 256, instead of the "
                                                         "tiny default (channels 128/128/128/256, 2 heads, one block per level, 8 frames of 3 x 64 x 64)")
@@ -67,7 +70,10 @@ def main():
         return train_uvit3d(a, rank, world)
     if a.model in ("facmat", "facdit"):
         return train_factorized(a, rank, world)
-    diff = a.model == "k600diff"
+    diff, mcraft = a.model == "k600diff", a.model == "mcraft"
+    x_shape, tokens = ((32, 8, 8), 16) if mcraft else ((16, 16, 16), 5)
+    if mcraft:  # dataset=minecraft / dmlab: actions of dim 4 with mask_first; @diffusion/continuous
+        a.cond, a.continuous = a.cond or "action:4", True
     ctype, cnum, ckw = None, 0, {}
     if a.cond:
         ctype, cnum = a.cond.split(":")[0], int(a.cond.split(":")[1])
@@ -86,12 +92,14 @@ def main():
                                           variable_context=dfot_amd.ContextTraining(enabled=True, prob=0.25, dropout=0.3))
     else:
         cfg = dict(name="dit3d", variant="full", pos_emb_type="rope_3d", patch_size=1, hidden_size=1152, depth=28, num_heads=16)
+        if mcraft:  # patch 2 on 8x8 latents of 32 channels: a 128-wide patch vector, 16 patches per frame
+            cfg.update(patch_size=2, **(dict(hidden_size=768, depth=12, num_heads=12) if a.b else dict(hidden_size=384, depth=2, num_heads=6)))
         cfg["use_fourier_noise_embedding"] = a.continuous
         if a.cond:
             cfg["external_cond_dropout"] = 0.1
-        init = dfot_amd.DiT3D(cfg, x_shape=(16, 16, 16), max_tokens=5, **ckw)
+        init = dfot_amd.DiT3D(cfg, x_shape=x_shape, max_tokens=tokens, **ckw)
         sampling = dfot_amd.TrainingNoise(noise_level="random_independent", is_continuous=a.continuous, n_context_tokens=2)
-    trainer = dfot_amd.DiT3DTrainer(cfg, x_shape=(16, 16, 16), max_tokens=5, lr=a.lr,
+    trainer = dfot_amd.DiT3DTrainer(cfg, x_shape=x_shape, max_tokens=tokens, lr=a.lr,
                                     diffusion=dfot_amd.DiffusionConfig(is_continuous=True) if a.continuous else None, **ckw)
     if a.ckpt:
         dfot_amd.load_reference_checkpoint(trainer, a.ckpt)
@@ -109,7 +117,7 @@ def main():
         else:
             encoder.init_random(seed=0)
         gv = torch.Generator(device="cuda").manual_seed(2000 + rank)
-    masks = torch.ones(a.batch, 5, dtype=torch.bool)
+    masks = torch.ones(a.batch, tokens, dtype=torch.bool)
     t0 = time.perf_counter()
     for step in range(a.steps):
         for _ in range(a.accumulate):
@@ -117,12 +125,12 @@ def main():
                 videos = torch.rand(a.batch, 17, 3, 128, 128, device="cuda", generator=gv)
                 frames = dfot_amd.encode_videos(encoder, videos, vae_batch_size=2, generator=gv, data_mean=K600_DATA_MEAN, data_std=K600_DATA_STD)
             else:
-                frames = torch.randn(a.batch, 5, 16, 16, 16, generator=g)
-            noise = torch.randn(a.batch, 10 if diff else 5, 16, 16, 16, generator=g)
-            levels, loss_masks = sampling.sample(a.batch, 5, masks, g, training=True)
+                frames = torch.randn(a.batch, tokens, *x_shape, generator=g)
+            noise = torch.randn(a.batch, 2 * tokens if diff else tokens, *x_shape, generator=g)
+            levels, loss_masks = sampling.sample(a.batch, tokens, masks, g, training=True)
             conds = None
             if ctype == "action":
-                conds = torch.randn(a.batch, 5, cnum, generator=g)
+                conds = torch.randn(a.batch, tokens, cnum, generator=g)
                 conds[:, :1] = 0  # external_cond_processing: mask_first
             elif ctype == "label":
                 conds = torch.randint(0, cnum, (a.batch, 1), generator=g)

@@ -284,6 +284,20 @@ int dfot_dit_forward_f(dfot_dit_t h, const float* x, const float* noise_levels, 
  * model, which tabulates nothing), "stream" [B*T*P][hidden] (residual stream after the last block), "cond_emb" [B*T][hidden] (e of the
  * last per-frame forward), "noise_feat" [B*T][noise_dim] (Fourier features of the last dfot_dit_forward_f) */
 int dfot_dit_read_tap(dfot_dit_t h, const char* name, float* out, size_t capacity_floats, void* stream);
+/* The DiT final layer alone (test / benchmark entry of the launch both engines make): out [frames][c][h][w] fp32 = unpatchify(Linear(
+ * LayerNorm(x) * (1 + scale) + shift)) for x [rows][hidden] fp32, rows = frames * rows_per_frame, rows_per_frame = (h / patch) * (w / patch),
+ * (shift | scale) = table[clamp(levels[frame], 0, max_level)][off .. off + 2 * hidden) with table rows of ldt floats, weight [patch * patch * c]
+ * [hidden] fp32 with the output index (py, px, channel), channel fastest, bias [patch * patch * c].  hidden: a LayerNorm kernel width <= 2048;
+ * patch * patch * c <= 256.  form 0: the engine's own choice (the LDS-resident kernel whenever the weight fits in 160 KiB, else the chunked
+ * one); 1: the LDS-resident kernel, DFOT_ERR_SHAPE if the weight does not fit; 2: the chunked kernel, which streams floor(160 KiB / (4 *
+ * hidden)) weight rows at a time through LDS.  Both kernels add an output's products in the same order: the same bits. */
+int dfot_op_dit_final_layer(const float* x, const float* table, const int32_t* levels, int64_t ldt, int64_t off, const float* w, const float* b,
+                            float* out, int hidden, int rows_per_frame, int rows, float eps, int max_level, int c, int h, int width, int patch,
+                            int form, void* stream);
+/* the chunked kernel with `chunk` (> 0, at most what fits) weight rows per pass: lets a test split a small weight as a large one splits */
+int dfot_op_dit_final_layer_chunked(const float* x, const float* table, const int32_t* levels, int64_t ldt, int64_t off, const float* w,
+                                    const float* b, float* out, int hidden, int rows_per_frame, int rows, float eps, int max_level, int c, int h,
+                                    int width, int patch, int chunk, void* stream);
 
 /* ---- attention maps (the read-out of the reference's attn_hook: algorithms/common/attn_hook/hook.py, dit_blocks.py:100-118) ----
  * Which frame attends to which, per head, of the blocks whose attention mixes frames: the blocks of variant 0 (full 3-D attention), the

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Micro-benchmarks of the C-ABI primitives at the RE10K model shapes (model batch 2), HIP-event timed.
-Usage (GPU box): python tools/bench_ops.py [gemm] [conv] [attn] [tattn] [mattn] [tattn_bwd] [facdit_train] [mattn_bwd] [facmat_train] [vae_encode] [equal] [dit_front] [ivae] [uvit3d] [gnfilm_frame] [uvit3d_train] [attnmap] [titok]"""
+Usage (GPU box): python tools/bench_ops.py [gemm] [conv] [attn] [tattn] [mattn] [tattn_bwd] [facdit_train] [mattn_bwd] [facmat_train] [vae_encode] [equal] [dit_front] [ivae] [uvit3d] [gnfilm_frame] [uvit3d_train] [attnmap] [titok] [mcraft]"""
 import ctypes as C
 import math
 import os
@@ -84,6 +84,55 @@ def dit_front(name, bb, cls, x_shape, max_tokens, batch, tokens):
         print(f"dit_front {name:10s} B={batch} T={tokens} {path:9s}: front end {front*1e3:8.1f} us  forward {whole:8.3f} ms", flush=True)
     f, c = rows[0], rows[1]
     print(f"dit_front {name:10s} float - int cond: front end {(f[1]-c[1])*1e3:+.1f} us, forward {(f[2]-c[2])*1e3:+.1f} us", flush=True)
+
+
+def final_layer(hidden, oc_c, patch, hw, frames, form):
+    """dfot_op_dit_final_layer alone: frames x (hw / patch)^2 rows -> (ms, rows, outputs per row)"""
+    per_frame = (hw // patch) ** 2
+    rows, oc = frames * per_frame, patch * patch * oc_c
+    x = torch.randn(rows, hidden, device="cuda")
+    table = 0.5 * torch.randn(frames, 2 * hidden, device="cuda")
+    levels = torch.arange(frames, device="cuda", dtype=torch.int32)
+    w = torch.randn(oc, hidden, device="cuda") / math.sqrt(hidden)
+    b = torch.zeros(oc, device="cuda")
+    out = torch.empty(frames, oc_c, hw, hw, device="cuda")
+    ms = timeit(lambda: capi.check(capi.lib.dfot_op_dit_final_layer(P(x), P(table), P(levels), 2 * hidden, 0, P(w), P(b), P(out), hidden, per_frame, rows,
+                                                                    1e-6, frames - 1, oc_c, hw, hw, patch, form, S())), iters=50, warm=5)
+    return ms, rows, oc
+
+
+def mcraft():
+    """The Minecraft / dmlab recipe (`dataset=minecraft algorithm=dfot_video @diffusion/continuous @DiT/B`): latents 32x8x8, patch 2 (128-wide
+    patch vector, 16 patches per frame), 16 frames, actions of dim 4.  The chunked final-layer launch alone next to the LDS-resident one at
+    the K600 shape, one forward at batch 16, one training step at batch 8."""
+    ms, rows, oc = final_layer(768, 32, 2, 8, 16 * 16, 2)
+    print(f"mcraft final layer chunked  rows={rows} hidden=768 oc={oc}: {ms*1e3:8.1f} us  {ms * 1e6 / (rows * oc):6.3f} ns per (row x output), "
+          f"weight {oc * 768 * 4 / 1024:.0f} KB per 16-row workgroup in 3 chunks", flush=True)
+    ms, rows, oc = final_layer(1152, 16, 1, 16, 8 * 5, 1)
+    print(f"mcraft final layer resident rows={rows} hidden=1152 oc={oc} (K600): {ms*1e3:8.1f} us  {ms * 1e6 / (rows * oc):6.3f} ns per (row x output), "
+          f"weight {oc * 1152 * 4 / 1024:.0f} KB per 16-row workgroup", flush=True)
+    ms, rows, oc = final_layer(1152, 16, 1, 16, 8 * 5, 2)
+    print(f"mcraft final layer chunked  rows={rows} hidden=1152 oc={oc} (K600, one chunk): {ms*1e3:8.1f} us  {ms * 1e6 / (rows * oc):6.3f} ns per (row x output)",
+          flush=True)
+    bb = dict(name="dit3d", variant="full", pos_emb_type="rope_3d", patch_size=2, hidden_size=768, depth=12, num_heads=12, mlp_ratio=4.0,
+              external_cond_dropout=0.1, use_fourier_noise_embedding=True)
+    kw = dict(external_cond_type="action", external_cond_dim=4)
+    model = dfot_amd.DiT3D(bb, x_shape=(32, 8, 8), max_tokens=16, **kw).cuda().eval()
+    model.init_random(0)
+    x = torch.randn(16, 16, 32, 8, 8, device="cuda")
+    lv = 2.5 * torch.randn(16, 16, device="cuda")
+    cond = torch.randn(16, 16, 4, device="cuda")
+    with torch.no_grad():
+        ms = timeit(lambda: model(x, lv, cond), iters=50, warm=5)
+    print(f"mcraft forward @DiT/B B=16 T=16 (4096 rows): {ms:8.3f} ms", flush=True)
+    tr = dfot_amd.DiT3DTrainer(bb, x_shape=(32, 8, 8), max_tokens=16, diffusion=dfot_amd.DiffusionConfig(is_continuous=True), **kw)
+    tr.load_state_dict({k: v.detach() for k, v in model.state_dict().items()})
+    g = torch.Generator(device="cuda").manual_seed(0)
+    xs, noise = torch.randn(8, 16, 32, 8, 8, device="cuda", generator=g), torch.randn(8, 16, 32, 8, 8, device="cuda", generator=g)
+    t = torch.rand(8, 16, device="cuda", generator=g)
+    acts = torch.randn(8, 16, 4, device="cuda", generator=g)
+    ms = timeit(lambda: tr.training_step(xs, t, noise, None, conditions=acts, dropout_generator=g), iters=20, warm=3)
+    print(f"mcraft training step @DiT/B B=8 T=16, actions, continuous: {ms:8.2f} ms", flush=True)
 
 
 HBM_TBS = 8.0  # the HBM3E rate the repository's rooflines use (DESIGN.md)
@@ -483,6 +532,8 @@ def main():
         titok()
     if "attnmap" in what:
         attnmap()
+    if "mcraft" in what:
+        mcraft()
     if "ivae" in what:
         ivae()
     if "vae_encode" in what:
@@ -526,8 +577,8 @@ def main():
         xl = dict(name="dit3d", variant="full", pos_emb_type="rope_3d", patch_size=1, hidden_size=1152, depth=28, num_heads=16)
         dit_front("XL K600", xl, dfot_amd.DiT3D, (16, 16, 16), 5, 8, 5)  # @DiT/XL at the K600 latents: B = 8, T = 5, P = 256
         b = dict(name="dit3d", variant="full", pos_emb_type="rope_3d", patch_size=2, hidden_size=768, depth=12, num_heads=12)
-        # @DiT/B width, 16 tokens x 16 patches, B = 16.  8 latent channels: at hidden 768 the final layer stages its (p*p*C x hidden) fp32 weight in
-        # LDS and refuses the 32-channel dmlab / Minecraft latents (393 KB); the front end does not depend on the channel count
+        # @DiT/B width, 16 tokens x 16 patches, B = 16.  8 latent channels (a final weight that stays in LDS; `mcraft` measures the recipe's own
+        # 32 channels, whose 393 KB weight takes the chunked final layer); the front end does not depend on the channel count
         dit_front("DiT/B", b, dfot_amd.DiT3D, (8, 8, 8), 16, 16, 16)
     if "conv" in what:
         for name, (bt, h, w, ci, co) in {"L0 res": (16, 128, 128, 128, 128), "L1 res": (16, 64, 64, 256, 256),
