@@ -23,4 +23,5 @@ from .vae import VideoVAEDecoder, VideoVAEEncoder, VideoVAEPosterior, decode_lat
 from .image_vae import (ImageVAEDecoder, ImageVAEEncoder, ImageVAEPosterior, decode_image_latents,  # noqa: F401,E402
                         encode_image_frames, ddconfig_from_diffusers, diffusers_to_reference_keys,  # noqa: F401,E402
                         load_diffusers_checkpoint)  # noqa: F401,E402
-from .titok import TiTokDecoder, decode_titok_latents, load_titok_checkpoint  # noqa: F401,E402
+from .titok import (TiTokDecoder, TiTokEncoder, decode_titok_latents, encode_titok_frames,  # noqa: F401,E402
+                    load_titok_checkpoint)  # noqa: F401,E402

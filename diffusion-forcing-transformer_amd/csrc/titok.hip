@@ -21,6 +21,11 @@
 //   dfot_op_bias_act_bf16     fp32 GEMM output + bias -> GELU (exact erf form, nn.GELU()) or tanh -> bf16
 //   dfot_op_titok_tokens      F.normalize(z, dim=1), decoder_embed (K = token_size: VALU), the positional adds, the cls / mask rows and
 //                             ln_pre in one launch -> the fp32 residual stream
+// and for the encoder half (the same blocks over [cls | grid^2 patches | 32 latent tokens]):
+//   dfot_op_titok_patch_rows  frames fp32 (F, 3, S, S) -> the bf16 A operand [F * grid^2][768] of the patch-embedding GEMM
+//   dfot_op_titok_enc_tokens  cls / patch rows + positional_embedding, latent_tokens + their positional embedding, ln_pre in one launch
+//   dfot_op_titok_moments     conv_out on the reference's reshape of the ln_post rows (a reinterpretation of each frame's block) -> the
+//                             moments in the layout dfot_op_vae_posterior reads, all fp32
 #include <math.h>
 
 #include "attention_common.h"
@@ -286,6 +291,88 @@ __global__ __launch_bounds__(256) void titok_tokens_kernel(const float* __restri
   ln_row(v, n4, lane, c, eps, gamma, beta, nullptr, out + row * c);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Encoder front and back (blocks_kl.py:140-166).
+// The A operand of the patch-embedding GEMM.  One thread per 8 output elements, in destination order: a wave writes 1024 contiguous
+// bytes and reads the 16-pixel runs behind them (64 contiguous bytes each, two lanes per run).
+__global__ __launch_bounds__(256) void titok_patch_rows_kernel(const float* __restrict__ frames, bf16* __restrict__ rows, long total8, int s, int g) {
+  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= total8) return;
+  const long row = idx / 96;                       // 768 / 8 chunks per row
+  const int k8 = (int)(idx - row * 96);
+  const int c = k8 >> 5, dy = (k8 >> 1) & 15, half = k8 & 1;
+  const int g2 = g * g;
+  const long f = row / g2;
+  const int p = (int)(row - f * g2);
+  const int py = p / g, px = p - py * g;
+  const float* src = frames + ((f * 3 + c) * s + 16 * py + dy) * (long)s + 16 * px + 8 * half;
+  const f32x4 a = *reinterpret_cast<const f32x4*>(src), b = *reinterpret_cast<const f32x4*>(src + 4);
+  bf16x8 o;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    o[j] = f2bf(a[j]);
+    o[4 + j] = f2bf(b[j]);
+  }
+  *reinterpret_cast<bf16x8*>(rows + row * 768 + k8 * 8) = o;
+}
+
+__global__ __launch_bounds__(256) void titok_enc_tokens_kernel(const float* __restrict__ patches, long ldp, const float* __restrict__ cls,
+                                                               const float* __restrict__ pos, const float* __restrict__ lat, const float* __restrict__ lpos,
+                                                               const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
+                                                               float* __restrict__ out, long rows, int grid2, int nlat, int c) {
+  const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const int lane = threadIdx.x & 63, n4 = c >> 8;
+  const int len = 1 + grid2 + nlat;
+  const long f = row / len;
+  const int i = (int)(row - f * len);
+  // [cls | patch_embed(x)] + positional_embedding[i], then latent_tokens[t] + latent_token_positional_embedding[t]
+  const float* a = i == 0 ? cls : i <= grid2 ? patches + (f * grid2 + i - 1) * ldp : lat + (long)(i - 1 - grid2) * c;
+  const float* b = i <= grid2 ? pos + (long)i * c : lpos + (long)(i - 1 - grid2) * c;
+  f32x4 v[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+    if (k < n4) {
+      const int col = 4 * (lane + 64 * k);
+      v[k] = *reinterpret_cast<const f32x4*>(a + col) + *reinterpret_cast<const f32x4*>(b + col);
+    }
+  ln_row(v, n4, lane, c, eps, gamma, beta, nullptr, out + row * c);
+}
+
+// conv_out on the reference's reshape(batch, width, num_latent, 1) of the contiguous (batch, num_latent, width) ln_post rows: a
+// REINTERPRETATION, not a transpose -- "channel" ch at position n is flat element ch * nlat + n of the frame's block.  A workgroup owns
+// one frame and two output channels.  Thread e < slices * nlat (slices = 256 / nlat) is position n = e % nlat of slice e / nlat and sums
+// the channels ch = slice, slice + slices, ...: in step k the active threads read the flat elements k * slices * nlat + e, contiguous.
+// The slices' partial sums are added in slice order: one summation order per (nlat, channels), all fp32.
+__global__ __launch_bounds__(256) void titok_moments_kernel(const float* __restrict__ t, const float* __restrict__ w, const float* __restrict__ bias,
+                                                            float* __restrict__ out, long ldo, int nlat, int c, int pairs) {
+  __shared__ float part[2][256];
+  const int e = threadIdx.x;
+  const long f = blockIdx.x / pairs;
+  const int o = 2 * (int)(blockIdx.x - f * pairs);
+  const int slices = 256 / nlat;
+  const int slice = e / nlat, n = e - slice * nlat;
+  const float* tf = t + f * (long)nlat * c;
+  const float* w0 = w + (long)o * c;
+  const float* w1 = w0 + c;
+  float a0 = 0.f, a1 = 0.f;
+  if (slice < slices)
+    for (int ch = slice; ch < c; ch += slices) {
+      const float x = tf[(long)ch * nlat + n];
+      a0 = fmaf(w0[ch], x, a0);
+      a1 = fmaf(w1[ch], x, a1);
+    }
+  part[0][e] = a0;
+  part[1][e] = a1;
+  __syncthreads();
+  if (e < 2 * nlat) {
+    const int j = e / nlat, m = e - j * nlat;
+    float s = bias[o + j];
+    for (int sl = 0; sl < slices; ++sl) s += part[j][sl * nlat + m];
+    out[(f * nlat + m) * ldo + o + j] = s;
+  }
+}
+
 bool width_ok(int c) { return c == 512 || c == 768 || c == 1024; }
 
 }  // namespace
@@ -347,6 +434,49 @@ int dfot_op_titok_tokens(const float* z, const float* embed_w, const float* embe
   const long rows = (long)frames * (1 + grid2 + num_latent);
   hipLaunchKernelGGL(titok_tokens_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, (hipStream_t)stream, z, embed_w, embed_b, latent_pos, cls, mask_token, pos,
                      gamma, beta, eps, out, rows, grid2, num_latent, token_size, channels, l2norm);
+  DFOT_CHECK_HIP(hipGetLastError());
+  return DFOT_OK;
+}
+
+int dfot_op_titok_patch_rows(const float* frames, void* rows_bf16, int nframes, int image_size, void* stream) {
+  DFOT_REQUIRE(frames && rows_bf16 && (const void*)frames != rows_bf16, DFOT_ERR_ARG, "op_titok_patch_rows: null or aliased argument");
+  DFOT_REQUIRE(nframes > 0 && image_size >= 16 && image_size % 16 == 0 && image_size <= 4096 &&
+                   (long)nframes * (image_size / 16) * (image_size / 16) < (1L << 31) / 96,
+               DFOT_ERR_SHAPE, "op_titok_patch_rows: nframes=%d frames of image_size=%d (a positive multiple of 16, up to 4096; nframes * (image_size / 16)^2 "
+               "rows below 2^31 / 96)", nframes, image_size);
+  const int g = image_size / 16;
+  const long total8 = (long)nframes * g * g * 96;
+  hipLaunchKernelGGL(titok_patch_rows_kernel, dim3(cdiv(total8, 256)), dim3(256), 0, (hipStream_t)stream, frames, (bf16*)rows_bf16, total8, image_size, g);
+  DFOT_CHECK_HIP(hipGetLastError());
+  return DFOT_OK;
+}
+
+int dfot_op_titok_enc_tokens(const float* patches, int64_t ldp, const float* cls, const float* pos, const float* latent_tokens, const float* latent_pos,
+                             const float* gamma, const float* beta, float eps, float* out, int frames, int grid2, int num_latent, int channels,
+                             void* stream) {
+  DFOT_REQUIRE(patches && cls && pos && latent_tokens && latent_pos && gamma && beta && out && patches != out, DFOT_ERR_ARG,
+               "op_titok_enc_tokens: null or aliased argument");
+  DFOT_REQUIRE(frames > 0 && grid2 >= 1 && num_latent >= 1 && width_ok(channels) && ldp >= channels && ldp % 4 == 0 &&
+                   (long)frames * (1 + grid2 + num_latent) < (1L << 31),
+               DFOT_ERR_SHAPE, "op_titok_enc_tokens: frames=%d grid2=%d num_latent=%d channels=%d (512, 768 or 1024), patch row stride ldp=%ld (>= channels, a "
+               "multiple of 4)", frames, grid2, num_latent, channels, (long)ldp);
+  const long rows = (long)frames * (1 + grid2 + num_latent);
+  hipLaunchKernelGGL(titok_enc_tokens_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, (hipStream_t)stream, patches, (long)ldp, cls, pos, latent_tokens,
+                     latent_pos, gamma, beta, eps, out, rows, grid2, num_latent, channels);
+  DFOT_CHECK_HIP(hipGetLastError());
+  return DFOT_OK;
+}
+
+int dfot_op_titok_moments(const float* t, const float* w, const float* bias, float* out, int64_t ldo, int frames, int num_latent, int channels,
+                          int out_channels, void* stream) {
+  DFOT_REQUIRE(t && w && bias && out && t != out, DFOT_ERR_ARG, "op_titok_moments: null or aliased argument");
+  DFOT_REQUIRE(frames > 0 && num_latent >= 1 && num_latent <= 128 && width_ok(channels) && out_channels >= 2 && out_channels <= 128 &&
+                   out_channels % 2 == 0 && ldo >= out_channels && (long)frames * (out_channels / 2) < (1L << 31),
+               DFOT_ERR_SHAPE, "op_titok_moments: frames=%d num_latent=%d (1 .. 128) channels=%d (512, 768 or 1024) out_channels=%d (even, 2 .. 128), row "
+               "stride ldo=%ld (>= out_channels)", frames, num_latent, channels, out_channels, (long)ldo);
+  const int pairs = out_channels / 2;
+  hipLaunchKernelGGL(titok_moments_kernel, dim3((unsigned)((long)frames * pairs)), dim3(256), 0, (hipStream_t)stream, t, w, bias, out, (long)ldo,
+                     num_latent, channels, pairs);
   DFOT_CHECK_HIP(hipGetLastError());
   return DFOT_OK;
 }

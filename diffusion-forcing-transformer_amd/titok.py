@@ -1,7 +1,14 @@
-"""TiTok-KL decoder on the MI355X engine: the 1-D token autoencoder whose latent space the taichi recipes run in
-(``algorithm/vae=titok_kl_preprocessor``: 32 tokens of 4 channels per frame, latents ``[4, 1, 32]``).  Forward only, decoder only.
+"""TiTok-KL on the MI355X engine: the 1-D token autoencoder whose latent space the taichi recipes run in
+(``algorithm/vae=titok_kl_preprocessor``: 32 tokens of 4 channels per frame, latents ``[4, 1, 32]``).  Forward only; the decoder
+(``TiTokDecoder``) and the encoder (``TiTokEncoder``) are two modules over the one checkpoint.
 
 Mirrors:
+  * ``TiTok_KL.encode``                         algorithms/vae/tiktok_kl/titok_kl.py:78-98  (encoder, ``DiagonalGaussianDistribution``;
+    ``sample=True`` returns the mode)
+  * ``TiTokEncoder``                            algorithms/vae/tiktok_kl/blocks_kl.py:95-166  (the same ViT over
+    ``[cls | grid^2 patches | 32 latent tokens]``, ``ln_post`` of the latent rows, ``conv_out`` behind a ``reshape`` that reinterprets each
+    frame's ``32 x C`` block as ``C x 32`` without permuting: dfot_op_titok_moments computes exactly that)
+  * ``BaseVideoAlgo._encode``                   algorithms/common/base_pytorch_video_algo.py:553-596  (TiTok branch :592-593)
   * ``TiTok_KL.decode``                         algorithms/vae/tiktok_kl/titok_kl.py:100-109  (F.normalize, decoder, channel softmax,
     ``pixel_quantize_conv``, ``pixel_decoder``)
   * ``TiTokDecoder`` / ``ResidualAttentionBlock``   algorithms/vae/tiktok_kl/blocks_kl.py:39-88, 169-245  (a ViT over
@@ -34,6 +41,7 @@ from typing import Dict, List, Mapping, Optional, Tuple
 import torch
 
 from . import capi
+from .image_vae import ImageVAEPosterior
 from .vae import BF, _P, _S, _VideoVAEModule, _pad_to
 
 PRESETS = {"small": (512, 8, 8), "base": (768, 12, 12), "large": (1024, 24, 16)}     # width, layers, heads (head dim 64)
@@ -47,7 +55,67 @@ def max_sequence_length() -> int:
     return int(capi.lib.dfot_op_mha_packed_max_len())
 
 
-class TiTokDecoder(_VideoVAEModule):
+class _TiTokModule(_VideoVAEModule):
+    """What the two ViT halves of ``TiTok_KL`` share: the GEMM / LayerNorm / bias + activation calls and the loop over the
+    ``ResidualAttentionBlock``s.  Subclasses set ``width``, ``layers``, ``heads`` and ``seq`` and fill ``_packed`` in ``_sync``."""
+
+    def _par(self, name: str) -> torch.Tensor:
+        return self.get_parameter(name).detach()
+
+    def _gemm(self, a: torch.Tensor, wname: str, bias: Optional[torch.Tensor], resid: Optional[torch.Tensor], rows1: int) -> torch.Tensor:
+        """fp32 [M][N] = a bf16 [M][K] w^T (+ bias) (+ resid).  Whether K is split inside the workgroup (the one tile form with another
+        summation order, picked for few tiles and a long K) is decided from ONE frame's padded rows `rows1`, so a frame's bits do not
+        depend on the batch."""
+        w = self._packed[wname]
+        m, (n, k) = a.shape[0], w.shape
+        out = torch.empty(m, n, device=a.device)
+        if k >= 2048 and (_pad_to(rows1, 128) // 128) * (-(-n // 128)) <= 256:
+            d = capi.GemmDesc()
+            d.qscale, d.eps, d.ksplit, d.variant = 1.0, 1e-6, 1, _GEMM_KS2
+            d.A, d.lda, d.W, d.M, d.N, d.K = a.data_ptr(), k, w.data_ptr(), m, n, k
+            d.bias, d.resid = (bias.data_ptr() if bias is not None else None), (resid.data_ptr() if resid is not None else None)
+            d.out_f32, d.ldo = out.data_ptr(), n
+            capi.check(capi.lib.dfot_op_gemm_ex(C.byref(d), _S()))
+        else:   # here the shape-picked form never splits K: a frame's tile count only grows with the batch
+            capi.check(capi.lib.dfot_op_gemm_f32(_P(a), k, _P(w), _P(bias), _P(resid), _P(out), n, m, n, k, _S()))
+        return out
+
+    def _ln(self, x: torch.Tensor, name: str, rows: int, gather: Tuple[int, int, int] = (0, 0, 0), out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """LayerNorm(eps 1e-5) of the first `rows` rows -> bf16 GEMM operand (rows past `rows` of `out` stay as they are: zero)"""
+        if out is None:
+            out = torch.zeros(x.shape, dtype=BF, device=x.device)
+        capi.check(capi.lib.dfot_op_layernorm(_P(x), _P(self._par(name + ".weight")), _P(self._par(name + ".bias")), 1e-5, _P(out), None, rows,
+                                              self.width, *gather, _S()))
+        return out
+
+    def _bias_act(self, x: torch.Tensor, bias: torch.Tensor, act: int) -> torch.Tensor:
+        out = torch.empty(x.shape, dtype=BF, device=x.device)
+        capi.check(capi.lib.dfot_op_bias_act_bf16(_P(x), x.shape[1], _P(bias), _P(out), x.shape[0], x.shape[1], act, _S()))
+        return out
+
+    def _blocks(self, prefix: str, x: torch.Tensor, f: int) -> torch.Tensor:
+        """``layers`` x ResidualAttentionBlock ``{prefix}.{i}`` on the fp32 residual stream x [pad128(f * seq)][width] (pad rows zero) of f
+        sequences of ``seq`` rows back to back"""
+        w, L = self.width, self.seq
+        rows, rows1, mp, dev = f * L, L, x.shape[0], x.device
+        p = self._par
+        h = torch.zeros(mp, w, dtype=BF, device=dev)          # LayerNorm output: pad rows stay zero
+        o = torch.zeros(mp, w, dtype=BF, device=dev)          # attention output: rows >= F * L are never written
+        qkv = torch.empty(mp, 3 * w, dtype=BF, device=dev)
+        for i in range(self.layers):
+            r = f"{prefix}.{i}"
+            self._ln(x, r + ".ln_1", rows, out=h)
+            capi.check(capi.lib.dfot_op_gemm_bf16(_P(h), w, _P(self._packed[r + ".attn.in_proj_weight"]), _P(p(r + ".attn.in_proj_bias")), _P(qkv), 3 * w,
+                                                  mp, 3 * w, w, _S()))
+            capi.check(capi.lib.dfot_op_mha_packed(_P(qkv), 3 * w, _P(o), f, L, self.heads, _S()))
+            x = self._gemm(o, r + ".attn.out_proj.weight", p(r + ".attn.out_proj.bias"), x, rows1)
+            self._ln(x, r + ".ln_2", rows, out=h)
+            u = self._gemm(h, r + ".mlp.c_fc.weight", None, None, rows1)
+            x = self._gemm(self._bias_act(u, p(r + ".mlp.c_fc.bias"), _ACT_GELU), r + ".mlp.c_proj.weight", p(r + ".mlp.c_proj.bias"), x, rows1)
+        return x
+
+
+class TiTokDecoder(_TiTokModule):
     """The decoder half of the reference ``TiTok_KL`` with its constructor keywords; encoder-only keywords (``vit_enc_model_size``,
     ``vit_enc_patch_size``, ``use_checkpoint``, ...) are accepted and ignored.  Any frame count >= 1 decodes (see the module docstring)."""
 
@@ -135,41 +203,7 @@ class TiTokDecoder(_VideoVAEModule):
                     pk[name[:-6] + "bias"] = b
         self._packed, self._sig = pk, sig
 
-    def _par(self, name: str) -> torch.Tensor:
-        return self.get_parameter(name).detach()
-
     # ------------------------------------------------------------------ building blocks
-    def _gemm(self, a: torch.Tensor, wname: str, bias: Optional[torch.Tensor], resid: Optional[torch.Tensor], rows1: int) -> torch.Tensor:
-        """fp32 [M][N] = a bf16 [M][K] w^T (+ bias) (+ resid).  Whether K is split inside the workgroup (the one tile form with another
-        summation order, picked for few tiles and a long K) is decided from ONE frame's padded rows `rows1`, so a frame's bits do not
-        depend on the batch."""
-        w = self._packed[wname]
-        m, (n, k) = a.shape[0], w.shape
-        out = torch.empty(m, n, device=a.device)
-        if k >= 2048 and (_pad_to(rows1, 128) // 128) * (-(-n // 128)) <= 256:
-            d = capi.GemmDesc()
-            d.qscale, d.eps, d.ksplit, d.variant = 1.0, 1e-6, 1, _GEMM_KS2
-            d.A, d.lda, d.W, d.M, d.N, d.K = a.data_ptr(), k, w.data_ptr(), m, n, k
-            d.bias, d.resid = (bias.data_ptr() if bias is not None else None), (resid.data_ptr() if resid is not None else None)
-            d.out_f32, d.ldo = out.data_ptr(), n
-            capi.check(capi.lib.dfot_op_gemm_ex(C.byref(d), _S()))
-        else:   # here the shape-picked form never splits K: a frame's tile count only grows with the batch
-            capi.check(capi.lib.dfot_op_gemm_f32(_P(a), k, _P(w), _P(bias), _P(resid), _P(out), n, m, n, k, _S()))
-        return out
-
-    def _ln(self, x: torch.Tensor, name: str, rows: int, gather: Tuple[int, int, int] = (0, 0, 0), out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """LayerNorm(eps 1e-5) of the first `rows` rows -> bf16 GEMM operand (rows past `rows` of `out` stay as they are: zero)"""
-        if out is None:
-            out = torch.zeros(x.shape, dtype=BF, device=x.device)
-        capi.check(capi.lib.dfot_op_layernorm(_P(x), _P(self._par(name + ".weight")), _P(self._par(name + ".bias")), 1e-5, _P(out), None, rows,
-                                              self.width, *gather, _S()))
-        return out
-
-    def _bias_act(self, x: torch.Tensor, bias: torch.Tensor, act: int) -> torch.Tensor:
-        out = torch.empty(x.shape, dtype=BF, device=x.device)
-        capi.check(capi.lib.dfot_op_bias_act_bf16(_P(x), x.shape[1], _P(bias), _P(out), x.shape[0], x.shape[1], act, _S()))
-        return out
-
     def _check(self, z: torch.Tensor) -> torch.device:
         if z.ndim != 4 or tuple(z.shape[1:]) != (self.token_size, 1, self.nlat):
             raise ValueError(f"z has shape {tuple(z.shape)}, expected (F, {self.token_size}, 1, {self.nlat})")
@@ -191,8 +225,7 @@ class TiTokDecoder(_VideoVAEModule):
         dev = self._check(z)
         self._sync()
         f, w, L, g2 = z.shape[0], self.width, self.seq, self.grid ** 2
-        rows, rows1 = f * L, L
-        mp = _pad_to(rows, 128)
+        mp = _pad_to(f * L, 128)
         p = self._par
         x = torch.zeros(mp, w, device=dev)
         zf = z.detach().float().contiguous()                  # (a local: the op takes a raw pointer)
@@ -201,19 +234,7 @@ class TiTokDecoder(_VideoVAEModule):
             _P(p("decoder.latent_token_positional_embedding")), _P(p("decoder.class_embedding")), _P(p("decoder.mask_token")),
             _P(p("decoder.positional_embedding")), _P(p("decoder.ln_pre.weight")), _P(p("decoder.ln_pre.bias")), 1e-5, _P(x), f, g2, self.nlat,
             self.token_size, w, int(self.l2norm), _S()))
-        h = torch.zeros(mp, w, dtype=BF, device=dev)          # LayerNorm output: pad rows stay zero
-        o = torch.zeros(mp, w, dtype=BF, device=dev)          # attention output: rows >= F * L are never written
-        qkv = torch.empty(mp, 3 * w, dtype=BF, device=dev)
-        for i in range(self.layers):
-            r = f"decoder.transformer.{i}"
-            self._ln(x, r + ".ln_1", rows, out=h)
-            capi.check(capi.lib.dfot_op_gemm_bf16(_P(h), w, _P(self._packed[r + ".attn.in_proj_weight"]), _P(p(r + ".attn.in_proj_bias")), _P(qkv), 3 * w,
-                                                  mp, 3 * w, w, _S()))
-            capi.check(capi.lib.dfot_op_mha_packed(_P(qkv), 3 * w, _P(o), f, L, self.heads, _S()))
-            x = self._gemm(o, r + ".attn.out_proj.weight", p(r + ".attn.out_proj.bias"), x, rows1)
-            self._ln(x, r + ".ln_2", rows, out=h)
-            u = self._gemm(h, r + ".mlp.c_fc.weight", None, None, rows1)
-            x = self._gemm(self._bias_act(u, p(r + ".mlp.c_fc.bias"), _ACT_GELU), r + ".mlp.c_proj.weight", p(r + ".mlp.c_proj.bias"), x, rows1)
+        x = self._blocks("decoder.transformer", x, f)
         fp = self._frames_padded(f)
         y = torch.zeros(fp * g2, w, dtype=BF, device=dev)     # ln_post of rows 1 .. grid^2 of every sequence, compact
         self._ln(x, "decoder.ln_post", f * g2, gather=(L, 1, g2), out=y)
@@ -309,8 +330,132 @@ class TiTokDecoder(_VideoVAEModule):
         return super().load_reference_state_dict(dict(state_dict))
 
 
+class TiTokEncoder(_TiTokModule):
+    """The encoder half of the reference ``TiTok_KL`` (``encoder.*`` and ``latent_tokens``) with its constructor keywords; decoder-only
+    keywords (``use_l2_norm``, ``vit_dec_model_size``, ``vit_dec_patch_size``, ``use_checkpoint``, ...) are accepted and ignored.  Any frame
+    count >= 1 encodes, and a frame encodes to the same bits whatever batch it is part of (see the module docstring)."""
+
+    def __init__(self, image_size: int = 256, token_size: int = 4, vit_enc_model_size: str = "large", vit_enc_patch_size: int = 16,
+                 num_latent_tokens: int = 32, **decoder_only_keywords_ignored):
+        super().__init__()
+        if vit_enc_model_size not in PRESETS:
+            raise ValueError(f"vit_enc_model_size='{vit_enc_model_size}' is not one of {sorted(PRESETS)}")
+        if int(vit_enc_patch_size) != 16:
+            raise NotImplementedError(f"vit_enc_patch_size={vit_enc_patch_size} is not supported: the patch gather is written for 16 x 16 patches "
+                                      "(the recipes' size)")
+        if int(image_size) < 16 or int(image_size) % 16:
+            raise ValueError(f"image_size={image_size} must be a positive multiple of 16")
+        if not 1 <= int(token_size) <= 64:
+            raise ValueError(f"token_size={token_size} must be in [1, 64]: the moments hold 2 * token_size <= 128 channels")
+        if not 1 <= int(num_latent_tokens) <= 128:
+            raise ValueError(f"num_latent_tokens={num_latent_tokens} must be in [1, 128]")
+        self.image_size, self.token_size = int(image_size), int(token_size)
+        self.size, self.nlat = vit_enc_model_size, int(num_latent_tokens)
+        self.width, self.layers, self.heads = PRESETS[vit_enc_model_size]
+        self.grid = self.image_size // 16
+        self.seq = 1 + self.grid ** 2 + self.nlat
+        if self.seq > max_sequence_length():
+            raise ValueError(f"image_size={image_size} gives sequences of {self.seq} tokens; the attention kernel takes up to {max_sequence_length()}")
+        w = self.width
+        sp: List[Tuple[str, Tuple[int, ...]]] = [
+            ("latent_tokens", (self.nlat, w)),                 # a parameter of TiTok_KL itself: first in its state dict
+            ("encoder.class_embedding", (1, w)), ("encoder.positional_embedding", (self.grid ** 2 + 1, w)),
+            ("encoder.latent_token_positional_embedding", (self.nlat, w)),
+            ("encoder.patch_embed.weight", (w, 3, 16, 16)), ("encoder.patch_embed.bias", (w,)),
+            ("encoder.ln_pre.weight", (w,)), ("encoder.ln_pre.bias", (w,))]
+        for i in range(self.layers):
+            r = f"encoder.transformer.{i}"
+            sp += [(f"{r}.ln_1.weight", (w,)), (f"{r}.ln_1.bias", (w,)), (f"{r}.attn.in_proj_weight", (3 * w, w)), (f"{r}.attn.in_proj_bias", (3 * w,)),
+                   (f"{r}.attn.out_proj.weight", (w, w)), (f"{r}.attn.out_proj.bias", (w,)), (f"{r}.ln_2.weight", (w,)), (f"{r}.ln_2.bias", (w,)),
+                   (f"{r}.mlp.c_fc.weight", (4 * w, w)), (f"{r}.mlp.c_fc.bias", (4 * w,)), (f"{r}.mlp.c_proj.weight", (w, 4 * w)),
+                   (f"{r}.mlp.c_proj.bias", (w,))]
+        sp += [("encoder.ln_post.weight", (w,)), ("encoder.ln_post.bias", (w,)),
+               ("encoder.conv_out.weight", (2 * self.token_size, w, 1, 1)), ("encoder.conv_out.bias", (2 * self.token_size,))]
+        self._specs = sp
+        self._register()
+
+    def _sync(self) -> None:
+        """the Linear weights and ``patch_embed.weight`` (flattened (C, 3 * 16 * 16): the column order dfot_op_titok_patch_rows writes) packed
+        to bf16 GEMM operands, once per weight change; ``conv_out.weight``, biases, norm weights and the embeddings are read in fp32"""
+        params = dict(self.named_parameters())
+        sig = tuple((t.data_ptr(), t._version) for t in params.values())
+        if sig == self._sig:
+            return
+        pk: Dict[str, torch.Tensor] = {}
+        for name, t in params.items():
+            if not t.is_cuda:
+                raise RuntimeError(f"parameter {name} is on {t.device}; move the module to the GPU first (there is no CPU path)")
+            if name == "encoder.patch_embed.weight" or (name.endswith("weight") and t.ndim == 2):
+                pk[name] = t.detach().float().reshape(t.shape[0], -1).to(BF).contiguous()
+        self._packed, self._sig = pk, sig
+
+    def _check(self, x: torch.Tensor) -> torch.device:
+        s = self.image_size
+        if x.ndim != 4 or tuple(x.shape[1:]) != (3, s, s):
+            raise ValueError(f"x has shape {tuple(x.shape)}, expected (F, 3, {s}, {s})")
+        if x.shape[0] < 1:
+            raise ValueError("x holds no frame")
+        if not x.is_cuda:
+            raise ValueError(f"frames are on {x.device}: the encoder runs on the GPU only (there is no CPU path)")
+        dev = next(self.parameters()).device
+        capi.require_device(dev, x=x)
+        return dev
+
+    def _moments(self, x: torch.Tensor) -> torch.Tensor:
+        """``TiTokEncoder.forward`` (blocks_kl.py:140-166): frames (F, 3, S, S) -> moments fp32 [F][num_latent][2 * token_size]"""
+        dev = self._check(x)
+        self._sync()
+        f, w, L, g2, oc = x.shape[0], self.width, self.seq, self.grid ** 2, 2 * self.token_size
+        p = self._par
+        xf = x.detach().float().contiguous()                  # (a local: the op takes a raw pointer)
+        a = torch.zeros(_pad_to(f * g2, 128), 768, dtype=BF, device=dev)     # pad rows stay zero
+        capi.check(capi.lib.dfot_op_titok_patch_rows(_P(xf), _P(a), f, self.image_size, _S()))
+        patches = self._gemm(a, "encoder.patch_embed.weight", p("encoder.patch_embed.bias"), None, g2)   # K = 768: never split
+        tok = torch.zeros(_pad_to(f * L, 128), w, device=dev)
+        capi.check(capi.lib.dfot_op_titok_enc_tokens(
+            _P(patches), w, _P(p("encoder.class_embedding")), _P(p("encoder.positional_embedding")), _P(p("latent_tokens")),
+            _P(p("encoder.latent_token_positional_embedding")), _P(p("encoder.ln_pre.weight")), _P(p("encoder.ln_pre.bias")), 1e-5, _P(tok), f, g2,
+            self.nlat, w, _S()))
+        tok = self._blocks("encoder.transformer", tok, f)
+        t = torch.empty(f * self.nlat, w, device=dev)         # ln_post of the last num_latent rows of every sequence, compact, fp32
+        capi.check(capi.lib.dfot_op_layernorm(_P(tok), _P(p("encoder.ln_post.weight")), _P(p("encoder.ln_post.bias")), 1e-5, None, _P(t), f * self.nlat, w,
+                                              L, 1 + g2, self.nlat, _S()))
+        mom = torch.empty(f, self.nlat, oc, device=dev)
+        capi.check(capi.lib.dfot_op_titok_moments(_P(t), _P(p("encoder.conv_out.weight")), _P(p("encoder.conv_out.bias")), _P(mom), oc, f, self.nlat, w,
+                                                  oc, _S()))
+        return mom
+
+    # ------------------------------------------------------------------ public entry points
+    @torch.no_grad()
+    def encode_moments(self, x: torch.Tensor) -> torch.Tensor:
+        """``TiTokEncoder.forward``: frames (F, 3, S, S) -> moments (F, 2 * token_size, 1, num_latent_tokens), mean | logvar (not clamped)"""
+        return self._moments(x).permute(0, 2, 1).unsqueeze(2).contiguous()
+
+    @torch.no_grad()
+    def encode(self, x: torch.Tensor, sample: bool = False, sample_posterior: bool = False, noise: Optional[torch.Tensor] = None,
+               generator: Optional[torch.Generator] = None):
+        """``TiTok_KL.encode`` (titok_kl.py:78-98): the posterior of the frames (F, 3, S, S) (``mean`` / ``logvar`` / ``std`` of shape
+        (F, token_size, 1, num_latent_tokens), ``parameters``, ``mode()``, ``sample(noise, generator)``); with ``sample`` its mode, or with
+        ``sample_posterior`` too ``mean + std * noise`` (noise given, or drawn from ``generator``).  No L2 normalisation: ``decode`` does it."""
+        post = ImageVAEPosterior(self._moments(x).unsqueeze(1), self.token_size)       # [F][1][num_latent][2 ts]: h = 1, w = num_latent
+        if not sample:
+            return post
+        return post.sample(noise, generator) if sample_posterior else post.mode()
+
+    def load_reference_state_dict(self, state_dict: Mapping[str, torch.Tensor]) -> List[str]:
+        """keys of a reference ``TiTok_KL`` (optionally ``vae.``-prefixed): the encoder's own keys (``encoder.*``, ``latent_tokens``) are
+        loaded strictly (every one present, with its shape); the decoder's (``decoder.*``, ``pixel_quantize_conv.*``, ``pixel_decoder.*``)
+        are ignored and returned.  Any other key raises ``ValueError``."""
+        own = set(self._names)
+        for k in state_dict:
+            n = k[4:] if k.startswith("vae.") else k
+            if n not in own and not n.startswith(("decoder.", "pixel_quantize_conv.", "pixel_decoder.")):
+                raise ValueError(f"unexpected key in a TiTok_KL state dict: {k}")
+        return super().load_reference_state_dict(dict(state_dict))
+
+
 def load_titok_checkpoint(path: str) -> Dict[str, torch.Tensor]:
-    """The recipe's ``model.safetensors`` (a ``TiTok_KL`` state dict) from disk:
+    """The recipe's ``model.safetensors`` (a ``TiTok_KL`` state dict) from disk, for either half:
 
         vae = TiTokDecoder(image_size=256, token_size=4).cuda(); vae.load_reference_state_dict(load_titok_checkpoint("model.safetensors"))"""
     from safetensors.torch import load_file
@@ -331,4 +476,22 @@ def decode_titok_latents(vae: TiTokDecoder, latents: torch.Tensor, vae_batch_siz
         b, t = ch.shape[:2]
         y = vae.decode(ch.reshape(b * t, *ch.shape[2:]))
         outs.append(y.reshape(b, t, *y.shape[1:]))
+    return torch.cat(outs, 0)
+
+
+@torch.no_grad()
+def encode_titok_frames(vae: TiTokEncoder, videos: torch.Tensor, vae_batch_size: int = 2, shape: str = "b t c h w") -> torch.Tensor:
+    """``BaseVideoAlgo._encode`` for a TiTok_KL (base_pytorch_video_algo.py:553-596, TiTok branch :592-593, and
+    ``Titok_KLPreprocessor._encode_videos``, tiktok_kl/preprocessor.py:124-132): videos ``(B, T, 3, S, S)``, chunks of ``vae.batch_size``
+    videos whose frames go to the batch, ``encode(y, sample=True)`` -- the posterior's mode -- as it is (no rescaling), result
+    ``(B, T, token_size, 1, num_latent_tokens)``.  Frames are independent, so the chunking does not change a bit of the result."""
+    if shape != "b t c h w":
+        raise ValueError("only the 'b t c h w' layout of the sampling path is supported")
+    if videos.ndim != 5:
+        raise ValueError(f"videos have shape {tuple(videos.shape)}, expected (B, T, 3, S, S)")
+    outs = []
+    for ch in torch.chunk(videos, (videos.shape[0] + vae_batch_size - 1) // vae_batch_size, 0):
+        b, t = ch.shape[:2]
+        z = vae.encode(ch.reshape(b * t, *ch.shape[2:]), sample=True)
+        outs.append(z.reshape(b, t, *z.shape[1:]))
     return torch.cat(outs, 0)

@@ -15,6 +15,8 @@
                                                      dim 4 with mask_first, continuous diffusion; --decode-image-vae decodes the 8x8 latents)
   python examples/sample.py taichi --decode-titok [--titok-ckpt model.safetensors]   (DiT-XL on the 1-D token latents 4x1x32 of the taichi
                                                      recipe, patch 1, 16 frames; TiTok-KL decoder: 32 tokens -> a 256x256 frame)
+  python examples/sample.py taichi --encode-titok [--decode-titok] [--titok-ckpt model.safetensors]   (the context latents of the run are
+                                                     256x256 context frames encoded by the TiTok-KL encoder: frames -> latents -> latents -> frames)
 
 Without --ckpt the backbone gets seeded random weights (there is no network here to fetch the released checkpoints);
 with it, the reference's .ckpt / ema.safetensors is read by dfot_amd.load_reference_checkpoint (keys
@@ -58,8 +60,12 @@ def main():
     ap.add_argument("--decode-titok", action="store_true",
                     help="taichi: decode the sampled 4x1x32 token latents with the TiTok-KL decoder (the `large` preset at 256x256, as "
                          "titok_kl_preprocessor; random weights unless --titok-ckpt is given)")
+    ap.add_argument("--encode-titok", action="store_true",
+                    help="taichi: encode synthetic 256x256 context frames with the TiTok-KL encoder (the `large` preset, as titok_kl_preprocessor; "
+                         "random weights unless --titok-ckpt is given) into the context latents of the run")
     ap.add_argument("--titok-ckpt", metavar="model.safetensors",
-                    help="with --decode-titok: the recipe's TiTok_KL checkpoint, read by dfot_amd.load_titok_checkpoint")
+                    help="with --decode-titok / --encode-titok: the recipe's TiTok_KL checkpoint, read by dfot_amd.load_titok_checkpoint (one file "
+                         "feeds both halves)")
     ap.add_argument("--attention-maps", metavar="OUT.npz",
                     help="k600 / facdit / facmat: write the frame-to-frame attention maps of every frame-mixing block (per head, query frame x key "
                          "frame; rows follow the model batch) at the steps of --attention-steps, as '<step>/<block name>' and '<step>/noise_levels'")
@@ -67,8 +73,8 @@ def main():
     a = ap.parse_args()
     if a.attention_maps and a.model not in ("k600", "facdit", "facmat"):
         raise SystemExit("--attention-maps: the DiT3D models k600, facdit and facmat only")
-    if a.decode_titok and a.model != "taichi":
-        raise SystemExit("--decode-titok: the taichi model only (latents of 4x1x32 tokens)")
+    if (a.decode_titok or a.encode_titok) and a.model != "taichi":
+        raise SystemExit("--decode-titok / --encode-titok: the taichi model only (latents of 4x1x32 tokens)")
     gen = torch.Generator(device="cuda").manual_seed(a.seed)
     noise = dfot_amd.device_noise_fn(gen)
     conds = None
@@ -161,6 +167,22 @@ def main():
             conds = conds.float() if conds.is_floating_point() else conds.long()
     xs = xs.cuda()
     conds = None if conds is None else conds.cuda()
+    titok_sd = dfot_amd.load_titok_checkpoint(a.titok_ckpt) if a.titok_ckpt else None
+    if a.encode_titok:  # `_encode` of the reference: context frames (B, n_ctx, 3, 256, 256) in [0, 1] -> the posterior's mode, not rescaled
+        enc = dfot_amd.TiTokEncoder(image_size=256, token_size=xs.shape[2], vit_enc_model_size="large", num_latent_tokens=xs.shape[4]).cuda()
+        if titok_sd is not None:
+            ignored = enc.load_reference_state_dict(titok_sd)
+            print(f"loaded {a.titok_ckpt} ({len(ignored)} decoder keys ignored)")
+        else:
+            enc.init_random(seed=a.seed + 1)
+        ctx = torch.rand(xs.shape[0], n_ctx, 3, 256, 256, generator=torch.Generator().manual_seed(300 + a.seed)).cuda()
+        dfot_amd.encode_titok_frames(enc, ctx[:1, :1], vae_batch_size=1)   # packs the weights, loads the kernels
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        xs[:, :n_ctx] = dfot_amd.encode_titok_frames(enc, ctx, vae_batch_size=2)
+        torch.cuda.synchronize()
+        print(f"TiTok encode ({a.titok_ckpt or 'random weights'}): {tuple(ctx.shape)} -> {tuple(xs[:, :n_ctx].shape)} in "
+              f"{(time.perf_counter() - t0) * 1e3:.1f} ms")
     model.eval()  # (train() would draw the per-video dropout of a condition embedding)
     if a.attention_maps:
         steps = a.attention_steps if a.attention_steps else sorted({0, a.steps // 2, a.steps - 1})
@@ -196,8 +218,8 @@ def main():
         print(f"ImageVAE decode ({a.image_vae_ckpt or 'random weights'}): {tuple(out.shape)} -> {tuple(frames.shape)} in {(time.perf_counter() - t0) * 1e3:.1f} ms")
     if a.decode_titok:
         vae = dfot_amd.TiTokDecoder(image_size=256, token_size=out.shape[2], vit_dec_model_size="large", num_latent_tokens=out.shape[4]).cuda()
-        if a.titok_ckpt:
-            ignored = vae.load_reference_state_dict(dfot_amd.load_titok_checkpoint(a.titok_ckpt))
+        if titok_sd is not None:
+            ignored = vae.load_reference_state_dict(titok_sd)
             print(f"loaded {a.titok_ckpt} ({len(ignored)} encoder keys ignored)")
         else:
             vae.init_random(seed=a.seed)

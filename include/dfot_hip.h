@@ -754,6 +754,29 @@ int dfot_op_titok_tokens(const float* z, const float* embed_w, const float* embe
                          const float* pos, const float* gamma, const float* beta, float eps, float* out, int frames, int grid2, int num_latent,
                          int token_size, int channels, int l2norm, void* stream);
 
+/* ---- TiTok-KL encoder pieces (blocks_kl.py:95-166; the ResidualAttentionBlocks, ln_post and the posterior are the ops above). ---------- */
+/* The A operand of the patch-embedding GEMM (Conv2d(3, C, k 16, s 16)): rows bf16 [nframes * g^2][768], g = image_size / 16, from frames
+ * fp32 (nframes, 3, image_size, image_size) contiguous:
+ *   rows[f * g^2 + py * g + px][c * 256 + dy * 16 + dx] = bf16(frames[f][c][16 py + dy][16 px + dx])   (round to nearest even)
+ * the flattening order of patch_embed.weight (C, 3, 16, 16).  Rows past nframes * g^2 are not written.  image_size a positive multiple of
+ * 16; anything else: DFOT_ERR_SHAPE before any device work. */
+int dfot_op_titok_patch_rows(const float* frames, void* rows_bf16, int nframes, int image_size, void* stream);
+/* The encoder's token sequence in one launch (blocks_kl.py:140-154): out fp32 [frames * (1 + grid2 + num_latent)][channels] = ln_pre of
+ * [cls + pos[0] | patches[f * grid2 + p] + pos[1 + p] | latent_tokens[t] + latent_pos[t]]; patches fp32 [frames * grid2][ldp] is the
+ * patch-embedding GEMM's output with its bias (ldp >= channels, a multiple of 4).  channels in {512, 768, 1024}; fp32 statistics. */
+int dfot_op_titok_enc_tokens(const float* patches, int64_t ldp, const float* cls, const float* pos, const float* latent_tokens, const float* latent_pos,
+                             const float* gamma, const float* beta, float eps, float* out, int frames, int grid2, int num_latent, int channels,
+                             void* stream);
+/* conv_out (1x1, channels -> out_channels) on the reference's `reshape(batch, width, num_latent, 1)` of the contiguous ln_post rows
+ * t fp32 [frames][num_latent][channels] (blocks_kl.py:163-165).  The reshape does not permute: it reads each frame's num_latent x channels
+ * block as channels x num_latent, so
+ *   out[f][n][o] = bias[o] + sum_c w[o][c] * t_f[c * num_latent + n]        (t_f the frame's block, flat)
+ * w fp32 [out_channels][channels], out fp32 [frames][num_latent][ldo] (ldo >= out_channels): the moments layout dfot_op_vae_posterior
+ * reads (batch = frames, frames = 1, hw = num_latent, zc = out_channels / 2).  All math fp32, one summation order per (num_latent, channels).
+ * channels in {512, 768, 1024}, num_latent <= 128, out_channels even and <= 128; anything else: DFOT_ERR_SHAPE before any device work. */
+int dfot_op_titok_moments(const float* t, const float* w, const float* bias, float* out, int64_t ldo, int frames, int num_latent, int channels,
+                          int out_channels, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Micro-benchmarks of the C-ABI primitives at the RE10K model shapes (model batch 2), HIP-event timed.
-Usage (GPU box): python tools/bench_ops.py [gemm] [conv] [attn] [tattn] [mattn] [tattn_bwd] [facdit_train] [mattn_bwd] [facmat_train] [vae_encode] [equal] [dit_front] [ivae] [uvit3d] [gnfilm_frame] [uvit3d_train] [attnmap] [titok] [mcraft]"""
+Usage (GPU box): python tools/bench_ops.py [gemm] [conv] [attn] [tattn] [mattn] [tattn_bwd] [facdit_train] [mattn_bwd] [facmat_train] [vae_encode] [equal] [dit_front] [ivae] [uvit3d] [gnfilm_frame] [uvit3d_train] [attnmap] [titok] [titok_enc] [mcraft]"""
 import ctypes as C
 import math
 import os
@@ -526,10 +526,45 @@ def titok():
               f"{ms_t:.3f} ms", flush=True)
 
 
+def titok_enc():
+    """the TiTok-KL encoder of the taichi recipes: 16 frames at 256 x 256 through the `large` encoder (and the `small` one) -- the yardstick
+    is the transformer share `titok` prints for the decoder, the same 24 blocks over the same 16 x 289 tokens -- and its three own launches
+    alone at that shape.  Each figure: the median of 7 repeats of (warm-up + timed launches between two HIP events)."""
+    import statistics
+    med = lambda fn, **kw: statistics.median(timeit(fn, **kw) for _ in range(7))
+    f, s, c, nlat, oc = 16, 256, 1024, 32, 8
+    g2 = (s // 16) ** 2
+    x = torch.rand(f, 3, s, s, device="cuda")
+    rows = torch.zeros(f * g2, 768, dtype=torch.bfloat16, device="cuda")
+    us = med(lambda: capi.check(capi.lib.dfot_op_titok_patch_rows(P(x), P(rows), f, s, S()))) * 1e3
+    print(f"titok_enc patch_rows {f} frames {s}x{s} -> [{f * g2}][768] bf16: {us:8.1f} us ({(x.numel() * 4 + rows.numel() * 2) / us / 1e6:6.2f} TB/s)",
+          flush=True)
+    patches = torch.randn(f * g2, c, device="cuda")
+    cls, pos, lat, lpos = (torch.randn(n, c, device="cuda") for n in (1, g2 + 1, nlat, nlat))
+    gamma, beta = torch.ones(c, device="cuda"), torch.zeros(c, device="cuda")
+    tok = torch.zeros(-(-f * (1 + g2 + nlat) // 128) * 128, c, device="cuda")
+    us = med(lambda: capi.check(capi.lib.dfot_op_titok_enc_tokens(P(patches), c, P(cls), P(pos), P(lat), P(lpos), P(gamma), P(beta), 1e-5, P(tok), f, g2,
+                                                                   nlat, c, S()))) * 1e3
+    print(f"titok_enc enc_tokens {f} x {1 + g2 + nlat} rows of {c}: {us:8.1f} us ({(patches.numel() + f * (1 + g2 + nlat) * c) * 4 / us / 1e6:6.2f} TB/s)",
+          flush=True)
+    t, w, bias = torch.randn(f, nlat, c, device="cuda"), torch.randn(oc, c, device="cuda") / 32, torch.zeros(oc, device="cuda")
+    mom = torch.empty(f, nlat, oc, device="cuda")
+    us = med(lambda: capi.check(capi.lib.dfot_op_titok_moments(P(t), P(w), P(bias), P(mom), oc, f, nlat, c, oc, S()))) * 1e3
+    print(f"titok_enc moments {f} frames [{nlat}][{c}] -> [{nlat}][{oc}]: {us:8.1f} us", flush=True)
+    for size in ("large", "small"):
+        enc = dfot_amd.TiTokEncoder(image_size=s, token_size=4, vit_enc_model_size=size).cuda()
+        enc.init_random(0)
+        ms = med(lambda: enc.encode_moments(x), iters=5, warm=1)
+        ms_z = med(lambda: enc.encode(x, sample=True), iters=5, warm=1)
+        print(f"titok_enc encode {f} frames 3x{s}x{s} -> moments 8x1x32 ({size}): {ms:.3f} ms; encode(x, sample=True) -> 4x1x32: {ms_z:.3f} ms", flush=True)
+
+
 def main():
     what = sys.argv[1:] or ["gemm", "conv", "attn"]
     if "titok" in what:
         titok()
+    if "titok_enc" in what:
+        titok_enc()
     if "attnmap" in what:
         attnmap()
     if "mcraft" in what:
