@@ -126,7 +126,8 @@ int launch_attention_temporal(const bf16* q, const bf16* k, const bf16* v, bf16*
   DFOT_REQUIRE(batch > 0 && heads > 0 && batch <= 65535 && heads <= 65535, DFOT_ERR_SHAPE, "temporal attention: batch %d, heads %d", batch, heads);
   DFOT_REQUIRE(tokens >= 1 && tokens <= 32, DFOT_ERR_SHAPE, "temporal attention: %d frames (1 to 32 are supported)", tokens);
   DFOT_REQUIRE(d > 0 && d % 4 == 0 && d <= 128, DFOT_ERR_SHAPE, "temporal attention: head dim %d must be a multiple of 4, <= 128", d);
-  DFOT_REQUIRE(patches > 0 && patches % 128 == 0, DFOT_ERR_SHAPE, "temporal attention: %d patches per frame must be a multiple of 128", patches);
+  // (the grid is patches / pb with pb a power of two <= 32)
+  DFOT_REQUIRE(patches > 0 && patches % 64 == 0, DFOT_ERR_SHAPE, "temporal attention: %d patches per frame must be a multiple of 64", patches);
   const int ch = d % 8 == 0 ? 8 : 4;
   DFOT_REQUIRE(ldo >= (long)heads * d && ldo % ch == 0, DFOT_ERR_SHAPE, "temporal attention: ldo %ld must cover %d columns and be a multiple of %d",
                ldo, heads * d, ch);
@@ -167,6 +168,8 @@ int launch_attention_temporal(const bf16* q, const bf16* k, const bf16* v, bf16*
 extern "C" int dfot_op_attention_temporal(const void* q, const void* k, const void* v, void* o, int ldo, int batch, int tokens, int patches,
                                           int heads, int d, void* stream) {
   using namespace dfot;
+  // the op keeps its documented contract (dfot_hip.h); the launcher itself also takes the engine's 64-patch frames
+  DFOT_REQUIRE(patches > 0 && patches % 128 == 0, DFOT_ERR_SHAPE, "temporal attention: %d patches per frame must be a multiple of 128", patches);
   return launch_attention_temporal((const bf16*)q, (const bf16*)k, (const bf16*)v, (bf16*)o, ldo, batch, tokens, patches, heads, d,
                                    (hipStream_t)stream);
 }

@@ -1034,14 +1034,22 @@ static int dit_create_impl(const DitCfg& c, dfot_dit_t* out) {
                "3 = dit3d factorized matrix)", c.variant);
   if (c.variant == 2) {
     const int P = (c.height / c.patch_size) * (c.width / c.patch_size);
-    DFOT_REQUIRE(P % 128 == 0, DFOT_ERR_SHAPE, "factorized attention variant: %d patches per frame must be a multiple of 128", P);
+    DFOT_REQUIRE(P % 128 == 0 || P == 64, DFOT_ERR_SHAPE, "factorized attention variant: %d patches per frame must be a multiple of 128, or 64", P);
+    DFOT_REQUIRE(P != 64 || c.max_tokens % 2 == 0, DFOT_ERR_SHAPE,
+                 "factorized attention variant: max_tokens %d x 64 patches per frame = %d rows per window; the row tiles need a multiple of 128",
+                 c.max_tokens, c.max_tokens * 64);
     DFOT_REQUIRE(c.max_tokens <= 32, DFOT_ERR_SHAPE, "factorized attention variant: max_tokens %d exceeds 32", c.max_tokens);
     DFOT_REQUIRE(c.temporal_mlp_hidden >= 0 && c.temporal_mlp_hidden % 64 == 0, DFOT_ERR_SHAPE, "temporal_mlp_hidden %d must be a multiple of 64",
                  c.temporal_mlp_hidden);
   }
   if (c.variant == 1 || c.variant == 3) {  // the models with matrix blocks
     const int P = (c.height / c.patch_size) * (c.width / c.patch_size);
-    DFOT_REQUIRE(P % 128 == 0, DFOT_ERR_SHAPE, "factorized matrix variant: %d patches per frame must be a multiple of 128", P);
+    // 64 patches (attention_seq64.hip runs the per-frame attention): DiT3D's variant 3 only; the difference model keeps its rule
+    DFOT_REQUIRE(P % 128 == 0 || (P == 64 && c.variant == 3), DFOT_ERR_SHAPE,
+                 "factorized matrix variant: %d patches per frame must be a multiple of 128%s", P, c.variant == 3 ? ", or 64" : "");
+    DFOT_REQUIRE(P != 64 || c.max_tokens % 2 == 0, DFOT_ERR_SHAPE,
+                 "factorized matrix variant: max_tokens %d x 64 patches per frame = %d rows per window; the row tiles need a multiple of 128",
+                 c.max_tokens, c.max_tokens * 64);
     DFOT_REQUIRE(c.embed_col_dim > 0 && c.embed_col_dim % 64 == 0, DFOT_ERR_SHAPE, "embed_col_dim %d must be a multiple of 64", c.embed_col_dim);
     DFOT_REQUIRE(c.num_col_heads > 0 && c.embed_col_dim % c.num_col_heads == 0 && c.num_row_heads > 0 &&
                      c.hidden_size % c.num_row_heads == 0 && (c.hidden_size / c.num_row_heads) % 4 == 0,
@@ -1360,6 +1368,8 @@ static int dit_forward_impl(dfot_dit_t h, const float* x, const int32_t* noise_l
     if (timed) DFOT_CHECK_HIP(hipEventRecord(h->ev_start[h->ev_used], s));
     if (temporal)
       r2 = launch_attention_temporal(h->q, h->k, h->v, h->A, hd, batch, tokens, P, c.num_heads, h->d, s);
+    else if (seq == 64)  // 64 patches per frame (variants 2 and 3): sequences shorter than launch_attention_padded's 128-row tile
+      r2 = launch_attention_seq64(h->q, h->k, h->v, h->A, hd, nseq, c.num_heads, h->d, s);
     else
       r2 = launch_attention_padded(h->q, h->k, h->v, h->A, hd, nseq, c.num_heads, seq, h->d, s);
     if (r2) return r2;

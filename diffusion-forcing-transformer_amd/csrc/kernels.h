@@ -138,8 +138,11 @@ int attention_dstride(int d);
 // lse (optional, training): [B][heads][N] fp32, log2-domain log-sum-exp of every query row
 int launch_attention_padded(const bf16* q, const bf16* k, const bf16* v, bf16* o, long ldo, int batch, int heads, int n, int d,
                             hipStream_t stream, float* lse = nullptr);
+// attention_seq64.hip: launch_attention_padded's operands and output with n = 64 (sequences shorter than that launcher's 128-row tile):
+// one workgroup per (sequence, head), single-pass softmax.  d % 8 == 0, d <= 128, ldo % 8 == 0
+int launch_attention_seq64(const bf16* q, const bf16* k, const bf16* v, bf16* o, long ldo, int nseq, int heads, int d, hipStream_t stream);
 // attention_temporal.hip: q, k, v [batch*tokens][heads][patches][dstride]; every (video, head, patch position) attends over its `tokens`
-// frames (1 .. 32); o [(video, frame, patch)][ldo] compact.  patches % 128 == 0, d % 4 == 0
+// frames (1 .. 32); o [(video, frame, patch)][ldo] compact.  patches % 64 == 0, d % 4 == 0
 int launch_attention_temporal(const bf16* q, const bf16* k, const bf16* v, bf16* o, long ldo, int batch, int tokens, int patches, int heads,
                               int d, hipStream_t s);
 // attention_temporal_bwd.hip: backward of launch_attention_temporal, the T x T problem recomputed (no lse, no delta); d_o compact

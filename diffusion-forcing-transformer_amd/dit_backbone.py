@@ -70,7 +70,28 @@ def condition_tensors(c: "capi.DiTConfig", external_cond: torch.Tensor, batch: i
     return None, lab.to(torch.int32).contiguous()
 
 
-def configure_facmat(c: "capi.DiTConfig", cfg, max_tokens: int) -> None:
+def _check_patches(variant: str, c: "capi.DiTConfig", max_tokens: int, allow_p64: bool, what: str) -> None:
+    """the patch-count rule of the two factorized variants: a multiple of 128 per frame, or (inference only: allow_p64) exactly 64 with an
+    even max_tokens, so that a full window is a whole number of 128-row tiles (csrc/attention_seq64.hip runs the 64-token frames).  The
+    trainers (allow_p64 False) refuse 64 patches in the words they always had; at an odd max_tokens the inference class refuses in the
+    same words plus the rule it broke, and so do the trainers: one message for one configuration."""
+    patches = (c.height // c.patch_size) * (c.width // c.patch_size)
+    if patches == 64 and allow_p64 and max_tokens % 2 == 0:
+        return
+    if patches % 128 != 0:
+        msg = (f"variant '{variant}': x_shape {(c.in_channels, c.height, c.width)} with patch_size {c.patch_size} gives {patches} patches per "
+               f"frame; the {what} need a multiple of 128 ")
+        if patches == 64 and max_tokens % 2:
+            msg += (f"(the 64-patch recipes are not supported) in training; inference takes 64 patches with an even max_tokens only: max_tokens "
+                    f"{max_tokens} × 64 patches per frame = {max_tokens * 64} rows per window; the row tiles need a multiple of 128")
+        elif allow_p64:
+            msg += "(or exactly 64 with an even max_tokens)"
+        else:
+            msg += "(the 64-patch recipes are not supported)"
+        raise ValueError(msg)
+
+
+def configure_facmat(c: "capi.DiTConfig", cfg, max_tokens: int, allow_p64: bool = False) -> None:
     """dit3d_factorized_matrix.yaml (+ the @FacMatDiT shortcuts) -> engine variant 3: per depth a per-frame spatial DiTBlock (num_heads,
     spatial_mlp_ratio) and a MatrixDiTBlock (embed_col_dim x embed_row_dim, num_col_heads x num_row_heads, mlp_ratio, use_bias) whose
     attention rotates q and k with a RoPE-1D over the frame axis when use_temporal_rope is set (dit_base.py:197-226, 297-306;
@@ -89,10 +110,7 @@ def configure_facmat(c: "capi.DiTConfig", cfg, max_tokens: int) -> None:
         raise AssertionError("spatial_mlp_ratio must be specified for matrix attention")
     if _get(cfg, "use_bias", None) is None:
         raise AssertionError("use_bias must be specified for matrix attention")
-    patches = (c.height // c.patch_size) * (c.width // c.patch_size)
-    if patches % 128 != 0:
-        raise ValueError(f"variant 'factorized_matrix_attention': x_shape {(c.in_channels, c.height, c.width)} with patch_size {c.patch_size} gives "
-                         f"{patches} patches per frame; the per-frame kernels need a multiple of 128 (the 64-patch recipes are not supported)")
+    _check_patches("factorized_matrix_attention", c, max_tokens, allow_p64, "per-frame kernels")
     if max_tokens > 32:
         raise ValueError(f"variant 'factorized_matrix_attention': max_tokens {max_tokens} exceeds the matrix attention kernel's 32 frames")
     c.hidden_size = int(_get(cfg, "embed_row_dim"))
@@ -107,7 +125,7 @@ def configure_facmat(c: "capi.DiTConfig", cfg, max_tokens: int) -> None:
     c.use_temporal_rope = int(rope)
 
 
-def configure_fac(c: "capi.DiTConfig", cfg, max_tokens: int) -> None:
+def configure_fac(c: "capi.DiTConfig", cfg, max_tokens: int, allow_p64: bool = False) -> None:
     """dit3d_factorized_attention.yaml (+ the @FacDiT shortcuts) -> engine variant 2: per depth a per-frame spatial DiTBlock
     (spatial_mlp_ratio) and a temporal DiTBlock (mlp_ratio) over the frames of every patch position (dit_base.py:197-226, 364-417).
     c.patch_size / height / width are already set.  Shared by DiT3D and trainer.FacDiTTrainer."""
@@ -117,11 +135,7 @@ def configure_fac(c: "capi.DiTConfig", cfg, max_tokens: int) -> None:
     c.mlp_hidden = int(c.hidden_size * ratio) if ratio else 0
     c.variant = 2
     c.temporal_mlp_hidden = int(c.hidden_size * tratio) if tratio else 0
-    patches = (c.height // c.patch_size) * (c.width // c.patch_size)
-    if patches % 128 != 0:
-        raise ValueError(f"variant 'factorized_attention': x_shape {(c.in_channels, c.height, c.width)} with patch_size {c.patch_size} gives "
-                         f"{patches} patches per frame; the per-frame attention kernels need a multiple of 128 (the 64-patch recipes are not "
-                         "supported)")
+    _check_patches("factorized_attention", c, max_tokens, allow_p64, "per-frame attention kernels")
     if max_tokens > 32:
         raise ValueError(f"variant 'factorized_attention': max_tokens {max_tokens} exceeds the temporal attention kernel's 32 frames")
 
@@ -216,10 +230,10 @@ class DiT3D(nn.Module):
             raise ValueError(f"unsupported pos_emb_type {pos!r} for variant {variant!r}: {supported}")
         ratio = _get(cfg, "spatial_mlp_ratio", None)
         if variant == "factorized_matrix_attention":
-            configure_facmat(c, cfg, max_tokens)
+            configure_facmat(c, cfg, max_tokens, allow_p64=True)
             return
         if variant == "factorized_attention":
-            configure_fac(c, cfg, max_tokens)
+            configure_fac(c, cfg, max_tokens, allow_p64=True)
             return
         c.hidden_size = int(_get(cfg, "hidden_size"))
         c.max_tokens = max_tokens

@@ -6,6 +6,9 @@
   python examples/sample.py k600diff [--ckpt ...]
   python examples/sample.py facdit   [--ckpt ...]   (FacDiT-XL, the taichikl recipe: 4x32x32 latents, patch 2, 16 frames)
   python examples/sample.py facmat   [--ckpt ...]   (FacMatDiT XL-64-1, the same recipe: matrix attention with RoPE over the 16 frames)
+  python examples/sample.py facdit-s128 [--ckpt ...]   (FacDiT-S, the taichi res-128 recipes: 4x16x16 latents, patch 2 = 64 patches per frame,
+                                                        16 frames; --decode-image-vae gives the 128x128 frames)
+  python examples/sample.py facmat-s128 [--ckpt ...]   (FacMatDiT S-64-1 of the same ladder: 12 spatial heads, 1 x 6 matrix heads, use_bias)
   python examples/sample.py <k600|facdit|facmat> --attention-maps maps.npz [--attention-steps 0 25 49]   (which frame attends to which)
   python examples/sample.py uvit3d   [--cond action:4]   (the pose-free U-ViT at the RE10K widths, 256x256 frames, continuous diffusion)
   python examples/sample.py k600 --continuous --decode-image-vae   (latents -> frames through a random-weight per-frame ImageVAE)
@@ -38,7 +41,7 @@ from bench import RE10K, synth_poses  # noqa: E402
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("model", choices=["re10k", "uvit3d", "k600", "k600diff", "facdit", "facmat", "taichi", "mcraft"])
+    ap.add_argument("model", choices=["re10k", "uvit3d", "k600", "k600diff", "facdit", "facmat", "facdit-s128", "facmat-s128", "taichi", "mcraft"])
     ap.add_argument("--ckpt")
     ap.add_argument("--inputs")
     ap.add_argument("--frames", type=int, default=8)
@@ -53,7 +56,8 @@ def main():
     ap.add_argument("--decode-image-vae", action="store_true",
                     help="decode the sampled latents with an ImageVAE (image_vae.yaml widths, z_channels = the latent channels; random weights "
                          "unless --image-vae-ckpt is given), the per-frame autoencoder of the dmlab / Minecraft / taichikl recipes; latents of "
-                         "8x8, 16x16 (k600) or 32x32 (facdit / facmat: 256x256 frames), the mid attention's sizes")
+                         "8x8, 16x16 (k600; facdit-s128 / facmat-s128: 128x128 frames) or 32x32 (facdit / facmat: 256x256 frames), the mid "
+                         "attention's sizes")
     ap.add_argument("--image-vae-ckpt", metavar="PATH",
                     help="with --decode-image-vae: a VAE in the diffusers layout (a folder with config.json and a .safetensors file, e.g. "
                          "stabilityai/sd-vae-ft-ema or the fine-tuned Taichi VAE), read by dfot_amd.load_diffusers_checkpoint")
@@ -71,8 +75,8 @@ def main():
                          "frame; rows follow the model batch) at the steps of --attention-steps, as '<step>/<block name>' and '<step>/noise_levels'")
     ap.add_argument("--attention-steps", type=int, nargs="*", default=None, help="step indices of the window (default: first, middle, last)")
     a = ap.parse_args()
-    if a.attention_maps and a.model not in ("k600", "facdit", "facmat"):
-        raise SystemExit("--attention-maps: the DiT3D models k600, facdit and facmat only")
+    if a.attention_maps and a.model not in ("k600", "facdit", "facmat", "facdit-s128", "facmat-s128"):
+        raise SystemExit("--attention-maps: the DiT3D models k600, facdit, facmat, facdit-s128 and facmat-s128 only")
     if (a.decode_titok or a.encode_titok) and a.model != "taichi":
         raise SystemExit("--decode-titok / --encode-titok: the taichi model only (latents of 4x1x32 tokens)")
     gen = torch.Generator(device="cuda").manual_seed(a.seed)
@@ -120,8 +124,9 @@ def main():
         conds = torch.randn(a.batch, tokens, dim, generator=torch.Generator().manual_seed(200 + a.seed))
         n_ctx = 4
     else:
-        diff, fac, facmat = a.model == "k600diff", a.model == "facdit", a.model == "facmat"
-        x_shape, tokens = ((4, 32, 32), 16) if fac or facmat else ((4, 1, 32), 16) if a.model == "taichi" else ((16, 16, 16), 5)
+        s128 = a.model.endswith("-s128")  # the res-128 ladder: S widths, depth 6, 16x16 latents (64 patches per frame)
+        diff, fac, facmat = a.model == "k600diff", a.model.startswith("facdit"), a.model.startswith("facmat")
+        x_shape, tokens = ((4, 16, 16), 16) if s128 else ((4, 32, 32), 16) if fac or facmat else ((4, 1, 32), 16) if a.model == "taichi" else ((16, 16, 16), 5)
         ckw, skw = {}, {}
         if a.cond:
             ctype, num = a.cond.split(":")
@@ -138,11 +143,15 @@ def main():
         elif fac:  # per depth a per-frame spatial block and a temporal block over the 16 frames of every patch position (inference only)
             bb = dict(name="dit3d", variant="factorized_attention", pos_emb_type="sinusoidal_factorized", patch_size=2, hidden_size=1152,
                       depth=28, num_heads=16, mlp_ratio=4.0, spatial_mlp_ratio=0.0)
+            if s128:  # @FacDiT/S
+                bb.update(hidden_size=384, depth=6, num_heads=6)
             model = dfot_amd.DiT3D(dict(bb, use_fourier_noise_embedding=a.continuous), x_shape=x_shape, max_tokens=tokens, **ckw).cuda()
         elif facmat:  # per depth a per-frame spatial block and a matrix block whose attention takes every frame as one token (inference only)
             bb = dict(name="dit3d", variant="factorized_matrix_attention", pos_emb_type="sinusoidal_2d", use_temporal_rope=True, patch_size=2,
                       embed_col_dim=64, embed_row_dim=1152, num_heads=16, num_col_heads=1, num_row_heads=16, depth=28, mlp_ratio=4.0,
                       spatial_mlp_ratio=4.0, use_bias=False, matrix_block="matrix", flatten_matrix_rope=False, matrix_multi_token=False)
+            if s128:  # @FacMatDiT/S-64-1
+                bb.update(embed_row_dim=384, depth=6, num_heads=12, num_row_heads=6, use_bias=True)
             model = dfot_amd.DiT3D(dict(bb, use_fourier_noise_embedding=a.continuous), x_shape=x_shape, max_tokens=tokens, **ckw).cuda()
         else:
             bb = dict(name="dit3d", variant="full", pos_emb_type="rope_3d", patch_size=1, hidden_size=1152, depth=28, num_heads=16)
@@ -215,7 +224,8 @@ def main():
         t0 = time.perf_counter()
         frames = dfot_amd.decode_image_latents(vae, out, vae_batch_size=2)
         torch.cuda.synchronize()
-        print(f"ImageVAE decode ({a.image_vae_ckpt or 'random weights'}): {tuple(out.shape)} -> {tuple(frames.shape)} in {(time.perf_counter() - t0) * 1e3:.1f} ms")
+        print(f"ImageVAE decode ({a.image_vae_ckpt or 'random weights'}): {tuple(out.shape)} -> {tuple(frames.shape)} in {(time.perf_counter() - t0) * 1e3:.1f} ms"
+              f"{'' if bool(torch.isfinite(frames).all()) else '  (NON-FINITE frames)'}")
     if a.decode_titok:
         vae = dfot_amd.TiTokDecoder(image_size=256, token_size=out.shape[2], vit_dec_model_size="large", num_latent_tokens=out.shape[4]).cuda()
         if titok_sd is not None:

@@ -203,13 +203,15 @@ typedef struct {
    *   + shortcut/FacDiT; dit_base.py:197-226,364-417): per depth one per-frame spatial DiTBlock (MLP mlp_hidden, 0 = none) and one
    *   temporal DiTBlock (MLP temporal_mlp_hidden, 0 = none) whose attention runs over the T frames of one patch position; the 2-D
    *   sinusoidal table is added at the patch embedding, the 1-D temporal table [max_tokens][hidden] after spatial block 0.
-   *   Uses hidden_size, num_heads, mlp_hidden, temporal_mlp_hidden; (H/p)*(W/p) % 128 == 0, max_tokens <= 32.  Trained through
+   *   Uses hidden_size, num_heads, mlp_hidden, temporal_mlp_hidden; (H/p)*(W/p) % 128 == 0, or == 64 with an even max_tokens
+   *   (inference only: the per-frame attention is then dfot_op_attention_seq64's kernel); max_tokens <= 32.  Trained through
    *   dfot_facdit_train_create; dfot_dit_train_create[_f] refuse it.
    * variant 3: DiT3D "factorized_matrix_attention" + sinusoidal_2d (FacMatDiT: configurations/algorithm/backbone/
    *   dit3d_factorized_matrix.yaml + shortcut/FacMatDiT): the block sequence and parameters of variant 1 without the difference front
    *   end -- no diff_embedder, the conditioning depends on the noise level only, max_tokens is the caller's (<= 32, odd counts
    *   allowed) -- and with use_temporal_rope the RoPE-1D over the frame axis (dit_base.py:297-306) on q and k of the matrix attention;
-   *   the (cos, sin) table [max_tokens][hd/2] is built in float64 at create time and is not a parameter.  Trained through
+   *   the (cos, sin) table [max_tokens][hd/2] is built in float64 at create time and is not a parameter.  (H/p)*(W/p) % 128 == 0, or
+   *   == 64 with an even max_tokens and even token counts (inference only; variant 1 keeps % 128).  Trained through
    *   dfot_facmat_train_create; dfot_dit_train_create[_f] refuse it. */
   int32_t variant;
   int32_t embed_col_dim;        /* 64 */
@@ -261,7 +263,8 @@ int dfot_dit_attn_timing(dfot_dit_t h, double* total_ms, int64_t* launches);
 /* out[B,T,C,H,W] = model(x[B,T,C,H,W], noise_levels[B,T]) ; x/out fp32, noise_levels int32 in [0, timesteps)
  * (device pointer; out-of-range levels are clamped), T <= max_tokens with T*(H/p)*(W/p) % 128 == 0.
  * variant 1: x holds the interleaved (difference_0, frame_0, difference_1, ...) tokens, T even, (H/p)*(W/p) % 128 == 0.
- * variant 2: any 1 <= T <= max_tokens (the temporal table's first T rows are used), (H/p)*(W/p) % 128 == 0. */
+ * variant 2: any 1 <= T <= max_tokens (the temporal table's first T rows are used), (H/p)*(W/p) % 128 == 0; variants 2 and 3 at
+ * (H/p)*(W/p) == 64: even T only (the rule of the first line). */
 int dfot_dit_forward(dfot_dit_t h, const float* x, const int32_t* noise_levels, float* out, int batch, int tokens,
                      void* stream);
 /* The same forward with an external condition per (video, token): `cond` fp32 [B,T,cond_dim] (action models) or `labels` int32 [B,T]
@@ -482,6 +485,13 @@ int dfot_op_attention(const void* q, const void* k, const void* v, void* o, int 
  * pad columns are zero; o[B,N,heads*d] is compact (row stride ldo) */
 int dfot_op_attention_padded(const void* q, const void* k, const void* v, void* o, int ldo, int batch, int heads, int n,
                              int d, void* stream);
+/* dfot_op_attention_padded for sequences of exactly 64 tokens (the per-frame spatial attention of FacDiT / FacMatDiT at 64 patches per
+ * frame): q, k, v [nseq][heads][64][dstride] bf16 with dstride = (d <= 64 ? 64 : 128), pad columns zero, q pre-scaled by log2(e)/sqrt(d);
+ * o[(seq*64 + row)][head*d + c], c < d, compact with row stride ldo; only those columns are written.  One workgroup per (sequence,
+ * head) with a single-pass softmax: the bits of a sequence depend on (d, its operands) alone, never on nseq or on the other sequences,
+ * and no row outside the nseq sequences is read or written (the operand buffers need no slack).  d % 8 == 0, 0 < d <= 128, nseq > 0,
+ * heads > 0, ldo % 8 == 0 covering heads*d; anything else: DFOT_ERR_SHAPE (null pointers: DFOT_ERR_ARG), nothing launched */
+int dfot_op_attention_seq64(const void* q, const void* k, const void* v, void* o, int ldo, int nseq, int heads, int d, void* stream);
 /* temporal attention of the factorized-attention DiT: q, k, v [batch*tokens][heads][patches][dstride] bf16 as above (what the per-frame
  * QKV epilogue writes; q pre-scaled); for every (video, head, patch position) the `tokens` frames of the video attend to each other.
  * o[(video, frame, patch)][heads*d] compact (row stride ldo).  1 <= tokens <= 32, d % 4 == 0, d <= 128, patches % 128 == 0, ldo a

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Micro-benchmarks of the C-ABI primitives at the RE10K model shapes (model batch 2), HIP-event timed.
-Usage (GPU box): python tools/bench_ops.py [gemm] [conv] [attn] [tattn] [mattn] [tattn_bwd] [facdit_train] [mattn_bwd] [facmat_train] [vae_encode] [equal] [dit_front] [ivae] [uvit3d] [gnfilm_frame] [uvit3d_train] [attnmap] [titok] [titok_enc] [mcraft]"""
+Usage (GPU box): python tools/bench_ops.py [gemm] [conv] [attn] [tattn] [mattn] [tattn_bwd] [facdit_train] [mattn_bwd] [facmat_train] [vae_encode] [equal] [dit_front] [ivae] [uvit3d] [gnfilm_frame] [uvit3d_train] [attnmap] [titok] [titok_enc] [mcraft] [sattn64]"""
 import ctypes as C
 import math
 import os
@@ -195,6 +195,41 @@ def attnmap():
     fwd = timeit(lambda: capi.check(capi.lib.dfot_op_matrix_attention_rope(P(z), P(o), P(table), b, tokens, e, h, cc, rr, scale, S())), iters=50, warm=5)
     t_map = timeit(lambda: capi.check(capi.lib.dfot_op_matrix_attention_map(P(z), P(table), P(m), b, tokens, e, h, cc, rr, scale, S())), iters=50, warm=5)
     print(f"attnmap taichikl matrix B={b} L={tokens} E={e} h={h}: forward {fwd*1e3:8.1f} us  map {t_map*1e3:8.1f} us", flush=True)
+
+
+def sattn64(b, heads, tokens, d):
+    """per-frame spatial attention at 64 patches per frame (the taichi res-128 recipes): us of dfot_op_attention_seq64 over b * tokens
+    sequences of 64, GB/s against its algorithmic bytes ((3 dstride + d) * 2 per (row, head), as tattn counts them), and next to it us of
+    dfot_op_attention_padded at the same number of rows with n = 128: half as many sequences, twice as long -- the same bytes, twice the score
+    FLOPs; the only yardstick there is, since that launcher cannot run n = 64"""
+    ds, nseq = 64 if d <= 64 else 128, b * tokens
+    q, k, v = (torch.zeros(nseq, heads, 64, ds, device="cuda", dtype=torch.bfloat16) for _ in range(3))
+    for t, mul in ((q, 0.2), (k, 1.0), (v, 1.0)):
+        t[..., :d] = (torch.randn(nseq, heads, 64, d, device="cuda") * mul).bfloat16()
+    o = torch.empty(nseq * 64, heads * d, device="cuda", dtype=torch.bfloat16)
+    ms = timeit(lambda: capi.check(capi.lib.dfot_op_attention_seq64(P(q), P(k), P(v), P(o), heads * d, nseq, heads, d, S())), iters=50, warm=5)
+    # the same buffers read as nseq / 2 sequences of 128 (per head the rows of two neighbouring frames are not adjacent: another problem on the
+    # same bytes, which is all a timing needs)
+    ms128 = timeit(lambda: capi.check(capi.lib.dfot_op_attention_padded(P(q), P(k), P(v), P(o), heads * d, nseq // 2, heads, 128, d, S())),
+                   iters=50, warm=5)
+    return ms, nseq * 64 * heads * (3 * ds + d) * 2.0 / ms / 1e6, ms128
+
+
+def p64_forward(kind, b):
+    """whole forward of FacDiT-S / FacMatDiT-S-64-1 (depth 6) at the res-128 shape: 4x16x16 latents, patch 2 (64 patches), 16 frames; ms"""
+    if kind == "facdit":
+        bb = dict(name="dit3d", variant="factorized_attention", pos_emb_type="sinusoidal_factorized", patch_size=2, hidden_size=384, depth=6,
+                  num_heads=6, mlp_ratio=4.0, spatial_mlp_ratio=0.0)
+    else:
+        bb = dict(name="dit3d", variant="factorized_matrix_attention", pos_emb_type="sinusoidal_2d", use_temporal_rope=True, patch_size=2,
+                  embed_col_dim=64, embed_row_dim=384, num_heads=12, num_col_heads=1, num_row_heads=6, depth=6, mlp_ratio=4.0,
+                  spatial_mlp_ratio=4.0, use_bias=True, matrix_block="matrix")
+    model = dfot_amd.DiT3D(bb, x_shape=(4, 16, 16), max_tokens=16).cuda().eval()
+    model.init_random(0)
+    x = torch.randn(b, 16, 4, 16, 16, device="cuda")
+    k = torch.randint(0, 1000, (b, 16), device="cuda")
+    with torch.no_grad():
+        return timeit(lambda: model(x, k), iters=20, warm=5)
 
 
 def facdit_forward(b):
@@ -631,6 +666,15 @@ def main():
                   f"{tf:6.2f} TF/s", flush=True)
         for b in (2, 16):
             print(f"facdit XL forward B={b} x 16 frames x 256 patches: {facdit_forward(b):.3f} ms", flush=True)
+    if "sattn64" in what:
+        # @FacMatDiT/S spatial blocks (384 / 12 heads = d 32) and @FacDiT/S (6 heads, d 64); 2 and 16 videos x 16 frames x 64 patches
+        for name, (hd, d) in {"FacMat-S": (12, 32), "FacDiT-S": (6, 64)}.items():
+            for b in (2, 16):
+                ms, gbs, ms128 = sattn64(b, hd, 16, d)
+                print(f"sattn64 {name:8s} B={b:2d} x 16 frames H={hd} d={d}: seq64 {ms*1e3:8.1f} us  {gbs:7.1f} GB/s ({gbs / 1e3 / HBM_TBS:.2f} of "
+                      f"{HBM_TBS:.0f} TB/s HBM)  padded n=128 at equal rows {ms128*1e3:8.1f} us  seq64 / padded {ms / ms128:.2f}", flush=True)
+        for kind, label in (("facdit", "FacDiT-S"), ("facmat", "FacMatDiT-S-64-1")):
+            print(f"{label} forward (depth 6) B=2 x 16 frames x 64 patches: {p64_forward(kind, 2):.3f} ms", flush=True)
     if "tattn_bwd" in what:
         for name, (b, hd, t, pn, d) in {"XL B2": (2, 16, 16, 256, 72), "XL B16": (16, 16, 16, 256, 72), "S B2": (2, 6, 16, 256, 64),
                                         "S B16": (16, 6, 16, 256, 64)}.items():
