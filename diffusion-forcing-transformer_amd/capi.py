@@ -177,6 +177,8 @@ SIGNATURES = {
     "dfot_op_attention_temporal_map": (_I, [_P, _P, _P, _P, C.c_size_t, _I, _I, _I, _I, _I, _P]),
     "dfot_op_matrix_attention_map": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P]),
     "dfot_op_matrix_attention": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _F, _P]),
+    "dfot_op_facmat_contract": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
+    "dfot_op_facmat_expand": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
     "dfot_op_attention_bwd": (_I, [_P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _P]),
     "dfot_op_conv3x3_bwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "dfot_op_conv3x3_bwd2": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),

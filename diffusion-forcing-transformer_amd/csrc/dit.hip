@@ -1050,7 +1050,11 @@ static int dit_create_impl(const DitCfg& c, dfot_dit_t* out) {
     DFOT_REQUIRE(P != 64 || c.max_tokens % 2 == 0, DFOT_ERR_SHAPE,
                  "factorized matrix variant: max_tokens %d x 64 patches per frame = %d rows per window; the row tiles need a multiple of 128",
                  c.max_tokens, c.max_tokens * 64);
-    DFOT_REQUIRE(c.embed_col_dim > 0 && c.embed_col_dim % 64 == 0, DFOT_ERR_SHAPE, "embed_col_dim %d must be a multiple of 64", c.embed_col_dim);
+    if (c.variant == 3)  // 1 .. 32: the streaming left factors of facmat_narrow.hip; multiples of 64: the factor GEMMs
+      DFOT_REQUIRE((c.embed_col_dim >= 1 && c.embed_col_dim <= 32) || (c.embed_col_dim > 0 && c.embed_col_dim % 64 == 0), DFOT_ERR_SHAPE,
+                   "embed_col_dim %d must be 1 to 32 (the narrow factor kernels) or a multiple of 64 (the factor GEMMs)", c.embed_col_dim);
+    else
+      DFOT_REQUIRE(c.embed_col_dim > 0 && c.embed_col_dim % 64 == 0, DFOT_ERR_SHAPE, "embed_col_dim %d must be a multiple of 64", c.embed_col_dim);
     DFOT_REQUIRE(c.num_col_heads > 0 && c.embed_col_dim % c.num_col_heads == 0 && c.num_row_heads > 0 &&
                      c.hidden_size % c.num_row_heads == 0 && (c.hidden_size / c.num_row_heads) % 4 == 0,
                  DFOT_ERR_SHAPE, "matrix attention heads (%d col, %d row) do not divide (%d, %d)", c.num_col_heads, c.num_row_heads,
@@ -1187,7 +1191,17 @@ int dfot_dit_reserve(dfot_dit_t h, int max_batch) {
     if ((rc = dit_alloc(h, &h->Z, frames * c.embed_col_dim * 3 * c.hidden_size, true))) return rc;
     if ((rc = dit_alloc(h, &h->idx, frames, true))) return rc;
   }
-  if (c.variant == 3) {
+  if (c.variant == 3 && c.embed_col_dim <= 32) {
+    // narrow column widths (facmat_narrow.hip): no transposes, so T1 holds the expanded frames and W2 is not needed.  The right-factor
+    // GEMM runs over frames * E rows rounded up to whole 128-row tiles: W1 and Z are sized to that and zeroed here.  The contract kernel
+    // and the attention write the real rows only, so a pad row holds zeros or a real row of an earlier, larger call: finite operands whose
+    // products (rows of Z past frames * E) are never read.
+    const size_t frames = (size_t)max_batch * c.max_tokens, wrows = (frames * c.embed_col_dim + 127) / 128 * 128;
+    if ((rc = dit_alloc(h, &h->T1, frames * h->P * c.hidden_size, true))) return rc;
+    if ((rc = dit_alloc(h, &h->W1, wrows * c.hidden_size, true)) || (rc = dit_alloc(h, &h->Z, 3 * wrows * c.hidden_size, true))) return rc;
+    DFOT_CHECK_HIP(hipMemset(h->W1, 0, wrows * c.hidden_size * sizeof(bf16)));
+    DFOT_CHECK_HIP(hipMemset(h->Z, 0, 3 * wrows * c.hidden_size * sizeof(bf16)));
+  } else if (c.variant == 3) {
     // the factor GEMMs of the matrix blocks take whole 128-row tiles: frames * E and frames * hidden rows, both multiples of 64, so an odd
     // frame count runs them on one more frame.  That frame holds the zeros written here or a real frame of an earlier, larger call (the
     // transposes and the attention kernel touch the real frames only): finite operands whose products are never read.
@@ -1279,6 +1293,7 @@ static int dit_forward_impl(dfot_dit_t h, const float* x, const int32_t* noise_l
   const bool diffm = c.variant == 1, facmat = c.variant == 1 || c.variant == 3, fac = c.variant == 2;
   const int frames = batch * tokens, P = h->P, E = c.embed_col_dim;
   const int gframes = c.variant == 3 ? (frames + 1) & ~1 : frames;  // frames of the matrix blocks' factor GEMMs (see reserve)
+  const bool narrow = c.variant == 3 && E <= 32;                    // the left factors are the streaming kernels of facmat_narrow.hip
   DFOT_REQUIRE(!diffm || tokens % 2 == 0, DFOT_ERR_SHAPE, "forward: %d tokens; the difference model takes (difference, frame) pairs", tokens);
   int max_level = c.timesteps - 1;
   const int* lvl = noise_levels;
@@ -1401,15 +1416,18 @@ static int dit_forward_impl(dfot_dit_t h, const float* x, const int32_t* noise_l
     // ---- MatrixDiTBlock: every frame is one token; qkv = U^T m V + bias, o = softmax(q k^T) v, out = U'^T o V' + bias' ----
     const DitBlockW& t = h->tblocks[bi];
     if ((rc = ln_mod(t.mod1))) return rc;
-    if ((rc = transpose(h->A, h->T1, P, hd))) return rc;  // m^T per frame: [hd][P]
-    {
+    if (narrow) {  // left factor in the natural layout: w[frame][e][d] = sum_p U[p][e] m[frame][p][d]  (facmat_narrow.hip)
+      if ((rc = launch_facmat_contract(h->A, t.ut, h->W1, frames, P, hd, E, s))) return rc;
+    } else {
+      if ((rc = transpose(h->A, h->T1, P, hd))) return rc;  // m^T per frame: [hd][P]
       GemmArgs g;  // left factor: w[frame][e][d] = sum_p U[p][e] m[frame][p][d]   (rows (frame, d), K = p, transposed store)
       g.A = h->T1; g.lda = P; g.W = t.ut; g.M = gframes * hd; g.N = E; g.K = P; g.out_bf16 = h->W1; g.ldo = E; g.tr_rows = hd;
       if ((rc = launch_gemm(A_DENSE, E_BF16, h->gemm_variant, g, s))) return rc;
     }
     {
-      GemmArgs g;  // right factor + bias[e][k]
-      g.A = h->W1; g.lda = hd; g.W = t.vt; g.M = gframes * E; g.N = 3 * hd; g.K = hd; g.bias = t.qkv_bias; g.bias_rows = t.qkv_bias ? E : 0;
+      GemmArgs g;  // right factor + bias[e][k]  (narrow: frames * E rows rounded up to whole tiles, see reserve)
+      g.A = h->W1; g.lda = hd; g.W = t.vt; g.M = narrow ? (frames * E + 127) / 128 * 128 : gframes * E; g.N = 3 * hd; g.K = hd;
+      g.bias = t.qkv_bias; g.bias_rows = t.qkv_bias ? E : 0;
       g.out_bf16 = h->Z; g.ldo = 3 * hd;
       if ((rc = launch_gemm(A_DENSE, E_BF16, h->gemm_variant, g, s))) return rc;
     }
@@ -1425,8 +1443,10 @@ static int dit_forward_impl(dfot_dit_t h, const float* x, const int32_t* noise_l
           (rc = launch_matrix_attn_map(h->Z, h->trope, h->cap_maps[map_slot], batch, tokens, E, hd, c.num_col_heads, c.num_row_heads, mscale, s)))
         return rc;
     }
-    if ((rc = transpose(h->W1, h->W2, E, hd))) return rc;  // o^T per frame: [hd][E]
-    {
+    if (narrow) {  // left factor of the projection, natural layout: s[frame][p][d] = sum_e U'[e][p] o[frame][e][d]
+      if ((rc = launch_facmat_expand(h->W1, t.put, h->T1, frames, P, hd, E, s))) return rc;
+    } else {
+      if ((rc = transpose(h->W1, h->W2, E, hd))) return rc;  // o^T per frame: [hd][E]
       GemmArgs g;  // left factor of the projection: s[frame][p][d] = sum_e U'[e][p] o[frame][e][d]
       g.A = h->W2; g.lda = E; g.W = t.put; g.M = gframes * hd; g.N = P; g.K = E; g.out_bf16 = h->T1; g.ldo = P; g.tr_rows = hd;
       if ((rc = launch_gemm(A_DENSE, E_BF16, h->gemm_variant, g, s))) return rc;

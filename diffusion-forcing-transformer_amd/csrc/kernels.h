@@ -157,6 +157,11 @@ int launch_matrix_attn_rope(const bf16* z, bf16* o, const float* rope_cs, int ba
 // attention_matrix_bwd.hip: backward of launch_matrix_attn_rope; d_o [batch*L*E][h], dz [batch*L*E][3h] (dq|dk|dv); same shape rules
 int launch_matrix_attn_rope_bwd(const bf16* z, const bf16* d_o, const float* rope_cs, bf16* dz, int batch, int L, int E, int h, int cc, int rr,
                                 float scale, hipStream_t s);
+// facmat_narrow.hip: the left factors of the MatrixDiTBlock at 1 <= E <= 32, in the natural layouts (no transposes around them):
+//   contract: w [frames][E][h] = u [E][P] x m [frames][P][h];   expand: s [frames][P][h] = u [P][E] x o [frames][E][h]
+// bf16 operands and outputs, fp32 sums in a fixed order per frame.  P % 64 == 0, h % 64 == 0, h <= 2048, 16-byte aligned pointers
+int launch_facmat_contract(const bf16* m, const bf16* u, bf16* w, int frames, int P, int h, int E, hipStream_t s);
+int launch_facmat_expand(const bf16* o, const bf16* u, bf16* sp, int frames, int P, int h, int E, hipStream_t s);
 // ---- attention maps (attention_map.hip): fp32 softmax probabilities recomputed from the forward's q / k; read-only on q / k ----
 // launch_attention_map: q, k as launch_attention_padded takes them, n = tokens * patches, patches % 64 == 0, 1 <= tokens <= 32.
 //   full: out [B][heads][n][n] (part unused);  frame: out [B][heads][tokens][tokens], part = attention_map_part_floats() floats of scratch

@@ -9,6 +9,9 @@
   python examples/sample.py facdit-s128 [--ckpt ...]   (FacDiT-S, the taichi res-128 recipes: 4x16x16 latents, patch 2 = 64 patches per frame,
                                                         16 frames; --decode-image-vae gives the 128x128 frames)
   python examples/sample.py facmat-s128 [--ckpt ...]   (FacMatDiT S-64-1 of the same ladder: 12 spatial heads, 1 x 6 matrix heads, use_bias)
+  python examples/sample.py facmat-s128-1 / facmat-s128-8   (FacMatDiT S-1-1 / S-8-1 with use_bias, the narrow rungs of that ladder: the left
+                                                        factors of the matrix blocks are the streaming kernels of csrc/facmat_narrow.hip)
+  python examples/sample.py facmat-s128 --embed-col-dim 32 --col-heads 4   (any other rung: a width of 1 .. 32 or a multiple of 64)
   python examples/sample.py <k600|facdit|facmat> --attention-maps maps.npz [--attention-steps 0 25 49]   (which frame attends to which)
   python examples/sample.py uvit3d   [--cond action:4]   (the pose-free U-ViT at the RE10K widths, 256x256 frames, continuous diffusion)
   python examples/sample.py k600 --continuous --decode-image-vae   (latents -> frames through a random-weight per-frame ImageVAE)
@@ -41,7 +44,8 @@ from bench import RE10K, synth_poses  # noqa: E402
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("model", choices=["re10k", "uvit3d", "k600", "k600diff", "facdit", "facmat", "facdit-s128", "facmat-s128", "taichi", "mcraft"])
+    ap.add_argument("model", choices=["re10k", "uvit3d", "k600", "k600diff", "facdit", "facmat", "facdit-s128", "facmat-s128", "facmat-s128-1",
+                                      "facmat-s128-8", "taichi", "mcraft"])
     ap.add_argument("--ckpt")
     ap.add_argument("--inputs")
     ap.add_argument("--frames", type=int, default=8)
@@ -49,6 +53,8 @@ def main():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--out", default="sample_out.npz")
+    ap.add_argument("--embed-col-dim", type=int, help="facmat*: column width of the matrix token (1 .. 32 or a multiple of 64; default: the recipe's)")
+    ap.add_argument("--col-heads", type=int, help="facmat*: num_col_heads (must divide the column width; default 1)")
     ap.add_argument("--cond", help="k600 / k600diff: synthetic external condition, 'action:DIM' (e.g. action:3, as dmlab) or 'label:CLASSES' (label:101)")
     ap.add_argument("--continuous", action="store_true",
                     help="k600 / k600diff / facdit / facmat: continuous diffusion as @diffusion/continuous (Fourier noise-level embedding, float levels, "
@@ -75,8 +81,10 @@ def main():
                          "frame; rows follow the model batch) at the steps of --attention-steps, as '<step>/<block name>' and '<step>/noise_levels'")
     ap.add_argument("--attention-steps", type=int, nargs="*", default=None, help="step indices of the window (default: first, middle, last)")
     a = ap.parse_args()
-    if a.attention_maps and a.model not in ("k600", "facdit", "facmat", "facdit-s128", "facmat-s128"):
-        raise SystemExit("--attention-maps: the DiT3D models k600, facdit, facmat, facdit-s128 and facmat-s128 only")
+    if a.attention_maps and not (a.model in ("k600", "facdit", "facdit-s128") or a.model.startswith("facmat")):
+        raise SystemExit("--attention-maps: the DiT3D models k600, facdit, facdit-s128 and facmat* only")
+    if (a.embed_col_dim or a.col_heads) and not a.model.startswith("facmat"):
+        raise SystemExit("--embed-col-dim / --col-heads: the facmat* models only")
     if (a.decode_titok or a.encode_titok) and a.model != "taichi":
         raise SystemExit("--decode-titok / --encode-titok: the taichi model only (latents of 4x1x32 tokens)")
     gen = torch.Generator(device="cuda").manual_seed(a.seed)
@@ -124,7 +132,7 @@ def main():
         conds = torch.randn(a.batch, tokens, dim, generator=torch.Generator().manual_seed(200 + a.seed))
         n_ctx = 4
     else:
-        s128 = a.model.endswith("-s128")  # the res-128 ladder: S widths, depth 6, 16x16 latents (64 patches per frame)
+        s128 = "-s128" in a.model  # the res-128 ladder: S widths, depth 6, 16x16 latents (64 patches per frame)
         diff, fac, facmat = a.model == "k600diff", a.model.startswith("facdit"), a.model.startswith("facmat")
         x_shape, tokens = ((4, 16, 16), 16) if s128 else ((4, 32, 32), 16) if fac or facmat else ((4, 1, 32), 16) if a.model == "taichi" else ((16, 16, 16), 5)
         ckw, skw = {}, {}
@@ -150,8 +158,14 @@ def main():
             bb = dict(name="dit3d", variant="factorized_matrix_attention", pos_emb_type="sinusoidal_2d", use_temporal_rope=True, patch_size=2,
                       embed_col_dim=64, embed_row_dim=1152, num_heads=16, num_col_heads=1, num_row_heads=16, depth=28, mlp_ratio=4.0,
                       spatial_mlp_ratio=4.0, use_bias=False, matrix_block="matrix", flatten_matrix_rope=False, matrix_multi_token=False)
-            if s128:  # @FacMatDiT/S-64-1
+            if s128:  # @FacMatDiT/S-64-1; facmat-s128-1 / facmat-s128-8: S-1-1 / S-8-1 (train_dfot_facmat-s-{1,8}-1-bias)
                 bb.update(embed_row_dim=384, depth=6, num_heads=12, num_row_heads=6, use_bias=True)
+                if a.model != "facmat-s128":
+                    bb.update(embed_col_dim=int(a.model.rsplit("-", 1)[1]))
+            if a.embed_col_dim:
+                bb.update(embed_col_dim=a.embed_col_dim)
+            if a.col_heads:
+                bb.update(num_col_heads=a.col_heads)
             model = dfot_amd.DiT3D(dict(bb, use_fourier_noise_embedding=a.continuous), x_shape=x_shape, max_tokens=tokens, **ckw).cuda()
         else:
             bb = dict(name="dit3d", variant="full", pos_emb_type="rope_3d", patch_size=1, hidden_size=1152, depth=28, num_heads=16)

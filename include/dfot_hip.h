@@ -211,7 +211,9 @@ typedef struct {
    *   end -- no diff_embedder, the conditioning depends on the noise level only, max_tokens is the caller's (<= 32, odd counts
    *   allowed) -- and with use_temporal_rope the RoPE-1D over the frame axis (dit_base.py:297-306) on q and k of the matrix attention;
    *   the (cos, sin) table [max_tokens][hd/2] is built in float64 at create time and is not a parameter.  (H/p)*(W/p) % 128 == 0, or
-   *   == 64 with an even max_tokens and even token counts (inference only; variant 1 keeps % 128).  Trained through
+   *   == 64 with an even max_tokens and even token counts (inference only; variant 1 keeps % 128).  embed_col_dim: a multiple of 64
+   *   (left factors as GEMMs between per-frame transposes) or 1 .. 32 (inference only: the streaming kernels of
+   *   dfot_op_facmat_contract / dfot_op_facmat_expand, no transposes); variant 1 keeps multiples of 64.  Trained through
    *   dfot_facmat_train_create; dfot_dit_train_create[_f] refuse it. */
   int32_t variant;
   int32_t embed_col_dim;        /* 64 */
@@ -523,6 +525,16 @@ int dfot_op_matrix_attention_rope_bwd(const void* z, const void* d_o, const floa
 /* the DifferenceDiT3D (variant 1) form of the same core, without rotation: register forms for L in {2, 4, 6, 8, 10}, one pair of
  * tokens per wave pass for every other L <= 32.  Test / measurement entry of the engine's own launcher */
 int dfot_op_matrix_attention(const void* z, void* o, int batch, int L, int E, int h, int cc, int rr, float scale, void* stream);
+/* Left factors of the MatrixDiTBlock at narrow column widths, 1 <= E <= 32 (FacMatDiT S-1-1 .. S-32-4, B-1-1 .. B-32-1), in the natural
+ * layouts -- no per-frame transpose before or after.  All operands bf16, sums fp32, outputs rounded to bf16.
+ *   contract: w[f][e][d] = sum_p u[e][p] * m[f][p][d]   m [frames][P][h] (the modulated frame), u [E][P] (qkv_u transposed), w [frames][E][h]
+ *   expand:   s[f][p][d] = sum_e u[p][e] * o[f][e][d]   o [frames][E][h] (the attention output), u [P][E] (proj_u transposed), s [frames][P][h]
+ * Streaming kernels: one wave owns 64 columns of one frame (expand: and 32 rows); a frame's sums are formed in an order fixed by (P, E)
+ * alone -- no atomics, the same bits for a frame alone and inside any batch -- and nothing outside the stated extents is read or written.
+ * frames >= 1, 1 <= E <= 32 (odd widths included), P % 64 == 0, h % 64 == 0, h <= 2048, 16-byte aligned pointers; anything else:
+ * DFOT_ERR_SHAPE (null / misaligned pointer: DFOT_ERR_ARG) with the op named in dfot_last_error(), before any device work */
+int dfot_op_facmat_contract(const void* m, const void* u, void* w, int frames, int P, int h, int E, void* stream);
+int dfot_op_facmat_expand(const void* o, const void* u, void* s, int frames, int P, int h, int E, void* stream);
 /* Attention-map kernels (test / measurement entries; see the dfot_dit_capture_attention section).  All outputs fp32; fixed summation order, no
  * atomics: two calls give the same bits.  None of them writes q, k or z.
  * Full attention: q, k as dfot_op_attention_padded takes them, n = tokens * patches with n % 128 == 0, patches % 64 == 0, 1 <= tokens <= 32.

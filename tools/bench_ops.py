@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Micro-benchmarks of the C-ABI primitives at the RE10K model shapes (model batch 2), HIP-event timed.
-Usage (GPU box): python tools/bench_ops.py [gemm] [conv] [attn] [tattn] [mattn] [tattn_bwd] [facdit_train] [mattn_bwd] [facmat_train] [vae_encode] [equal] [dit_front] [ivae] [uvit3d] [gnfilm_frame] [uvit3d_train] [attnmap] [titok] [titok_enc] [mcraft] [sattn64]"""
+Usage (GPU box): python tools/bench_ops.py [gemm] [conv] [attn] [tattn] [mattn] [tattn_bwd] [facdit_train] [mattn_bwd] [facmat_train] [vae_encode] [equal] [dit_front] [ivae] [uvit3d] [gnfilm_frame] [uvit3d_train] [attnmap] [titok] [titok_enc] [mcraft] [sattn64] [facmat_narrow]"""
 import ctypes as C
 import math
 import os
@@ -213,6 +213,46 @@ def sattn64(b, heads, tokens, d):
     ms128 = timeit(lambda: capi.check(capi.lib.dfot_op_attention_padded(P(q), P(k), P(v), P(o), heads * d, nseq // 2, heads, 128, d, S())),
                    iters=50, warm=5)
     return ms, nseq * 64 * heads * (3 * ds + d) * 2.0 / ms / 1e6, ms128
+
+
+def facmat_narrow_ops(frames, p, h, e):
+    """the two left-factor kernels of csrc/facmat_narrow.hip at one shape: (us, algorithmic bytes) of contract and expand, and us of a device
+    copy of each launch's byte count timed in the same run (a copy of n bytes reads n / 2 and writes n / 2)"""
+    m = torch.randn(frames, p, h, device="cuda").bfloat16()
+    o = torch.randn(frames, e, h, device="cuda").bfloat16()
+    uc = (torch.randn(e, p, device="cuda") / math.sqrt(p)).bfloat16()
+    ue = (torch.randn(p, e, device="cuda") / math.sqrt(e)).bfloat16()
+    w, s = torch.empty_like(o), torch.empty_like(m)
+    nbytes = 2.0 * (frames * p * h + frames * e * h + e * p)  # either direction: the big tile once, the small one once, u once
+    src = torch.empty(int(nbytes) // 2, device="cuda", dtype=torch.uint8)
+    dst = torch.empty_like(src)
+    out = []
+    for _ in range(5):  # alternate the three launches; the median of each
+        out.append((timeit(lambda: capi.check(capi.lib.dfot_op_facmat_contract(P(m), P(uc), P(w), frames, p, h, e, S())), iters=50, warm=5),
+                    timeit(lambda: capi.check(capi.lib.dfot_op_facmat_expand(P(o), P(ue), P(s), frames, p, h, e, S())), iters=50, warm=5),
+                    timeit(lambda: dst.copy_(src), iters=50, warm=5)))
+    med = lambda i: sorted(t[i] for t in out)[len(out) // 2]  # noqa: E731
+    return med(0), med(1), med(2), nbytes
+
+
+def facmat_narrow_forward(widths, b, rounds=5):
+    """whole forwards of @FacMatDiT/S-<E>-<cc> (depth 6, use_bias, temporal RoPE) at the res-128 shape -- 4x16x16 latents, patch 2 (64 patches),
+    16 frames -- for every (E, cc) of `widths`, alternated over `rounds` rounds in one process: {(E, cc): [ms per round]}"""
+    models = {}
+    for e, cc in widths:
+        bb = dict(name="dit3d", variant="factorized_matrix_attention", pos_emb_type="sinusoidal_2d", use_temporal_rope=True, patch_size=2,
+                  embed_col_dim=e, embed_row_dim=384, num_heads=12, num_col_heads=cc, num_row_heads=6, depth=6, mlp_ratio=4.0,
+                  spatial_mlp_ratio=4.0, use_bias=True, matrix_block="matrix")
+        models[(e, cc)] = dfot_amd.DiT3D(bb, x_shape=(4, 16, 16), max_tokens=16).cuda().eval()
+        models[(e, cc)].init_random(0)
+    x = torch.randn(b, 16, 4, 16, 16, device="cuda")
+    k = torch.randint(0, 1000, (b, 16), device="cuda")
+    out = {w: [] for w in widths}
+    with torch.no_grad():
+        for _ in range(rounds):
+            for w, model in models.items():
+                out[w].append(timeit(lambda: model(x, k), iters=50, warm=5))
+    return out
 
 
 def p64_forward(kind, b):
@@ -675,6 +715,21 @@ def main():
                       f"{HBM_TBS:.0f} TB/s HBM)  padded n=128 at equal rows {ms128*1e3:8.1f} us  seq64 / padded {ms / ms128:.2f}", flush=True)
         for kind, label in (("facdit", "FacDiT-S"), ("facmat", "FacMatDiT-S-64-1")):
             print(f"{label} forward (depth 6) B=2 x 16 frames x 64 patches: {p64_forward(kind, 2):.3f} ms", flush=True)
+    if "facmat_narrow" in what:
+        # the S shape (embed_row_dim 384, 64 patches, 16 videos x 16 frames) and an XL-like one (1152, 256 patches, 128 frames)
+        for name, (frames, p, h) in {"S": (256, 64, 384), "XL": (128, 256, 1152)}.items():
+            for e in (1, 8, 32):
+                tc, tx, tcopy, nbytes = facmat_narrow_ops(frames, p, h, e)
+                gb = lambda t: nbytes / t / 1e6  # noqa: E731
+                print(f"facmat_narrow {name:2s} frames={frames} P={p} h={h} E={e:2d}: {nbytes / 1e6:7.2f} MB  contract {tc*1e3:7.1f} us {gb(tc):7.1f} GB/s  "
+                      f"expand {tx*1e3:7.1f} us {gb(tx):7.1f} GB/s  device copy of the same bytes {tcopy*1e3:7.1f} us {gb(tcopy):7.1f} GB/s  "
+                      f"(contract {tcopy / tc:.2f}, expand {tcopy / tx:.2f} of the copy's rate)", flush=True)
+        widths = [(64, 1), (1, 1), (8, 1), (32, 4)]
+        ms = facmat_narrow_forward(widths, 16)
+        for e, cc in widths:
+            r = sorted(ms[(e, cc)])
+            print(f"FacMatDiT-S-{e}-{cc} forward (depth 6) B=16 x 16 frames x 64 patches: median {r[len(r) // 2]:.3f} ms  (min {r[0]:.3f}, max {r[-1]:.3f} over "
+                  f"{len(r)} alternated rounds)", flush=True)
     if "tattn_bwd" in what:
         for name, (b, hd, t, pn, d) in {"XL B2": (2, 16, 16, 256, 72), "XL B16": (16, 16, 16, 256, 72), "S B2": (2, 6, 16, 256, 64),
                                         "S B16": (16, 6, 16, 256, 64)}.items():
