@@ -25,3 +25,5 @@ from .image_vae import (ImageVAEDecoder, ImageVAEEncoder, ImageVAEPosterior, dec
                         load_diffusers_checkpoint)  # noqa: F401,E402
 from .titok import (TiTokDecoder, TiTokEncoder, decode_titok_latents, encode_titok_frames,  # noqa: F401,E402
                     load_titok_checkpoint)  # noqa: F401,E402
+from .dcae import (DCAEDecoder, DCAEEncoder, dcae_config, decode_dcae_latents, encode_dcae_frames,  # noqa: F401,E402
+                   load_dcae_checkpoint)  # noqa: F401,E402

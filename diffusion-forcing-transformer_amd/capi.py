@@ -246,6 +246,12 @@ SIGNATURES = {
     "dfot_op_titok_patch_rows": (_I, [_P, _P, _I, _I, _P]),
     "dfot_op_titok_enc_tokens": (_I, [_P, _L] + [_P] * 6 + [_F, _P] + [_I] * 4 + [_P]),
     "dfot_op_titok_moments": (_I, [_P, _P, _P, _P, _L, _I, _I, _I, _I, _P]),
+    "dfot_op_dcae_linear_attention": (_I, [_P, _L, _P, _L, _I, _I, _I, _P]),
+    "dfot_op_dcae_dw_glu": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "dfot_op_dcae_down_shortcut": (_I, [_P, _L, _P, _P] + [_I] * 6 + [_P]),
+    "dfot_op_dcae_up_shortcut": (_I, [_P, _L, _P, _L, _P] + [_I] * 6 + [_P]),
+    "dfot_op_dcae_rmsnorm": (_I, [_P, _P, _P, _F, _P, _P, _P, _I, _L, _I, _P]),
+    "dfot_op_dcae_act_bf16": (_I, [_P, _P, _L, _I, _P]),
     "dfot_op_f32_to_bf16": (_I, [_P, _P, _L, _P]),
     "dfot_op_bf16_to_f32": (_I, [_P, _P, _L, _P]),
     "dfot_op_equal_bits": (_I, [_P, _P, _L, _P, _P]),

@@ -659,7 +659,10 @@ class DFoTVideoPoseSampler:
                        noise=torch.empty(n_steps, bm, *xs.shape[1:], device="cuda") if need_noise else None,
                        xs=torch.empty_like(xs), out=None, graph=None,
                        # the captured backbone calls read the conditions HERE: every window copies its own in before the replay
-                       cond=None if cond_src is None else torch.empty_like(cond_src))
+                       cond=None if cond_src is None else torch.empty_like(cond_src),
+                       # ... and the branch mask: the window's own tensor is freed when the window returns, and a later window with the
+                       # same key replays the pointer that was captured (the key holds the mask's content, so the copy never goes stale)
+                       cmask=p0["cmask_dev"].clone() if self._static_graph_cond and p0["cmask_dev"] is not None else None)
         ent["tables"].copy_(flat_dev.view(n_steps, 8, bm, horizon))
         ent["gens"].copy_(gens_dev)
         ent["lives"].copy_(gens_dev if nfe == 1 else gens_dev.repeat_interleave(nfe, dim=1))
@@ -672,6 +675,8 @@ class DFoTVideoPoseSampler:
                 else:
                     ent["noise"][i].zero_()
         p_static = dict(p0, weights_dev=ent["weights"])
+        if ent["cmask"] is not None:
+            p_static["cmask_dev"] = ent["cmask"]
         if cond_src is not None:
             ent["cond"].copy_(cond_src)
             p_static["cond"] = ent["cond"]

@@ -19,6 +19,9 @@
                                                      4x32x32 latents -> 256x256 frames; the checkpoint in the diffusers layout)
   python examples/sample.py mcraft   [--ckpt ...]   (the Minecraft / dmlab DiT recipe: @DiT/B on 32x8x8 latents, patch 2, 16 frames, actions of
                                                      dim 4 with mask_first, continuous diffusion; --decode-image-vae decodes the 8x8 latents)
+  python examples/sample.py mcraft --decode-dc-ae [--dc-ae 8x|16x] [--dc-ae-ckpt dcae.pth] [--encode-dc-ae]   (the recipe's own autoencoder:
+                                                     DC-AE, 32x8x8 latents -> 64x64 frames (8x, dmlab) or 128x128 frames (16x, Minecraft);
+                                                     --encode-dc-ae encodes synthetic context frames into the run's context latents)
   python examples/sample.py taichi --decode-titok [--titok-ckpt model.safetensors]   (DiT-XL on the 1-D token latents 4x1x32 of the taichi
                                                      recipe, patch 1, 16 frames; TiTok-KL decoder: 32 tokens -> a 256x256 frame)
   python examples/sample.py taichi --encode-titok [--decode-titok] [--titok-ckpt model.safetensors]   (the context latents of the run are
@@ -76,6 +79,16 @@ def main():
     ap.add_argument("--titok-ckpt", metavar="model.safetensors",
                     help="with --decode-titok / --encode-titok: the recipe's TiTok_KL checkpoint, read by dfot_amd.load_titok_checkpoint (one file "
                          "feeds both halves)")
+    ap.add_argument("--decode-dc-ae", action="store_true",
+                    help="mcraft: decode the sampled 32x8x8 latents with the DC-AE decoder (dc_ae_preprocessor / dc_ae_16x_preprocessor widths; "
+                         "random weights unless --dc-ae-ckpt is given)")
+    ap.add_argument("--encode-dc-ae", action="store_true",
+                    help="mcraft: encode synthetic context frames (64x64 at 8x, 128x128 at 16x) with the DC-AE encoder into the context latents "
+                         "of the run")
+    ap.add_argument("--dc-ae", choices=["8x", "16x"], default="8x", help="the DC-AE configuration: 8x (dmlab, 64x64 frames) or 16x (Minecraft, 128x128)")
+    ap.add_argument("--dc-ae-ckpt", metavar="PATH",
+                    help="with --decode-dc-ae / --encode-dc-ae: the flat .pth / .safetensors state dict of the reference's MyAutoencoderDC, read "
+                         "by dfot_amd.load_dcae_checkpoint (one file feeds both halves)")
     ap.add_argument("--attention-maps", metavar="OUT.npz",
                     help="k600 / facdit / facmat: write the frame-to-frame attention maps of every frame-mixing block (per head, query frame x key "
                          "frame; rows follow the model batch) at the steps of --attention-steps, as '<step>/<block name>' and '<step>/noise_levels'")
@@ -87,6 +100,8 @@ def main():
         raise SystemExit("--embed-col-dim / --col-heads: the facmat* models only")
     if (a.decode_titok or a.encode_titok) and a.model != "taichi":
         raise SystemExit("--decode-titok / --encode-titok: the taichi model only (latents of 4x1x32 tokens)")
+    if (a.decode_dc_ae or a.encode_dc_ae) and a.model != "mcraft":
+        raise SystemExit("--decode-dc-ae / --encode-dc-ae: the mcraft model only (latents of 32x8x8)")
     gen = torch.Generator(device="cuda").manual_seed(a.seed)
     noise = dfot_amd.device_noise_fn(gen)
     conds = None
@@ -206,6 +221,23 @@ def main():
         torch.cuda.synchronize()
         print(f"TiTok encode ({a.titok_ckpt or 'random weights'}): {tuple(ctx.shape)} -> {tuple(xs[:, :n_ctx].shape)} in "
               f"{(time.perf_counter() - t0) * 1e3:.1f} ms")
+    dcae_sd = dfot_amd.load_dcae_checkpoint(a.dc_ae_ckpt) if a.dc_ae_ckpt else None
+    if a.encode_dc_ae:  # `_encode` of the reference for MyAutoencoderDC: context frames in [0, 1] -> latents, scaling_factor not applied
+        enc = dfot_amd.DCAEEncoder(**dfot_amd.dcae_config(a.dc_ae)).cuda()
+        if dcae_sd is not None:
+            ignored = enc.load_reference_state_dict(dcae_sd)
+            print(f"loaded {a.dc_ae_ckpt} ({len(ignored)} decoder keys ignored)")
+        else:
+            enc.init_random(seed=a.seed + 1)
+        size = xs.shape[-1] * enc.s_factor
+        ctx = torch.rand(xs.shape[0], n_ctx, 3, size, size, generator=torch.Generator().manual_seed(300 + a.seed)).cuda()
+        dfot_amd.encode_dcae_frames(enc, ctx[:1, :1], vae_batch_size=1)   # packs the weights, loads the kernels
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        xs[:, :n_ctx] = dfot_amd.encode_dcae_frames(enc, ctx, vae_batch_size=2)
+        torch.cuda.synchronize()
+        print(f"DC-AE {a.dc_ae} encode ({a.dc_ae_ckpt or 'random weights'}): {tuple(ctx.shape)} -> {tuple(xs[:, :n_ctx].shape)} in "
+              f"{(time.perf_counter() - t0) * 1e3:.1f} ms")
     model.eval()  # (train() would draw the per-video dropout of a condition embedding)
     if a.attention_maps:
         steps = a.attention_steps if a.attention_steps else sorted({0, a.steps // 2, a.steps - 1})
@@ -240,6 +272,20 @@ def main():
         torch.cuda.synchronize()
         print(f"ImageVAE decode ({a.image_vae_ckpt or 'random weights'}): {tuple(out.shape)} -> {tuple(frames.shape)} in {(time.perf_counter() - t0) * 1e3:.1f} ms"
               f"{'' if bool(torch.isfinite(frames).all()) else '  (NON-FINITE frames)'}")
+    if a.decode_dc_ae:
+        vae = dfot_amd.DCAEDecoder(**dfot_amd.dcae_config(a.dc_ae)).cuda()
+        if dcae_sd is not None:
+            ignored = vae.load_reference_state_dict(dcae_sd)
+            print(f"loaded {a.dc_ae_ckpt} ({len(ignored)} encoder keys ignored)")
+        else:
+            vae.init_random(seed=a.seed)
+        dfot_amd.decode_dcae_latents(vae, out[:1, :1], vae_batch_size=1)   # packs the weights, loads the kernels
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        frames = dfot_amd.decode_dcae_latents(vae, out, vae_batch_size=2)
+        torch.cuda.synchronize()
+        print(f"DC-AE {a.dc_ae} decode ({a.dc_ae_ckpt or 'random weights'}): {tuple(out.shape)} -> {tuple(frames.shape)} in "
+              f"{(time.perf_counter() - t0) * 1e3:.1f} ms{'' if bool(torch.isfinite(frames).all()) else '  (NON-FINITE frames)'}")
     if a.decode_titok:
         vae = dfot_amd.TiTokDecoder(image_size=256, token_size=out.shape[2], vit_dec_model_size="large", num_latent_tokens=out.shape[4]).cuda()
         if titok_sd is not None:

@@ -799,6 +799,43 @@ int dfot_op_titok_enc_tokens(const float* patches, int64_t ldp, const float* cls
 int dfot_op_titok_moments(const float* t, const float* w, const float* bias, float* out, int64_t ldo, int frames, int num_latent, int channels,
                           int out_channels, void* stream);
 
+/* ---- DC-AE pieces (algorithms/vae/dc_ae/autoencoder_dc_model.py:45-466: the deep-compression autoencoder of the dmlab / Minecraft latents;
+ * its 3x3 and 1x1 convolutions are the ops above).  Channels-last operands, one launch for all frames, no atomics, no allocation; every
+ * value depends on its own frame only, so a frame has the same bits alone and in any batch. -------------------------------------------- */
+/* ReLU linear attention of SanaMultiscaleLinearAttention (:86-95) on the fused projection output qkv bf16 [frames * n][ld]: head g is the
+ * 96 consecutive columns [96 g, 96 g + 96) = q | k | v of 32 channels each (the reference's reshape to (B, -1, 3 * 32, H W)).  Per frame
+ * and head, in fp32:   S[j][d] = sum_n relu(k[n][j]) * [v[n] ; 1][d]   (32 x 33, positions summed in ascending order),
+ *                      o[n][d] = (sum_j relu(q[n][j]) S[j][d]) / (sum_j relu(q[n][j]) S[j][32] + 1e-15),  d < 32
+ * o bf16 [frames * n][heads * 32] (row stride ldo), head g at columns [32 g, 32 g + 32).  n a multiple of 64 in [64, 4096], heads in
+ * [1, 64], ld >= 96 heads and ldo >= 32 heads, both multiples of 8; anything else: DFOT_ERR_SHAPE before any device work.  Rows past
+ * frames * n are neither read nor written. */
+int dfot_op_dcae_linear_attention(const void* qkv, int64_t ld, void* o, int64_t ldo, int frames, int n, int heads, void* stream);
+/* The middle of GLUMBConv: depthwise Conv2d(2 hc, 2 hc, 3, 1, 1, groups = 2 hc) + bias on x bf16 [frames][h][w][2 hc], then
+ * out[c] = y[c] * silu(y[hc + c]) as bf16 [frames][h][w][hc].  w_taps fp32 [9][2 hc] (tap dy * 3 + dx major, the transpose of the
+ * reference's [2 hc][1][3][3]), bias fp32 [2 hc]; fp32 accumulation in tap order, pixels outside the map contribute nothing (zero padding).
+ * hc a multiple of 256; x and out must not alias. */
+int dfot_op_dcae_dw_glu(const void* x, const float* w_taps, const float* bias, void* out, int frames, int h, int w, int hc, void* stream);
+/* DCDownBlock2d's tail (:226-240) and the encoder's output shortcut (:365-368), factor f in {1, 2}:
+ *   out fp32 [frames][h / f][w / f][cout] = pixel_unshuffle(conv, f) + mean over groups of gs = f f cin / cout channels of pixel_unshuffle(src, f)
+ * conv fp32 [frames][h][w][ldc] holds cout / f^2 channels (ldc >= that: the convolution's padded output), src fp32 [frames][h][w][cin]
+ * (NULL: no shortcut).  Unshuffled channel e = c f^2 + dy f + dx is channel c of pixel (f Y + dy, f X + dx); the group is summed in
+ * ascending order and divided by gs.  cout % 4 == 0, cout % f^2 == 0, f^2 cin % cout == 0. */
+int dfot_op_dcae_down_shortcut(const float* conv, int64_t ldc, const float* src, float* out, int frames, int h, int w, int cin, int cout, int factor,
+                               void* stream);
+/* DCUpBlock2d's tail (:268-283) and the decoder's input shortcut (:453-455), factor f in {1, 2}:
+ *   out fp32 [frames][f h][f w][cout] = pixel_shuffle(conv, f) + pixel_shuffle(repeat_interleave(src, rep), f),  rep = f f cout / cin
+ * conv fp32 [frames][h][w][ldc] holds f^2 cout channels, src fp32 [frames][h][w][lds] holds cin (NULL: no shortcut).
+ * f^2 cout % cin == 0. */
+int dfot_op_dcae_up_shortcut(const float* conv, int64_t ldc, const float* src, int64_t lds, float* out, int frames, int h, int w, int cin, int cout,
+                             int factor, void* stream);
+/* Channel RMSNorm with weight and bias (diffusers RMSNorm(dim, eps, elementwise_affine, bias)) of fp32 rows [rows][channels]:
+ *   y = x * rsqrt(mean(x^2) + eps) * weight + bias (+ resid) (relu: max(y, 0)),  written as fp32 and / or bf16 (either may be NULL, not both;
+ * out_f32 may be x or resid).  fp32 statistics, one wave per row.  channels a multiple of 4 up to 2048. */
+int dfot_op_dcae_rmsnorm(const float* x, const float* weight, const float* bias, float eps, const float* resid, float* out_f32, void* out_bf16,
+                         int relu, int64_t rows, int channels, void* stream);
+/* out bf16 [n] = act(x fp32 [n]); act 0 = none, 1 = ReLU, 2 = SiLU: a ResBlock's activation in front of conv2 (:129).  n % 4 == 0. */
+int dfot_op_dcae_act_bf16(const float* x, void* out, int64_t n, int act, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

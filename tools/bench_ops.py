@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Micro-benchmarks of the C-ABI primitives at the RE10K model shapes (model batch 2), HIP-event timed.
-Usage (GPU box): python tools/bench_ops.py [gemm] [conv] [attn] [tattn] [mattn] [tattn_bwd] [facdit_train] [mattn_bwd] [facmat_train] [vae_encode] [equal] [dit_front] [ivae] [uvit3d] [gnfilm_frame] [uvit3d_train] [attnmap] [titok] [titok_enc] [mcraft] [sattn64] [facmat_narrow]"""
+Usage (GPU box): python tools/bench_ops.py [gemm] [conv] [attn] [tattn] [mattn] [tattn_bwd] [facdit_train] [mattn_bwd] [facmat_train] [vae_encode] [equal] [dit_front] [ivae] [uvit3d] [gnfilm_frame] [uvit3d_train] [attnmap] [titok] [titok_enc] [mcraft] [sattn64] [facmat_narrow] [dcae]"""
 import ctypes as C
 import math
 import os
@@ -578,6 +578,63 @@ def ivae():
         print(f"ivae encode 16 frames 3x{r}x{r} -> moments (image_vae.yaml): {med(lambda: enc.encode(y)):.3f} ms", flush=True)
 
 
+def dcae():
+    """the DC-AE of the dmlab / Minecraft latents (csrc/dcae.hip): each new launch alone at the stock shapes of 16 frames, next to a
+    device-to-device copy of the same number of bytes (the yardstick of the streaming kernels: what moving that traffic costs at all), and a
+    whole encode / decode of 16 frames at both stock configurations.  No speed threshold: nothing of this had been measured before.  Each
+    figure: the median of 7 repeats of (3 warm-up + 20 timed launches between two HIP events)."""
+    import statistics
+    med = lambda fn, **kw: statistics.median(timeit(fn, **kw) for _ in range(7))
+
+    def copy_us(nbytes):
+        a = torch.empty(nbytes // 2, dtype=torch.uint8, device="cuda")
+        b = torch.empty_like(a)
+        return med(lambda: b.copy_(a)) * 1e3
+
+    def line(name, us, nbytes):
+        print(f"dcae {name}: {us:8.1f} us  ({nbytes / 1e6:7.2f} MB moved, {nbytes / us / 1e6:5.2f} TB/s; a device copy of as many bytes: "
+              f"{copy_us(nbytes):6.1f} us)", flush=True)
+    f = 16
+    for n, c in ((64, 512), (256, 512), (64, 1024)):      # dmlab stage 3; Minecraft stage 3 and stage 4
+        side, heads, m = int(n ** 0.5), c // 32, f * n
+        qkv = torch.randn(m, 3 * c, device="cuda").bfloat16()
+        o = torch.empty(m, c, dtype=torch.bfloat16, device="cuda")
+        us = med(lambda: capi.check(capi.lib.dfot_op_dcae_linear_attention(P(qkv), 3 * c, P(o), c, f, n, heads, S()))) * 1e3
+        line(f"linear_attention {f} frames N={n} C={c} ({f * heads} workgroups)", us, qkv.numel() * 2 + o.numel() * 2)
+        t = torch.randn(f, side, side, 8 * c, device="cuda").bfloat16()
+        wt, bias = torch.randn(9, 8 * c, device="cuda") / 3, torch.zeros(8 * c, device="cuda")
+        gl = torch.empty(f, side, side, 4 * c, dtype=torch.bfloat16, device="cuda")
+        us = med(lambda: capi.check(capi.lib.dfot_op_dcae_dw_glu(P(t), P(wt), P(bias), P(gl), f, side, side, 4 * c, S()))) * 1e3
+        line(f"dw_glu {f} frames {side}x{side} 2h={8 * c}", us, t.numel() * 2 + gl.numel() * 2)
+        x, r = torch.randn(m, c, device="cuda"), torch.randn(m, c, device="cuda")
+        w1, b1 = torch.ones(c, device="cuda"), torch.zeros(c, device="cuda")
+        o32, o16 = torch.empty_like(x), torch.empty(m, c, dtype=torch.bfloat16, device="cuda")
+        us = med(lambda: capi.check(capi.lib.dfot_op_dcae_rmsnorm(P(x), P(w1), P(b1), 1e-5, P(r), P(o32), P(o16), 0, m, c, S()))) * 1e3
+        line(f"rmsnorm + residual, fp32 and bf16 out, {m} rows of {c}", us, x.numel() * 14)
+    for name, (h, cin, cout) in {"down 256 -> 512 at 32x32": (32, 256, 512), "down 512 -> 512 at 16x16": (16, 512, 512)}.items():
+        conv, src = torch.randn(f, h, h, cout // 4, device="cuda"), torch.randn(f, h, h, cin, device="cuda")
+        out = torch.empty(f, h // 2, h // 2, cout, device="cuda")
+        us = med(lambda: capi.check(capi.lib.dfot_op_dcae_down_shortcut(P(conv), cout // 4, P(src), P(out), f, h, h, cin, cout, 2, S()))) * 1e3
+        line(f"{name} (unshuffle + group mean {4 * cin // cout})", us, (conv.numel() + src.numel() + out.numel()) * 4)
+    for name, (h, cin, cout) in {"up 512 -> 256 at 16x16": (16, 512, 256), "up 256 -> 128 at 32x32": (32, 256, 128)}.items():
+        conv, src = torch.randn(f, h, h, 4 * cout, device="cuda"), torch.randn(f, h, h, cin, device="cuda")
+        out = torch.empty(f, 2 * h, 2 * h, cout, device="cuda")
+        us = med(lambda: capi.check(capi.lib.dfot_op_dcae_up_shortcut(P(conv), 4 * cout, P(src), cin, P(out), f, h, h, cin, cout, 2, S()))) * 1e3
+        line(f"{name} (shuffle + repeat {4 * cout // cin})", us, (conv.numel() + src.numel() + out.numel()) * 4)
+    t32 = torch.randn(f * 32 * 32, 256, device="cuda")
+    tb = torch.empty(t32.shape, dtype=torch.bfloat16, device="cuda")
+    us = med(lambda: capi.check(capi.lib.dfot_op_dcae_act_bf16(P(t32), P(tb), t32.numel(), 2, S()))) * 1e3
+    line(f"act_bf16 (SiLU) {t32.shape[0]} rows of 256", us, t32.numel() * 6)
+    for kind, size in (("8x", 64), ("16x", 128)):
+        cfg = dfot_amd.dcae_config(kind)
+        enc, dec = dfot_amd.DCAEEncoder(**cfg).cuda(), dfot_amd.DCAEDecoder(**cfg).cuda()
+        enc.init_random(1)
+        dec.init_random(0)
+        y, z = torch.rand(f, 3, size, size, device="cuda") * 2 - 1, torch.randn(f, 32, 8, 8, device="cuda")
+        ms_e, ms_d = med(lambda: enc.encode(y), iters=5, warm=1), med(lambda: dec.decode(z), iters=5, warm=1)
+        print(f"dcae {kind} encode {f} frames 3x{size}x{size} -> 32x8x8: {ms_e:.3f} ms; decode 32x8x8 -> 3x{size}x{size}: {ms_d:.3f} ms", flush=True)
+
+
 def titok():
     """the TiTok-KL decoder of the taichi recipes: the ragged attention launch alone at the production shape (16 frames of 289 tokens, the
     `large` preset's 16 heads) and a whole decode of 16 frames at 256 x 256 through the `large` decoder (and the `small` one).  Each figure:
@@ -646,6 +703,8 @@ def main():
         mcraft()
     if "ivae" in what:
         ivae()
+    if "dcae" in what:
+        dcae()
     if "vae_encode" in what:
         vae_encode()
     variants = [int(x) for x in os.environ.get("VARIANTS", "1").split(",")]

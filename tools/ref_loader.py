@@ -11,6 +11,17 @@ replaced or copied:
   timm==1.0.17     PatchEmbed  -> Conv2d(k=s=patch) [+ flatten(2).transpose(1,2) if flatten]
                    Mlp         -> fc1 -> act -> fc2
   diffusers==0.32.2 TimestepEmbedding -> linear_1 -> SiLU -> linear_2 ; LabelEmbedding -> nn.Embedding
+                   for install_dcae() (the DC-AE file imports its layers from diffusers); written from knowledge of that release and
+                   NOT checked against the library, which is not available here:
+                   RMSNorm(dim, eps, elementwise_affine, bias) -> x * rsqrt(mean(x^2, -1) in fp32 + eps) * weight + bias
+                   get_normalization -> rms_norm: RMSNorm(C, 1e-5, True, True); batch_norm: nn.BatchNorm2d(C)
+                   get_activation    -> silu / swish, relu, relu6, gelu, mish
+                   GLUMBConv         -> conv_inverted 1x1 C -> 8C, SiLU, depthwise 3x3 on 8C, chunk(2): x * silu(gate),
+                                        conv_point 1x1 4C -> C (no bias), RMSNorm on channels, + residual
+                   SanaMultiscaleAttnProcessor2_0 -> cat[to_q | to_k | to_v] (+ multiscale branches), reshape (B, -1, 3 * head_dim, H W),
+                                        chunk(3, dim 2), ReLU on q and k, linear attention iff H W > head_dim (fp32), to_out, norm_out,
+                                        + residual
+                   ConfigMixin / ModelMixin / register_to_config / apply_forward_hook / EncoderOutput / DecoderOutput -> trivial
   rotary_embedding_torch==0.8.6 rotate_half -> interleaved pairs (x1,x2) -> (-x2,x1)
   omegaconf==2.3.0 DictConfig  -> attribute dict with .get ; OmegaConf.to_container -> plain dict
   lightning==2.5.1 LightningModule -> nn.Module with .device/.log/.trainer
@@ -296,3 +307,142 @@ def install_titok():
         _mod("omegaconf", DictConfig=AttrDict, OmegaConf=types.SimpleNamespace(to_container=_to_container, create=AttrDict))
     model = importlib.import_module("algorithms.vae.tiktok_kl.titok_kl")   # imports algorithms.vae.common.distribution for real
     return model.TiTok_KL
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# diffusers 0.32.2 stand-ins for the DC-AE file (see the header: stated from knowledge of the release, unverified against the library)
+class _RMSNorm(nn.Module):
+    def __init__(self, dim, eps, elementwise_affine=True, bias=False):
+        super().__init__()
+        self.eps, self.weight, self.bias = eps, None, None
+        if elementwise_affine:
+            self.weight = nn.Parameter(torch.ones(dim))
+            if bias:
+                self.bias = nn.Parameter(torch.zeros(dim))
+
+    def forward(self, x):
+        dtype = x.dtype
+        var = x.to(torch.float32).pow(2).mean(-1, keepdim=True)
+        x = x * torch.rsqrt(var + self.eps)
+        if self.weight is not None:
+            x = x.to(self.weight.dtype) * self.weight
+            if self.bias is not None:
+                x = x + self.bias
+            return x
+        return x.to(dtype)
+
+
+def _get_normalization(norm_type="batch_norm", num_features=None, eps=1e-5, elementwise_affine=True, bias=True):
+    if norm_type == "rms_norm":
+        return _RMSNorm(num_features, eps=eps, elementwise_affine=elementwise_affine, bias=bias)
+    if norm_type == "batch_norm":
+        return nn.BatchNorm2d(num_features, eps=eps, affine=elementwise_affine)
+    raise ValueError(f"norm_type={norm_type} is not supported")
+
+
+def _get_activation(act_fn):
+    acts = {"silu": nn.SiLU, "swish": nn.SiLU, "relu": nn.ReLU, "relu6": nn.ReLU6, "gelu": nn.GELU, "mish": nn.Mish}
+    return acts[act_fn.lower()]()
+
+
+class _GLUMBConv(nn.Module):
+    def __init__(self, in_channels, out_channels, expand_ratio=4, norm_type=None, residual_connection=True):
+        super().__init__()
+        hidden = int(expand_ratio * in_channels)
+        self.norm_type, self.residual_connection = norm_type, residual_connection
+        self.nonlinearity = nn.SiLU()
+        self.conv_inverted = nn.Conv2d(in_channels, hidden * 2, 1, 1, 0)
+        self.conv_depth = nn.Conv2d(hidden * 2, hidden * 2, 3, 1, 1, groups=hidden * 2)
+        self.conv_point = nn.Conv2d(hidden, out_channels, 1, 1, 0, bias=False)
+        self.norm = _RMSNorm(out_channels, eps=1e-5, elementwise_affine=True, bias=True) if norm_type == "rms_norm" else None
+
+    def forward(self, x):
+        residual = x
+        x = self.conv_depth(self.nonlinearity(self.conv_inverted(x)))
+        x, gate = torch.chunk(x, 2, dim=1)
+        x = self.conv_point(x * self.nonlinearity(gate))
+        if self.norm_type == "rms_norm":
+            x = self.norm(x.movedim(1, -1)).movedim(-1, 1)
+        return x + residual if self.residual_connection else x
+
+
+class _SanaMultiscaleAttentionProjection(nn.Module):
+    def __init__(self, in_channels, num_attention_heads, kernel_size):
+        super().__init__()
+        ch = 3 * in_channels
+        self.proj_in = nn.Conv2d(ch, ch, kernel_size, padding=kernel_size // 2, groups=ch, bias=False)
+        self.proj_out = nn.Conv2d(ch, ch, 1, 1, 0, groups=3 * num_attention_heads, bias=False)
+
+    def forward(self, x):
+        return self.proj_out(self.proj_in(x))
+
+
+class _SanaMultiscaleAttnProcessor2_0:
+    def __call__(self, attn, hidden_states):
+        height, width = hidden_states.shape[-2:]
+        use_linear = height * width > attn.attention_head_dim
+        residual, dtype = hidden_states, hidden_states.dtype
+        hidden_states = hidden_states.movedim(1, -1)
+        hidden_states = torch.cat([attn.to_q(hidden_states), attn.to_k(hidden_states), attn.to_v(hidden_states)], dim=3).movedim(-1, 1)
+        multi = [hidden_states] + [block(hidden_states) for block in attn.to_qkv_multiscale]
+        hidden_states = torch.cat(multi, dim=1)
+        if use_linear:
+            hidden_states = hidden_states.to(torch.float32)
+        hidden_states = hidden_states.reshape(hidden_states.shape[0], -1, 3 * attn.attention_head_dim, height * width)
+        query, key, value = hidden_states.chunk(3, dim=2)
+        query, key = attn.nonlinearity(query), attn.nonlinearity(key)
+        _SanaMultiscaleAttnProcessor2_0.branches.append("linear" if use_linear else "quadratic")
+        if use_linear:
+            hidden_states = attn.apply_linear_attention(query, key, value).to(dtype)
+        else:
+            hidden_states = attn.apply_quadratic_attention(query, key, value)
+        hidden_states = torch.reshape(hidden_states, (hidden_states.shape[0], -1, height, width))
+        hidden_states = attn.to_out(hidden_states.movedim(1, -1)).movedim(-1, 1)
+        if attn.norm_type == "rms_norm":
+            hidden_states = attn.norm_out(hidden_states.movedim(1, -1)).movedim(-1, 1)
+        else:
+            hidden_states = attn.norm_out(hidden_states)
+        return hidden_states + residual if attn.residual_connection else hidden_states
+
+
+_SanaMultiscaleAttnProcessor2_0.branches = []   # which branch each call took (tools/make_golden_dcae.py asserts: linear only)
+
+
+def install_dcae():
+    """The reference's DC-AE (algorithms/vae/dc_ae/autoencoder_dc_model.py) importable on its own: namespace packages skip the package
+    __init__ files, the diffusers layers it imports are the stand-ins above (unverified against the library), the Lightning / omegaconf /
+    utils imports are names only.  Returns (MyAutoencoderDC, the module): the module also holds Encoder, Decoder and the blocks."""
+    if REF not in sys.path:
+        sys.path.insert(0, REF)
+    sys.dont_write_bytecode = True
+    for name, rel in [("algorithms", "algorithms"), ("algorithms.vae", "algorithms/vae"), ("algorithms.vae.dc_ae", "algorithms/vae/dc_ae"),
+                      ("algorithms.common", "algorithms/common"), ("utils", "utils")]:
+        if name not in sys.modules:
+            _ns(name, f"{REF}/{rel}")
+    if "omegaconf" not in sys.modules:
+        _mod("omegaconf", DictConfig=AttrDict, OmegaConf=types.SimpleNamespace(to_container=_to_container, create=AttrDict))
+    _mod("algorithms.common.base_pytorch_algo", BasePytorchAlgo=_LightningModule)
+    if "lightning" not in sys.modules:
+        lt = _mod("lightning")
+        lt.pytorch = _mod("lightning.pytorch", LightningModule=_LightningModule)
+        _mod("lightning.pytorch.utilities")
+        _mod("lightning.pytorch.utilities.types", STEP_OUTPUT=object)
+    _mod("utils.storage_utils", safe_torch_save=None)
+    _mod("utils.logging_utils", log_video=lambda *a, **k: None)
+    _mod("utils.ckpt_utils", is_wandb_run_path=lambda p: False, is_hf_path=lambda p: False, wandb_to_local_path=lambda p: p,
+         download_pretrained=lambda p: p)
+    for name in ("diffusers", "diffusers.models", "diffusers.models.autoencoders", "diffusers.models.transformers", "diffusers.utils"):
+        if name not in sys.modules:
+            _mod(name)
+    out_cls = lambda n: type(n, (dict,), {})  # noqa: E731
+    _mod("diffusers.configuration_utils", ConfigMixin=type("ConfigMixin", (), {}), register_to_config=lambda f: f)
+    _mod("diffusers.models.activations", get_activation=_get_activation)
+    _mod("diffusers.models.attention_processor", SanaMultiscaleAttentionProjection=_SanaMultiscaleAttentionProjection,
+         SanaMultiscaleAttnProcessor2_0=_SanaMultiscaleAttnProcessor2_0)
+    _mod("diffusers.models.autoencoders.vae", DecoderOutput=out_cls("DecoderOutput"), EncoderOutput=out_cls("EncoderOutput"))
+    _mod("diffusers.models.modeling_utils", ModelMixin=type("ModelMixin", (nn.Module,), {}))
+    _mod("diffusers.models.normalization", RMSNorm=_RMSNorm, get_normalization=_get_normalization)
+    _mod("diffusers.models.transformers.sana_transformer", GLUMBConv=_GLUMBConv)
+    _mod("diffusers.utils.accelerate_utils", apply_forward_hook=lambda f: f)
+    model = importlib.import_module("algorithms.vae.dc_ae.autoencoder_dc_model")
+    return model.MyAutoencoderDC, model
