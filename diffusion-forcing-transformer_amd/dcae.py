@@ -28,16 +28,11 @@ import math
 from typing import Dict, List, Mapping, Optional, Sequence, Tuple
 
 import torch
-from torch import nn
 
 from . import capi
-from .image_vae import _ImageVAEModule, _chunks
-from .vae import BF, _P, _S, _pad_to
+from .codec_common import BF, _P, _S, CodecModule, conv3x3, flat_frames, gemm, map_frame_chunks, pack_conv3x3, pad_to
 
-_GEMM_KS2 = 8            # GemmVariant GEMM_DMA_128_KS2 (csrc/gemm.h)
-_E_BF16, _ACT_SILU = 1, 2
-_ACTS = {"relu": 1, "silu": 2}
-_BUFFERS = ("running_mean", "running_var", "num_batches_tracked")
+_ACTS = {"relu": 1, "silu": 2}       # dfot_op_dcae_act_bf16
 _OTHER_KEYS = ("name", "defaults", "pretrained_path", "pretrained_kwargs", "precision", "latent_type", "max_encode_length", "logging",
                "batch_size")   # keys of the reference's yaml files that do not describe the model
 MAX_POSITIONS = 4096     # dfot_op_dcae_linear_attention: N a multiple of 64 up to this
@@ -123,11 +118,11 @@ def _plan(kind: str, side: str, types, channels, layers, multiscales, norms, act
     return ch, layers, types, norms, acts
 
 
-class _DCAEModule(_ImageVAEModule):
-    """What the DC-AE encoder and decoder share on top of the VAE module helpers (registration under the reference's names, 3x3 weight
-    packing, the convolution call): BatchNorm buffers, the weight forms of this model and its blocks."""
+class _DCAEModule(CodecModule):
+    """What the DC-AE encoder and decoder share on top of the codec base (registration under the reference's names, BatchNorm buffers
+    included; strict loading): the weight forms of this model and its blocks."""
 
-    load_diffusers_state_dict = None   # (the AutoencoderKL key map of the ImageVAE classes does not apply to this model)
+    _tensor_noun = ""
 
     def _common(self, kind: str, cfg: Mapping) -> Mapping:
         cfg = dict(cfg)
@@ -148,14 +143,16 @@ class _DCAEModule(_ImageVAEModule):
         self.scaling_factor = float(full["scaling_factor"])
         self.latent = int(full["latent_channels"])
         self._specs: List[Tuple[str, Tuple[int, ...]]] = []
-        self._kind: Dict[str, str] = {}
         self._bn: List[str] = []        # ResBlocks whose norm is a BatchNorm2d
         return full
 
     # ------------------------------------------------------------------ registration
+    def _spec_conv(self, name: str, ci: int, co: int) -> None:
+        self._specs += [(f"{name}.weight", (co, ci, 3, 3)), (f"{name}.bias", (co,))]
+
     def _spec_block(self, name: str, kind: str, c: int, norm: str) -> None:
         if kind == "ResBlock":
-            self._spec_conv(f"{name}.conv1", c, c, 3)
+            self._spec_conv(f"{name}.conv1", c, c)
             self._specs += [(f"{name}.conv2.weight", (c, c, 3, 3)), (f"{name}.norm.weight", (c,)), (f"{name}.norm.bias", (c,))]
             if norm == "batch_norm":
                 self._specs += [(f"{name}.norm.running_mean", (c,)), (f"{name}.norm.running_var", (c,)), (f"{name}.norm.num_batches_tracked", ())]
@@ -168,59 +165,6 @@ class _DCAEModule(_ImageVAEModule):
                         (f"{name}.conv_out.conv_point.weight", (c, 4 * c, 1, 1)),
                         (f"{name}.conv_out.norm.weight", (c,)), (f"{name}.conv_out.norm.bias", (c,))]
 
-    def _register(self) -> None:
-        self._names = [n for n, _ in self._specs]
-        for name, shape in self._specs:
-            *path, leaf = name.split(".")
-            node: nn.Module = self
-            for part in path:
-                if part not in node._modules:
-                    node.add_module(part, nn.Module())
-                node = node._modules[part]
-            if leaf == "num_batches_tracked":
-                node.register_buffer(leaf, torch.tensor(0, dtype=torch.long))
-            elif leaf in _BUFFERS:
-                node.register_buffer(leaf, torch.ones(shape) if leaf == "running_var" else torch.zeros(shape))
-            else:
-                node.register_parameter(leaf, nn.Parameter(torch.zeros(shape), requires_grad=False))
-        self._packed: Dict[str, torch.Tensor] = {}
-        self._sig = None
-
-    def _tensors(self) -> Dict[str, torch.Tensor]:
-        sd = dict(self.named_parameters())
-        sd.update(dict(self.named_buffers()))
-        return {n: sd[n] for n in self._names}
-
-    def init_random(self, seed: int = 0) -> None:
-        super().init_random(seed)
-        g = torch.Generator().manual_seed(seed + 1)
-        with torch.no_grad():
-            for n, b in self.named_buffers():
-                if n.endswith("running_var"):
-                    b.copy_((0.5 + torch.rand(b.shape, generator=g)).to(b.device))
-                elif n.endswith("running_mean"):
-                    b.copy_((0.1 * torch.randn(b.shape, generator=g)).to(b.device))
-
-    def load_reference_state_dict(self, state_dict: Mapping[str, torch.Tensor]) -> List[str]:
-        """keys of a reference ``MyAutoencoderDC`` (optionally ``vae.``-prefixed): this module's own keys -- the BatchNorm buffers among
-        them -- are loaded, strictly (every one must be present with its shape); every other key is ignored and returned."""
-        own = self._tensors()
-        ignored, seen = [], set()
-        with torch.no_grad():
-            for k, v in state_dict.items():
-                n = k[4:] if k.startswith("vae.") else k
-                if n in own:
-                    if tuple(v.shape) != tuple(own[n].shape):
-                        raise ValueError(f"size mismatch for {n}: {tuple(v.shape)} vs {tuple(own[n].shape)}")
-                    own[n].copy_(v)
-                    seen.add(n)
-                else:
-                    ignored.append(k)
-        missing = [n for n in own if n not in seen]
-        if missing:
-            raise ValueError(f"keys not found in the checkpoint: {missing[:5]}{'...' if len(missing) > 5 else ''}")
-        return ignored
-
     # ------------------------------------------------------------------ weights -> GEMM / kernel operands
     @staticmethod
     def fold_batch_norm(w: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, mean: torch.Tensor, var: torch.Tensor,
@@ -229,20 +173,13 @@ class _DCAEModule(_ImageVAEModule):
         s = gamma / torch.sqrt(var + eps)
         return w * s.reshape(-1, 1, 1, 1), beta - mean * s
 
-    def _sync(self) -> None:
-        ts = self._tensors()
-        sig = tuple((t.data_ptr(), t._version) for t in ts.values())
-        if sig == self._sig:
-            return
-        for name, t in ts.items():
-            if not t.is_cuda:
-                raise RuntimeError(f"{name} is on {t.device}; move the module to the GPU first (there is no CPU path)")
-        dev = next(iter(ts.values())).device
-        f = {n: (t.detach().float() if t.is_floating_point() else t) for n, t in ts.items()}
+    def _pack_weights(self, f: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+        dev = next(iter(f.values())).device
         pk: Dict[str, torch.Tensor] = {}
 
         def conv(name: str, w: torch.Tensor, b: Optional[torch.Tensor]) -> None:
-            pk[name + ".weight"], cop = self._pack(name, w)
+            cop = pad_to(w.shape[0], 64)            # both channel counts padded to 64: a narrow output is the next layer's K operand
+            pk[name + ".weight"] = pack_conv3x3(w, cop, pad_to(w.shape[1], 64))
             bias = torch.zeros(cop, device=dev)
             if b is not None:
                 bias[: b.shape[0]] = b
@@ -275,44 +212,12 @@ class _DCAEModule(_ImageVAEModule):
                     conv(stem, w, None)
             else:
                 conv(stem, w, f[stem + ".bias"])
-        self._packed, self._sig = pk, sig
+        return pk
 
     # ------------------------------------------------------------------ building blocks (channels-last [F][H][W][C])
-    def _par(self, name: str) -> torch.Tensor:
-        return self._tensors_cache[name]
-
-    def _begin(self) -> None:
-        self._sync()
-        self._tensors_cache = {n: t.detach() for n, t in self._tensors().items()}
-
     def _conv3(self, xb: torch.Tensor, name: str, resid: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Conv2d(k 3, s 1, p 1) on a bf16 [F][H][W][Ci] operand -> fp32 [F][H][W][pad64(Co)] (+ resid)"""
-        wp, bias = self._packed[name + ".weight"], self._packed[name + ".bias"]
-        f, h, w, ci = xb.shape
-        out = torch.empty(f, h, w, wp.shape[0], device=xb.device)
-        capi.check(capi.lib.dfot_op_conv3t_f32(_P(xb), _P(wp), _P(bias), _P(resid), _P(out), f, 1, h, w, ci, wp.shape[0], 1, 1, 1, _S()))
-        return out
-
-    def _gemm(self, a: torch.Tensor, w: torch.Tensor, rows1: int, bias: Optional[torch.Tensor] = None, silu_bf16: bool = False) -> torch.Tensor:
-        """a bf16 [M][K] w^T (+ bias) -> fp32 [M][N], or SiLU(.) as bf16 (the GEMM's bf16 epilogue with act = 2).  Whether K is split
-        inside the workgroup (the one tile form with another summation order: few tiles and K >= 2048, conv_point at 512 channels and
-        up) is decided from ONE frame's padded rows, so a frame's bits do not depend on the batch."""
-        m, (n, k) = a.shape[0], w.shape
-        out = torch.empty(m, n, dtype=BF if silu_bf16 else torch.float32, device=a.device)
-        ks2 = k >= 2048 and (_pad_to(rows1, 128) // 128) * (-(-n // 128)) <= 256
-        if not silu_bf16 and not ks2:   # here the shape-picked form never splits K
-            capi.check(capi.lib.dfot_op_gemm_f32(_P(a), k, _P(w), _P(bias), None, _P(out), n, m, n, k, _S()))
-            return out
-        d = capi.GemmDesc()
-        d.qscale, d.eps, d.ksplit, d.variant = 1.0, 1e-6, 1, (_GEMM_KS2 if ks2 else -1)
-        d.A, d.lda, d.W, d.M, d.N, d.K = a.data_ptr(), k, w.data_ptr(), m, n, k
-        d.bias, d.ldo = (bias.data_ptr() if bias is not None else None), n
-        if silu_bf16:
-            d.epi, d.act, d.out_bf16 = _E_BF16, _ACT_SILU, out.data_ptr()
-        else:
-            d.out_f32 = out.data_ptr()
-        capi.check(capi.lib.dfot_op_gemm_ex(C.byref(d), _S()))
-        return out
+        return conv3x3(xb, self._packed[name + ".weight"], self._packed[name + ".bias"], resid)
 
     def _rms(self, x: torch.Tensor, name: str, resid: Optional[torch.Tensor] = None, f32: bool = True, bf16: bool = False, relu: bool = False):
         """channel RMSNorm (weight, bias, eps 1e-5) (+ resid) (ReLU) -> (fp32 or None, bf16 or None)"""
@@ -340,14 +245,14 @@ class _DCAEModule(_ImageVAEModule):
         capi.check(capi.lib.dfot_op_gemm_bf16(_P(hb), c, _P(self._packed[name + ".attn.qkv"]), None, _P(qkv), 3 * c, m, 3 * c, c, _S()))
         o = torch.empty(m, c, dtype=BF, device=h.device)
         capi.check(capi.lib.dfot_op_dcae_linear_attention(_P(qkv), 3 * c, _P(o), c, f, n, c // 32, _S()))
-        u = self._gemm(o, self._packed[name + ".attn.to_out.weight"], n)
+        u = gemm(o, self._packed[name + ".attn.to_out.weight"], n)
         h1, h1b = self._rms(u.view(f, hh, ww, c), name + ".attn.norm_out", resid=h, bf16=True)
         mb = name + ".conv_out"
-        t = self._gemm(h1b.view(m, c), self._packed[mb + ".conv_inverted.weight"], n, self._packed[mb + ".conv_inverted.bias"], silu_bf16=True)
+        t = gemm(h1b.view(m, c), self._packed[mb + ".conv_inverted.weight"], n, self._packed[mb + ".conv_inverted.bias"], silu_bf16=True)
         gl = torch.empty(m, 4 * c, dtype=BF, device=h.device)
         capi.check(capi.lib.dfot_op_dcae_dw_glu(_P(t), _P(self._packed[mb + ".conv_depth.weight"]), _P(self._packed[mb + ".conv_depth.bias"]), _P(gl),
                                                 f, hh, ww, 4 * c, _S()))
-        u = self._gemm(gl, self._packed[mb + ".conv_point.weight"], n)
+        u = gemm(gl, self._packed[mb + ".conv_point.weight"], n)
         return self._rms(u.view(f, hh, ww, c), mb + ".norm", resid=h1)[0]
 
     def _block(self, h: torch.Tensor, name: str, kind: str, norm: str, act: str) -> torch.Tensor:
@@ -403,13 +308,13 @@ class DCAEEncoder(_DCAEModule):
                                                        c["encoder_layers_per_block"], c["encoder_qkv_multiscales"], ("rms_norm",) * n, ("silu",) * n,
                                                        int(c["attention_head_dim"]), self.latent, int(c["in_channels"]))
         self.s_factor = 2 ** (n - 1)
-        self._spec_conv("encoder.conv_in.conv", 3, self.ch[1] // 4, 3)
+        self._spec_conv("encoder.conv_in.conv", 3, self.ch[1] // 4)
         for i in range(n):
             for j in range(self.layers[i]):
                 self._spec_block(f"encoder.down_blocks.{i}.{j}", self.types[i], self.ch[i], "rms_norm")
             if i < n - 1 and self.layers[i] > 0:
-                self._spec_conv(f"encoder.down_blocks.{i}.{self.layers[i]}.conv", self.ch[i], self.ch[i + 1] // 4, 3)
-        self._spec_conv("encoder.conv_out", self.ch[-1], self.latent, 3)
+                self._spec_conv(f"encoder.down_blocks.{i}.{self.layers[i]}.conv", self.ch[i], self.ch[i + 1] // 4)
+        self._spec_conv("encoder.conv_out", self.ch[-1], self.latent)
         self._register()
 
     def _check(self, x: torch.Tensor) -> int:
@@ -429,10 +334,10 @@ class DCAEEncoder(_DCAEModule):
 
     def _latents(self, x: torch.Tensor, b: int, t: int, strides: Tuple[int, ...], scale: float, shift: float, need: int) -> torch.Tensor:
         """frames (b x t of them, element strides (b, c, t, h, w)), scale * x + shift -> latents fp32 (b * t, latent, h', w')"""
-        self._begin()
+        self._sync()
         h, w = x.shape[-2:]
         sb, sc, st, sh, sw = strides
-        f, fp = b * t, _pad_to(b * t, need)
+        f, fp = b * t, pad_to(b * t, need)
         xp = torch.zeros(fp, h, w, 64, dtype=BF, device=x.device)    # frames past f: the zero padding up to whole GEMM tiles
         capi.check(capi.lib.dfot_op_vae_pixels(C.c_void_p(x.data_ptr()), sb, sc, st, sh, sw, scale, shift, _P(xp), b, t, h, w, _S()))
         n = len(self.ch)
@@ -468,16 +373,16 @@ class DCAEDecoder(_DCAEModule):
             c["decoder_qkv_multiscales"], c["decoder_norm_types"], c["decoder_act_fns"], int(c["attention_head_dim"]), self.latent,
             int(c["in_channels"]))
         self.s_factor = 2 ** (n - 1)
-        self._spec_conv("decoder.conv_in", self.latent, self.ch[-1], 3)
+        self._spec_conv("decoder.conv_in", self.latent, self.ch[-1])
         for i in range(n):          # the reference inserts the stages at the front of a list: up_blocks.0 registers first
             j0 = 0
             if i < n - 1 and self.layers[i] > 0:
-                self._spec_conv(f"decoder.up_blocks.{i}.0.conv", self.ch[i + 1], 4 * self.ch[i], 3)
+                self._spec_conv(f"decoder.up_blocks.{i}.0.conv", self.ch[i + 1], 4 * self.ch[i])
                 j0 = 1
             for j in range(self.layers[i]):
                 self._spec_block(f"decoder.up_blocks.{i}.{j0 + j}", self.types[i], self.ch[i], self.norms[i])
         self._specs += [("decoder.norm_out.weight", (self.ch[1],)), ("decoder.norm_out.bias", (self.ch[1],))]
-        self._spec_conv("decoder.conv_out.conv", self.ch[1], 12, 3)
+        self._spec_conv("decoder.conv_out.conv", self.ch[1], 12)
         self._register()
 
     def decode(self, z: torch.Tensor) -> torch.Tensor:
@@ -492,9 +397,9 @@ class DCAEDecoder(_DCAEModule):
         dev = next(self.parameters()).device
         capi.require_device(dev, z=z)
         with torch.no_grad():
-            self._begin()
+            self._sync()
             n = len(self.ch)
-            zc = torch.zeros(_pad_to(f, need), h, w, 64, device=dev)     # frames past f: the zero padding up to whole GEMM tiles
+            zc = torch.zeros(pad_to(f, need), h, w, 64, device=dev)     # frames past f: the zero padding up to whole GEMM tiles
             zc[:f, ..., :cz] = z.detach().float().permute(0, 2, 3, 1)
             hcur = self._up(self._conv3(self._bf(zc), "decoder.conv_in"), zc, cz, self.ch[-1], 1)
             for i in reversed(range(n)):
@@ -528,32 +433,17 @@ def decode_dcae_latents(vae: DCAEDecoder, latents: torch.Tensor, vae_batch_size:
     """``BaseVideoAlgo._decode`` for a ``MyAutoencoderDC`` (base_pytorch_video_algo.py:597-604): latents in the sampler's ``b t c h w``
     layout, chunks of ``vae.batch_size`` videos whose frames go to the batch, ``decode(y) * 0.5 + 0.5``, result back in ``b t c h w``.
     Like the reference, ``scaling_factor`` is not applied.  Frames are independent, so the chunking does not change a bit."""
-    if shape != "b t c h w":
-        raise ValueError("only the 'b t c h w' layout of the sampling path is supported")
-    if latents.ndim != 5:
-        raise ValueError(f"latents have shape {tuple(latents.shape)}, expected (B, T, C, h, w)")
-    outs = []
-    for ch in _chunks(latents, vae_batch_size):
-        b, t = ch.shape[:2]
-        y = vae.decode(ch.reshape(b * t, *ch.shape[2:])) * 0.5 + 0.5
-        outs.append(y.reshape(b, t, *y.shape[1:]))
-    return torch.cat(outs, 0)
+    return map_frame_chunks(lambda ch, row: vae.decode(flat_frames(ch)) * 0.5 + 0.5, latents, vae_batch_size, shape, "latents", "(B, T, C, h, w)")
 
 
 def encode_dcae_frames(vae: DCAEEncoder, videos: torch.Tensor, vae_batch_size: int = 2, shape: str = "b t c h w") -> torch.Tensor:
     """``BaseVideoAlgo._encode`` for a ``MyAutoencoderDC`` (base_pytorch_video_algo.py:588-596): frames in [0, 1] in the ``b t c h w``
     layout, chunks of ``vae.batch_size`` videos whose frames go to the batch, ``encode(2 y - 1)`` (fused into the pixel pack), latents
     back in ``b t c h w``.  Deterministic; ``scaling_factor`` is not applied."""
-    if shape != "b t c h w":
-        raise ValueError("only the 'b t c h w' layout of the training / sampling path is supported")
-    if videos.ndim != 5:
-        raise ValueError(f"videos have shape {tuple(videos.shape)}, expected (B, T, 3, H, W)")
-    outs = []
-    for ch in _chunks(videos, vae_batch_size):
+    def encode_chunk(ch: torch.Tensor, row: int) -> torch.Tensor:
         need = vae._check(ch)
         b, t = ch.shape[:2]
         sb, st, sc, sh, sw = ch.stride()
         with torch.no_grad():
-            z = vae._latents(ch.detach(), b, t, (sb, sc, st, sh, sw), 2.0, -1.0, need)
-        outs.append(z.reshape(b, t, *z.shape[1:]))
-    return torch.cat(outs, 0)
+            return vae._latents(ch.detach(), b, t, (sb, sc, st, sh, sw), 2.0, -1.0, need)
+    return map_frame_chunks(encode_chunk, videos, vae_batch_size, shape, "videos", "(B, T, 3, H, W)", "training / sampling")

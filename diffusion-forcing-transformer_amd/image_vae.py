@@ -32,7 +32,8 @@ from typing import Dict, List, Mapping, Optional, Sequence, Tuple
 import torch
 
 from . import capi
-from .vae import BF, _P, _S, _VideoVAEModule, _channel_vector, _pad_to
+from .codec_common import (BF, _P, _S, CodecModule, channel_vector, conv3x3, flat_frames, gn_res_block, map_frame_chunks, pack_1x1, pack_conv3x3,
+                           pack_conv_layers, pad_to, refuse_layout, upconv3x3)
 
 _WIDTHS = (128, 256, 512, 1024)
 
@@ -59,9 +60,14 @@ def _refuse(kind: str, attn_resolutions, use_linear_attn, attn_type, resamp_with
         raise NotImplementedError(f"{kind}: resamp_with_conv=False is not supported")
 
 
-class _ImageVAEModule(_VideoVAEModule):
-    """What the ImageVAE encoder and decoder share on top of the VideoVAE helpers (parameter registration, packing on weight change,
-    GroupNorm, ResnetBlock, strict loading): 2-D weight packing, the convolution dispatch and the fused mid attention."""
+class _ImageVAEModule(CodecModule):
+    """What the ImageVAE encoder and decoder share on top of the codec base: 2-D weight packing, the convolution dispatch, the GroupNorm
+    ResnetBlock, the fused mid attention and the diffusers key map."""
+
+    _res = gn_res_block
+
+    def _pack_weights(self, f: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+        return pack_conv_layers(f, self._pack)
 
     def _spec_conv(self, name: str, ci: int, co: int, k: int, kind: str = "s1") -> None:
         self._kind[name] = kind if k == 3 else "1x1"
@@ -89,16 +95,8 @@ class _ImageVAEModule(_VideoVAEModule):
         """[co][ci][k][k] fp32 -> bf16 [cop][9 * cip] (tap-major, dfot_op_pack_conv3) or [cop][cip] for 1x1; both channel counts padded
         to 64, so that a narrow output (the latent) is the next layer's K operand as it stands"""
         co, ci, kh, kw = w.shape
-        cip, cop = _pad_to(ci, 64), _pad_to(co, 64)
-        if (kh, kw) == (1, 1):
-            m = torch.zeros(cop, cip, device=w.device)
-            m[:co, :ci] = w.reshape(co, ci)
-            return m.to(BF).contiguous(), cop
-        w2 = torch.zeros(cop, cip, 3, 3, device=w.device)
-        w2[:co, :ci] = w
-        out = torch.empty(cop, 9 * cip, dtype=BF, device=w.device)
-        capi.check(capi.lib.dfot_op_pack_conv3(_P(w2.contiguous()), _P(out), cop, cip, 0, _S()))
-        return out, cop
+        cip, cop = pad_to(ci, 64), pad_to(co, 64)
+        return (pack_1x1 if (kh, kw) == (1, 1) else pack_conv3x3)(w, cop, cip), cop
 
     def _conv(self, x: torch.Tensor, name: str, resid: Optional[torch.Tensor] = None) -> torch.Tensor:
         """one convolution on a bf16 [F][H][W][Ci] operand -> fp32 [F][H'][W'][Co] (+ resid where the layer has one)"""
@@ -109,14 +107,12 @@ class _ImageVAEModule(_VideoVAEModule):
             out = torch.empty(f, h, w, co, device=x.device)
             capi.check(capi.lib.dfot_op_gemm_f32(_P(x), ci, _P(wp), _P(bias), _P(resid), _P(out), co, f * h * w, co, ci, _S()))
         elif kind == "s1":      # Conv2d(k 3, s 1, p 1) per frame: the strided entry with one temporal tap and stride 1
-            out = torch.empty(f, h, w, co, device=x.device)
-            capi.check(capi.lib.dfot_op_conv3t_f32(_P(x), _P(wp), _P(bias), _P(resid), _P(out), f, 1, h, w, ci, co, 1, 1, 1, _S()))
+            out = conv3x3(x, wp, bias, resid)
         elif kind == "down":    # Downsample: pad (0, 1, 0, 1) + Conv2d(k 3, s 2)
             out = torch.empty(f, h // 2, w // 2, co, device=x.device)
             capi.check(capi.lib.dfot_op_conv3x3_s2_f32(_P(x), _P(wp), _P(bias), _P(out), f, h, w, ci, co, _S()))
         else:                   # Upsample: nearest 2x fused into the gather of Conv2d(k 3, s 1, p 1)
-            out = torch.empty(f, 2 * h, 2 * w, co, device=x.device)
-            capi.check(capi.lib.dfot_op_upconv3x3_f32(_P(x), _P(wp), _P(bias), _P(out), f, h, w, ci, co, _S()))
+            out = upconv3x3(x, wp, bias)
         return out
 
     def _attn(self, x: torch.Tensor, name: str, b: int) -> torch.Tensor:
@@ -147,7 +143,7 @@ class _ImageVAEModule(_VideoVAEModule):
         need = 128 // math.gcd(128, h * w)
         if frames % need:
             raise ValueError(f"{what}: {frames} frames of {h}x{w} at the coarsest level are {frames * h * w} GEMM rows, not whole 128-row tiles; "
-                             f"{_pad_to(frames, need)} frames would work (a multiple of {need})")
+                             f"{pad_to(frames, need)} frames would work (a multiple of {need})")
 
 
 class ImageVAEDecoder(_ImageVAEModule):
@@ -472,25 +468,12 @@ def load_diffusers_checkpoint(path: str, config: Optional[Mapping] = None) -> Tu
     return dd, diffusers_to_reference_keys(load_file(path), len(dd["ch_mult"]))
 
 
-def _chunks(x: torch.Tensor, vae_batch_size: int):
-    return torch.chunk(x, (x.shape[0] + vae_batch_size - 1) // vae_batch_size, 0)
-
-
 @torch.no_grad()
 def decode_image_latents(vae: ImageVAEDecoder, latents: torch.Tensor, vae_batch_size: int = 2, shape: str = "b t c h w") -> torch.Tensor:
     """``BaseVideoAlgo._decode`` for an ImageVAE (base_pytorch_video_algo.py:553-629): latents in the sampler's ``b t c h w`` layout, chunks of
     ``vae.batch_size`` videos whose frames go to the batch (``(b t) c h w``), ``decode(y) * 0.5 + 0.5``, result back in ``b t c h w`` (frames
     in [0, 1]).  Frames are independent, so the chunking does not change a bit of the result."""
-    if shape != "b t c h w":
-        raise ValueError("only the 'b t c h w' layout of the sampling path is supported")
-    if latents.ndim != 5:
-        raise ValueError(f"latents have shape {tuple(latents.shape)}, expected (B, T, C, h, w)")
-    outs = []
-    for ch in _chunks(latents, vae_batch_size):
-        b, t = ch.shape[:2]
-        y = vae.decode(ch.reshape(b * t, *ch.shape[2:])) * 0.5 + 0.5
-        outs.append(y.reshape(b, t, *y.shape[1:]))
-    return torch.cat(outs, 0)
+    return map_frame_chunks(lambda ch, row: vae.decode(flat_frames(ch)) * 0.5 + 0.5, latents, vae_batch_size, shape, "latents", "(B, T, C, h, w)")
 
 
 @torch.no_grad()
@@ -502,18 +485,16 @@ def encode_image_frames(vae: ImageVAEEncoder, videos: torch.Tensor, vae_batch_si
     ``b t c h w``; with data_mean / data_std also ``_normalize_x`` (:491-496), fused into the posterior kernel.  ``noise`` (b t c h w, like
     the output) replaces the draws; otherwise each chunk draws ``randn`` of its ((b t), c, h, w) latent shape from ``generator``, as the
     reference does per chunk."""
-    if shape != "b t c h w":
-        raise ValueError("only the 'b t c h w' layout of the training / sampling path is supported")
-    if videos.ndim != 5:
-        raise ValueError(f"videos have shape {tuple(videos.shape)}, expected (B, T, 3, H, W)")
+    layout = (shape, "videos", "(B, T, 3, H, W)", "training / sampling")
+    refuse_layout(videos, *layout)          # the layout refusals come before those of the other arguments
     dev, zc = videos.device, vae.embed
-    dm, ds = _channel_vector(data_mean, zc, dev, "data_mean"), _channel_vector(data_std, zc, dev, "data_std")
+    dm, ds = channel_vector(data_mean, zc, dev, "data_mean"), channel_vector(data_std, zc, dev, "data_std")
     if (dm is None) != (ds is None):
         raise ValueError("data_mean and data_std go together")
     if noise is not None and noise.shape[0] != videos.shape[0]:
         raise ValueError(f"noise has {noise.shape[0]} videos, the input {videos.shape[0]}")
-    outs, row = [], 0
-    for ch in _chunks(videos, vae_batch_size):
+
+    def encode_chunk(ch: torch.Tensor, row: int) -> torch.Tensor:
         vae._check(ch)
         b, t = ch.shape[:2]
         sb, st, sc, sh, sw = ch.stride()
@@ -527,6 +508,5 @@ def encode_image_frames(vae: ImageVAEEncoder, videos: torch.Tensor, vae_batch_si
                     raise ValueError(f"noise has shape {tuple(noise.shape)}, expected (B, {t}, {zc}, {lshape[3]}, {lshape[4]})")
             else:
                 eps = torch.randn(tuple(post.mean.shape), generator=generator, device=generator.device if generator is not None else dev).to(dev)
-        outs.append(post.latents(eps, dm, ds).reshape(lshape))
-        row += b
-    return torch.cat(outs, 0)
+        return post.latents(eps, dm, ds)
+    return map_frame_chunks(encode_chunk, videos, vae_batch_size, *layout)

@@ -35,19 +35,18 @@ every summation order is decided from one frame's shape, so a frame decodes to t
 """
 from __future__ import annotations
 
-import ctypes as C
+import math
 from typing import Dict, List, Mapping, Optional, Tuple
 
 import torch
 
 from . import capi
+from .codec_common import BF, _P, _S, CodecModule, conv3x3, flat_frames, gemm, map_frame_chunks, pack_1x1, pack_conv3x3, pad_to, upconv3x3
 from .image_vae import ImageVAEPosterior
-from .vae import BF, _P, _S, _VideoVAEModule, _pad_to
 
 PRESETS = {"small": (512, 8, 8), "base": (768, 12, 12), "large": (1024, 24, 16)}     # width, layers, heads (head dim 64)
 _PIXEL_UP = ((4, 512, 512), (3, 512, 256), (2, 256, 256), (1, 256, 128), (0, 128, 128))  # (block index, in, out) in run order
-_GEMM_KS2 = 8             # dfot_op_gemm variant: 128x128 tile with K split inside the workgroup
-_ACT_GELU, _ACT_TANH = 0, 1
+_ACT_GELU, _ACT_TANH = 0, 1             # dfot_op_bias_act_bf16
 
 
 def max_sequence_length() -> int:
@@ -55,30 +54,12 @@ def max_sequence_length() -> int:
     return int(capi.lib.dfot_op_mha_packed_max_len())
 
 
-class _TiTokModule(_VideoVAEModule):
-    """What the two ViT halves of ``TiTok_KL`` share: the GEMM / LayerNorm / bias + activation calls and the loop over the
-    ``ResidualAttentionBlock``s.  Subclasses set ``width``, ``layers``, ``heads`` and ``seq`` and fill ``_packed`` in ``_sync``."""
+class _TiTokModule(CodecModule):
+    """What the two ViT halves of ``TiTok_KL`` share on top of the codec base: the LayerNorm / bias + activation calls and the loop over
+    the ``ResidualAttentionBlock``s.  Subclasses set ``width``, ``layers``, ``heads`` and ``seq`` and pack their matrices in
+    ``_pack_weights``.  Every GEMM's K split is decided from ONE frame's padded rows (``codec_common.splits_k``)."""
 
-    def _par(self, name: str) -> torch.Tensor:
-        return self.get_parameter(name).detach()
-
-    def _gemm(self, a: torch.Tensor, wname: str, bias: Optional[torch.Tensor], resid: Optional[torch.Tensor], rows1: int) -> torch.Tensor:
-        """fp32 [M][N] = a bf16 [M][K] w^T (+ bias) (+ resid).  Whether K is split inside the workgroup (the one tile form with another
-        summation order, picked for few tiles and a long K) is decided from ONE frame's padded rows `rows1`, so a frame's bits do not
-        depend on the batch."""
-        w = self._packed[wname]
-        m, (n, k) = a.shape[0], w.shape
-        out = torch.empty(m, n, device=a.device)
-        if k >= 2048 and (_pad_to(rows1, 128) // 128) * (-(-n // 128)) <= 256:
-            d = capi.GemmDesc()
-            d.qscale, d.eps, d.ksplit, d.variant = 1.0, 1e-6, 1, _GEMM_KS2
-            d.A, d.lda, d.W, d.M, d.N, d.K = a.data_ptr(), k, w.data_ptr(), m, n, k
-            d.bias, d.resid = (bias.data_ptr() if bias is not None else None), (resid.data_ptr() if resid is not None else None)
-            d.out_f32, d.ldo = out.data_ptr(), n
-            capi.check(capi.lib.dfot_op_gemm_ex(C.byref(d), _S()))
-        else:   # here the shape-picked form never splits K: a frame's tile count only grows with the batch
-            capi.check(capi.lib.dfot_op_gemm_f32(_P(a), k, _P(w), _P(bias), _P(resid), _P(out), n, m, n, k, _S()))
-        return out
+    _reference_model = "TiTok_KL"
 
     def _ln(self, x: torch.Tensor, name: str, rows: int, gather: Tuple[int, int, int] = (0, 0, 0), out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """LayerNorm(eps 1e-5) of the first `rows` rows -> bf16 GEMM operand (rows past `rows` of `out` stay as they are: zero)"""
@@ -98,20 +79,20 @@ class _TiTokModule(_VideoVAEModule):
         sequences of ``seq`` rows back to back"""
         w, L = self.width, self.seq
         rows, rows1, mp, dev = f * L, L, x.shape[0], x.device
-        p = self._par
+        p, pk = self._par, self._packed
         h = torch.zeros(mp, w, dtype=BF, device=dev)          # LayerNorm output: pad rows stay zero
         o = torch.zeros(mp, w, dtype=BF, device=dev)          # attention output: rows >= F * L are never written
         qkv = torch.empty(mp, 3 * w, dtype=BF, device=dev)
         for i in range(self.layers):
             r = f"{prefix}.{i}"
             self._ln(x, r + ".ln_1", rows, out=h)
-            capi.check(capi.lib.dfot_op_gemm_bf16(_P(h), w, _P(self._packed[r + ".attn.in_proj_weight"]), _P(p(r + ".attn.in_proj_bias")), _P(qkv), 3 * w,
+            capi.check(capi.lib.dfot_op_gemm_bf16(_P(h), w, _P(pk[r + ".attn.in_proj_weight"]), _P(p(r + ".attn.in_proj_bias")), _P(qkv), 3 * w,
                                                   mp, 3 * w, w, _S()))
             capi.check(capi.lib.dfot_op_mha_packed(_P(qkv), 3 * w, _P(o), f, L, self.heads, _S()))
-            x = self._gemm(o, r + ".attn.out_proj.weight", p(r + ".attn.out_proj.bias"), x, rows1)
+            x = gemm(o, pk[r + ".attn.out_proj.weight"], rows1, p(r + ".attn.out_proj.bias"), x)
             self._ln(x, r + ".ln_2", rows, out=h)
-            u = self._gemm(h, r + ".mlp.c_fc.weight", None, None, rows1)
-            x = self._gemm(self._bias_act(u, p(r + ".mlp.c_fc.bias"), _ACT_GELU), r + ".mlp.c_proj.weight", p(r + ".mlp.c_proj.bias"), x, rows1)
+            u = gemm(h, pk[r + ".mlp.c_fc.weight"], rows1)
+            x = gemm(self._bias_act(u, p(r + ".mlp.c_fc.bias"), _ACT_GELU), pk[r + ".mlp.c_proj.weight"], rows1, p(r + ".mlp.c_proj.bias"), x)
         return x
 
 
@@ -173,35 +154,23 @@ class TiTokDecoder(_TiTokModule):
         self._register()
 
     # ------------------------------------------------------------------ weights -> bf16 GEMM operands
-    def _sync(self) -> None:
-        """every matrix weight (Linear [out][in], in_proj_weight, 1x1 and 3x3 convolutions) packed to its bf16 GEMM operand, once per weight
-        change; biases, norm weights and the embeddings are read in fp32 as they stand"""
-        params = dict(self.named_parameters())
-        sig = tuple((t.data_ptr(), t._version) for t in params.values())
-        if sig == self._sig:
-            return
+    def _pack_weights(self, f: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+        """every matrix weight (Linear [out][in], in_proj_weight, 1x1 and 3x3 convolutions) packed to its bf16 GEMM operand; biases, norm
+        weights and the embeddings are read in fp32 as they stand"""
         pk: Dict[str, torch.Tensor] = {}
-        for name, t in params.items():
-            if not t.is_cuda:
-                raise RuntimeError(f"parameter {name} is on {t.device}; move the module to the GPU first (there is no CPU path)")
-            w = t.detach().float()
+        for name, w in f.items():
             if name.endswith("weight") and w.ndim == 2 and name != "decoder.decoder_embed.weight":
                 pk[name] = w.to(BF).contiguous()
             elif w.ndim == 4 and w.shape[2:] == (1, 1):
-                pk[name] = w.reshape(w.shape[0], w.shape[1]).to(BF).contiguous()
-            elif w.ndim == 4:
+                pk[name] = pack_1x1(w, *w.shape[:2])
+            elif w.ndim == 4:       # 3x3: output channels padded to 64, input channels as they are
                 co, ci = w.shape[:2]
-                cop = _pad_to(co, 64)
-                w2 = torch.zeros(cop, ci, 3, 3, device=w.device)
-                w2[:co] = w
-                out = torch.empty(cop, 9 * ci, dtype=BF, device=w.device)
-                capi.check(capi.lib.dfot_op_pack_conv3(_P(w2.contiguous()), _P(out), cop, ci, 0, _S()))
-                pk[name] = out
-                if name[:-6] + "bias" in params:
-                    b = torch.zeros(cop, device=w.device)
-                    b[:co] = params[name[:-6] + "bias"].detach().float()
+                pk[name] = pack_conv3x3(w, pad_to(co, 64), ci)
+                if name[:-6] + "bias" in f:
+                    b = torch.zeros(pad_to(co, 64), device=w.device)
+                    b[:co] = f[name[:-6] + "bias"]
                     pk[name[:-6] + "bias"] = b
-        self._packed, self._sig = pk, sig
+        return pk
 
     # ------------------------------------------------------------------ building blocks
     def _check(self, z: torch.Tensor) -> torch.device:
@@ -217,15 +186,14 @@ class TiTokDecoder(_TiTokModule):
 
     def _frames_padded(self, f: int) -> int:
         """frames the grid-shaped part runs on: whole 128-row tiles of the coarsest map"""
-        import math
-        return _pad_to(f, 128 // math.gcd(128, self.grid ** 2))
+        return pad_to(f, 128 // math.gcd(128, self.grid ** 2))
 
     def _transformer(self, z: torch.Tensor) -> torch.Tensor:
         """steps 1-3 and the ffn: z (F, token_size, 1, nlat) -> logits fp32 [Fp * grid^2][1024], rows of frames >= F are padding"""
         dev = self._check(z)
         self._sync()
         f, w, L, g2 = z.shape[0], self.width, self.seq, self.grid ** 2
-        mp = _pad_to(f * L, 128)
+        mp = pad_to(f * L, 128)
         p = self._par
         x = torch.zeros(mp, w, device=dev)
         zf = z.detach().float().contiguous()                  # (a local: the op takes a raw pointer)
@@ -238,27 +206,19 @@ class TiTokDecoder(_TiTokModule):
         fp = self._frames_padded(f)
         y = torch.zeros(fp * g2, w, dtype=BF, device=dev)     # ln_post of rows 1 .. grid^2 of every sequence, compact
         self._ln(x, "decoder.ln_post", f * g2, gather=(L, 1, g2), out=y)
-        u = self._gemm(y, "decoder.ffn.0.weight", None, None, g2)
-        return self._gemm(self._bias_act(u, p("decoder.ffn.0.bias"), _ACT_TANH), "decoder.ffn.2.weight", p("decoder.ffn.2.bias"), None, g2)
+        u = gemm(y, self._packed["decoder.ffn.0.weight"], g2)
+        return gemm(self._bias_act(u, p("decoder.ffn.0.bias"), _ACT_TANH), self._packed["decoder.ffn.2.weight"], g2, p("decoder.ffn.2.bias"))
 
     def _pixel_input(self, lg: torch.Tensor) -> torch.Tensor:
         """softmax over the 1024 channels + pixel_quantize_conv: fp32 [rows][1024] -> fp32 [rows][256]"""
         probs = torch.empty(lg.shape, dtype=BF, device=lg.device)
         capi.check(capi.lib.dfot_op_softmax_rows(_P(lg), _P(probs), lg.shape[0], 1024, 1.0, _S()))
-        return self._gemm(probs, "pixel_quantize_conv.weight", self._par("pixel_quantize_conv.bias"), None, self.grid ** 2)
+        return gemm(probs, self._packed["pixel_quantize_conv.weight"], self.grid ** 2, self._par("pixel_quantize_conv.bias"))
 
     def _conv(self, x: torch.Tensor, name: str, resid: Optional[torch.Tensor] = None, up: bool = False) -> torch.Tensor:
         """Conv2dSame(k 3) = Conv2d(k 3, s 1, p 1) on a bf16 [F][H][W][Ci] operand -> fp32 [F][H'][W'][Co]; up: nearest 2x fused in front"""
         wp, bias = self._packed[name + ".weight"], self._packed.get(name + ".bias")
-        f, h, w, ci = x.shape
-        co = wp.shape[0]
-        if up:
-            out = torch.empty(f, 2 * h, 2 * w, co, device=x.device)
-            capi.check(capi.lib.dfot_op_upconv3x3_f32(_P(x), _P(wp), _P(bias), _P(out), f, h, w, ci, co, _S()))
-        else:
-            out = torch.empty(f, h, w, co, device=x.device)
-            capi.check(capi.lib.dfot_op_conv3t_f32(_P(x), _P(wp), _P(bias), _P(resid), _P(out), f, 1, h, w, ci, co, 1, 1, 1, _S()))
-        return out
+        return upconv3x3(x, wp, bias) if up else conv3x3(x, wp, bias, resid)
 
     def _res(self, x: torch.Tensor, name: str, ci: int, co: int, b: int) -> torch.Tensor:
         h = self._conv(self._gn(x, name + ".norm1", True, b), name + ".conv1")
@@ -266,8 +226,8 @@ class TiTokDecoder(_TiTokModule):
             return self._conv(self._gn(h, name + ".norm2", True, b), name + ".conv2", resid=x)
         h = self._conv(self._gn(h, name + ".norm2", True, b), name + ".conv2")
         f, hh, ww, _ = h.shape                                # h + nin_shortcut(h): the block's input is dropped
-        return self._gemm(self._bf(h).reshape(f * hh * ww, co), name + ".nin_shortcut.weight", None, h.reshape(f * hh * ww, co),
-                          hh * ww).reshape(f, hh, ww, co)
+        return gemm(self._bf(h).reshape(f * hh * ww, co), self._packed[name + ".nin_shortcut.weight"], hh * ww,
+                    resid=h.reshape(f * hh * ww, co)).reshape(f, hh, ww, co)
 
     def _pixel_decoder(self, lat: torch.Tensor) -> torch.Tensor:
         """maskgit_vqgan.Decoder on fp32 channels-last [Fp][g][g][256] -> fp32 [Fp][16 g][16 g][64] (channels >= 3 are 0)"""
@@ -322,12 +282,7 @@ class TiTokDecoder(_TiTokModule):
     def load_reference_state_dict(self, state_dict: Mapping[str, torch.Tensor]) -> List[str]:
         """keys of a reference ``TiTok_KL`` (optionally ``vae.``-prefixed): the decoder's own keys are loaded strictly (every one present,
         with its shape); the encoder's (``encoder.*``, ``latent_tokens``) are ignored and returned.  Any other key raises ``ValueError``."""
-        own = set(self._names)
-        for k in state_dict:
-            n = k[4:] if k.startswith("vae.") else k
-            if n not in own and not (n.startswith("encoder.") or n == "latent_tokens"):
-                raise ValueError(f"unexpected key in a TiTok_KL state dict: {k}")
-        return super().load_reference_state_dict(dict(state_dict))
+        return super().load_reference_state_dict(state_dict, lambda n: n.startswith("encoder.") or n == "latent_tokens")
 
 
 class TiTokEncoder(_TiTokModule):
@@ -374,20 +329,11 @@ class TiTokEncoder(_TiTokModule):
         self._specs = sp
         self._register()
 
-    def _sync(self) -> None:
+    def _pack_weights(self, f: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
         """the Linear weights and ``patch_embed.weight`` (flattened (C, 3 * 16 * 16): the column order dfot_op_titok_patch_rows writes) packed
-        to bf16 GEMM operands, once per weight change; ``conv_out.weight``, biases, norm weights and the embeddings are read in fp32"""
-        params = dict(self.named_parameters())
-        sig = tuple((t.data_ptr(), t._version) for t in params.values())
-        if sig == self._sig:
-            return
-        pk: Dict[str, torch.Tensor] = {}
-        for name, t in params.items():
-            if not t.is_cuda:
-                raise RuntimeError(f"parameter {name} is on {t.device}; move the module to the GPU first (there is no CPU path)")
-            if name == "encoder.patch_embed.weight" or (name.endswith("weight") and t.ndim == 2):
-                pk[name] = t.detach().float().reshape(t.shape[0], -1).to(BF).contiguous()
-        self._packed, self._sig = pk, sig
+        to bf16 GEMM operands; ``conv_out.weight``, biases, norm weights and the embeddings are read in fp32"""
+        return {name: w.reshape(w.shape[0], -1).to(BF).contiguous() for name, w in f.items()
+                if name == "encoder.patch_embed.weight" or (name.endswith("weight") and w.ndim == 2)}
 
     def _check(self, x: torch.Tensor) -> torch.device:
         s = self.image_size
@@ -408,10 +354,10 @@ class TiTokEncoder(_TiTokModule):
         f, w, L, g2, oc = x.shape[0], self.width, self.seq, self.grid ** 2, 2 * self.token_size
         p = self._par
         xf = x.detach().float().contiguous()                  # (a local: the op takes a raw pointer)
-        a = torch.zeros(_pad_to(f * g2, 128), 768, dtype=BF, device=dev)     # pad rows stay zero
+        a = torch.zeros(pad_to(f * g2, 128), 768, dtype=BF, device=dev)     # pad rows stay zero
         capi.check(capi.lib.dfot_op_titok_patch_rows(_P(xf), _P(a), f, self.image_size, _S()))
-        patches = self._gemm(a, "encoder.patch_embed.weight", p("encoder.patch_embed.bias"), None, g2)   # K = 768: never split
-        tok = torch.zeros(_pad_to(f * L, 128), w, device=dev)
+        patches = gemm(a, self._packed["encoder.patch_embed.weight"], g2, p("encoder.patch_embed.bias"))   # K = 768: never split
+        tok = torch.zeros(pad_to(f * L, 128), w, device=dev)
         capi.check(capi.lib.dfot_op_titok_enc_tokens(
             _P(patches), w, _P(p("encoder.class_embedding")), _P(p("encoder.positional_embedding")), _P(p("latent_tokens")),
             _P(p("encoder.latent_token_positional_embedding")), _P(p("encoder.ln_pre.weight")), _P(p("encoder.ln_pre.bias")), 1e-5, _P(tok), f, g2,
@@ -446,12 +392,7 @@ class TiTokEncoder(_TiTokModule):
         """keys of a reference ``TiTok_KL`` (optionally ``vae.``-prefixed): the encoder's own keys (``encoder.*``, ``latent_tokens``) are
         loaded strictly (every one present, with its shape); the decoder's (``decoder.*``, ``pixel_quantize_conv.*``, ``pixel_decoder.*``)
         are ignored and returned.  Any other key raises ``ValueError``."""
-        own = set(self._names)
-        for k in state_dict:
-            n = k[4:] if k.startswith("vae.") else k
-            if n not in own and not n.startswith(("decoder.", "pixel_quantize_conv.", "pixel_decoder.")):
-                raise ValueError(f"unexpected key in a TiTok_KL state dict: {k}")
-        return super().load_reference_state_dict(dict(state_dict))
+        return super().load_reference_state_dict(state_dict, lambda n: n.startswith(("decoder.", "pixel_quantize_conv.", "pixel_decoder.")))
 
 
 def load_titok_checkpoint(path: str) -> Dict[str, torch.Tensor]:
@@ -467,16 +408,7 @@ def decode_titok_latents(vae: TiTokDecoder, latents: torch.Tensor, vae_batch_siz
     """``BaseVideoAlgo._decode`` for a TiTok_KL (base_pytorch_video_algo.py:553-629): latents in the sampler's ``b t c h w`` layout
     (``(B, T, 4, 1, 32)``), chunks of ``vae.batch_size`` videos whose frames go to the batch, ``decode(y)`` as it is (no rescaling, unlike the
     ImageVAE branch), result ``(B, T, 3, H, W)``.  Frames are independent, so the chunking does not change a bit of the result."""
-    if shape != "b t c h w":
-        raise ValueError("only the 'b t c h w' layout of the sampling path is supported")
-    if latents.ndim != 5:
-        raise ValueError(f"latents have shape {tuple(latents.shape)}, expected (B, T, C, 1, tokens)")
-    outs = []
-    for ch in torch.chunk(latents, (latents.shape[0] + vae_batch_size - 1) // vae_batch_size, 0):
-        b, t = ch.shape[:2]
-        y = vae.decode(ch.reshape(b * t, *ch.shape[2:]))
-        outs.append(y.reshape(b, t, *y.shape[1:]))
-    return torch.cat(outs, 0)
+    return map_frame_chunks(lambda ch, row: vae.decode(flat_frames(ch)), latents, vae_batch_size, shape, "latents", "(B, T, C, 1, tokens)")
 
 
 @torch.no_grad()
@@ -485,13 +417,4 @@ def encode_titok_frames(vae: TiTokEncoder, videos: torch.Tensor, vae_batch_size:
     ``Titok_KLPreprocessor._encode_videos``, tiktok_kl/preprocessor.py:124-132): videos ``(B, T, 3, S, S)``, chunks of ``vae.batch_size``
     videos whose frames go to the batch, ``encode(y, sample=True)`` -- the posterior's mode -- as it is (no rescaling), result
     ``(B, T, token_size, 1, num_latent_tokens)``.  Frames are independent, so the chunking does not change a bit of the result."""
-    if shape != "b t c h w":
-        raise ValueError("only the 'b t c h w' layout of the sampling path is supported")
-    if videos.ndim != 5:
-        raise ValueError(f"videos have shape {tuple(videos.shape)}, expected (B, T, 3, S, S)")
-    outs = []
-    for ch in torch.chunk(videos, (videos.shape[0] + vae_batch_size - 1) // vae_batch_size, 0):
-        b, t = ch.shape[:2]
-        z = vae.encode(ch.reshape(b * t, *ch.shape[2:]), sample=True)
-        outs.append(z.reshape(b, t, *z.shape[1:]))
-    return torch.cat(outs, 0)
+    return map_frame_chunks(lambda ch, row: vae.encode(flat_frames(ch), sample=True), videos, vae_batch_size, shape, "videos", "(B, T, 3, S, S)")

@@ -22,88 +22,19 @@ import ctypes as C
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
-from torch import nn
 
 from . import capi
-
-BF = torch.bfloat16
-_P = capi.ptr
-_S = capi.stream_ptr
+from .codec_common import BF, _P, _S, CodecModule, channel_vector, chunks, gn_res_block, pack_1x1, pack_conv3x3, pack_conv_layers, pad_to, refuse_layout
 
 
-def _pad_to(n: int, m: int) -> int:
-    return -(-n // m) * m
-
-
-class _VideoVAEModule(nn.Module):
-    """What the VideoVAE encoder and decoder share: parameters registered under the reference's state-dict names, the bf16 GEMM
-    operands packed from them once per weight change, and the GroupNorm / ResnetBlock / AttnBlock3D building blocks on channels-last
+class _VideoVAEModule(CodecModule):
+    """What the VideoVAE encoder and decoder share on top of the codec base: the GroupNorm ResnetBlock and AttnBlock3D on channels-last
     [B][T][H][W][C] activations.  Subclasses list their parameters in ``_specs`` and provide ``_pack`` and ``_conv``."""
 
-    def _register(self) -> None:
-        self._names = [n for n, _ in self._specs]
-        for name, shape in self._specs:
-            *path, leaf = name.split(".")
-            node: nn.Module = self
-            for part in path:
-                if part not in node._modules:
-                    node.add_module(part, nn.Module())
-                node = node._modules[part]
-            node.register_parameter(leaf, nn.Parameter(torch.zeros(shape), requires_grad=False))
-        self._packed: Dict[str, torch.Tensor] = {}
-        self._sig = None
+    _res = gn_res_block
 
-    # ------------------------------------------------------------------ weights -> bf16 GEMM operands
-    def init_random(self, seed: int = 0) -> None:
-        g = torch.Generator().manual_seed(seed)
-        with torch.no_grad():
-            for n, p in self.named_parameters():
-                if n.endswith("bias"):
-                    v = 0.02 * torch.randn(p.shape, generator=g)
-                elif p.ndim == 1:
-                    v = 1.0 + 0.1 * torch.randn(p.shape, generator=g)
-                else:
-                    v = torch.randn(p.shape, generator=g) / (p[0].numel() ** 0.5)
-                p.copy_(v.to(p.device))
-
-    def _sync(self) -> None:
-        params = dict(self.named_parameters())
-        sig = tuple((t.data_ptr(), t._version) for t in params.values())
-        if sig == self._sig:
-            return
-        pk: Dict[str, torch.Tensor] = {}
-        for name, t in params.items():
-            if not t.is_cuda:
-                raise RuntimeError(f"parameter {name} is on {t.device}; move the module to the GPU first (there is no CPU path)")
-            if t.ndim < 4:  # convolution weights only (norm weights and biases are 1-D)
-                continue
-            pk[name], cop = self._pack(name, t.detach().float())
-            b = torch.zeros(cop, device=t.device)
-            b[: t.shape[0]] = params[name[:-6] + "bias"].detach().float()
-            pk[name[:-6] + "bias"] = b
-        self._packed, self._sig = pk, sig
-
-    # ------------------------------------------------------------------ building blocks (channels-last [B][T][H][W][C])
-    def _gn(self, x: torch.Tensor, name: str, silu: bool, b: int) -> torch.Tensor:
-        """GroupNorm(32) with statistics over each of ``b`` equal slices of x: b = videos (over T, H, W) or videos * frames (per frame)"""
-        c = x.shape[-1]
-        pixels = x.numel() // (b * c)
-        out = torch.empty(x.shape, dtype=BF, device=x.device)
-        scratch = torch.empty(int(capi.lib.dfot_op_groupnorm_scratch_floats(b, pixels)), device=x.device)
-        p = dict(self.named_parameters())
-        capi.check(capi.lib.dfot_op_groupnorm(_P(x), _P(p[name + ".weight"].detach()), _P(p[name + ".bias"].detach()), 1e-6, _P(out), _P(scratch), b,
-                                              pixels, c, int(silu), _S()))
-        return out
-
-    def _bf(self, x: torch.Tensor) -> torch.Tensor:
-        out = torch.empty(x.shape, dtype=BF, device=x.device)
-        capi.check(capi.lib.dfot_op_f32_to_bf16(_P(x), _P(out), x.numel(), _S()))
-        return out
-
-    def _res(self, x: torch.Tensor, name: str, ci: int, co: int, b: int) -> torch.Tensor:
-        h = self._conv(self._gn(x, name + ".norm1", True, b), name + ".conv1")
-        sc = x if ci == co else self._conv(self._bf(x), name + ".nin_shortcut")
-        return self._conv(self._gn(h, name + ".norm2", True, b), name + ".conv2", resid=sc)
+    def _pack_weights(self, f: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+        return pack_conv_layers(f, self._pack)
 
     def _attn(self, x: torch.Tensor, name: str, b: int) -> torch.Tensor:
         """AttnBlock3D: per frame, one head over the H*W positions with all C channels"""
@@ -128,26 +59,6 @@ class _VideoVAEModule(nn.Module):
         capi.check(capi.lib.dfot_op_gemm_f32(_P(o), c, _P(self._packed[f"{name}.proj_out.conv.weight"]), _P(self._packed[f"{name}.proj_out.conv.bias"]),
                                              _P(x), _P(out), c, bb * t * n, c, c, _S()))
         return out
-
-    def load_reference_state_dict(self, state_dict: Dict[str, torch.Tensor]) -> List[str]:
-        """keys of a reference VideoVAE (optionally ``vae.``-prefixed as in the Lightning checkpoint, video_vae/model.py:520-527): this
-        module's own keys are loaded, strictly (every one must be present with its shape); every other key is ignored and returned."""
-        own = dict(self.named_parameters())
-        ignored, seen = [], set()
-        with torch.no_grad():
-            for k, v in state_dict.items():
-                n = k[4:] if k.startswith("vae.") else k
-                if n in own:
-                    if tuple(v.shape) != tuple(own[n].shape):
-                        raise ValueError(f"size mismatch for {n}: {tuple(v.shape)} vs {tuple(own[n].shape)}")
-                    own[n].copy_(v)
-                    seen.add(n)
-                else:
-                    ignored.append(k)
-        missing = [n for n in own if n not in seen]
-        if missing:
-            raise ValueError(f"keys not found in the checkpoint: {missing[:5]}{'...' if len(missing) > 5 else ''}")
-        return ignored
 
 
 class VideoVAEDecoder(_VideoVAEModule):
@@ -219,19 +130,11 @@ class VideoVAEDecoder(_VideoVAEModule):
     # ------------------------------------------------------------------ weights -> bf16 GEMM operands
     def _pack(self, name: str, w: torch.Tensor) -> Tuple[torch.Tensor, int]:
         co, ci, kt, kh, kw = w.shape
-        cip, cop = _pad_to(ci, 64), _pad_to(co, 8)
+        cip, cop = pad_to(ci, 64), pad_to(co, 8)
         if (kh, kw) == (1, 1):  # 1x1x1: a Linear [co][ci]
-            m = torch.zeros(cop, cip, device=w.device)
-            m[:co, :ci] = w.view(co, ci)
-            return m.to(BF).contiguous(), cop
-        taps = []  # one packed [co][tap][ci] operand per temporal tap (dfot_op_pack_conv3: [Co][Ci][3][3] fp32 -> [Co][9][Ci] bf16)
-        for dt in range(kt):
-            w2 = torch.zeros(cop, cip, 3, 3, device=w.device)
-            w2[:co, :ci] = w[:, :, dt]
-            out = torch.empty(cop, 9 * cip, dtype=BF, device=w.device)
-            capi.check(capi.lib.dfot_op_pack_conv3(_P(w2.contiguous()), _P(out), cop, cip, 0, _S()))
-            taps.append(out)
-        return torch.stack(taps), cop
+            return pack_1x1(w, cop, cip), cop
+        # one packed [co][tap][ci] operand per temporal tap
+        return torch.stack([pack_conv3x3(w[:, :, dt], cop, cip) for dt in range(kt)]), cop
 
     # ------------------------------------------------------------------ building blocks (channels-last [B][T][H][W][C])
     def _conv(self, x: torch.Tensor, name: str, resid: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -269,12 +172,12 @@ class VideoVAEDecoder(_VideoVAEModule):
         b, cz, t, h, w = z.shape
         if (t * h * w) % 128:
             raise ValueError(f"T*H*W = {t * h * w} must be a multiple of 128 (GEMM row tiles)")
-        cl = torch.zeros(b, t, h, w, _pad_to(cz, 64), device=dev)
+        cl = torch.zeros(b, t, h, w, pad_to(cz, 64), device=dev)
         cl[..., :cz] = z.detach().float().permute(0, 2, 3, 4, 1)
         x = self._bf(cl)
         if self.use_quant:
             y = self._conv(x, "post_quant_conv")                      # [.., pad8(z)] fp32
-            cl = torch.zeros(b, t, h, w, _pad_to(self.z, 64), device=dev)
+            cl = torch.zeros(b, t, h, w, pad_to(self.z, 64), device=dev)
             cl[..., : self.z] = y[..., : self.z]
             x = self._bf(cl)
         hcur = self._conv(x, "decoder.conv_in")
@@ -307,8 +210,7 @@ def decode_latents(vae: VideoVAEDecoder, latents: torch.Tensor, n_frames: int, v
     if shape != "b t c h w":
         raise ValueError("only the 'b t c h w' layout of the sampling path is supported")
     x = latents.permute(0, 2, 1, 3, 4)
-    n_chunks = (x.shape[0] + vae_batch_size - 1) // vae_batch_size
-    outs = [vae.decode(ch, n_frames) * 0.5 + 0.5 for ch in torch.chunk(x, n_chunks, 0)]
+    outs = [vae.decode(ch, n_frames) * 0.5 + 0.5 for ch in chunks(x, vae_batch_size)]
     return torch.cat(outs, 0).permute(0, 2, 1, 3, 4).contiguous()
 
 
@@ -471,19 +373,10 @@ class VideoVAEEncoder(_VideoVAEModule):
         if w.ndim == 4:
             w = w.unsqueeze(2)
         co, ci, kt, kh, kw = w.shape
-        cip, cop = _pad_to(ci, 64), _pad_to(co, 64)
+        cip, cop = pad_to(ci, 64), pad_to(co, 64)
         if (kh, kw) == (1, 1):
-            m = torch.zeros(cop, cip, device=w.device)
-            m[:co, :ci] = w.reshape(co, ci)
-            return m.to(BF).contiguous(), cop
-        taps = []
-        for dt in range(kt):
-            w2 = torch.zeros(cop, cip, 3, 3, device=w.device)
-            w2[:co, :ci] = w[:, :, dt]
-            out = torch.empty(cop, 9 * cip, dtype=BF, device=w.device)
-            capi.check(capi.lib.dfot_op_pack_conv3(_P(w2.contiguous()), _P(out), cop, cip, 0, _S()))
-            taps.append(out)
-        return torch.cat(taps, 1).contiguous(), cop
+            return pack_1x1(w, cop, cip), cop
+        return torch.cat([pack_conv3x3(w[:, :, dt], cop, cip) for dt in range(kt)], 1).contiguous(), cop
 
     def _conv(self, x: torch.Tensor, name: str, resid: Optional[torch.Tensor] = None) -> torch.Tensor:
         """one convolution of the encoder on a bf16 [B][T][H][W][Ci] operand -> fp32 [B][T'][H'][W'][Co] (+ resid)"""
@@ -584,15 +477,6 @@ class VideoVAEEncoder(_VideoVAEModule):
         return VideoVAEPosterior(self._moments(x, self._frames(x, "b c t h w"), 1.0, 0.0), self.moment_ch // 2)
 
 
-def _channel_vector(v, n: int, dev, what: str) -> Optional[torch.Tensor]:
-    if v is None:
-        return None
-    t = torch.as_tensor(v, dtype=torch.float32).reshape(-1).to(dev).contiguous()
-    if t.numel() != n:
-        raise ValueError(f"{what} has {t.numel()} values, expected one per latent channel ({n})")
-    return t
-
-
 @torch.no_grad()
 def encode_videos(vae: VideoVAEEncoder, videos: torch.Tensor, vae_batch_size: int = 2, shape: str = "b t c h w", sample: bool = True,
                   noise: Optional[torch.Tensor] = None, generator: Optional[torch.Generator] = None, data_mean=None, data_std=None) -> torch.Tensor:
@@ -600,21 +484,17 @@ def encode_videos(vae: VideoVAEEncoder, videos: torch.Tensor, vae_batch_size: in
     ``vae.batch_size`` videos, ``encode(2 y - 1).sample()`` (``.mode()`` with sample=False), latents back in ``b t c h w``; with data_mean /
     data_std also ``_normalize_x`` (:491-496), fused into the posterior kernel.  ``noise`` (b t c h w, like the output) replaces the draws;
     otherwise each chunk draws ``randn`` of its (b, c, t, h, w) latent shape from ``generator``, as the reference does per chunk."""
-    if shape != "b t c h w":
-        raise ValueError("only the 'b t c h w' layout of the training / sampling path is supported")
-    if videos.ndim != 5:
-        raise ValueError(f"videos have shape {tuple(videos.shape)}, expected (B, T, 3, H, W)")
+    refuse_layout(videos, shape, "videos", "(B, T, 3, H, W)", "training / sampling")
     vae._check(videos, 1)
     dev = videos.device
     zc = vae.moment_ch // 2
-    dm, ds = _channel_vector(data_mean, zc, dev, "data_mean"), _channel_vector(data_std, zc, dev, "data_std")
+    dm, ds = channel_vector(data_mean, zc, dev, "data_mean"), channel_vector(data_std, zc, dev, "data_std")
     if (dm is None) != (ds is None):
         raise ValueError("data_mean and data_std go together")
     if noise is not None and noise.shape[0] != videos.shape[0]:
         raise ValueError(f"noise has {noise.shape[0]} videos, the input {videos.shape[0]}")
-    n_chunks = (videos.shape[0] + vae_batch_size - 1) // vae_batch_size
     outs, row = [], 0
-    for ch in torch.chunk(videos, n_chunks, 0):
+    for ch in chunks(videos, vae_batch_size):
         post = VideoVAEPosterior(vae._moments(ch, vae._frames(ch, "b t c h w"), 2.0, -1.0), zc)
         eps = None
         if sample:
