@@ -7,6 +7,7 @@ from . import ops  # noqa: F401  (registers the torch.library operators dfot::*)
 from .backbone import UViT3DPose  # noqa: F401
 from .uvit3d_backbone import UViT3D  # noqa: F401
 from .dit_backbone import DiT3D, DifferenceDiT3D  # noqa: F401
+from .dit1d_backbone import DiT1D  # noqa: F401
 from . import attention_maps  # noqa: F401
 from .attention_maps import frame_map, to_hook_layout  # noqa: F401
 from .diffusion import DiffusionConfig, Schedule  # noqa: F401

@@ -54,6 +54,14 @@ class DiTConfigF(DiTConfig):
     _fields_ = [("fourier_noise", C.c_int32)]
 
 
+class DiT1DConfig(C.Structure):
+    """dfot_dit1d_config"""
+    _fields_ = [
+        ("hidden", C.c_int32), ("depth", C.c_int32), ("heads", C.c_int32), ("mlp_hidden", C.c_int32), ("in_channels", C.c_int32),
+        ("tokens_per_frame", C.c_int32), ("max_tokens", C.c_int32), ("timesteps", C.c_int32), ("causal", C.c_int32), ("eps", C.c_float),
+    ]
+
+
 COND_NONE, COND_ACTION, COND_LABEL = 0, 1, 2  # dfot_dit_config.cond_type
 ATTN_MAP_OFF, ATTN_MAP_FRAME, ATTN_MAP_FULL = -1, 0, 1  # DFOT_ATTN_MAP_*
 
@@ -257,6 +265,17 @@ SIGNATURES = {
     "dfot_op_equal_bits": (_I, [_P, _P, _L, _P, _P]),
     "dfot_op_dit_final_layer": (_I, [_P, _P, _P, _L, _L, _P, _P, _P, _I, _I, _I, _F] + [_I] * 6 + [_P]),
     "dfot_op_dit_final_layer_chunked": (_I, [_P, _P, _P, _L, _L, _P, _P, _P, _I, _I, _I, _F] + [_I] * 6 + [_P]),
+    "dfot_op_attention_frame_causal": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "dfot_dit1d_create": (_I, [C.POINTER(DiT1DConfig), C.POINTER(_P)]),
+    "dfot_dit1d_destroy": (_I, [_P]),
+    "dfot_dit1d_num_params": (_I, [_P]),
+    "dfot_dit1d_param_name": (C.c_char_p, [_P, _I]),
+    "dfot_dit1d_param_shape": (_I, [_P, _I, C.POINTER(_L), C.POINTER(_I)]),
+    "dfot_dit1d_load_weight": (_I, [_P, C.c_char_p, _P, C.POINTER(_L), _I, _P]),
+    "dfot_dit1d_finalize": (_I, [_P, _P]),
+    "dfot_dit1d_reserve": (_I, [_P, _I]),
+    "dfot_dit1d_workspace_bytes": (C.c_size_t, [_P]),
+    "dfot_dit1d_forward": (_I, [_P, _P, _P, _P, _I, _I, _P]),
 }
 
 

@@ -141,6 +141,10 @@ int launch_attention_padded(const bf16* q, const bf16* k, const bf16* v, bf16* o
 // attention_seq64.hip: launch_attention_padded's operands and output with n = 64 (sequences shorter than that launcher's 128-row tile):
 // one workgroup per (sequence, head), single-pass softmax.  d % 8 == 0, d <= 128, ldo % 8 == 0
 int launch_attention_seq64(const bf16* q, const bf16* k, const bf16* v, bf16* o, long ldo, int nseq, int heads, int d, hipStream_t stream);
+// attention_frame_causal.hip: launch_attention_padded's operands and output under the block-lower-triangular mask of the DiT1D backbone:
+// query i sees key j iff j / frame_len <= i / frame_len.  frame_len in {16, 32, 64, 128}, n % 128 == 0, d % 8 == 0, d <= 128, ldo % 8 == 0
+int launch_attention_frame_causal(const bf16* q, const bf16* k, const bf16* v, bf16* o, long ldo, int batch, int heads, int n, int frame_len,
+                                  int d, hipStream_t stream);
 // attention_temporal.hip: q, k, v [batch*tokens][heads][patches][dstride]; every (video, head, patch position) attends over its `tokens`
 // frames (1 .. 32); o [(video, frame, patch)][ldo] compact.  patches % 64 == 0, d % 4 == 0
 int launch_attention_temporal(const bf16* q, const bf16* k, const bf16* v, bf16* o, long ldo, int batch, int tokens, int patches, int heads,

@@ -11,13 +11,14 @@ FakeTensor tracing, ``torch.compile`` graphs and stream capture treat the HIP ke
     dfot::dit3d_forward_cond(x, noise_levels, external_cond, external_cond_mask?, model) -> v       [dfot_dit_forward_cond]
     dfot::dit3d_forward_f(x, noise_levels (float), external_cond?, external_cond_mask?, model) -> v [dfot_dit_forward_f]
     dfot::dit3d_forward_f_train(x, noise_levels (float), external_cond?, mask?, params[], model) -> v  [autograd: dfot_dit_train_forward_f]
+    dfot::dit1d_forward(x, noise_levels, model) -> v                                                [dfot_dit1d_forward]
     dfot::ray_encoding(raw_poses, resolution) -> cond                                               [dfot_ray_encode]
     dfot::hg_prepare(x, noise?, qa, qb, nfe) -> x_in                                                [dfot_hg_prepare]
     dfot::ddim_hg_step(x, x_in, v, sa, s1, an, cn, keep, weight, gen, nfe) -> x_next                [dfot_ddim_compose / _tokw]
     dfot::dit_final_layer(x, table, levels, off, weight, bias, eps, c, h, w, patch, form) -> out    [dfot_op_dit_final_layer]
 
 ``model`` is an integer key of a live backbone module (``register_model``): operators take tensors and scalars only.
-The nn.Module mirrors (`UViT3DPose`, `UViT3D`, `DiT3D`, `DifferenceDiT3D`) dispatch their ``forward`` through these operators and the
+The nn.Module mirrors (`UViT3DPose`, `UViT3D`, `DiT3D`, `DifferenceDiT3D`, `DiT1D`) dispatch their ``forward`` through these operators and the
 sampler's ``_process_conditions`` through ``dfot::ray_encoding``; the sampler's step loop calls the same C entry points
 directly (it re-uses its output buffers across steps), ``dfot::hg_prepare`` / ``dfot::ddim_hg_step`` are the functional forms
 for a host that drives the step itself.
@@ -232,6 +233,17 @@ def _(x, noise_levels, external_cond, external_cond_mask, params, model):
 
 
 dit3d_forward_f_train.register_autograd(_dit_cond_train_backward, setup_context=_dit_cond_train_setup_context)
+
+
+# the DiT1D backbone (dit1d_backbone.DiT1D): integer levels, no condition; forward only
+@custom_op("dfot::dit1d_forward", mutates_args=())
+def dit1d_forward(x: Tensor, noise_levels: Tensor, model: int) -> Tensor:
+    return _model(model)._forward_impl(x, noise_levels)
+
+
+@dit1d_forward.register_fake
+def _(x, noise_levels, model):
+    return torch.empty_like(x)
 
 
 @custom_op("dfot::ray_encoding", mutates_args=())

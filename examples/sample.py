@@ -26,6 +26,8 @@
                                                      recipe, patch 1, 16 frames; TiTok-KL decoder: 32 tokens -> a 256x256 frame)
   python examples/sample.py taichi --encode-titok [--decode-titok] [--titok-ckpt model.safetensors]   (the context latents of the run are
                                                      256x256 context frames encoded by the TiTok-KL encoder: frames -> latents -> latents -> frames)
+  python examples/sample.py taichi1d [--decode-titok] [--encode-titok]   (DiT1D, the frame-causal backbone at the stock dit1d.yaml widths, on
+                                                     the same 4x1x32 token latents, 16 frames: every frame attends to itself and earlier frames)
 
 Without --ckpt the backbone gets seeded random weights (there is no network here to fetch the released checkpoints);
 with it, the reference's .ckpt / ema.safetensors is read by dfot_amd.load_reference_checkpoint (keys
@@ -48,7 +50,7 @@ from bench import RE10K, synth_poses  # noqa: E402
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("model", choices=["re10k", "uvit3d", "k600", "k600diff", "facdit", "facmat", "facdit-s128", "facmat-s128", "facmat-s128-1",
-                                      "facmat-s128-8", "taichi", "mcraft"])
+                                      "facmat-s128-8", "taichi", "taichi1d", "mcraft"])
     ap.add_argument("--ckpt")
     ap.add_argument("--inputs")
     ap.add_argument("--frames", type=int, default=8)
@@ -98,8 +100,8 @@ def main():
         raise SystemExit("--attention-maps: the DiT3D models k600, facdit, facdit-s128 and facmat* only")
     if (a.embed_col_dim or a.col_heads) and not a.model.startswith("facmat"):
         raise SystemExit("--embed-col-dim / --col-heads: the facmat* models only")
-    if (a.decode_titok or a.encode_titok) and a.model != "taichi":
-        raise SystemExit("--decode-titok / --encode-titok: the taichi model only (latents of 4x1x32 tokens)")
+    if (a.decode_titok or a.encode_titok) and a.model not in ("taichi", "taichi1d"):
+        raise SystemExit("--decode-titok / --encode-titok: the taichi / taichi1d models only (latents of 4x1x32 tokens)")
     if (a.decode_dc_ae or a.encode_dc_ae) and a.model != "mcraft":
         raise SystemExit("--decode-dc-ae / --encode-dc-ae: the mcraft model only (latents of 32x8x8)")
     gen = torch.Generator(device="cuda").manual_seed(a.seed)
@@ -146,6 +148,17 @@ def main():
         xs = torch.randn(a.batch, tokens, *x_shape, generator=torch.Generator().manual_seed(a.seed))
         conds = torch.randn(a.batch, tokens, dim, generator=torch.Generator().manual_seed(200 + a.seed))
         n_ctx = 4
+    elif a.model == "taichi1d":  # `backbone=dit1d` at the stock dit1d.yaml widths: the frame-causal transformer over the 4x1x32 token latents
+        x_shape, tokens = (4, 1, 32), 16
+        bb = dict(name="dit1d", hidden_size=1152, depth=28, num_heads=16, mlp_ratio=4, learn_sigma=False, merge_mode="share_norm",
+                  causal_attn_mode="video_temporal_causal", use_rotary_emb=False, qk_norm=False)
+        model = dfot_amd.DiT1D(bb, x_shape=x_shape, max_tokens=tokens).cuda()
+        cfg = dfot_amd.SamplerConfig(x_shape=x_shape, max_tokens=tokens,
+                                     diffusion=dfot_amd.DiffusionConfig(sampling_timesteps=a.steps, beta_schedule="cosine", is_continuous=False),
+                                     prediction_guidance={"name": "conditional"})
+        sampler = dfot_amd.DFoTVideoSampler(cfg, model, noise)
+        xs = torch.randn(a.batch, tokens, *x_shape, generator=torch.Generator().manual_seed(a.seed))
+        n_ctx = 2
     else:
         s128 = "-s128" in a.model  # the res-128 ladder: S widths, depth 6, 16x16 latents (64 patches per frame)
         diff, fac, facmat = a.model == "k600diff", a.model.startswith("facdit"), a.model.startswith("facmat")

@@ -836,6 +836,48 @@ int dfot_op_dcae_rmsnorm(const float* x, const float* weight, const float* bias,
 /* out bf16 [n] = act(x fp32 [n]); act 0 = none, 1 = ReLU, 2 = SiLU: a ResBlock's activation in front of conv2 (:129).  n % 4 == 0. */
 int dfot_op_dcae_act_bf16(const float* x, void* out, int64_t n, int act, void* stream);
 
+/* ---- DiT1D (algorithms/dfot/backbones/dit1d/dit_model.py:358-530 at the stock dit1d.yaml: merge_mode share_norm, no rotary embedding, no
+ * qk-norm, no context tokens): the frame-causal transformer over 1-D token latents (B, T, C, 1, L), e.g. the [4, 1, 32] TiTok-KL frames. ---- */
+/* Frame-causal ("block lower triangular") flash attention: operands and output exactly as dfot_op_attention_padded takes them (q, k, v
+ * [B][heads][n][dstride] bf16 with dstride = (d <= 64 ? 64 : 128), pad columns zero, q pre-scaled by log2(e)/sqrt(d); o[(b*n + row)][head*d
+ * + c], c < d, compact with row stride ldo, only those columns written).  n = frames * frame_len tokens; query i attends to key j iff
+ * j / frame_len <= i / frame_len.  A workgroup owns 128 query rows and reads the keys below the end of its last frame only; masked
+ * scores are replaced by -inf before the row maximum (never a bias), so they contribute exactly 0.  No atomics, no allocation, no host
+ * synchronisation; the summation order depends on (n, frame_len, d) and the query tile alone: a video gives the same bits alone and in a
+ * batch, and frames <= f give the same bits whatever frames > f hold (finite values).  frame_len in {16, 32, 64, 128}, n % 128 == 0,
+ * d % 8 == 0, 0 < d <= 128, batch * heads * (n / 128) < 2^31 (the grid), ldo % 8 == 0 covering heads*d; anything else: DFOT_ERR_SHAPE (null pointers:
+ * DFOT_ERR_ARG) before any device work. */
+int dfot_op_attention_frame_causal(const void* q, const void* k, const void* v, void* o, int ldo, int batch, int heads, int n, int frame_len,
+                                   int d, void* stream);
+
+typedef struct dfot_dit1d_s* dfot_dit1d_t;
+typedef struct {
+  int32_t hidden;           /* hidden_size: a multiple of 64, <= 2048 */
+  int32_t depth;
+  int32_t heads;            /* head dim hidden / heads: a multiple of 8, <= 128 */
+  int32_t mlp_hidden;       /* hidden * mlp_ratio: a multiple of 64 */
+  int32_t in_channels;      /* C = x_shape[0], 1 .. 64 */
+  int32_t tokens_per_frame; /* L = x_shape[2]: 16, 32, 64 or 128 */
+  int32_t max_tokens;       /* T: frames per window; T * L a multiple of 128.  The model runs at exactly T frames (pos_embed fixes the length) */
+  int32_t timesteps;        /* discrete noise levels 0 .. timesteps - 1 */
+  int32_t causal;           /* 1: frame-causal attention (causal_attn_mode temporal_causal / video_temporal_causal); 0: no mask (null) */
+  float eps;                /* LayerNorm epsilon (1e-6) */
+} dfot_dit1d_config;
+/* Parameters are enumerated in the reference module's state_dict order (pos_embed first: it is loaded, not recomputed) and loaded by name
+ * as fp32 device tensors; dfot_dit1d_finalize tabulates the modulations of every noise level and synchronises.  dfot_dit1d_reserve sizes
+ * the workspace for a batch (grow-only); after it dfot_dit1d_forward allocates nothing and does not synchronise (capturable in a graph).
+ * out[B,T,C,1,L] = model(x[B,T,C,1,L], noise_levels[B,T] int32, clamped to [0, timesteps)); tokens must equal max_tokens (DFOT_ERR_SHAPE). */
+int dfot_dit1d_create(const dfot_dit1d_config* cfg, dfot_dit1d_t* out);
+int dfot_dit1d_destroy(dfot_dit1d_t h);
+int dfot_dit1d_num_params(dfot_dit1d_t h);
+const char* dfot_dit1d_param_name(dfot_dit1d_t h, int index);
+int dfot_dit1d_param_shape(dfot_dit1d_t h, int index, int64_t shape[4], int* ndim);
+int dfot_dit1d_load_weight(dfot_dit1d_t h, const char* name, const float* data, const int64_t* shape, int ndim, void* stream);
+int dfot_dit1d_finalize(dfot_dit1d_t h, void* stream);
+int dfot_dit1d_reserve(dfot_dit1d_t h, int max_batch);
+size_t dfot_dit1d_workspace_bytes(dfot_dit1d_t h);
+int dfot_dit1d_forward(dfot_dit1d_t h, const float* x, const int32_t* noise_levels, float* out, int batch, int tokens, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

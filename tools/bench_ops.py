@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Micro-benchmarks of the C-ABI primitives at the RE10K model shapes (model batch 2), HIP-event timed.
-Usage (GPU box): python tools/bench_ops.py [gemm] [conv] [attn] [tattn] [mattn] [tattn_bwd] [facdit_train] [mattn_bwd] [facmat_train] [vae_encode] [equal] [dit_front] [ivae] [uvit3d] [gnfilm_frame] [uvit3d_train] [attnmap] [titok] [titok_enc] [mcraft] [sattn64] [facmat_narrow] [dcae]"""
+Usage (GPU box): python tools/bench_ops.py [gemm] [conv] [attn] [tattn] [mattn] [tattn_bwd] [facdit_train] [mattn_bwd] [facmat_train] [vae_encode] [equal] [dit_front] [ivae] [uvit3d] [gnfilm_frame] [uvit3d_train] [attnmap] [titok] [titok_enc] [mcraft] [sattn64] [facmat_narrow] [dcae] [attn_fc] [dit1d]"""
 import ctypes as C
 import math
 import os
@@ -213,6 +213,48 @@ def sattn64(b, heads, tokens, d):
     ms128 = timeit(lambda: capi.check(capi.lib.dfot_op_attention_padded(P(q), P(k), P(v), P(o), heads * d, nseq // 2, heads, 128, d, S())),
                    iters=50, warm=5)
     return ms, nseq * 64 * heads * (3 * ds + d) * 2.0 / ms / 1e6, ms128
+
+
+def attn_fc(b, heads, n, frame_len, d, rounds=7):
+    """the frame-causal launch (dfot_op_attention_frame_causal) next to dfot_op_attention_padded on the same unit-normal operands, alternated
+    over `rounds` rounds in one process: ([ms frame-causal], [ms padded]) per round; the non-causal launcher is the only yardstick there is
+    (it computes another result: every (query tile, 128-key block) pair instead of the pairs on and below the block diagonal)"""
+    ds = 64 if d <= 64 else 128
+    q, k, v = (torch.zeros(b, heads, n, ds, device="cuda", dtype=torch.bfloat16) for _ in range(3))
+    for t, mul in ((q, math.log2(math.e) / math.sqrt(d)), (k, 1.0), (v, 1.0)):
+        t[..., :d] = (torch.randn(b, heads, n, d, device="cuda") * mul).bfloat16()
+    o = torch.empty(b * n, heads * d, device="cuda", dtype=torch.bfloat16)
+    fc, pad = [], []
+    for _ in range(rounds):
+        fc.append(timeit(lambda: capi.check(capi.lib.dfot_op_attention_frame_causal(P(q), P(k), P(v), P(o), heads * d, b, heads, n, frame_len, d, S())),
+                         iters=100, warm=10))
+        pad.append(timeit(lambda: capi.check(capi.lib.dfot_op_attention_padded(P(q), P(k), P(v), P(o), heads * d, b, heads, n, d, S())),
+                          iters=100, warm=10))
+    return fc, pad
+
+
+def dit1d_forward(b, rounds=5):
+    """whole forward of DiT1D at the stock dit1d.yaml widths (hidden 1152, depth 28, 16 heads) on the taichi token latents [4, 1, 32] x 16 frames,
+    frame-causal and unmasked, next to DiT3D @DiT/XL patch 1 (full attention, RoPE-3D) on the same latents, alternated in one process:
+    {name: [ms per round]}.  Not the same amount of work: a DiT1D block carries a 4x MLP (12 H^2 weights), a `full` DiT3D block at @DiT/XL
+    (spatial_mlp_ratio unset) none (4 H^2)"""
+    bb1 = dict(name="dit1d", hidden_size=1152, depth=28, num_heads=16, mlp_ratio=4, learn_sigma=False, merge_mode="share_norm",
+               causal_attn_mode="video_temporal_causal", use_rotary_emb=False, qk_norm=False)
+    bb3 = dict(name="dit3d", variant="full", pos_emb_type="rope_3d", patch_size=1, hidden_size=1152, depth=28, num_heads=16)
+    models = {"DiT1D frame-causal": dfot_amd.DiT1D(bb1, x_shape=(4, 1, 32), max_tokens=16),
+              "DiT1D no mask": dfot_amd.DiT1D(dict(bb1, causal_attn_mode=None), x_shape=(4, 1, 32), max_tokens=16),
+              "DiT3D XL patch 1": dfot_amd.DiT3D(bb3, x_shape=(4, 1, 32), max_tokens=16)}
+    for m in models.values():
+        m.cuda().eval()
+        m.init_random(0)
+    x = torch.randn(b, 16, 4, 1, 32, device="cuda")
+    k = torch.randint(0, 1000, (b, 16), device="cuda")
+    out = {name: [] for name in models}
+    with torch.no_grad():
+        for _ in range(rounds):
+            for name, model in models.items():
+                out[name].append(timeit(lambda: model(x, k), iters=10, warm=3))
+    return out
 
 
 def facmat_narrow_ops(frames, p, h, e):
@@ -774,6 +816,21 @@ def main():
                       f"{HBM_TBS:.0f} TB/s HBM)  padded n=128 at equal rows {ms128*1e3:8.1f} us  seq64 / padded {ms / ms128:.2f}", flush=True)
         for kind, label in (("facdit", "FacDiT-S"), ("facmat", "FacMatDiT-S-64-1")):
             print(f"{label} forward (depth 6) B=2 x 16 frames x 64 patches: {p64_forward(kind, 2):.3f} ms", flush=True)
+    if "attn_fc" in what:
+        med = lambda r: sorted(r)[len(r) // 2]  # noqa: E731
+        # the stock DiT1D attention (1152 / 16 heads = d 72, L = 32) at 16 and 32 frames, model batch 16
+        for n in (512, 1024):
+            fc, pad = attn_fc(16, 16, n, 32, 72)
+            tiles = n // 128
+            print(f"attn_fc B=16 H=16 N={n} L=32 d=72: frame-causal median {med(fc)*1e3:8.1f} us (min {min(fc)*1e3:.1f}, max {max(fc)*1e3:.1f})  "
+                  f"padded {med(pad)*1e3:8.1f} us (min {min(pad)*1e3:.1f}, max {max(pad)*1e3:.1f})  frame-causal / padded {med(fc) / med(pad):.2f}  "
+                  f"({tiles * (tiles + 1) // 2} of {tiles * tiles} (query tile, 128-key block) pairs visited; {len(fc)} alternated rounds)", flush=True)
+    if "dit1d" in what:
+        ms = dit1d_forward(16)
+        for name, r in ms.items():
+            r = sorted(r)
+            print(f"{name} forward B=16 x 16 frames x 32 tokens (hidden 1152, depth 28): median {r[len(r) // 2]:.3f} ms  (min {r[0]:.3f}, max {r[-1]:.3f} "
+                  f"over {len(r)} alternated rounds)", flush=True)
     if "facmat_narrow" in what:
         # the S shape (embed_row_dim 384, 64 patches, 16 videos x 16 frames) and an XL-like one (1152, 256 patches, 128 frames)
         for name, (frames, p, h) in {"S": (256, 64, 384), "XL": (128, 256, 1152)}.items():

@@ -446,3 +446,43 @@ def install_dcae():
     _mod("diffusers.utils.accelerate_utils", apply_forward_hook=lambda f: f)
     model = importlib.import_module("algorithms.vae.dc_ae.autoencoder_dc_model")
     return model.MyAutoencoderDC, model
+
+
+def install_dit1d():
+    """The reference's DIT1D (algorithms/dfot/backbones/dit1d/dit_model.py) importable on its own: namespace packages skip the package
+    __init__ files; timm's Mlp is the stand-in above, ``timm.layers.use_fused_attn`` answers False (the module then runs its own
+    ``softmax(q k^T * scale + mask) v``, dit_model.py:78-85, the arithmetic F.scaled_dot_product_attention restates), and
+    ``rotary_embedding_torch.RotaryEmbedding`` is a name that is never constructed (use_rotary_emb: false).  The constructor's eight
+    ``print`` calls are silenced.  Returns (DIT1D constructor, the module): the module also holds get_1d_sincos_pos_embed."""
+    import contextlib
+    import functools
+    import io
+    if REF not in sys.path:
+        sys.path.insert(0, REF)
+    sys.dont_write_bytecode = True
+    for name, rel in [("algorithms", "algorithms"), ("algorithms.dfot", "algorithms/dfot"), ("algorithms.dfot.backbones", "algorithms/dfot/backbones"),
+                      ("algorithms.dfot.backbones.dit1d", "algorithms/dfot/backbones/dit1d")]:
+        if name not in sys.modules:
+            _ns(name, f"{REF}/{rel}")
+    for name in ("timm", "timm.models"):
+        if name not in sys.modules:
+            _mod(name)
+    if "timm.models.vision_transformer" not in sys.modules:
+        _mod("timm.models.vision_transformer", PatchEmbed=_PatchEmbed, Mlp=_Mlp, Attention=nn.Module)
+    if "timm.layers" not in sys.modules:
+        _mod("timm.layers", PatchEmbed=_PatchEmbed, Mlp=_Mlp)
+    sys.modules["timm.layers"].use_fused_attn = lambda: False
+    if "rotary_embedding_torch" not in sys.modules:
+        _mod("rotary_embedding_torch")
+
+    class _NeverBuilt:
+        def __init__(self, *a, **k):
+            raise AssertionError("RotaryEmbedding is a name only: use_rotary_emb is false on this path")
+    sys.modules["rotary_embedding_torch"].RotaryEmbedding = _NeverBuilt
+    model = importlib.import_module("algorithms.dfot.backbones.dit1d.dit_model")
+
+    @functools.wraps(model.DIT1D)
+    def quiet(*a, **k):
+        with contextlib.redirect_stdout(io.StringIO()):
+            return model.DIT1D(*a, **k)
+    return quiet, model
