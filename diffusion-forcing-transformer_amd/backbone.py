@@ -24,19 +24,90 @@ import torch
 from torch import nn
 
 from . import capi, ops
+from .engine_module import EngineModule, _Node, _get  # noqa: F401  (_Node and _get are imported from here too)
+
+_FOURIER_BUFFERS = ("noise_level_pos_embedding.timesteps.freqs", "noise_level_pos_embedding.timesteps.phases")
 
 
-def _get(cfg, key, default=None):
-    if isinstance(cfg, dict):
-        return cfg.get(key, default)
-    return getattr(cfg, key, default) if not hasattr(cfg, "get") else cfg.get(key, default)
+class UViTModule(EngineModule):
+    """What the two U-ViT backbones (UViT3DPose here, uvit3d_backbone.UViT3D) share beyond the engine plumbing: the handle type -- so the
+    read-outs and taps of the dfot_uvit_* engine -- the persistent Fourier buffers and the initialisers."""
+    _family = "uvit"
+
+    def _new_tensor(self, name: str, shape: Tuple[int, ...]) -> torch.Tensor:
+        t = torch.zeros(shape, dtype=torch.float32)
+        return t if name in _FOURIER_BUFFERS else nn.Parameter(t)
+
+    def _tensors(self) -> Dict[str, torch.Tensor]:
+        return self._engine_tensors()
+
+    def reset_parameters(self, seed: int = 0) -> None:
+        """Reference-style default init (zero-initialised output projections included)."""
+        g = torch.Generator().manual_seed(seed)
+        with torch.no_grad():
+            for name, t in self._tensors().items():
+                leaf = name.rsplit(".", 1)[-1]
+                if leaf == "freqs":
+                    t.copy_(2 * math.pi * torch.randn(t.shape, generator=g))
+                elif leaf == "phases":
+                    t.copy_(2 * math.pi * torch.rand(t.shape, generator=g))
+                elif any(s in name for s in (".attn_out.", ".mlp_out.2.", ".out_rest.1.", "project_output")):
+                    t.zero_()
+                elif leaf == "bias":
+                    t.zero_()
+                elif t.ndim == 1:
+                    t.fill_(1.0)
+                else:
+                    fan_in = math.prod(t.shape[1:])
+                    bound = 1.0 / math.sqrt(fan_in)
+                    t.copy_((torch.rand(t.shape, generator=g) * 2 - 1) * bound)
+
+    def init_random(self, seed: int = 0, zero_init_scale: float = 0.3) -> None:
+        """Non-degenerate random weights for benchmarks (the reference's default init zeroes every output
+        projection, which would make all activations trivial): weights ~ N(0, 1/fan_in), biases ~ N(0, 0.02^2),
+        gains ~ 1 + N(0, 0.1^2), Fourier freqs 2*pi*N(0,1), phases 2*pi*U(0,1)."""
+        g = torch.Generator().manual_seed(seed)
+        with torch.no_grad():
+            for name, t in self._tensors().items():
+                leaf = name.rsplit(".", 1)[-1]
+                if leaf == "freqs":
+                    v = 2 * math.pi * torch.randn(t.shape, generator=g)
+                elif leaf == "phases":
+                    v = 2 * math.pi * torch.rand(t.shape, generator=g)
+                elif leaf == "bias":
+                    v = 0.02 * torch.randn(t.shape, generator=g)
+                elif t.ndim == 1:
+                    v = 1.0 + 0.1 * torch.randn(t.shape, generator=g)
+                else:
+                    fan_in = t.shape[0] if name.startswith("project_output") else math.prod(t.shape[1:])
+                    v = torch.randn(t.shape, generator=g) / math.sqrt(fan_in)
+                    if any(s in name for s in (".attn_out.", ".mlp_out.2.", ".out_rest.1.", "project_output")):
+                        v = v * zero_init_scale
+                t.copy_(v.to(t.device))
+
+    def query(self, key: str) -> float:
+        """read-outs of the engine ("score_bound_l2", "attn_kernel_l2": include/dfot_hip.h); the weights are synced first"""
+        self.sync_weights()
+        val = C.c_double()
+        capi.check(capi.lib.dfot_uvit_query(self._handle, key.encode(), C.byref(val)))
+        return float(val.value)
+
+    def attn_timing(self):
+        """(total_ms, launches) of the level-2 attention launches recorded since set_option('time_attn', N)."""
+        tot, n = C.c_double(), C.c_int64()
+        capi.check(capi.lib.dfot_uvit_attn_timing(self._handle, C.byref(tot), C.byref(n)))
+        return tot.value, n.value
+
+    def read_tap(self, name: str, channels: int, level: int, batch: int) -> torch.Tensor:
+        r = self.x_shape[-1] // 2 // (2 ** level)
+        out = torch.empty(batch * self.temporal_length, channels, r, r, device="cuda", dtype=torch.float32)
+        capi.check(capi.lib.dfot_uvit_read_tap(self._handle, name.encode(), capi.ptr(out), out.numel(), capi.stream_ptr()))
+        return out
 
 
-class _Node(nn.Module):
-    """Anonymous container so that dotted reference key names map onto a module tree."""
+class UViT3DPose(UViTModule):
+    _create = "dfot_uvit_create"
 
-
-class UViT3DPose(nn.Module):
     def __init__(self, cfg, x_shape: Sequence[int], max_tokens: int, external_cond_dim: int = 0,
                  external_cond_type: str = "action", external_cond_num_classes: Optional[int] = None,
                  use_causal_mask: bool = False, **kwargs):
@@ -71,21 +142,7 @@ class UViT3DPose(nn.Module):
         if int(_get(cfg, "patch_size", 2)) != 2:
             raise ValueError("only patch_size=2 is supported")
         self._ccfg = c
-        self._handle = C.c_void_p()
-        capi.check(capi.lib.dfot_uvit_create(C.byref(c), C.byref(self._handle)))
-        self._names = []
-        self._persistent_buffers = {"noise_level_pos_embedding.timesteps.freqs",
-                                    "noise_level_pos_embedding.timesteps.phases"}
-        shape = (C.c_int64 * 4)()
-        ndim = C.c_int()
-        for i in range(capi.lib.dfot_uvit_num_params(self._handle)):
-            name = capi.lib.dfot_uvit_param_name(self._handle, i).decode()
-            capi.check(capi.lib.dfot_uvit_param_shape(self._handle, i, shape, C.byref(ndim)))
-            self._register(name, tuple(shape[k] for k in range(ndim.value)))
-            self._names.append(name)
-        self._synced: Optional[Tuple] = None
-        self._reserved = 0
-        self._op_key: Optional[int] = None
+        self._build_tree()
         self._cond_key = None
         self._cond_refs = None
         self._cond_gen = None        # reserve_generation at the time the conditioning cache was keyed
@@ -100,115 +157,8 @@ class UViT3DPose(nn.Module):
         self._train_stamp = 0        # counts training forwards: the autograd ctx of a forward remembers its number (ops._train_setup_context)
         self._dropout_generator: Optional[torch.Generator] = None  # set a CUDA generator to enable the MLP-branch nn.Dropout in train()
 
-    # ------------------------------------------------------------------ module tree
-    def _register(self, name: str, shape: Tuple[int, ...]) -> None:
-        *path, leaf = name.split(".")
-        node: nn.Module = self
-        for part in path:
-            if part not in node._modules:
-                node.add_module(part, _Node())
-            node = node._modules[part]
-        t = torch.zeros(shape, dtype=torch.float32)
-        if name in self._persistent_buffers:
-            node.register_buffer(leaf, t, persistent=True)
-        else:
-            node.register_parameter(leaf, nn.Parameter(t))
-
-    def _tensors(self) -> Dict[str, torch.Tensor]:
-        sd = dict(self.named_parameters())
-        sd.update(dict(self.named_buffers()))
-        return sd
-
-    def reset_parameters(self, seed: int = 0) -> None:
-        """Reference-style default init (zero-initialised output projections included)."""
-        g = torch.Generator().manual_seed(seed)
-        with torch.no_grad():
-            for name, t in self._tensors().items():
-                leaf = name.rsplit(".", 1)[-1]
-                if leaf == "freqs":
-                    t.copy_(2 * math.pi * torch.randn(t.shape, generator=g))
-                elif leaf == "phases":
-                    t.copy_(2 * math.pi * torch.rand(t.shape, generator=g))
-                elif any(s in name for s in (".attn_out.", ".mlp_out.2.", ".out_rest.1.", "project_output")):
-                    t.zero_()
-                elif leaf == "bias":
-                    t.zero_()
-                elif t.ndim == 1:
-                    t.fill_(1.0)
-                else:
-                    fan_in = math.prod(t.shape[1:])
-                    bound = 1.0 / math.sqrt(fan_in)
-                    t.copy_((torch.rand(t.shape, generator=g) * 2 - 1) * bound)
-
-    # ------------------------------------------------------------------ weights -> engine
-    def _signature(self) -> Tuple:
-        return tuple((t.data_ptr(), t._version) for t in self._tensors().values())
-
-    def sync_weights(self, force: bool = False) -> None:
-        sig = self._signature()
-        if not force and sig == self._synced:
-            return
-        tensors = self._tensors()
-        s = capi.stream_ptr()
-        for name in self._names:
-            t = tensors[name]
-            if not t.is_cuda:
-                raise RuntimeError(f"parameter {name} is on {t.device}; move the module to the GPU first")
-            src = t.detach().to(torch.float32).contiguous()
-            shape = (C.c_int64 * src.ndim)(*src.shape)
-            capi.check(capi.lib.dfot_uvit_load_weight(self._handle, name.encode(), capi.ptr(src), shape, src.ndim, s))
-        capi.check(capi.lib.dfot_uvit_finalize(self._handle, s))
-        self._synced = sig
-        # captured sampler graphs bake the kernels chosen for the OLD weights (attention variant by score bound) and their pointers
-        self.reserve_generation = getattr(self, "reserve_generation", 0) + 1
-
-    def set_option(self, key: str, value: int) -> None:
-        self.reserve_generation = getattr(self, "reserve_generation", 0) + 1  # options select kernels: captured graphs are stale
-        capi.check(capi.lib.dfot_uvit_set_option(self._handle, key.encode(), int(value)))
-
-    def query(self, key: str) -> float:
-        """read-outs of the engine ("score_bound_l2", "attn_kernel_l2": include/dfot_hip.h); the weights are synced first"""
-        self.sync_weights()
-        val = C.c_double()
-        capi.check(capi.lib.dfot_uvit_query(self._handle, key.encode(), C.byref(val)))
-        return float(val.value)
-
-    def attn_timing(self):
-        """(total_ms, launches) of the level-2 attention launches recorded since set_option('time_attn', N)."""
-        tot, n = C.c_double(), C.c_int64()
-        capi.check(capi.lib.dfot_uvit_attn_timing(self._handle, C.byref(tot), C.byref(n)))
-        return tot.value, n.value
-
-    def init_random(self, seed: int = 0, zero_init_scale: float = 0.3) -> None:
-        """Non-degenerate random weights for benchmarks (the reference's default init zeroes every output
-        projection, which would make all activations trivial): weights ~ N(0, 1/fan_in), biases ~ N(0, 0.02^2),
-        gains ~ 1 + N(0, 0.1^2), Fourier freqs 2*pi*N(0,1), phases 2*pi*U(0,1)."""
-        g = torch.Generator().manual_seed(seed)
-        with torch.no_grad():
-            for name, t in self._tensors().items():
-                leaf = name.rsplit(".", 1)[-1]
-                if leaf == "freqs":
-                    v = 2 * math.pi * torch.randn(t.shape, generator=g)
-                elif leaf == "phases":
-                    v = 2 * math.pi * torch.rand(t.shape, generator=g)
-                elif leaf == "bias":
-                    v = 0.02 * torch.randn(t.shape, generator=g)
-                elif t.ndim == 1:
-                    v = 1.0 + 0.1 * torch.randn(t.shape, generator=g)
-                else:
-                    fan_in = t.shape[0] if name.startswith("project_output") else math.prod(t.shape[1:])
-                    v = torch.randn(t.shape, generator=g) / math.sqrt(fan_in)
-                    if any(s in name for s in (".attn_out.", ".mlp_out.2.", ".out_rest.1.", "project_output")):
-                        v = v * zero_init_scale
-                t.copy_(v.to(t.device))
-
-    def reserve(self, batch: int) -> None:
-        if batch > self._reserved:
-            torch.cuda.synchronize()
-            capi.check(capi.lib.dfot_uvit_reserve(self._handle, int(batch)))
-            self._reserved = batch
-            self.reserve_generation = getattr(self, "reserve_generation", 0) + 1  # workspace pointers changed
-            self._cond_key = None
+    def _after_reserve(self) -> None:
+        self._cond_key = None  # the pose / FiLM caches lived in the old workspace
 
     # ------------------------------------------------------------------ forward
     def forward(self, x: torch.Tensor, noise_levels: torch.Tensor, external_cond: Optional[torch.Tensor] = None,
@@ -393,17 +343,3 @@ class UViT3DPose(nn.Module):
                                                            capi.ptr(fresh, torch.uint8, "fresh_frames"), capi.stream_ptr()))
         self._fresh_key = key
         return out.to(x.dtype)
-
-    def read_tap(self, name: str, channels: int, level: int, batch: int) -> torch.Tensor:
-        r = self.x_shape[-1] // 2 // (2 ** level)
-        out = torch.empty(batch * self.temporal_length, channels, r, r, device="cuda", dtype=torch.float32)
-        capi.check(capi.lib.dfot_uvit_read_tap(self._handle, name.encode(), capi.ptr(out), out.numel(), capi.stream_ptr()))
-        return out
-
-    def __del__(self):
-        try:
-            if getattr(self, "_handle", None) and self._handle.value:
-                capi.lib.dfot_uvit_destroy(self._handle)
-                self._handle = C.c_void_p()
-        except Exception:
-            pass

@@ -9,27 +9,20 @@
 // 288 GB), and forward never touches the embedding MLP or the 228 MB of modulation weights again.
 #include <cmath>
 #include <cstring>
-#include <functional>
-#include <map>
 #include <string>
 #include <vector>
 
 #include "dfot_hip.h"
 #include "dit_model.h"
+#include "engine_device.h"
 #include "gemm.h"
 #include "kernels.h"
+#include "level_embed.h"
 
 namespace dfot {
 namespace {
 
 typedef __attribute__((ext_vector_type(4))) float float4v;
-
-struct DitParam {
-  std::string name;
-  std::vector<int64_t> shape;
-  std::function<int(const float*, hipStream_t)> load;
-  bool loaded = false;
-};
 
 struct DitBlockW {  // DiTBlock (attn.qkv / attn.proj) or MatrixDiTBlock (the attention factors); norm1, norm2 and the MLP are common
   bf16 *w_qkv = nullptr, *w_proj = nullptr, *w_fc1 = nullptr, *w_fc2 = nullptr;
@@ -39,43 +32,7 @@ struct DitBlockW {  // DiTBlock (attn.qkv / attn.proj) or MatrixDiTBlock (the at
   float *qkv_bias = nullptr, *proj_bias = nullptr;                      // [E][3h], [P][h]
 };
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
-// ---- finalize-time kernels (run once per weight load) -------------------------------------------------------------
-// get_timestep_embedding(flip_sin_to_cos=True, downscale_freq_shift=0): feat[level] = [cos(level*f_i) | sin(level*f_i)]
-__global__ void tstep_features_kernel(const float* __restrict__ freqs, float* __restrict__ feat, int levels, int dim) {
-  const int half = dim / 2;
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (long)levels * dim) return;
-  const int lv = (int)(i / dim), c = (int)(i % dim);
-  const float a = __fmul_rn((float)lv, freqs[c < half ? c : c - half]);
-  feat[i] = c < half ? cosf(a) : sinf(a);
-}
-
-// out[r][o] = act(b[o] + sum_k W[o][k] * in[r][k]); one wave per (o, r); ACT: 0 none, 1 SiLU
-template <int ACT>
-__global__ __launch_bounds__(256) void rows_linear_kernel(const float* __restrict__ in, const float* __restrict__ w,
-                                                          const float* __restrict__ b, float* __restrict__ out,
-                                                          bf16* __restrict__ out_silu_bf16, int kdim, int odim) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int o = blockIdx.x * 4 + wave;
-  const long r = blockIdx.y;
-  if (o >= odim) return;
-  float acc = 0.f;
-  for (int i = lane; i < kdim; i += 64) acc += w[(long)o * kdim + i] * in[r * kdim + i];
-  acc = wave_sum(acc);
-  if (lane == 0) {
-    float v = acc + b[o];
-    if (ACT == 1) v = silu_f(v);
-    out[r * odim + o] = v;
-    if (out_silu_bf16) out_silu_bf16[r * odim + o] = f2bf(silu_f(v));
-  }
-}
-
+// ---- finalize-time kernels (run once per weight load; the level-embedding ones are level_embed.h) ---------------------
 // semb[(flag*lpad + level)][:] = bf16(SiLU(emb[level] + diff_table[flag]))  (DifferenceDiT3D: c = noise emb + diff emb)
 __global__ void add_diff_silu_kernel(const float* __restrict__ emb, const float* __restrict__ diff_table, bf16* __restrict__ semb,
                                      int levels, int lpad, int hidden, int flags) {
@@ -759,13 +716,10 @@ int launch_final_layer(const float* x, const float* table, const int* levels, lo
 
 using namespace dfot;
 
-struct dfot_dit_s : DitGeom {  // the geometry of cfg (dit_model.h): gh, gw, P, d, dstride, kpatch, oc, c_rows, ldt, mod_final
+struct dfot_dit_s : DitGeom, EngineDevice {  // the geometry of cfg (dit_model.h): gh, gw, P, d, dstride, kpatch, oc, c_rows, ldt, mod_final
+  dfot_dit_s() : EngineDevice("") {}
   DitCfg cfg{};
   int lpad = 0;      // level count padded to the GEMM's row tile
-  std::vector<DitParam> params;
-  std::map<std::string, int> index;
-  std::vector<void*> owned, ws_owned;
-  size_t ws_bytes = 0;
   // weights
   float *t_w1 = nullptr, *t_b1 = nullptr, *t_w2 = nullptr, *t_b2 = nullptr, *pe_w = nullptr, *pe_b = nullptr,
         *fin_w = nullptr, *fin_b = nullptr, *b_mod = nullptr;
@@ -813,54 +767,14 @@ struct dfot_dit_s : DitGeom {  // the geometry of cfg (dit_model.h): gh, gw, P, 
 namespace dfot {
 namespace {
 
-template <typename T>
-int dit_alloc(dfot_dit_s* h, T** out, size_t count, bool workspace = false) {
-  void* p = nullptr;
-  const size_t bytes = count * sizeof(T);
-  DFOT_CHECK_HIP(hipMalloc(&p, bytes ? bytes : 16));
-  (workspace ? h->ws_owned : h->owned).push_back(p);
-  if (workspace) h->ws_bytes += bytes;
-  *out = reinterpret_cast<T*>(p);
-  return DFOT_OK;
-}
-
-void dit_add(dfot_dit_s* h, const std::string& name, std::vector<int64_t> shape, std::function<int(const float*, hipStream_t)> load) {
-  h->index[name] = (int)h->params.size();
-  h->params.push_back(DitParam{name, std::move(shape), std::move(load), false});
-}
-
-// the loaders of an inventory entry (dit_model.h): fp32 as given, at dst / in storage allocated here ...
-void dit_add_slice(dfot_dit_s* h, const DitTensor& t, float* dst) {
-  const size_t n = (size_t)t.numel();
-  dit_add(h, t.name, t.shape, [=](const float* src, hipStream_t s) {
-    DFOT_CHECK_HIP(hipMemcpyAsync(dst, src, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-    return DFOT_OK;
-  });
-}
-int dit_add_f32(dfot_dit_s* h, const DitTensor& t, float** dst) {
-  int rc = dit_alloc(h, dst, (size_t)t.numel());
-  if (!rc) dit_add_slice(h, t, *dst);
-  return rc;
-}
-
-// ... Linear weight [rows][k] fp32 -> bf16 at dst (row stride k) / in storage allocated here ...
-void dit_add_bf16(dfot_dit_s* h, const DitTensor& t, bf16* dst) {
-  const int rows = (int)t.shape[0], k = (int)t.shape[1];
-  dit_add(h, t.name, t.shape, [=](const float* src, hipStream_t s) { return launch_pack_rows(src, dst, nullptr, rows, k, k, k, 0, s); });
-}
-int dit_add_linear(dfot_dit_s* h, const DitTensor& t, bf16** dst) {
-  int rc = dit_alloc(h, dst, (size_t)t.numel());
-  if (!rc) dit_add_bf16(h, t, *dst);
-  return rc;
-}
-
-// ... dst[c][r] bf16 = src[r][c]: the matrix factors are stored (in, out); the GEMMs want [out][in]
+// the loader of an inventory entry (dit_model.h) that only this engine has (the others: engine_device.h): dst[c][r] bf16 = src[r][c].
+// The matrix factors are stored (in, out); the GEMMs want [out][in]
 int dit_add_transposed(dfot_dit_s* h, const DitTensor& t, bf16** dst) {
-  int rc = dit_alloc(h, dst, (size_t)t.numel());
+  int rc = h->alloc(dst, (size_t)t.numel());
   if (rc) return rc;
   bf16* d = *dst;
   const int rows = (int)t.shape[0], cols = (int)t.shape[1];
-  dit_add(h, t.name, t.shape, [=](const float* src, hipStream_t s) {
+  h->params.add(t.name, t.shape, [=](const float* src, hipStream_t s) {
     hipLaunchKernelGGL(pack_transpose_kernel, dim3(cdiv((long)rows * cols, 256)), dim3(256), 0, s, src, d, rows, cols);
     DFOT_CHECK_HIP(hipGetLastError());
     return DFOT_OK;
@@ -916,7 +830,7 @@ int dit_cap_slot(const dfot_dit_s* h, int block) {
 }
 
 int dit_upload(dfot_dit_s* h, float** dst, const std::vector<float>& table) {
-  int rc = dit_alloc(h, dst, table.size());
+  int rc = h->alloc(dst, table.size());
   if (rc) return rc;
   DFOT_CHECK_HIP(hipMemcpy(*dst, table.data(), table.size() * sizeof(float), hipMemcpyHostToDevice));
   return DFOT_OK;
@@ -928,7 +842,7 @@ int dit_build(dfot_dit_s* h) {
   const int hd = c.hidden_size;
   h->lpad = (c.timesteps + 255) / 256 * 256;
   int rc = 0;
-  if ((rc = dit_alloc(h, &h->w_mod, (size_t)h->ldt * hd)) || (rc = dit_alloc(h, &h->b_mod, (size_t)h->ldt))) return rc;
+  if ((rc = h->alloc(&h->w_mod, (size_t)h->ldt * hd)) || (rc = h->alloc(&h->b_mod, (size_t)h->ldt))) return rc;
   h->blocks.resize(c.depth);
   if (h->fac) h->fblocks.resize(c.depth);
   if (h->facmat) h->tblocks.resize(c.depth);
@@ -938,41 +852,43 @@ int dit_build(dfot_dit_s* h) {
     if (t.col >= 0) {  // a modulation Linear: rows [col, col + out) of the stacked weight, the same columns of the stacked bias
       if (t.kind == DIT_MOD1_W) w->mod1 = t.col;
       if (t.kind == DIT_MOD2_W) w->mod2 = t.col;
-      if (t.shape.size() == 2) dit_add_bf16(h, t, h->w_mod + t.col * hd);
-      else dit_add_slice(h, t, h->b_mod + t.col);
+      if (t.shape.size() == 2) h->add_bf16(t.name, (int)t.shape[0], (int)t.shape[1], h->w_mod + t.col * hd);
+      else h->add_slice(t.name, t.shape, h->b_mod + t.col);
       continue;
     }
+    auto f32 = [&](float** dst) { return h->add_f32(t.name, t.shape, dst); };
+    auto linear = [&](bf16** dst) { return h->add_linear(t.name, (int)t.shape[0], (int)t.shape[1], dst); };
     switch (t.kind) {
-      case DIT_FZ_FREQS: rc = dit_add_f32(h, t, &h->fz_freqs); break;
-      case DIT_FZ_PHASES: rc = dit_add_f32(h, t, &h->fz_phases); break;
-      case DIT_T_W1: rc = dit_add_f32(h, t, &h->t_w1); break;
-      case DIT_T_B1: rc = dit_add_f32(h, t, &h->t_b1); break;
-      case DIT_T_W2: rc = dit_add_f32(h, t, &h->t_w2); break;
-      case DIT_T_B2: rc = dit_add_f32(h, t, &h->t_b2); break;
-      case DIT_C_W1: rc = dit_add_f32(h, t, &h->c_w1); break;
-      case DIT_C_B1: rc = dit_add_f32(h, t, &h->c_b1); break;
-      case DIT_C_W2: rc = dit_add_f32(h, t, &h->c_w2); break;
-      case DIT_C_B2: rc = dit_add_f32(h, t, &h->c_b2); break;
-      case DIT_C_TABLE: rc = dit_add_f32(h, t, &h->c_table); break;
-      case DIT_PE_W: rc = dit_add_f32(h, t, &h->pe_w); break;
-      case DIT_PE_B: rc = dit_add_f32(h, t, &h->pe_b); break;
-      case DIT_DIFF: rc = dit_add_f32(h, t, &h->diff_table); break;
-      case DIT_QKV_W: rc = dit_add_linear(h, t, &w->w_qkv); break;
-      case DIT_QKV_B: rc = dit_add_f32(h, t, &w->b_qkv); break;
-      case DIT_PROJ_W: rc = dit_add_linear(h, t, &w->w_proj); break;
-      case DIT_PROJ_B: rc = dit_add_f32(h, t, &w->b_proj); break;
+      case DIT_FZ_FREQS: rc = f32(&h->fz_freqs); break;
+      case DIT_FZ_PHASES: rc = f32(&h->fz_phases); break;
+      case DIT_T_W1: rc = f32(&h->t_w1); break;
+      case DIT_T_B1: rc = f32(&h->t_b1); break;
+      case DIT_T_W2: rc = f32(&h->t_w2); break;
+      case DIT_T_B2: rc = f32(&h->t_b2); break;
+      case DIT_C_W1: rc = f32(&h->c_w1); break;
+      case DIT_C_B1: rc = f32(&h->c_b1); break;
+      case DIT_C_W2: rc = f32(&h->c_w2); break;
+      case DIT_C_B2: rc = f32(&h->c_b2); break;
+      case DIT_C_TABLE: rc = f32(&h->c_table); break;
+      case DIT_PE_W: rc = f32(&h->pe_w); break;
+      case DIT_PE_B: rc = f32(&h->pe_b); break;
+      case DIT_DIFF: rc = f32(&h->diff_table); break;
+      case DIT_QKV_W: rc = linear(&w->w_qkv); break;
+      case DIT_QKV_B: rc = f32(&w->b_qkv); break;
+      case DIT_PROJ_W: rc = linear(&w->w_proj); break;
+      case DIT_PROJ_B: rc = f32(&w->b_proj); break;
       case DIT_QKV_U: rc = dit_add_transposed(h, t, &w->ut); break;
       case DIT_PROJ_U: rc = dit_add_transposed(h, t, &w->put); break;
       case DIT_QKV_V: rc = dit_add_transposed(h, t, &w->vt); break;
       case DIT_PROJ_V: rc = dit_add_transposed(h, t, &w->pvt); break;
-      case DIT_QKV_BIAS: rc = dit_add_f32(h, t, &w->qkv_bias); break;
-      case DIT_PROJ_BIAS: rc = dit_add_f32(h, t, &w->proj_bias); break;
-      case DIT_FC1_W: rc = dit_add_linear(h, t, &w->w_fc1); break;
-      case DIT_FC1_B: rc = dit_add_f32(h, t, &w->b_fc1); break;
-      case DIT_FC2_W: rc = dit_add_linear(h, t, &w->w_fc2); break;
-      case DIT_FC2_B: rc = dit_add_f32(h, t, &w->b_fc2); break;
-      case DIT_FIN_W: rc = dit_add_f32(h, t, &h->fin_w); break;
-      case DIT_FIN_B: rc = dit_add_f32(h, t, &h->fin_b); break;
+      case DIT_QKV_BIAS: rc = f32(&w->qkv_bias); break;
+      case DIT_PROJ_BIAS: rc = f32(&w->proj_bias); break;
+      case DIT_FC1_W: rc = linear(&w->w_fc1); break;
+      case DIT_FC1_B: rc = f32(&w->b_fc1); break;
+      case DIT_FC2_W: rc = linear(&w->w_fc2); break;
+      case DIT_FC2_B: rc = f32(&w->b_fc2); break;
+      case DIT_FIN_W: rc = f32(&h->fin_w); break;
+      case DIT_FIN_B: rc = f32(&h->fin_b); break;
       default: break;  // the modulation kinds: bound above by their column
     }
     if (rc) return rc;
@@ -981,12 +897,12 @@ int dit_build(dfot_dit_s* h) {
   // derived tables (a fourier_noise model has no finite set of levels: nothing is tabulated, the embedding runs per frame in forward)
   if (!c.fourier_noise) {
     if ((rc = dit_upload(h, &h->freqs, dit_timestep_freqs(c)))) return rc;
-    if ((rc = dit_alloc(h, &h->feat, (size_t)h->lpad * c.noise_dim))) return rc;
-    if ((rc = dit_alloc(h, &h->thid, (size_t)h->lpad * hd))) return rc;
-    if ((rc = dit_alloc(h, &h->emb, (size_t)h->lpad * hd))) return rc;
+    if ((rc = h->alloc(&h->feat, (size_t)h->lpad * c.noise_dim))) return rc;
+    if ((rc = h->alloc(&h->thid, (size_t)h->lpad * hd))) return rc;
+    if ((rc = h->alloc(&h->emb, (size_t)h->lpad * hd))) return rc;
     const int nflag = h->diffm ? 2 : 1;  // variant 1: the conditioning also depends on the token kind (difference / frame)
-    if ((rc = dit_alloc(h, &h->semb, (size_t)nflag * h->lpad * hd))) return rc;
-    if ((rc = dit_alloc(h, &h->mod_table, (size_t)nflag * h->lpad * h->ldt))) return rc;
+    if ((rc = h->alloc(&h->semb, (size_t)nflag * h->lpad * hd))) return rc;
+    if ((rc = h->alloc(&h->mod_table, (size_t)nflag * h->lpad * h->ldt))) return rc;
   }
   // positional tables (dit_model.h): sinusoidal_2d at the patch embedding of the factorized variants (+ the temporal table of variant 2,
   // the RoPE-1D of variant 3's matrix attention), RoPE-3D of the full-attention variant
@@ -1007,8 +923,7 @@ extern "C" {
 
 int dfot_dit_destroy(dfot_dit_t h) {
   if (!h) return DFOT_OK;
-  for (void* p : h->owned) (void)hipFree(p);
-  for (void* p : h->ws_owned) (void)hipFree(p);
+  h->free_all();
   dit_cap_release(h);
   for (hipEvent_t e : h->ev_start) (void)hipEventDestroy(e);
   for (hipEvent_t e : h->ev_stop) (void)hipEventDestroy(e);
@@ -1092,35 +1007,24 @@ int dfot_dit_create_f(const dfot_dit_config_f* cfg, dfot_dit_t* out) {
   return dit_create_impl(dit_cfg(cfg->base, cfg->fourier_noise), out);
 }
 
-int dfot_dit_num_params(dfot_dit_t h) { return h ? (int)h->params.size() : 0; }
-const char* dfot_dit_param_name(dfot_dit_t h, int i) {
-  return (h && i >= 0 && i < (int)h->params.size()) ? h->params[i].name.c_str() : nullptr;
-}
+int dfot_dit_num_params(dfot_dit_t h) { return h ? h->params.count() : 0; }
+const char* dfot_dit_param_name(dfot_dit_t h, int i) { return h ? h->params.name(i) : nullptr; }
 int dfot_dit_param_shape(dfot_dit_t h, int i, int64_t shape[4], int* ndim) {
-  DFOT_REQUIRE(h && shape && ndim && i >= 0 && i < (int)h->params.size(), DFOT_ERR_ARG, "param_shape: bad argument");
-  *ndim = (int)h->params[i].shape.size();
-  for (int k = 0; k < *ndim; ++k) shape[k] = h->params[i].shape[k];
-  return DFOT_OK;
+  DFOT_REQUIRE(h, DFOT_ERR_ARG, "param_shape: bad argument");
+  return h->params.shape(i, shape, ndim);
 }
 
 int dfot_dit_load_weight(dfot_dit_t h, const char* name, const float* data, const int64_t* shape, int ndim, void* stream) {
-  DFOT_REQUIRE(h && name && data && shape, DFOT_ERR_ARG, "load_weight: null argument");
-  auto it = h->index.find(name);
-  DFOT_REQUIRE(it != h->index.end(), DFOT_ERR_NAME, "load_weight: unexpected key '%s'", name);
-  DitParam& p = h->params[it->second];
-  bool same = (int)p.shape.size() == ndim;
-  for (int k = 0; same && k < ndim; ++k) same = p.shape[k] == shape[k];
-  DFOT_REQUIRE(same, DFOT_ERR_SHAPE, "load_weight: size mismatch for '%s'", name);
-  int rc = p.load(data, (hipStream_t)stream);
-  if (rc) return rc;
-  p.loaded = true;
-  h->finalized = false;
-  return DFOT_OK;
+  DFOT_REQUIRE(h, DFOT_ERR_ARG, "load_weight: null argument");
+  int rc = h->params.load(name, data, shape, ndim, (hipStream_t)stream);
+  if (!rc) h->finalized = false;
+  return rc;
 }
 
 int dfot_dit_finalize(dfot_dit_t h, void* stream) {
   DFOT_REQUIRE(h, DFOT_ERR_ARG, "finalize: null handle");
-  for (const DitParam& p : h->params) DFOT_REQUIRE(p.loaded, DFOT_ERR_STATE, "finalize: missing key '%s'", p.name.c_str());
+  int rc = h->params.require_all_loaded();
+  if (rc) return rc;
   hipStream_t s = (hipStream_t)stream;
   const DitCfg& c = h->cfg;
   const int hd = c.hidden_size, L = c.timesteps;
@@ -1150,8 +1054,7 @@ int dfot_dit_finalize(dfot_dit_t h, void* stream) {
   g.A = h->semb; g.lda = hd; g.W = h->w_mod; g.M = nflag * h->lpad; g.N = (int)h->ldt; g.K = hd;
   g.bias = h->b_mod; g.out_f32 = h->mod_table; g.ldo = h->ldt;
   h->mod_variant = gemm_pick_variant(A_DENSE, g.M, g.N, g.K, true);
-  int rc = launch_gemm(A_DENSE, E_F32, h->mod_variant, g, s);
-  if (rc) return rc;
+  if ((rc = launch_gemm(A_DENSE, E_F32, h->mod_variant, g, s))) return rc;
   DFOT_CHECK_HIP(hipStreamSynchronize(s));
   h->finalized = true;
   return DFOT_OK;
@@ -1166,30 +1069,28 @@ int dfot_dit_reserve(dfot_dit_t h, int max_batch) {
                  "reserve: the captured attention maps of %zu blocks need %zu bytes at batch %d x %d tokens, above max_bytes %zu", h->cap_blocks.size(),
                  need, max_batch, h->cfg.max_tokens, h->cap_max_bytes);
   }
-  for (void* p : h->ws_owned) (void)hipFree(p);
-  h->ws_owned.clear();
-  h->ws_bytes = 0;
+  h->free_workspace();
   h->max_batch = 0;
   const DitCfg& c = h->cfg;
   const size_t rows = (size_t)max_batch * c.max_tokens * h->P;
   const size_t qkv = (size_t)max_batch * c.num_heads * c.max_tokens * h->P * h->dstride;
   int rc = 0;
-  if ((rc = dit_alloc(h, &h->X, rows * c.hidden_size, true))) return rc;
-  if ((rc = dit_alloc(h, &h->A, rows * c.hidden_size, true))) return rc;
-  if ((rc = dit_alloc(h, &h->q, qkv, true)) || (rc = dit_alloc(h, &h->k, qkv, true)) || (rc = dit_alloc(h, &h->v, qkv, true))) return rc;
+  if ((rc = h->alloc(&h->X, rows * c.hidden_size, true))) return rc;
+  if ((rc = h->alloc(&h->A, rows * c.hidden_size, true))) return rc;
+  if ((rc = h->alloc(&h->q, qkv, true)) || (rc = h->alloc(&h->k, qkv, true)) || (rc = h->alloc(&h->v, qkv, true))) return rc;
   // pad columns d..dstride of q/k/v are never written by the QKV epilogue: zero them once
   DFOT_CHECK_HIP(hipMemset(h->q, 0, qkv * sizeof(bf16)));
   DFOT_CHECK_HIP(hipMemset(h->k, 0, qkv * sizeof(bf16)));
   DFOT_CHECK_HIP(hipMemset(h->v, 0, qkv * sizeof(bf16)));
   const int hid_cols = c.variant != 0 && c.temporal_mlp_hidden > c.mlp_hidden ? c.temporal_mlp_hidden : c.mlp_hidden;
-  if (hid_cols && (rc = dit_alloc(h, &h->hid, rows * hid_cols, true))) return rc;
+  if (hid_cols && (rc = h->alloc(&h->hid, rows * hid_cols, true))) return rc;
   if (c.variant == 1) {
     const size_t frames = (size_t)max_batch * c.max_tokens;
-    if ((rc = dit_alloc(h, &h->T1, rows * c.hidden_size, true))) return rc;
-    if ((rc = dit_alloc(h, &h->W1, frames * c.embed_col_dim * c.hidden_size, true))) return rc;
-    if ((rc = dit_alloc(h, &h->W2, frames * c.embed_col_dim * c.hidden_size, true))) return rc;
-    if ((rc = dit_alloc(h, &h->Z, frames * c.embed_col_dim * 3 * c.hidden_size, true))) return rc;
-    if ((rc = dit_alloc(h, &h->idx, frames, true))) return rc;
+    if ((rc = h->alloc(&h->T1, rows * c.hidden_size, true))) return rc;
+    if ((rc = h->alloc(&h->W1, frames * c.embed_col_dim * c.hidden_size, true))) return rc;
+    if ((rc = h->alloc(&h->W2, frames * c.embed_col_dim * c.hidden_size, true))) return rc;
+    if ((rc = h->alloc(&h->Z, frames * c.embed_col_dim * 3 * c.hidden_size, true))) return rc;
+    if ((rc = h->alloc(&h->idx, frames, true))) return rc;
   }
   if (c.variant == 3 && c.embed_col_dim <= 32) {
     // narrow column widths (facmat_narrow.hip): no transposes, so T1 holds the expanded frames and W2 is not needed.  The right-factor
@@ -1197,8 +1098,8 @@ int dfot_dit_reserve(dfot_dit_t h, int max_batch) {
     // and the attention write the real rows only, so a pad row holds zeros or a real row of an earlier, larger call: finite operands whose
     // products (rows of Z past frames * E) are never read.
     const size_t frames = (size_t)max_batch * c.max_tokens, wrows = (frames * c.embed_col_dim + 127) / 128 * 128;
-    if ((rc = dit_alloc(h, &h->T1, frames * h->P * c.hidden_size, true))) return rc;
-    if ((rc = dit_alloc(h, &h->W1, wrows * c.hidden_size, true)) || (rc = dit_alloc(h, &h->Z, 3 * wrows * c.hidden_size, true))) return rc;
+    if ((rc = h->alloc(&h->T1, frames * h->P * c.hidden_size, true))) return rc;
+    if ((rc = h->alloc(&h->W1, wrows * c.hidden_size, true)) || (rc = h->alloc(&h->Z, 3 * wrows * c.hidden_size, true))) return rc;
     DFOT_CHECK_HIP(hipMemset(h->W1, 0, wrows * c.hidden_size * sizeof(bf16)));
     DFOT_CHECK_HIP(hipMemset(h->Z, 0, 3 * wrows * c.hidden_size * sizeof(bf16)));
   } else if (c.variant == 3) {
@@ -1206,8 +1107,8 @@ int dfot_dit_reserve(dfot_dit_t h, int max_batch) {
     // frame count runs them on one more frame.  That frame holds the zeros written here or a real frame of an earlier, larger call (the
     // transposes and the attention kernel touch the real frames only): finite operands whose products are never read.
     const size_t frames = (size_t)max_batch * c.max_tokens + 1, fe = frames * c.embed_col_dim * c.hidden_size;
-    if ((rc = dit_alloc(h, &h->T1, frames * h->P * c.hidden_size, true))) return rc;
-    if ((rc = dit_alloc(h, &h->W1, fe, true)) || (rc = dit_alloc(h, &h->W2, fe, true)) || (rc = dit_alloc(h, &h->Z, 3 * fe, true))) return rc;
+    if ((rc = h->alloc(&h->T1, frames * h->P * c.hidden_size, true))) return rc;
+    if ((rc = h->alloc(&h->W1, fe, true)) || (rc = h->alloc(&h->W2, fe, true)) || (rc = h->alloc(&h->Z, 3 * fe, true))) return rc;
     DFOT_CHECK_HIP(hipMemset(h->T1, 0, frames * h->P * c.hidden_size * sizeof(bf16)));
     DFOT_CHECK_HIP(hipMemset(h->W1, 0, fe * sizeof(bf16)));
     DFOT_CHECK_HIP(hipMemset(h->W2, 0, fe * sizeof(bf16)));
@@ -1215,13 +1116,13 @@ int dfot_dit_reserve(dfot_dit_t h, int max_batch) {
   }
   if (c.cond_type != DFOT_COND_NONE || c.fourier_noise) {
     const size_t frames = (size_t)max_batch * c.max_tokens;
-    if (c.fourier_noise && ((rc = dit_alloc(h, &h->nfeat, frames * c.noise_dim, true)) || (rc = dit_alloc(h, &h->nact, frames * c.hidden_size, true)))) return rc;
+    if (c.fourier_noise && ((rc = h->alloc(&h->nfeat, frames * c.noise_dim, true)) || (rc = h->alloc(&h->nact, frames * c.hidden_size, true)))) return rc;
     h->fpad = (int)((frames + 255) / 256 * 256);  // whole row tiles of every GEMM form finalize() may have picked
-    if ((rc = dit_alloc(h, &h->csemb, (size_t)h->fpad * c.hidden_size, true))) return rc;
+    if ((rc = h->alloc(&h->csemb, (size_t)h->fpad * c.hidden_size, true))) return rc;
     DFOT_CHECK_HIP(hipMemset(h->csemb, 0, (size_t)h->fpad * c.hidden_size * sizeof(bf16)));  // rows past the batch: finite operands
-    if ((rc = dit_alloc(h, &h->cmod, (size_t)h->fpad * h->ldt, true))) return rc;
-    if ((rc = dit_alloc(h, &h->cemb, frames * c.hidden_size, true))) return rc;
-    if ((rc = dit_alloc(h, &h->cidx, frames, true))) return rc;
+    if ((rc = h->alloc(&h->cmod, (size_t)h->fpad * h->ldt, true))) return rc;
+    if ((rc = h->alloc(&h->cemb, frames * c.hidden_size, true))) return rc;
+    if ((rc = h->alloc(&h->cidx, frames, true))) return rc;
   }
   if (h->cap_form != DFOT_ATTN_MAP_OFF && (rc = dit_cap_alloc(h, max_batch))) return rc;
   h->max_batch = max_batch;

@@ -12,14 +12,14 @@
 // ln_share_kernel writes both the normalised row (fp32, the new residual base, in place) and its modulated bf16 copy (the GEMM operand);
 // the gated GEMM epilogue then adds onto the normalised row.
 #include <cmath>
-#include <functional>
-#include <map>
 #include <string>
 #include <vector>
 
 #include "dfot_hip.h"
+#include "engine_device.h"
 #include "gemm.h"
 #include "kernels.h"
+#include "level_embed.h"
 
 namespace dfot {
 namespace {
@@ -28,55 +28,11 @@ typedef __attribute__((ext_vector_type(4))) float float4v;
 constexpr int D1_FREQ = 256;     // TimestepEmbedder.frequency_embedding_size
 constexpr int D1_MAX_CHUNKS = 8; // float4 chunks per lane of a row: hidden <= 2048
 
-struct D1Param {
-  std::string name;
-  std::vector<int64_t> shape;
-  std::function<int(const float*, hipStream_t)> load;
-  bool loaded = false;
-};
-
 struct D1Block {
   bf16 *w_qkv = nullptr, *w_proj = nullptr, *w_fc1 = nullptr, *w_fc2 = nullptr;
   float *b_qkv = nullptr, *b_proj = nullptr, *b_fc1 = nullptr, *b_fc2 = nullptr;
   long mod = 0;  // column of this block's (shift_msa|scale_msa|gate_msa|shift_mlp|scale_mlp|gate_mlp) inside a mod_table row
 };
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
-// (the two finalize-time kernels below restate dit.hip's, which are local to that translation unit and stay untouched)
-// timestep_embedding(t, 256) (dit_model.py:133-150): feat[level] = [cos(level * f_i) | sin(level * f_i)], f_i = exp(-ln(10000) i / 128)
-__global__ void d1_features_kernel(const float* __restrict__ freqs, float* __restrict__ feat, int levels) {
-  const int half = D1_FREQ / 2;
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (long)levels * D1_FREQ) return;
-  const int lv = (int)(i / D1_FREQ), c = (int)(i % D1_FREQ);
-  const float a = __fmul_rn((float)lv, freqs[c < half ? c : c - half]);
-  feat[i] = c < half ? cosf(a) : sinf(a);
-}
-
-// v = act(b[o] + sum_k W[o][k] * in[r][k]); one wave per (o, r); ACT 1 = SiLU; out (optional) = v, out_silu_bf16 (optional) = bf16(SiLU(v))
-template <int ACT>
-__global__ __launch_bounds__(256) void d1_rows_linear_kernel(const float* __restrict__ in, const float* __restrict__ w,
-                                                             const float* __restrict__ b, float* __restrict__ out,
-                                                             bf16* __restrict__ out_silu_bf16, int kdim, int odim) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int o = blockIdx.x * 4 + wave;
-  const long r = blockIdx.y;
-  if (o >= odim) return;
-  float acc = 0.f;
-  for (int i = lane; i < kdim; i += 64) acc += w[(long)o * kdim + i] * in[r * kdim + i];
-  acc = wave_sum(acc);
-  if (lane == 0) {
-    float v = acc + b[o];
-    if (ACT == 1) v = silu_f(v);
-    if (out) out[r * odim + o] = v;
-    if (out_silu_bf16) out_silu_bf16[r * odim + o] = f2bf(silu_f(v));
-  }
-}
 
 __global__ void d1_clamp_levels_kernel(const int* __restrict__ levels, int* __restrict__ idx, int n, int max_level) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -196,14 +152,11 @@ __global__ __launch_bounds__(256) void d1_final_kernel(const float* __restrict__
 
 using namespace dfot;
 
-struct dfot_dit1d_s {
+struct dfot_dit1d_s : EngineDevice {
+  dfot_dit1d_s() : EngineDevice("dit1d ") {}
   dfot_dit1d_config cfg{};
   int d = 0, dstride = 0, lpad = 0, ntok = 0;  // head dim, q/k/v row stride, level count padded to the GEMM row tile, T * L
   long ldt = 0;                                // mod_table row: depth * 6 * hidden
-  std::vector<D1Param> params;
-  std::map<std::string, int> index;
-  std::vector<void*> owned, ws_owned;
-  size_t ws_bytes = 0;
   // weights
   float *pos = nullptr, *x_w = nullptr, *x_b = nullptr, *t_w1 = nullptr, *t_b1 = nullptr, *t_w2 = nullptr, *t_b2 = nullptr,
         *fin_w = nullptr, *fin_b = nullptr, *b_mod = nullptr;
@@ -223,51 +176,6 @@ struct dfot_dit1d_s {
 namespace dfot {
 namespace {
 
-template <typename T>
-int d1_alloc(dfot_dit1d_s* h, T** out, size_t count, bool workspace = false) {
-  void* p = nullptr;
-  const size_t bytes = count * sizeof(T);
-  DFOT_CHECK_HIP(hipMalloc(&p, bytes ? bytes : 16));
-  (workspace ? h->ws_owned : h->owned).push_back(p);
-  if (workspace) h->ws_bytes += bytes;
-  *out = reinterpret_cast<T*>(p);
-  return DFOT_OK;
-}
-
-void d1_add(dfot_dit1d_s* h, const std::string& name, std::vector<int64_t> shape, std::function<int(const float*, hipStream_t)> load) {
-  h->index[name] = (int)h->params.size();
-  h->params.push_back(D1Param{name, std::move(shape), std::move(load), false});
-}
-
-long d1_numel(const std::vector<int64_t>& shape) {
-  long n = 1;
-  for (int64_t s : shape) n *= s;
-  return n;
-}
-
-// fp32 as given, at dst
-void d1_add_slice(dfot_dit1d_s* h, const std::string& name, std::vector<int64_t> shape, float* dst) {
-  const size_t n = (size_t)d1_numel(shape);
-  d1_add(h, name, std::move(shape), [=](const float* src, hipStream_t s) {
-    DFOT_CHECK_HIP(hipMemcpyAsync(dst, src, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-    return DFOT_OK;
-  });
-}
-int d1_add_f32(dfot_dit1d_s* h, const std::string& name, std::vector<int64_t> shape, float** dst) {
-  int rc = d1_alloc(h, dst, (size_t)d1_numel(shape));
-  if (!rc) d1_add_slice(h, name, std::move(shape), *dst);
-  return rc;
-}
-// Linear weight [rows][k] fp32 -> bf16 at dst (row stride k)
-void d1_add_bf16(dfot_dit1d_s* h, const std::string& name, int rows, int k, bf16* dst) {
-  d1_add(h, name, {rows, k}, [=](const float* src, hipStream_t s) { return launch_pack_rows(src, dst, nullptr, rows, k, k, k, 0, s); });
-}
-int d1_add_linear(dfot_dit1d_s* h, const std::string& name, int rows, int k, bf16** dst) {
-  int rc = d1_alloc(h, dst, (size_t)rows * k);
-  if (!rc) d1_add_bf16(h, name, rows, k, *dst);
-  return rc;
-}
-
 int d1_build(dfot_dit1d_s* h) {
   const dfot_dit1d_config& c = h->cfg;
   const int hd = c.hidden, mh = c.mlp_hidden;
@@ -277,38 +185,38 @@ int d1_build(dfot_dit1d_s* h) {
   h->ldt = (long)c.depth * 6 * hd;
   h->lpad = (c.timesteps + 255) / 256 * 256;
   int rc = 0;
-  if ((rc = d1_alloc(h, &h->w_mod, (size_t)h->ldt * hd)) || (rc = d1_alloc(h, &h->b_mod, (size_t)h->ldt))) return rc;
+  if ((rc = h->alloc(&h->w_mod, (size_t)h->ldt * hd)) || (rc = h->alloc(&h->b_mod, (size_t)h->ldt))) return rc;
   h->blocks.resize(c.depth);
   // registration order == the reference module's state_dict order
-  if ((rc = d1_add_f32(h, "pos_embed", {1, h->ntok, hd}, &h->pos))) return rc;
-  if ((rc = d1_add_f32(h, "x_embedder.weight", {hd, c.in_channels}, &h->x_w)) || (rc = d1_add_f32(h, "x_embedder.bias", {hd}, &h->x_b))) return rc;
-  if ((rc = d1_add_f32(h, "t_embedder.mlp.0.weight", {hd, D1_FREQ}, &h->t_w1)) || (rc = d1_add_f32(h, "t_embedder.mlp.0.bias", {hd}, &h->t_b1)) ||
-      (rc = d1_add_f32(h, "t_embedder.mlp.2.weight", {hd, hd}, &h->t_w2)) || (rc = d1_add_f32(h, "t_embedder.mlp.2.bias", {hd}, &h->t_b2)))
+  if ((rc = h->add_f32("pos_embed", {1, h->ntok, hd}, &h->pos))) return rc;
+  if ((rc = h->add_f32("x_embedder.weight", {hd, c.in_channels}, &h->x_w)) || (rc = h->add_f32("x_embedder.bias", {hd}, &h->x_b))) return rc;
+  if ((rc = h->add_f32("t_embedder.mlp.0.weight", {hd, D1_FREQ}, &h->t_w1)) || (rc = h->add_f32("t_embedder.mlp.0.bias", {hd}, &h->t_b1)) ||
+      (rc = h->add_f32("t_embedder.mlp.2.weight", {hd, hd}, &h->t_w2)) || (rc = h->add_f32("t_embedder.mlp.2.bias", {hd}, &h->t_b2)))
     return rc;
   for (int i = 0; i < c.depth; ++i) {
     D1Block& w = h->blocks[i];
     const std::string p = "blocks." + std::to_string(i) + ".";
     w.mod = (long)i * 6 * hd;
-    if ((rc = d1_add_linear(h, p + "attn.qkv.weight", 3 * hd, hd, &w.w_qkv)) || (rc = d1_add_f32(h, p + "attn.qkv.bias", {3 * hd}, &w.b_qkv)) ||
-        (rc = d1_add_linear(h, p + "attn.proj.weight", hd, hd, &w.w_proj)) || (rc = d1_add_f32(h, p + "attn.proj.bias", {hd}, &w.b_proj)) ||
-        (rc = d1_add_linear(h, p + "mlp.fc1.weight", mh, hd, &w.w_fc1)) || (rc = d1_add_f32(h, p + "mlp.fc1.bias", {mh}, &w.b_fc1)) ||
-        (rc = d1_add_linear(h, p + "mlp.fc2.weight", hd, mh, &w.w_fc2)) || (rc = d1_add_f32(h, p + "mlp.fc2.bias", {hd}, &w.b_fc2)))
+    if ((rc = h->add_linear(p + "attn.qkv.weight", 3 * hd, hd, &w.w_qkv)) || (rc = h->add_f32(p + "attn.qkv.bias", {3 * hd}, &w.b_qkv)) ||
+        (rc = h->add_linear(p + "attn.proj.weight", hd, hd, &w.w_proj)) || (rc = h->add_f32(p + "attn.proj.bias", {hd}, &w.b_proj)) ||
+        (rc = h->add_linear(p + "mlp.fc1.weight", mh, hd, &w.w_fc1)) || (rc = h->add_f32(p + "mlp.fc1.bias", {mh}, &w.b_fc1)) ||
+        (rc = h->add_linear(p + "mlp.fc2.weight", hd, mh, &w.w_fc2)) || (rc = h->add_f32(p + "mlp.fc2.bias", {hd}, &w.b_fc2)))
       return rc;
-    d1_add_bf16(h, p + "adaLN_modulation.1.weight", 6 * hd, hd, h->w_mod + w.mod * hd);
-    d1_add_slice(h, p + "adaLN_modulation.1.bias", {6 * hd}, h->b_mod + w.mod);
+    h->add_bf16(p + "adaLN_modulation.1.weight", 6 * hd, hd, h->w_mod + w.mod * hd);
+    h->add_slice(p + "adaLN_modulation.1.bias", {6 * hd}, h->b_mod + w.mod);
   }
-  if ((rc = d1_add_f32(h, "final_layer.1.weight", {c.in_channels, hd}, &h->fin_w)) ||
-      (rc = d1_add_f32(h, "final_layer.1.bias", {c.in_channels}, &h->fin_b)))
+  if ((rc = h->add_f32("final_layer.1.weight", {c.in_channels, hd}, &h->fin_w)) ||
+      (rc = h->add_f32("final_layer.1.bias", {c.in_channels}, &h->fin_b)))
     return rc;
 
   std::vector<float> freqs(D1_FREQ / 2);
   for (int i = 0; i < D1_FREQ / 2; ++i)  // torch.exp(-math.log(10000) * arange(half, dtype=float32) / half): fp32 throughout
     freqs[i] = expf((float)(-std::log(10000.0)) * (float)i / (float)(D1_FREQ / 2));
-  if ((rc = d1_alloc(h, &h->freqs, freqs.size()))) return rc;
+  if ((rc = h->alloc(&h->freqs, freqs.size()))) return rc;
   DFOT_CHECK_HIP(hipMemcpy(h->freqs, freqs.data(), freqs.size() * sizeof(float), hipMemcpyHostToDevice));
-  if ((rc = d1_alloc(h, &h->feat, (size_t)h->lpad * D1_FREQ)) || (rc = d1_alloc(h, &h->thid, (size_t)h->lpad * hd)) ||
-      (rc = d1_alloc(h, &h->semb, (size_t)h->lpad * hd)) ||
-      (rc = d1_alloc(h, &h->mod_table, (size_t)h->lpad * h->ldt)))
+  if ((rc = h->alloc(&h->feat, (size_t)h->lpad * D1_FREQ)) || (rc = h->alloc(&h->thid, (size_t)h->lpad * hd)) ||
+      (rc = h->alloc(&h->semb, (size_t)h->lpad * hd)) ||
+      (rc = h->alloc(&h->mod_table, (size_t)h->lpad * h->ldt)))
     return rc;
   return DFOT_OK;
 }
@@ -320,8 +228,7 @@ extern "C" {
 
 int dfot_dit1d_destroy(dfot_dit1d_t h) {
   if (!h) return DFOT_OK;
-  for (void* p : h->owned) (void)hipFree(p);
-  for (void* p : h->ws_owned) (void)hipFree(p);
+  h->free_all();
   delete h;
   return DFOT_OK;
 }
@@ -353,52 +260,40 @@ int dfot_dit1d_create(const dfot_dit1d_config* cfg, dfot_dit1d_t* out) {
   return DFOT_OK;
 }
 
-int dfot_dit1d_num_params(dfot_dit1d_t h) { return h ? (int)h->params.size() : 0; }
-const char* dfot_dit1d_param_name(dfot_dit1d_t h, int i) {
-  return (h && i >= 0 && i < (int)h->params.size()) ? h->params[i].name.c_str() : nullptr;
-}
+int dfot_dit1d_num_params(dfot_dit1d_t h) { return h ? h->params.count() : 0; }
+const char* dfot_dit1d_param_name(dfot_dit1d_t h, int i) { return h ? h->params.name(i) : nullptr; }
 int dfot_dit1d_param_shape(dfot_dit1d_t h, int i, int64_t shape[4], int* ndim) {
-  DFOT_REQUIRE(h && shape && ndim && i >= 0 && i < (int)h->params.size(), DFOT_ERR_ARG, "dit1d param_shape: bad argument");
-  *ndim = (int)h->params[i].shape.size();
-  for (int k = 0; k < *ndim; ++k) shape[k] = h->params[i].shape[k];
-  return DFOT_OK;
+  DFOT_REQUIRE(h, DFOT_ERR_ARG, "dit1d param_shape: bad argument");
+  return h->params.shape(i, shape, ndim);
 }
 
 int dfot_dit1d_load_weight(dfot_dit1d_t h, const char* name, const float* data, const int64_t* shape, int ndim, void* stream) {
-  DFOT_REQUIRE(h && name && data && shape, DFOT_ERR_ARG, "dit1d load_weight: null argument");
-  auto it = h->index.find(name);
-  DFOT_REQUIRE(it != h->index.end(), DFOT_ERR_NAME, "dit1d load_weight: unexpected key '%s'", name);
-  D1Param& p = h->params[it->second];
-  bool same = (int)p.shape.size() == ndim;
-  for (int k = 0; same && k < ndim; ++k) same = p.shape[k] == shape[k];
-  DFOT_REQUIRE(same, DFOT_ERR_SHAPE, "dit1d load_weight: size mismatch for '%s'", name);
-  int rc = p.load(data, (hipStream_t)stream);
-  if (rc) return rc;
-  p.loaded = true;
-  h->finalized = false;
-  return DFOT_OK;
+  DFOT_REQUIRE(h, DFOT_ERR_ARG, "dit1d load_weight: null argument");
+  int rc = h->params.load(name, data, shape, ndim, (hipStream_t)stream);
+  if (!rc) h->finalized = false;
+  return rc;
 }
 
 int dfot_dit1d_finalize(dfot_dit1d_t h, void* stream) {
   DFOT_REQUIRE(h, DFOT_ERR_ARG, "dit1d finalize: null handle");
-  for (const D1Param& p : h->params) DFOT_REQUIRE(p.loaded, DFOT_ERR_STATE, "dit1d finalize: missing key '%s'", p.name.c_str());
+  int rc = h->params.require_all_loaded();
+  if (rc) return rc;
   hipStream_t s = (hipStream_t)stream;
   const dfot_dit1d_config& c = h->cfg;
   const int hd = c.hidden, Lv = c.timesteps;
   // embedding of every level: [cos | sin] -> Linear -> SiLU -> Linear (t) ; semb = bf16(SiLU(t)) feeds every adaLN_modulation
-  hipLaunchKernelGGL(d1_features_kernel, dim3(cdiv((long)Lv * D1_FREQ, 256)), dim3(256), 0, s, h->freqs, h->feat, Lv);
+  hipLaunchKernelGGL(tstep_features_kernel, dim3(cdiv((long)Lv * D1_FREQ, 256)), dim3(256), 0, s, h->freqs, h->feat, Lv, D1_FREQ);
   DFOT_CHECK_HIP(hipGetLastError());
-  hipLaunchKernelGGL(d1_rows_linear_kernel<1>, dim3(cdiv(hd, 4), Lv), dim3(256), 0, s, h->feat, h->t_w1, h->t_b1, h->thid, (bf16*)nullptr,
+  hipLaunchKernelGGL(rows_linear_kernel<1>, dim3(cdiv(hd, 4), Lv), dim3(256), 0, s, h->feat, h->t_w1, h->t_b1, h->thid, (bf16*)nullptr,
                      D1_FREQ, hd);
   DFOT_CHECK_HIP(hipGetLastError());
   DFOT_CHECK_HIP(hipMemsetAsync(h->semb, 0, (size_t)h->lpad * hd * sizeof(bf16), s));
-  hipLaunchKernelGGL(d1_rows_linear_kernel<0>, dim3(cdiv(hd, 4), Lv), dim3(256), 0, s, h->thid, h->t_w2, h->t_b2, (float*)nullptr, h->semb, hd, hd);
+  hipLaunchKernelGGL(rows_linear_kernel<0>, dim3(cdiv(hd, 4), Lv), dim3(256), 0, s, h->thid, h->t_w2, h->t_b2, (float*)nullptr, h->semb, hd, hd);
   DFOT_CHECK_HIP(hipGetLastError());
   GemmArgs g;
   g.A = h->semb; g.lda = hd; g.W = h->w_mod; g.M = h->lpad; g.N = (int)h->ldt; g.K = hd;
   g.bias = h->b_mod; g.out_f32 = h->mod_table; g.ldo = h->ldt;
-  int rc = launch_gemm(A_DENSE, E_F32, gemm_pick_variant(A_DENSE, g.M, g.N, g.K, true), g, s);
-  if (rc) return rc;
+  if ((rc = launch_gemm(A_DENSE, E_F32, gemm_pick_variant(A_DENSE, g.M, g.N, g.K, true), g, s))) return rc;
   DFOT_CHECK_HIP(hipStreamSynchronize(s));
   h->finalized = true;
   return DFOT_OK;
@@ -407,22 +302,20 @@ int dfot_dit1d_finalize(dfot_dit1d_t h, void* stream) {
 int dfot_dit1d_reserve(dfot_dit1d_t h, int max_batch) {
   DFOT_REQUIRE(h && max_batch > 0, DFOT_ERR_ARG, "dit1d reserve: bad argument");
   if (max_batch <= h->max_batch) return DFOT_OK;
-  for (void* p : h->ws_owned) (void)hipFree(p);
-  h->ws_owned.clear();
-  h->ws_bytes = 0;
+  h->free_workspace();
   h->max_batch = 0;
   const dfot_dit1d_config& c = h->cfg;
   const size_t rows = (size_t)max_batch * h->ntok;
   const size_t qkv = (size_t)max_batch * c.heads * h->ntok * h->dstride;
   int rc = 0;
-  if ((rc = d1_alloc(h, &h->X, rows * c.hidden, true)) || (rc = d1_alloc(h, &h->A, rows * c.hidden, true))) return rc;
-  if ((rc = d1_alloc(h, &h->q, qkv, true)) || (rc = d1_alloc(h, &h->k, qkv, true)) || (rc = d1_alloc(h, &h->v, qkv, true))) return rc;
+  if ((rc = h->alloc(&h->X, rows * c.hidden, true)) || (rc = h->alloc(&h->A, rows * c.hidden, true))) return rc;
+  if ((rc = h->alloc(&h->q, qkv, true)) || (rc = h->alloc(&h->k, qkv, true)) || (rc = h->alloc(&h->v, qkv, true))) return rc;
   // pad columns d..dstride of q/k/v are never written by the QKV epilogue: zero them once
   DFOT_CHECK_HIP(hipMemset(h->q, 0, qkv * sizeof(bf16)));
   DFOT_CHECK_HIP(hipMemset(h->k, 0, qkv * sizeof(bf16)));
   DFOT_CHECK_HIP(hipMemset(h->v, 0, qkv * sizeof(bf16)));
-  if ((rc = d1_alloc(h, &h->hid, rows * c.mlp_hidden, true))) return rc;
-  if ((rc = d1_alloc(h, &h->idx, (size_t)max_batch * c.max_tokens, true))) return rc;
+  if ((rc = h->alloc(&h->hid, rows * c.mlp_hidden, true))) return rc;
+  if ((rc = h->alloc(&h->idx, (size_t)max_batch * c.max_tokens, true))) return rc;
   h->max_batch = max_batch;
   return DFOT_OK;
 }

@@ -6,12 +6,11 @@
 #include <cstdarg>
 #include <cstdlib>
 #include <cstring>
-#include <functional>
-#include <map>
 #include <string>
 #include <vector>
 
 #include "dfot_hip.h"
+#include "engine_device.h"
 #include "gemm.h"
 #include "kernels.h"
 
@@ -63,18 +62,12 @@ struct ConvW {
   float* b = nullptr;
 };
 
-struct Param {
-  std::string name;
-  std::vector<int64_t> shape;
-  std::function<int(const float*, hipStream_t)> load;
-  bool loaded = false;
-};
-
 }  // namespace dfot
 
 using namespace dfot;
 
-struct dfot_uvit_s {
+struct dfot_uvit_s : EngineDevice {
+  dfot_uvit_s() : EngineDevice("") {}
   dfot_uvit_config cfg{};
   int T = 0, E = 0, heads = 0, r[4] = {0, 0, 0, 0}, ch[4] = {0, 0, 0, 0};
   int kpose = 0;  // padded K of the pose patch-embed GEMM
@@ -84,9 +77,6 @@ struct dfot_uvit_s {
   int act_dim = 0;          // external_cond_dim of the action MLP, 0 = the model has no external_cond_embedding
   bool act_dropout = false; // external_cond_dropout > 0: the keys sit under ".embedding." and the per-video mask is honoured
   float *ac_w1 = nullptr, *ac_b1 = nullptr, *ac_w2 = nullptr, *ac_b2 = nullptr;
-  std::vector<Param> params;
-  std::map<std::string, int> index;
-  std::vector<void*> owned;  // every hipMalloc'ed block
 
   // weights
   float *ne_freqs = nullptr, *ne_phases = nullptr, *ne_w1 = nullptr, *ne_b1 = nullptr, *ne_w2 = nullptr, *ne_b2 = nullptr;
@@ -103,8 +93,6 @@ struct dfot_uvit_s {
 
   // workspace
   int max_batch = 0;
-  size_t ws_bytes = 0;
-  std::vector<void*> ws_owned;
   float *nemb = nullptr, *nhid = nullptr, *X[4] = {nullptr, nullptr, nullptr, nullptr}, *HSA[3] = {nullptr, nullptr, nullptr}, *tmp = nullptr,
         *gn_partial = nullptr, *gn_partial2 = nullptr, *gn_stats = nullptr, *sv = nullptr;
   int gn1_nblk = 0;  // > 0: gn_partial holds that many partial blocks per image for the next GroupNorm input
@@ -149,69 +137,36 @@ struct dfot_uvit_s {
 
 namespace dfot {
 
-template <typename T>
-static int dev_alloc(dfot_uvit_s* h, T** out, size_t count, bool workspace = false) {
-  void* p = nullptr;
-  const size_t bytes = count * sizeof(T);
-  DFOT_CHECK_HIP(hipMalloc(&p, bytes ? bytes : 16));
-  (workspace ? h->ws_owned : h->owned).push_back(p);
-  if (workspace) h->ws_bytes += bytes;
-  *out = reinterpret_cast<T*>(p);
-  return DFOT_OK;
-}
-
-static int copy_f32(float* dst, const float* src, size_t n, hipStream_t s) {
-  DFOT_CHECK_HIP(hipMemcpyAsync(dst, src, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-  return DFOT_OK;
-}
-
-static void add_param(dfot_uvit_s* h, const std::string& name, std::vector<int64_t> shape,
-                      std::function<int(const float*, hipStream_t)> load) {
-  h->index[name] = (int)h->params.size();
-  h->params.push_back(Param{name, std::move(shape), std::move(load), false});
-}
-
-// plain fp32 tensor kept as-is
-static int add_f32(dfot_uvit_s* h, const std::string& name, std::vector<int64_t> shape, float** dst) {
-  size_t n = 1;
-  for (auto d : shape) n *= (size_t)d;
-  int rc = dev_alloc(h, dst, n);
-  if (rc) return rc;
-  float* d = *dst;
-  add_param(h, name, shape, [d, n](const float* src, hipStream_t s) { return copy_f32(d, src, n, s); });
-  return DFOT_OK;
-}
-
 static int add_res_block(dfot_uvit_s* h, const std::string& pre, int c, ResW* w) {
   const int e = h->E;
   w->c = c;
   int rc = 0;
-  if ((rc = dev_alloc(h, &w->w_film, (size_t)2 * c * e))) return rc;
-  if ((rc = dev_alloc(h, &w->b_film_raw, (size_t)2 * c))) return rc;
-  if ((rc = dev_alloc(h, &w->b_film, (size_t)2 * c))) return rc;
-  if ((rc = dev_alloc(h, &w->w1, (size_t)c * 9 * c))) return rc;
-  if ((rc = dev_alloc(h, &w->w2, (size_t)c * 9 * c))) return rc;
+  if ((rc = h->alloc(&w->w_film, (size_t)2 * c * e))) return rc;
+  if ((rc = h->alloc(&w->b_film_raw, (size_t)2 * c))) return rc;
+  if ((rc = h->alloc(&w->b_film, (size_t)2 * c))) return rc;
+  if ((rc = h->alloc(&w->w1, (size_t)c * 9 * c))) return rc;
+  if ((rc = h->alloc(&w->w2, (size_t)c * 9 * c))) return rc;
   const int lvl = c == h->ch[0] ? 0 : 1;
   int* map = h->film_map[lvl];
   bf16* wf = w->w_film;
-  add_param(h, pre + ".emb_layer.weight", {2 * c, e, 1, 1}, [=](const float* src, hipStream_t s) {
+  h->params.add(pre + ".emb_layer.weight", {2 * c, e, 1, 1}, [=](const float* src, hipStream_t s) {
     return launch_pack_rows(src, wf, map, 2 * c, e, e, e, 0, s);
   });
   float *braw = w->b_film_raw, *bre = w->b_film;
-  add_param(h, pre + ".emb_layer.bias", {2 * c}, [=](const float* src, hipStream_t s) {
+  h->params.add(pre + ".emb_layer.bias", {2 * c}, [=](const float* src, hipStream_t s) {
     int r2 = copy_f32(braw, src, 2 * c, s);
     return r2 ? r2 : launch_gather_f32(braw, bre, map, 2 * c, s);
   });
-  if ((rc = add_f32(h, pre + ".in_layers.0.weight", {c}, &w->g1))) return rc;
-  if ((rc = add_f32(h, pre + ".in_layers.0.bias", {c}, &w->be1))) return rc;
+  if ((rc = h->add_f32(pre + ".in_layers.0.weight", {c}, &w->g1))) return rc;
+  if ((rc = h->add_f32(pre + ".in_layers.0.bias", {c}, &w->be1))) return rc;
   bf16* w1 = w->w1;
-  add_param(h, pre + ".in_layers.2.weight", {c, c, 3, 3}, [=](const float* src, hipStream_t s) { return launch_pack_conv3(src, w1, c, c, s); });
-  if ((rc = add_f32(h, pre + ".in_layers.2.bias", {c}, &w->bias1))) return rc;
-  if ((rc = add_f32(h, pre + ".out_norm.weight", {c}, &w->g2))) return rc;
-  if ((rc = add_f32(h, pre + ".out_norm.bias", {c}, &w->be2))) return rc;
+  h->params.add(pre + ".in_layers.2.weight", {c, c, 3, 3}, [=](const float* src, hipStream_t s) { return launch_pack_conv3(src, w1, c, c, s); });
+  if ((rc = h->add_f32(pre + ".in_layers.2.bias", {c}, &w->bias1))) return rc;
+  if ((rc = h->add_f32(pre + ".out_norm.weight", {c}, &w->g2))) return rc;
+  if ((rc = h->add_f32(pre + ".out_norm.bias", {c}, &w->be2))) return rc;
   bf16* w2 = w->w2;
-  add_param(h, pre + ".out_rest.1.weight", {c, c, 3, 3}, [=](const float* src, hipStream_t s) { return launch_pack_conv3(src, w2, c, c, s); });
-  if ((rc = add_f32(h, pre + ".out_rest.1.bias", {c}, &w->bias2))) return rc;
+  h->params.add(pre + ".out_rest.1.weight", {c, c, 3, 3}, [=](const float* src, hipStream_t s) { return launch_pack_conv3(src, w2, c, c, s); });
+  if ((rc = h->add_f32(pre + ".out_rest.1.bias", {c}, &w->bias2))) return rc;
   return DFOT_OK;
 }
 
@@ -219,39 +174,36 @@ static int add_tr_block(dfot_uvit_s* h, const std::string& pre, int lvl, TrW* w)
   const int e = h->E, c = h->ch[lvl], d = c / h->heads;
   w->c = c;
   int rc = 0;
-  if ((rc = dev_alloc(h, &w->w_film, (size_t)2 * c * e))) return rc;
-  if ((rc = dev_alloc(h, &w->b_film_raw, (size_t)2 * c))) return rc;
-  if ((rc = dev_alloc(h, &w->b_film, (size_t)2 * c))) return rc;
-  if ((rc = dev_alloc(h, &w->w_fused, (size_t)7 * c * c))) return rc;
-  if ((rc = dev_alloc(h, &w->w_out, (size_t)c * 5 * c))) return rc;
-  if ((rc = dev_alloc(h, &w->b_out, (size_t)c))) return rc;
+  if ((rc = h->alloc(&w->w_film, (size_t)2 * c * e))) return rc;
+  if ((rc = h->alloc(&w->b_film_raw, (size_t)2 * c))) return rc;
+  if ((rc = h->alloc(&w->b_film, (size_t)2 * c))) return rc;
+  if ((rc = h->alloc(&w->w_fused, (size_t)7 * c * c))) return rc;
+  if ((rc = h->alloc(&w->w_out, (size_t)c * 5 * c))) return rc;
+  if ((rc = h->alloc(&w->b_out, (size_t)c))) return rc;
   int* map = h->film_map[lvl];
   bf16* wf = w->w_film;
-  add_param(h, pre + ".norm.emb_layer.weight", {2 * c, e}, [=](const float* src, hipStream_t s) {
+  h->params.add(pre + ".norm.emb_layer.weight", {2 * c, e}, [=](const float* src, hipStream_t s) {
     return launch_pack_rows(src, wf, map, 2 * c, e, e, e, 0, s);
   });
   float *braw = w->b_film_raw, *bre = w->b_film;
-  add_param(h, pre + ".norm.emb_layer.bias", {2 * c}, [=](const float* src, hipStream_t s) {
+  h->params.add(pre + ".norm.emb_layer.bias", {2 * c}, [=](const float* src, hipStream_t s) {
     int r2 = copy_f32(braw, src, 2 * c, s);
     return r2 ? r2 : launch_gather_f32(braw, bre, map, 2 * c, s);
   });
-  if ((rc = add_f32(h, pre + ".norm.norm.weight", {c}, &w->nw))) return rc;
-  bf16* wfu = w->w_fused;
-  add_param(h, pre + ".fused_attn_mlp_proj.weight", {7 * c, c}, [=](const float* src, hipStream_t s) {
-    return launch_pack_rows(src, wfu, nullptr, 7 * c, c, c, c, 0, s);
-  });
-  if ((rc = add_f32(h, pre + ".fused_attn_mlp_proj.bias", {7 * c}, &w->b_fused))) return rc;
-  if ((rc = add_f32(h, pre + ".q_norm.weight", {d}, &w->qw))) return rc;
-  if ((rc = add_f32(h, pre + ".k_norm.weight", {d}, &w->kw))) return rc;
+  if ((rc = h->add_f32(pre + ".norm.norm.weight", {c}, &w->nw))) return rc;
+  h->add_bf16(pre + ".fused_attn_mlp_proj.weight", 7 * c, c, w->w_fused);
+  if ((rc = h->add_f32(pre + ".fused_attn_mlp_proj.bias", {7 * c}, &w->b_fused))) return rc;
+  if ((rc = h->add_f32(pre + ".q_norm.weight", {d}, &w->qw))) return rc;
+  if ((rc = h->add_f32(pre + ".k_norm.weight", {d}, &w->kw))) return rc;
   bf16* wo = w->w_out;
-  add_param(h, pre + ".attn_out.weight", {c, c}, [=](const float* src, hipStream_t s) {
+  h->params.add(pre + ".attn_out.weight", {c, c}, [=](const float* src, hipStream_t s) {
     return launch_pack_rows(src, wo, nullptr, c, c, c, 5 * c, 0, s);
   });
-  if ((rc = add_f32(h, pre + ".attn_out.bias", {c}, &w->b_attn))) return rc;
-  add_param(h, pre + ".mlp_out.2.weight", {c, 4 * c}, [=](const float* src, hipStream_t s) {
+  if ((rc = h->add_f32(pre + ".attn_out.bias", {c}, &w->b_attn))) return rc;
+  h->params.add(pre + ".mlp_out.2.weight", {c, 4 * c}, [=](const float* src, hipStream_t s) {
     return launch_pack_rows(src, wo, nullptr, c, 4 * c, 4 * c, 5 * c, c, s);
   });
-  if ((rc = add_f32(h, pre + ".mlp_out.2.bias", {c}, &w->b_mlp))) return rc;
+  if ((rc = h->add_f32(pre + ".mlp_out.2.bias", {c}, &w->b_mlp))) return rc;
   return DFOT_OK;
 }
 
@@ -259,10 +211,10 @@ static int add_conv(dfot_uvit_s* h, const std::string& pre, int cin, int cout, C
   w->cin = cin;
   w->cout = cout;
   int rc = 0;
-  if ((rc = dev_alloc(h, &w->w, (size_t)cout * 9 * cin))) return rc;
+  if ((rc = h->alloc(&w->w, (size_t)cout * 9 * cin))) return rc;
   bf16* dst = w->w;
-  add_param(h, pre + ".weight", {cout, cin, 3, 3}, [=](const float* src, hipStream_t s) { return launch_pack_conv3(src, dst, cout, cin, s); });
-  return add_f32(h, pre + ".bias", {cout}, &w->b);
+  h->params.add(pre + ".weight", {cout, cin, 3, 3}, [=](const float* src, hipStream_t s) { return launch_pack_conv3(src, dst, cout, cin, s); });
+  return h->add_f32(pre + ".bias", {cout}, &w->b);
 }
 
 static int build(dfot_uvit_s* h) {
@@ -284,40 +236,40 @@ static int build(dfot_uvit_s* h) {
       const int g = n / 64, t = n % 64;
       m[n] = t < 32 ? 32 * g + t : cc + 32 * g + (t - 32);
     }
-    if ((rc = dev_alloc(h, &h->film_map[l], (size_t)2 * cc))) return rc;
+    if ((rc = h->alloc(&h->film_map[l], (size_t)2 * cc))) return rc;
     DFOT_CHECK_HIP(hipMemcpy(h->film_map[l], m.data(), m.size() * sizeof(int), hipMemcpyHostToDevice));
   }
-  if ((rc = dev_alloc(h, &h->zeros, 256))) return rc;
+  if ((rc = h->alloc(&h->zeros, 256))) return rc;
   DFOT_CHECK_HIP(hipMemset(h->zeros, 0, 256 * sizeof(bf16)));
 
   const int e = h->E, nd = c.noise_dim;
   const std::string ne = "noise_level_pos_embedding.";
-  if ((rc = add_f32(h, ne + "timesteps.freqs", {nd}, &h->ne_freqs))) return rc;
-  if ((rc = add_f32(h, ne + "timesteps.phases", {nd}, &h->ne_phases))) return rc;
-  if ((rc = add_f32(h, ne + "embedding.linear_1.weight", {e, nd}, &h->ne_w1))) return rc;
-  if ((rc = add_f32(h, ne + "embedding.linear_1.bias", {e}, &h->ne_b1))) return rc;
-  if ((rc = add_f32(h, ne + "embedding.linear_2.weight", {e, e}, &h->ne_w2))) return rc;
-  if ((rc = add_f32(h, ne + "embedding.linear_2.bias", {e}, &h->ne_b2))) return rc;
+  if ((rc = h->add_f32(ne + "timesteps.freqs", {nd}, &h->ne_freqs))) return rc;
+  if ((rc = h->add_f32(ne + "timesteps.phases", {nd}, &h->ne_phases))) return rc;
+  if ((rc = h->add_f32(ne + "embedding.linear_1.weight", {e, nd}, &h->ne_w1))) return rc;
+  if ((rc = h->add_f32(ne + "embedding.linear_1.bias", {e}, &h->ne_b1))) return rc;
+  if ((rc = h->add_f32(ne + "embedding.linear_2.weight", {e, e}, &h->ne_w2))) return rc;
+  if ((rc = h->add_f32(ne + "embedding.linear_2.bias", {e}, &h->ne_b2))) return rc;
   if (h->posefree) {
     if (h->act_dim > 0) {  // RandomDropoutCondEmbedding: a TimestepEmbedding itself (dropout 0) or one under .embedding (embeddings.py:364-387)
       const std::string ce = h->act_dropout ? "external_cond_embedding.embedding." : "external_cond_embedding.";
-      if ((rc = add_f32(h, ce + "linear_1.weight", {e, h->act_dim}, &h->ac_w1))) return rc;
-      if ((rc = add_f32(h, ce + "linear_1.bias", {e}, &h->ac_b1))) return rc;
-      if ((rc = add_f32(h, ce + "linear_2.weight", {e, e}, &h->ac_w2))) return rc;
-      if ((rc = add_f32(h, ce + "linear_2.bias", {e}, &h->ac_b2))) return rc;
+      if ((rc = h->add_f32(ce + "linear_1.weight", {e, h->act_dim}, &h->ac_w1))) return rc;
+      if ((rc = h->add_f32(ce + "linear_1.bias", {e}, &h->ac_b1))) return rc;
+      if ((rc = h->add_f32(ce + "linear_2.weight", {e, e}, &h->ac_w2))) return rc;
+      if ((rc = h->add_f32(ce + "linear_2.bias", {e}, &h->ac_b2))) return rc;
     }
   } else {
-    if ((rc = dev_alloc(h, &h->pose_w, (size_t)e * h->kpose))) return rc;
+    if ((rc = h->alloc(&h->pose_w, (size_t)e * h->kpose))) return rc;
     bf16* pw = h->pose_w;
     const int k = c.cond_dim * 4, kp = h->kpose;
-    add_param(h, "external_cond_embedding.patch_embedder.proj.weight", {e, c.cond_dim, 2, 2},
+    h->params.add("external_cond_embedding.patch_embedder.proj.weight", {e, c.cond_dim, 2, 2},
               [=](const float* src, hipStream_t s) { return launch_pack_rows(src, pw, nullptr, e, k, kp, kp, 0, s); });
-    if ((rc = add_f32(h, "external_cond_embedding.patch_embedder.proj.bias", {e}, &h->pose_b))) return rc;
+    if ((rc = h->add_f32("external_cond_embedding.patch_embedder.proj.bias", {e}, &h->pose_b))) return rc;
   }
-  if ((rc = add_f32(h, "embed_input.proj.weight", {h->ch[0], c.in_channels, 2, 2}, &h->ein_w))) return rc;
-  if ((rc = add_f32(h, "embed_input.proj.bias", {h->ch[0]}, &h->ein_b))) return rc;
-  if ((rc = add_f32(h, "project_output.proj.weight", {h->ch[0], c.in_channels, 2, 2}, &h->pout_w))) return rc;
-  if ((rc = add_f32(h, "project_output.proj.bias", {c.in_channels}, &h->pout_b))) return rc;
+  if ((rc = h->add_f32("embed_input.proj.weight", {h->ch[0], c.in_channels, 2, 2}, &h->ein_w))) return rc;
+  if ((rc = h->add_f32("embed_input.proj.bias", {h->ch[0]}, &h->ein_b))) return rc;
+  if ((rc = h->add_f32("project_output.proj.weight", {h->ch[0], c.in_channels, 2, 2}, &h->pout_w))) return rc;
+  if ((rc = h->add_f32("project_output.proj.bias", {c.in_channels}, &h->pout_b))) return rc;
 
   for (int l = 0; l < 3; ++l) {
     const int n = c.num_updown_blocks[l];
@@ -384,7 +336,7 @@ static int build_rope(dfot_uvit_s* h, int lvl) {
       }
     }
   }
-  int rc = dev_alloc(h, &h->rope_cs[lvl], cs.size());
+  int rc = h->alloc(&h->rope_cs[lvl], cs.size());
   if (rc) return rc;
   DFOT_CHECK_HIP(hipMemcpy(h->rope_cs[lvl], cs.data(), cs.size() * sizeof(float), hipMemcpyHostToDevice));
   return DFOT_OK;
@@ -675,8 +627,7 @@ int dfot_uvit_create(const dfot_uvit_config* cfg, dfot_uvit_t* out) {
 
 int dfot_uvit_destroy(dfot_uvit_t h) {
   if (!h) return DFOT_OK;
-  for (void* p : h->owned) (void)hipFree(p);
-  for (void* p : h->ws_owned) (void)hipFree(p);
+  h->free_all();
   for (hipEvent_t e : h->ev_start) (void)hipEventDestroy(e);
   for (hipEvent_t e : h->ev_stop) (void)hipEventDestroy(e);
   delete h;
@@ -723,35 +674,24 @@ int dfot_uvit3d_create(const dfot_uvit3d_config* cfg, dfot_uvit_t* out) {
 }
 int64_t dfot_uvit3d_config_bytes(void) { return (int64_t)sizeof(dfot_uvit3d_config); }
 
-int dfot_uvit_num_params(dfot_uvit_t h) { return h ? (int)h->params.size() : 0; }
-const char* dfot_uvit_param_name(dfot_uvit_t h, int i) {
-  return (h && i >= 0 && i < (int)h->params.size()) ? h->params[i].name.c_str() : nullptr;
-}
+int dfot_uvit_num_params(dfot_uvit_t h) { return h ? h->params.count() : 0; }
+const char* dfot_uvit_param_name(dfot_uvit_t h, int i) { return h ? h->params.name(i) : nullptr; }
 int dfot_uvit_param_shape(dfot_uvit_t h, int i, int64_t shape[4], int* ndim) {
-  DFOT_REQUIRE(h && shape && ndim && i >= 0 && i < (int)h->params.size(), DFOT_ERR_ARG, "param_shape: bad argument");
-  *ndim = (int)h->params[i].shape.size();
-  for (int k = 0; k < *ndim; ++k) shape[k] = h->params[i].shape[k];
-  return DFOT_OK;
+  DFOT_REQUIRE(h, DFOT_ERR_ARG, "param_shape: bad argument");
+  return h->params.shape(i, shape, ndim);
 }
 
 int dfot_uvit_load_weight(dfot_uvit_t h, const char* name, const float* data, const int64_t* shape, int ndim, void* stream) {
-  DFOT_REQUIRE(h && name && data && shape, DFOT_ERR_ARG, "load_weight: null argument");
-  auto it = h->index.find(name);
-  DFOT_REQUIRE(it != h->index.end(), DFOT_ERR_NAME, "load_weight: unexpected key '%s'", name);
-  Param& p = h->params[it->second];
-  bool same = (int)p.shape.size() == ndim;
-  for (int k = 0; same && k < ndim; ++k) same = p.shape[k] == shape[k];
-  DFOT_REQUIRE(same, DFOT_ERR_SHAPE, "load_weight: size mismatch for '%s'", name);
-  int rc = p.load(data, (hipStream_t)stream);
-  if (rc) return rc;
-  p.loaded = true;
-  h->finalized = false;
-  return DFOT_OK;
+  DFOT_REQUIRE(h, DFOT_ERR_ARG, "load_weight: null argument");
+  int rc = h->params.load(name, data, shape, ndim, (hipStream_t)stream);
+  if (!rc) h->finalized = false;
+  return rc;
 }
 
 int dfot_uvit_finalize(dfot_uvit_t h, void* stream) {
   DFOT_REQUIRE(h, DFOT_ERR_ARG, "finalize: null handle");
-  for (const Param& p : h->params) DFOT_REQUIRE(p.loaded, DFOT_ERR_STATE, "finalize: missing key '%s'", p.name.c_str());
+  int rc = h->params.require_all_loaded();
+  if (rc) return rc;
   hipStream_t s = (hipStream_t)stream;
   auto fuse = [&](std::vector<TrW>& v) -> int {
     for (TrW& w : v) {
@@ -760,7 +700,6 @@ int dfot_uvit_finalize(dfot_uvit_t h, void* stream) {
     }
     return DFOT_OK;
   };
-  int rc = 0;
   if ((rc = fuse(h->down_tr)) || (rc = fuse(h->mid_tr)) || (rc = fuse(h->up_tr))) return rc;
   for (int l = 2; l < 4; ++l)
     if (!h->rope_cs[l] && (rc = build_rope(h, l))) return rc;
@@ -791,9 +730,7 @@ int dfot_uvit_finalize(dfot_uvit_t h, void* stream) {
 int dfot_uvit_reserve(dfot_uvit_t h, int max_batch) {
   DFOT_REQUIRE(h && max_batch > 0, DFOT_ERR_ARG, "reserve: bad argument");
   if (max_batch <= h->max_batch) return DFOT_OK;
-  for (void* p : h->ws_owned) (void)hipFree(p);
-  h->ws_owned.clear();
-  h->ws_bytes = 0;
+  h->free_workspace();
   h->max_batch = 0;
   h->out_part = nullptr;
   h->pend_part = nullptr;
@@ -803,29 +740,29 @@ int dfot_uvit_reserve(dfot_uvit_t h, int max_batch) {
   size_t pix[4];
   for (int l = 0; l < 4; ++l) pix[l] = (size_t)h->r[l] * h->r[l];
   int rc = 0;
-  if ((rc = dev_alloc(h, &h->nemb, bt * h->E, true))) return rc;
-  if ((rc = dev_alloc(h, &h->nhid, bt * h->E, true))) return rc;
+  if ((rc = h->alloc(&h->nemb, bt * h->E, true))) return rc;
+  if ((rc = h->alloc(&h->nhid, bt * h->E, true))) return rc;
   for (int l = 0; l < 4; ++l) {
-    if ((rc = dev_alloc(h, &h->XB[l], bt * pix[l] * h->ch[l], true))) return rc;
+    if ((rc = h->alloc(&h->XB[l], bt * pix[l] * h->ch[l], true))) return rc;
     // fp32 scratch of a transformer level (the out-projection's fallback path, run_tr_block)
-    if (l >= 2 && (rc = dev_alloc(h, &h->X[l], bt * pix[l] * h->ch[l], true))) return rc;
-    if (!h->posefree && (rc = dev_alloc(h, &h->emb[l], bt * pix[l] * h->E, true))) return rc;
+    if (l >= 2 && (rc = h->alloc(&h->X[l], bt * pix[l] * h->ch[l], true))) return rc;
+    if (!h->posefree && (rc = h->alloc(&h->emb[l], bt * pix[l] * h->E, true))) return rc;
   }
   for (int l = 0; l < 3; ++l)
-    if ((rc = dev_alloc(h, &h->HSA[l], bt * pix[l + 1] * h->ch[l + 1], true))) return rc;
+    if ((rc = h->alloc(&h->HSA[l], bt * pix[l + 1] * h->ch[l + 1], true))) return rc;
   if (!h->posefree) {
-    if ((rc = dev_alloc(h, &h->acond, bt * pix[0] * h->kpose, true))) return rc;
+    if ((rc = h->alloc(&h->acond, bt * pix[0] * h->kpose, true))) return rc;
     DFOT_CHECK_HIP(hipMemset(h->acond, 0, bt * pix[0] * h->kpose * sizeof(bf16)));
   }
   size_t act = 0, tmpn = 0;
   for (int l = 0; l < 4; ++l) act = std::max(act, bt * pix[l] * h->ch[l]);
   for (int l = 0; l < 3; ++l) tmpn = std::max(tmpn, bt * pix[l + 1] * h->ch[l]);
-  if ((rc = dev_alloc(h, &h->s1, act, true))) return rc;
-  if ((rc = dev_alloc(h, &h->hbf, act, true))) return rc;
-  if ((rc = dev_alloc(h, &h->tmp, tmpn, true))) return rc;
-  if ((rc = dev_alloc(h, &h->gn_partial, bt * (pix[0] / 64) * 64, true))) return rc;
-  if ((rc = dev_alloc(h, &h->gn_partial2, bt * (pix[0] / 64) * 64, true))) return rc;
-  if ((rc = dev_alloc(h, &h->gn_stats, bt * 64, true))) return rc;
+  if ((rc = h->alloc(&h->s1, act, true))) return rc;
+  if ((rc = h->alloc(&h->hbf, act, true))) return rc;
+  if ((rc = h->alloc(&h->tmp, tmpn, true))) return rc;
+  if ((rc = h->alloc(&h->gn_partial, bt * (pix[0] / 64) * 64, true))) return rc;
+  if ((rc = h->alloc(&h->gn_partial2, bt * (pix[0] / 64) * 64, true))) return rc;
+  if ((rc = h->alloc(&h->gn_stats, bt * 64, true))) return rc;
   size_t mtr = 0, mc = 0;
   for (int l = 2; l < 4; ++l) {
     mtr = std::max(mtr, bt * pix[l]);
@@ -837,7 +774,7 @@ int dfot_uvit_reserve(dfot_uvit_t h, int max_batch) {
     std::vector<FilmChunk> table;
     long sv_off = 0;
     auto add = [&](bf16** fc, long* off, const bf16* wf, const float* bf_, int c, int lvl) -> int {
-      int r2 = h->posefree ? DFOT_OK : dev_alloc(h, fc, bt * pix[lvl] * 2 * c, true);  // pose-free: no cache, fcache stays nullptr
+      int r2 = h->posefree ? DFOT_OK : h->alloc(fc, bt * pix[lvl] * 2 * c, true);  // pose-free: no cache, fcache stays nullptr
       if (r2) return r2;
       *off = sv_off;
       for (int r0 = 0; r0 < 2 * c; r0 += 64) table.push_back(FilmChunk{wf + (long)r0 * h->E, bf_ + r0, sv_off + r0, 2 * c});
@@ -851,21 +788,21 @@ int dfot_uvit_reserve(dfot_uvit_t h, int max_batch) {
     for (TrW& w : h->down_tr) if ((rc = add(&w.fcache, &w.sv_off, w.w_film, w.b_film, w.c, 2))) return rc;
     for (TrW& w : h->up_tr) if ((rc = add(&w.fcache, &w.sv_off, w.w_film, w.b_film, w.c, 2))) return rc;
     for (TrW& w : h->mid_tr) if ((rc = add(&w.fcache, &w.sv_off, w.w_film, w.b_film, w.c, 3))) return rc;
-    if ((rc = dev_alloc(h, &h->sv, (size_t)sv_off, true))) return rc;
-    if ((rc = dev_alloc(h, &h->film_table, table.size(), true))) return rc;
+    if ((rc = h->alloc(&h->sv, (size_t)sv_off, true))) return rc;
+    if ((rc = h->alloc(&h->film_table, table.size(), true))) return rc;
     DFOT_CHECK_HIP(hipMemcpy(h->film_table, table.data(), table.size() * sizeof(FilmChunk), hipMemcpyHostToDevice));
     h->film_chunks = (int)table.size();
-    if ((rc = dev_alloc(h, &h->cond_mask, (size_t)max_batch, true))) return rc;
+    if ((rc = h->alloc(&h->cond_mask, (size_t)max_batch, true))) return rc;
     h->cond_batch = 0;
   }
-  if ((rc = dev_alloc(h, &h->cat, mc * 5, true))) return rc;
-  if ((rc = dev_alloc(h, &h->q, mc, true))) return rc;
-  if ((rc = dev_alloc(h, &h->k, mc, true))) return rc;
-  if ((rc = dev_alloc(h, &h->v, mc, true))) return rc;
+  if ((rc = h->alloc(&h->cat, mc * 5, true))) return rc;
+  if ((rc = h->alloc(&h->q, mc, true))) return rc;
+  if ((rc = h->alloc(&h->k, mc, true))) return rc;
+  if ((rc = h->alloc(&h->v, mc, true))) return rc;
   {  // both transformer levels may take the two-slice out-projection at small sizes: room for the larger of their outputs, twice
     const size_t e2 = bt * pix[2] * h->ch[2], e3 = bt * pix[3] * h->ch[3];
     h->out_part_elems = 3 * (e2 > e3 ? e2 : e3);
-    if ((rc = dev_alloc(h, &h->out_part, h->out_part_elems, true))) return rc;
+    if ((rc = h->alloc(&h->out_part, h->out_part_elems, true))) return rc;
   }
   // key-split partial buffers of the level-2 attention's balanced tail, large enough for every batch this workspace can serve:
   // owned by the handle (nothing is allocated, freed or shared with another handle inside forward / stream capture)
@@ -873,7 +810,7 @@ int dfot_uvit_reserve(dfot_uvit_t h, int max_batch) {
     size_t need = 16;
     for (int b = 1; b <= max_batch; ++b)
       for (int l = 2; l < 4; ++l) need = std::max(need, attention_scratch_bytes(b, h->heads, h->T * h->r[l] * h->r[l], h->ch[l] / h->heads));
-    if ((rc = dev_alloc(h, &h->attn_scratch.p, need / sizeof(float), true))) return rc;
+    if ((rc = h->alloc(&h->attn_scratch.p, need / sizeof(float), true))) return rc;
     h->attn_scratch.bytes = need;
   }
   h->max_batch = max_batch;

@@ -15,15 +15,14 @@ NotImplementedError (training would need the backward of the frame-causal attent
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
-from typing import Dict, Optional, Sequence, Tuple
+from typing import Optional, Sequence, Tuple
 
 import torch
 from torch import nn
 
 from . import capi, ops
-from .backbone import _Node, _get
+from .engine_module import EngineModule, _get
 
 CAUSAL_MODES = (None, "temporal_causal", "video_temporal_causal")
 FRAME_LENGTHS = (16, 32, 64, 128)
@@ -57,7 +56,9 @@ def state_dict_layout(hidden: int, depth: int, mlp_hidden: int, channels: int, t
     return out
 
 
-class DiT1D(nn.Module):
+class DiT1D(EngineModule):
+    _family, _create = "dit1d", "dfot_dit1d_create"
+
     def __init__(self, cfg, x_shape: Sequence[int], max_tokens: int, external_cond_type: Optional[str] = None,
                  external_cond_num_classes: Optional[int] = None, external_cond_dim: int = 0, use_causal_mask: bool = True,
                  timesteps: int = 1000):
@@ -121,17 +122,10 @@ class DiT1D(nn.Module):
         c.eps = 1e-6
         self._ccfg = c
         # The module (parameters, the sin-cos pos_embed) is built on the host; the engine handle, whose creation allocates device memory, is
-        # created at the first weight sync (_ensure_handle), which also checks that the engine enumerates exactly these keys and shapes.
-        self._handle = C.c_void_p()
-        self._layout = state_dict_layout(hidden, depth, mlp_hidden, channels, max_tokens * length)
-        self._names = [name for name, _ in self._layout]
-        for name, shape in self._layout:
-            self._register(name, shape)
+        # created at the first weight sync or reserve, which also checks that the engine enumerates exactly these keys and shapes.
+        self._build_tree(state_dict_layout(hidden, depth, mlp_hidden, channels, max_tokens * length))
         with torch.no_grad():
             self.pos_embed.copy_(sincos_pos_embed_1d(hidden, max_tokens * length))
-        self._synced: Optional[Tuple] = None
-        self._reserved = 0
-        self._op_key: Optional[int] = None
 
     @property
     def in_channels(self) -> int:
@@ -141,18 +135,9 @@ class DiT1D(nn.Module):
     def noise_level_dim(self) -> int:
         return 256
 
-    def _register(self, name: str, shape: Tuple[int, ...]) -> None:
-        *path, leaf = name.split(".")
-        node: nn.Module = self
-        for part in path:
-            if part not in node._modules:
-                node.add_module(part, _Node())
-            node = node._modules[part]
+    def _new_tensor(self, name: str, shape: Tuple[int, ...]) -> torch.Tensor:
         # pos_embed is a frozen parameter in the reference (requires_grad=False); the others are what its optimizer trains
-        node.register_parameter(leaf, nn.Parameter(torch.zeros(shape, dtype=torch.float32), requires_grad=name != "pos_embed"))
-
-    def _tensors(self) -> Dict[str, torch.Tensor]:
-        return dict(self.named_parameters())
+        return nn.Parameter(torch.zeros(shape, dtype=torch.float32), requires_grad=name != "pos_embed")
 
     def reset_parameters(self, seed: int = 0) -> None:
         """The reference's init (dit_model.py:458-486): xavier-uniform Linear weights, N(0, 0.02) timestep MLP, zero biases, zero
@@ -184,51 +169,6 @@ class DiT1D(nn.Module):
                     gain = 0.5 if ".adaLN_modulation." in name else 1.0
                     v = gain * torch.randn(t.shape, generator=g) / math.sqrt(t.shape[1])
                 t.copy_(v.to(t.device))
-
-    def _ensure_handle(self) -> None:
-        if self._handle.value:
-            return
-        handle = C.c_void_p()
-        capi.check(capi.lib.dfot_dit1d_create(C.byref(self._ccfg), C.byref(handle)))
-        shape = (C.c_int64 * 4)()
-        ndim = C.c_int()
-        got = []
-        for i in range(capi.lib.dfot_dit1d_num_params(handle)):
-            capi.check(capi.lib.dfot_dit1d_param_shape(handle, i, shape, C.byref(ndim)))
-            got.append((capi.lib.dfot_dit1d_param_name(handle, i).decode(), tuple(shape[k] for k in range(ndim.value))))
-        if got != self._layout:
-            capi.lib.dfot_dit1d_destroy(handle)
-            raise RuntimeError("the engine's parameter list differs from the module's state-dict layout")
-        self._handle = handle
-
-    def _signature(self) -> Tuple:
-        return tuple((t.data_ptr(), t._version) for t in self._tensors().values())
-
-    def sync_weights(self, force: bool = False) -> None:
-        sig = self._signature()
-        if not force and sig == self._synced:
-            return
-        tensors = self._tensors()
-        for name in self._names:
-            if not tensors[name].is_cuda:
-                raise RuntimeError(f"parameter {name} is on {tensors[name].device}; move the module to the GPU first")
-        self._ensure_handle()
-        s = capi.stream_ptr()
-        for name in self._names:
-            src = tensors[name].detach().to(torch.float32).contiguous()
-            shape = (C.c_int64 * src.ndim)(*src.shape)
-            capi.check(capi.lib.dfot_dit1d_load_weight(self._handle, name.encode(), capi.ptr(src), shape, src.ndim, s))
-        capi.check(capi.lib.dfot_dit1d_finalize(self._handle, s))
-        self._synced = sig
-        self.reserve_generation = getattr(self, "reserve_generation", 0) + 1  # captured sampler graphs hold the old tables
-
-    def reserve(self, batch: int) -> None:
-        if batch > self._reserved:
-            torch.cuda.synchronize()
-            self._ensure_handle()
-            capi.check(capi.lib.dfot_dit1d_reserve(self._handle, int(batch)))
-            self._reserved = batch
-            self.reserve_generation = getattr(self, "reserve_generation", 0) + 1  # workspace pointers changed
 
     def forward(self, x: torch.Tensor, noise_levels: torch.Tensor, external_cond: Optional[torch.Tensor] = None,
                 external_cond_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -267,11 +207,3 @@ class DiT1D(nn.Module):
         capi.check(capi.lib.dfot_dit1d_forward(self._handle, capi.ptr(xf, torch.float32, "x"), capi.ptr(kf, torch.int32, "noise_levels"),
                                                capi.ptr(out), b, t, capi.stream_ptr()))
         return out.to(x.dtype)
-
-    def __del__(self):
-        try:
-            if getattr(self, "_handle", None) and self._handle.value:
-                capi.lib.dfot_dit1d_destroy(self._handle)
-                self._handle = C.c_void_p()
-        except Exception:
-            pass

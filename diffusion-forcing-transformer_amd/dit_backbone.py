@@ -21,13 +21,12 @@ from __future__ import annotations
 import ctypes as C
 import math
 from collections import OrderedDict
-from typing import Dict, Optional, Sequence, Tuple, Union
+from typing import Optional, Sequence, Tuple, Union
 
 import torch
-from torch import nn
 
 from . import capi, ops
-from .backbone import _Node, _get
+from .engine_module import EngineModule, _get
 
 
 # FourierEmbedding's persistent buffers, in the reference's state_dict order (before noise_level_pos_embedding.embedding.*)
@@ -159,7 +158,9 @@ def _init_random_matrix(tensors, seed: int) -> None:
             t.copy_(v.to(t.device))
 
 
-class DiT3D(nn.Module):
+class DiT3D(EngineModule):
+    _family, _create = "dit", "dfot_dit_create_f"
+
     def __init__(self, cfg, x_shape: Sequence[int], max_tokens: int, external_cond_type: str = "action",
                  external_cond_num_classes: Optional[int] = None, external_cond_dim: int = 0,
                  use_causal_mask: bool = False, timesteps: int = 1000, **kwargs):
@@ -191,19 +192,7 @@ class DiT3D(nn.Module):
         self.max_tokens = int(c.max_tokens)
         self._ccfg = c
         self.num_patches = (c.height // c.patch_size) * (c.width // c.patch_size)
-        self._handle = C.c_void_p()
-        capi.check(capi.lib.dfot_dit_create_f(C.byref(c), C.byref(self._handle)))
-        self._names = []
-        shape = (C.c_int64 * 4)()
-        ndim = C.c_int()
-        for i in range(capi.lib.dfot_dit_num_params(self._handle)):
-            name = capi.lib.dfot_dit_param_name(self._handle, i).decode()
-            capi.check(capi.lib.dfot_dit_param_shape(self._handle, i, shape, C.byref(ndim)))
-            self._register(name, tuple(shape[k] for k in range(ndim.value)))
-            self._names.append(name)
-        self._synced: Optional[Tuple] = None
-        self._reserved = 0
-        self._op_key: Optional[int] = None
+        self._build_tree()
         # training form (autograd): the saved-activation engine of trainer.DiT3DTrainer, built at the first forward under grad
         self._ctor = dict(max_tokens=int(max_tokens), timesteps=int(timesteps), external_cond_type=external_cond_type,
                           external_cond_num_classes=external_cond_num_classes, external_cond_dim=self.external_cond_dim)
@@ -248,26 +237,12 @@ class DiT3D(nn.Module):
     def noise_level_dim(self) -> int:
         return 256
 
-    def _register(self, name: str, shape: Tuple[int, ...]) -> None:
-        *path, leaf = name.split(".")
-        node: nn.Module = self
-        for part in path:
-            if part not in node._modules:
-                node.add_module(part, _Node())
-            node = node._modules[part]
+    def _new_tensor(self, name: str, shape: Tuple[int, ...]) -> torch.Tensor:
         if name == FOURIER_BUFFERS[0]:  # drawn as FourierEmbedding.__init__ draws them (bandwidth 1), from torch's default generator
-            node.register_buffer(leaf, 2 * math.pi * torch.randn(shape))
-        elif name == FOURIER_BUFFERS[1]:
-            node.register_buffer(leaf, 2 * math.pi * torch.rand(shape))
-        else:
-            node.register_parameter(leaf, nn.Parameter(torch.zeros(shape, dtype=torch.float32)))
-
-    def _tensors(self) -> Dict[str, torch.Tensor]:
-        return dict(self.named_parameters())
-
-    def _engine_tensors(self) -> Dict[str, torch.Tensor]:
-        """everything the engine loads: the parameters and, on a Fourier model, the two buffers"""
-        return {**dict(self.named_parameters()), **dict(self.named_buffers())}
+            return 2 * math.pi * torch.randn(shape)
+        if name == FOURIER_BUFFERS[1]:
+            return 2 * math.pi * torch.rand(shape)
+        return super()._new_tensor(name, shape)
 
     def reset_parameters(self, seed: int = 0) -> None:
         """The reference's init (dit3d.py:92-109, dit_blocks.py:392-395,422-425,476-486,528-531): xavier-uniform Linear
@@ -300,47 +275,18 @@ class DiT3D(nn.Module):
                     v = gain * torch.randn(t.shape, generator=g) / math.sqrt(math.prod(t.shape[1:]))
                 t.copy_(v.to(t.device))
 
-    def _signature(self) -> Tuple:
-        return tuple((t.data_ptr(), t._version) for t in self._engine_tensors().values())
-
-    def sync_weights(self, force: bool = False) -> None:
-        sig = self._signature()
-        if not force and sig == self._synced:
-            return
-        tensors = self._engine_tensors()
-        s = capi.stream_ptr()
-        for name in self._names:
-            t = tensors[name]
-            if not t.is_cuda:
-                raise RuntimeError(f"parameter {name} is on {t.device}; move the module to the GPU first")
-            src = t.detach().to(torch.float32).contiguous()
-            shape = (C.c_int64 * src.ndim)(*src.shape)
-            capi.check(capi.lib.dfot_dit_load_weight(self._handle, name.encode(), capi.ptr(src), shape, src.ndim, s))
-        capi.check(capi.lib.dfot_dit_finalize(self._handle, s))
-        self._synced = sig
-        # captured sampler graphs bake the kernels chosen for the OLD weights (attention variant by score bound) and their pointers
-        self.reserve_generation = getattr(self, "reserve_generation", 0) + 1
-
-    def set_option(self, key: str, value: int) -> None:
-        self.reserve_generation = getattr(self, "reserve_generation", 0) + 1  # options select kernels: captured graphs are stale
-        capi.check(capi.lib.dfot_dit_set_option(self._handle, key.encode(), int(value)))
-
     def attn_timing(self):
         tot, n = C.c_double(), C.c_int64()
         capi.check(capi.lib.dfot_dit_attn_timing(self._handle, C.byref(tot), C.byref(n)))
         return tot.value, n.value
 
     def reserve(self, batch: int) -> None:
-        if batch > self._reserved:
-            torch.cuda.synchronize()
-            try:
-                capi.check(capi.lib.dfot_dit_reserve(self._handle, int(batch)))
-            except capi.DfotError as e:
-                if self._capture_names and e.code == capi.ERR_SHAPE:  # the captured maps at this batch exceed max_bytes
-                    raise ValueError(str(e)) from None
-                raise
-            self._reserved = batch
-            self.reserve_generation = getattr(self, "reserve_generation", 0) + 1  # workspace pointers changed
+        try:
+            super().reserve(batch)
+        except capi.DfotError as e:
+            if self._capture_names and e.code == capi.ERR_SHAPE:  # the captured maps at this batch exceed max_bytes
+                raise ValueError(str(e)) from None
+            raise
 
     def _condition_mask(self, external_cond_mask: Optional[torch.Tensor], batch: int, dev) -> Optional[torch.Tensor]:
         """which videos run without their condition, as the reference's modules decide it: an action model built with
@@ -538,7 +484,7 @@ class DiT3D(nn.Module):
         if blocks is False:
             capi.check(capi.lib.dfot_dit_capture_attention(self._handle, None, 0, capi.ATTN_MAP_OFF, 0))
             self._capture_names = ()
-            self.reserve_generation = getattr(self, "reserve_generation", 0) + 1  # captured graphs hold the map launches
+            self._bump_generation()  # captured graphs hold the map launches
             return
         if self._ccfg.variant == 1:
             raise NotImplementedError("capture_attention: DifferenceDiT3D (the difference model) is not supported")
@@ -574,7 +520,7 @@ class DiT3D(nn.Module):
             raise
         self._capture_names = tuple(names[i] for i in chosen)
         self._capture_max_bytes = int(max_bytes)
-        self.reserve_generation = getattr(self, "reserve_generation", 0) + 1
+        self._bump_generation()
 
     @property
     def capturing_attention(self) -> bool:
@@ -599,14 +545,6 @@ class DiT3D(nn.Module):
             capi.check(capi.lib.dfot_dit_read_attention_map(self._handle, slot, capi.ptr(t), t.numel(), capi.stream_ptr()))
             out[name] = t
         return out
-
-    def __del__(self):
-        try:
-            if getattr(self, "_handle", None) and self._handle.value:
-                capi.lib.dfot_dit_destroy(self._handle)
-                self._handle = C.c_void_p()
-        except Exception:
-            pass
 
 
 class DifferenceDiT3D(DiT3D):

@@ -13,25 +13,23 @@ conditioning cache and no per-window state.  Forward only: under autograd it rai
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Optional, Sequence
 
 import torch
-from torch import nn
 
 from . import capi, ops
-from .backbone import UViT3DPose, _get
+from .backbone import UViTModule, _get
 
 _BLOCKS = ["ResBlock", "ResBlock", "TransformerBlock", "TransformerBlock"]
 
 
-class UViT3D(UViT3DPose):
-    """Shares the module-tree / weight-sync / workspace plumbing of UViT3DPose (the handle type is the same); construction and forward
-    are its own."""
+class UViT3D(UViTModule):
+    """The handle type is UViT3DPose's (backbone.UViTModule: its read-outs, taps and initialisers); construction and forward are its own."""
+    _create = "dfot_uvit3d_create"
 
     def __init__(self, cfg, x_shape: Sequence[int], max_tokens: int, external_cond_dim: int = 0, use_causal_mask: bool = True,
                  external_cond_type: str = "action", external_cond_num_classes: Optional[int] = None):
-        nn.Module.__init__(self)
+        super().__init__()
         block_types = list(_get(cfg, "block_types", _BLOCKS))
         if "AxialTransformerBlock" in block_types:
             raise ValueError("block type 'AxialTransformerBlock' is not built: only [ResBlock, ResBlock, TransformerBlock, TransformerBlock]")
@@ -75,21 +73,7 @@ class UViT3D(UViT3DPose):
         c.eps = 1e-6
         c.cond_dropout = int(self.external_cond_dropout > 0)
         self._ccfg = c
-        self._handle = C.c_void_p()
-        capi.check(capi.lib.dfot_uvit3d_create(C.byref(c), C.byref(self._handle)))
-        self._names = []
-        self._persistent_buffers = {"noise_level_pos_embedding.timesteps.freqs", "noise_level_pos_embedding.timesteps.phases"}
-        shape = (C.c_int64 * 4)()
-        ndim = C.c_int()
-        for i in range(capi.lib.dfot_uvit_num_params(self._handle)):
-            name = capi.lib.dfot_uvit_param_name(self._handle, i).decode()
-            capi.check(capi.lib.dfot_uvit_param_shape(self._handle, i, shape, C.byref(ndim)))
-            self._register(name, tuple(shape[k] for k in range(ndim.value)))
-            self._names.append(name)
-        self._synced = None
-        self._reserved = 0
-        self._op_key = None
-        self._cond_key = None        # (unused: there is no conditioning cache; reserve() of the shared plumbing resets it)
+        self._build_tree()
         self.live_frames = None      # set by the sampler around its backbone calls (uint8 (B, T), 0 = output discarded), None otherwise
         self._dropout_generator: Optional[torch.Generator] = None  # generator of the per-video condition dropout draw in train()
 
@@ -165,13 +149,3 @@ class UViT3D(UViT3DPose):
         out = torch.empty(batch * self.temporal_length, int(self._ccfg.emb_channels), device="cuda", dtype=torch.float32)
         capi.check(capi.lib.dfot_uvit_read_tap(self._handle, b"nemb", capi.ptr(out), out.numel(), capi.stream_ptr()))
         return out
-
-    # ------------------------------------------------------------------ what the pose model has and this one does not
-    def _train_engine(self, params):
-        raise NotImplementedError("UViT3D has no training engine")
-
-    def _train_forward_impl(self, *a, **k):
-        raise NotImplementedError("UViT3D has no training engine")
-
-    def _train_backward_impl(self, *a, **k):
-        raise NotImplementedError("UViT3D has no training engine")
