@@ -266,6 +266,8 @@ SIGNATURES = {
     "dfot_op_dit_final_layer": (_I, [_P, _P, _P, _L, _L, _P, _P, _P, _I, _I, _I, _F] + [_I] * 6 + [_P]),
     "dfot_op_dit_final_layer_chunked": (_I, [_P, _P, _P, _L, _L, _P, _P, _P, _I, _I, _I, _F] + [_I] * 6 + [_P]),
     "dfot_op_attention_frame_causal": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "dfot_op_attention_frame_causal_lse": (_I, [_P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _P]),
+    "dfot_op_attention_frame_causal_bwd": (_I, [_P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "dfot_dit1d_create": (_I, [C.POINTER(DiT1DConfig), C.POINTER(_P)]),
     "dfot_dit1d_destroy": (_I, [_P]),
     "dfot_dit1d_num_params": (_I, [_P]),

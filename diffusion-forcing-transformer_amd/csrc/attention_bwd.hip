@@ -68,13 +68,55 @@ __device__ __forceinline__ void tile_store(char* dst, const bf16x8 (&r)[BwdCfg<D
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// FC (compile-time): the frame-causal form of each of the four kernels, the backward of attention_frame_causal.hip: query i sees key j
+// iff (j >> flog) <= (i >> flog), frame_len = 1 << flog in {16, 32, 64, 128}, so a workgroup's 128 rows are whole frames.
+//   dq : the workgroup at query rows Q0 .. Q0+127 streams the K/V tiles t < (Q0 + 128) / 64 only; the last two straddle the diagonal.
+//   dkv: the workgroup at key rows K0 .. K0+127 streams the Q/dO tiles t >= K0 / 64 only; the first two straddle the diagonal.
+// Every masked score is SELECTED to -inf before exp2 (P = 0 exactly) and its dP - delta to 0, so dS = 0 * 0: a select on registers,
+// never a bias or a multiply by a mask -- large finite data in masked rows cannot reach a sum.  The selects run on every streamed tile
+// (off the diagonal the compare is false for every register): a branch around them that is uniform per tile splits the tile's
+// arithmetic into basic blocks, which cost the d = 128 and d = 64 dq instances 44 / 136 bytes of scratch.  A wave whose 32 rows see
+// nothing of a tile skips the tile's arithmetic behind a wave-uniform branch; loads, waits and barriers stay outside it.  Heaviest
+// workgroup of a head first: the largest Q0 (dq), the smallest K0 (dk/dv).  The summation order is a function of (n, frame_len, d) and
+// the tile.  With FC = false nothing of this is compiled and flog is not read.
+// Accumulator register r of a lane holds streamed-tile row row0 + 8 (r >> 2) + (r & 3) + 4 lh (C layout above).  With `bound` the first
+// key the lane's query may NOT see (dq: the streamed rows are keys, masked when >= bound) or the first query that sees the lane's key
+// (dkv: the streamed rows are queries, masked when < bound), the test of register r is one compare of a constant with
+// bound - row0 - 4 lh.
+template <bool KEYS_STREAMED>
+__device__ __forceinline__ void fc_mask(f32x16& sacc, f32x16& pacc, int row0, int lh, int bound) {
+  const int lim = bound - row0 - 4 * lh;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int c = 8 * (r >> 2) + (r & 3);
+    const bool masked = KEYS_STREAMED ? c >= lim : c < lim;
+    sacc[r] = masked ? -INFINITY : sacc[r];
+    pacc[r] = masked ? 0.f : pacc[r];
+  }
+}
+// what a wave knows about the mask (all zero and unused with FC = false)
+struct FcRows {
+  int bound;     // fc_mask's bound for this lane's own row (query in dq, key in dkv)
+  int wave_end;  // dq: the wave's 32 queries see the keys [0, wave_end).  dkv: the first frame of the wave's 32 keys
+};
+template <bool FC>
+__device__ __forceinline__ FcRows fc_dq_rows(int q0, int lq, int flog) {
+  if constexpr (!FC) return FcRows{0, 0};
+  return FcRows{(((q0 + lq) >> flog) + 1) << flog, __builtin_amdgcn_readfirstlane((((q0 + 31) >> flog) + 1) << flog)};
+}
+template <bool FC>
+__device__ __forceinline__ FcRows fc_dkv_rows(int k0, int lq, int flog) {
+  if constexpr (!FC) return FcRows{0, 0};
+  return FcRows{((k0 + lq) >> flog) << flog, __builtin_amdgcn_readfirstlane(k0 >> flog)};
+}
+
 // DC / DW: head-dim columns actually multiplied when the logical head dim is smaller than the row stride D (pad columns are
 // zero): DC (multiple of 16) where the head dim is contracted (S, dP), DW (multiple of 32) where it is the output (dQ, dK, dV)
-template <int D, int DC = D, int DW = D>
+template <int D, int DC = D, int DW = D, bool FC = false>
 __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const bf16* __restrict__ Q, const bf16* __restrict__ K,
                                                           const bf16* __restrict__ V, const bf16* __restrict__ dO, long ldo,
                                                           const float* __restrict__ L2, const float* __restrict__ delta,
-                                                          bf16* __restrict__ dQ, int N, int heads, int d, float sq) {
+                                                          bf16* __restrict__ dQ, int N, int heads, int d, float sq, int flog) {
   using C = BwdCfg<D>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -83,7 +125,8 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const bf16* __restrict
   const int lin = xcd_remap(blockIdx.x, gridDim.x);
   const int bh = lin / qtiles;
   const long base = (long)bh * N * D;
-  const int q0 = (lin % qtiles) * 128 + wave * 32;
+  const int Q0 = (FC ? qtiles - 1 - lin % qtiles : lin % qtiles) * 128;  // frame-causal: the heaviest query tile of a head first
+  const int q0 = Q0 + wave * 32;
   const bf16* Kb = K + base;
   const bf16* Vb = V + base;
 
@@ -111,7 +154,8 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const bf16* __restrict
   tile_store<D>(smem, rk, tid);
   tile_store<D>(smem + C::TILE, rv, tid);
   __syncthreads();
-  const int nt = N / C::TR;
+  const int nt = FC ? (Q0 + 128) / C::TR : N / C::TR;  // frame-causal: the key tiles below the end of this workgroup's last frame
+  const FcRows fc = fc_dq_rows<FC>(q0, lq, flog);
   int cur = 0;
   for (int t = 0; t < nt; ++t) {
     const char* sk = smem + cur * 2 * C::TILE;
@@ -120,33 +164,36 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const bf16* __restrict
       tile_load<D>(Kb + (long)(t + 1) * C::TR * D, rk, tid);
       tile_load<D>(Vb + (long)(t + 1) * C::TR * D, rv, tid);
     }
-    bf16x8 dsf[2][2];
+    if (!FC || t * C::TR < fc.wave_end) {  // wave-uniform: some row of this wave sees some key of the tile
+      bf16x8 dsf[2][2];
 #pragma unroll
-    for (int kt2 = 0; kt2 < 2; ++kt2) {
-      f32x16 sacc, pacc;
+      for (int kt2 = 0; kt2 < 2; ++kt2) {
+        f32x16 sacc, pacc;
 #pragma unroll
-      for (int r = 0; r < 16; ++r) { sacc[r] = -l2; pacc[r] = -dl; }
-      const int row = kt2 * 32 + lq;
+        for (int r = 0; r < 16; ++r) { sacc[r] = -l2; pacc[r] = -dl; }
+        const int row = kt2 * 32 + lq;
 #pragma unroll
-      for (int ks = 0; ks < DC / 16; ++ks) {
-        const bf16x8 kf = *reinterpret_cast<const bf16x8*>(sk + row * C::ROWB + (ks * 2 + lh) * 16);
-        sacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[ks], sacc, 0, 0, 0);
-        const bf16x8 vf = *reinterpret_cast<const bf16x8*>(sv + row * C::ROWB + (ks * 2 + lh) * 16);
-        pacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, dof[ks], pacc, 0, 0, 0);
-      }
-#pragma unroll
-      for (int s = 0; s < 2; ++s)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) dsf[kt2][s][j] = f2bf(__builtin_amdgcn_exp2f(sacc[8 * s + j]) * pacc[8 * s + j]);
-    }
-    // dQ^T[c][q] += K^T[c][key] dS^T[key][q]
-#pragma unroll
-    for (int dvt = 0; dvt < DW / 32; ++dvt)
-#pragma unroll
-      for (int kt2 = 0; kt2 < 2; ++kt2)
+        for (int ks = 0; ks < DC / 16; ++ks) {
+          const bf16x8 kf = *reinterpret_cast<const bf16x8*>(sk + row * C::ROWB + (ks * 2 + lh) * 16);
+          sacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[ks], sacc, 0, 0, 0);
+          const bf16x8 vf = *reinterpret_cast<const bf16x8*>(sv + row * C::ROWB + (ks * 2 + lh) * 16);
+          pacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, dof[ks], pacc, 0, 0, 0);
+        }
+        if constexpr (FC) fc_mask<true>(sacc, pacc, t * C::TR + kt2 * 32, lh, fc.bound);
 #pragma unroll
         for (int s = 0; s < 2; ++s)
-          acc[dvt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_frag<D>(sk, dvt * 32, kt2, s, lane), dsf[kt2][s], acc[dvt], 0, 0, 0);
+#pragma unroll
+          for (int j = 0; j < 8; ++j) dsf[kt2][s][j] = f2bf(__builtin_amdgcn_exp2f(sacc[8 * s + j]) * pacc[8 * s + j]);
+      }
+      // dQ^T[c][q] += K^T[c][key] dS^T[key][q]
+#pragma unroll
+      for (int dvt = 0; dvt < DW / 32; ++dvt)
+#pragma unroll
+        for (int kt2 = 0; kt2 < 2; ++kt2)
+#pragma unroll
+          for (int s = 0; s < 2; ++s)
+            acc[dvt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_frag<D>(sk, dvt * 32, kt2, s, lane), dsf[kt2][s], acc[dvt], 0, 0, 0);
+    }
     if (t + 1 < nt) {
       char* nk = smem + (cur ^ 1) * 2 * C::TILE;
       tile_store<D>(nk, rk, tid);
@@ -172,12 +219,12 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const bf16* __restrict
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-template <int D, int DC = D, int DW = D>
+template <int D, int DC = D, int DW = D, bool FC = false>
 __global__ __launch_bounds__(256, (DC <= 96 ? 2 : 1)) void attn_bwd_dkv_kernel(const bf16* __restrict__ Q, const bf16* __restrict__ K,
                                                            const bf16* __restrict__ V, const bf16* __restrict__ dO, long ldo,
                                                            const float* __restrict__ L2, const float* __restrict__ delta,
                                                            bf16* __restrict__ dK, bf16* __restrict__ dV, int N, int heads, int d,
-                                                           float sk_scale) {
+                                                           float sk_scale, int flog) {
   using C = BwdCfg<D>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -186,7 +233,8 @@ __global__ __launch_bounds__(256, (DC <= 96 ? 2 : 1)) void attn_bwd_dkv_kernel(c
   const int lin = xcd_remap(blockIdx.x, gridDim.x);
   const int bh = lin / ktiles;
   const long base = (long)bh * N * D;
-  const int k0 = (lin % ktiles) * 128 + wave * 32;
+  const int K0 = (lin % ktiles) * 128;  // frame-causal: the smallest K0 streams the most query tiles, and it comes first as it is
+  const int k0 = K0 + wave * 32;
   const bf16* Qb = Q + base;
   const bf16* Ob = dO + (long)(bh / heads) * N * ldo + (long)(bh % heads) * d;  // compact [B*N][ldo], this head's columns
   const float* Lb = L2 + (long)bh * N;
@@ -224,58 +272,63 @@ __global__ __launch_bounds__(256, (DC <= 96 ? 2 : 1)) void attn_bwd_dkv_kernel(c
     tile_store<D>(b + C::TILE, ro, tid);
     if (tid < 2 * C::TR) reinterpret_cast<float*>(b + 2 * C::TILE)[tid] = rs;
   };
-  load(0);
+  const int t0 = FC ? K0 / C::TR : 0;  // frame-causal: no earlier query sees these keys
+  load(t0);
   store(0);
   __syncthreads();
   const int nt = N / C::TR;
+  const FcRows fc = fc_dkv_rows<FC>(k0, lq, flog);
   int cur = 0;
-  for (int t = 0; t < nt; ++t) {
+  for (int t = t0; t < nt; ++t) {
     const char* sq = smem + cur * STAGE;
     const char* so = sq + C::TILE;
     const float* sl = reinterpret_cast<const float*>(sq + 2 * C::TILE);
     const float* sd = sl + C::TR;
-    bf16x8 pf[2][2], dsf[2][2];
+    if (!FC || ((t * C::TR + C::TR - 1) >> flog) >= fc.wave_end) {  // wave-uniform: some query of the tile sees some key of this wave
+      bf16x8 pf[2][2], dsf[2][2];
 #pragma unroll
-    for (int kt2 = 0; kt2 < 2; ++kt2) {
-      // accumulators start at -L2[q] / -delta[q] of their row (q = kt2*32 + 8g + 4h + j; the LDS copies are negated): the four 16-byte
-      // reads ARE the accumulator tuple -- no move, no negation on the vector pipe
-      f32x4 l4[4], d4[4];
+      for (int kt2 = 0; kt2 < 2; ++kt2) {
+        // accumulators start at -L2[q] / -delta[q] of their row (q = kt2*32 + 8g + 4h + j; the LDS copies are negated): the four 16-byte
+        // reads ARE the accumulator tuple -- no move, no negation on the vector pipe
+        f32x4 l4[4], d4[4];
 #pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        l4[g] = *reinterpret_cast<const f32x4*>(sl + kt2 * 32 + 8 * g + 4 * lh);
-        d4[g] = *reinterpret_cast<const f32x4*>(sd + kt2 * 32 + 8 * g + 4 * lh);
-      }
-      typedef __attribute__((ext_vector_type(8))) float f32x8;
-      f32x16 sacc = __builtin_shufflevector(__builtin_shufflevector(l4[0], l4[1], 0, 1, 2, 3, 4, 5, 6, 7), __builtin_shufflevector(l4[2], l4[3], 0, 1, 2, 3, 4, 5, 6, 7),
-                                            0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15);
-      f32x16 pacc = __builtin_shufflevector(__builtin_shufflevector(d4[0], d4[1], 0, 1, 2, 3, 4, 5, 6, 7), __builtin_shufflevector(d4[2], d4[3], 0, 1, 2, 3, 4, 5, 6, 7),
-                                            0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15);
-      const int row = kt2 * 32 + lq;
-#pragma unroll
-      for (int ks = 0; ks < DC / 16; ++ks) {
-        const bf16x8 qa = *reinterpret_cast<const bf16x8*>(sq + row * C::ROWB + (ks * 2 + lh) * 16);
-        sacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qa, kf[ks], sacc, 0, 0, 0);
-        const bf16x8 oa = *reinterpret_cast<const bf16x8*>(so + row * C::ROWB + (ks * 2 + lh) * 16);
-        pacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(oa, vf[ks], pacc, 0, 0, 0);
-      }
-#pragma unroll
-      for (int s = 0; s < 2; ++s)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const float p = __builtin_amdgcn_exp2f(sacc[8 * s + j]);
-          pf[kt2][s][j] = f2bf(p);
-          dsf[kt2][s][j] = f2bf(p * pacc[8 * s + j]);
+        for (int g = 0; g < 4; ++g) {
+          l4[g] = *reinterpret_cast<const f32x4*>(sl + kt2 * 32 + 8 * g + 4 * lh);
+          d4[g] = *reinterpret_cast<const f32x4*>(sd + kt2 * 32 + 8 * g + 4 * lh);
         }
+        typedef __attribute__((ext_vector_type(8))) float f32x8;
+        f32x16 sacc = __builtin_shufflevector(__builtin_shufflevector(l4[0], l4[1], 0, 1, 2, 3, 4, 5, 6, 7), __builtin_shufflevector(l4[2], l4[3], 0, 1, 2, 3, 4, 5, 6, 7),
+                                              0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15);
+        f32x16 pacc = __builtin_shufflevector(__builtin_shufflevector(d4[0], d4[1], 0, 1, 2, 3, 4, 5, 6, 7), __builtin_shufflevector(d4[2], d4[3], 0, 1, 2, 3, 4, 5, 6, 7),
+                                              0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15);
+        const int row = kt2 * 32 + lq;
+#pragma unroll
+        for (int ks = 0; ks < DC / 16; ++ks) {
+          const bf16x8 qa = *reinterpret_cast<const bf16x8*>(sq + row * C::ROWB + (ks * 2 + lh) * 16);
+          sacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qa, kf[ks], sacc, 0, 0, 0);
+          const bf16x8 oa = *reinterpret_cast<const bf16x8*>(so + row * C::ROWB + (ks * 2 + lh) * 16);
+          pacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(oa, vf[ks], pacc, 0, 0, 0);
+        }
+        if constexpr (FC) fc_mask<false>(sacc, pacc, t * C::TR + kt2 * 32, lh, fc.bound);
+#pragma unroll
+        for (int s = 0; s < 2; ++s)
+#pragma unroll
+          for (int j = 0; j < 8; ++j) {
+            const float p = __builtin_amdgcn_exp2f(sacc[8 * s + j]);
+            pf[kt2][s][j] = f2bf(p);
+            dsf[kt2][s][j] = f2bf(p * pacc[8 * s + j]);
+          }
+      }
+#pragma unroll
+      for (int dvt = 0; dvt < DW / 32; ++dvt)
+#pragma unroll
+        for (int kt2 = 0; kt2 < 2; ++kt2)
+#pragma unroll
+          for (int s = 0; s < 2; ++s) {
+            dva[dvt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_frag<D>(so, dvt * 32, kt2, s, lane), pf[kt2][s], dva[dvt], 0, 0, 0);
+            dka[dvt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_frag<D>(sq, dvt * 32, kt2, s, lane), dsf[kt2][s], dka[dvt], 0, 0, 0);
+          }
     }
-#pragma unroll
-    for (int dvt = 0; dvt < DW / 32; ++dvt)
-#pragma unroll
-      for (int kt2 = 0; kt2 < 2; ++kt2)
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-          dva[dvt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_frag<D>(so, dvt * 32, kt2, s, lane), pf[kt2][s], dva[dvt], 0, 0, 0);
-          dka[dvt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_frag<D>(sq, dvt * 32, kt2, s, lane), dsf[kt2][s], dka[dvt], 0, 0, 0);
-        }
     if (t + 1 < nt) {  // staged after the products: the tile registers are not live across them (register budget at D = 128)
       load(t + 1);
       store(cur ^ 1);
@@ -352,11 +405,11 @@ __device__ __forceinline__ void bw_tr_frags(unsigned tile_addr, int dvt, int lan
   f[1][1] = as_bf16x8(r110, r111);
 }
 
-template <int D, int DC = D, int DW = D>
+template <int D, int DC = D, int DW = D, bool FC = false>
 __global__ __launch_bounds__(256, (D == 64 ? 3 : 2)) void attn_bwd_dq_dma_kernel(const bf16* __restrict__ Q, const bf16* __restrict__ K,
                                                                  const bf16* __restrict__ V, const bf16* __restrict__ dO, long ldo,
                                                                  const float* __restrict__ L2, const float* __restrict__ delta,
-                                                                 bf16* __restrict__ dQ, int N, int heads, int d, float sq) {
+                                                                 bf16* __restrict__ dQ, int N, int heads, int d, float sq, int flog) {
   using C = DmaCfg<D>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -365,7 +418,8 @@ __global__ __launch_bounds__(256, (D == 64 ? 3 : 2)) void attn_bwd_dq_dma_kernel
   const int lin = xcd_remap(blockIdx.x, gridDim.x);
   const int bh = lin / qtiles;
   const long base = (long)bh * N * D;
-  const int q0 = (lin % qtiles) * 128 + wave * 32;
+  const int Q0 = (FC ? qtiles - 1 - lin % qtiles : lin % qtiles) * 128;  // frame-causal: the heaviest query tile of a head first
+  const int q0 = Q0 + wave * 32;
   const bf16* Kb = K + base;
   const bf16* Vb = V + base;
 
@@ -414,7 +468,8 @@ __global__ __launch_bounds__(256, (D == 64 ? 3 : 2)) void attn_bwd_dq_dma_kernel
   for (int ks = 0; ks < DC / 16; ++ks) asm volatile("" : "+v"(qf[ks]), "+v"(dof[ks]));  // see attn_bwd_dkv_dma_kernel
   float l2v = l2, dlv = dl;
   asm volatile("" : "+v"(l2v), "+v"(dlv));
-  const int nt = N / C::TR;
+  const int nt = FC ? (Q0 + 128) / C::TR : N / C::TR;  // frame-causal: the key tiles below the end of this workgroup's last frame
+  const FcRows fc = fc_dq_rows<FC>(q0, lq, flog);
   const unsigned lds0 = (unsigned)(size_t)DFOT_LDS_PTR(smem);
   int cur = 0;
   for (int t = 0; t < nt; ++t) {
@@ -426,36 +481,39 @@ __global__ __launch_bounds__(256, (D == 64 ? 3 : 2)) void attn_bwd_dq_dma_kernel
     int lv = lane;
     asm volatile("" : "+v"(lv));
     const int lqv = lv & 31, lhv = lv >> 5;
-    bf16x8 dsf[2][2];
+    if (!FC || t * C::TR < fc.wave_end) {  // wave-uniform: some row of this wave sees some key of the tile
+      bf16x8 dsf[2][2];
 #pragma unroll
-    for (int kt2 = 0; kt2 < 2; ++kt2) {
-      f32x16 sacc, pacc;
+      for (int kt2 = 0; kt2 < 2; ++kt2) {
+        f32x16 sacc, pacc;
 #pragma unroll
-      for (int r = 0; r < 16; ++r) { sacc[r] = -l2v; pacc[r] = -dlv; }
-      const int row = kt2 * 32 + lqv;
+        for (int r = 0; r < 16; ++r) { sacc[r] = -l2v; pacc[r] = -dlv; }
+        const int row = kt2 * 32 + lqv;
 #pragma unroll
-      for (int ks = 0; ks < DC / 16; ++ks) {
-        const int off = row * C::ROWB + C::swz(row, ks * 2 + lhv) * 16;
-        const bf16x8 kf = *reinterpret_cast<const bf16x8*>(sk + off);
-        sacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[ks], sacc, 0, 0, 0);
-        const bf16x8 vf = *reinterpret_cast<const bf16x8*>(sv + off);
-        pacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, dof[ks], pacc, 0, 0, 0);
+        for (int ks = 0; ks < DC / 16; ++ks) {
+          const int off = row * C::ROWB + C::swz(row, ks * 2 + lhv) * 16;
+          const bf16x8 kf = *reinterpret_cast<const bf16x8*>(sk + off);
+          sacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[ks], sacc, 0, 0, 0);
+          const bf16x8 vf = *reinterpret_cast<const bf16x8*>(sv + off);
+          pacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, dof[ks], pacc, 0, 0, 0);
+        }
+        if constexpr (FC) fc_mask<true>(sacc, pacc, t * C::TR + kt2 * 32, lhv, fc.bound);
+#pragma unroll
+        for (int s = 0; s < 2; ++s)
+#pragma unroll
+          for (int j = 0; j < 8; ++j) dsf[kt2][s][j] = f2bf(__builtin_amdgcn_exp2f(sacc[8 * s + j]) * pacc[8 * s + j]);
       }
+      // dQ^T[c][q] += K^T[c][key] dS^T[key][q]
+      const unsigned ka = lds0 + cur * 2 * C::TILE;
 #pragma unroll
-      for (int s = 0; s < 2; ++s)
+      for (int dvt = 0; dvt < DW / 32; ++dvt) {
+        bf16x8 kt[2][2];
+        bw_tr_frags<D>(ka, dvt, lv, kt);
 #pragma unroll
-        for (int j = 0; j < 8; ++j) dsf[kt2][s][j] = f2bf(__builtin_amdgcn_exp2f(sacc[8 * s + j]) * pacc[8 * s + j]);
-    }
-    // dQ^T[c][q] += K^T[c][key] dS^T[key][q]
-    const unsigned ka = lds0 + cur * 2 * C::TILE;
+        for (int kt2 = 0; kt2 < 2; ++kt2)
 #pragma unroll
-    for (int dvt = 0; dvt < DW / 32; ++dvt) {
-      bf16x8 kt[2][2];
-      bw_tr_frags<D>(ka, dvt, lv, kt);
-#pragma unroll
-      for (int kt2 = 0; kt2 < 2; ++kt2)
-#pragma unroll
-        for (int s = 0; s < 2; ++s) acc[dvt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kt[kt2][s], dsf[kt2][s], acc[dvt], 0, 0, 0);
+          for (int s = 0; s < 2; ++s) acc[dvt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kt[kt2][s], dsf[kt2][s], acc[dvt], 0, 0, 0);
+      }
     }
     asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
     cur ^= 1;
@@ -478,12 +536,12 @@ __global__ __launch_bounds__(256, (D == 64 ? 3 : 2)) void attn_bwd_dq_dma_kernel
 
 // (the d = 128 instance holds k, v fragments (64 VGPRs) and the dK, dV accumulators (128): 256 cannot be met, it keeps one wave per
 // SIMD -- what it gains is the prefetch of the next tile behind the products)
-template <int D, int DC = D, int DW = D>
+template <int D, int DC = D, int DW = D, bool FC = false>
 __global__ __launch_bounds__(256, (DC <= 96 ? 2 : 1)) void attn_bwd_dkv_dma_kernel(const bf16* __restrict__ Q, const bf16* __restrict__ K,
                                                                   const bf16* __restrict__ V, const bf16* __restrict__ dO, long ldo,
                                                                   const float* __restrict__ L2, const float* __restrict__ delta,
                                                                   bf16* __restrict__ dK, bf16* __restrict__ dV, int N, int heads, int d,
-                                                                  float sk_scale, const bf16* __restrict__ zeros) {
+                                                                  float sk_scale, const bf16* __restrict__ zeros, int flog) {
   using C = DmaCfg<D>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -492,7 +550,8 @@ __global__ __launch_bounds__(256, (DC <= 96 ? 2 : 1)) void attn_bwd_dkv_dma_kern
   const int lin = xcd_remap(blockIdx.x, gridDim.x);
   const int bh = lin / ktiles;
   const long base = (long)bh * N * D;
-  const int k0 = (lin % ktiles) * 128 + wave * 32;
+  const int K0 = (lin % ktiles) * 128;  // frame-causal: the smallest K0 streams the most query tiles, and it comes first as it is
+  const int k0 = K0 + wave * 32;
   const bf16* Qb = Q + base;
   const bf16* Ob = dO + (long)(bh / heads) * N * ldo + (long)(bh % heads) * d;  // compact [B*N][ldo], this head's columns
   const float* Lb = L2 + (long)bh * N;
@@ -534,7 +593,8 @@ __global__ __launch_bounds__(256, (DC <= 96 ? 2 : 1)) void attn_bwd_dkv_dma_kern
   auto store_stats = [&](int stage) {
     if (tid < 2 * C::TR) reinterpret_cast<float*>(smem + stage * STAGE + 2 * C::TILE)[tid] = rs;
   };
-  issue(0, 0);
+  const int t0 = FC ? K0 / C::TR : 0;  // frame-causal: no earlier query sees these keys
+  issue(t0, 0);
 
   bf16x8 kf[DC / 16], vf[DC / 16];
 #pragma unroll
@@ -555,9 +615,10 @@ __global__ __launch_bounds__(256, (DC <= 96 ? 2 : 1)) void attn_bwd_dkv_dma_kern
 #pragma unroll
   for (int ks = 0; ks < DC / 16; ++ks) asm volatile("" : "+v"(kf[ks]), "+v"(vf[ks]));
   const int nt = N / C::TR;
+  const FcRows fc = fc_dkv_rows<FC>(k0, lq, flog);
   const unsigned lds0 = (unsigned)(size_t)DFOT_LDS_PTR(smem);
   int cur = 0;
-  for (int t = 0; t < nt; ++t) {
+  for (int t = t0; t < nt; ++t) {
     const char* sq = smem + cur * STAGE;
     const char* so = sq + C::TILE;
     const float* sl = reinterpret_cast<const float*>(sq + 2 * C::TILE);
@@ -566,50 +627,53 @@ __global__ __launch_bounds__(256, (DC <= 96 ? 2 : 1)) void attn_bwd_dkv_dma_kern
     int lv = lane;  // opaque per tile: see attn_bwd_dq_dma_kernel
     asm volatile("" : "+v"(lv));
     const int lqv = lv & 31, lhv = lv >> 5;
-    bf16x8 pf[2][2], dsf[2][2];
+    if (!FC || ((t * C::TR + C::TR - 1) >> flog) >= fc.wave_end) {  // wave-uniform: some query of the tile sees some key of this wave
+      bf16x8 pf[2][2], dsf[2][2];
 #pragma unroll
-    for (int kt2 = 0; kt2 < 2; ++kt2) {
-      f32x16 sacc, pacc;
-      // accumulators start at -L2[q] / -delta[q] of their row: q = kt2*32 + 8g + 4h + j (the LDS copies are negated)
+      for (int kt2 = 0; kt2 < 2; ++kt2) {
+        f32x16 sacc, pacc;
+        // accumulators start at -L2[q] / -delta[q] of their row: q = kt2*32 + 8g + 4h + j (the LDS copies are negated)
 #pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const f32x4 l4 = *reinterpret_cast<const f32x4*>(sl + kt2 * 32 + 8 * g + 4 * lhv);
-        const f32x4 d4 = *reinterpret_cast<const f32x4*>(sd + kt2 * 32 + 8 * g + 4 * lhv);
+        for (int g = 0; g < 4; ++g) {
+          const f32x4 l4 = *reinterpret_cast<const f32x4*>(sl + kt2 * 32 + 8 * g + 4 * lhv);
+          const f32x4 d4 = *reinterpret_cast<const f32x4*>(sd + kt2 * 32 + 8 * g + 4 * lhv);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) { sacc[4 * g + j] = NEGL ? l4[j] : -l4[j]; pacc[4 * g + j] = NEGL ? d4[j] : -d4[j]; }
-      }
-      const int row = kt2 * 32 + lqv;
-#pragma unroll
-      for (int ks = 0; ks < DC / 16; ++ks) {
-        const int off = row * C::ROWB + C::swz(row, ks * 2 + lhv) * 16;
-        const bf16x8 qa = *reinterpret_cast<const bf16x8*>(sq + off);
-        sacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qa, kf[ks], sacc, 0, 0, 0);
-        const bf16x8 oa = *reinterpret_cast<const bf16x8*>(so + off);
-        pacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(oa, vf[ks], pacc, 0, 0, 0);
-      }
-#pragma unroll
-      for (int s = 0; s < 2; ++s)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const float p = __builtin_amdgcn_exp2f(sacc[8 * s + j]);
-          pf[kt2][s][j] = f2bf(p);
-          dsf[kt2][s][j] = f2bf(p * pacc[8 * s + j]);
+          for (int j = 0; j < 4; ++j) { sacc[4 * g + j] = NEGL ? l4[j] : -l4[j]; pacc[4 * g + j] = NEGL ? d4[j] : -d4[j]; }
         }
-    }
-    const unsigned qa0 = lds0 + cur * STAGE, oa0 = qa0 + C::TILE;
+        const int row = kt2 * 32 + lqv;
 #pragma unroll
-    for (int dvt = 0; dvt < DW / 32; ++dvt) {
-      bf16x8 ft[2][2];
-      bw_tr_frags<D>(oa0, dvt, lv, ft);
+        for (int ks = 0; ks < DC / 16; ++ks) {
+          const int off = row * C::ROWB + C::swz(row, ks * 2 + lhv) * 16;
+          const bf16x8 qa = *reinterpret_cast<const bf16x8*>(sq + off);
+          sacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qa, kf[ks], sacc, 0, 0, 0);
+          const bf16x8 oa = *reinterpret_cast<const bf16x8*>(so + off);
+          pacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(oa, vf[ks], pacc, 0, 0, 0);
+        }
+        if constexpr (FC) fc_mask<false>(sacc, pacc, t * C::TR + kt2 * 32, lhv, fc.bound);
 #pragma unroll
-      for (int kt2 = 0; kt2 < 2; ++kt2)
+        for (int s = 0; s < 2; ++s)
 #pragma unroll
-        for (int s = 0; s < 2; ++s) dva[dvt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ft[kt2][s], pf[kt2][s], dva[dvt], 0, 0, 0);
-      bw_tr_frags<D>(qa0, dvt, lv, ft);
+          for (int j = 0; j < 8; ++j) {
+            const float p = __builtin_amdgcn_exp2f(sacc[8 * s + j]);
+            pf[kt2][s][j] = f2bf(p);
+            dsf[kt2][s][j] = f2bf(p * pacc[8 * s + j]);
+          }
+      }
+      const unsigned qa0 = lds0 + cur * STAGE, oa0 = qa0 + C::TILE;
 #pragma unroll
-      for (int kt2 = 0; kt2 < 2; ++kt2)
+      for (int dvt = 0; dvt < DW / 32; ++dvt) {
+        bf16x8 ft[2][2];
+        bw_tr_frags<D>(oa0, dvt, lv, ft);
 #pragma unroll
-        for (int s = 0; s < 2; ++s) dka[dvt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ft[kt2][s], dsf[kt2][s], dka[dvt], 0, 0, 0);
+        for (int kt2 = 0; kt2 < 2; ++kt2)
+#pragma unroll
+          for (int s = 0; s < 2; ++s) dva[dvt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ft[kt2][s], pf[kt2][s], dva[dvt], 0, 0, 0);
+        bw_tr_frags<D>(qa0, dvt, lv, ft);
+#pragma unroll
+        for (int kt2 = 0; kt2 < 2; ++kt2)
+#pragma unroll
+          for (int s = 0; s < 2; ++s) dka[dvt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ft[kt2][s], dsf[kt2][s], dka[dvt], 0, 0, 0);
+      }
     }
     if (t + 1 < nt) store_stats(cur ^ 1);
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
@@ -736,9 +800,9 @@ int launch_attention_bwd_delta(const bf16* o, const bf16* d_o, long ldo, float* 
 
 const bf16* g_bwd_zeros = nullptr;
 
-template <int D, int DC = D, int DW = D>
+template <int D, int DC = D, int DW = D, bool FC = false>
 static int launch_bwd_t(const bf16* q, const bf16* k, const bf16* v, const bf16* d_o, long ldo, const float* l2, const float* delta, bf16* dq,
-                        bf16* dk, bf16* dv, int batch, int heads, int n, int d, float sq, float sk, hipStream_t s) {
+                        bf16* dk, bf16* dv, int batch, int heads, int n, int d, float sq, float sk, hipStream_t s, int flog = 0) {
   // 1 (default): LDS-DMA forms for the 128-element-row instances only; 2: for all; 0: register-staged everywhere.  Measured
   // (RE10K step, same box): d = 128 dq 367 -> 253 us, dk/dv 567 -> 480 us; d = 64 dq 1782 -> 1782 us, dk/dv 2377 -> 2565 us (its
   // 226 VGPRs leave two waves per SIMD where the register-staged form's 167 leave three)
@@ -747,28 +811,28 @@ static int launch_bwd_t(const bf16* q, const bf16* k, const bf16* v, const bf16*
   if (dma == 2 || (dma == 1 && D == 128)) {
     using C = DmaCfg<D>;
     const int lds1 = 4 * C::TILE, lds2 = 2 * (2 * C::TILE + 2 * C::TR * 4);
-    if (int rc = ensure_dyn_lds<attn_bwd_dq_dma_kernel<D, DC, DW>>(lds1)) return rc;
-    if (int rc = ensure_dyn_lds<attn_bwd_dkv_dma_kernel<D, DC, DW>>(lds2)) return rc;
+    if (int rc = ensure_dyn_lds<attn_bwd_dq_dma_kernel<D, DC, DW, FC>>(lds1)) return rc;
+    if (int rc = ensure_dyn_lds<attn_bwd_dkv_dma_kernel<D, DC, DW, FC>>(lds2)) return rc;
     if (!g_bwd_zeros) {
       void* z = nullptr;
       DFOT_CHECK_HIP(hipMalloc(&z, 256));
       DFOT_CHECK_HIP(hipMemset(z, 0, 256));
       g_bwd_zeros = (const bf16*)z;
     }
-    hipLaunchKernelGGL((attn_bwd_dq_dma_kernel<D, DC, DW>), dim3(grid), dim3(256), lds1, s, q, k, v, d_o, ldo, l2, delta, dq, n, heads, d, sq);
+    hipLaunchKernelGGL((attn_bwd_dq_dma_kernel<D, DC, DW, FC>), dim3(grid), dim3(256), lds1, s, q, k, v, d_o, ldo, l2, delta, dq, n, heads, d, sq, flog);
     DFOT_CHECK_HIP(hipGetLastError());
-    hipLaunchKernelGGL((attn_bwd_dkv_dma_kernel<D, DC, DW>), dim3(grid), dim3(256), lds2, s, q, k, v, d_o, ldo, l2, delta, dk, dv, n, heads, d, sk,
-                       g_bwd_zeros);
+    hipLaunchKernelGGL((attn_bwd_dkv_dma_kernel<D, DC, DW, FC>), dim3(grid), dim3(256), lds2, s, q, k, v, d_o, ldo, l2, delta, dk, dv, n, heads, d, sk,
+                       g_bwd_zeros, flog);
     DFOT_CHECK_HIP(hipGetLastError());
     return DFOT_OK;
   }
   using C = BwdCfg<D>;
   const int lds1 = 4 * C::TILE, lds2 = 2 * (2 * C::TILE + 2 * C::TR * 4);
-  if (int rc = ensure_dyn_lds<attn_bwd_dq_kernel<D, DC, DW>>(lds1)) return rc;
-  if (int rc = ensure_dyn_lds<attn_bwd_dkv_kernel<D, DC, DW>>(lds2)) return rc;
-  hipLaunchKernelGGL((attn_bwd_dq_kernel<D, DC, DW>), dim3(grid), dim3(256), lds1, s, q, k, v, d_o, ldo, l2, delta, dq, n, heads, d, sq);
+  if (int rc = ensure_dyn_lds<attn_bwd_dq_kernel<D, DC, DW, FC>>(lds1)) return rc;
+  if (int rc = ensure_dyn_lds<attn_bwd_dkv_kernel<D, DC, DW, FC>>(lds2)) return rc;
+  hipLaunchKernelGGL((attn_bwd_dq_kernel<D, DC, DW, FC>), dim3(grid), dim3(256), lds1, s, q, k, v, d_o, ldo, l2, delta, dq, n, heads, d, sq, flog);
   DFOT_CHECK_HIP(hipGetLastError());
-  hipLaunchKernelGGL((attn_bwd_dkv_kernel<D, DC, DW>), dim3(grid), dim3(256), lds2, s, q, k, v, d_o, ldo, l2, delta, dk, dv, n, heads, d, sk);
+  hipLaunchKernelGGL((attn_bwd_dkv_kernel<D, DC, DW, FC>), dim3(grid), dim3(256), lds2, s, q, k, v, d_o, ldo, l2, delta, dk, dv, n, heads, d, sk, flog);
   DFOT_CHECK_HIP(hipGetLastError());
   return DFOT_OK;
 }
@@ -789,4 +853,47 @@ int launch_attention_bwd(const bf16* q, const bf16* k, const bf16* v, const bf16
 #undef BWD_ARGS
 }
 
+static int fc_bwd_shape_check(int batch, int heads, int n, int frame_len, int d, long ldo) {
+  DFOT_REQUIRE(frame_len == 16 || frame_len == 32 || frame_len == 64 || frame_len == 128, DFOT_ERR_SHAPE,
+               "attention_frame_causal_bwd: frame_len %d not in {16, 32, 64, 128}", frame_len);
+  DFOT_REQUIRE(n > 0 && n % 128 == 0, DFOT_ERR_SHAPE, "attention_frame_causal_bwd: N=%d must be a positive multiple of 128", n);
+  DFOT_REQUIRE(d > 0 && d <= 128 && d % 8 == 0, DFOT_ERR_SHAPE, "attention_frame_causal_bwd: head dim %d must be a multiple of 8, <= 128", d);
+  DFOT_REQUIRE(batch > 0 && heads > 0 && (long)batch * heads * (n / 128) < (1L << 31), DFOT_ERR_SHAPE,
+               "attention_frame_causal_bwd: batch %d x heads %d x %d tiles exceeds the grid", batch, heads, n / 128);
+  DFOT_REQUIRE(ldo % 8 == 0 && ldo >= (long)heads * d, DFOT_ERR_SHAPE,
+               "attention_frame_causal_bwd: d_o row stride %ld must be a multiple of 8 covering heads*d = %d", ldo, heads * d);
+  return DFOT_OK;
+}
+
+// the backward of launch_attention_frame_causal (attention_frame_causal.hip), operands and scale factors as launch_attention_bwd: the FC
+// instantiations of the same four kernels.  l2: the forward's lse; delta: launch_attention_bwd_delta
+int launch_attention_frame_causal_bwd(const bf16* q, const bf16* k, const bf16* v, const bf16* d_o, long ldo, const float* l2,
+                                      const float* delta, bf16* dq, bf16* dk, bf16* dv, int batch, int heads, int n, int frame_len, int d,
+                                      hipStream_t s) {
+  DFOT_REQUIRE(q && k && v && d_o && l2 && delta && dq && dk && dv, DFOT_ERR_ARG, "attention_frame_causal_bwd: null pointer");
+  if (int rc = fc_bwd_shape_check(batch, heads, n, frame_len, d, ldo)) return rc;
+  const int flog = frame_len == 16 ? 4 : frame_len == 32 ? 5 : frame_len == 64 ? 6 : 7;
+  const float sq = 1.0f / sqrtf((float)d), sk = 0.6931471805599453f;
+#define BWD_ARGS q, k, v, d_o, ldo, l2, delta, dq, dk, dv, batch, heads, n, d, sq, sk, s, flog
+  if (d <= 32) return launch_bwd_t<64, 32, 32, true>(BWD_ARGS);
+  if (d <= 64) return launch_bwd_t<64, 64, 64, true>(BWD_ARGS);
+  if (d <= 80) return launch_bwd_t<128, 80, 96, true>(BWD_ARGS);
+  if (d <= 96) return launch_bwd_t<128, 96, 96, true>(BWD_ARGS);
+  return launch_bwd_t<128, 128, 128, true>(BWD_ARGS);
+#undef BWD_ARGS
+}
+
 }  // namespace dfot
+
+extern "C" int dfot_op_attention_frame_causal_bwd(const void* q, const void* k, const void* v, const void* o, const void* d_o, int ldo,
+                                                  const float* lse, float* delta, void* dq, void* dk, void* dv, int batch, int heads, int n,
+                                                  int frame_len, int d, void* stream) {
+  using dfot::bf16;
+  DFOT_REQUIRE(q && k && v && o && d_o && lse && delta && dq && dk && dv, DFOT_ERR_ARG, "attention_frame_causal_bwd: null pointer");
+  // the shape rules are checked before the delta launch: nothing runs on a refused call
+  if (int rc = dfot::fc_bwd_shape_check(batch, heads, n, frame_len, d, ldo)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  if (int rc = dfot::launch_attention_bwd_delta((const bf16*)o, (const bf16*)d_o, ldo, delta, batch, heads, n, d, s)) return rc;
+  return dfot::launch_attention_frame_causal_bwd((const bf16*)q, (const bf16*)k, (const bf16*)v, (const bf16*)d_o, ldo, lse, delta, (bf16*)dq,
+                                                 (bf16*)dk, (bf16*)dv, batch, heads, n, frame_len, d, s);
+}

@@ -27,10 +27,12 @@
 
 namespace dfot {
 
-template <int D, int NST, int DQK, int DV>
+// LSE (training): the kernel also leaves the log2-domain log-sum-exp of every query row, lse[(b * heads + head) * N + row] = m + log2(l),
+// which attention_bwd.hip's frame-causal kernels consume.  A compile-time parameter: the inference instantiation carries no test of it.
+template <int D, int NST, int DQK, int DV, bool LSE>
 __global__ __launch_bounds__(256) void attn_frame_causal_kernel(const bf16* __restrict__ Q, const bf16* __restrict__ K,
                                                                 const bf16* __restrict__ V, bf16* __restrict__ O, long ldo, int N,
-                                                                int heads, int flog, int ohs, int dvalid) {
+                                                                int heads, int flog, int ohs, int dvalid, float* __restrict__ lse) {
   static_assert(DQK % 16 == 0 && DV % 32 == 0 && DQK <= D && DV <= D, "head-dim sub-range");
   using C = AttnCfg<D>;
   constexpr float THR = 8.0f;
@@ -223,6 +225,9 @@ __global__ __launch_bounds__(256) void attn_frame_causal_kernel(const bf16* __re
   // ---- normalise and store: lane holds O[q0+lq][dvt*32 + 8*g + 4*lh + {0..3}] in oacc[dvt][4g..4g+3] ----
   const float l_tot = l_i + __shfl_xor(l_i, 32);
   const float inv = 1.0f / l_tot;
+  if constexpr (LSE) {
+    if (lh == 0) lse[(long)bh * N + q0 + lq] = m_run + __log2f(l_tot);  // one of the row's two lanes
+  }
   const int b = bh / heads, hd = bh % heads;
   bf16* orow = O + ((long)b * N + q0 + lq) * ldo + hd * ohs;
 #pragma unroll
@@ -237,19 +242,25 @@ __global__ __launch_bounds__(256) void attn_frame_causal_kernel(const bf16* __re
     }
 }
 
-template <int D, int NST, int DQK, int DV>
-static int launch_fc(const bf16* q, const bf16* k, const bf16* v, bf16* o, long ldo, int batch, int heads, int n, int flog, int d,
-                     hipStream_t stream) {
-  constexpr auto kern = attn_frame_causal_kernel<D, NST, DQK, DV>;
+template <int D, int NST, int DQK, int DV, bool LSE>
+static int launch_fc_t(const bf16* q, const bf16* k, const bf16* v, bf16* o, long ldo, int batch, int heads, int n, int flog, int d,
+                       hipStream_t stream, float* lse) {
+  constexpr auto kern = attn_frame_causal_kernel<D, NST, DQK, DV, LSE>;
   const int lds = 2 * NST * AttnCfg<D>::TILE;  // NST stages of (K, V): 48 KiB (D = 64, three stages) or 64 KiB (D = 128, two)
   if (int rc = ensure_dyn_lds<kern>(lds)) return rc;
-  hipLaunchKernelGGL(kern, dim3((n / 128) * batch * heads), dim3(256), lds, stream, q, k, v, o, ldo, n, heads, flog, d, d);
+  hipLaunchKernelGGL(kern, dim3((n / 128) * batch * heads), dim3(256), lds, stream, q, k, v, o, ldo, n, heads, flog, d, d, lse);
   DFOT_CHECK_HIP(hipGetLastError());
   return DFOT_OK;
 }
+template <int D, int NST, int DQK, int DV>
+static int launch_fc(const bf16* q, const bf16* k, const bf16* v, bf16* o, long ldo, int batch, int heads, int n, int flog, int d,
+                     hipStream_t stream, float* lse) {
+  return lse ? launch_fc_t<D, NST, DQK, DV, true>(q, k, v, o, ldo, batch, heads, n, flog, d, stream, lse)
+             : launch_fc_t<D, NST, DQK, DV, false>(q, k, v, o, ldo, batch, heads, n, flog, d, stream, nullptr);
+}
 
 int launch_attention_frame_causal(const bf16* q, const bf16* k, const bf16* v, bf16* o, long ldo, int batch, int heads, int n,
-                                  int frame_len, int d, hipStream_t stream) {
+                                  int frame_len, int d, hipStream_t stream, float* lse) {
   DFOT_REQUIRE(q && k && v && o, DFOT_ERR_ARG, "attention_frame_causal: null pointer");
   DFOT_REQUIRE(frame_len == 16 || frame_len == 32 || frame_len == 64 || frame_len == 128, DFOT_ERR_SHAPE,
                "attention_frame_causal: frame_len %d not in {16, 32, 64, 128}", frame_len);
@@ -261,11 +272,11 @@ int launch_attention_frame_causal(const bf16* q, const bf16* k, const bf16* v, b
                "attention_frame_causal: output row stride %ld must be a multiple of 8 covering heads*d = %d", ldo, heads * d);
   const int flog = frame_len == 16 ? 4 : frame_len == 32 ? 5 : frame_len == 64 ? 6 : 7;
   // ring depths as launch_attention_padded picked them by measurement: three stages at 64-element rows, two at 128
-  if (d <= 32) return launch_fc<64, 3, 32, 32>(q, k, v, o, ldo, batch, heads, n, flog, d, stream);
-  if (d <= 64) return launch_fc<64, 3, 64, 64>(q, k, v, o, ldo, batch, heads, n, flog, d, stream);
-  if (d <= 80) return launch_fc<128, 2, 80, 96>(q, k, v, o, ldo, batch, heads, n, flog, d, stream);
-  if (d <= 96) return launch_fc<128, 2, 96, 96>(q, k, v, o, ldo, batch, heads, n, flog, d, stream);
-  return launch_fc<128, 2, 128, 128>(q, k, v, o, ldo, batch, heads, n, flog, d, stream);
+  if (d <= 32) return launch_fc<64, 3, 32, 32>(q, k, v, o, ldo, batch, heads, n, flog, d, stream, lse);
+  if (d <= 64) return launch_fc<64, 3, 64, 64>(q, k, v, o, ldo, batch, heads, n, flog, d, stream, lse);
+  if (d <= 80) return launch_fc<128, 2, 80, 96>(q, k, v, o, ldo, batch, heads, n, flog, d, stream, lse);
+  if (d <= 96) return launch_fc<128, 2, 96, 96>(q, k, v, o, ldo, batch, heads, n, flog, d, stream, lse);
+  return launch_fc<128, 2, 128, 128>(q, k, v, o, ldo, batch, heads, n, flog, d, stream, lse);
 }
 
 }  // namespace dfot
@@ -275,4 +286,12 @@ extern "C" int dfot_op_attention_frame_causal(const void* q, const void* k, cons
   using dfot::bf16;
   return dfot::launch_attention_frame_causal((const bf16*)q, (const bf16*)k, (const bf16*)v, (bf16*)o, ldo, batch, heads, n, frame_len, d,
                                              (hipStream_t)stream);
+}
+
+extern "C" int dfot_op_attention_frame_causal_lse(const void* q, const void* k, const void* v, void* o, int ldo, float* lse, int batch,
+                                                  int heads, int n, int frame_len, int d, void* stream) {
+  using dfot::bf16;
+  DFOT_REQUIRE(lse, DFOT_ERR_ARG, "attention_frame_causal_lse: null lse pointer");
+  return dfot::launch_attention_frame_causal((const bf16*)q, (const bf16*)k, (const bf16*)v, (bf16*)o, ldo, batch, heads, n, frame_len, d,
+                                             (hipStream_t)stream, lse);
 }

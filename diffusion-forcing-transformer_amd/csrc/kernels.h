@@ -143,8 +143,9 @@ int launch_attention_padded(const bf16* q, const bf16* k, const bf16* v, bf16* o
 int launch_attention_seq64(const bf16* q, const bf16* k, const bf16* v, bf16* o, long ldo, int nseq, int heads, int d, hipStream_t stream);
 // attention_frame_causal.hip: launch_attention_padded's operands and output under the block-lower-triangular mask of the DiT1D backbone:
 // query i sees key j iff j / frame_len <= i / frame_len.  frame_len in {16, 32, 64, 128}, n % 128 == 0, d % 8 == 0, d <= 128, ldo % 8 == 0
+// lse (optional, training): [B][heads][N] fp32, log2-domain log-sum-exp of every query row; null launches the inference instantiation
 int launch_attention_frame_causal(const bf16* q, const bf16* k, const bf16* v, bf16* o, long ldo, int batch, int heads, int n, int frame_len,
-                                  int d, hipStream_t stream);
+                                  int d, hipStream_t stream, float* lse = nullptr);
 // attention_temporal.hip: q, k, v [batch*tokens][heads][patches][dstride]; every (video, head, patch position) attends over its `tokens`
 // frames (1 .. 32); o [(video, frame, patch)][ldo] compact.  patches % 64 == 0, d % 4 == 0
 int launch_attention_temporal(const bf16* q, const bf16* k, const bf16* v, bf16* o, long ldo, int batch, int tokens, int patches, int heads,
@@ -196,5 +197,11 @@ int launch_attention_bwd_delta(const bf16* o, const bf16* d_o, long ldo, float* 
 // q (pre-scaled as in the forward) / k / v / dq / dk / dv: [B][heads][N][dstride]; d_o compact; dq is the gradient of the UNSCALED q
 int launch_attention_bwd(const bf16* q, const bf16* k, const bf16* v, const bf16* d_o, long ldo, const float* l2, const float* delta,
                          bf16* dq, bf16* dk, bf16* dv, int batch, int heads, int n, int d, hipStream_t s);
+// the backward of launch_attention_frame_causal under launch_attention_bwd's contract (l2 = that forward's lse, delta from
+// launch_attention_bwd_delta, dq the gradient of the UNSCALED q, dk carrying ln 2): the frame-causal instantiations of the same kernels,
+// which stream only the tiles on and below the block diagonal.  The forward's shape rules
+int launch_attention_frame_causal_bwd(const bf16* q, const bf16* k, const bf16* v, const bf16* d_o, long ldo, const float* l2,
+                                      const float* delta, bf16* dq, bf16* dk, bf16* dv, int batch, int heads, int n, int frame_len, int d,
+                                      hipStream_t s);
 
 }  // namespace dfot

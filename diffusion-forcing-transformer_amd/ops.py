@@ -12,6 +12,7 @@ FakeTensor tracing, ``torch.compile`` graphs and stream capture treat the HIP ke
     dfot::dit3d_forward_f(x, noise_levels (float), external_cond?, external_cond_mask?, model) -> v [dfot_dit_forward_f]
     dfot::dit3d_forward_f_train(x, noise_levels (float), external_cond?, mask?, params[], model) -> v  [autograd: dfot_dit_train_forward_f]
     dfot::dit1d_forward(x, noise_levels, model) -> v                                                [dfot_dit1d_forward]
+    dfot::frame_causal_attention(q, k, v, frame_len) -> o                    [autograd: dfot_op_attention_frame_causal_lse / _bwd]
     dfot::ray_encoding(raw_poses, resolution) -> cond                                               [dfot_ray_encode]
     dfot::hg_prepare(x, noise?, qa, qb, nfe) -> x_in                                                [dfot_hg_prepare]
     dfot::ddim_hg_step(x, x_in, v, sa, s1, an, cn, keep, weight, gen, nfe) -> x_next                [dfot_ddim_compose / _tokw]
@@ -244,6 +245,110 @@ def dit1d_forward(x: Tensor, noise_levels: Tensor, model: int) -> Tensor:
 @dit1d_forward.register_fake
 def _(x, noise_levels, model):
     return torch.empty_like(x)
+
+
+# ---- frame-causal attention as a differentiable operator: the drop-in for the reference DiT1D's
+# F.scaled_dot_product_attention(q, k, v, attn_mask=<block lower triangular>) (dit1d/dit_model.py:57-88) ---------------------------------
+# q, k, v (B, heads, N, d) of one floating dtype on the GPU; o = softmax(q k^T / sqrt(d) + mask) v with mask[i, j] = -inf iff
+# j // frame_len > i // frame_len, in q's shape and dtype.  The result is a transposed view of the kernel's compact (B, N, heads, d)
+# buffer, so the reference's `x.transpose(1, 2).reshape(B, N, C)` is a view.  Host plumbing in torch: q, k, v are packed into the kernels'
+# [B][heads][N][dstride] bf16 layout (pad columns zero, q times log2(e)/sqrt(d) BEFORE the bf16 rounding, as the engines' QKV epilogue
+# does); the gradients come back in the inputs' dtype, first d columns.
+_FC_FRAME_LENS = (16, 32, 64, 128)
+_LOG2E = 1.4426950408889634
+
+
+def _fc_check(q: Tensor, k: Tensor, v: Tensor, frame_len: int, need_gpu: bool = True):
+    if q.dim() != 4 or k.shape != q.shape or v.shape != q.shape:
+        raise ValueError(f"frame_causal_attention: q, k, v must share one (B, heads, N, d) shape, got {tuple(q.shape)}, {tuple(k.shape)}, "
+                         f"{tuple(v.shape)}")
+    if not q.is_floating_point() or k.dtype != q.dtype or v.dtype != q.dtype:
+        raise ValueError(f"frame_causal_attention: q, k, v must share one floating dtype, got {q.dtype}, {k.dtype}, {v.dtype}")
+    b, heads, n, d = q.shape
+    if frame_len not in _FC_FRAME_LENS:
+        raise ValueError(f"frame_causal_attention: frame_len {frame_len} not in {_FC_FRAME_LENS}")
+    if n <= 0 or n % 128 != 0:
+        raise ValueError(f"frame_causal_attention: N={n} must be a positive multiple of 128")
+    if d <= 0 or d % 8 != 0 or d > 128:
+        raise ValueError(f"frame_causal_attention: head dim {d} must be a multiple of 8, <= 128")
+    if b <= 0 or heads <= 0:
+        raise ValueError(f"frame_causal_attention: batch {b} and heads {heads} must be positive")
+    if need_gpu and not (q.is_cuda and k.is_cuda and v.is_cuda):
+        raise ValueError(f"frame_causal_attention: q, k, v are on {q.device}, {k.device}, {v.device}: GPU tensors only (there is no CPU path)")
+    return b, heads, n, d
+
+
+def _fc_pack(t: Tensor, d: int, mul: float = 1.0) -> Tensor:
+    """(B, heads, N, d) of any strides -> contiguous [B][heads][N][dstride] bf16, pad columns zero; the product with `mul` is taken in fp32"""
+    ds = 64 if d <= 64 else 128
+    src = t.detach().float() * mul if mul != 1.0 else t.detach()
+    if ds == d:
+        return src.to(torch.bfloat16).contiguous()
+    out = torch.zeros(*t.shape[:3], ds, dtype=torch.bfloat16, device=t.device)
+    out[..., :d] = src
+    return out
+
+
+# what the last forward left for its backward: (packed q, k, v, compact o, lse).  register_autograd's setup_context sees the operator's
+# inputs and output only; it runs right after the forward it describes (same thread), takes the entry and clears it
+_FC_SAVED = None
+
+
+@custom_op("dfot::frame_causal_attention", mutates_args=())
+def frame_causal_attention(q: Tensor, k: Tensor, v: Tensor, frame_len: int) -> Tensor:
+    global _FC_SAVED
+    b, heads, n, d = _fc_check(q, k, v, frame_len)
+    qp, kp, vp = _fc_pack(q, d, _LOG2E / d ** 0.5), _fc_pack(k, d), _fc_pack(v, d)
+    o = torch.empty(b * n, heads * d, dtype=torch.bfloat16, device=q.device)
+    lse = torch.empty(b, heads, n, dtype=torch.float32, device=q.device)
+    capi.check(capi.lib.dfot_op_attention_frame_causal_lse(capi.ptr(qp), capi.ptr(kp), capi.ptr(vp), capi.ptr(o), heads * d, capi.ptr(lse),
+                                                           b, heads, n, frame_len, d, capi.stream_ptr()))
+    out = o.view(b, n, heads, d).transpose(1, 2)
+    out = out if q.dtype == torch.bfloat16 else out.to(q.dtype)  # .to keeps the strides: still compact as (B, N, heads, d)
+    _FC_SAVED = (out.data_ptr(), qp, kp, vp, o, lse)
+    return out
+
+
+@frame_causal_attention.register_fake
+def _(q, k, v, frame_len):
+    b, heads, n, d = _fc_check(q, k, v, frame_len, need_gpu=False)
+    return q.new_empty((b, n, heads, d)).transpose(1, 2)
+
+
+@custom_op("dfot::frame_causal_attention_backward", mutates_args=())
+def frame_causal_attention_backward(grad_out: Tensor, qp: Tensor, kp: Tensor, vp: Tensor, o: Tensor, lse: Tensor, frame_len: int,
+                                    d: int) -> List[Tensor]:
+    b, heads, n, _ = qp.shape
+    d_o = grad_out.detach().transpose(1, 2).to(torch.bfloat16).contiguous().view(b * n, heads * d)
+    delta = torch.empty_like(lse)
+    dq, dk, dv = (torch.empty_like(qp) for _ in range(3))
+    capi.check(capi.lib.dfot_op_attention_frame_causal_bwd(capi.ptr(qp), capi.ptr(kp), capi.ptr(vp), capi.ptr(o), capi.ptr(d_o), heads * d,
+                                                           capi.ptr(lse), capi.ptr(delta), capi.ptr(dq), capi.ptr(dk), capi.ptr(dv), b, heads, n,
+                                                           frame_len, d, capi.stream_ptr()))
+    return [t[..., :d].to(grad_out.dtype) for t in (dq, dk, dv)]
+
+
+@frame_causal_attention_backward.register_fake
+def _(grad_out, qp, kp, vp, o, lse, frame_len, d):
+    return [grad_out.new_empty((*qp.shape[:3], d)) for _ in range(3)]
+
+
+def _fc_setup_context(ctx, inputs, output):
+    global _FC_SAVED
+    saved, _FC_SAVED = _FC_SAVED, None
+    if saved is None or saved[0] != output.data_ptr():
+        raise RuntimeError("dfot::frame_causal_attention: the forward left no saved operands for this output (the operator is not "
+                           "differentiable under FakeTensor tracing)")
+    ctx.save_for_backward(*saved[1:])
+    ctx.frame_len, ctx.d = inputs[3], inputs[0].shape[3]
+
+
+def _fc_backward(ctx, grad_out):
+    dq, dk, dv = torch.ops.dfot.frame_causal_attention_backward(grad_out, *ctx.saved_tensors, ctx.frame_len, ctx.d)
+    return dq, dk, dv, None
+
+
+frame_causal_attention.register_autograd(_fc_backward, setup_context=_fc_setup_context)
 
 
 @custom_op("dfot::ray_encoding", mutates_args=())

@@ -849,6 +849,25 @@ int dfot_op_dcae_act_bf16(const float* x, void* out, int64_t n, int act, void* s
  * DFOT_ERR_ARG) before any device work. */
 int dfot_op_attention_frame_causal(const void* q, const void* k, const void* v, void* o, int ldo, int batch, int heads, int n, int frame_len,
                                    int d, void* stream);
+/* The same forward for training: the same kernel body compiled with the log-sum-exp store, so o has the bits of
+ * dfot_op_attention_frame_causal, and lse[(b*heads + head)*n + row] (fp32, must not be null: DFOT_ERR_ARG) receives the log2-domain
+ * log-sum-exp m + log2(sum_j 2^(s_j - m)) of the row's visible scores.  Shape rules and refusals as above. */
+int dfot_op_attention_frame_causal_lse(const void* q, const void* k, const void* v, void* o, int ldo, float* lse, int batch, int heads, int n,
+                                       int frame_len, int d, void* stream);
+/* Backward of the frame-causal attention under the contract of dfot_op_attention_bwd_lse: q, k, v as the forward read them, o / d_o compact
+ * [(b*n + row)][ldo] (head hd at column hd*d; nothing beyond a head's d columns is read), lse from dfot_op_attention_frame_causal_lse,
+ * delta [B][heads][n] fp32 scratch that receives sum_c d_o * o (computed here, then consumed), dq / dk / dv [B][heads][n][dstride] bf16
+ * with the pad columns written as zero.  dq is the gradient of the UNSCALED q (it carries 1/sqrt(d)), dk carries the ln 2 that undoes
+ * q's log2(e).  A workgroup owns 128 query rows (dq) or 128 key rows (dk/dv) and streams only the 64-row tiles on and below the block
+ * diagonal; on the tiles that straddle it a masked score is selected to -inf before exp2 and its dS to 0 (a select on registers), so
+ * large finite data in masked rows never reaches a sum.  No atomics, no split of a row across workgroups, no allocation after the first
+ * call, no host synchronisation; the summation order depends on (n, frame_len, d) and the tile alone: a video gives the same bits alone
+ * and in a batch, dq of frames <= f does not depend on frames > f, dk / dv of frames >= f do not depend on q / d_o of frames < f.
+ * Shape rules of the forward (ldo is d_o's and o's row stride); null pointers: DFOT_ERR_ARG, shapes: DFOT_ERR_SHAPE, both before any
+ * device work. */
+int dfot_op_attention_frame_causal_bwd(const void* q, const void* k, const void* v, const void* o, const void* d_o, int ldo, const float* lse,
+                                       float* delta, void* dq, void* dk, void* dv, int batch, int heads, int n, int frame_len, int d,
+                                       void* stream);
 
 typedef struct dfot_dit1d_s* dfot_dit1d_t;
 typedef struct {

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Micro-benchmarks of the C-ABI primitives at the RE10K model shapes (model batch 2), HIP-event timed.
-Usage (GPU box): python tools/bench_ops.py [gemm] [conv] [attn] [tattn] [mattn] [tattn_bwd] [facdit_train] [mattn_bwd] [facmat_train] [vae_encode] [equal] [dit_front] [ivae] [uvit3d] [gnfilm_frame] [uvit3d_train] [attnmap] [titok] [titok_enc] [mcraft] [sattn64] [facmat_narrow] [dcae] [attn_fc] [dit1d]"""
+Usage (GPU box): python tools/bench_ops.py [gemm] [conv] [attn] [tattn] [mattn] [tattn_bwd] [facdit_train] [mattn_bwd] [facmat_train] [vae_encode] [equal] [dit_front] [ivae] [uvit3d] [gnfilm_frame] [uvit3d_train] [attnmap] [titok] [titok_enc] [mcraft] [sattn64] [facmat_narrow] [dcae] [attn_fc] [attn_fc_bwd] [dit1d]"""
 import ctypes as C
 import math
 import os
@@ -231,6 +231,31 @@ def attn_fc(b, heads, n, frame_len, d, rounds=7):
         pad.append(timeit(lambda: capi.check(capi.lib.dfot_op_attention_padded(P(q), P(k), P(v), P(o), heads * d, b, heads, n, d, S())),
                           iters=100, warm=10))
     return fc, pad
+
+
+def attn_fc_bwd(b, heads, n, frame_len, d, rounds=7):
+    """the frame-causal backward (dfot_op_attention_frame_causal_bwd: delta + dQ + dK/dV kernels) next to the non-causal
+    dfot_op_attention_bwd_lse on the same q, k, v, d_o, each with the o and lse of its own forward, alternated over `rounds` rounds in
+    one process: ([ms frame-causal], [ms non-causal]) per round.  The frame-causal kernels stream a subset of the non-causal tile products"""
+    ds = 64 if d <= 64 else 128
+    q, k, v = (torch.zeros(b, heads, n, ds, device="cuda", dtype=torch.bfloat16) for _ in range(3))
+    for t, mul in ((q, math.log2(math.e) / math.sqrt(d)), (k, 1.0), (v, 1.0)):
+        t[..., :d] = (torch.randn(b, heads, n, d, device="cuda") * mul).bfloat16()
+    d_o = torch.randn(b * n, heads * d, device="cuda").bfloat16()
+    o_fc, o_nc = (torch.empty(b * n, heads * d, device="cuda", dtype=torch.bfloat16) for _ in range(2))
+    lse_fc, lse_nc, delta = (torch.empty(b, heads, n, device="cuda", dtype=torch.float32) for _ in range(3))
+    dq, dk, dv = (torch.empty_like(q) for _ in range(3))
+    capi.check(capi.lib.dfot_op_attention_frame_causal_lse(P(q), P(k), P(v), P(o_fc), heads * d, P(lse_fc), b, heads, n, frame_len, d, S()))
+    capi.check(capi.lib.dfot_op_attention_fwd_lse(P(q), P(k), P(v), P(o_nc), heads * d, P(lse_nc), b, heads, n, d, S()))
+    fc, nc = [], []
+    for _ in range(rounds):
+        fc.append(timeit(lambda: capi.check(capi.lib.dfot_op_attention_frame_causal_bwd(P(q), P(k), P(v), P(o_fc), P(d_o), heads * d, P(lse_fc), P(delta),
+                                                                                        P(dq), P(dk), P(dv), b, heads, n, frame_len, d, S())),
+                         iters=50, warm=5))
+        nc.append(timeit(lambda: capi.check(capi.lib.dfot_op_attention_bwd_lse(P(q), P(k), P(v), P(o_nc), P(d_o), heads * d, P(lse_nc), P(delta), P(dq),
+                                                                               P(dk), P(dv), b, heads, n, d, S())),
+                         iters=50, warm=5))
+    return fc, nc
 
 
 def dit1d_forward(b, rounds=5):
@@ -825,6 +850,17 @@ def main():
             print(f"attn_fc B=16 H=16 N={n} L=32 d=72: frame-causal median {med(fc)*1e3:8.1f} us (min {min(fc)*1e3:.1f}, max {max(fc)*1e3:.1f})  "
                   f"padded {med(pad)*1e3:8.1f} us (min {min(pad)*1e3:.1f}, max {max(pad)*1e3:.1f})  frame-causal / padded {med(fc) / med(pad):.2f}  "
                   f"({tiles * (tiles + 1) // 2} of {tiles * tiles} (query tile, 128-key block) pairs visited; {len(fc)} alternated rounds)", flush=True)
+    if "attn_fc_bwd" in what:
+        med = lambda r: sorted(r)[len(r) // 2]  # noqa: E731
+        # the backward at the attn_fc shapes; the condition of DESIGN.md section 4e: the frame-causal median is not above the non-causal
+        # median by more than the non-causal min-to-max spread of the same run
+        for n in (512, 1024):
+            fc, nc = attn_fc_bwd(16, 16, n, 32, 72)
+            tiles = n // 64
+            print(f"attn_fc_bwd B=16 H=16 N={n} L=32 d=72: frame-causal median {med(fc)*1e3:8.1f} us (min {min(fc)*1e3:.1f}, max {max(fc)*1e3:.1f})  "
+                  f"non-causal {med(nc)*1e3:8.1f} us (min {min(nc)*1e3:.1f}, max {max(nc)*1e3:.1f})  frame-causal / non-causal "
+                  f"{med(fc) / med(nc):.2f}  ({tiles * (tiles + 2) // 4} of {tiles * tiles // 2} (128-row block, 64-row tile) pairs streamed per "
+                  f"kernel; {len(fc)} alternated rounds)", flush=True)
     if "dit1d" in what:
         ms = dit1d_forward(16)
         for name, r in ms.items():
