@@ -265,6 +265,20 @@ SIGNATURES = {
     "dfot_op_equal_bits": (_I, [_P, _P, _L, _P, _P]),
     "dfot_op_dit_final_layer": (_I, [_P, _P, _P, _L, _L, _P, _P, _P, _I, _I, _I, _F] + [_I] * 6 + [_P]),
     "dfot_op_dit_final_layer_chunked": (_I, [_P, _P, _P, _L, _L, _P, _P, _P, _I, _I, _I, _F] + [_I] * 6 + [_P]),
+    "dfot_op_dit_ln_mod": (_I, [_P] * 5 + [_L, _L, _I, _I, _I, _F, _I, _P]),
+    "dfot_op_dit_gate_combine": (_I, [_P] * 4 + [_L, _L, _I, _I, _I, _P]),
+    "dfot_op_dit_gate_bwd": (_I, [_P] * 3 + [_L, _L] + [_P] * 5 + [_I, _I, _I, _P]),
+    "dfot_op_dit_ln_bwd": (_I, [_P] * 3 + [_L, _L] + [_P] * 4 + [_I, _I, _I, _F, _P]),
+    "dfot_op_dit_ln_bwd_rows": (_I, [_P] * 3 + [_L, _L, _P, _P, _I, _I, _I, _F, _P]),
+    "dfot_op_dit_gelu": (_I, [_P, _P, _P, _L, _P]),
+    "dfot_op_dit_patch_embed": (_I, [_P] * 5 + [_I] * 5 + [_L, _P]),
+    "dfot_op_dit_patch_embed_dgrad": (_I, [_P] * 3 + [_I] * 5 + [_L, _P]),
+    "dfot_op_dit_patch_embed_wgrad": (_I, [_P] * 4 + [_I] * 5 + [_L, _P]),
+    "dfot_op_dit_final_gather": (_I, [_P, _P, _P, _L] + [_I] * 5 + [_P]),
+    "dfot_op_dit_qkv_grad_pack": (_I, [_P] * 5 + [_L, _I, _I, _I, _I, _P]),
+    "dfot_op_dit1d_tok_embed": (_I, [_P] * 5 + [_I] * 4 + [_L, _P]),
+    "dfot_op_dit1d_ln_share": (_I, [_P] * 5 + [_L, _L, _I, _I, _I, _F, _I, _P]),
+    "dfot_op_dit1d_final": (_I, [_P] * 4 + [_I] * 4 + [_F, _P]),
     "dfot_op_attention_frame_causal": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "dfot_op_attention_frame_causal_lse": (_I, [_P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _P]),
     "dfot_op_attention_frame_causal_bwd": (_I, [_P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),

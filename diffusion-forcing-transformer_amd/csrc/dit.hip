@@ -662,6 +662,15 @@ int launch_ln_mod(const float* xin, float* x, bf16* obf, const float* table, con
   return DFOT_OK;
 }
 
+// the patch embedding of both engines (inference forward, training forward): 8 token rows per workgroup
+int launch_patch_embed(const float* x, const float* w, const float* b, const float* pos, float* out, int c, int hh, int ww, int ps, int hidden,
+                       long rows, hipStream_t s) {
+  hipLaunchKernelGGL(patch_embed_kernel, dim3(cdiv(rows, PE_TOK)), dim3(256), PE_TOK * c * ps * ps * sizeof(float), s, x, w, b, pos, out, c, hh, ww,
+                     ps, hidden, rows);
+  DFOT_CHECK_HIP(hipGetLastError());
+  return DFOT_OK;
+}
+
 int launch_final_layer(const float* x, const float* table, const int* levels, long ldt, long off, const float* w, const float* b,
                        float* out, int hidden, int rows_per_frame, int rows, float eps, int max_level, int c, int hh, int ww, int ps,
                        hipStream_t s, int form = 0, int chunk = 0) {
@@ -1239,9 +1248,7 @@ static int dit_forward_impl(dfot_dit_t h, const float* x, const int32_t* noise_l
     max_level = 2 * h->lpad - 1;
   }
   if (h->front_only) return DFOT_OK;
-  hipLaunchKernelGGL(patch_embed_kernel, dim3(cdiv(rows, PE_TOK)), dim3(256), PE_TOK * h->kpatch * sizeof(float), s, x, h->pe_w,
-                     h->pe_b, h->pos2d, h->X, c.in_channels, c.height, c.width, c.patch_size, hd, rows);
-  DFOT_CHECK_HIP(hipGetLastError());
+  if ((rc = launch_patch_embed(x, h->pe_w, h->pe_b, h->pos2d, h->X, c.in_channels, c.height, c.width, c.patch_size, hd, rows, s))) return rc;
   const float qscale = 1.4426950408889634f / sqrtf((float)h->d);  // attention works in the exp2 domain
   auto ln_mod = [&](long off) -> int {
     return launch_ln_mod(h->X, h->X, h->A, table, lvl, h->ldt, off, hd, P, (int)rows, c.eps, max_level, s);
@@ -1564,6 +1571,35 @@ int dfot_op_dit_final_layer_chunked(const float* x, const float* table, const in
                                     int width, int patch, int chunk, void* stream) {
   DFOT_REQUIRE(chunk > 0, DFOT_ERR_ARG, "final layer: chunk of %d output rows", chunk);
   return op_final_layer(x, table, levels, ldt, off, w, b, out, hidden, rows_per_frame, rows, eps, max_level, c, h, width, patch, 2, chunk, stream);
+}
+
+// ---- single launches of the DiT blocks (test entries: each runs the launcher the engines call, on caller-provided buffers) ----
+int dfot_op_dit_ln_mod(const float* xin, float* xout, void* obf, const float* table, const int32_t* levels, int64_t ldt, int64_t off, int hidden,
+                       int rows_per_frame, int rows, float eps, int max_level, void* stream) {
+  DFOT_REQUIRE(xin && xout && obf && table && levels, DFOT_ERR_ARG, "ln_mod: null argument");
+  DFOT_REQUIRE(hidden > 0 && rows > 0 && rows_per_frame > 0 && rows % rows_per_frame == 0, DFOT_ERR_SHAPE, "ln_mod: %d rows of %d per frame, hidden %d",
+               rows, rows_per_frame, hidden);
+  DFOT_REQUIRE(max_level >= 0 && off >= 0 && off % 4 == 0 && ldt % 4 == 0 && ldt >= off + 2L * hidden, DFOT_ERR_ARG,
+               "ln_mod: table row of %ld with (shift | scale) at %ld (multiples of 4), max_level %d", (long)ldt, (long)off, max_level);
+  return launch_ln_mod(xin, xout, (bf16*)obf, table, levels, ldt, off, hidden, rows_per_frame, rows, eps, max_level, (hipStream_t)stream);
+}
+
+// c, h, width, patch of a patch embedding and its row count: the checks of the three patch-embedding entries and of the final gather
+static int op_patch_geometry(const char* what, int c, int hh, int ww, int patch, int hidden, int64_t rows) {
+  DFOT_REQUIRE(c > 0 && patch > 0 && hh > 0 && ww > 0 && hh % patch == 0 && ww % patch == 0 && hidden > 0, DFOT_ERR_SHAPE,
+               "%s: %d channels, %d x %d frames in patches of %d, hidden %d", what, c, hh, ww, patch, hidden);
+  DFOT_REQUIRE((long)c * patch * patch <= 256, DFOT_ERR_SHAPE, "%s: patch vector too long (patch_size^2 * channels = %ld, at most 256)", what,
+               (long)c * patch * patch);
+  DFOT_REQUIRE(rows > 0 && rows % ((hh / patch) * (ww / patch)) == 0 && rows * (long)hidden < (1L << 31) && rows * 256 < (1L << 31), DFOT_ERR_SHAPE,
+               "%s: %ld rows are no whole number of %d-patch frames (or too many)", what, (long)rows, (hh / patch) * (ww / patch));
+  return DFOT_OK;
+}
+
+int dfot_op_dit_patch_embed(const float* x, const float* w, const float* b, const float* pos, float* out, int c, int h, int width, int patch,
+                            int hidden, int64_t rows, void* stream) {
+  DFOT_REQUIRE(x && w && b && out, DFOT_ERR_ARG, "patch_embed: null argument");
+  if (int rc = op_patch_geometry("patch_embed", c, h, width, patch, hidden, rows)) return rc;
+  return launch_patch_embed(x, w, b, pos, out, c, h, width, patch, hidden, (long)rows, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -147,6 +147,32 @@ __global__ __launch_bounds__(256) void d1_final_kernel(const float* __restrict__
   }
 }
 
+// ---- the launches of the kernels above: each exists once, for the engine's forward and for the dfot_op_dit1d_* entries ----
+int launch_d1_clamp_levels(const int* levels, int* idx, int frames, int max_level, hipStream_t s) {
+  hipLaunchKernelGGL(d1_clamp_levels_kernel, dim3(cdiv(frames, 256)), dim3(256), 0, s, levels, idx, frames, max_level);
+  DFOT_CHECK_HIP(hipGetLastError());
+  return DFOT_OK;
+}
+// x [frames][C][L] -> X [rows][hidden], rows = videos * n tokens, n a whole number of L-token frames; pos [n][hidden]
+int launch_d1_tok_embed(const float* x, const float* w, const float* b, const float* pos, float* X, int C, int L, int n, int hidden, long rows,
+                        hipStream_t s) {
+  const long total4 = rows * (hidden / 4);
+  hipLaunchKernelGGL(d1_tok_embed_kernel, dim3(cdiv(total4, 256)), dim3(256), 0, s, x, w, b, pos, X, C, L, n, hidden, total4);
+  DFOT_CHECK_HIP(hipGetLastError());
+  return DFOT_OK;
+}
+int launch_d1_ln_share(float* X, bf16* A, const float* table, const int* idx, long ldt, long off, int hidden, int rows_per_frame, int rows, float eps,
+                       hipStream_t s) {
+  hipLaunchKernelGGL(d1_ln_share_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, s, X, A, table, idx, ldt, off, hidden, rows_per_frame, rows, eps);
+  DFOT_CHECK_HIP(hipGetLastError());
+  return DFOT_OK;
+}
+int launch_d1_final(const float* X, const float* w, const float* b, float* out, int hidden, int C, int L, int rows, float eps, hipStream_t s) {
+  hipLaunchKernelGGL(d1_final_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, s, X, w, b, out, hidden, C, L, rows, eps);
+  DFOT_CHECK_HIP(hipGetLastError());
+  return DFOT_OK;
+}
+
 }  // namespace
 }  // namespace dfot
 
@@ -333,20 +359,11 @@ int dfot_dit1d_forward(dfot_dit1d_t h, const float* x, const int32_t* noise_leve
   const int hd = c.hidden, L = c.tokens_per_frame, n = h->ntok, frames = batch * tokens;
   const long rows = (long)batch * n;
   int rc = 0;
-  hipLaunchKernelGGL(d1_clamp_levels_kernel, dim3(cdiv(frames, 256)), dim3(256), 0, s, noise_levels, h->idx, frames, c.timesteps - 1);
-  DFOT_CHECK_HIP(hipGetLastError());
-  {
-    const long total4 = rows * (hd / 4);
-    hipLaunchKernelGGL(d1_tok_embed_kernel, dim3(cdiv(total4, 256)), dim3(256), 0, s, x, h->x_w, h->x_b, h->pos, h->X, c.in_channels, L, n, hd,
-                       total4);
-    DFOT_CHECK_HIP(hipGetLastError());
-  }
+  if ((rc = launch_d1_clamp_levels(noise_levels, h->idx, frames, c.timesteps - 1, s))) return rc;
+  if ((rc = launch_d1_tok_embed(x, h->x_w, h->x_b, h->pos, h->X, c.in_channels, L, n, hd, rows, s))) return rc;
   const float qscale = 1.4426950408889634f / sqrtf((float)h->d);  // attention works in the exp2 domain
   auto ln_share = [&](long off) -> int {
-    hipLaunchKernelGGL(d1_ln_share_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, s, h->X, h->A, h->mod_table, h->idx, h->ldt, off, hd, L, (int)rows,
-                       c.eps);
-    DFOT_CHECK_HIP(hipGetLastError());
-    return DFOT_OK;
+    return launch_d1_ln_share(h->X, h->A, h->mod_table, h->idx, h->ldt, off, hd, L, (int)rows, c.eps, s);
   };
   auto gated = [&](const bf16* a, int kdim, const bf16* w, const float* bias, long gate_off) -> int {
     GemmArgs g;  // X <- X + gate * (a W^T + bias), in place onto the normalised row
@@ -379,9 +396,43 @@ int dfot_dit1d_forward(dfot_dit1d_t h, const float* x, const int32_t* noise_leve
     }
     if ((rc = gated(h->hid, c.mlp_hidden, w.w_fc2, w.b_fc2, w.mod + 5 * hd))) return rc;
   }
-  hipLaunchKernelGGL(d1_final_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, s, h->X, h->fin_w, h->fin_b, out, hd, c.in_channels, L, (int)rows, c.eps);
-  DFOT_CHECK_HIP(hipGetLastError());
+  return launch_d1_final(h->X, h->fin_w, h->fin_b, out, hd, c.in_channels, L, (int)rows, c.eps, s);
+}
+
+// ---- single launches of the forward (test entries: the engine's own launchers on caller-provided buffers) ----
+static int op_d1_hidden(const char* what, int hidden) {
+  DFOT_REQUIRE(hidden > 0 && hidden % 64 == 0 && hidden <= 2048, DFOT_ERR_SHAPE, "%s: hidden %d must be a multiple of 64, <= 2048", what, hidden);
   return DFOT_OK;
+}
+
+int dfot_op_dit1d_tok_embed(const float* x, const float* w, const float* b, const float* pos, float* X, int C, int L, int n, int hidden, int64_t rows,
+                            void* stream) {
+  DFOT_REQUIRE(x && w && b && pos && X, DFOT_ERR_ARG, "dit1d tok_embed: null argument");
+  if (int rc = op_d1_hidden("dit1d tok_embed", hidden)) return rc;
+  DFOT_REQUIRE(C > 0 && C <= 64, DFOT_ERR_SHAPE, "dit1d tok_embed: in_channels %d must be in [1, 64]", C);
+  DFOT_REQUIRE(L > 0 && n > 0 && n % L == 0 && rows > 0 && rows % n == 0 && rows * (long)hidden < (1L << 31), DFOT_ERR_SHAPE,
+               "dit1d tok_embed: %ld rows in sequences of %d tokens, %d per frame", (long)rows, n, L);
+  return launch_d1_tok_embed(x, w, b, pos, X, C, L, n, hidden, (long)rows, (hipStream_t)stream);
+}
+
+int dfot_op_dit1d_ln_share(float* X, void* A, const float* table, const int32_t* levels, int32_t* idx, int64_t ldt, int64_t off, int hidden,
+                           int rows_per_frame, int rows, float eps, int max_level, void* stream) {
+  DFOT_REQUIRE(X && A && table && levels && idx, DFOT_ERR_ARG, "dit1d ln_share: null argument");
+  if (int rc = op_d1_hidden("dit1d ln_share", hidden)) return rc;
+  DFOT_REQUIRE(rows > 0 && rows_per_frame > 0 && rows % rows_per_frame == 0, DFOT_ERR_SHAPE, "dit1d ln_share: %d rows of %d per frame", rows,
+               rows_per_frame);
+  DFOT_REQUIRE(max_level >= 0 && off >= 0 && off % 4 == 0 && ldt % 4 == 0 && ldt >= off + 2L * hidden, DFOT_ERR_ARG,
+               "dit1d ln_share: table row of %ld with (shift | scale) at %ld (multiples of 4), max_level %d", (long)ldt, (long)off, max_level);
+  hipStream_t s = (hipStream_t)stream;
+  if (int rc = launch_d1_clamp_levels(levels, idx, rows / rows_per_frame, max_level, s)) return rc;
+  return launch_d1_ln_share(X, (bf16*)A, table, idx, ldt, off, hidden, rows_per_frame, rows, eps, s);
+}
+
+int dfot_op_dit1d_final(const float* X, const float* w, const float* b, float* out, int hidden, int C, int L, int rows, float eps, void* stream) {
+  DFOT_REQUIRE(X && w && b && out, DFOT_ERR_ARG, "dit1d final: null argument");
+  if (int rc = op_d1_hidden("dit1d final", hidden)) return rc;
+  DFOT_REQUIRE(C > 0 && C <= 64 && L > 0 && rows > 0 && rows % L == 0, DFOT_ERR_SHAPE, "dit1d final: %d rows of %d per frame, %d channels", rows, L, C);
+  return launch_d1_final(X, w, b, out, hidden, C, L, rows, eps, (hipStream_t)stream);
 }
 
 }  // extern "C"

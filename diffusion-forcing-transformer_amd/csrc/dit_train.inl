@@ -531,6 +531,59 @@ static int launch_pe_wgrad(const float* dx0, const float* x, float* dW, float* d
   return det_sum(part + (long)hidden * kdim, rowlen, ny * nsub, hidden, db, true, s);
 }
 
+// ---- the launches of the kernels above: each grid, block and argument order exists once, for the trainer and for the dfot_op_dit_* entries ----
+int launch_gate_combine(const float* x, float* y, const bf16* a, const float* table, long ldt, long off, int hidden, int rows_per_frame, long rows,
+                        hipStream_t s) {
+  hipLaunchKernelGGL(gate_combine_kernel, dim3(cdiv(rows * hidden / 4, 256)), dim3(256), 0, s, x, y, a, table, ldt, off, hidden, rows_per_frame,
+                     rows * hidden / 4);
+  DFOT_CHECK_HIP(hipGetLastError());
+  return DFOT_OK;
+}
+// da = dy * gate, dgate partials into dmod_part's planes at column `off`, dbias = the sum of da's rows (through dbias_part)
+int launch_gate_bwd(const float* dy, const bf16* a, const float* table, long ldt, long off, bf16* da, float* dmod_part, float* dbias_part, float* dbias,
+                    int hidden, int rows_per_frame, int frames, hipStream_t s) {
+  hipLaunchKernelGGL(gate_bwd_kernel, dim3(frames, cdiv(hidden, 256), TR_CHUNKS), dim3(256), 0, s, dy, a, table, ldt, off, da, dmod_part, dbias_part,
+                     hidden, rows_per_frame);
+  DFOT_CHECK_HIP(hipGetLastError());
+  return det_sum(dbias_part, hidden, frames * TR_CHUNKS, hidden, dbias, false, s);
+}
+int launch_ln_bwd_frames(const float* dm, const float* x, const float* stats, float* dmod_part, long ldt, long off, int hidden, int rows_per_frame,
+                         int frames, hipStream_t s) {
+  hipLaunchKernelGGL(ln_bwd_frames_kernel, dim3(frames, cdiv(hidden, 256), TR_CHUNKS), dim3(256), 0, s, dm, x, stats, dmod_part, ldt, off, hidden,
+                     rows_per_frame);
+  DFOT_CHECK_HIP(hipGetLastError());
+  return DFOT_OK;
+}
+int launch_dmod_reduce(const float* dmod_part, float* dmod, long n, hipStream_t s) {
+  static_assert(TR_CHUNKS == 4, "dmod_reduce_kernel adds four planes");
+  hipLaunchKernelGGL(dmod_reduce_kernel, dim3(cdiv(n, 256)), dim3(256), 0, s, dmod_part, dmod, n);
+  DFOT_CHECK_HIP(hipGetLastError());
+  return DFOT_OK;
+}
+// h = GELU(u) (h may be null) ; dh_to_du *= GELU'(u) in place (may be null); n elements, a multiple of 8
+int launch_gelu(const bf16* u, bf16* h, bf16* dh_to_du, long n, hipStream_t s) {
+  hipLaunchKernelGGL(gelu_kernel, dim3(cdiv(n / 8, 256)), dim3(256), 0, s, u, h, dh_to_du, n / 8);
+  DFOT_CHECK_HIP(hipGetLastError());
+  return DFOT_OK;
+}
+int launch_final_gather(const float* dout, bf16* dyp, bf16* dyt, long rows, int c, int hh, int ww, int ps, int ocp, hipStream_t s) {
+  hipLaunchKernelGGL(final_gather_kernel, dim3(cdiv(rows * (ps * ps * c), 256)), dim3(256), 0, s, dout, dyp, dyt, rows, c, hh, ww, ps, ocp);
+  DFOT_CHECK_HIP(hipGetLastError());
+  return DFOT_OK;
+}
+int launch_qkv_grad_pack(const bf16* dq, const bf16* dk, const bf16* dv, const float* rope_cs, bf16* out, long rows, int ntok, int heads, int d,
+                         int dstride, hipStream_t s) {
+  hipLaunchKernelGGL(qkv_grad_pack_kernel, dim3(cdiv(rows * (3 * heads * d / 8), 256)), dim3(256), 0, s, dq, dk, dv, rope_cs, out, rows, ntok, heads, d,
+                     dstride);
+  DFOT_CHECK_HIP(hipGetLastError());
+  return DFOT_OK;
+}
+int launch_pe_dgrad(const float* dy, const float* w, float* dx, int c, int hh, int ww, int ps, int hidden, long rows, hipStream_t s) {
+  hipLaunchKernelGGL(pe_dgrad_kernel, dim3(cdiv(rows * (c * ps * ps), 256)), dim3(256), 0, s, dy, w, dx, c, hh, ww, ps, hidden, rows);
+  DFOT_CHECK_HIP(hipGetLastError());
+  return DFOT_OK;
+}
+
 // ---- MatrixDiTBlock (factorized matrix attention, variant 1) ------------------------------------------------------------
 // backward of matrix_attn_kernel: z [B*L*E][3h] (q|k|v), d_o [B*L*E][h] -> dz [B*L*E][3h].  The hn*hd entries of one (video, c, r)
 // head are split over MA_CHUNKS workgroups:
@@ -1298,18 +1351,15 @@ static int dit_train_forward_impl(dfot_dit_train_t h, const float* x, const int3
     if ((rc = launch_gemm(A_DENSE, E_F32, GEMM_AUTO, g, s))) return rc;
   }
   // the residual stream lives in the blocks' own x_in buffers (each is what the backward of that block needs): no copies
-  hipLaunchKernelGGL(patch_embed_kernel, dim3(cdiv(rows, PE_TOK)), dim3(256), PE_TOK * h->kpatch * sizeof(float), s, x, p + h->o_pe_w,
-                     p + h->o_pe_b, (const float*)h->pos2d, h->blocks[0].x_in, c.in_channels, c.height, c.width, c.patch_size, hd, rows);
-  DFOT_CHECK_HIP(hipGetLastError());
+  if ((rc = launch_patch_embed(x, p + h->o_pe_w, p + h->o_pe_b, h->pos2d, h->blocks[0].x_in, c.in_channels, c.height, c.width, c.patch_size, hd, rows,
+                               s)))
+    return rc;
   const float qscale = 1.4426950408889634f / sqrtf((float)h->d);
   // attention sequences: the whole video with RoPE-3D (variant 0) or one frame without RoPE (the spatial blocks of variants 1, 2, 3)
   const int seq = facmat || fac ? P : n, nseq = facmat || fac ? frames : batch;
   const int gfe = (c.variant == 3 ? (frames + 1) & ~1 : frames) * E;  // rows of the right-factor GEMMs (see reserve)
   auto combine = [&](const bf16* a, long gate_off, float* dst) -> int {
-    hipLaunchKernelGGL(gate_combine_kernel, dim3(cdiv(rows * hd / 4, 256)), dim3(256), 0, s, h->X, dst, a, h->mod_table, h->ldt, gate_off, hd, P,
-                       rows * hd / 4);
-    DFOT_CHECK_HIP(hipGetLastError());
-    return DFOT_OK;
+    return launch_gate_combine(h->X, dst, a, h->mod_table, h->ldt, gate_off, hd, P, rows, s);
   };
   for (size_t bi = 0; bi < h->blocks.size(); ++bi) {
     TrainBlock& b = h->blocks[bi];
@@ -1416,14 +1466,11 @@ int dfot_dit_train_backward(dfot_dit_train_t h, const float* d_out, void* stream
   if ((rc = zero_fill(G, (size_t)h->total * sizeof(float), s))) return rc;
   if ((rc = zero_fill(h->dmod, (size_t)fp * h->ldt * sizeof(float), s))) return rc;
   if ((rc = zero_fill(h->dmod_part, (size_t)TR_CHUNKS * frames * h->ldt * sizeof(float), s))) return rc;
-  const dim3 fgrid(frames, cdiv(hd, 256), TR_CHUNKS);
 
   // ---- final layer: out = Linear(mfin), mfin = LN(x_fin)(1 + scale) + shift ----
   if ((rc = zero_fill(h->dyp, (size_t)rows * h->ocp * sizeof(bf16), s)) || (rc = zero_fill(h->dyt, (size_t)256 * rows * sizeof(bf16), s))) return rc;
-  hipLaunchKernelGGL(final_gather_kernel, dim3(cdiv(rows * h->oc, 256)), dim3(256), 0, s, d_out, h->dyp, h->dyt, rows, c.in_channels, c.height,
-                     c.width, c.patch_size, h->ocp);
-  launch_colsum_bf16(h->dyp, G + h->o_fin_b, rows, h->oc, (long)h->ocp, s);
-  DFOT_CHECK_HIP(hipGetLastError());
+  if ((rc = launch_final_gather(d_out, h->dyp, h->dyt, rows, c.in_channels, c.height, c.width, c.patch_size, h->ocp, s))) return rc;
+  if ((rc = launch_colsum_bf16(h->dyp, G + h->o_fin_b, rows, h->oc, (long)h->ocp, s))) return rc;
   float *dY = h->dX, *dN = h->dX2;  // gradient of the current block's output / scratch for the next one
   if ((rc = launch_ln_mod(h->x_fin, dN, h->mfin, h->mod_table, h->idx, h->ldt, h->mod_final, hd, P, (int)rows, c.eps, frames - 1, s))) return rc;
   if ((rc = tr_transpose(h->mfin, h->T2, (int)rows, hd, s))) return rc;                                   // mfin^T [hd][rows]
@@ -1433,15 +1480,12 @@ int dfot_dit_train_backward(dfot_dit_train_t h, const float* d_out, void* stream
   auto ln_bwd = [&](const float* x_in, long off) -> int {  // dY holds dm; leaves dx in dY
     int r = launch_ln_bwd_rows(dY, x_in, h->mod_table, h->ldt, off, dN, h->stats, hd, P, (int)rows, c.eps, s);
     if (r) return r;
-    hipLaunchKernelGGL(ln_bwd_frames_kernel, fgrid, dim3(256), 0, s, dY, x_in, h->stats, h->dmod_part, h->ldt, off, hd, P);
-    DFOT_CHECK_HIP(hipGetLastError());
+    if ((r = launch_ln_bwd_frames(dY, x_in, h->stats, h->dmod_part, h->ldt, off, hd, P, frames, s))) return r;
     std::swap(dY, dN);
     return DFOT_OK;
   };
   auto gate_bwd = [&](const bf16* a, long gate_off, float* dbias) -> int {  // h->da = dY * gate, dgate into dmod, row sums of da into dbias
-    hipLaunchKernelGGL(gate_bwd_kernel, fgrid, dim3(256), 0, s, dY, a, h->mod_table, h->ldt, gate_off, h->da, h->dmod_part, h->dbias_part, hd, P);
-    DFOT_CHECK_HIP(hipGetLastError());
-    return det_sum(h->dbias_part, hd, frames * TR_CHUNKS, hd, dbias, false, s);
+    return launch_gate_bwd(dY, a, h->mod_table, h->ldt, gate_off, h->da, h->dmod_part, h->dbias_part, dbias, hd, P, frames, s);
   };
   auto frames_sum = [&](const bf16* src, float* dst, long per_frame) -> int {
     hipLaunchKernelGGL(frames_sum_bf16_kernel, dim3(cdiv(per_frame / 4, 256)), dim3(256), 0, s, src, dst, frames, per_frame);
@@ -1469,9 +1513,8 @@ int dfot_dit_train_backward(dfot_dit_train_t h, const float* d_out, void* stream
       if ((rc = gate_bwd(b.y, b.mod2 + 2 * hd, G + b.o_fc2_b))) return rc;
       if ((rc = tr_gemm_bf16(h->da, hd, b.w_fc2T, (int)rows, mh, hd, nullptr, h->dh, mh, s))) return rc;        // dh = dy W2
       if ((rc = wgrad(h->da, hd, b.hact, mh, rows, G + b.o_fc2_w))) return rc;                                   // dW2 = dy^T h
-      hipLaunchKernelGGL(gelu_kernel, dim3(cdiv(rows * mh / 8, 256)), dim3(256), 0, s, b.u, (bf16*)nullptr, h->dh, rows * mh / 8);  // du
-      launch_colsum_bf16(h->dh, G + b.o_fc1_b, rows, mh, (long)mh, s);
-      DFOT_CHECK_HIP(hipGetLastError());
+      if ((rc = launch_gelu(b.u, nullptr, h->dh, rows * mh, s))) return rc;  // du
+      if ((rc = launch_colsum_bf16(h->dh, G + b.o_fc1_b, rows, mh, (long)mh, s))) return rc;
       if ((rc = tr_gemm_f32(h->dh, mh, b.w_fc1T, (int)rows, hd, mh, dY, hd, dY, s))) return rc;                    // dm2 = dY + du W1
       if ((rc = wgrad(h->dh, mh, b.m2, hd, rows, G + b.o_fc1_w))) return rc;                                    // dW1 = du^T m2
       if ((rc = ln_bwd(b.x_mid, b.mod2))) return rc;
@@ -1486,10 +1529,10 @@ int dfot_dit_train_backward(dfot_dit_train_t h, const float* d_out, void* stream
         if ((rc = launch_attention_bwd_delta(b.o, h->dO, hd, h->delta, nseq, c.num_heads, seq, h->d, s))) return rc;
         if ((rc = launch_attention_bwd(b.q, b.k, b.v, h->dO, hd, b.lse, h->delta, h->dq, h->dk, h->dv, nseq, c.num_heads, seq, h->d, s))) return rc;
       }
-      hipLaunchKernelGGL(qkv_grad_pack_kernel, dim3(cdiv(rows * (3 * hd / 8), 256)), dim3(256), 0, s, h->dq, h->dk, h->dv,
-                         facmat || fac ? (const float*)nullptr : h->rope_cs, h->dqkv, rows, seq, c.num_heads, h->d, h->dstride);
-      launch_colsum_bf16(h->dqkv, G + b.o_qkv_b, rows, 3 * hd, (long)3 * hd, s);
-      DFOT_CHECK_HIP(hipGetLastError());
+      if ((rc = launch_qkv_grad_pack(h->dq, h->dk, h->dv, facmat || fac ? (const float*)nullptr : h->rope_cs, h->dqkv, rows, seq, c.num_heads, h->d,
+                                     h->dstride, s)))
+        return rc;
+      if ((rc = launch_colsum_bf16(h->dqkv, G + b.o_qkv_b, rows, 3 * hd, (long)3 * hd, s))) return rc;
       if ((rc = tr_gemm_f32(h->dqkv, 3 * hd, b.w_qkvT, (int)rows, hd, 3 * hd, dY, hd, dY, s))) return rc;       // dm = dY + dqkv Wqkv (in place)
       if ((rc = wgrad(h->dqkv, 3 * hd, b.m, hd, rows, G + b.o_qkv_w))) return rc;  // dWqkv = dqkv^T m
     } else {
@@ -1542,13 +1585,11 @@ int dfot_dit_train_backward(dfot_dit_train_t h, const float* d_out, void* stream
   }
 
   // ---- patch embedding ----
-  launch_pe_wgrad(dY, h->x_saved, G + h->o_pe_w, G + h->o_pe_b, c.in_channels, c.height, c.width, c.patch_size, hd, rows, s);
-  DFOT_CHECK_HIP(hipGetLastError());
+  if ((rc = launch_pe_wgrad(dY, h->x_saved, G + h->o_pe_w, G + h->o_pe_b, c.in_channels, c.height, c.width, c.patch_size, hd, rows, s))) return rc;
   h->d_embed = dY;  // gradient w.r.t. the patch-embedding output: dfot_dit_train_input_grad turns it into d / d x
 
   // ---- modulation Linears: table = SiLU(c) W_mod^T + b_mod over the frames ----
-  static_assert(TR_CHUNKS == 4, "dmod_reduce_kernel adds four planes");
-  hipLaunchKernelGGL(dmod_reduce_kernel, dim3(cdiv((long)frames * h->ldt, 256)), dim3(256), 0, s, h->dmod_part, h->dmod, (long)frames * h->ldt);
+  if ((rc = launch_dmod_reduce(h->dmod_part, h->dmod, (long)frames * h->ldt, s))) return rc;
   hipLaunchKernelGGL(frames_colsum_kernel, dim3(cdiv(h->ldt, 256)), dim3(256), 0, s, h->dmod, h->dbmod, frames, h->ldt);
   DFOT_CHECK_HIP(hipGetLastError());
   if ((rc = launch_f32_to_bf16(h->dmod, h->dmod_bf, (long)fp * h->ldt, s))) return rc;
@@ -1605,11 +1646,8 @@ int dfot_dit_train_input_grad(dfot_dit_train_t h, float* dx, void* stream) {
   DFOT_REQUIRE(h->batch > 0 && h->d_embed, DFOT_ERR_STATE, "train_input_grad: run dfot_dit_train_backward first");
   const DitCfg& c = h->cfg;
   const long rows = (long)h->batch * h->tokens * h->P;
-  const int kdim = c.in_channels * c.patch_size * c.patch_size;
-  hipLaunchKernelGGL(pe_dgrad_kernel, dim3(cdiv(rows * kdim, 256)), dim3(256), 0, (hipStream_t)stream, h->d_embed, h->params_f32 + h->o_pe_w, dx,
-                     c.in_channels, c.height, c.width, c.patch_size, c.hidden_size, rows);
-  DFOT_CHECK_HIP(hipGetLastError());
-  return DFOT_OK;
+  return launch_pe_dgrad(h->d_embed, h->params_f32 + h->o_pe_w, dx, c.in_channels, c.height, c.width, c.patch_size, c.hidden_size, rows,
+                         (hipStream_t)stream);
 }
 
 /* ---- flat-buffer optimizer pieces (generic) ---- */
@@ -1628,6 +1666,96 @@ int dfot_adamw_step(float* params, const float* grads, float* exp_avg, float* ex
   DFOT_REQUIRE(params && grads && exp_avg && exp_avg_sq && n > 0, DFOT_ERR_ARG, "adamw_step: bad argument");
   return launch_adamw(params, grads, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, step, grad_sumsq, max_grad_norm, ema,
                       ema_decay, (hipStream_t)stream);
+}
+
+/* ---- single launches of the training path (test entries: the trainer's own launchers on caller-provided buffers) ---- */
+// the per-frame table of the trainer: row f of `table` belongs to frame f; `cols` modulation columns at `off`
+static int op_frame_table(const char* what, int64_t ldt, int64_t off, int cols, int hidden, int rows_per_frame, int frames) {
+  DFOT_REQUIRE(hidden > 0 && hidden % 4 == 0, DFOT_ERR_SHAPE, "%s: hidden %d must be a positive multiple of 4", what, hidden);
+  DFOT_REQUIRE(frames > 0 && rows_per_frame > 0 && (long)frames * rows_per_frame * hidden < (1L << 31), DFOT_ERR_SHAPE,
+               "%s: %d frames of %d rows, hidden %d", what, frames, rows_per_frame, hidden);
+  DFOT_REQUIRE(off >= 0 && off % 4 == 0 && ldt % 4 == 0 && ldt >= off + (long)cols * hidden, DFOT_ERR_ARG,
+               "%s: table row of %ld with %d x %d columns at %ld (multiples of 4)", what, (long)ldt, cols, hidden, (long)off);
+  return DFOT_OK;
+}
+static int op_frame_chunks(const char* what, int rows_per_frame) {
+  DFOT_REQUIRE(rows_per_frame % TR_CHUNKS == 0, DFOT_ERR_ARG, "%s: %d rows per frame must be a multiple of %d", what, rows_per_frame, TR_CHUNKS);
+  return DFOT_OK;
+}
+
+int dfot_op_dit_gate_combine(const float* x, float* y, const void* a, const float* table, int64_t ldt, int64_t off, int hidden, int rows_per_frame,
+                             int rows, void* stream) {
+  DFOT_REQUIRE(x && y && a && table, DFOT_ERR_ARG, "gate_combine: null argument");
+  DFOT_REQUIRE(rows > 0 && rows_per_frame > 0 && rows % rows_per_frame == 0, DFOT_ERR_SHAPE, "gate_combine: %d rows of %d per frame", rows, rows_per_frame);
+  if (int rc = op_frame_table("gate_combine", ldt, off, 1, hidden, rows_per_frame, rows / rows_per_frame)) return rc;
+  return launch_gate_combine(x, y, (const bf16*)a, table, ldt, off, hidden, rows_per_frame, rows, (hipStream_t)stream);
+}
+
+int dfot_op_dit_gate_bwd(const float* dy, const void* a, const float* table, int64_t ldt, int64_t off, void* da, float* dmod_part, float* dbias_part,
+                         float* dbias, float* dmod, int hidden, int rows_per_frame, int frames, void* stream) {
+  DFOT_REQUIRE(dy && a && table && da && dmod_part && dbias_part && dbias && dmod, DFOT_ERR_ARG, "gate_bwd: null argument");
+  int rc = op_frame_table("gate_bwd", ldt, off, 1, hidden, rows_per_frame, frames);
+  if (rc || (rc = op_frame_chunks("gate_bwd", rows_per_frame))) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  if ((rc = launch_gate_bwd(dy, (const bf16*)a, table, ldt, off, (bf16*)da, dmod_part, dbias_part, dbias, hidden, rows_per_frame, frames, s))) return rc;
+  return launch_dmod_reduce(dmod_part, dmod, (long)frames * ldt, s);
+}
+
+int dfot_op_dit_ln_bwd(const float* dm, const float* x, const float* table, int64_t ldt, int64_t off, float* dx, float* stats, float* dmod_part,
+                       float* dmod, int hidden, int rows_per_frame, int frames, float eps, void* stream) {
+  DFOT_REQUIRE(dm && x && table && dx && stats && dmod_part && dmod, DFOT_ERR_ARG, "ln_bwd: null argument");
+  int rc = op_frame_table("ln_bwd", ldt, off, 2, hidden, rows_per_frame, frames);
+  if (rc || (rc = op_frame_chunks("ln_bwd", rows_per_frame))) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  if ((rc = launch_ln_bwd_rows(dm, x, table, ldt, off, dx, stats, hidden, rows_per_frame, frames * rows_per_frame, eps, s))) return rc;
+  if ((rc = launch_ln_bwd_frames(dm, x, stats, dmod_part, ldt, off, hidden, rows_per_frame, frames, s))) return rc;
+  return launch_dmod_reduce(dmod_part, dmod, (long)frames * ldt, s);
+}
+/* the row part alone (any rows_per_frame: the frame reductions are what needs a multiple of four) */
+int dfot_op_dit_ln_bwd_rows(const float* dm, const float* x, const float* table, int64_t ldt, int64_t off, float* dx, float* stats, int hidden,
+                            int rows_per_frame, int frames, float eps, void* stream) {
+  DFOT_REQUIRE(dm && x && table && dx && stats, DFOT_ERR_ARG, "ln_bwd_rows: null argument");
+  if (int rc = op_frame_table("ln_bwd_rows", ldt, off, 2, hidden, rows_per_frame, frames)) return rc;
+  return launch_ln_bwd_rows(dm, x, table, ldt, off, dx, stats, hidden, rows_per_frame, frames * rows_per_frame, eps, (hipStream_t)stream);
+}
+
+int dfot_op_dit_gelu(const void* u, void* h, void* dh_to_du, int64_t n, void* stream) {
+  DFOT_REQUIRE(u && (h || dh_to_du), DFOT_ERR_ARG, "gelu: null argument (u, and h or dh_to_du)");
+  DFOT_REQUIRE(n > 0 && n % 8 == 0, DFOT_ERR_SHAPE, "gelu: %ld elements must be a positive multiple of 8", (long)n);
+  return launch_gelu((const bf16*)u, (bf16*)h, (bf16*)dh_to_du, (long)n, (hipStream_t)stream);
+}
+
+int dfot_op_dit_patch_embed_dgrad(const float* dy, const float* w, float* dx, int c, int h, int width, int patch, int hidden, int64_t rows,
+                                  void* stream) {
+  DFOT_REQUIRE(dy && w && dx, DFOT_ERR_ARG, "patch_embed_dgrad: null argument");
+  if (int rc = op_patch_geometry("patch_embed_dgrad", c, h, width, patch, hidden, rows)) return rc;
+  return launch_pe_dgrad(dy, w, dx, c, h, width, patch, hidden, (long)rows, (hipStream_t)stream);
+}
+
+int dfot_op_dit_patch_embed_wgrad(const float* dy, const float* x, float* dw, float* db, int c, int h, int width, int patch, int hidden, int64_t rows,
+                                  void* stream) {
+  DFOT_REQUIRE(dy && x && dw && db, DFOT_ERR_ARG, "patch_embed_wgrad: null argument");
+  if (int rc = op_patch_geometry("patch_embed_wgrad", c, h, width, patch, hidden, rows)) return rc;
+  return launch_pe_wgrad(dy, x, dw, db, c, h, width, patch, hidden, (long)rows, (hipStream_t)stream);
+}
+
+int dfot_op_dit_final_gather(const float* dout, void* dyp, void* dyt, int64_t rows, int c, int h, int width, int patch, int ocp, void* stream) {
+  DFOT_REQUIRE(dout && dyp && dyt, DFOT_ERR_ARG, "final_gather: null argument");
+  if (int rc = op_patch_geometry("final_gather", c, h, width, patch, 1, rows)) return rc;
+  DFOT_REQUIRE(ocp >= c * patch * patch, DFOT_ERR_ARG, "final_gather: row stride %d of dyp is shorter than the %d outputs", ocp, c * patch * patch);
+  return launch_final_gather(dout, (bf16*)dyp, (bf16*)dyt, (long)rows, c, h, width, patch, ocp, (hipStream_t)stream);
+}
+
+int dfot_op_dit_qkv_grad_pack(const void* dq, const void* dk, const void* dv, const float* rope_cs, void* out, int64_t rows, int ntok, int heads, int d,
+                              int dstride, void* stream) {
+  DFOT_REQUIRE(dq && dk && dv && out, DFOT_ERR_ARG, "qkv_grad_pack: null argument");
+  DFOT_REQUIRE(heads > 0 && d > 0 && d % 8 == 0 && (3L * heads * d) % 8 == 0, DFOT_ERR_SHAPE,
+               "qkv_grad_pack: head dim %d and row length 3 x %d x %d must be multiples of 8", d, heads, d);
+  DFOT_REQUIRE(dstride >= d && dstride % 8 == 0, DFOT_ERR_ARG, "qkv_grad_pack: head stride %d for head dim %d (a multiple of 8, >= d)", dstride, d);
+  DFOT_REQUIRE(ntok > 0 && rows > 0 && rows % ntok == 0 && rows * 3 * heads * (long)dstride < (1L << 31), DFOT_ERR_SHAPE,
+               "qkv_grad_pack: %ld rows in sequences of %d tokens", (long)rows, ntok);
+  return launch_qkv_grad_pack((const bf16*)dq, (const bf16*)dk, (const bf16*)dv, rope_cs, (bf16*)out, (long)rows, ntok, heads, d, dstride,
+                              (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -304,6 +304,58 @@ int dfot_op_dit_final_layer_chunked(const float* x, const float* table, const in
                                     const float* b, float* out, int hidden, int rows_per_frame, int rows, float eps, int max_level, int c, int h,
                                     int width, int patch, int chunk, void* stream);
 
+/* ---- single launches of the DiT / DiT1D block kernels (test entries) ----
+ * Each runs the launcher function the engines call (same grid, block and argument order) on buffers the caller provides; nothing is
+ * allocated except the grow-only partial-sum scratch of the deterministic sums.  Conventions: x / dx / dy / dm [rows][hidden] fp32,
+ * rows = frames * rows_per_frame; `bf16` buffers are [rows][hidden] unless stated; a modulation table has rows of ldt floats and the op's
+ * columns start at `off` (ldt and off multiples of 4).  ln_mod and dit1d_ln_share index the table by clamp(levels[frame], 0, max_level);
+ * the training ops (gate_combine, gate_bwd, ln_bwd) take the trainer's per-frame table: row f belongs to frame f.
+ * Refused by name: a hidden size without a LayerNorm kernel instance (DFOT_ERR_SHAPE), rows_per_frame % 4 != 0 for gate_bwd / ln_bwd,
+ * hidden % 4 != 0, head dim or packed row length not multiples of 8, patch * patch * c > 256, null pointers. */
+/* xout [rows][hidden] fp32 and obf bf16 <- LayerNorm(xin) * (1 + scale) + shift; xout may be xin; (shift | scale) at off */
+int dfot_op_dit_ln_mod(const float* xin, float* xout, void* obf, const float* table, const int32_t* levels, int64_t ldt, int64_t off, int hidden,
+                       int rows_per_frame, int rows, float eps, int max_level, void* stream);
+/* y = x + gate[frame] * a (a bf16), gate = table[frame][off .. off + hidden) */
+int dfot_op_dit_gate_combine(const float* x, float* y, const void* a, const float* table, int64_t ldt, int64_t off, int hidden, int rows_per_frame,
+                             int rows, void* stream);
+/* da bf16 = dy * gate; dbias [hidden] = sum over all rows of da (as stored, bf16); dmod[frame][off + c] = sum over the frame's rows of dy * a.
+ * dmod_part [4][frames][ldt]: the kernel stores the gate's hidden columns of every plane; dbias_part [4 * frames][hidden];
+ * dmod [frames][ldt] = the four planes of dmod_part added in a fixed order, every column (what the caller left in the others included) */
+int dfot_op_dit_gate_bwd(const float* dy, const void* a, const float* table, int64_t ldt, int64_t off, void* da, float* dmod_part, float* dbias_part,
+                         float* dbias, float* dmod, int hidden, int rows_per_frame, int frames, void* stream);
+/* backward of m = LayerNorm(x) * (1 + scale) + shift for dm: dx [rows][hidden], stats [rows][2] = (mean, rstd), and through dmod_part / dmod (as
+ * gate_bwd) dshift at columns [off, off + hidden) and dscale at [off + hidden, off + 2 * hidden); scale = table[frame][off + hidden ...) */
+int dfot_op_dit_ln_bwd(const float* dm, const float* x, const float* table, int64_t ldt, int64_t off, float* dx, float* stats, float* dmod_part,
+                       float* dmod, int hidden, int rows_per_frame, int frames, float eps, void* stream);
+/* the row part of ln_bwd alone (dx and stats), any rows_per_frame */
+int dfot_op_dit_ln_bwd_rows(const float* dm, const float* x, const float* table, int64_t ldt, int64_t off, float* dx, float* stats, int hidden,
+                            int rows_per_frame, int frames, float eps, void* stream);
+/* tanh-GELU on n bf16 elements (n % 8 == 0): h = gelu(u) when h is given; dh_to_du *= gelu'(u) in place when it is given */
+int dfot_op_dit_gelu(const void* u, void* h, void* dh_to_du, int64_t n, void* stream);
+/* PatchEmbed (Conv2d, kernel = stride = patch): x [frames][c][h][width] -> out [rows][hidden], w [hidden][c * patch * patch], pos [rows per
+ * frame][hidden] or NULL; its data gradient dx [frames][c][h][width] from dy [rows][hidden]; its weight gradients dw += , db += */
+int dfot_op_dit_patch_embed(const float* x, const float* w, const float* b, const float* pos, float* out, int c, int h, int width, int patch,
+                            int hidden, int64_t rows, void* stream);
+int dfot_op_dit_patch_embed_dgrad(const float* dy, const float* w, float* dx, int c, int h, int width, int patch, int hidden, int64_t rows,
+                                  void* stream);
+int dfot_op_dit_patch_embed_wgrad(const float* dy, const float* x, float* dw, float* db, int c, int h, int width, int patch, int hidden, int64_t rows,
+                                  void* stream);
+/* dout [frames][c][h][width] fp32 gathered per token: dyp [rows][ocp] bf16 (columns (py, px, channel) < patch * patch * c written) and its
+ * transpose dyt [..][rows] (rows < patch * patch * c written); the caller zeroes the padding */
+int dfot_op_dit_final_gather(const float* dout, void* dyp, void* dyt, int64_t rows, int c, int h, int width, int patch, int ocp, void* stream);
+/* (dq, dk, dv) [rows / ntok][heads][ntok][dstride] bf16 -> out [rows][3 * heads * d] (q | k | v, head-major); with rope_cs [ntok][d / 2][2]
+ * (cos, sin) dq and dk are rotated by the transpose of the forward rotation */
+int dfot_op_dit_qkv_grad_pack(const void* dq, const void* dk, const void* dv, const float* rope_cs, void* out, int64_t rows, int ntok, int heads, int d,
+                              int dstride, void* stream);
+/* DiT1D: X [rows][hidden] = w x + b + pos for x [frames][C][L] (channel-major frames), rows = videos * n, n tokens per video, pos [n][hidden] */
+int dfot_op_dit1d_tok_embed(const float* x, const float* w, const float* b, const float* pos, float* X, int C, int L, int n, int hidden, int64_t rows,
+                            void* stream);
+/* DiT1D share_norm: X <- LayerNorm(X) in place, A bf16 <- LayerNorm(X) * (1 + scale) + shift; idx [frames] int32 receives the clamped levels */
+int dfot_op_dit1d_ln_share(float* X, void* A, const float* table, const int32_t* levels, int32_t* idx, int64_t ldt, int64_t off, int hidden,
+                           int rows_per_frame, int rows, float eps, int max_level, void* stream);
+/* DiT1D final layer: out [frames][C][L] = Linear(LayerNorm(X)), w [C][hidden] */
+int dfot_op_dit1d_final(const float* X, const float* w, const float* b, float* out, int hidden, int C, int L, int rows, float eps, void* stream);
+
 /* ---- attention maps (the read-out of the reference's attn_hook: algorithms/common/attn_hook/hook.py, dit_blocks.py:100-118) ----
  * Which frame attends to which, per head, of the blocks whose attention mixes frames: the blocks of variant 0 (full 3-D attention), the
  * temporal blocks of variant 2 and the matrix blocks of variant 3.  The forward kernels never form the score matrix; with a capture on,
