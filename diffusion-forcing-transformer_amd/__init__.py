@@ -19,6 +19,7 @@ from . import parallel  # noqa: F401,E402
 from .training import ContextTraining, TrainingNoise, training_step_forward  # noqa: F401,E402
 from .checkpoint import load_reference_checkpoint  # noqa: F401,E402
 from .trainer import DiT3DTrainer, FacDiTTrainer, FacMatDiTTrainer  # noqa: F401,E402
+from .dit1d_trainer import DiT1DTrainer  # noqa: F401,E402
 from . import uvit_train  # noqa: F401,E402
 from .uvit_train import UViT3DPoseTrainer, UViT3DTrainer  # noqa: F401,E402
 from .vae import VideoVAEDecoder, VideoVAEEncoder, VideoVAEPosterior, decode_latents, encode_videos  # noqa: F401,E402

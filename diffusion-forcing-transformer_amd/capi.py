@@ -279,6 +279,11 @@ SIGNATURES = {
     "dfot_op_dit1d_tok_embed": (_I, [_P] * 5 + [_I] * 4 + [_L, _P]),
     "dfot_op_dit1d_ln_share": (_I, [_P] * 5 + [_L, _L, _I, _I, _I, _F, _I, _P]),
     "dfot_op_dit1d_final": (_I, [_P] * 4 + [_I] * 4 + [_F, _P]),
+    "dfot_op_dit1d_ln_share_train": (_I, [_P] * 5 + [_L, _L, _I, _I, _I, _F, _P]),
+    "dfot_op_dit1d_ln_share_bwd": (_I, [_P] * 5 + [_L, _L, _P, _P, _I, _I, _I, _P]),
+    "dfot_op_dit1d_final_bwd": (_I, [_P] * 8 + [_I] * 4 + [_F, _P]),
+    "dfot_op_dit1d_tok_embed_wgrad": (_I, [_P] * 5 + [_I] * 3 + [_L, _P]),
+    "dfot_op_dit1d_tok_embed_dgrad": (_I, [_P] * 3 + [_I] * 3 + [_L, _P]),
     "dfot_op_attention_frame_causal": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "dfot_op_attention_frame_causal_lse": (_I, [_P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _P]),
     "dfot_op_attention_frame_causal_bwd": (_I, [_P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
@@ -292,6 +297,20 @@ SIGNATURES = {
     "dfot_dit1d_reserve": (_I, [_P, _I]),
     "dfot_dit1d_workspace_bytes": (C.c_size_t, [_P]),
     "dfot_dit1d_forward": (_I, [_P, _P, _P, _P, _I, _I, _P]),
+    "dfot_dit1d_train_create": (_I, [C.POINTER(DiT1DConfig), C.POINTER(_P)]),
+    "dfot_dit1d_train_destroy": (_I, [_P]),
+    "dfot_dit1d_train_num_params": (_I, [_P]),
+    "dfot_dit1d_train_param_name": (C.c_char_p, [_P, _I]),
+    "dfot_dit1d_train_param_shape": (_I, [_P, _I, C.POINTER(_L), C.POINTER(_I)]),
+    "dfot_dit1d_train_param_offset": (_L, [_P, _I]),
+    "dfot_dit1d_train_total_numel": (_L, [_P]),
+    "dfot_dit1d_train_load_buffer": (_I, [_P, C.c_char_p, _P, _L, _P]),
+    "dfot_dit1d_train_attach": (_I, [_P, _P, _P]),
+    "dfot_dit1d_train_sync_weights": (_I, [_P, _P]),
+    "dfot_dit1d_train_reserve": (_I, [_P, _I]),
+    "dfot_dit1d_train_forward": (_I, [_P, _P, _P, _P, _I, _I, _P]),
+    "dfot_dit1d_train_backward": (_I, [_P, _P, _P]),
+    "dfot_dit1d_train_input_grad": (_I, [_P, _P, _P]),
 }
 
 

@@ -1605,4 +1605,5 @@ int dfot_op_dit_patch_embed(const float* x, const float* w, const float* b, cons
 }  // extern "C"
 
 #include "dit_train.inl"
+#include "dit1d_train.inl"
 #include "uvit_train.inl"

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "dfot_hip.h"
+#include "dit1d_train.h"
 #include "engine_device.h"
 #include "gemm.h"
 #include "kernels.h"
@@ -174,6 +175,16 @@ int launch_d1_final(const float* X, const float* w, const float* b, float* out, 
 }
 
 }  // namespace
+
+// the two ends of the forward for the training engine (dit1d_train.inl, another translation unit; declared in dit1d_train.h)
+int d1_tok_embed(const float* x, const float* w, const float* b, const float* pos, float* X, int C, int L, int n, int hidden, long rows,
+                 hipStream_t s) {
+  return launch_d1_tok_embed(x, w, b, pos, X, C, L, n, hidden, rows, s);
+}
+int d1_final(const float* X, const float* w, const float* b, float* out, int hidden, int C, int L, int rows, float eps, hipStream_t s) {
+  return launch_d1_final(X, w, b, out, hidden, C, L, rows, eps, s);
+}
+
 }  // namespace dfot
 
 using namespace dfot;

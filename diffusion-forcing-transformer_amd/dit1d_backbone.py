@@ -11,7 +11,7 @@ Built: the stock configuration -- ``merge_mode: share_norm`` (whose blocks overw
 ``learn_sigma: false``, no external condition (a non-zero ``external_cond_dim`` makes the reference's own constructor raise), discrete
 noise levels.  Constructor keywords, ``forward`` signature and the state-dict key names / order are the reference's.  The ``pos_embed``
 add fixes the sequence length: like the reference, the model runs at exactly ``max_tokens`` frames.  Forward only: under autograd it raises
-NotImplementedError (training would need the backward of the frame-causal attention).
+NotImplementedError; training is ``dit1d_trainer.DiT1DTrainer``, whose state dict loads into this module.
 """
 from __future__ import annotations
 
@@ -56,6 +56,59 @@ def state_dict_layout(hidden: int, depth: int, mlp_hidden: int, channels: int, t
     return out
 
 
+def check_config(cfg, x_shape: Sequence[int], max_tokens: int, external_cond_dim: int = 0, timesteps: int = 1000):
+    """What DiT1D and DiT1DTrainer build, refused by name otherwise.  -> (x_shape, causal_attn_mode, engine config)"""
+    merge = _get(cfg, "merge_mode", "share_norm")
+    if merge != "share_norm":
+        raise ValueError(f"merge_mode={merge!r} is not built: only merge_mode='share_norm' (the stock dit1d.yaml)")
+    if _get(cfg, "use_rotary_emb", False):
+        raise ValueError("use_rotary_emb=True is not built: the model adds the frozen pos_embed table (use_rotary_emb: false)")
+    if _get(cfg, "qk_norm", False):
+        raise ValueError("qk_norm=True is not built: the attention takes q and k as the projection gives them (qk_norm: false)")
+    if _get(cfg, "learn_sigma", False):
+        raise ValueError("learn_sigma=True is not built: the output has the input's channels (learn_sigma: false)")
+    mode = _get(cfg, "causal_attn_mode", "video_temporal_causal")
+    if mode not in CAUSAL_MODES:
+        raise ValueError(f"causal_attn_mode={mode!r} is unknown: one of None, 'temporal_causal', 'video_temporal_causal'")
+    if external_cond_dim:
+        raise ValueError(f"external_cond_dim={external_cond_dim} is not built: the reference's own DiT1D constructor fails on a non-zero "
+                         "external_cond_dim (external_cond_emb_dim reads self.external_cond_dim, which is never assigned); the model is "
+                         "unconditioned")
+    x_shape = tuple(int(v) for v in x_shape)
+    if len(x_shape) != 3 or x_shape[1] != 1:
+        raise ValueError(f"x_shape[1] must be 1: DiT1D takes 1-D token latents (C, 1, L), got x_shape {x_shape}")
+    channels, _, length = x_shape
+    if length not in FRAME_LENGTHS:
+        raise ValueError(f"L = x_shape[2] = {length} tokens per frame is outside the frame-causal attention kernel's {set(FRAME_LENGTHS)}")
+    max_tokens = int(max_tokens)
+    if max_tokens <= 0 or (max_tokens * length) % 128 != 0:
+        raise ValueError(f"max_tokens * L = {max_tokens} x {length} = {max_tokens * length} tokens per window; the attention row tiles need a "
+                         "multiple of 128")
+    hidden, heads = int(_get(cfg, "hidden_size")), int(_get(cfg, "num_heads"))
+    if hidden <= 0 or hidden % 64 or hidden > 2048:
+        raise ValueError(f"hidden_size={hidden} is outside the engine's limit: a multiple of 64, at most 2048")
+    depth = int(_get(cfg, "depth"))
+    if depth <= 0:
+        raise ValueError(f"depth={depth} must be positive")
+    mlp_hidden = int(hidden * float(_get(cfg, "mlp_ratio", 4.0)))
+    if mlp_hidden <= 0 or mlp_hidden % 64:
+        raise ValueError(f"mlp_ratio={_get(cfg, 'mlp_ratio', 4.0)} gives an MLP width of {mlp_hidden}; the GEMMs need a positive multiple of 64")
+    if not 1 <= channels <= 64:
+        raise ValueError(f"x_shape[0] = {channels} channels is outside the token embedding's 1 .. 64")
+    if int(timesteps) <= 0:
+        raise ValueError(f"timesteps={timesteps} must be positive")
+    if heads <= 0 or hidden % heads or (hidden // heads) % 8 or hidden // heads > 128:
+        raise ValueError(f"head dim hidden_size / num_heads = {hidden} / {heads} = {hidden / max(heads, 1):g} must be a multiple of 8, at most 128")
+    c = capi.DiT1DConfig()
+    c.hidden, c.depth, c.heads = hidden, depth, heads
+    c.mlp_hidden = mlp_hidden
+    c.in_channels, c.tokens_per_frame, c.max_tokens = channels, length, max_tokens
+    c.timesteps = int(timesteps)
+    c.causal = int(mode is not None)
+    c.eps = 1e-6
+    return x_shape, mode, c
+
+
 class DiT1D(EngineModule):
     _family, _create = "dit1d", "dfot_dit1d_create"
 
@@ -63,47 +116,9 @@ class DiT1D(EngineModule):
                  external_cond_num_classes: Optional[int] = None, external_cond_dim: int = 0, use_causal_mask: bool = True,
                  timesteps: int = 1000):
         super().__init__()
-        merge = _get(cfg, "merge_mode", "share_norm")
-        if merge != "share_norm":
-            raise ValueError(f"merge_mode={merge!r} is not built: only merge_mode='share_norm' (the stock dit1d.yaml)")
-        if _get(cfg, "use_rotary_emb", False):
-            raise ValueError("use_rotary_emb=True is not built: the model adds the frozen pos_embed table (use_rotary_emb: false)")
-        if _get(cfg, "qk_norm", False):
-            raise ValueError("qk_norm=True is not built: the attention takes q and k as the projection gives them (qk_norm: false)")
-        if _get(cfg, "learn_sigma", False):
-            raise ValueError("learn_sigma=True is not built: the output has the input's channels (learn_sigma: false)")
-        mode = _get(cfg, "causal_attn_mode", "video_temporal_causal")
-        if mode not in CAUSAL_MODES:
-            raise ValueError(f"causal_attn_mode={mode!r} is unknown: one of None, 'temporal_causal', 'video_temporal_causal'")
-        if external_cond_dim:
-            raise ValueError(f"external_cond_dim={external_cond_dim} is not built: the reference's own DiT1D constructor fails on a non-zero "
-                             "external_cond_dim (external_cond_emb_dim reads self.external_cond_dim, which is never assigned); the model is "
-                             "unconditioned")
-        self.x_shape = tuple(int(v) for v in x_shape)
-        if len(self.x_shape) != 3 or self.x_shape[1] != 1:
-            raise ValueError(f"x_shape[1] must be 1: DiT1D takes 1-D token latents (C, 1, L), got x_shape {self.x_shape}")
+        self.x_shape, mode, c = check_config(cfg, x_shape, max_tokens, external_cond_dim, timesteps)
         channels, _, length = self.x_shape
-        if length not in FRAME_LENGTHS:
-            raise ValueError(f"L = x_shape[2] = {length} tokens per frame is outside the frame-causal attention kernel's {set(FRAME_LENGTHS)}")
-        max_tokens = int(max_tokens)
-        if max_tokens <= 0 or (max_tokens * length) % 128 != 0:
-            raise ValueError(f"max_tokens * L = {max_tokens} x {length} = {max_tokens * length} tokens per window; the attention row tiles need a "
-                             "multiple of 128")
-        hidden, heads = int(_get(cfg, "hidden_size")), int(_get(cfg, "num_heads"))
-        if hidden <= 0 or hidden % 64 or hidden > 2048:
-            raise ValueError(f"hidden_size={hidden} is outside the engine's limit: a multiple of 64, at most 2048")
-        depth = int(_get(cfg, "depth"))
-        if depth <= 0:
-            raise ValueError(f"depth={depth} must be positive")
-        mlp_hidden = int(hidden * float(_get(cfg, "mlp_ratio", 4.0)))
-        if mlp_hidden <= 0 or mlp_hidden % 64:
-            raise ValueError(f"mlp_ratio={_get(cfg, 'mlp_ratio', 4.0)} gives an MLP width of {mlp_hidden}; the GEMMs need a positive multiple of 64")
-        if not 1 <= channels <= 64:
-            raise ValueError(f"x_shape[0] = {channels} channels is outside the token embedding's 1 .. 64")
-        if int(timesteps) <= 0:
-            raise ValueError(f"timesteps={timesteps} must be positive")
-        if heads <= 0 or hidden % heads or (hidden // heads) % 8 or hidden // heads > 128:
-            raise ValueError(f"head dim hidden_size / num_heads = {hidden} / {heads} = {hidden / max(heads, 1):g} must be a multiple of 8, at most 128")
+        max_tokens, hidden, depth, mlp_hidden = int(c.max_tokens), int(c.hidden), int(c.depth), int(c.mlp_hidden)
         self.cfg = cfg
         self.causal_attn_mode = mode
         self.external_cond_type = external_cond_type
@@ -113,13 +128,6 @@ class DiT1D(EngineModule):
         self.max_tokens = self.num_frames = max_tokens
         self.num_patches = self.n_token_per_frame = length
         self.hidden_size = hidden
-        c = capi.DiT1DConfig()
-        c.hidden, c.depth, c.heads = hidden, depth, heads
-        c.mlp_hidden = mlp_hidden
-        c.in_channels, c.tokens_per_frame, c.max_tokens = channels, length, max_tokens
-        c.timesteps = int(timesteps)
-        c.causal = int(mode is not None)
-        c.eps = 1e-6
         self._ccfg = c
         # The module (parameters, the sin-cos pos_embed) is built on the host; the engine handle, whose creation allocates device memory, is
         # created at the first weight sync or reserve, which also checks that the engine enumerates exactly these keys and shapes.

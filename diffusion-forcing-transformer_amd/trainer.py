@@ -60,23 +60,35 @@ class DiT3DTrainer(FlatAdamWOwner):
         self.max_tokens = int(c.max_tokens)
         self._handle = C.c_void_p()
         self._create(c)
-        lib, h = capi.lib, self._handle
-        self.numel = int(lib.dfot_dit_train_total_numel(h))
-        shape, ndim = (C.c_int64 * 4)(), C.c_int()
-        self.layout: Dict[str, Tuple[int, Tuple[int, ...]]] = {}
-        for i in range(lib.dfot_dit_train_num_params(h)):
-            capi.check(lib.dfot_dit_train_param_shape(h, i, shape, C.byref(ndim)))
-            self.layout[lib.dfot_dit_train_param_name(h, i).decode()] = (
-                int(lib.dfot_dit_train_param_offset(h, i)), tuple(int(shape[k]) for k in range(ndim.value)))
-        # flat buffers: torch owns them (the gradient buffer is what torch.distributed all-reduces)
-        self.opt = FlatAdamW(self.layout, self.numel)
-        capi.check(lib.dfot_dit_train_attach(h, capi.ptr(self.params), capi.ptr(self.grads)))
+        self._bind_engine()
         # FourierEmbedding's buffers (reference draw: 2 pi N(0,1), 2 pi U[0,1)); tensors of their own, never part of the flat buffers
         self.buffers: Dict[str, torch.Tensor] = {}
         if fourier:
             self.buffers = {FOURIER_BUFFERS[0]: (2 * np.pi * torch.randn(int(c.noise_dim))).cuda(),
                             FOURIER_BUFFERS[1]: (2 * np.pi * torch.rand(int(c.noise_dim))).cuda()}
             self._load_buffers()
+        self._init_training_state(timesteps, diffusion, lr, weight_decay, betas, eps, max_grad_norm, loss_weighting)
+
+    _family = "dit"  # the engine's C family: every call below is dfot_<family>_train_<name> (DiT1DTrainer: "dit1d")
+
+    def _engine(self, name: str):
+        return getattr(capi.lib, f"dfot_{self._family}_train_{name}")
+
+    def _bind_engine(self) -> None:
+        """the created handle's parameter layout, the flat AdamW state over it (torch owns the buffers: the gradient buffer is what
+        torch.distributed all-reduces), attached to the engine"""
+        h = self._handle
+        self.numel = int(self._engine("total_numel")(h))
+        shape, ndim = (C.c_int64 * 4)(), C.c_int()
+        self.layout: Dict[str, Tuple[int, Tuple[int, ...]]] = {}
+        for i in range(self._engine("num_params")(h)):
+            capi.check(self._engine("param_shape")(h, i, shape, C.byref(ndim)))
+            self.layout[self._engine("param_name")(h, i).decode()] = (
+                int(self._engine("param_offset")(h, i)), tuple(int(shape[k]) for k in range(ndim.value)))
+        self.opt = FlatAdamW(self.layout, self.numel)
+        capi.check(self._engine("attach")(h, capi.ptr(self.params), capi.ptr(self.grads)))
+
+    def _init_training_state(self, timesteps, diffusion, lr, weight_decay, betas, eps, max_grad_norm, loss_weighting) -> None:
         self.lr, self.weight_decay, self.betas, self.eps, self.max_grad_norm = lr, weight_decay, tuple(betas), eps, max_grad_norm
         self.schedule = Schedule(diffusion or DiffusionConfig(beta_schedule="cosine", is_continuous=False, timesteps=timesteps))
         self.loss_weighting = dict(loss_weighting or {})
@@ -120,13 +132,13 @@ class DiT3DTrainer(FlatAdamWOwner):
     def __del__(self):
         h = getattr(self, "_handle", None)
         if h:
-            capi.lib.dfot_dit_train_destroy(h)
+            self._engine("destroy")(h)
             self._handle = None
 
     # ------------------------------------------------------------------ parameters (reference state_dict names)
     def _load_buffers(self) -> None:
         for k, t in self.buffers.items():
-            capi.check(capi.lib.dfot_dit_train_load_buffer(self._handle, k.encode(), capi.ptr(t, torch.float32, k), t.numel(), capi.stream_ptr()))
+            capi.check(self._engine("load_buffer")(self._handle, k.encode(), capi.ptr(t, torch.float32, k), t.numel(), capi.stream_ptr()))
 
     def load_state_dict(self, state: Dict[str, torch.Tensor], strict: bool = True) -> None:
         missing = [k for k in (*self.buffers, *self.layout) if k not in state]
@@ -155,7 +167,7 @@ class DiT3DTrainer(FlatAdamWOwner):
 
     def _sync(self) -> None:
         if self._dirty:
-            capi.check(capi.lib.dfot_dit_train_sync_weights(self._handle, capi.stream_ptr()))
+            capi.check(self._engine("sync_weights")(self._handle, capi.stream_ptr()))
             self._dirty = False
 
     # ------------------------------------------------------------------ forward / backward (the autograd pair)
@@ -166,10 +178,7 @@ class DiT3DTrainer(FlatAdamWOwner):
         b, t = x.shape[:2]
         if tuple(x.shape[2:]) != self.x_shape:
             raise ValueError(f"x has frame shape {tuple(x.shape[2:])}, expected {self.x_shape}")
-        if b > self._reserved:
-            capi.check(capi.lib.dfot_dit_train_reserve(self._handle, b))
-            self._reserved = b
-        self._sync()
+        self._prepare(b)
         xd = x.to(device="cuda", dtype=torch.float32).contiguous()
         if self.is_continuous != bool(noise_levels.is_floating_point()):
             raise TypeError("a continuous-diffusion trainer takes floating noise levels (precond_scale * logsnr)" if self.is_continuous
@@ -202,14 +211,21 @@ class DiT3DTrainer(FlatAdamWOwner):
         raise NotImplementedError(f"capture_attention: {type(self).__name__} is a training engine; attention maps are captured on the "
                                   "inference model (DiT3D.capture_attention) with the same weights")
 
+    def _prepare(self, b: int) -> None:
+        """workspace for a batch of b and current compute weights"""
+        if b > self._reserved:
+            capi.check(self._engine("reserve")(self._handle, b))
+            self._reserved = b
+        self._sync()
+
     def backward(self, d_out: torch.Tensor) -> None:
         g = d_out.to(device="cuda", dtype=torch.float32).contiguous()
-        capi.check(capi.lib.dfot_dit_train_backward(self._handle, capi.ptr(g), capi.stream_ptr()))
+        capi.check(self._engine("backward")(self._handle, capi.ptr(g), capi.stream_ptr()))
 
     def input_grad(self) -> torch.Tensor:
         """d(sum(out * d_out)) / d x of the last forward / backward pair, in x's layout (reconstruction guidance, discrete_diffusion.py:485-513)"""
         dx = torch.empty_like(self._keep[0])
-        capi.check(capi.lib.dfot_dit_train_input_grad(self._handle, capi.ptr(dx), capi.stream_ptr()))
+        capi.check(self._engine("input_grad")(self._handle, capi.ptr(dx), capi.stream_ptr()))
         return dx
 
     # ------------------------------------------------------------------ one training step

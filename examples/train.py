@@ -6,6 +6,7 @@
   python examples/train.py k600diff [--accumulate 2]                                  # the model bash/k600/*.sh train
   python examples/train.py facmat   [--xl] [--batch 8]                                # FacMatDiT (dit3d_factorized_matrix.yaml); --xl: XL-64-1, taichikl shape
   python examples/train.py facdit   [--xl] [--batch 8]                                # FacDiT (dit3d_factorized_attention.yaml); --xl: @DiT/XL widths, taichikl shape
+  python examples/train.py taichi1d [--xl] [--batch 8]                                # DiT1D (dit1d.yaml), frame-causal, 4x1x32 token latents; --xl: its stock widths, 16 frames
   python examples/train.py mcraft   [--b] [--batch 8]                                 # the Minecraft / dmlab DiT recipe (32x8x8 latents, patch 2, 16 frames,
                                                                                       # actions of dim 4, continuous); --b: @DiT/B, else width 384, depth 2
   python examples/train.py re10k    [--batch 8]                                       # RE10K UViT3DPose (BASELINE config 5), synthetic frames + poses
@@ -37,7 +38,7 @@ K600_DATA_STD = [5.591, 5.257, 7.033, 6.401, 6.091, 11.233, 5.608, 7.5, 5.277, 5
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("model", choices=["k600", "k600diff", "facmat", "facdit", "re10k", "uvit3d", "mcraft"])
+    ap.add_argument("model", choices=["k600", "k600diff", "facmat", "facdit", "taichi1d", "re10k", "uvit3d", "mcraft"])
     ap.add_argument("--ckpt")
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--batch", type=int, default=8)
@@ -50,7 +51,9 @@ def main():
                     help="k600 / k600diff: continuous diffusion as @diffusion/continuous (Fourier noise-level embedding, levels in [0, 1], cosine "
                          "training schedule shifted 0.125, sigmoid loss weighting)")
     ap.add_argument("--xl", action="store_true", help="facmat / facdit: @FacMatDiT/XL-64-1 / @DiT/XL widths at the taichikl shape (4x32x32 latents, "
-                                                      "patch 2, 16 frames) instead of the tiny default (width 128, depth 2, 4x16x8 latents, 5 frames)")
+                                                      "patch 2, 16 frames) instead of the tiny default (width 128, depth 2, 4x16x8 latents, 5 frames); "
+                                                      "taichi1d: the dit1d.yaml widths (1152, depth 28, 16 heads) at 16 frames of 4x1x32 instead of "
+                                                      "width 128, depth 2, 8 frames")
     ap.add_argument("--b", action="store_true", help="mcraft: @DiT/B (hidden 768, depth 12, 12 heads) instead of the tiny default (hidden 384, depth 2, 6 heads)")
     ap.add_argument("--full", action="store_true", help="uvit3d: the widths, depths and dropouts of u_vit3d.yaml with num_heads 8 (its 4 heads give head "
                                                         "dim 256, which the attention kernels do not take) on 8 frames of 3 x 256 x 256, instead of the "
@@ -68,7 +71,7 @@ def main():
         return train_re10k(a, rank, world)
     if a.model == "uvit3d":
         return train_uvit3d(a, rank, world)
-    if a.model in ("facmat", "facdit"):
+    if a.model in ("facmat", "facdit", "taichi1d"):
         return train_factorized(a, rank, world)
     diff, mcraft = a.model == "k600diff", a.model == "mcraft"
     x_shape, tokens = ((32, 8, 8), 16) if mcraft else ((16, 16, 16), 5)
@@ -152,11 +155,21 @@ def main():
 def train_factorized(a, rank, world):
     """DFoTVideo training of the two factorized DiT3D backbones, discrete diffusion, random_independent levels, fused-min-SNR v-loss:
     facmat (bash/taichikl/train_dfot_facmat-*): factorized matrix attention with the temporal RoPE, FacMatDiTTrainer;
-    facdit (bash/taichikl/train_dfot_facdit-*): factorized attention, sinusoidal_factorized, FacDiTTrainer -- the baseline of the former"""
+    facdit (bash/taichikl/train_dfot_facdit-*): factorized attention, sinusoidal_factorized, FacDiTTrainer -- the baseline of the former;
+    taichi1d (`backbone=dit1d`): the frame-causal DiT1D over the 4x1x32 TiTok-KL token latents, DiT1DTrainer (unconditioned)"""
     if a.continuous or a.pixels:
         raise SystemExit(f"{a.model} trains on synthetic latents under discrete diffusion")
     x_shape, tokens = ((4, 32, 32), 16) if a.xl else ((4, 16, 8), 5)
-    if a.model == "facdit":
+    backbone_cls = dfot_amd.DiT3D
+    if a.model == "taichi1d":
+        x_shape, tokens = (4, 1, 32), 16 if a.xl else 8
+        cfg = dict(hidden_size=1152, depth=28, num_heads=16) if a.xl else dict(hidden_size=128, depth=2, num_heads=4)
+        cfg.update(name="dit1d", mlp_ratio=4, learn_sigma=False, merge_mode="share_norm", causal_attn_mode="video_temporal_causal",
+                   use_rotary_emb=False, qk_norm=False)
+        trainer_cls, backbone_cls = dfot_amd.DiT1DTrainer, dfot_amd.DiT1D
+        if a.cond:
+            raise SystemExit("taichi1d: the DiT1D backbone is unconditioned")
+    elif a.model == "facdit":
         cfg = dict(patch_size=2, hidden_size=1152, num_heads=16, depth=28) if a.xl else dict(patch_size=1, hidden_size=128, num_heads=4, depth=2)
         cfg.update(name="dit3d", variant="factorized_attention", pos_emb_type="sinusoidal_factorized", mlp_ratio=4.0, spatial_mlp_ratio=4.0)
         trainer_cls = dfot_amd.FacDiTTrainer
@@ -179,7 +192,7 @@ def train_factorized(a, rank, world):
     if a.ckpt:
         dfot_amd.load_reference_checkpoint(trainer, a.ckpt)
     else:
-        init = dfot_amd.DiT3D(cfg, x_shape=x_shape, max_tokens=tokens, **ckw)
+        init = backbone_cls(cfg, x_shape=x_shape, max_tokens=tokens, **ckw)
         init.init_random(seed=0)  # the same on every rank
         trainer.load_state_dict({k: v.detach() for k, v in init.state_dict().items()})
         del init

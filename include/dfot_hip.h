@@ -355,6 +355,29 @@ int dfot_op_dit1d_ln_share(float* X, void* A, const float* table, const int32_t*
                            int rows_per_frame, int rows, float eps, int max_level, void* stream);
 /* DiT1D final layer: out [frames][C][L] = Linear(LayerNorm(X)), w [C][hidden] */
 int dfot_op_dit1d_final(const float* X, const float* w, const float* b, float* out, int hidden, int C, int L, int rows, float eps, void* stream);
+/* DiT1D training kernels (csrc/dit1d_train.hip).  All fp32, fixed-order sums: two calls on the same inputs give the same bits.
+ * share_norm LayerNorm with saved statistics, not in place: N [rows][hidden] = LayerNorm(X), rstd [rows], M bf16 = N * (1 + scale) + shift
+ * with (shift | scale) = table[row / rows_per_frame][off, off + 2 * hidden): one table row per frame */
+int dfot_op_dit1d_ln_share_train(const float* X, float* N, float* rstd, void* M, const float* table, int64_t ldt, int64_t off, int hidden,
+                                 int rows_per_frame, int rows, float eps, void* stream);
+/* its backward.  The residual base of a share_norm block is N itself, so two gradients arrive: dres [rows][hidden] over the residual path and
+ * dm [rows][hidden] of the modulated GEMM operand.  dn = dres + dm * (1 + scale); dx = rstd * (dn - mean(dn) - N * mean(dn * N));
+ * dmod_part [4][frames][ldt]: plane z receives, at columns [off, off + hidden) and [off + hidden, off + 2 * hidden), the sums of dm and of
+ * dm * N over rows [z, z + 1) * rows_per_frame / 4 of every frame (rows_per_frame % 4 == 0; dres enters neither).  dm == NULL is the final
+ * layer's LayerNorm: dn = dres, table and dmod_part are not used.  dx may be dres. */
+int dfot_op_dit1d_ln_share_bwd(const float* dres, const float* dm, const float* N, const float* rstd, const float* table, int64_t ldt, int64_t off,
+                               float* dx, float* dmod_part, int hidden, int rows_per_frame, int frames, void* stream);
+/* backward of dfot_op_dit1d_final for dout [frames][C][L]: dx [rows][hidden] (d nf = dout * w goes through the LayerNorm backward without
+ * being stored), stats [rows][2] = (mean, rstd) of X's rows, dW [C][hidden] = sum over the rows of dout * LayerNorm(X), db [C] = sum of dout.
+ * part: workspace of ceil(rows / 64) * C * (hidden + 1) floats (the sums of 64 rows each, then added in their order) */
+int dfot_op_dit1d_final_bwd(const float* dout, const float* X, const float* w, float* dx, float* stats, float* part, float* dW, float* db, int hidden,
+                            int C, int L, int rows, float eps, void* stream);
+/* backward of dfot_op_dit1d_tok_embed for dX0 [rows][hidden], weights: dW [hidden][C] = sum over the rows of dX0 * x[(frame, c, l)],
+ * db [hidden] = sum of dX0 (pos is a frozen buffer: nothing is computed for it).  part: ceil(rows / 64) * (C + 1) * hidden floats */
+int dfot_op_dit1d_tok_embed_wgrad(const float* dX0, const float* x, float* part, float* dW, float* db, int C, int L, int hidden, int64_t rows,
+                                  void* stream);
+/* ... and input: dx [frames][C][L] = dX0 * w, w [hidden][C] */
+int dfot_op_dit1d_tok_embed_dgrad(const float* dX0, const float* w, float* dx, int C, int L, int hidden, int64_t rows, void* stream);
 
 /* ---- attention maps (the read-out of the reference's attn_hook: algorithms/common/attn_hook/hook.py, dit_blocks.py:100-118) ----
  * Which frame attends to which, per head, of the blocks whose attention mixes frames: the blocks of variant 0 (full 3-D attention), the
@@ -948,6 +971,32 @@ int dfot_dit1d_finalize(dfot_dit1d_t h, void* stream);
 int dfot_dit1d_reserve(dfot_dit1d_t h, int max_batch);
 size_t dfot_dit1d_workspace_bytes(dfot_dit1d_t h);
 int dfot_dit1d_forward(dfot_dit1d_t h, const float* x, const int32_t* noise_levels, float* out, int batch, int tokens, void* stream);
+
+/* ---- DiT1D training (csrc/dit1d_train.inl; Python mirror: dit1d_trainer.DiT1DTrainer) ----
+ * The dfot_dit_train_* contract for the DiT1D backbone: the trainable parameters live in ONE caller-owned flat fp32 buffer with a gradient
+ * buffer of the same layout (the reference module's parameters() order, every tensor 16-byte aligned at dfot_dit1d_train_param_offset).
+ * pos_embed is a frozen parameter of the reference (requires_grad = False): it is NOT in the flat buffers -- no gradient, no optimizer
+ * state, no weight decay -- and is loaded once with dfot_dit1d_train_load_buffer("pos_embed", device fp32 [T * L * hidden]).
+ * Limits: those of dfot_dit1d_create, with hidden and mlp_hidden multiples of 128 (the weight-gradient GEMMs tile a feature axis by 128);
+ * a violation is DFOT_ERR_SHAPE / DFOT_ERR_ARG with the field's name.  The six modulations of every block are evaluated per frame from
+ * the live weights.  attach -> [load_buffer] -> sync_weights (after every parameter update) -> reserve -> forward -> backward (OVERWRITES
+ * the gradient buffer with d sum(out * d_out) / d parameter) -> input_grad (d / d x of the same pair).  tokens must equal max_tokens.
+ * x must stay alive until backward.  No atomics: two runs give the same bits. */
+typedef struct dfot_dit1d_train_s* dfot_dit1d_train_t;
+int dfot_dit1d_train_create(const dfot_dit1d_config* cfg, dfot_dit1d_train_t* out);
+int dfot_dit1d_train_destroy(dfot_dit1d_train_t h);
+int dfot_dit1d_train_num_params(dfot_dit1d_train_t h);
+const char* dfot_dit1d_train_param_name(dfot_dit1d_train_t h, int i);
+int dfot_dit1d_train_param_shape(dfot_dit1d_train_t h, int i, int64_t shape[4], int* ndim);
+int64_t dfot_dit1d_train_param_offset(dfot_dit1d_train_t h, int i);
+int64_t dfot_dit1d_train_total_numel(dfot_dit1d_train_t h);
+int dfot_dit1d_train_load_buffer(dfot_dit1d_train_t h, const char* name, const float* data, int64_t numel, void* stream);
+int dfot_dit1d_train_attach(dfot_dit1d_train_t h, float* params, float* grads);
+int dfot_dit1d_train_sync_weights(dfot_dit1d_train_t h, void* stream);
+int dfot_dit1d_train_reserve(dfot_dit1d_train_t h, int max_batch);
+int dfot_dit1d_train_forward(dfot_dit1d_train_t h, const float* x, const int32_t* noise_levels, float* out, int batch, int tokens, void* stream);
+int dfot_dit1d_train_backward(dfot_dit1d_train_t h, const float* d_out, void* stream);
+int dfot_dit1d_train_input_grad(dfot_dit1d_train_t h, float* dx, void* stream);
 
 #ifdef __cplusplus
 }

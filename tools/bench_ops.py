@@ -282,6 +282,47 @@ def dit1d_forward(b, rounds=5):
     return out
 
 
+def dit1d_train_ops(rows=4096, hidden=1152, per=32, rounds=7):
+    """the share_norm LayerNorm kernels of DiT1D training alone at rows x hidden (one table row per frame of `per` rows), next to the DiT3D
+    pair that does the same job with one fp32 input stream fewer (dfot_op_dit_ln_bwd: ln_bwd_rows + ln_bwd_frames + the plane sum),
+    alternated in one process: {name: ([ms per round], algorithmic bytes)}"""
+    frames, ldt = rows // per, 6 * hidden
+    x, dres, dm = (torch.randn(rows, hidden, device="cuda") for _ in range(3))
+    table = torch.randn(frames, ldt, device="cuda")
+    n, rstd, m = torch.empty_like(x), torch.empty(rows, device="cuda"), torch.empty(rows, hidden, dtype=torch.bfloat16, device="cuda")
+    dx, stats = torch.empty_like(x), torch.empty(rows, 2, device="cuda")
+    part, dmod = torch.zeros(4, frames, ldt, device="cuda"), torch.zeros(frames, ldt, device="cuda")
+    lib = capi.lib
+    fb = rows * hidden * 4  # one fp32 stream
+    runs = {
+        "ln_share_train": (lambda: capi.check(lib.dfot_op_dit1d_ln_share_train(P(x), P(n), P(rstd), P(m), P(table), ldt, 0, hidden, per, rows, 1e-6, S())),
+                           2 * fb + fb // 2),
+        "ln_share_bwd": (lambda: capi.check(lib.dfot_op_dit1d_ln_share_bwd(P(dres), P(dm), P(n), P(rstd), P(table), ldt, 0, P(dx), P(part), hidden, per,
+                                                                           frames, S())), 4 * fb),
+        "dit ln_bwd (rows + frames + plane sum)": (lambda: capi.check(lib.dfot_op_dit_ln_bwd(P(dm), P(x), P(table), ldt, 0, P(dx), P(stats), P(part), P(dmod),
+                                                                                            hidden, per, frames, 1e-6, S())), 3 * fb + 2 * fb),
+    }
+    out = {name: ([], nbytes) for name, (_, nbytes) in runs.items()}
+    for _ in range(rounds):
+        for name, (fn, _) in runs.items():
+            out[name][0].append(timeit(fn))
+    return out
+
+
+def dit1d_train(b, depth=28):
+    """one training step (loss, backward, AdamW) of DiT1D at the stock dit1d.yaml widths on 16 frames of [4, 1, 32], ms"""
+    bb = dict(name="dit1d", hidden_size=1152, depth=depth, num_heads=16, mlp_ratio=4, learn_sigma=False, merge_mode="share_norm",
+              causal_attn_mode="video_temporal_causal", use_rotary_emb=False, qk_norm=False)
+    tr = dfot_amd.DiT1DTrainer(bb, x_shape=(4, 1, 32), max_tokens=16, loss_weighting=dict(strategy="fused_min_snr", cum_snr_decay=0.96))
+    model = dfot_amd.DiT1D(bb, x_shape=(4, 1, 32), max_tokens=16)  # for its init_random only
+    model.init_random(0)
+    tr.load_state_dict({n: t.detach() for n, t in model.state_dict().items()})
+    del model
+    xs, noise = torch.randn(b, 16, 4, 1, 32, device="cuda"), torch.randn(b, 16, 4, 1, 32, device="cuda")
+    k = torch.randint(0, 1000, (b, 16))
+    return timeit(lambda: tr.training_step(xs, k, noise), iters=5, warm=2)
+
+
 def facmat_narrow_ops(frames, p, h, e):
     """the two left-factor kernels of csrc/facmat_narrow.hip at one shape: (us, algorithmic bytes) of contract and expand, and us of a device
     copy of each launch's byte count timed in the same run (a copy of n bytes reads n / 2 and writes n / 2)"""
@@ -867,6 +908,21 @@ def main():
             r = sorted(r)
             print(f"{name} forward B=16 x 16 frames x 32 tokens (hidden 1152, depth 28): median {r[len(r) // 2]:.3f} ms  (min {r[0]:.3f}, max {r[-1]:.3f} "
                   f"over {len(r)} alternated rounds)", flush=True)
+    if "dit1d_train" in what:
+        for name, (r, nbytes) in dit1d_train_ops().items():
+            r = sorted(r)
+            med = r[len(r) // 2]
+            print(f"dit1d_train {name} rows 4096 x hidden 1152: median {med*1e3:7.1f} us (min {r[0]*1e3:.1f}, max {r[-1]*1e3:.1f} over {len(r)} alternated "
+                  f"rounds)  {nbytes / 1e6:.1f} MB  {nbytes / med / 1e6:7.1f} GB/s ({nbytes / med / 1e9 / HBM_TBS:.2f} of {HBM_TBS:.0f} TB/s HBM)", flush=True)
+        for b in (8, 4, 2):  # the largest of these batches that fits
+            try:
+                ms = dit1d_train(b)
+            except (torch.cuda.OutOfMemoryError, capi.DfotError) as err:
+                print(f"dit1d_train XL B={b}: does not fit ({type(err).__name__})", flush=True)
+                torch.cuda.empty_cache()
+                continue
+            print(f"dit1d_train stock widths B={b} x 16 frames x 32 tokens: {ms:.2f} ms per training step", flush=True)
+            break
     if "facmat_narrow" in what:
         # the S shape (embed_row_dim 384, 64 patches, 16 videos x 16 frames) and an XL-like one (1152, 256 patches, 128 frames)
         for name, (frames, p, h) in {"S": (256, 64, 384), "XL": (128, 256, 1152)}.items():
