@@ -5,6 +5,7 @@ there is no CPU fallback."""
 from . import capi  # noqa: F401  (raises ImportError when libdfot_hip.so is missing)
 from . import ops  # noqa: F401  (registers the torch.library operators dfot::*)
 from .ops import frame_causal_attention  # noqa: F401  (differentiable drop-in for SDPA under the block-lower-triangular mask)
+from .ops import attention_seq64  # noqa: F401  (differentiable drop-in for SDPA over 64-token sequences: the per-frame attention at res-128)
 from .backbone import UViT3DPose  # noqa: F401
 from .uvit3d_backbone import UViT3D  # noqa: F401
 from .dit_backbone import DiT3D, DifferenceDiT3D  # noqa: F401

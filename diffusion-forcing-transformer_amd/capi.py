@@ -176,6 +176,7 @@ SIGNATURES = {
     "dfot_op_attention": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "dfot_op_attention_padded": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "dfot_op_attention_seq64": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "dfot_op_attention_seq64_bwd": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _P]),
     "dfot_op_attention_temporal": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "dfot_op_attention_temporal_bwd": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "dfot_op_matrix_attention_rope": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P]),

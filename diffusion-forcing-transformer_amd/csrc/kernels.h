@@ -141,6 +141,11 @@ int launch_attention_padded(const bf16* q, const bf16* k, const bf16* v, bf16* o
 // attention_seq64.hip: launch_attention_padded's operands and output with n = 64 (sequences shorter than that launcher's 128-row tile):
 // one workgroup per (sequence, head), single-pass softmax.  d % 8 == 0, d <= 128, ldo % 8 == 0
 int launch_attention_seq64(const bf16* q, const bf16* k, const bf16* v, bf16* o, long ldo, int nseq, int heads, int d, hipStream_t stream);
+// attention_seq64_bwd.hip: backward of launch_attention_seq64, the 64 x 64 problem recomputed in one launch (no lse, no delta, no o);
+// d_o compact as that launcher's o; dq / dk / dv in the layout of q / k / v under the contract of launch_attention_bwd below (dq: gradient
+// of the UNSCALED q, dk carrying ln 2), live columns only.  The forward's shape rules
+int launch_attention_seq64_bwd(const bf16* q, const bf16* k, const bf16* v, const bf16* d_o, long ldo, bf16* dq, bf16* dk, bf16* dv, int nseq,
+                               int heads, int d, hipStream_t s);
 // attention_frame_causal.hip: launch_attention_padded's operands and output under the block-lower-triangular mask of the DiT1D backbone:
 // query i sees key j iff j / frame_len <= i / frame_len.  frame_len in {16, 32, 64, 128}, n % 128 == 0, d % 8 == 0, d <= 128, ldo % 8 == 0
 // lse (optional, training): [B][heads][N] fp32, log2-domain log-sum-exp of every query row; null launches the inference instantiation

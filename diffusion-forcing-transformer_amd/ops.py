@@ -13,6 +13,7 @@ FakeTensor tracing, ``torch.compile`` graphs and stream capture treat the HIP ke
     dfot::dit3d_forward_f_train(x, noise_levels (float), external_cond?, mask?, params[], model) -> v  [autograd: dfot_dit_train_forward_f]
     dfot::dit1d_forward(x, noise_levels, model) -> v                                                [dfot_dit1d_forward]
     dfot::frame_causal_attention(q, k, v, frame_len) -> o                    [autograd: dfot_op_attention_frame_causal_lse / _bwd]
+    dfot::attention_seq64(q, k, v) -> o                                      [autograd: dfot_op_attention_seq64 / _seq64_bwd]
     dfot::ray_encoding(raw_poses, resolution) -> cond                                               [dfot_ray_encode]
     dfot::hg_prepare(x, noise?, qa, qb, nfe) -> x_in                                                [dfot_hg_prepare]
     dfot::ddim_hg_step(x, x_in, v, sa, s1, an, cn, keep, weight, gen, nfe) -> x_next                [dfot_ddim_compose / _tokw]
@@ -279,7 +280,8 @@ def _fc_check(q: Tensor, k: Tensor, v: Tensor, frame_len: int, need_gpu: bool = 
 
 
 def _fc_pack(t: Tensor, d: int, mul: float = 1.0) -> Tensor:
-    """(B, heads, N, d) of any strides -> contiguous [B][heads][N][dstride] bf16, pad columns zero; the product with `mul` is taken in fp32"""
+    """(B, heads, N, d) of any strides -> contiguous [B][heads][N][dstride] bf16, pad columns zero; the product with `mul` is taken in fp32.
+    The pack of both attention operators (frame_causal_attention above, attention_seq64 below)"""
     ds = 64 if d <= 64 else 128
     src = t.detach().float() * mul if mul != 1.0 else t.detach()
     if ds == d:
@@ -349,6 +351,85 @@ def _fc_backward(ctx, grad_out):
 
 
 frame_causal_attention.register_autograd(_fc_backward, setup_context=_fc_setup_context)
+
+
+# ---- attention over 64-token sequences as a differentiable operator: the drop-in for the F.scaled_dot_product_attention(q, k, v) that the
+# reference's spatial DiTBlock issues per frame at 64 patches per frame (the taichi res-128 recipes) ------------------------------------
+# q, k, v (F, heads, 64, d) of one floating dtype on the GPU, F = the number of sequences (frames); o = softmax(q k^T / sqrt(d)) v in q's
+# shape and dtype, a transposed view of the kernel's compact (F, 64, heads, d) buffer.  Host plumbing as frame_causal_attention above (_fc_pack
+# serves both).  The backward kernel recomputes the 64 x 64 softmax, so the forward saves the packed q, k, v and nothing else.
+def _s64_check(q: Tensor, k: Tensor, v: Tensor, need_gpu: bool = True):
+    if q.dim() != 4 or k.shape != q.shape or v.shape != q.shape:
+        raise ValueError(f"attention_seq64: q, k, v must share one (F, heads, 64, d) shape, got {tuple(q.shape)}, {tuple(k.shape)}, "
+                         f"{tuple(v.shape)}")
+    if not q.is_floating_point() or k.dtype != q.dtype or v.dtype != q.dtype:
+        raise ValueError(f"attention_seq64: q, k, v must share one floating dtype, got {q.dtype}, {k.dtype}, {v.dtype}")
+    f, heads, n, d = q.shape
+    if n != 64:
+        raise ValueError(f"attention_seq64: N={n} must be 64")
+    if d <= 0 or d % 8 != 0 or d > 128:
+        raise ValueError(f"attention_seq64: head dim {d} must be a multiple of 8, <= 128")
+    if f <= 0 or heads <= 0:
+        raise ValueError(f"attention_seq64: sequences {f} and heads {heads} must be positive")
+    if need_gpu and not (q.is_cuda and k.is_cuda and v.is_cuda):
+        raise ValueError(f"attention_seq64: q, k, v are on {q.device}, {k.device}, {v.device}: GPU tensors only (there is no CPU path)")
+    return f, heads, d
+
+
+# what the last forward left for its backward: (packed q, k, v), handed over as _FC_SAVED is
+_S64_SAVED = None
+
+
+@custom_op("dfot::attention_seq64", mutates_args=())
+def attention_seq64(q: Tensor, k: Tensor, v: Tensor) -> Tensor:
+    global _S64_SAVED
+    f, heads, d = _s64_check(q, k, v)
+    qp, kp, vp = _fc_pack(q, d, _LOG2E / d ** 0.5), _fc_pack(k, d), _fc_pack(v, d)
+    o = torch.empty(f * 64, heads * d, dtype=torch.bfloat16, device=q.device)
+    capi.check(capi.lib.dfot_op_attention_seq64(capi.ptr(qp), capi.ptr(kp), capi.ptr(vp), capi.ptr(o), heads * d, f, heads, d, capi.stream_ptr()))
+    out = o.view(f, 64, heads, d).transpose(1, 2)
+    out = out if q.dtype == torch.bfloat16 else out.to(q.dtype)  # .to keeps the strides: still compact as (F, 64, heads, d)
+    _S64_SAVED = (out.data_ptr(), qp, kp, vp)
+    return out
+
+
+@attention_seq64.register_fake
+def _(q, k, v):
+    f, heads, d = _s64_check(q, k, v, need_gpu=False)
+    return q.new_empty((f, 64, heads, d)).transpose(1, 2)
+
+
+@custom_op("dfot::attention_seq64_backward", mutates_args=())
+def attention_seq64_backward(grad_out: Tensor, qp: Tensor, kp: Tensor, vp: Tensor, d: int) -> List[Tensor]:
+    f, heads = qp.shape[:2]
+    d_o = grad_out.detach().transpose(1, 2).to(torch.bfloat16).contiguous().view(f * 64, heads * d)
+    dq, dk, dv = (torch.empty_like(qp) for _ in range(3))
+    capi.check(capi.lib.dfot_op_attention_seq64_bwd(capi.ptr(qp), capi.ptr(kp), capi.ptr(vp), capi.ptr(d_o), heads * d, capi.ptr(dq), capi.ptr(dk),
+                                                    capi.ptr(dv), f, heads, d, capi.stream_ptr()))
+    return [t[..., :d].to(grad_out.dtype) for t in (dq, dk, dv)]
+
+
+@attention_seq64_backward.register_fake
+def _(grad_out, qp, kp, vp, d):
+    return [grad_out.new_empty((*qp.shape[:3], d)) for _ in range(3)]
+
+
+def _s64_setup_context(ctx, inputs, output):
+    global _S64_SAVED
+    saved, _S64_SAVED = _S64_SAVED, None
+    if saved is None or saved[0] != output.data_ptr():
+        raise RuntimeError("dfot::attention_seq64: the forward left no saved operands for this output (the operator is not differentiable "
+                           "under FakeTensor tracing)")
+    ctx.save_for_backward(*saved[1:])
+    ctx.d = inputs[0].shape[3]
+
+
+def _s64_backward(ctx, grad_out):
+    dq, dk, dv = torch.ops.dfot.attention_seq64_backward(grad_out, *ctx.saved_tensors, ctx.d)
+    return dq, dk, dv
+
+
+attention_seq64.register_autograd(_s64_backward, setup_context=_s64_setup_context)
 
 
 @custom_op("dfot::ray_encoding", mutates_args=())

@@ -569,6 +569,15 @@ int dfot_op_attention_padded(const void* q, const void* k, const void* v, void* 
  * and no row outside the nseq sequences is read or written (the operand buffers need no slack).  d % 8 == 0, 0 < d <= 128, nseq > 0,
  * heads > 0, ldo % 8 == 0 covering heads*d; anything else: DFOT_ERR_SHAPE (null pointers: DFOT_ERR_ARG), nothing launched */
 int dfot_op_attention_seq64(const void* q, const void* k, const void* v, void* o, int ldo, int nseq, int heads, int d, void* stream);
+/* backward of dfot_op_attention_seq64 for the upstream gradient d_o[(seq*64 + row)][head*d + c] bf16 (row stride ldo; nothing beyond a
+ * head's d columns is read) of o: dq, dk, dv in the layout of q, k, v (live columns c < d only; pad columns are not written).  One launch,
+ * one workgroup per (sequence, head): scores, the single-pass softmax and delta are recomputed from q, k, v and d_o, so nothing but the
+ * forward's operands is needed (no lse, no o).  dq is the gradient of the UNSCALED q (the factor 1/sqrt(d) is applied), dk carries
+ * ln 2 (q holds log2 e).  The bits of a sequence depend on (d, its operands) alone, and no row outside the nseq sequences is read or
+ * written.  The forward's shape rules: d % 8 == 0, 0 < d <= 128, nseq > 0, heads > 0, nseq*heads < 2^31, ldo % 8 == 0 covering heads*d;
+ * anything else: DFOT_ERR_SHAPE (null pointers: DFOT_ERR_ARG), nothing launched */
+int dfot_op_attention_seq64_bwd(const void* q, const void* k, const void* v, const void* d_o, int ldo, void* dq, void* dk, void* dv, int nseq,
+                                int heads, int d, void* stream);
 /* temporal attention of the factorized-attention DiT: q, k, v [batch*tokens][heads][patches][dstride] bf16 as above (what the per-frame
  * QKV epilogue writes; q pre-scaled); for every (video, head, patch position) the `tokens` frames of the video attend to each other.
  * o[(video, frame, patch)][heads*d] compact (row stride ldo).  1 <= tokens <= 32, d % 4 == 0, d <= 128, patches % 128 == 0, ldo a

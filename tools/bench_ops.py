@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Micro-benchmarks of the C-ABI primitives at the RE10K model shapes (model batch 2), HIP-event timed.
-Usage (GPU box): python tools/bench_ops.py [gemm] [conv] [attn] [tattn] [mattn] [tattn_bwd] [facdit_train] [mattn_bwd] [facmat_train] [vae_encode] [equal] [dit_front] [ivae] [uvit3d] [gnfilm_frame] [uvit3d_train] [attnmap] [titok] [titok_enc] [mcraft] [sattn64] [facmat_narrow] [dcae] [attn_fc] [attn_fc_bwd] [dit1d]"""
+Usage (GPU box): python tools/bench_ops.py [gemm] [conv] [attn] [tattn] [mattn] [tattn_bwd] [facdit_train] [mattn_bwd] [facmat_train] [vae_encode] [equal] [dit_front] [ivae] [uvit3d] [gnfilm_frame] [uvit3d_train] [attnmap] [titok] [titok_enc] [mcraft] [sattn64] [facmat_narrow] [dcae] [attn_fc] [attn_fc_bwd] [dit1d] [seq64_bwd]"""
 import ctypes as C
 import math
 import os
@@ -256,6 +256,30 @@ def attn_fc_bwd(b, heads, n, frame_len, d, rounds=7):
                                                                                P(dk), P(dv), b, heads, n, d, S())),
                          iters=50, warm=5))
     return fc, nc
+
+
+def seq64_bwd(nseq, heads, d, rounds=7):
+    """the 64-token attention backward (dfot_op_attention_seq64_bwd, one launch) next to its forward (dfot_op_attention_seq64) on the same
+    unit-normal operands and next to a device copy that moves the bytes the backward moves (4 reads + 3 writes of 64 x dstride bf16 per
+    (sequence, head): a copy of 3.5 such tiles reads and writes as much), alternated over `rounds` rounds in one process:
+    ([ms backward], [ms forward], [ms copy], bytes moved)"""
+    ds = 64 if d <= 64 else 128
+    q, k, v = (torch.zeros(nseq, heads, 64, ds, device="cuda", dtype=torch.bfloat16) for _ in range(3))
+    for t, mul in ((q, math.log2(math.e) / math.sqrt(d)), (k, 1.0), (v, 1.0)):
+        t[..., :d] = (torch.randn(nseq, heads, 64, d, device="cuda") * mul).bfloat16()
+    d_o = torch.randn(nseq * 64, heads * d, device="cuda").bfloat16()
+    o = torch.empty_like(d_o)
+    dq, dk, dv = (torch.empty_like(q) for _ in range(3))
+    nbytes = 7 * nseq * heads * 64 * ds * 2
+    src = torch.randn(nbytes // 4, device="cuda").bfloat16()  # nbytes / 2 bytes read + nbytes / 2 written
+    dst = torch.empty_like(src)
+    bwd, fwd, cp = [], [], []
+    for _ in range(rounds):
+        bwd.append(timeit(lambda: capi.check(capi.lib.dfot_op_attention_seq64_bwd(P(q), P(k), P(v), P(d_o), heads * d, P(dq), P(dk), P(dv), nseq, heads,
+                                                                                  d, S())), iters=100, warm=10))
+        fwd.append(timeit(lambda: capi.check(capi.lib.dfot_op_attention_seq64(P(q), P(k), P(v), P(o), heads * d, nseq, heads, d, S())), iters=100, warm=10))
+        cp.append(timeit(lambda: dst.copy_(src), iters=100, warm=10))
+    return bwd, fwd, cp, nbytes
 
 
 def dit1d_forward(b, rounds=5):
@@ -902,6 +926,14 @@ def main():
                   f"non-causal {med(nc)*1e3:8.1f} us (min {min(nc)*1e3:.1f}, max {max(nc)*1e3:.1f})  frame-causal / non-causal "
                   f"{med(fc) / med(nc):.2f}  ({tiles * (tiles + 2) // 4} of {tiles * tiles // 2} (128-row block, 64-row tile) pairs streamed per "
                   f"kernel; {len(fc)} alternated rounds)", flush=True)
+    if "seq64_bwd" in what:
+        med = lambda r: sorted(r)[len(r) // 2]  # noqa: E731
+        # @FacDiT/S at res-128 (6 heads, d 64), 16 videos x 16 frames = 256 sequences of 64 patches; d 72 and d 128 at the same sequence count
+        for d in (64, 72, 128):
+            bwd, fwd, cp, nbytes = seq64_bwd(256, 6, d)
+            print(f"seq64_bwd 256 sequences H=6 d={d}: backward median {med(bwd)*1e3:7.1f} us (min {min(bwd)*1e3:.1f})  forward {med(fwd)*1e3:7.1f} us "
+                  f"(min {min(fwd)*1e3:.1f})  copy of {nbytes / 1e6:.1f} MB moved {med(cp)*1e3:7.1f} us (min {min(cp)*1e3:.1f})  backward / forward "
+                  f"{med(bwd) / med(fwd):.2f}  backward / copy {med(bwd) / med(cp):.2f}  ({len(bwd)} alternated rounds)", flush=True)
     if "dit1d" in what:
         ms = dit1d_forward(16)
         for name, r in ms.items():
