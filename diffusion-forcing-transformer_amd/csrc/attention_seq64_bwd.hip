@@ -32,6 +32,9 @@
 // There is no tail case: the grid is exactly nseq * heads workgroups, and the operand buffers need no slack behind the last sequence.
 // The summation order is fixed by (D, DQK, DV), i.e. by d alone: a sequence's bits do not depend on the launch it is part of.  No
 // atomics, no allocation, no synchronisation with the host.
+//
+// Two forms of the final store (template parameter PACKED, see the kernel): dq, dk, dv as three buffers in the layout of q, k, v, or all
+// three straight into the rows of the packed dqkv [rows][3*heads*d] the weight-gradient GEMMs read (launch_attention_seq64_bwd_packed).
 #include "common.h"
 #include "dfot_hip.h"
 #include "kernels.h"
@@ -97,11 +100,16 @@ __device__ __forceinline__ void seq64_store_row(const f32x16 (&acc)[DV / 32], fl
 
 // D: row stride of q / k / v (64 or 128); DQK: head-dim columns contracted in S and dP (multiple of 16 covering d); DV: head-dim columns
 // that are outputs of dQ, dK, dV (multiple of 32 covering d, >= DQK) -- the pad columns d..DV of q, k, v hold zeros; d: live columns
-template <int D, int DQK, int DV>
+// PACKED: the second form of the store.  The products, their order and the roundings are those of the first form; only the address of a
+// lane's row changes: row seq*64 + r of ONE buffer dQ [nseq*64][ldg] (dK, dV unused), dq at column head*d, dk at heads*d + head*d, dv at
+// 2*heads*d + head*d -- the layout qkv_grad_pack_kernel (no RoPE) copies the first form's three buffers into, so that copy and its
+// launch drop out of a spatial block's backward.  Still 16-byte stores of live columns only: with d % 8 == 0 and ldg % 8 == 0 every one
+// is aligned, inside the workgroup's own 64 rows and below column 3*heads*d <= ldg.
+template <int D, int DQK, int DV, bool PACKED>
 __global__ __launch_bounds__(256) void attn_seq64_bwd_kernel(const bf16* __restrict__ Q, const bf16* __restrict__ K,
                                                              const bf16* __restrict__ V, const bf16* __restrict__ dO, long ldo,
-                                                             bf16* __restrict__ dQ, bf16* __restrict__ dK, bf16* __restrict__ dV, int heads,
-                                                             int d, float sq, float sk_scale) {
+                                                             bf16* __restrict__ dQ, bf16* __restrict__ dK, bf16* __restrict__ dV, long ldg,
+                                                             int heads, int d, float sq, float sk_scale) {
   static_assert(DQK % 16 == 0 && DV % 32 == 0 && DQK <= DV && DV <= D, "head-dim sub-range");
   using C = Seq64BwdCfg<D>;
   constexpr int CH = DV / 8;          // staged 16-byte chunks per row
@@ -146,6 +154,12 @@ __global__ __launch_bounds__(256) void attn_seq64_bwd_kernel(const bf16* __restr
   // row t2*32 + 8g + 4lh + j ----
   const bool qrole = wave < 2;  // wave-uniform
   const int own0 = (wave & 1) * 32;
+  // this lane's output row of dq / dk / dv
+  const long cdim = (long)heads * d;
+  const long orow = PACKED ? ((long)(bh / heads) * 64 + own0 + lq) * ldg + (long)(bh % heads) * d : base + (long)(own0 + lq) * D;
+  bf16* const dq_row = dQ + orow;
+  bf16* const dk_row = PACKED ? dQ + orow + cdim : dK + orow;
+  bf16* const dv_row = PACKED ? dQ + orow + 2 * cdim : dV + orow;
   const char* s_own = qrole ? sq_ : sk;
   const char* p_own = qrole ? so : sv;
   const char* s_oth = qrole ? sk : sq_;
@@ -221,7 +235,7 @@ __global__ __launch_bounds__(256) void attn_seq64_bwd_kernel(const bf16* __restr
         for (int s = 0; s < 2; ++s)
           acc[dvt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(seq64_tr_frag<D>(sk, dvt * 32, t2, s, lane), dsf[t2][s], acc[dvt], 0, 0, 0);
     }
-    seq64_store_row<DV>(acc, sq, dQ + base + (long)(own0 + lq) * D, lh, d);
+    seq64_store_row<DV>(acc, sq, dq_row, lh, d);
   } else {
     // P and dS of key own0 + lq from the statistics of the registers' query rows: four rows per 16-byte read
     bf16x8 pf[2][2];
@@ -254,20 +268,32 @@ __global__ __launch_bounds__(256) void attn_seq64_bwd_kernel(const bf16* __restr
           dka[dvt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(seq64_tr_frag<D>(sq_, dvt * 32, t2, s, lane), dsf[t2][s], dka[dvt], 0, 0, 0);
         }
     }
-    seq64_store_row<DV>(dva, 1.0f, dV + base + (long)(own0 + lq) * D, lh, d);
-    seq64_store_row<DV>(dka, sk_scale, dK + base + (long)(own0 + lq) * D, lh, d);
+    seq64_store_row<DV>(dva, 1.0f, dv_row, lh, d);
+    seq64_store_row<DV>(dka, sk_scale, dk_row, lh, d);
   }
 }
 
-template <int D, int DQK, int DV>
-int launch_seq64_bwd(const bf16* q, const bf16* k, const bf16* v, const bf16* d_o, long ldo, bf16* dq, bf16* dk, bf16* dv, int nseq, int heads,
-                     int d, hipStream_t s) {
+template <int D, int DQK, int DV, bool PACKED>
+int launch_seq64_bwd(const bf16* q, const bf16* k, const bf16* v, const bf16* d_o, long ldo, bf16* dq, bf16* dk, bf16* dv, long ldg, int nseq,
+                     int heads, int d, hipStream_t s) {
   constexpr int lds = Seq64BwdCfg<D>::LDS;  // 35.6 KB at D = 64, 68.8 KB at D = 128: four / two workgroups per CU
-  if (int rc = ensure_dyn_lds<attn_seq64_bwd_kernel<D, DQK, DV>>(lds)) return rc;
+  if (int rc = ensure_dyn_lds<attn_seq64_bwd_kernel<D, DQK, DV, PACKED>>(lds)) return rc;
   const float sq = 1.0f / sqrtf((float)d), sk = 0.6931471805599453f;  // as launch_attention_bwd
-  hipLaunchKernelGGL((attn_seq64_bwd_kernel<D, DQK, DV>), dim3(nseq * heads), dim3(256), lds, s, q, k, v, d_o, ldo, dq, dk, dv, heads, d, sq, sk);
+  hipLaunchKernelGGL((attn_seq64_bwd_kernel<D, DQK, DV, PACKED>), dim3(nseq * heads), dim3(256), lds, s, q, k, v, d_o, ldo, dq, dk, dv, ldg, heads,
+                     d, sq, sk);
   DFOT_CHECK_HIP(hipGetLastError());
   return DFOT_OK;
+}
+
+// the instantiation of a head dim: (D, DQK, DV) depend on d alone, in both forms
+template <bool PACKED>
+int dispatch_seq64_bwd(const bf16* q, const bf16* k, const bf16* v, const bf16* d_o, long ldo, bf16* dq, bf16* dk, bf16* dv, long ldg, int nseq,
+                       int heads, int d, hipStream_t s) {
+  if (d <= 32) return launch_seq64_bwd<64, 32, 32, PACKED>(q, k, v, d_o, ldo, dq, dk, dv, ldg, nseq, heads, d, s);
+  if (d <= 64) return launch_seq64_bwd<64, 64, 64, PACKED>(q, k, v, d_o, ldo, dq, dk, dv, ldg, nseq, heads, d, s);
+  if (d <= 80) return launch_seq64_bwd<128, 80, 96, PACKED>(q, k, v, d_o, ldo, dq, dk, dv, ldg, nseq, heads, d, s);
+  if (d <= 96) return launch_seq64_bwd<128, 96, 96, PACKED>(q, k, v, d_o, ldo, dq, dk, dv, ldg, nseq, heads, d, s);
+  return launch_seq64_bwd<128, 128, 128, PACKED>(q, k, v, d_o, ldo, dq, dk, dv, ldg, nseq, heads, d, s);
 }
 
 }  // namespace
@@ -281,11 +307,22 @@ int launch_attention_seq64_bwd(const bf16* q, const bf16* k, const bf16* v, cons
                heads);
   DFOT_REQUIRE(ldo >= (long)heads * d && ldo % 8 == 0, DFOT_ERR_SHAPE,
                "attention_seq64_bwd: d_o row stride %ld must cover %d columns and be a multiple of 8 (16-byte loads)", ldo, heads * d);
-  if (d <= 32) return launch_seq64_bwd<64, 32, 32>(q, k, v, d_o, ldo, dq, dk, dv, nseq, heads, d, s);
-  if (d <= 64) return launch_seq64_bwd<64, 64, 64>(q, k, v, d_o, ldo, dq, dk, dv, nseq, heads, d, s);
-  if (d <= 80) return launch_seq64_bwd<128, 80, 96>(q, k, v, d_o, ldo, dq, dk, dv, nseq, heads, d, s);
-  if (d <= 96) return launch_seq64_bwd<128, 96, 96>(q, k, v, d_o, ldo, dq, dk, dv, nseq, heads, d, s);
-  return launch_seq64_bwd<128, 128, 128>(q, k, v, d_o, ldo, dq, dk, dv, nseq, heads, d, s);
+  return dispatch_seq64_bwd<false>(q, k, v, d_o, ldo, dq, dk, dv, 0, nseq, heads, d, s);
+}
+
+// q, k, v, d_o as above; dqkv [nseq*64][ldg]: row seq*64 + r holds dq | dk | dv of that token, head-major, in its first 3*heads*d columns
+// (what launch_qkv_grad_pack without a rope table makes of the three buffers above); columns beyond them are not written
+int launch_attention_seq64_bwd_packed(const bf16* q, const bf16* k, const bf16* v, const bf16* d_o, long ldo, bf16* dqkv, long ldg, int nseq,
+                                      int heads, int d, hipStream_t s) {
+  DFOT_REQUIRE(q && k && v && d_o && dqkv, DFOT_ERR_ARG, "attention_seq64_bwd_packed: null pointer");
+  DFOT_REQUIRE(d > 0 && d <= 128 && d % 8 == 0, DFOT_ERR_SHAPE, "attention_seq64_bwd_packed: head dim %d must be a multiple of 8, <= 128", d);
+  DFOT_REQUIRE(nseq > 0 && heads > 0 && (long)nseq * heads <= 0x7fffffffL, DFOT_ERR_SHAPE, "attention_seq64_bwd_packed: %d sequences, %d heads",
+               nseq, heads);
+  DFOT_REQUIRE(ldo >= (long)heads * d && ldo % 8 == 0, DFOT_ERR_SHAPE,
+               "attention_seq64_bwd_packed: d_o row stride %ld must cover %d columns and be a multiple of 8 (16-byte loads)", ldo, heads * d);
+  DFOT_REQUIRE(ldg >= 3L * heads * d && ldg % 8 == 0, DFOT_ERR_SHAPE,
+               "attention_seq64_bwd_packed: dqkv row stride %ld must cover 3 x %d columns and be a multiple of 8 (16-byte stores)", ldg, heads * d);
+  return dispatch_seq64_bwd<true>(q, k, v, d_o, ldo, dqkv, nullptr, nullptr, ldg, nseq, heads, d, s);
 }
 
 }  // namespace dfot
@@ -295,4 +332,11 @@ extern "C" int dfot_op_attention_seq64_bwd(const void* q, const void* k, const v
   using namespace dfot;
   return launch_attention_seq64_bwd((const bf16*)q, (const bf16*)k, (const bf16*)v, (const bf16*)d_o, ldo, (bf16*)dq, (bf16*)dk, (bf16*)dv, nseq,
                                     heads, d, (hipStream_t)stream);
+}
+
+extern "C" int dfot_op_attention_seq64_bwd_packed(const void* q, const void* k, const void* v, const void* d_o, int ldo, void* dqkv, int ldg,
+                                                  int nseq, int heads, int d, void* stream) {
+  using namespace dfot;
+  return launch_attention_seq64_bwd_packed((const bf16*)q, (const bf16*)k, (const bf16*)v, (const bf16*)d_o, ldo, (bf16*)dqkv, ldg, nseq, heads, d,
+                                           (hipStream_t)stream);
 }

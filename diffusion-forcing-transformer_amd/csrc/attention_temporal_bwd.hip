@@ -217,7 +217,8 @@ int launch_attention_temporal_bwd(const bf16* q, const bf16* k, const bf16* v, c
                batch, heads);
   DFOT_REQUIRE(tokens >= 1 && tokens <= 32, DFOT_ERR_SHAPE, "temporal attention backward: %d frames (1 to 32 are supported)", tokens);
   DFOT_REQUIRE(d > 0 && d % 8 == 0 && d <= 128, DFOT_ERR_SHAPE, "temporal attention backward: head dim %d must be a multiple of 8, <= 128", d);
-  DFOT_REQUIRE(patches > 0 && patches % 128 == 0, DFOT_ERR_SHAPE, "temporal attention backward: %d patches per frame must be a multiple of 128",
+  // (the grid is patches / pb with pb a power of two <= 32)
+  DFOT_REQUIRE(patches > 0 && patches % 64 == 0, DFOT_ERR_SHAPE, "temporal attention backward: %d patches per frame must be a multiple of 64",
                patches);
   DFOT_REQUIRE(ldo >= (long)heads * d && ldo % 8 == 0, DFOT_ERR_SHAPE,
                "temporal attention backward: ldo %ld must cover %d columns and be a multiple of 8", ldo, heads * d);
@@ -251,6 +252,18 @@ int launch_attention_temporal_bwd(const bf16* q, const bf16* k, const bf16* v, c
 extern "C" int dfot_op_attention_temporal_bwd(const void* q, const void* k, const void* v, const void* d_o, int ldo, void* dq, void* dk,
                                               void* dv, int batch, int tokens, int patches, int heads, int d, void* stream) {
   using namespace dfot;
+  // the op keeps its documented contract (dfot_hip.h); the launcher itself also takes the engine's 64-patch frames
+  DFOT_REQUIRE(patches > 0 && patches % 128 == 0, DFOT_ERR_SHAPE, "temporal attention backward: %d patches per frame must be a multiple of 128",
+               patches);
   return launch_attention_temporal_bwd((const bf16*)q, (const bf16*)k, (const bf16*)v, (const bf16*)d_o, ldo, (bf16*)dq, (bf16*)dk, (bf16*)dv,
                                        batch, tokens, patches, heads, d, (hipStream_t)stream);
+}
+
+// the same launcher at 64 patches per frame, the shape the FacDiT trainer runs it at for the res-128 recipes; any 1 <= tokens <= 32 (that
+// a training window is a whole number of 128-row tiles is the engine's rule, not this kernel's)
+extern "C" int dfot_op_attention_temporal_bwd_p64(const void* q, const void* k, const void* v, const void* d_o, int ldo, void* dq, void* dk,
+                                                  void* dv, int batch, int tokens, int heads, int d, void* stream) {
+  using namespace dfot;
+  return launch_attention_temporal_bwd((const bf16*)q, (const bf16*)k, (const bf16*)v, (const bf16*)d_o, ldo, (bf16*)dq, (bf16*)dk, (bf16*)dv,
+                                       batch, tokens, 64, heads, d, (hipStream_t)stream);
 }

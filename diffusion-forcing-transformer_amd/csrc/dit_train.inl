@@ -835,6 +835,13 @@ struct dfot_dit_train_s : dfot::DitGeom {  // the geometry of cfg (dit_model.h):
   float *fz_freqs = nullptr, *fz_phases = nullptr;
   bool fz_loaded[2] = {false, false};
   bool synced = false;
+  // variant 2 at exactly 64 patches per frame, set once at create: the spatial blocks' sequences are single 64-token frames, so they run
+  // attention_seq64.hip forward and its backward, and keep no lse.  The ONE predicate reserve, forward and backward choose those kernels
+  // by (variant 0 at 64 patches has whole-video sequences, n % 128 == 0, and keeps launch_attention_padded with its lse)
+  bool seq64 = false;
+  // seq64: the spatial blocks' attention backward stores dq | dk | dv straight into dqkv (attention_seq64_bwd.hip, PACKED);
+  // false: the three-buffer form + launch_qkv_grad_pack, the same bits (dfot_facdit_train_set_seq64_packed, for A/B timing)
+  bool seq64_packed = true;
   // workspace
   int max_batch = 0, fp = 0, batch = 0, tokens = 0;
   int* idx = nullptr;
@@ -1014,8 +1021,19 @@ static int dit_train_create_impl(const DitCfg& c, dfot_dit_train_t* out, int ent
   static_cast<DitGeom&>(*h) = dit_geometry(c);
   h->ocp = (h->oc + 63) / 64 * 64;
   const int hd = c.hidden_size, E = c.embed_col_dim, P = h->P;
-  if (h->P % TR_CHUNKS != 0 || ((facmat || fac) && h->P % 128 != 0)) {
-    set_error("train_create: %d patches per frame must be a multiple of %d", h->P, facmat || fac ? 128 : TR_CHUNKS);
+  // variant 2 also trains at exactly 64 patches per frame (the res-128 recipes: attention_seq64.hip and its backward run the per-frame
+  // sequences) when max_tokens is even, so that a full window is a whole number of the GEMMs' 128-row tiles
+  h->seq64 = fac && h->P == 64;
+  const bool p64 = h->seq64;
+  if (p64 && c.max_tokens % 2 != 0) {
+    set_error("train_create: 64 patches per frame need an even max_tokens (max_tokens %d x 64 = %d rows per window; the row tiles need a "
+              "multiple of 128)", c.max_tokens, c.max_tokens * 64);
+    delete h;
+    return DFOT_ERR_SHAPE;
+  }
+  if (h->P % TR_CHUNKS != 0 || ((facmat || fac) && h->P % 128 != 0 && !p64)) {
+    set_error(fac ? "train_create: %d patches per frame must be a multiple of %d (or exactly 64 with an even max_tokens)"
+                  : "train_create: %d patches per frame must be a multiple of %d", h->P, facmat || fac ? 128 : TR_CHUNKS);
     delete h;
     return DFOT_ERR_ARG;
   }
@@ -1140,6 +1158,14 @@ int dfot_facdit_train_create(const dfot_dit_config_f* cfg, dfot_dit_train_t* out
   return dit_train_create_impl(dit_cfg(cfg->base), out, 2);
 }
 
+// A measurement hook, not a supported option: which form of the 64-token attention backward the spatial blocks call at 64 patches.  1 (the default): one launch storing
+// into the packed dqkv; 0: the three-buffer form + the pack kernel.  Both give the same gradient bits; tools/bench_ops.py times both
+int dfot_facdit_train_set_seq64_packed(dfot_dit_train_t h, int packed) {
+  DFOT_REQUIRE(h && h->cfg.variant == 2, DFOT_ERR_ARG, "facdit_train_set_seq64_packed: not a variant 2 training handle");
+  h->seq64_packed = packed != 0;
+  return DFOT_OK;
+}
+
 int dfot_dit_train_num_params(dfot_dit_train_t h) { return h ? (int)h->params.size() : 0; }
 const char* dfot_dit_train_param_name(dfot_dit_train_t h, int i) {
   return (h && i >= 0 && i < (int)h->params.size()) ? h->params[i].name.c_str() : nullptr;
@@ -1249,7 +1275,7 @@ int dfot_dit_train_reserve(dfot_dit_train_t h, int max_batch) {
     WS(b.x_in, rows * hd); WS(b.m, rows * hd); WS(b.a, rows * hd);
     if (!b.matrix) {
       WS(b.q, qsz); WS(b.k, qsz); WS(b.v, qsz); WS(b.o, rows * hd);
-      if (!b.temporal) { WS(b.lse, bhn); }  // the temporal backward recomputes its T x T problem
+      if (!b.temporal && !h->seq64) { WS(b.lse, bhn); }  // the temporal and the 64-token backward recompute their whole problem
     } else {
       WS(b.w1, fe * hd); WS(b.z, fe * 3 * hd); WS(b.o2, fe * hd); WS(b.sfac, rows * hd);
     }
@@ -1380,6 +1406,8 @@ static int dit_train_forward_impl(dfot_dit_train_t h, const float* x, const int3
       if ((rc = launch_gemm(A_DENSE, E_QKV_DIT, GEMM_AUTO, g, s))) return rc;
       if (b.temporal)  // over the frames of every patch position, on the operands of the per-frame layout
         rc = launch_attention_temporal(b.q, b.k, b.v, b.o, hd, batch, tokens, P, c.num_heads, h->d, s);
+      else if (h->seq64)  // 64 patches per frame (variant 2): one 64 x 64 tile per (frame, head); no lse, the backward recomputes it
+        rc = launch_attention_seq64(b.q, b.k, b.v, b.o, hd, nseq, c.num_heads, h->d, s);
       else
         rc = launch_attention_padded(b.q, b.k, b.v, b.o, hd, nseq, c.num_heads, seq, h->d, s, b.lse);
       if (rc) return rc;
@@ -1523,14 +1551,20 @@ int dfot_dit_train_backward(dfot_dit_train_t h, const float* d_out, void* stream
       if ((rc = gate_bwd(b.a, b.mod + 2 * hd, G + b.o_proj_b))) return rc;
       if ((rc = tr_gemm_bf16(h->da, hd, b.w_projT, (int)rows, hd, hd, nullptr, h->dO, hd, s))) return rc;      // dO = da Wp
       if ((rc = wgrad(h->da, hd, b.o, hd, rows, G + b.o_proj_w))) return rc;  // dWp = da^T o
+      bool packed = false;  // dqkv already written by the attention backward
       if (b.temporal) {  // one launch, no lse / delta: dq, dk, dv in the per-frame layout the pack kernel reads
         if ((rc = launch_attention_temporal_bwd(b.q, b.k, b.v, h->dO, hd, h->dq, h->dk, h->dv, batch, tokens, P, c.num_heads, h->d, s))) return rc;
+      } else if (h->seq64 && h->seq64_packed) {  // one launch, no lse / delta, and (no RoPE here) straight into the rows of dqkv
+        if ((rc = launch_attention_seq64_bwd_packed(b.q, b.k, b.v, h->dO, hd, h->dqkv, 3L * hd, nseq, c.num_heads, h->d, s))) return rc;
+        packed = true;
+      } else if (h->seq64) {
+        if ((rc = launch_attention_seq64_bwd(b.q, b.k, b.v, h->dO, hd, h->dq, h->dk, h->dv, nseq, c.num_heads, h->d, s))) return rc;
       } else {
         if ((rc = launch_attention_bwd_delta(b.o, h->dO, hd, h->delta, nseq, c.num_heads, seq, h->d, s))) return rc;
         if ((rc = launch_attention_bwd(b.q, b.k, b.v, h->dO, hd, b.lse, h->delta, h->dq, h->dk, h->dv, nseq, c.num_heads, seq, h->d, s))) return rc;
       }
-      if ((rc = launch_qkv_grad_pack(h->dq, h->dk, h->dv, facmat || fac ? (const float*)nullptr : h->rope_cs, h->dqkv, rows, seq, c.num_heads, h->d,
-                                     h->dstride, s)))
+      if (!packed && (rc = launch_qkv_grad_pack(h->dq, h->dk, h->dv, facmat || fac ? (const float*)nullptr : h->rope_cs, h->dqkv, rows, seq,
+                                                c.num_heads, h->d, h->dstride, s)))
         return rc;
       if ((rc = launch_colsum_bf16(h->dqkv, G + b.o_qkv_b, rows, 3 * hd, (long)3 * hd, s))) return rc;
       if ((rc = tr_gemm_f32(h->dqkv, 3 * hd, b.w_qkvT, (int)rows, hd, 3 * hd, dY, hd, dY, s))) return rc;       // dm = dY + dqkv Wqkv (in place)

@@ -146,6 +146,10 @@ int launch_attention_seq64(const bf16* q, const bf16* k, const bf16* v, bf16* o,
 // of the UNSCALED q, dk carrying ln 2), live columns only.  The forward's shape rules
 int launch_attention_seq64_bwd(const bf16* q, const bf16* k, const bf16* v, const bf16* d_o, long ldo, bf16* dq, bf16* dk, bf16* dv, int nseq,
                                int heads, int d, hipStream_t s);
+// the same kernel storing straight into the packed layout launch_qkv_grad_pack (no rope table) would give: row seq*64 + r of
+// dqkv [nseq*64][ldg], dq at column head*d, dk at heads*d + head*d, dv at 2*heads*d + head*d; the same bits.  ldg >= 3*heads*d, ldg % 8 == 0
+int launch_attention_seq64_bwd_packed(const bf16* q, const bf16* k, const bf16* v, const bf16* d_o, long ldo, bf16* dqkv, long ldg, int nseq,
+                                      int heads, int d, hipStream_t s);
 // attention_frame_causal.hip: launch_attention_padded's operands and output under the block-lower-triangular mask of the DiT1D backbone:
 // query i sees key j iff j / frame_len <= i / frame_len.  frame_len in {16, 32, 64, 128}, n % 128 == 0, d % 8 == 0, d <= 128, ldo % 8 == 0
 // lse (optional, training): [B][heads][N] fp32, log2-domain log-sum-exp of every query row; null launches the inference instantiation
@@ -157,7 +161,7 @@ int launch_attention_temporal(const bf16* q, const bf16* k, const bf16* v, bf16*
                               int d, hipStream_t s);
 // attention_temporal_bwd.hip: backward of launch_attention_temporal, the T x T problem recomputed (no lse, no delta); d_o compact
 // [(video, frame, patch)][ldo]; dq / dk / dv in the layout of q / k / v under the contract of launch_attention_bwd below (dq: gradient of
-// the UNSCALED q), live columns only.  The forward's shape rules with d % 8 == 0
+// the UNSCALED q), live columns only.  The forward's shape rules (patches % 64 == 0) with d % 8 == 0
 int launch_attention_temporal_bwd(const bf16* q, const bf16* k, const bf16* v, const bf16* d_o, long ldo, bf16* dq, bf16* dk, bf16* dv,
                                   int batch, int tokens, int patches, int heads, int d, hipStream_t s);
 // attention_matrix.hip: MatrixAttention core of the FacMatDiT backbone; z [batch*L*E][3h] (q|k|v), o [batch*L*E][h], one problem per

@@ -321,9 +321,19 @@ class FacDiTTrainer(DiT3DTrainer):
     """Trainer of the FacDiT backbone: ``name: dit3d`` with ``variant: factorized_attention``, ``pos_emb_type: sinusoidal_factorized``
     (dit3d_factorized_attention.yaml + the @FacDiT shortcuts; the reference's bash/taichikl train_dfot_facdit-* recipes).  Same constructor
     keywords and methods as DiT3DTrainer; ``spatial_mlp_ratio`` is the spatial blocks' MLP (0 / None: none), ``mlp_ratio`` the temporal
-    blocks'; ``use_gradient_checkpointing`` is ignored (the engine keeps every activation its backward needs).  Any 1 <= T <= max_tokens <= 32
-    trains, with the first T rows of the temporal table.  The temporal attention and its backward run over the frames of every patch
-    position (csrc/attention_temporal.hip, csrc/attention_temporal_bwd.hip).  Discrete diffusion only; patches per frame a multiple of 128."""
+    blocks'; ``use_gradient_checkpointing`` is ignored (the engine keeps every activation its backward needs).  At a multiple of 128 patches
+    per frame any 1 <= T <= max_tokens <= 32 trains, with the first T rows of the temporal table.  Exactly 64 patches per frame (latents
+    4x16x16 at patch 2, the taichi res-128 recipes) train when the constructor gets ``allow_p64=True``; without the keyword the shape is
+    refused in the words it always was, so nothing that relied on the refusal changes.  max_tokens and T must then be even, so that a
+    window is a whole number of 128-row tiles; the spatial blocks run the 64-token attention and its backward (csrc/attention_seq64.hip, csrc/attention_seq64_bwd.hip, which stores
+    dq | dk | dv straight into the packed gradient rows).  The temporal attention and its backward run over the frames of every patch
+    position (csrc/attention_temporal.hip, csrc/attention_temporal_bwd.hip).  Discrete diffusion only."""
+
+    allow_p64 = False  # the constructor keyword; a class default, so that _configure also runs on an instance __init__ has not seen
+
+    def __init__(self, *args, allow_p64: bool = False, **kwargs):
+        self.allow_p64 = bool(allow_p64)
+        super().__init__(*args, **kwargs)
 
     def _configure(self, c: "capi.DiTConfigF", cfg, max_tokens: int) -> None:
         from .dit_backbone import configure_fac
@@ -334,7 +344,27 @@ class FacDiTTrainer(DiT3DTrainer):
                              "factorized-matrix DiT3D)")
         if _get(cfg, "use_fourier_noise_embedding", False):
             raise ValueError("use_fourier_noise_embedding=True is not supported by FacDiTTrainer: it trains under discrete diffusion only")
-        configure_fac(c, cfg, max_tokens)  # refuses the patch count and max_tokens by name, as DiT3D does
+        try:
+            configure_fac(c, cfg, max_tokens, allow_p64=self.allow_p64)  # refuses the patch count and max_tokens by name, as DiT3D does
+        except ValueError as err:
+            if self.allow_p64 or max_tokens % 2 or (c.height // c.patch_size) * (c.width // c.patch_size) != 64:
+                raise
+            # the refusal in the words it always had, then the way on: this shape is the one the keyword switches on
+            raise ValueError(f"{err} by default: FacDiTTrainer(..., allow_p64=True) trains them (even max_tokens, even T)") from None
 
     def _create(self, c: "capi.DiTConfigF") -> None:
         capi.check(capi.lib.dfot_facdit_train_create(C.byref(c), C.byref(self._handle)))
+
+    def _check_tokens(self, t: int) -> None:
+        c = self._ccfg
+        if (c.height // c.patch_size) * (c.width // c.patch_size) == 64 and t % 2:
+            raise ValueError(f"FacDiTTrainer at 64 patches per frame takes an even number of tokens: {t} tokens × 64 patches = {t * 64} rows; "
+                             "the row tiles need a multiple of 128")
+
+    def forward(self, x, noise_levels, cond=None, cond_mask=None):
+        self._check_tokens(int(x.shape[1]))
+        return super().forward(x, noise_levels, cond, cond_mask)
+
+    def loss_and_grads(self, xs, k, noise, masks=None, conditions=None, dropout_generator=None):
+        self._check_tokens(int(xs.shape[1]))  # before the noising kernels, not only before the forward
+        return super().loss_and_grads(xs, k, noise, masks, conditions, dropout_generator)

@@ -204,8 +204,8 @@ typedef struct {
    *   temporal DiTBlock (MLP temporal_mlp_hidden, 0 = none) whose attention runs over the T frames of one patch position; the 2-D
    *   sinusoidal table is added at the patch embedding, the 1-D temporal table [max_tokens][hidden] after spatial block 0.
    *   Uses hidden_size, num_heads, mlp_hidden, temporal_mlp_hidden; (H/p)*(W/p) % 128 == 0, or == 64 with an even max_tokens
-   *   (inference only: the per-frame attention is then dfot_op_attention_seq64's kernel); max_tokens <= 32.  Trained through
-   *   dfot_facdit_train_create; dfot_dit_train_create[_f] refuse it.
+   *   (the per-frame attention is then dfot_op_attention_seq64's kernel, in training its backward dfot_op_attention_seq64_bwd[_packed]);
+   *   max_tokens <= 32.  Trained through dfot_facdit_train_create; dfot_dit_train_create[_f] refuse it.
    * variant 3: DiT3D "factorized_matrix_attention" + sinusoidal_2d (FacMatDiT: configurations/algorithm/backbone/
    *   dit3d_factorized_matrix.yaml + shortcut/FacMatDiT): the block sequence and parameters of variant 1 without the difference front
    *   end -- no diff_embedder, the conditioning depends on the noise level only, max_tokens is the caller's (<= 32, odd counts
@@ -423,8 +423,16 @@ int dfot_facmat_train_create(const dfot_dit_config_f* cfg, dfot_dit_train_t* out
  * registration order (all spatial blocks, then all temporal blocks), executed spatial i, temporal i; any 1 <= T <= max_tokens <= 32 (the
  * first T rows of the temporal sinusoidal table, which is built at create time and is not a parameter); (H/p)*(W/p) % 128 == 0, MLP
  * widths multiples of 128, head dim a multiple of 8; actions / labels through dfot_dit_train_forward_cond.  dfot_dit_train_create[_f]
- * keep refusing variant 2 and name this function. */
+ * keep refusing variant 2 and name this function.
+ * (H/p)*(W/p) == 64 (the taichi res-128 recipes) also trains when max_tokens is even (an odd one: DFOT_ERR_SHAPE), with even T only: the
+ * forward refuses T x 64 rows that are no multiple of 128 with DFOT_ERR_SHAPE before it launches anything.  The spatial blocks then run
+ * dfot_op_attention_seq64's kernel and, backward, dfot_op_attention_seq64_bwd_packed's (nothing but q, k, v is kept for it). */
 int dfot_facdit_train_create(const dfot_dit_config_f* cfg, dfot_dit_train_t* out);
+/* MEASUREMENT HOOK, not a supported option (it exists so that tools/bench_ops.py can time both forms on one handle, and may go once the
+ * three-buffer form is no longer worth comparing).  A variant 2 handle at 64 patches per frame: packed != 0 (the default) runs the spatial blocks' attention backward as ONE launch that
+ * stores dq | dk | dv into the packed gradient rows; 0 runs dfot_op_attention_seq64_bwd's form followed by the pack kernel.  The gradient
+ * bits are the same; the switch exists so that the two forms can be timed in one process.  No effect at other patch counts. */
+int dfot_facdit_train_set_seq64_packed(dfot_dit_train_t h, int packed);
 int dfot_dit_train_destroy(dfot_dit_train_t h);
 int dfot_dit_train_num_params(dfot_dit_train_t h);
 const char* dfot_dit_train_param_name(dfot_dit_train_t h, int i);
@@ -578,6 +586,13 @@ int dfot_op_attention_seq64(const void* q, const void* k, const void* v, void* o
  * anything else: DFOT_ERR_SHAPE (null pointers: DFOT_ERR_ARG), nothing launched */
 int dfot_op_attention_seq64_bwd(const void* q, const void* k, const void* v, const void* d_o, int ldo, void* dq, void* dk, void* dv, int nseq,
                                 int heads, int d, void* stream);
+/* dfot_op_attention_seq64_bwd with its results stored straight into the packed gradient rows the QKV Linear's backward reads: row
+ * seq*64 + r of dqkv (row stride ldg) holds dq of head hd at columns hd*d .. hd*d + d - 1, dk at heads*d + hd*d, dv at 2*heads*d + hd*d
+ * -- bit for bit what dfot_op_dit_qkv_grad_pack (no rope table) makes of dfot_op_attention_seq64_bwd's three outputs, in one launch.
+ * Columns at or beyond 3*heads*d and rows beyond nseq*64 are not written.  The shape rules of dfot_op_attention_seq64_bwd, and
+ * ldg >= 3*heads*d with ldg % 8 == 0; anything else: DFOT_ERR_SHAPE (null pointers: DFOT_ERR_ARG), nothing launched */
+int dfot_op_attention_seq64_bwd_packed(const void* q, const void* k, const void* v, const void* d_o, int ldo, void* dqkv, int ldg, int nseq,
+                                       int heads, int d, void* stream);
 /* temporal attention of the factorized-attention DiT: q, k, v [batch*tokens][heads][patches][dstride] bf16 as above (what the per-frame
  * QKV epilogue writes; q pre-scaled); for every (video, head, patch position) the `tokens` frames of the video attend to each other.
  * o[(video, frame, patch)][heads*d] compact (row stride ldo).  1 <= tokens <= 32, d % 4 == 0, d <= 128, patches % 128 == 0, ldo a
@@ -592,6 +607,10 @@ int dfot_op_attention_temporal(const void* q, const void* k, const void* v, void
  * anything else: DFOT_ERR_SHAPE (null pointer: DFOT_ERR_ARG) before any launch, nothing written */
 int dfot_op_attention_temporal_bwd(const void* q, const void* k, const void* v, const void* d_o, int ldo, void* dq, void* dk, void* dv,
                                    int batch, int tokens, int patches, int heads, int d, void* stream);
+/* dfot_op_attention_temporal_bwd at 64 patches per frame, the shape the FacDiT trainer runs the kernel at for the res-128 recipes (the
+ * op above keeps refusing it).  Every other rule is that op's; any 1 <= tokens <= 32 */
+int dfot_op_attention_temporal_bwd_p64(const void* q, const void* k, const void* v, const void* d_o, int ldo, void* dq, void* dk, void* dv,
+                                       int batch, int tokens, int heads, int d, void* stream);
 /* MatrixAttention core of the FacMatDiT backbone (DiT3D "factorized_matrix_attention", engine variant 3): every frame is one token whose
  * q / k / v are (E/cc x h/rr) matrices.  z [batch*L*E][3h] bf16 holds (q|k|v), rows (frame, col head, n), columns (row head, d);
  * o [batch*L*E][h] in the same order.  Per (video, col head, row head): S[l][l'] = scale * <rope(q_l), rope(k_l')> over the matrix

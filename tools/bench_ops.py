@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Micro-benchmarks of the C-ABI primitives at the RE10K model shapes (model batch 2), HIP-event timed.
-Usage (GPU box): python tools/bench_ops.py [gemm] [conv] [attn] [tattn] [mattn] [tattn_bwd] [facdit_train] [mattn_bwd] [facmat_train] [vae_encode] [equal] [dit_front] [ivae] [uvit3d] [gnfilm_frame] [uvit3d_train] [attnmap] [titok] [titok_enc] [mcraft] [sattn64] [facmat_narrow] [dcae] [attn_fc] [attn_fc_bwd] [dit1d] [seq64_bwd]"""
+Usage (GPU box): python tools/bench_ops.py [gemm] [conv] [attn] [tattn] [mattn] [tattn_bwd] [facdit_train] [mattn_bwd] [facmat_train] [vae_encode] [equal] [dit_front] [ivae] [uvit3d] [gnfilm_frame] [uvit3d_train] [attnmap] [titok] [titok_enc] [mcraft] [sattn64] [facmat_narrow] [dcae] [attn_fc] [attn_fc_bwd] [dit1d] [seq64_bwd] [seq64_bwd_packed] [facdit_s128_train]"""
 import ctypes as C
 import math
 import os
@@ -280,6 +280,64 @@ def seq64_bwd(nseq, heads, d, rounds=7):
         fwd.append(timeit(lambda: capi.check(capi.lib.dfot_op_attention_seq64(P(q), P(k), P(v), P(o), heads * d, nseq, heads, d, S())), iters=100, warm=10))
         cp.append(timeit(lambda: dst.copy_(src), iters=100, warm=10))
     return bwd, fwd, cp, nbytes
+
+
+def seq64_bwd_packed(nseq, heads, d, rounds=7):
+    """the packed form of the 64-token attention backward (dfot_op_attention_seq64_bwd_packed: one launch that stores dq | dk | dv into the
+    rows of dqkv [nseq*64][3*heads*d]) next to the pair it replaces in a spatial block's backward (dfot_op_attention_seq64_bwd, then
+    dfot_op_dit_qkv_grad_pack without a rope table) on the same unit-normal operands, and next to a device copy that moves the bytes the
+    packed form moves (q, k, v tiles of 64 x dstride, d_o and dqkv rows of heads*d and 3*heads*d columns), alternated over `rounds` rounds
+    in one process: ([ms packed], [ms pair], [ms copy], bytes moved)"""
+    ds = 64 if d <= 64 else 128
+    q, k, v = (torch.zeros(nseq, heads, 64, ds, device="cuda", dtype=torch.bfloat16) for _ in range(3))
+    for t, mul in ((q, math.log2(math.e) / math.sqrt(d)), (k, 1.0), (v, 1.0)):
+        t[..., :d] = (torch.randn(nseq, heads, 64, d, device="cuda") * mul).bfloat16()
+    d_o = torch.randn(nseq * 64, heads * d, device="cuda").bfloat16()
+    dq, dk, dv = (torch.empty_like(q) for _ in range(3))
+    ldg = 3 * heads * d
+    packed_out, pair_out = (torch.empty(nseq * 64, ldg, device="cuda", dtype=torch.bfloat16) for _ in range(2))
+    nbytes = (3 * nseq * heads * 64 * ds + 4 * nseq * 64 * heads * d) * 2
+    src = torch.randn(nbytes // 4, device="cuda").bfloat16()  # nbytes / 2 bytes read + nbytes / 2 written
+    dst = torch.empty_like(src)
+
+    def packed():
+        capi.check(capi.lib.dfot_op_attention_seq64_bwd_packed(P(q), P(k), P(v), P(d_o), heads * d, P(packed_out), ldg, nseq, heads, d, S()))
+
+    def pair():
+        capi.check(capi.lib.dfot_op_attention_seq64_bwd(P(q), P(k), P(v), P(d_o), heads * d, P(dq), P(dk), P(dv), nseq, heads, d, S()))
+        capi.check(capi.lib.dfot_op_dit_qkv_grad_pack(P(dq), P(dk), P(dv), None, P(pair_out), nseq * 64, 64, heads, d, ds, S()))
+    packed(), pair()
+    torch.cuda.synchronize()
+    assert torch.equal(packed_out.view(torch.int16), pair_out.view(torch.int16)), "the two forms disagree"
+    pk, pr, cp = [], [], []
+    for _ in range(rounds):
+        pk.append(timeit(packed, iters=100, warm=10))
+        pr.append(timeit(pair, iters=100, warm=10))
+        cp.append(timeit(lambda: dst.copy_(src), iters=100, warm=10))
+    return pk, pr, cp, nbytes
+
+
+def facdit_s128_train(b, mlp, rounds=7):
+    """one training step (loss, backward, clip, AdamW) of FacDiT-S (hidden 384, depth 6, 6 heads; spatial_mlp_ratio 4 with `mlp`, else 0) at
+    the taichi res-128 shape (4x16x16 latents, patch 2 = 64 patches per frame, 16 frames), with the spatial blocks' attention backward in
+    its packed form and as the pair (three buffers + pack kernel), alternated on ONE trainer over `rounds` rounds: ([ms packed], [ms pair])"""
+    bb = dict(name="dit3d", variant="factorized_attention", pos_emb_type="sinusoidal_factorized", patch_size=2, hidden_size=384, depth=6,
+              num_heads=6, mlp_ratio=4.0, spatial_mlp_ratio=4.0 if mlp else 0.0)
+    tr = dfot_amd.FacDiTTrainer(bb, x_shape=(4, 16, 16), max_tokens=16, allow_p64=True,
+                                loss_weighting=dict(strategy="fused_min_snr", cum_snr_decay=0.96))
+    model = dfot_amd.DiT3D(bb, x_shape=(4, 16, 16), max_tokens=16)  # for its init_random only
+    model.init_random(0)
+    tr.load_state_dict({n: t.detach() for n, t in model.state_dict().items()})
+    del model
+    xs, noise = torch.randn(b, 16, 4, 16, 16, device="cuda"), torch.randn(b, 16, 4, 16, 16, device="cuda")
+    k = torch.randint(0, 1000, (b, 16))
+    out = {1: [], 0: []}
+    for _ in range(rounds):
+        for form in (1, 0):
+            capi.check(capi.lib.dfot_facdit_train_set_seq64_packed(tr._handle, form))
+            out[form].append(timeit(lambda: tr.training_step(xs, k, noise), iters=10, warm=2))
+    capi.check(capi.lib.dfot_facdit_train_set_seq64_packed(tr._handle, 1))
+    return out[1], out[0]
 
 
 def dit1d_forward(b, rounds=5):
@@ -934,6 +992,22 @@ def main():
             print(f"seq64_bwd 256 sequences H=6 d={d}: backward median {med(bwd)*1e3:7.1f} us (min {min(bwd)*1e3:.1f})  forward {med(fwd)*1e3:7.1f} us "
                   f"(min {min(fwd)*1e3:.1f})  copy of {nbytes / 1e6:.1f} MB moved {med(cp)*1e3:7.1f} us (min {min(cp)*1e3:.1f})  backward / forward "
                   f"{med(bwd) / med(fwd):.2f}  backward / copy {med(bwd) / med(cp):.2f}  ({len(bwd)} alternated rounds)", flush=True)
+    if "seq64_bwd_packed" in what:
+        med = lambda r: sorted(r)[len(r) // 2]  # noqa: E731
+        # the shapes of seq64_bwd: @FacDiT/S at res-128 (16 videos x 16 frames, 6 heads, d 64), then d 72 and d 128
+        for d in (64, 72, 128):
+            pk, pr, cp, nbytes = seq64_bwd_packed(256, 6, d)
+            print(f"seq64_bwd_packed 256 sequences H=6 d={d}: packed median {med(pk)*1e3:7.1f} us (min {min(pk)*1e3:.1f}, max {max(pk)*1e3:.1f})  "
+                  f"pair (backward + qkv_grad_pack) {med(pr)*1e3:7.1f} us (min {min(pr)*1e3:.1f}, max {max(pr)*1e3:.1f})  copy of {nbytes / 1e6:.1f} MB "
+                  f"moved {med(cp)*1e3:7.1f} us (min {min(cp)*1e3:.1f}, max {max(cp)*1e3:.1f})  packed / pair {med(pk) / med(pr):.2f}  packed / copy "
+                  f"{med(pk) / med(cp):.2f}  ({len(pk)} alternated rounds, equal bits)", flush=True)
+    if "facdit_s128_train" in what:
+        med = lambda r: sorted(r)[len(r) // 2]  # noqa: E731
+        for mlp in (False, True):
+            pk, pr = facdit_s128_train(16, mlp)
+            print(f"facdit_s128_train FacDiT-S{'-mlp' if mlp else ''} B=16 x 16 frames x 64 patches (hidden 384, depth 6): step with the packed "
+                  f"spatial backward median {med(pk):.3f} ms (min {min(pk):.3f}, max {max(pk):.3f})  with the pair {med(pr):.3f} ms (min {min(pr):.3f}, "
+                  f"max {max(pr):.3f})  packed / pair {med(pk) / med(pr):.3f}  ({len(pk)} alternated rounds)", flush=True)
     if "dit1d" in what:
         ms = dit1d_forward(16)
         for name, r in ms.items():
