@@ -140,6 +140,7 @@ SIGNATURES = {
     "dfot_dit_train_create": (_I, [C.POINTER(DiTConfig), C.POINTER(_P)]),
     "dfot_dit_train_create_f": (_I, [C.POINTER(DiTConfigF), C.POINTER(_P)]),
     "dfot_facmat_train_create": (_I, [C.POINTER(DiTConfigF), C.POINTER(_P)]),
+    "dfot_facmat_train_create_p64": (_I, [C.POINTER(DiTConfigF), C.POINTER(_P)]),
     "dfot_facdit_train_create": (_I, [C.POINTER(DiTConfigF), C.POINTER(_P)]),
     "dfot_facdit_train_set_seq64_packed": (_I, [_P, _I]),
     "dfot_dit_train_destroy": (_I, [_P]),
@@ -182,6 +183,7 @@ SIGNATURES = {
     "dfot_op_attention_temporal": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "dfot_op_attention_temporal_bwd": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "dfot_op_attention_temporal_bwd_p64": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "dfot_op_facmat_factor_wgrad": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
     "dfot_op_matrix_attention_rope": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P]),
     "dfot_op_matrix_attention_rope_bwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P]),
     "dfot_op_attention_map_workspace_bytes": (C.c_size_t, [_I, _I, _I, _I, _I]),

@@ -835,7 +835,7 @@ struct dfot_dit_train_s : dfot::DitGeom {  // the geometry of cfg (dit_model.h):
   float *fz_freqs = nullptr, *fz_phases = nullptr;
   bool fz_loaded[2] = {false, false};
   bool synced = false;
-  // variant 2 at exactly 64 patches per frame, set once at create: the spatial blocks' sequences are single 64-token frames, so they run
+  // variant 2 (and variant 3 built by dfot_facmat_train_create_p64) at exactly 64 patches per frame, set once at create: the spatial blocks' sequences are single 64-token frames, so they run
   // attention_seq64.hip forward and its backward, and keep no lse.  The ONE predicate reserve, forward and backward choose those kernels
   // by (variant 0 at 64 patches has whole-video sequences, n % 128 == 0, and keeps launch_attention_padded with its lse)
   bool seq64 = false;
@@ -987,8 +987,9 @@ int dfot_dit_train_destroy(dfot_dit_train_t h) {
 }
 
 // entry: the variant the calling entry point is dedicated to -- 2 from dfot_facdit_train_create, 3 from dfot_facmat_train_create, the only
-// entries that build those variants; 0 from dfot_dit_train_create[_f], which build variants 0 and 1
-static int dit_train_create_impl(const DitCfg& c, dfot_dit_train_t* out, int entry = 0) {
+// entries that build those variants; 0 from dfot_dit_train_create[_f], which build variants 0 and 1.  facmat_p64: the entry is
+// dfot_facmat_train_create_p64, which also builds variant 3 at exactly 64 patches per frame (dfot_facmat_train_create keeps refusing them)
+static int dit_train_create_impl(const DitCfg& c, dfot_dit_train_t* out, int entry = 0, bool facmat_p64 = false) {
   DFOT_REQUIRE(c.variant != 2 || entry == 2, DFOT_ERR_ARG,
                "train_create: variant 2 (factorized attention DiT3D, FacDiT) is not built here; its trainer is dfot_facdit_train_create");
   DFOT_REQUIRE(c.variant != 3 || entry == 3, DFOT_ERR_ARG,
@@ -1022,8 +1023,9 @@ static int dit_train_create_impl(const DitCfg& c, dfot_dit_train_t* out, int ent
   h->ocp = (h->oc + 63) / 64 * 64;
   const int hd = c.hidden_size, E = c.embed_col_dim, P = h->P;
   // variant 2 also trains at exactly 64 patches per frame (the res-128 recipes: attention_seq64.hip and its backward run the per-frame
-  // sequences) when max_tokens is even, so that a full window is a whole number of the GEMMs' 128-row tiles
-  h->seq64 = fac && h->P == 64;
+  // sequences) when max_tokens is even, so that a full window is a whole number of the GEMMs' 128-row tiles; so does variant 3 through
+  // dfot_facmat_train_create_p64 (its left-factor gradients then go through facmat_factor_wgrad.hip)
+  h->seq64 = (fac || (c.variant == 3 && facmat_p64)) && h->P == 64;
   const bool p64 = h->seq64;
   if (p64 && c.max_tokens % 2 != 0) {
     set_error("train_create: 64 patches per frame need an even max_tokens (max_tokens %d x 64 = %d rows per window; the row tiles need a "
@@ -1032,8 +1034,8 @@ static int dit_train_create_impl(const DitCfg& c, dfot_dit_train_t* out, int ent
     return DFOT_ERR_SHAPE;
   }
   if (h->P % TR_CHUNKS != 0 || ((facmat || fac) && h->P % 128 != 0 && !p64)) {
-    set_error(fac ? "train_create: %d patches per frame must be a multiple of %d (or exactly 64 with an even max_tokens)"
-                  : "train_create: %d patches per frame must be a multiple of %d", h->P, facmat || fac ? 128 : TR_CHUNKS);
+    set_error(fac || facmat_p64 ? "train_create: %d patches per frame must be a multiple of %d (or exactly 64 with an even max_tokens)"
+                                : "train_create: %d patches per frame must be a multiple of %d", h->P, facmat || fac ? 128 : TR_CHUNKS);
     delete h;
     return DFOT_ERR_ARG;
   }
@@ -1146,6 +1148,18 @@ int dfot_facmat_train_create(const dfot_dit_config_f* cfg, dfot_dit_train_t* out
                cfg->base.variant);
   DFOT_REQUIRE(!cfg->fourier_noise, DFOT_ERR_ARG, "facmat_train_create: fourier_noise (continuous diffusion) is not supported for variant 3");
   return dit_train_create_impl(dit_cfg(cfg->base), out, 3);
+}
+
+// dfot_facmat_train_create that also accepts exactly 64 patches per frame with an even max_tokens (the taichi res-128 facmat-s recipes);
+// at a multiple of 128 patches it builds what that entry builds.  A separate entry: the older one is held to its refusal of 64 patches
+int dfot_facmat_train_create_p64(const dfot_dit_config_f* cfg, dfot_dit_train_t* out) {
+  DFOT_REQUIRE(cfg && out, DFOT_ERR_ARG, "facmat_train_create_p64: null argument");
+  DFOT_REQUIRE(cfg->base.variant == 3, DFOT_ERR_ARG,
+               "facmat_train_create_p64: variant %d; this entry builds variant 3 (DiT3D factorized matrix) only, dfot_dit_train_create[_f] build 0 "
+               "and 1, dfot_facdit_train_create builds 2",
+               cfg->base.variant);
+  DFOT_REQUIRE(!cfg->fourier_noise, DFOT_ERR_ARG, "facmat_train_create_p64: fourier_noise (continuous diffusion) is not supported for variant 3");
+  return dit_train_create_impl(dit_cfg(cfg->base), out, 3, true);
 }
 
 int dfot_facdit_train_create(const dfot_dit_config_f* cfg, dfot_dit_train_t* out) {
@@ -1303,8 +1317,11 @@ int dfot_dit_train_reserve(dfot_dit_train_t h, int max_batch) {
     WS(h->ma_sc, (size_t)(1 + MA_CHUNKS) * max_batch * c.num_col_heads * c.num_row_heads * 2 * c.max_tokens * c.max_tokens);  // sums, then the chunk planes
   }
   if (facmat) {
-    WS(h->mt, rows * hd); WS(h->do2, fe * hd); WS(h->dz, fe * 3 * hd); WS(h->dw1, fe * hd);
-    WS(h->perm_a, (size_t)(h->P > 128 ? h->P : 128) * frames * hd); WS(h->perm_b, (size_t)(h->P > 128 ? h->P : 128) * frames * hd);
+    // mt holds a per-frame transpose of [P][hd] (m, ds) or of [E][hd] (o, dw1): at 64 patches E = 128 is the larger of the two
+    WS(h->mt, (size_t)frames * (h->P > E ? h->P : E) * hd); WS(h->do2, fe * hd); WS(h->dz, fe * 3 * hd); WS(h->dw1, fe * hd);
+    if (!h->seq64) {  // at 64 patches the left-factor gradients read their operands in place (launch_facmat_factor_wgrad): no regrouped copies
+      WS(h->perm_a, (size_t)(h->P > 128 ? h->P : 128) * frames * hd); WS(h->perm_b, (size_t)(h->P > 128 ? h->P : 128) * frames * hd);
+    }
   }
 #undef WS
   h->max_batch = max_batch;
@@ -1331,6 +1348,9 @@ static int dit_train_forward_impl(dfot_dit_train_t h, const float* x, const int3
   DFOT_REQUIRE(tokens > 0 && tokens <= c.max_tokens, DFOT_ERR_SHAPE, "train_forward: %d tokens, max_tokens is %d", tokens, c.max_tokens);
   DFOT_REQUIRE(!diffm || tokens % 2 == 0, DFOT_ERR_SHAPE, "train_forward: %d tokens; the difference model takes (difference, frame) pairs", tokens);
   const int n = tokens * h->P, hd = c.hidden_size, P = h->P, frames = batch * tokens, nd = c.noise_dim, E = c.embed_col_dim;
+  DFOT_REQUIRE(!(h->seq64 && c.variant == 3) || tokens % 2 == 0, DFOT_ERR_SHAPE,
+               "train_forward: 64 patches per frame need an even number of tokens (%d tokens x 64 = %d rows; the row tiles need a multiple of 128)",
+               tokens, n);
   DFOT_REQUIRE(n % 128 == 0, DFOT_ERR_SHAPE, "train_forward: sequence length %d (tokens x patches) must be a multiple of 128", n);
   hipStream_t s = (hipStream_t)stream;
   const long rows = (long)batch * n;
@@ -1581,11 +1601,15 @@ int dfot_dit_train_backward(dfot_dit_train_t h, const float* d_out, void* stream
       if ((rc = wgrad(b.sfac, hd, h->da, hd, rows, G + b.o_proj_v))) return rc;                                  // dV'[in][out] = s^T da
       if ((rc = tr_transpose(h->dO, h->mt, P, hd, s, frames))) return rc;                                        // ds^T per frame [hd][P]
       if ((rc = tr_gemm_bf16(h->mt, P, b.pu_s, frames * hd, E, P, nullptr, h->do2, E, s, 0, hd))) return rc;       // do[f][e][d] = sum_p U'[e][p] ds[f][p][d]
-      // dU'[e][p] = sum_{f,d} o[f][e][d] ds[f][p][d]: operands regrouped to [e][(f,d)] / [p][(f,d)]; E rows padded to 128
-      DFOT_CHECK_HIP(hipMemsetAsync(h->perm_a, 0, (size_t)128 * fk * sizeof(bf16), s));
-      if ((rc = permute(b.o2, h->perm_a, E)) || (rc = permute(h->dO, h->perm_b, P))) return rc;
-      if ((rc = tr_wgrad(h->perm_a, h->perm_b, 128, P, (int)fk, h->dwf, s, h->wg_ws, h->wg_ws_floats))) return rc;
-      DFOT_CHECK_HIP(hipMemcpyAsync(G + b.o_proj_u, h->dwf, (size_t)E * P * sizeof(float), hipMemcpyDeviceToDevice, s));
+      if (h->seq64) {  // 64 patches: dU'[e][p] = sum_{f,d} o[f][e][d] ds[f][p][d] on the operands as they lie, straight into the gradient
+        if ((rc = launch_facmat_factor_wgrad(b.o2, h->dO, G + b.o_proj_u, h->wg_ws, h->wg_ws_floats, frames, E, P, hd, s))) return rc;
+      } else {
+        // dU'[e][p] = sum_{f,d} o[f][e][d] ds[f][p][d]: operands regrouped to [e][(f,d)] / [p][(f,d)]; E rows padded to 128
+        DFOT_CHECK_HIP(hipMemsetAsync(h->perm_a, 0, (size_t)128 * fk * sizeof(bf16), s));
+        if ((rc = permute(b.o2, h->perm_a, E)) || (rc = permute(h->dO, h->perm_b, P))) return rc;
+        if ((rc = tr_wgrad(h->perm_a, h->perm_b, 128, P, (int)fk, h->dwf, s, h->wg_ws, h->wg_ws_floats))) return rc;
+        DFOT_CHECK_HIP(hipMemcpyAsync(G + b.o_proj_u, h->dwf, (size_t)E * P * sizeof(float), hipMemcpyDeviceToDevice, s));
+      }
       // attention over the frames
       if (!diffm) {  // FacMatDiT: one launch, any token count, with the rotation and its inverse
         const int hn = E / c.num_col_heads, hdr = hd / c.num_row_heads;
@@ -1612,8 +1636,12 @@ int dfot_dit_train_backward(dfot_dit_train_t h, const float* d_out, void* stream
       hipLaunchKernelGGL(add_bf16_kernel, dim3(cdiv(rows * hd / 4, 256)), dim3(256), 0, s, dY, h->dO, rows * hd / 4);
       DFOT_CHECK_HIP(hipGetLastError());
       // dU[p][e] = sum_{f,d} m[f][p][d] dw1[f][e][d]
-      if ((rc = permute(b.m, h->perm_a, P)) || (rc = permute(h->dw1, h->perm_b, E))) return rc;
-      if ((rc = tr_wgrad(h->perm_a, h->perm_b, P, E, (int)fk, G + b.o_qkv_u, s, h->wg_ws, h->wg_ws_floats))) return rc;
+      if (h->seq64) {  // 64 patches: operands as they lie (m is not written between the forward and here; dw1 holds E rows per frame)
+        if ((rc = launch_facmat_factor_wgrad(b.m, h->dw1, G + b.o_qkv_u, h->wg_ws, h->wg_ws_floats, frames, P, E, hd, s))) return rc;
+      } else {
+        if ((rc = permute(b.m, h->perm_a, P)) || (rc = permute(h->dw1, h->perm_b, E))) return rc;
+        if ((rc = tr_wgrad(h->perm_a, h->perm_b, P, E, (int)fk, G + b.o_qkv_u, s, h->wg_ws, h->wg_ws_floats))) return rc;
+      }
     }
     if ((rc = ln_bwd(b.x_in, b.mod))) return rc;
   }

@@ -91,6 +91,14 @@ WgradPlan wgrad_plan(int m, int n, long rows, long max_slices);
 int launch_wgrad_conv_taps(const bf16* dy, const bf16* x, float* out, int co, int ci, long pix, int slices, int img_h, int img_w, hipStream_t s);
 int wgrad_conv_tiles(int co, int ci, int* target);
 int launch_wgrad_nt_plan(const bf16* a, long lda, const bf16* b, long ldb, float* out, int m, int n, long rows, WgradPlan plan, hipStream_t s);
+// ---- left-factor gradients of the FacMatDiT matrix block (facmat_factor_wgrad.hip): out[Ra][Rb] fp32 = sum_{f,d} A[f][ra][d] B[f][rb][d];
+// A [frames][Ra][hd], B [frames][Rb][hd] bf16 read as they lie; Ra, Rb in {64, 128}, hd % 128 == 0, frames >= 1.  The frame axis is split
+// over workgroups that store partial tiles to ws (ws_floats >= slices * Ra * Rb bounds the slice count; null: one slice, straight into
+// out) and a second launch sums them in a fixed order: no atomics, the same bits every call
+int launch_facmat_factor_wgrad(const bf16* a, const bf16* b, float* out, float* ws, size_t ws_floats, int frames, int ra, int rb, int hd,
+                               hipStream_t s);
+// the slice count of one call: a function of the shape and the device, at most max_slices (the workspace: slices * Ra * Rb floats)
+int facmat_factor_wgrad_slices(int frames, int ra, int rb, long max_slices);
 // ---- training: loss gradient, gradient norm, AdamW (flat fp32 buffers) ----
 int launch_vloss_grad(const float* x, const float* noise, const float* v, const float* a, const float* sg, const float* coef, float* dv,
                       int batch, int tokens, long f, bool vspace, hipStream_t s);

@@ -742,6 +742,21 @@ int dfot_op_wgrad_nt(const void* a, int lda, const void* b, int ldb, float* out,
   DFOT_CHECK_HIP(hipGetLastError());
   return DFOT_OK;
 }
+// test entry: out [ra][rb] fp32 = sum_{f,d} a[f][ra][d] b[f][rb][d] (a left-factor gradient of the FacMatDiT matrix block: the engine's
+// launcher with its slice plan and slice sum, on a workspace of the size the plan asks for)
+int dfot_op_facmat_factor_wgrad(const void* a, const void* b, float* out, int frames, int ra, int rb, int hd, void* stream) {
+  DFOT_REQUIRE(a && b && out, DFOT_ERR_ARG, "op_facmat_factor_wgrad: null argument");
+  DFOT_REQUIRE((ra == 64 || ra == 128) && (rb == 64 || rb == 128), DFOT_ERR_SHAPE, "op_facmat_factor_wgrad: %d x %d output; both sides are 64 or 128",
+               ra, rb);
+  DFOT_REQUIRE(hd > 0 && hd % 128 == 0, DFOT_ERR_SHAPE, "op_facmat_factor_wgrad: hidden %d must be a positive multiple of 128", hd);
+  DFOT_REQUIRE(frames >= 1, DFOT_ERR_SHAPE, "op_facmat_factor_wgrad: %d frames", frames);
+  const int slices = facmat_factor_wgrad_slices(frames, ra, rb, frames);
+  void* ws = nullptr;
+  if (slices > 1)
+    if (int rc = op_scratch(7, (size_t)slices * ra * rb * sizeof(float), &ws)) return rc;
+  return launch_facmat_factor_wgrad((const bf16*)a, (const bf16*)b, out, (float*)ws, ws ? (size_t)slices * ra * rb : 0, frames, ra, rb, hd,
+                                    (hipStream_t)stream);
+}
 }  // extern "C"
 
 // ---- forward passes in training form (values the backward needs are kept: no fused norm / activation epilogues) and generic op

@@ -301,7 +301,18 @@ class FacMatDiTTrainer(DiT3DTrainer):
     or without ``use_temporal_rope`` (dit3d_factorized_matrix.yaml + the @FacMatDiT shortcuts; the reference's bash/taichikl recipes).  Same
     constructor keywords and methods as DiT3DTrainer; max_tokens is the algorithm's (not doubled: there are no difference tokens), any
     1 <= T <= max_tokens <= 32 trains.  The matrix attention and its backward run with the RoPE-1D over the frame axis
-    (csrc/attention_matrix.hip, csrc/attention_matrix_bwd.hip).  Discrete diffusion only."""
+    (csrc/attention_matrix.hip, csrc/attention_matrix_bwd.hip).  Discrete diffusion only; embed_col_dim 64 or 128.  Exactly 64 patches per
+    frame (latents 4x16x16 at patch 2, the taichi res-128 facmat-s-*-bias recipes) train when the constructor gets ``allow_p64=True``;
+    without the keyword the shape is refused in the words it always was.  max_tokens and T must then be even, so that a window is a whole
+    number of 128-row tiles; the spatial blocks run the 64-token attention and its packed backward (csrc/attention_seq64.hip,
+    csrc/attention_seq64_bwd.hip) and the gradients of the left factors qkv_u / proj_u are computed on the operands as they lie
+    (csrc/facmat_factor_wgrad.hip)."""
+
+    allow_p64 = False  # the constructor keyword; a class default, so that _configure also runs on an instance __init__ has not seen
+
+    def __init__(self, *args, allow_p64: bool = False, **kwargs):
+        self.allow_p64 = bool(allow_p64)
+        super().__init__(*args, **kwargs)
 
     def _configure(self, c: "capi.DiTConfigF", cfg, max_tokens: int) -> None:
         from .dit_backbone import configure_facmat
@@ -311,10 +322,32 @@ class FacMatDiTTrainer(DiT3DTrainer):
                              f"{variant!r} / {pos!r} (DiT3DTrainer trains the 'full' DiT3D and the difference model)")
         if _get(cfg, "use_fourier_noise_embedding", False):
             raise ValueError("use_fourier_noise_embedding=True is not supported by FacMatDiTTrainer: it trains under discrete diffusion only")
-        configure_facmat(c, cfg, max_tokens)  # refuses matrix_multi_token, flatten_matrix_rope, fixed_u, matrix_block, patches, max_tokens by name
+        try:  # refuses matrix_multi_token, flatten_matrix_rope, fixed_u, matrix_block, patches, max_tokens by name
+            configure_facmat(c, cfg, max_tokens, allow_p64=self.allow_p64)
+        except ValueError as err:
+            if self.allow_p64 or max_tokens % 2 or (c.height // c.patch_size) * (c.width // c.patch_size) != 64 or "patches per frame" not in str(err):
+                raise
+            # the refusal in the words it always had, then the way on: this shape is the one the keyword switches on
+            raise ValueError(f"{err} by default: FacMatDiTTrainer(..., allow_p64=True) trains them (even max_tokens, even T)") from None
 
     def _create(self, c: "capi.DiTConfigF") -> None:
-        capi.check(capi.lib.dfot_facmat_train_create(C.byref(c), C.byref(self._handle)))
+        # the p64 entry builds what the older one builds at a multiple of 128 patches; the older one is held to its refusal of 64
+        create = capi.lib.dfot_facmat_train_create_p64 if self.allow_p64 else capi.lib.dfot_facmat_train_create
+        capi.check(create(C.byref(c), C.byref(self._handle)))
+
+    def _check_tokens(self, t: int) -> None:
+        c = self._ccfg
+        if (c.height // c.patch_size) * (c.width // c.patch_size) == 64 and t % 2:
+            raise ValueError(f"FacMatDiTTrainer at 64 patches per frame takes an even number of tokens: {t} tokens × 64 patches = {t * 64} rows; "
+                             "the row tiles need a multiple of 128")
+
+    def forward(self, x, noise_levels, cond=None, cond_mask=None):
+        self._check_tokens(int(x.shape[1]))
+        return super().forward(x, noise_levels, cond, cond_mask)
+
+    def loss_and_grads(self, xs, k, noise, masks=None, conditions=None, dropout_generator=None):
+        self._check_tokens(int(xs.shape[1]))  # before the noising kernels, not only before the forward
+        return super().loss_and_grads(xs, k, noise, masks, conditions, dropout_generator)
 
 
 class FacDiTTrainer(DiT3DTrainer):

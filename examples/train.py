@@ -8,6 +8,8 @@
   python examples/train.py facdit   [--xl] [--batch 8]                                # FacDiT (dit3d_factorized_attention.yaml); --xl: @DiT/XL widths, taichikl shape
   python examples/train.py facdit-s128 [--mlp] [--batch 16]                           # FacDiT-S at 64 patches per frame, the taichi res-128 recipes (4x16x16
                                                                                       # latents, patch 2, 16 frames); --mlp: spatial_mlp_ratio 4 (facdit-s-mlp)
+  python examples/train.py facmat-s128 [--embed-col-dim 64|128] [--col-heads N] [--batch 16]   # FacMatDiT-S with use_bias at the same shape, the taichi res-128
+                                                                                      # facmat-s-{64-1,64-4,64-16,128-1}-bias recipes (default S-64-1)
   python examples/train.py taichi1d [--xl] [--batch 8]                                # DiT1D (dit1d.yaml), frame-causal, 4x1x32 token latents; --xl: its stock widths, 16 frames
   python examples/train.py mcraft   [--b] [--batch 8]                                 # the Minecraft / dmlab DiT recipe (32x8x8 latents, patch 2, 16 frames,
                                                                                       # actions of dim 4, continuous); --b: @DiT/B, else width 384, depth 2
@@ -40,7 +42,7 @@ K600_DATA_STD = [5.591, 5.257, 7.033, 6.401, 6.091, 11.233, 5.608, 7.5, 5.277, 5
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("model", choices=["k600", "k600diff", "facmat", "facdit", "facdit-s128", "taichi1d", "re10k", "uvit3d", "mcraft"])
+    ap.add_argument("model", choices=["k600", "k600diff", "facmat", "facdit", "facdit-s128", "facmat-s128", "taichi1d", "re10k", "uvit3d", "mcraft"])
     ap.add_argument("--ckpt")
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--batch", type=int, default=8)
@@ -58,6 +60,9 @@ def main():
                                                       "width 128, depth 2, 8 frames")
     ap.add_argument("--mlp", action="store_true", help="facdit-s128: spatial_mlp_ratio 4 (train_dfot_facdit-s-mlp_taichikl_16_res128_ru.sh) instead of "
                                                        "attention-only spatial blocks (train_dfot_facdit-s_taichikl_16_res128_ru.sh)")
+    ap.add_argument("--embed-col-dim", type=int, default=64, choices=[64, 128],
+                    help="facmat-s128: column width of the matrix token, @FacMatDiT/group_S/S-64-* or S-128-1 (narrower widths do not train)")
+    ap.add_argument("--col-heads", type=int, default=1, help="facmat-s128: num_col_heads (1, 4 or 16 in the recipes; must divide the column width)")
     ap.add_argument("--b", action="store_true", help="mcraft: @DiT/B (hidden 768, depth 12, 12 heads) instead of the tiny default (hidden 384, depth 2, 6 heads)")
     ap.add_argument("--full", action="store_true", help="uvit3d: the widths, depths and dropouts of u_vit3d.yaml with num_heads 8 (its 4 heads give head "
                                                         "dim 256, which the attention kernels do not take) on 8 frames of 3 x 256 x 256, instead of the "
@@ -75,7 +80,7 @@ def main():
         return train_re10k(a, rank, world)
     if a.model == "uvit3d":
         return train_uvit3d(a, rank, world)
-    if a.model in ("facmat", "facdit", "facdit-s128", "taichi1d"):
+    if a.model in ("facmat", "facdit", "facdit-s128", "facmat-s128", "taichi1d"):
         return train_factorized(a, rank, world)
     diff, mcraft = a.model == "k600diff", a.model == "mcraft"
     x_shape, tokens = ((32, 8, 8), 16) if mcraft else ((16, 16, 16), 5)
@@ -162,6 +167,9 @@ def train_factorized(a, rank, world):
     facdit (bash/taichikl/train_dfot_facdit-*): factorized attention, sinusoidal_factorized, FacDiTTrainer -- the baseline of the former;
     facdit-s128 (bash/taichikl/resolution_128/train_dfot_facdit-s[-mlp]_taichikl_16_res128_ru.sh): the same model at the @FacDiT/S widths
         (hidden 384, depth 6, 6 heads) on 4x16x16 latents with patch 2 -- 64 patches per frame, 16 frames -- with (--mlp) or without the spatial MLP;
+    facmat-s128 (bash/taichikl/resolution_128/train_dfot_facmat-s-{64-1,64-4,64-16,128-1}-bias_taichikl_16_res128_ru.sh): FacMatDiT at the
+        @FacMatDiT/group_S widths (embed_row_dim 384, 6 row heads, depth 6, 12 spatial heads) with use_bias at that shape; --embed-col-dim 64 | 128
+        and --col-heads choose the rung;
     taichi1d (`backbone=dit1d`): the frame-causal DiT1D over the 4x1x32 TiTok-KL token latents, DiT1DTrainer (unconditioned)"""
     if a.continuous or a.pixels:
         raise SystemExit(f"{a.model} trains on synthetic latents under discrete diffusion")
@@ -180,6 +188,14 @@ def train_factorized(a, rank, world):
         cfg = dict(name="dit3d", variant="factorized_attention", pos_emb_type="sinusoidal_factorized", patch_size=2, hidden_size=384, depth=6,
                    num_heads=6, mlp_ratio=4.0, spatial_mlp_ratio=4.0 if a.mlp else 0.0)
         trainer_cls = dfot_amd.FacDiTTrainer
+    elif a.model == "facmat-s128":
+        x_shape, tokens = (4, 16, 16), 16
+        if a.embed_col_dim % a.col_heads:
+            raise SystemExit(f"facmat-s128: --col-heads {a.col_heads} does not divide --embed-col-dim {a.embed_col_dim}")
+        cfg = dict(name="dit3d", variant="factorized_matrix_attention", pos_emb_type="sinusoidal_2d", use_temporal_rope=True, patch_size=2,
+                   embed_col_dim=a.embed_col_dim, embed_row_dim=384, num_heads=12, num_col_heads=a.col_heads, num_row_heads=6, depth=6,
+                   mlp_ratio=4.0, spatial_mlp_ratio=4.0, use_bias=True, matrix_block="matrix")
+        trainer_cls = dfot_amd.FacMatDiTTrainer
     elif a.model == "facdit":
         cfg = dict(patch_size=2, hidden_size=1152, num_heads=16, depth=28) if a.xl else dict(patch_size=1, hidden_size=128, num_heads=4, depth=2)
         cfg.update(name="dit3d", variant="factorized_attention", pos_emb_type="sinusoidal_factorized", mlp_ratio=4.0, spatial_mlp_ratio=4.0)
@@ -200,7 +216,7 @@ def train_factorized(a, rank, world):
         ckw = dict(external_cond_type="action", external_cond_dim=cnum)
         cfg["external_cond_dropout"] = 0.1
     # 64 patches per frame train on request: without the keyword the trainer refuses them as it always did
-    tkw = dict(ckw, allow_p64=True) if a.model == "facdit-s128" else ckw
+    tkw = dict(ckw, allow_p64=True) if a.model in ("facdit-s128", "facmat-s128") else ckw
     trainer = trainer_cls(cfg, x_shape=x_shape, max_tokens=tokens, lr=a.lr, loss_weighting=dict(strategy="fused_min_snr", cum_snr_decay=0.96), **tkw)
     if a.ckpt:
         dfot_amd.load_reference_checkpoint(trainer, a.ckpt)

@@ -418,6 +418,15 @@ int dfot_dit_train_create_f(const dfot_dit_config_f* cfg, dfot_dit_train_t* out)
  * float64 when use_temporal_rope is set; actions / labels through dfot_dit_train_forward_cond.  dfot_dit_train_create[_f] keep refusing
  * variant 3 and name this function. */
 int dfot_facmat_train_create(const dfot_dit_config_f* cfg, dfot_dit_train_t* out);
+/* dfot_facmat_train_create that also builds (H/p)*(W/p) == 64, the taichi res-128 facmat-s-{64-1,64-4,64-16,128-1}-bias recipes (variant 3
+ * only, embed_col_dim 64 or 128 as there; any other variant or fourier_noise != 0: DFOT_ERR_ARG).  At 64 patches max_tokens must be even
+ * (an odd one: DFOT_ERR_SHAPE) and so must T: dfot_dit_train_forward[_cond] refuse an odd T with DFOT_ERR_SHAPE before they launch
+ * anything, so the gradients of the previous step stay as they were.  The spatial blocks then run dfot_op_attention_seq64's kernel and
+ * dfot_op_attention_seq64_bwd_packed's, the matrix block's forward is unchanged, and the gradients of the two left factors qkv_u / proj_u
+ * go through dfot_op_facmat_factor_wgrad's launcher, straight into the gradient buffer.  At a multiple of 128 patches it builds exactly
+ * what dfot_facmat_train_create builds (the same gradient bits).  A separate entry because dfot_facmat_train_create is held to its
+ * refusal of 64 patches. */
+int dfot_facmat_train_create_p64(const dfot_dit_config_f* cfg, dfot_dit_train_t* out);
 /* trainer of the DiT3D factorized-attention model (FacDiT: variant 2 only, any other variant: DFOT_ERR_ARG; fourier_noise != 0:
  * DFOT_ERR_ARG).  The handle is a dfot_dit_train_t: every other dfot_dit_train_* function takes it.  Parameters in the reference's
  * registration order (all spatial blocks, then all temporal blocks), executed spatial i, temporal i; any 1 <= T <= max_tokens <= 32 (the
@@ -625,6 +634,13 @@ int dfot_op_matrix_attention_rope(const void* z, void* o, const float* rope_cs, 
  * rules and error codes as the forward, checked before any launch; dz must not alias z or d_o (DFOT_ERR_ARG); rope_cs NULL = no rotation */
 int dfot_op_matrix_attention_rope_bwd(const void* z, const void* d_o, const float* rope_cs, void* dz, int batch, int L, int E, int h, int cc,
                                       int rr, float scale, void* stream);
+/* Gradient of a left factor (qkv_u, proj_u) of the MatrixDiTBlock at 64 patches per frame, operands as the training step leaves them:
+ *   out[ra][rb] (fp32) = sum_f sum_d a[f][ra][d] * b[f][rb][d],   a [frames][Ra][hd], b [frames][Rb][hd] bf16, no copies, no padding.
+ * dU'[e][p] is (a = o, b = ds), dU[p][e] is (a = m, b = dw1).  bf16 MFMA with fp32 accumulation; the frame axis is split over workgroups,
+ * every slice stores its partial tile to a workspace of the library's own and one pass sums the slices in slice order: no atomics, the
+ * same bits on every call.  Ra, Rb in {64, 128}, hd % 128 == 0, frames >= 1 (anything else: DFOT_ERR_SHAPE); a null a, b or out:
+ * DFOT_ERR_ARG; both before any launch.  Test / measurement entry of the launcher the engine calls */
+int dfot_op_facmat_factor_wgrad(const void* a, const void* b, float* out, int frames, int ra, int rb, int hd, void* stream);
 /* the DifferenceDiT3D (variant 1) form of the same core, without rotation: register forms for L in {2, 4, 6, 8, 10}, one pair of
  * tokens per wave pass for every other L <= 32.  Test / measurement entry of the engine's own launcher */
 int dfot_op_matrix_attention(const void* z, void* o, int batch, int L, int E, int h, int cc, int rr, float scale, void* stream);

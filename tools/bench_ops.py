@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Micro-benchmarks of the C-ABI primitives at the RE10K model shapes (model batch 2), HIP-event timed.
-Usage (GPU box): python tools/bench_ops.py [gemm] [conv] [attn] [tattn] [mattn] [tattn_bwd] [facdit_train] [mattn_bwd] [facmat_train] [vae_encode] [equal] [dit_front] [ivae] [uvit3d] [gnfilm_frame] [uvit3d_train] [attnmap] [titok] [titok_enc] [mcraft] [sattn64] [facmat_narrow] [dcae] [attn_fc] [attn_fc_bwd] [dit1d] [seq64_bwd] [seq64_bwd_packed] [facdit_s128_train]"""
+Usage (GPU box): python tools/bench_ops.py [gemm] [conv] [attn] [tattn] [mattn] [tattn_bwd] [facdit_train] [mattn_bwd] [facmat_train] [vae_encode] [equal] [dit_front] [ivae] [uvit3d] [gnfilm_frame] [uvit3d_train] [attnmap] [titok] [titok_enc] [mcraft] [sattn64] [facmat_narrow] [dcae] [attn_fc] [attn_fc_bwd] [dit1d] [seq64_bwd] [seq64_bwd_packed] [facdit_s128_train] [facmat_factor_wgrad] [facmat_s128_train]"""
 import ctypes as C
 import math
 import os
@@ -338,6 +338,41 @@ def facdit_s128_train(b, mlp, rounds=7):
             out[form].append(timeit(lambda: tr.training_step(xs, k, noise), iters=10, warm=2))
     capi.check(capi.lib.dfot_facdit_train_set_seq64_packed(tr._handle, 1))
     return out[1], out[0]
+
+
+def facmat_factor_wgrad(frames, ra, rb, hd, rounds=7):
+    """a left-factor gradient of the FacMatDiT matrix block at 64 patches per frame (dfot_op_facmat_factor_wgrad: the partial-tile launch
+    and the slice sum) on unit-normal operands a [frames][ra][hd], b [frames][rb][hd], next to a device copy of the bytes it reads (both
+    operands once; the ra x rb fp32 result is noise next to them), alternated over `rounds` rounds in one process:
+    ([ms op], [ms copy], bytes read)"""
+    a = torch.randn(frames, ra, hd, device="cuda").bfloat16()
+    b = torch.randn(frames, rb, hd, device="cuda").bfloat16()
+    out = torch.empty(ra, rb, device="cuda")
+    nbytes = (a.numel() + b.numel()) * 2
+    src = torch.randn(nbytes // 2, device="cuda").bfloat16()  # a copy that READS nbytes (and writes as many)
+    dst = torch.empty_like(src)
+    op, cp = [], []
+    for _ in range(rounds):
+        op.append(timeit(lambda: capi.check(capi.lib.dfot_op_facmat_factor_wgrad(P(a), P(b), P(out), frames, ra, rb, hd, S())), iters=100, warm=10))
+        cp.append(timeit(lambda: dst.copy_(src), iters=100, warm=10))
+    return op, cp, nbytes
+
+
+def facmat_s128_train(b, e, rounds=7):
+    """one training step (loss, backward, clip, AdamW) of FacMatDiT-S-`e`-1 with use_bias (embed_row_dim 384, depth 6, 12 spatial heads, 6 row
+    heads) at the taichi res-128 shape (4x16x16 latents, patch 2 = 64 patches per frame, 16 frames): [ms] over `rounds` rounds"""
+    bb = dict(name="dit3d", variant="factorized_matrix_attention", pos_emb_type="sinusoidal_2d", use_temporal_rope=True, patch_size=2,
+              embed_col_dim=e, embed_row_dim=384, num_heads=12, num_col_heads=1, num_row_heads=6, depth=6, mlp_ratio=4.0, spatial_mlp_ratio=4.0,
+              use_bias=True, matrix_block="matrix")
+    tr = dfot_amd.FacMatDiTTrainer(bb, x_shape=(4, 16, 16), max_tokens=16, allow_p64=True,
+                                   loss_weighting=dict(strategy="fused_min_snr", cum_snr_decay=0.96))
+    model = dfot_amd.DiT3D(bb, x_shape=(4, 16, 16), max_tokens=16)  # for its init_random only
+    model.init_random(0)
+    tr.load_state_dict({n: t.detach() for n, t in model.state_dict().items()})
+    del model
+    xs, noise = torch.randn(b, 16, 4, 16, 16, device="cuda"), torch.randn(b, 16, 4, 16, 16, device="cuda")
+    k = torch.randint(0, 1000, (b, 16))
+    return [timeit(lambda: tr.training_step(xs, k, noise), iters=10, warm=2) for _ in range(rounds)]
 
 
 def dit1d_forward(b, rounds=5):
@@ -1008,6 +1043,26 @@ def main():
             print(f"facdit_s128_train FacDiT-S{'-mlp' if mlp else ''} B=16 x 16 frames x 64 patches (hidden 384, depth 6): step with the packed "
                   f"spatial backward median {med(pk):.3f} ms (min {min(pk):.3f}, max {max(pk):.3f})  with the pair {med(pr):.3f} ms (min {min(pr):.3f}, "
                   f"max {max(pr):.3f})  packed / pair {med(pk) / med(pr):.3f}  ({len(pk)} alternated rounds)", flush=True)
+    factor_us = {}  # E -> us of the two left-factor gradients of one matrix block at the S shape (filled by facmat_factor_wgrad)
+    if "facmat_factor_wgrad" in what:
+        med = lambda r: sorted(r)[len(r) // 2]  # noqa: E731
+        # @FacMatDiT/group_S at res-128: 16 videos x 16 frames = 256 frames, embed_row_dim 384, 64 patches; dU' is (E, P), dU is (P, E)
+        for e in (64, 128):
+            for name, (ra, rb) in (("dU' (E, P)", (e, 64)), ("dU  (P, E)", (64, e))):
+                op, cp, nbytes = facmat_factor_wgrad(256, ra, rb, 384)
+                factor_us[e] = factor_us.get(e, 0.0) + med(op) * 1e3
+                print(f"facmat_factor_wgrad 256 frames hd=384 E={e} {name} {ra} x {rb}: launch + slice sum median {med(op)*1e3:7.1f} us (min "
+                      f"{min(op)*1e3:.1f}, max {max(op)*1e3:.1f})  copy reading the same {nbytes / 1e6:.1f} MB {med(cp)*1e3:7.1f} us (min "
+                      f"{min(cp)*1e3:.1f}, max {max(cp)*1e3:.1f})  op / copy {med(op) / med(cp):.2f}  {nbytes / med(op) / 1e9:.2f} TB/s read  "
+                      f"({len(op)} alternated rounds)", flush=True)
+    if "facmat_s128_train" in what:
+        med = lambda r: sorted(r)[len(r) // 2]  # noqa: E731
+        for e in (64, 128):
+            ms = facmat_s128_train(16, e)
+            share = f"  the two left-factor gradients x 6 blocks = {6 * factor_us[e] / 1e3:.3f} ms = {6 * factor_us[e] / 1e3 / med(ms):.1%} of the step" \
+                if e in factor_us else "  (run facmat_factor_wgrad in the same call for the factor gradients' share)"
+            print(f"facmat_s128_train FacMatDiT-S-{e}-1-bias B=16 x 16 frames x 64 patches (embed_row_dim 384, depth 6): step median {med(ms):.3f} ms "
+                  f"(min {min(ms):.3f}, max {max(ms):.3f}; {len(ms)} rounds){share}", flush=True)
     if "dit1d" in what:
         ms = dit1d_forward(16)
         for name, r in ms.items():
