@@ -837,12 +837,17 @@ static int launch_bwd_t(const bf16* q, const bf16* k, const bf16* v, const bf16*
   return DFOT_OK;
 }
 
+int attention_bwd_shape_check(int n, int d, long ldo) {
+  DFOT_REQUIRE(d > 0 && d <= 128 && d % 8 == 0 && ldo % 8 == 0, DFOT_ERR_SHAPE, "attention_bwd: head dim %d must be a multiple of 8, <= 128", d);
+  DFOT_REQUIRE(n > 0 && n % 128 == 0, DFOT_ERR_SHAPE, "attention_bwd: N=%d must be a multiple of 128", n);
+  return DFOT_OK;
+}
+
 // q/k/v/dq/dk/dv: [B][heads][N][dstride(d)] bf16 ; d_o: compact [B*N][ldo] ; l2/delta: [B][heads][N] fp32
 int launch_attention_bwd(const bf16* q, const bf16* k, const bf16* v, const bf16* d_o, long ldo, const float* l2, const float* delta,
                          bf16* dq, bf16* dk, bf16* dv, int batch, int heads, int n, int d, hipStream_t s) {
   DFOT_REQUIRE(q && k && v && d_o && l2 && delta && dq && dk && dv, DFOT_ERR_ARG, "attention_bwd: null pointer");
-  DFOT_REQUIRE(d > 0 && d <= 128 && d % 8 == 0 && ldo % 8 == 0, DFOT_ERR_SHAPE, "attention_bwd: head dim %d must be a multiple of 8, <= 128", d);
-  DFOT_REQUIRE(n > 0 && n % 128 == 0, DFOT_ERR_SHAPE, "attention_bwd: N=%d must be a multiple of 128", n);
+  if (int rc = attention_bwd_shape_check(n, d, ldo)) return rc;
   const float sq = 1.0f / sqrtf((float)d), sk = 0.6931471805599453f;
 #define BWD_ARGS q, k, v, d_o, ldo, l2, delta, dq, dk, dv, batch, heads, n, d, sq, sk, s
   if (d <= 32) return launch_bwd_t<64, 32, 32>(BWD_ARGS);

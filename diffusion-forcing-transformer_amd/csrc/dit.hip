@@ -1523,6 +1523,8 @@ int dfot_dit_read_attention_map(dfot_dit_t h, int slot, float* out, size_t capac
 int dfot_op_attention_bwd(const void* q, const void* k, const void* v, const void* d_o, void* o, int ldo, void* dq, void* dk, void* dv,
                           int batch, int heads, int n, int d, void* stream) {
   DFOT_REQUIRE(q && k && v && d_o && o && dq && dk && dv, DFOT_ERR_ARG, "attention_bwd: null argument");
+  // the backward's shape rules (narrower than the forward's) are checked before the forward: nothing runs on a refused call
+  if (int rc0 = attention_bwd_shape_check(n, d, ldo)) return rc0;
   hipStream_t s = (hipStream_t)stream;
   const size_t bhn = (size_t)batch * heads * n;
   float *lse = nullptr, *delta = nullptr;

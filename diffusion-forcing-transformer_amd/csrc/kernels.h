@@ -214,6 +214,9 @@ int launch_attention_bwd_delta(const bf16* o, const bf16* d_o, long ldo, float* 
 // q (pre-scaled as in the forward) / k / v / dq / dk / dv: [B][heads][N][dstride]; d_o compact; dq is the gradient of the UNSCALED q
 int launch_attention_bwd(const bf16* q, const bf16* k, const bf16* v, const bf16* d_o, long ldo, const float* l2, const float* delta,
                          bf16* dq, bf16* dk, bf16* dv, int batch, int heads, int n, int d, hipStream_t s);
+// launch_attention_bwd's shape rules, for an entry point that launches something else first (the forward, the delta kernel): checked up
+// front, a refused call launches nothing
+int attention_bwd_shape_check(int n, int d, long ldo);
 // the backward of launch_attention_frame_causal under launch_attention_bwd's contract (l2 = that forward's lse, delta from
 // launch_attention_bwd_delta, dq the gradient of the UNSCALED q, dk carrying ln 2): the frame-causal instantiations of the same kernels,
 // which stream only the tiles on and below the block diagonal.  The forward's shape rules

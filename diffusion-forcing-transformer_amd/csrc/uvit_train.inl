@@ -131,6 +131,10 @@ using namespace dfot;
 int dfot_op_conv3x3_bwd2(const void* x, const void* dy, const float* w, float* dx, void* dx_bf, float* dw, float* db, int bt, int hh, int ww, int cin,
                          int cout, void* stream) {
   DFOT_REQUIRE(x && dy && w && (dx != nullptr) != (dx_bf != nullptr) && dw && db, DFOT_ERR_ARG, "op_conv3x3_bwd2: null argument, or both / neither of dx and dx_bf");
+  // the shape rules of conv3_backward (channels) and of its data-gradient GEMM (whole 128-row tiles: 64 pixels pass conv3_backward's own
+  // rule, and launch_gemm refuses them only after db is zeroed), checked before anything runs: a refused call writes nothing
+  DFOT_REQUIRE(bt > 0 && hh > 0 && ww > 0 && cin > 0 && cout > 0 && cin % 64 == 0 && cout % 64 == 0 && ((long)bt * hh * ww) % 128 == 0, DFOT_ERR_SHAPE,
+               "op_conv3x3_bwd2: channels %d -> %d must be positive multiples of 64 and %ld pixels one of 128", cin, cout, (long)bt * hh * ww);
   hipStream_t s = (hipStream_t)stream;
   ConvBwdScratch sc;
   void *taps = nullptr, *ws = nullptr, *wd = nullptr, *zeros = nullptr;
@@ -381,6 +385,9 @@ using namespace dfot;
 int dfot_op_gn_silu_bwd(const float* x, const float* dy, const float* gamma, const float* beta, const void* film, float eps, float* dx, void* dfilm,
                         float* dgamma, float* dbeta, int bt, int pixels, int channels, void* stream) {
   DFOT_REQUIRE(x && dy && gamma && beta && dx && dgamma && dbeta, DFOT_ERR_ARG, "op_gn_silu_bwd: null argument");
+  // gn_silu_backward's rules, checked before anything is allocated, zeroed or launched: a refused call writes nothing
+  DFOT_REQUIRE((channels == 128 || channels == 256 || channels == 512 || channels == 1024) && (film == nullptr) == (dfilm == nullptr) && bt > 0 && pixels > 0,
+               DFOT_ERR_ARG, "op_gn_silu_bwd: channels %d must be 128, 256, 512 or 1024 (and film / dfilm both or neither)", channels);
   hipStream_t s = (hipStream_t)stream;
   float *stats = nullptr, *sums = nullptr;
   DFOT_CHECK_HIP(hipMalloc(&stats, (size_t)bt * 64 * sizeof(float)));
@@ -974,8 +981,11 @@ int dfot_op_attention_fwd_lse_bounded(const void* q, const void* k, const void* 
 int dfot_op_attention_bwd_lse(const void* q, const void* k, const void* v, const void* o, const void* d_o, int ldo, const float* lse, float* delta,
                               void* dq, void* dk, void* dv, int batch, int heads, int n, int d, void* stream) {
   DFOT_REQUIRE(q && k && v && o && d_o && lse && delta && dq && dk && dv, DFOT_ERR_ARG, "op_attention_bwd_lse: null argument");
+  // the backward's shape rules are checked before the delta launch: nothing runs on a refused call
+  int rc = attention_bwd_shape_check(n, d, ldo);
+  if (rc) return rc;
   hipStream_t s = (hipStream_t)stream;
-  int rc = launch_attention_bwd_delta((const bf16*)o, (const bf16*)d_o, ldo, delta, batch, heads, n, d, s);
+  rc = launch_attention_bwd_delta((const bf16*)o, (const bf16*)d_o, ldo, delta, batch, heads, n, d, s);
   if (rc) return rc;
   return launch_attention_bwd((const bf16*)q, (const bf16*)k, (const bf16*)v, (const bf16*)d_o, ldo, lse, delta, (bf16*)dq, (bf16*)dk, (bf16*)dv, batch,
                               heads, n, d, s);
@@ -1200,7 +1210,9 @@ int dfot_op_gn_silu_fwd2(const float* x, const float* gamma, const float* beta, 
   DFOT_REQUIRE(x && gamma && beta && out && stats && channels % 32 == 0 && (!film || (film_ld >= 2 * channels && film_ld % 4 == 0)), DFOT_ERR_ARG,
                "op_gn_silu_fwd: bad argument");
   hipStream_t s = (hipStream_t)stream;
-  DFOT_REQUIRE(channels % 128 == 0, DFOT_ERR_SHAPE, "op_gn_silu_fwd: channels %d must be a multiple of 128", channels);
+  // the statistics kernels' set (launch_gn_partial_f32), which is also the backward's: another multiple of 128 (384, 640) is refused here
+  DFOT_REQUIRE(channels == 128 || channels == 256 || channels == 512 || channels == 1024, DFOT_ERR_SHAPE,
+               "op_gn_silu_fwd: channels %d must be 128, 256, 512 or 1024", channels);
   // statistics: streaming partial sums over 64-pixel blocks of all channels + a deterministic finalize (the inference kernels); one
   // workgroup per (image, group) read 16-byte slivers of every 512-byte pixel row
   void* part = nullptr;

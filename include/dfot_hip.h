@@ -678,10 +678,12 @@ int dfot_op_attention_bwd(const void* q, const void* k, const void* v, const voi
                           int batch, int heads, int n, int d, void* stream);
 /* training path of the UViT3DPose ResBlocks / resamplers, test entry: gradients of y = conv3x3(x, w, padding 1) + b for the upstream
  * gradient dy: x [BT,H,W,Cin] and dy [BT,H,W,Cout] bf16 channels-last, w fp32 [Cout][Cin][3][3]; dx fp32 [BT,H,W,Cin], dw fp32 like w,
- * db fp32 [Cout].  Channel counts multiples of 64.  Replaces autograd through F.conv2d (u_vit_blocks.py:16-93). */
+ * db fp32 [Cout].  Channel counts multiples of 64, BT*H*W a multiple of 128 (the data-gradient GEMM takes whole 128-row tiles); anything
+ * else returns DFOT_ERR_SHAPE before a byte is written.  Replaces autograd through F.conv2d (u_vit_blocks.py:16-93). */
 int dfot_op_conv3x3_bwd(const void* x, const void* dy, const float* w, float* dx, float* dw, float* db, int bt, int h, int w_, int cin, int cout,
                         void* stream);
-/* the same with the data gradient in fp32 (dx) OR in bf16 (dx_bf; exactly one of the two): a gradient that only feeds the backward of the
+/* the same (shape rules included: channels % 64 == 0, BT*H*W % 128 == 0, DFOT_ERR_SHAPE before a byte is written) with the data gradient in
+ * fp32 (dx) OR in bf16 (dx_bf; exactly one of the two, anything else DFOT_ERR_ARG): a gradient that only feeds the backward of the
  * GroupNorm in front of the convolution is written once, at half the bytes -- what torch.autocast(bf16) leaves there in the reference
  * (F.conv2d runs in bf16 under the trainer's precision setting, configurations/experiment/base_pytorch_exp.yaml:12 `precision: bf16`). */
 int dfot_op_conv3x3_bwd2(const void* x, const void* dy, const float* w, float* dx, void* dx_bf, float* dw, float* db, int bt, int h, int w_, int cin,
